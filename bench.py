@@ -18,6 +18,11 @@ forward on one GPU, C3, C4) are parity-test cases (tests/), and C2 stays in the 
 (`roofline.c2`).  `USP_BENCH_WORKLOAD=configs` restores the per-N BASELINE configs of rounds 1-4 for A/B runs.
 Rank 0 prints ONE JSON line.  value = whole-job algorithmic TFLOP/s: fwd 4*B*Hq*S^2*D/2 (causal),
 bwd 2.5x fwd, no credit for masked tiles, recompute or merges; ms_per_step = the iteration time.
+
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.  --full adds every diagnostic
+(the in-bench parity check, N = 1: the kernel roofline with the MFMA-only ceiling, the reference ops on this GPU and the
+CPU baseline; N > 1: the overlap probe).  --dump-outputs DIR writes a seeded row sample of what the last timed step
+returned (out, and dq / dk / dv for fwd+bwd) as DIR/<name>.npy in float32, so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -759,6 +764,24 @@ def overlap_probe(step, steps, ws, dev, t_iter):
                     "local copy of the same size"}
 
 
+DUMP_ROWS = 512      # sequence rows sampled over all ranks: 19 MB of float32 at the metric's shape (the whole output is 2.3 GB)
+
+
+def dump_outputs(path, arrays, rank, ws, seed=0):
+    """--dump-outputs: the same seeded sequence rows (every head, all of D) of each array the step returned -- out, dq, dk, dv,
+    all (B, S_local, H, D) -- as float32 `path/<name>.npy`; rank r of N > 1 writes `<name>_rank<r>.npy`.  Returns what it wrote."""
+    os.makedirs(path, exist_ok=True)
+    n = arrays["out"].shape[1]
+    rows = np.sort(np.random.RandomState(seed).choice(n, size=min(n, DUMP_ROWS // ws), replace=False))
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().index_select(1, torch.from_numpy(rows).to(t.device)).float().cpu().numpy()
+        fname = name if ws == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(path, fname + ".npy"), a)
+        written[fname] = list(a.shape)
+    return {"dir": path, "arrays": written, "sample": f"{len(rows)} of {n} sequence rows of each rank, RandomState({seed})"}
+
+
 class _LineOnce:
     """Prints rank 0's JSON line exactly once, from whichever thread gets there first (None on other ranks)."""
 
@@ -805,9 +828,14 @@ def main(argv=None, dev=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-overlap", action="store_true", help="skip the compute-only / comm-only runs (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the diagnostics: in-bench parity, roofline + MFMA ceiling + reference ops + CPU baseline "
+                         "(N = 1), overlap probe (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a seeded row sample of the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the in-bench parity check")
+    ap.add_argument("--no-overlap", action="store_true", help="with --full: skip the compute-only / comm-only runs (N > 1)")
     ap.add_argument("--bwd", type=int, default=-1, help="override: 1 = fwd+bwd, 0 = fwd only")
     ap.add_argument("--async-ulysses", action="store_true",
                     help="use AsyncLongContextAttention (head-group pipelined all-to-all) instead of LongContextAttention")
@@ -876,16 +904,23 @@ def main(argv=None, dev=None):
     else:
         attn = Y.LongContextAttention(ring_impl_type=cfg["impl"], attn_type=Y.AttnType.HIP)
 
+    last = {}                             # --dump-outputs: what the latest step returned (references only, no copies)
+    keep = args.dump_outputs is not None
+
     def step():
         out = attn(lq, lk, lv, causal=True)
+        if keep:
+            last["out"] = out.detach()
         if cfg["bwd"]:
             out.backward(ldo)
+            if keep:
+                last.update(dq=lq.grad, dk=lk.grad, dv=lv.grad)
             lq.grad = lk.grad = lv.grad = None
         return out
 
     parity_op = parity_rows = None
     out = step()
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         try:
             parity_op, parity_rows = parity_check(cfg, rank, ws, out.detach(), q, k, v)
         except Exception as e:                      # never let the optional check kill the measurement
@@ -903,16 +938,19 @@ def main(argv=None, dev=None):
     # the kernel timings (N = 1, ~1 s), ~0.3 s of the step itself, the W warm-up steps, the K timed steps.  Round 2 had
     # the lookup and the freeze BEHIND the kernel timings: the part sat idle for seconds, clocked down, and the driver's
     # 20 steps read 22 % slower than the kernel they consist of (BENCH_r02.json: 0.5813 vs 0.4768 ms).
-    traffic = pmc_traffic() if (ws == 1 and rank == 0) else None
+    # A plain run (no --full) has neither the lookup nor the kernel timings: collector freeze, then W warm-up + K timed steps
+    # (same-box A/B of round 6, profiles/r06_bench_order_ab.txt: the kernel timings in front do not change the headline).
+    diagnostics = args.full and ws == 1 and rank == 0
+    traffic = pmc_traffic() if diagnostics else None
     gc.collect()
     gc.freeze()          # the documented pattern: the collector keeps running, over new objects only
 
-    # USP_BENCH_ORDER (N = 1): "kernels_first" = rounds 3-5, the kernel timings of the `roofline` block in front of the timed steps;
-    # "headline_first" = the W warm-up + K timed steps FIRST, the diagnostics (which include the MFMA-only ceiling probe: the
-    # hottest loop the part can run, and the slower kernel family's steps) behind them.
+    # USP_BENCH_ORDER (N = 1, --full): "kernels_first" = rounds 3-5, the kernel timings of the `roofline` block in front of the
+    # timed steps; "headline_first" = the W warm-up + K timed steps FIRST, the diagnostics (which include the MFMA-only ceiling
+    # probe: the hottest loop the part can run, and the slower kernel family's steps) behind them.
     order = os.environ.get("USP_BENCH_ORDER", BENCH_ORDER_DEFAULT)
     roofline = None
-    if ws == 1 and rank == 0 and order != "headline_first":
+    if diagnostics and order != "headline_first":
         roofline = kernel_roofline(cfg, dev, traffic)
     flops = fwd_flops(cfg["B"], cfg["Hq"], cfg["S"], cfg["D"]) * (3.5 if cfg["bwd"] else 1.0)
 
@@ -951,14 +989,16 @@ def main(argv=None, dev=None):
                        "tokens_per_gpu": cfg["S"] * cfg["B"] // ws,
                        "assumed": "B=1 and causal=True where BASELINE.json's config string is silent",
                        "iter_ms": round(ms, 4),
+                       "full": args.full,
                        "host": "host-only work (gc.collect + gc.freeze, PMC lookup) first, then device work only: kernel "
-                               "timings (N = 1), W warm-up steps, K timed steps"},
+                               "timings (N = 1), W warm-up steps, K timed steps" if diagnostics else
+                               "host-only work (gc.collect + gc.freeze) first, then device work only: W warm-up steps, K timed steps"},
             "ms_per_step_device_events": dms,
             "ms_per_step_rank_min_max": dict(rank_spread),
             "frac_of_mfma_roofline": round(value / (ws * PEAK_BF16_TFLOPS), 4),
-            "parity_max_abs_err_vs_reference_op": parity_op,
-            "parity_max_abs_err_vs_fp64_rows": parity_rows,
         }
+        if args.full:
+            line.update(parity_max_abs_err_vs_reference_op=parity_op, parity_max_abs_err_vs_fp64_rows=parity_rows)
         if smoke:
             line["smoke"] = f"backend={backend}, all ranks on {dev} -- NOT a measurement"
         return line
@@ -1038,12 +1078,16 @@ def main(argv=None, dev=None):
     # -- with the row-chunked tails beside a zigzag ring -- so the staged modes are: safe -> default -> + relayed pair exchange;
     # USP_SELF_CHUNK=0 / USP_TAILS=0 in the environment restore round 5's schedule for an A/B run.)
     value = flops / (ms * 1e-3) / 1e12
+    if keep:                                # before the overlap probe: it re-runs the step with patched transports
+        dumped = dump_outputs(args.dump_outputs, last, rank, ws)
+        if line is not None:
+            line["outputs"] = dumped
 
-    # The measurement is complete here.  What follows is informative and must never cost the line: the overlap probe
+    # The measurement is complete here.  What follows (--full) is informative and must never cost the line: the overlap probe
     # re-runs the step with patched transports on every rank, so it runs under a deadline -- if it has not returned
     # by then (a rank stuck in a collective), rank 0 prints the line without it and every rank leaves.
     emit = _LineOnce(line)
-    if ws > 1 and not args.no_overlap:
+    if args.full and ws > 1 and not args.no_overlap:
         with _Deadline(float(os.environ.get("USP_BENCH_PROBE_DEADLINE_S", "120")), emit,
                        {"overlap": {"value": None, "error": "overlap probe did not finish before its deadline"}}):
             try:
@@ -1054,7 +1098,7 @@ def main(argv=None, dev=None):
         if rank == 0:
             line["overlap"] = overlap
 
-    if rank == 0 and ws == 1:
+    if diagnostics:
         if roofline is None:
             roofline = kernel_roofline(cfg, dev, traffic)
         line["roofline"] = roofline

@@ -153,7 +153,7 @@ def _main_worker(rank, ws):
     b.cpu_baseline = lambda cfg: {"stub": True}
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
-        b.main(["--gpus", str(ws), "--steps", "2", "--warmup", "1"], dev=torch.device("cpu"))
+        b.main(["--gpus", str(ws), "--steps", "2", "--warmup", "1", "--full"], dev=torch.device("cpu"))
     lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
     if rank != 0:
         return lines == []
@@ -199,9 +199,73 @@ def _main_worker(rank, ws):
 @pytest.mark.parametrize("ws", [1, 2, 4, 8])
 def test_bench_main_prints_one_contract_line(ws):
     """The driver's contract on every GPU count it launches (N = 1, 2, 4, 8 -> ulysses x ring grids 1x1, 2x1, 1x4,
-    2x4 with GQA and a backward): rank 0 prints exactly ONE JSON line carrying the contract keys, the in-bench
-    parity of every rank's shard and -- for N > 1 -- the overlap probe; other ranks print nothing."""
+    2x4 with GQA and a backward): rank 0 prints exactly ONE JSON line carrying the contract keys, and with --full the
+    in-bench parity of every rank's shard and -- for N > 1 -- the overlap probe; other ranks print nothing."""
     assert all(run_distributed(_main_worker, ws))
+
+
+def _plain_worker(rank, ws, out_dir):
+    """bench.main() WITHOUT --full, with --dump-outputs: every diagnostic is made to fail if it is called."""
+    import contextlib
+    import io
+    import json
+    import yunchang_amd.hybrid.async_attn_layer as AL
+    from yunchang_amd.kernels import set_block_backend
+    from oracle_backend import OracleBlockBackend
+    b = _bench()
+    set_block_backend(OracleBlockBackend())
+    AL._FILL_ITEMS = 1
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(ws), LOCAL_RANK=str(rank), USP_BENCH_BACKEND="gloo")
+    for n, w in b.WORKLOADS.items():
+        w.update(B=1, S=64 * n, Hq=4, Hkv=4 if n < 8 else 2, D=32)
+
+    def refuse(*a, **k):
+        raise AssertionError("a plain run called a --full diagnostic")
+    for name in ("parity_check", "pmc_traffic", "kernel_roofline", "reference_kernel", "reference_fwdbwd", "cpu_baseline",
+                 "overlap_probe"):
+        setattr(b, name, refuse)
+    timed_steps, real_timed = [], b.timed
+    b.timed = lambda step, steps, *a, **k: (timed_steps.append(steps), real_timed(step, steps, *a, **k))[1]
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        b.main(["--gpus", str(ws), "--steps", "3", "--warmup", "1", "--dump-outputs", out_dir], dev=torch.device("cpu"))
+    assert timed_steps and set(timed_steps) == {3}, timed_steps       # --steps IS the number of timed steps
+    lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
+    if rank != 0:
+        return lines == []
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(line)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["config"]["full"] is False
+    assert not {"roofline", "cpu_baseline", "reference_kernel_on_this_gpu", "reference_fwdbwd_on_this_gpu", "overlap",
+                "parity_max_abs_err_vs_fp64_rows"} & set(line), line.keys()
+    sfx = "" if ws == 1 else "_rank0"
+    assert set(line["outputs"]["arrays"]) == {n + sfx for n in ("out", "dq", "dk", "dv")}
+    return line["outputs"]
+
+
+@pytest.mark.parametrize("ws", [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(ws, tmp_path):
+    """Without --full the benchmark runs no diagnostic and times exactly --steps steps; --dump-outputs writes a seeded row
+    sample of what the last timed step returned, float32, equal to exact attention and its gradients on those rows."""
+    outputs = run_distributed(_plain_worker, ws, str(tmp_path))[0]
+    files = sorted(os.listdir(tmp_path))
+    sfx = [""] if ws == 1 else [f"_rank{r}" for r in range(ws)]
+    assert files == sorted(f"{n}{s}.npy" for n in ("dk", "dq", "dv", "out") for s in sfx)
+    arrays = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype == np.float32 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    if ws > 1:
+        return
+    b = _bench()
+    cfg = dict(b.WORKLOADS[1]); cfg.update(B=1, S=64, Hq=4, Hkv=4, D=32)
+    q, k, v, do = (t.float().numpy().astype(np.float64) for t in b.make_global(cfg, torch.device("cpu")))
+    ro, rl = O.attention_ref(q, k, v, causal=True)
+    rdq, rdk, rdv = O.block_bwd(do, q, k, v, ro, rl, None, True)
+    rows = np.sort(np.random.RandomState(0).choice(64, size=min(64, b.DUMP_ROWS), replace=False))
+    assert outputs["arrays"]["out"] == [1, len(rows), 4, 32]
+    for name, want in (("out", ro), ("dq", rdq), ("dk", rdk), ("dv", rdv)):
+        assert np.abs(arrays[name] - want[:, rows]).max() < 5e-2, name
 
 
 def test_profile_is_quoted_only_for_the_kernel_it_was_taken_from(monkeypatch):

@@ -5,8 +5,8 @@
 #   1 link      RCCL send/recv around the ranks + the pair all_to_all_single (tools/r06/first_contact.py --stage link)
 #   2 parity    the real layer on the real grid, small size, forward + backward vs exact fp64 attention: safe mode, then the
 #               library default (pipelined exchange beside the ring, self-chunk start, row-chunked tails), then + relayed exchange
-#   3 bench     bench.py --gpus N with USP_SAFE_COMM=1 (ONE communicator in flight at a time), no overlap probe
-#   4 bench     bench.py --gpus N as the driver runs it: safe -> default -> + relay under its own deadlines, overlap probe
+#   3 bench     bench.py --gpus N --full with USP_SAFE_COMM=1 (ONE communicator in flight at a time), no overlap probe
+#   4 bench     bench.py --gpus N --full: safe -> default -> + relay under its own deadlines, overlap probe
 # A stage that times out or fails is recorded and the script goes on to the next; the exit code is 0 unless stage 1 failed.
 N=${1:-8}
 OUT=${2:-gpurun_out/first_contact}
@@ -30,9 +30,9 @@ for mode in safe default relay; do
   [ "$mode" = relay ] && [ "$N" != 8 ] && continue
   stage 2_parity_$mode 600 $RUN --master-port $((port + 1)) tools/r06/first_contact.py --stage parity --mode $mode --out "$OUT/2_parity_$mode.json"
 done
-USP_SAFE_COMM=1 stage 3_bench_safe 900 $RUN --master-port $((port + 1)) bench.py --gpus $N --steps 10 --warmup 3 --no-overlap
+USP_SAFE_COMM=1 stage 3_bench_safe 900 $RUN --master-port $((port + 1)) bench.py --gpus $N --steps 10 --warmup 3 --full --no-overlap
 grep -E '^\{' "$OUT/3_bench_safe.log" | tail -1 > "$OUT/3_bench_safe.json"
-stage 4_bench_staged 1800 $RUN --master-port $((port + 1)) bench.py --gpus $N --steps 20 --warmup 5
+stage 4_bench_staged 1800 $RUN --master-port $((port + 1)) bench.py --gpus $N --steps 20 --warmup 5 --full
 grep -E '^\{' "$OUT/4_bench_staged.log" | tail -1 > "$OUT/4_bench_staged.json"
 python - "$OUT" "$N" <<'PY'
 import glob, json, os, sys
