@@ -69,6 +69,14 @@ enum {
  * launch's outputs are not touched.  Both bits at once: USP_EINVAL. */
 #define USP_BWD_SKIP_DQ 16
 #define USP_BWD_SKIP_DKDV 32
+/* USP_ATTN_SOFTCAP: tanh logit soft-capping as flash-attn defines it (`softcap`, passed through by the reference's block
+ * calls, e.g. yunchang/ring/zigzag_ring_flash_attn.py:29-43): the `softcap` field is valid and every score S (softmax_scale
+ * already applied) is replaced by cap * tanh(S / cap) before the causal / window / ragged mask.  Without the bit the field
+ * is ignored (a binding built before it never sets the bit, so the library never reads past that binding's struct).
+ * With the bit, a softcap that is not a finite number > 0 is USP_EINVAL; with USP_FORCE_ROW64 it is USP_EUNSUPPORTED (the
+ * 64-row family declines it; unforced, such calls run on the two-waves-per-SIMD kernels).  usp_attn_features() tells a
+ * binding whether the library it loaded serves the bit. */
+#define USP_ATTN_SOFTCAP 64
 
 typedef struct usp_tensor {
   void* ptr;
@@ -86,6 +94,7 @@ typedef struct usp_tensor {
  *
  * Computes, for q (B,Sq,Hq,D), k/v (B,Sk,Hkv,D) [GQA: q head i uses kv head i / (Hq/Hkv)]:
  *     S = q k^T * softmax_scale ; causal: key j visible to query i iff j <= i + (Sk - Sq)
+ *     USP_ATTN_SOFTCAP: S <- softcap * tanh(S / softcap)          (before the mask)
  *     blk_lse = logsumexp_j S ;  blk_out = softmax(S) v          (fp32 accumulate)
  * then, per query row i of this call:
  *     merge_in != 0 : (o, lse) = merge((acc[i], lse[i]), (blk_out, blk_lse))   [utils.py:25-26]
@@ -139,6 +148,7 @@ typedef struct usp_fwd_args {
                                     `window_size` through): query row i sees key j iff
                                     i + (Sk - Sq) - window_left <= j <= i + (Sk - Sq) + window_right; a negative value =
                                     unbounded on that side; `causal` caps window_right at 0 */
+  float softcap;                 /* read only with USP_ATTN_SOFTCAP in `flags`: finite, > 0 (see the flag) */
 } usp_fwd_args;
 
 int usp_flash_fwd(const usp_fwd_args* args, void* stream);
@@ -164,6 +174,8 @@ int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* args, int32_t k_splits
  * (not this block's); delta (B,Hq,Sq) = rowsum(dout * out_global) from usp_bwd_delta().
  *     P = exp(S - lse) ; dV = P^T dO ; dP = dO V^T ; dS = P * (dP - delta) * scale
  *     dQ = dS K ; dK = dS^T Q                  (GQA: dK,dV summed over the Hq/Hkv query heads)
+ * USP_ATTN_SOFTCAP: with t = tanh(S / softcap), S = q k^T * softmax_scale:
+ *     P = exp(softcap * t - lse) ; dS = P * (dP - delta) * (1 - t^2) * scale   (the rest as above)
  * Outputs are fp32 (B,S,H,D) tensors: dq (+)= dQ, dk (+)= dK, dv (+)= dV, where "+=" is used when
  * the matching accum_* flag is non-zero and "=" otherwise.  Deterministic (no atomics).
  * `workspace` (optional) enables the GQA head split described at usp_flash_bwd_workspace_bytes().
@@ -207,6 +219,7 @@ typedef struct usp_bwd_args {
                                     into its accumulators -- a divisor of Hq/Hkv (else USP_EINVAL).  Hq/Hkv = the whole group
                                     inside the workgroup (no per-head partials, no reduce launch); 1 = one item per query
                                     head; 0 = the library decides (see usp_flash_bwd_workspace_bytes()) */
+  float softcap;                 /* as usp_fwd_args; read only with USP_ATTN_SOFTCAP in `flags` */
 } usp_bwd_args;
 
 int usp_flash_bwd(const usp_bwd_args* args, void* stream);
@@ -296,6 +309,9 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
                    float* sink, uint64_t* clocks, void* stream);
 
 int usp_abi_version(void);
+/* The USP_ATTN_* flag bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP).  Unknown flag bits are not rejected by
+ * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
+int usp_attn_features(void);
 const char* usp_strerror(int code);
 
 #ifdef __cplusplus

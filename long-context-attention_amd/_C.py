@@ -7,6 +7,7 @@ device memory and streams only; every kernel runs on ``torch.cuda.current_stream
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 from typing import Optional
@@ -24,6 +25,7 @@ USP_FORCE_ROW64 = 4            # ABI v6: the call must be served by the one-wave
 USP_FORCE_WAVE32 = 8           # ... or by the two-waves-per-SIMD (32 rows per wave) family
 USP_BWD_SKIP_DQ = 16           # usp_flash_bwd: only the dK/dV launch ...
 USP_BWD_SKIP_DKDV = 32         # ... only the dQ launch
+USP_ATTN_SOFTCAP = 64          # the softcap field is valid: scores are capped to softcap * tanh(S / softcap)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -77,7 +79,8 @@ class UspFwdArgs(ctypes.Structure):
                 ("final_end", ctypes.c_int32),
                 ("seq_q", ctypes.c_void_p), ("seq_k", ctypes.c_void_p), ("sched", ctypes.c_void_p),
                 ("flags", ctypes.c_int32), ("k_splits", ctypes.c_int32), ("workspace", ctypes.c_void_p),
-                ("window_left", ctypes.c_int32), ("window_right", ctypes.c_int32)]
+                ("window_left", ctypes.c_int32), ("window_right", ctypes.c_int32),
+                ("softcap", ctypes.c_float)]
 
 
 class UspBwdArgs(ctypes.Structure):
@@ -98,11 +101,12 @@ class UspBwdArgs(ctypes.Structure):
                 ("sched", ctypes.c_void_p), ("flags", ctypes.c_int32),
                 ("dq_splits", ctypes.c_int32), ("dkdv_splits", ctypes.c_int32),
                 ("window_left", ctypes.c_int32), ("window_right", ctypes.c_int32),
-                ("dkdv_heads", ctypes.c_int32)]
+                ("dkdv_heads", ctypes.c_int32), ("softcap", ctypes.c_float)]
 
 
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
-           "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe")
+           "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
+           "usp_attn_features")
 
 
 def lib_path() -> str:
@@ -127,6 +131,8 @@ def load():
     L.usp_abi_version.restype = ctypes.c_int
     L.usp_last_launch_kinds.restype = ctypes.c_int
     L.usp_last_launch_kinds.argtypes = []
+    L.usp_attn_features.restype = ctypes.c_int
+    L.usp_attn_features.argtypes = []
     if L.usp_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libusp_hip.so ABI {L.usp_abi_version()} != binding ABI {ABI_VERSION}")
     i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -294,14 +300,40 @@ def _window(window):
     return None if (wl < 0 and wr < 0) else (wl, wr)
 
 
+def softcap_value(softcap) -> Optional[float]:
+    """flash-attn's `softcap` -> the cap as a float, or None when it is off (None / 0).  flash-attn silently ignores a
+    negative value; this package fails loudly instead: a negative, NaN or infinite cap raises ValueError.  (Pure
+    argument check: the CPU orchestration tests call it without a library.)"""
+    if softcap is None:
+        return None
+    cap = float(softcap)
+    if cap == 0.0:
+        return None
+    if not (math.isfinite(cap) and cap > 0.0):
+        raise ValueError(f"softcap must be a finite number > 0 (0 / None = off), got {softcap!r}")
+    return cap
+
+
+def _set_softcap(a, cap: Optional[float]):
+    """Set USP_ATTN_SOFTCAP + the field on an argument block; a library that does not report the bit
+    (usp_attn_features) would ignore it silently, so it is refused here."""
+    if cap is None:
+        return
+    L = load()
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_SOFTCAP):
+        raise NotImplementedError(f"{_LIB_PATH} does not serve softcap (USP_ATTN_SOFTCAP): rebuild it")
+    a.flags |= USP_ATTN_SOFTCAP
+    a.softcap = cap
+
+
 def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end, interleave, n, window=None,
-              family_flag=0):
+              family_flag=0, softcap=None):
     """The filled usp_fwd_args block of a dense launch.  Everything but the seven pointers is a function of
     (dtype, shapes, strides, flags), and a training loop issues the same few launches over and over: the block is
     cached per thread under that signature and only the pointers are patched (filling 27 ctypes fields and five
     usp_tensor structs costs ~35 us of host time per launch, tools/host_step_cpu.py; a hit costs ~8)."""
     key = (q.dtype, q.shape, q.stride(), k.shape, k.stride(), v.stride(), lse.stride(), _strides(out), _strides(acc),
-           softmax_scale, causal, merge_in, final_begin, final_end, interleave, n, window, family_flag)
+           softmax_scale, causal, merge_in, final_begin, final_end, interleave, n, window, family_flag, softcap)
     cache = _TLS.__dict__.setdefault("fwd", {})
     a = cache.get(key)
     if a is None:
@@ -320,6 +352,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
         if window is not None:
             a.flags |= USP_ATTN_WINDOW
             a.window_left, a.window_right = window
+        _set_softcap(a, softcap)
         a.k_splits = n if n > 1 else 0
         if len(cache) >= _ARGS_CACHE_MAX:
             cache.clear()
@@ -333,18 +366,20 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
-              interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None):
+              interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
     window_size (left, right), None / (-1, -1) = none.  `family`: "row64" | "wave32" pins the kernel family of this call
-    (ABI v6; None: set_kernel_family's default, normally "auto"); both families serve a K split."""
+    (ABI v6; None: set_kernel_family's default, normally "auto"); both families serve a K split.  `softcap`: flash-attn's
+    logit soft-capping, None / 0 = off (softcap_value; the 64-row family declines it: family="row64" then fails)."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
+    cap = softcap_value(softcap)
     ff = _family_flag(family)
     n = fwd_k_splits(B, Sq, Hq, causal) if k_splits is None else int(k_splits)
     a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
-                  bool(interleave), n, _window(window), ff)
+                  bool(interleave), n, _window(window), ff, cap)
     L = load()
     if n > 1:
         # scratch for the partial results: one buffer per (device, stream), grown on demand; launches on one stream
@@ -400,11 +435,12 @@ def sched_block(device) -> torch.Tensor:
 
 def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scale: float,
                      causal: bool, lse, out=None, acc=None, merge_in: bool = False,
-                     final_begin: int = 0, final_end: int = 2, interleave: bool = False):
+                     final_begin: int = 0, final_end: int = 2, interleave: bool = False, softcap=None):
     """usp_flash_fwd in packed variable-length mode.  q/out/acc (T,Hq,D), k/v (T',Hkv,D), lse (Hq,T)
     fp32; seq_q/seq_k (num_seq,2) int32 device tables of (first_row, rows); final_begin/final_end
-    count half sequences (0,1,2)."""
+    count half sequences (0,1,2); `softcap` as flash_fwd."""
     _require_cuda(q, k, v, lse, out, acc)
+    cap = softcap_value(softcap)
     n = seq_q.shape[0]
     a = UspFwdArgs()
     a.dtype = dtype_code(q.dtype)
@@ -418,14 +454,17 @@ def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scal
     a.seq_q, a.seq_k = _seq(seq_q, n), _seq(seq_k, n)
     a.sched = sched_block(q.device).data_ptr()
     a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
+    _set_softcap(a, cap)
     _check(load().usp_flash_fwd(ctypes.byref(a), _stream()), "usp_flash_fwd")
 
 
 def flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q: int, max_k: int, dq, dk, dv,
                      softmax_scale: float, causal: bool, accum_dq=False, accum_dk=False,
-                     accum_dv=False, dq16=None, dk16=None, dv16=None, interleave: bool = False):
-    """usp_flash_bwd in packed variable-length mode (layouts as flash_fwd_packed; lse/delta (Hq,T))."""
+                     accum_dv=False, dq16=None, dk16=None, dv16=None, interleave: bool = False, softcap=None):
+    """usp_flash_bwd in packed variable-length mode (layouts as flash_fwd_packed; lse/delta (Hq,T); `softcap` as
+    flash_fwd)."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
+    cap = softcap_value(softcap)
     n = seq_q.shape[0]
     a = UspBwdArgs()
     a.dtype = dtype_code(q.dtype)
@@ -444,6 +483,7 @@ def flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q: int, max_k:
     a.seq_q, a.seq_k = _seq(seq_q, n), _seq(seq_k, n)
     a.sched = sched_block(q.device).data_ptr()
     a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
+    _set_softcap(a, cap)
     a.total_k = k.shape[0]
     L = load()
     need = L.usp_flash_bwd_workspace_bytes(ctypes.byref(a))
@@ -465,14 +505,16 @@ def bwd_delta(dout, out, delta):
 
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
-              interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0):
+              interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
+              softcap=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
     flash-attn's window_size (left, right), None / (-1, -1) = none.  `family`: as flash_fwd.  `only`: "dkdv" | "dq" issues
     just that launch of the two (ABI v6: USP_BWD_SKIP_DQ / USP_BWD_SKIP_DKDV).  `dkdv_heads` (ABI v7): query heads of a KV
-    group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides)."""
+    group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`: as flash_fwd."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
+    cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     a = UspBwdArgs()
@@ -497,6 +539,7 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     if win is not None:
         a.flags |= USP_ATTN_WINDOW
         a.window_left, a.window_right = win
+    _set_softcap(a, cap)
     L = load()
     need = L.usp_flash_bwd_workspace_bytes(ctypes.byref(a))     # GQA head split and / or cuts of few-item launches
     ws = None

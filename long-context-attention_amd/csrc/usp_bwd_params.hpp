@@ -47,6 +47,15 @@ struct BwdParams {
                                       // is accumulated into them: whole-row-piece stores (usp_mfma64.hpp: store_row16_wide)
 };
 
+// Logit soft-capping (USP_ATTN_SOFTCAP): kernel arguments of the softcap instantiations only (usp_flash_bwd.hip:
+// flash_bwd_softcap_kernel, flash_bwd_dkdv_softcap_kernel); the other kernels keep BwdParams and their machine code.
+struct BwdSoftcap {
+  int cap_on;                           // host: the call caps its scores (selects the softcap kernels, declines the 64-row ones)
+  float cap_log2;                       // cap * log2(e)
+  float tanh_k2;                        // 2 * scale * log2(e) / cap (usp_common.hpp: softcap_tanh)
+};
+struct BwdArgsSC : BwdParams, BwdSoftcap {};
+
 // rows of a 16-bit output tensor start on 16-byte boundaries (base pointer and every stride)
 inline bool rows16_aligned(const char* ptr, int64_t sb, int64_t ss, int64_t sh) {
   return ptr && (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && sb % 8 == 0 && ss % 8 == 0 && sh % 8 == 0;

@@ -144,6 +144,14 @@ USP_DEV void pin_here(uint32_t& w) { asm volatile("" : "+v"(w)); }
 
 USP_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// Logit soft-capping (USP_ATTN_SOFTCAP): tanh(x * scale / cap) of a RAW score x, as 1 - 2 / (2^(x * k2) + 1) with
+// k2 = 2 * scale * log2(e) / cap folded by the host -- one v_exp, one v_rcp, no libm call.  Large |x| saturates
+// exactly (2^.. = +inf -> rcp = 0 -> 1; 2^.. = 0 -> -1; x = -inf -> -1); near 0 the subtraction cancels to an absolute
+// error of ~1e-7 (times cap in the capped score), well inside the 16-bit tolerances.
+USP_DEV float softcap_tanh(float x, float k2) {
+  return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(fast_exp2(x * k2) + 1.f), 1.f);
+}
+
 // Host side: record which kernels a flash call launches (usp_last_launch_kinds; defined in usp_elementwise.hip)
 void launch_kinds_reset();
 void launch_kinds_note(int kind);

@@ -1,0 +1,385 @@
+// Body of flash_bwd_dkdv_kernel / flash_bwd_dkdv_softcap_kernel (usp_flash_bwd.hip): the dK/dV launch, role-specialised waves.
+// Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
+// the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
+// the `if constexpr (SC)` steps.  The including kernel defines `p_in`, KSPLIT / SC and sc_cl2 / sc_k2.
+// (Not a header: no include guard, no declarations of its own outside the function body.)
+  using E = Elem<DT>;
+  constexpr int NW = 8, OWN = 128;
+  constexpr int ROWB = D * 2;
+  constexpr int TILEB = kTile * ROWB;
+  constexpr int STATB = 2 * kTile * 4;
+  constexpr int BUFB = 2 * TILEB + STATB;
+  constexpr int NBUF = 3;
+  constexpr int PSLOT = 4096;                    // P of one 64 x 32 block, 16-bit
+  constexpr int POFF = NBUF * BUFB;              // P exchange: [4 slices][2 slots][PSLOT]
+  constexpr int NKT = D / 16;
+  constexpr int NDJ = D / 32;
+  constexpr int CHUNKS = TILEB / 1024;
+  constexpr int CPW = (CHUNKS + NW - 1) / NW;
+  constexpr int RPC = 1024 / ROWB;
+  constexpr int NGR = 2 * NDJ;                   // gradient MFMAs per half
+  constexpr int PF = 2;                          // LDS operands are fetched this many MFMAs ahead
+
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  USP_LDS char* smem = (USP_LDS char*)smem_raw;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int role = wave >> 2;                    // 0: A (S, P, dV)   1: B (dP, dS, dK)
+  const int slice = wave & 3;
+  const int l31 = lane & 31;
+  const int hi = lane >> 5;
+
+  const ItemWalk walk(p_in.n_items);             // persistent workgroups (usp_common.hpp)
+  ItemQueue queue{p_in.sched, p_in.seq_k, p_in.n_items / p_in.nblk, p_in.nblk,
+                  p_in.Hkv * p_in.ngrp, OWN, 0};
+  int qstate = 0;
+  USP_LDS int* qslots = (USP_LDS int*)(smem + p_in.sched_lds);
+  for (int pass = 0;; ++pass) {
+  int w = p_in.sched ? item_queue_next(queue, qstate, qslots, pass) : walk.at(pass);
+  if (w < 0) break;
+  BwdParams p = p_in;
+  if (!p_in.sched) w = walk.dealt(w, p.nblk);
+  const int blk = w % p.nblk;                    // early key blocks are seen by most rows: first
+  int rest = w / p.nblk;
+  int g = 0, cut = 0;
+  if (p.qsplit > 1) { cut = rest % p.qsplit; rest /= p.qsplit; }
+  if (p.ngrp > 1) { g = rest % p.ngrp; rest /= p.ngrp; }
+  const int hkv = rest % p.Hkv, b = rest / p.Hkv;
+  const int h0 = hkv * p.G + g * p.gsub;
+  int64_t ws_row0;
+  if (!bind_sequence(p, b, &ws_row0)) continue;
+  const int own0 = blk * OWN;
+  if (p.seq_q != nullptr && own0 >= p.Sk) continue;          // past the end of its sequence
+  const int off = p.causal_off;
+  const int ow = own0 + slice * 32;
+  const int orow = ow + l31;
+  const int orow_c = orow < p.Sk ? orow : p.Sk - 1;
+
+  // K (role A) or V (role B) fragments of this wave's 32 keys
+  u32x4 rf[NKT];
+  {
+    const char* pr = role == 0 ? p.k + 2 * (b * p.k_sb + (int64_t)orow_c * p.k_ss + hkv * p.k_sh)
+                               : p.v + 2 * (b * p.v_sb + (int64_t)orow_c * p.v_ss + hkv * p.v_sh);
+#pragma unroll
+    for (int t = 0; t < NKT; ++t) rf[t] = *(const u32x4*)(pr + 32 * t + 16 * hi);
+  }
+
+  int t_begin = 0, t_end = (p.Sq + kTile - 1) / kTile;
+  if (CAUSAL) {
+    const int first_q = own0 - off > 0 ? own0 - off : 0;
+    t_begin = first_q / kTile;
+    if (t_begin > t_end) t_begin = t_end;
+  }
+  if (p.win_on) {                                // query rows beyond the window of the block's last key: not streamed
+    const int last = own0 + OWN - 1 - p.win_lo;  // row i sees key j only if i <= j - win_lo
+    const int te = last >= 0 ? last / kTile + 1 : 0;
+    t_end = te < t_end ? te : t_end;
+    if (t_begin > t_end) t_begin = t_end;
+  }
+  if (p.qsplit > 1) {                            // this item's cut of the query tiles [t_begin, t_end): equal runs
+    const int per = (t_end - t_begin + p.qsplit - 1) / p.qsplit;
+    t_begin = t_begin + cut * per < t_end ? t_begin + cut * per : t_end;
+    t_end = t_begin + per < t_end ? t_begin + per : t_end;
+  }
+  const int per_head = t_end - t_begin;
+  const int heads_here = p.gsub;
+  const int n_iter = per_head * heads_here;
+
+  // ---- LDS-DMA staging of the Q / dO tiles -----------------------------------------------------------------
+  // ONE buffer descriptor pair per (item, query head), based on row 0 of that head; a tile is addressed by a scalar byte
+  // offset (the instruction's soffset operand).  Per tile that is two s_add and the loads.  (Round 2 kept 64-bit tile
+  // pointers / remaining-bytes counters and rebuilt both descriptors -- clamps included -- for every tile, and every
+  // tile recomputed the 64-bit addresses of its row statistics: ~170 scalar instructions and 40-50 SGPR-spill reloads
+  // (v_readlane) at the head of EVERY iteration of EVERY wave, 40 % of a wave's instruction stream -- the kernel was
+  // bound by instruction issue, not by the MFMA pipe: with every element operation removed it still ran at 973 of
+  // 1071 us, profiles/r03_bwd_ablations.txt.)  The host guarantees that a head's rows span less than 2^31 bytes.
+  int dma_voff1[CPW], dma_voff2[CPW];
+#pragma unroll
+  for (int i = 0; i < CPW; ++i) {
+    const int cidx = wave + NW * i;
+    const int r = cidx * RPC + lane / (D / 8);
+    const int c8 = (lane % (D / 8)) ^ tile_swz<D>(r);
+    dma_voff1[i] = r * (int)p.q_ss * 2 + c8 * 16;
+    dma_voff2[i] = r * (int)p.do_ss * 2 + c8 * 16;
+  }
+  float st_lse = 0.f, st_delta = 0.f;
+  bool st_in = false;
+  decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0)) rs1, rs2;
+  const int tb1 = kTile * (int)p.q_ss * 2, tb2 = kTile * (int)p.do_ss * 2;     // bytes per tile step
+  int pf_tile = t_begin, pf_hh = 0, soff1 = 0, soff2 = 0;
+  const float *lse_h = nullptr, *dl_h = nullptr;                             // row statistics of the cursor's head
+  const bool stat_wave = wave == 4;              // a role-B wave fetches the tile's statistics: role A is the longer stream
+  auto pf_head = [&]() {                         // (re)base the cursor on head h0 + pf_hh, tile t_begin
+    auto clampu = [](int64_t r) { return (int)(uint32_t)(r < 0 ? 0 : (r > 0xffffffffLL ? 0xffffffffLL : r)); };
+    const int h = h0 + pf_hh;
+    rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.q + 2 * (b * p.q_sb + h * p.q_sh)), 0,
+                                            clampu(((int64_t)(p.Sq - 1) * p.q_ss + D) * 2), 0x00020000);
+    rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dout + 2 * (b * p.do_sb + h * p.do_sh)), 0,
+                                            clampu(((int64_t)(p.Sq - 1) * p.do_ss + D) * 2), 0x00020000);
+    lse_h = p.lse + b * p.lse_sb + h * p.lse_sh;
+    dl_h = p.delta + b * p.dl_sb + h * p.dl_sh;
+    pf_tile = t_begin;
+    soff1 = t_begin * tb1;
+    soff2 = t_begin * tb2;
+  };
+  pf_head();
+  // issue the cursor's tile into LDS buffer `buf`, fetch its row statistics, advance the cursor
+  auto stage_next = [&](int buf) {
+    if (stat_wave) {                             // raw loads only: the values are consumed by stage_stats, a tile later
+      const int r = pf_tile * kTile + lane;
+      st_in = r < p.Sq;                          // rows past the end: P = 0 (their Q / dO rows read as zero)
+      const int rc = st_in ? r : p.Sq - 1;
+      st_lse = lse_h[rc];
+      st_delta = dl_h[rc];
+    }
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+      const int cidx = wave + NW * i;
+      if (CHUNKS % NW == 0 || cidx < CHUNKS) {
+        USP_LDS char* d1 = smem + buf * BUFB + cidx * 1024;
+        lds_dma16(rs1, d1, dma_voff1[i], soff1);
+        lds_dma16(rs2, d1 + TILEB, dma_voff2[i], soff2);
+      }
+    }
+    ++pf_tile;
+    soff1 += tb1;
+    soff2 += tb2;
+    if (heads_here > 1 && pf_tile == t_end) { ++pf_hh; pf_head(); }
+  };
+  auto stage_stats = [&](int buf) {
+    if (stat_wave) {
+      const float l2 = (st_in && st_lse != USP_NEG_INF) ? st_lse * kLog2e : __builtin_inff();
+      *(USP_LDS float*)(smem + buf * BUFB + 2 * TILEB + 4 * lane) = l2;
+      *(USP_LDS float*)(smem + buf * BUFB + 2 * TILEB + 4 * kTile + 4 * lane) = st_in ? -st_delta : 0.f;   // NEGATED:
+    }                                                                          // role B folds it into the dP chain
+  };
+
+  // ---- per-lane LDS addresses ------------------------------------------------------------------------
+  const int rd_row = l31 * ROWB;
+  const int rd_x = hi ^ tile_swz<D>(l31);
+  int tr_addr[NDJ][2];
+  {
+    const int i = lane & 15, grp = (lane >> 4) & 1;
+#pragma unroll
+    for (int dj = 0; dj < NDJ; ++dj)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int rr = 8 * e + 4 * hi + (i >> 2);
+        const int slot = 4 * dj + 2 * grp + ((i & 3) >> 1);
+        tr_addr[dj][e] = rr * ROWB + ((slot ^ tile_swz<D>(rr)) * 16) + (i & 1) * 8;
+      }
+  }
+  USP_LDS char* pex = smem + POFF + slice * 2 * PSLOT + lane * 16;   // + slot*PSLOT + (2h+k2)*1024
+
+  f32x16 acc[NDJ];                               // dV^T (role A) / dK^T (role B)
+#pragma unroll
+  for (int dj = 0; dj < NDJ; ++dj)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[dj][r] = 0.f;
+  const float c = p.scale_log2;
+  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+  if (n_iter > 0) { stage_next(0); stage_stats(0); }
+  dma_drain();            // this wave's DMA pieces of the staged tile have landed (usp_common.hpp)
+  __syncthreads();
+
+  // The streaming loop is instantiated once per role, with ROLE a compile-time constant, and the role
+  // is chosen by ONE branch around the whole loop: both roles execute the same barrier sequence.  (With
+  // run-time role tests inside the per-element code every MFMA slot was split into several basic
+  // blocks: 5.9 SALU per MFMA and 51 % of wave cycles parked; with one loop holding both roles' tile
+  // bodies their loop invariants added up and the kernel spilled.)
+  auto stream = [&](auto role_c) {
+    constexpr int ROLE = decltype(role_c)::value;
+    int tile_a = t_begin;                          // streamed tile role A works on in iteration `it`
+    int tile_b = t_begin;                          // ... and role B (the previous tile of A)
+    int buf_a = 0, buf_b = NBUF - 1;               // LDS buffers of those tiles (it % 3, (it - 1) % 3)
+    for (int it = 0; it <= n_iter; ++it) {
+      const bool prefetch = it + 1 < n_iter;
+      const int buf_n = buf_a + 1 == NBUF ? 0 : buf_a + 1;      // (it + 1) % NBUF
+      if (prefetch) stage_next(buf_n);
+
+      const int my_it = it - ROLE;
+      const int buf_of_my = ROLE == 0 ? buf_a : buf_b;
+      const int tile = ROLE == 0 ? tile_a : tile_b;
+      tile_b = tile_a;
+      tile_a = (tile_a + 1 == t_end) ? t_begin : tile_a + 1;
+      const int s0 = tile * kTile;
+      const bool valid = my_it >= 0 && my_it < n_iter;
+      const bool active = valid && ow < p.Sk && (!CAUSAL || (s0 + kTile - 1 + off >= ow)) &&
+                          (!p.win_on || s0 <= ow + 31 - p.win_lo);
+      const bool need_mask = (CAUSAL && (s0 + off < ow + 31)) || (p.win_on && s0 + kTile - 1 > ow - p.win_lo);
+
+      if (active) {
+        {
+          const int buf = buf_of_my;
+          USP_LDS const char* x1 = smem + buf * BUFB;            // Q tile
+          USP_LDS const char* x2 = x1 + TILEB;                   // dO tile
+          USP_LDS const char* xs = ROLE == 0 ? x1 : x2;          // row-read operand of the S / dP chain
+          USP_LDS const char* xg = ROLE == 0 ? x2 : x1;          // transpose-read operand of the gradient
+          USP_LDS const char* stat = x1 + 2 * TILEB + (ROLE == 0 ? 0 : 4 * kTile);
+          USP_LDS char* pslot = pex + (my_it & 1) * PSLOT;
+          f32x16 sc[2];                                          // S (role A) / dP (role B) of the two halves
+          u32x4 pk[2][2];                                        // packed P (A) / dS (B): B operand of the gradient
+          u32x4 pin[2][2];                                       // role B: P received from A
+          f32x4 st4;
+          f32x4 stq[4];
+          float pg_prev = 0.f;                                   // softcap, role A: P (1 - t^2) of the previous element
+          u32x4 pkg;                                             // ... packed: the k-step handed to B                                          // row statistics of one half, fetched ahead of use
+          auto load_stat = [&](int h, int j) {
+            stq[j] = *(USP_LDS const f32x4*)(stat + (32 * h + 4 * hi) * 4 + 32 * j);
+          };
+          auto load_stats = [&](int h) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) load_stat(h, j);
+          };
+
+          // element r of half h: role A: P = exp2(S*c - lse2); role B: dS = P * (dP - delta), where the dP chain
+          // STARTS from -delta (the MFMA's C operand = the row statistics tuple: one VALU per score less in the role
+          // that has the most of them)
+          auto elem = [&](int h, int r) {
+            if (ROLE == 0 && (r & 3) == 0) st4 = stq[r >> 2];
+            float val;
+            if (ROLE == 0) {
+              if constexpr (SC) {
+                const float x = sc[h][r];                         // raw score, -inf where masked
+                const float t = softcap_tanh(x, sc_k2);
+                val = fast_exp2(__builtin_fmaf(t, sc_cl2, -st4[r & 3]));
+                val = x == USP_NEG_INF ? 0.f : val;
+                const float pg = val * __builtin_fmaf(-t, t, 1.f);
+                if (r & 1) pkg[(r & 7) >> 1] = E::pack2(pg_prev, pg);
+                else pg_prev = pg;
+              } else {
+                val = fast_exp2(__builtin_fmaf(sc[h][r], c, -st4[r & 3]));
+              }
+            } else {
+              const uint32_t wd = pin[h][r >> 3][(r & 7) >> 1];
+              const float pr = (r & 1) ? E::hi(wd) : E::lo(wd);
+              val = pr * sc[h][r];
+            }
+            sc[h][r] = val;
+            if (r & 1) pk[h][r >> 3][(r & 7) >> 1] = E::pack2(sc[h][r - 1], sc[h][r]);
+            if (ROLE == 0 && (r & 7) == 7)                        // 8 elements done: hand one k-step of P to B
+              *(USP_LDS u32x4*)(pslot + (2 * h + (r >> 3)) * 1024) = SC ? pkg : pk[h][r >> 3];
+          };
+          auto chain_phase = [&](int h, int vh) {
+            u32x4 f[NKT];
+            auto rd = [&](int kt) {
+              f[kt] = *(USP_LDS const u32x4*)(xs + h * 32 * ROWB + rd_row + (((2 * kt) ^ rd_x) * 16));
+            };
+            f32x16 c0 = zero16;
+            if (ROLE == 1) {                                     // -delta of this half's 16 rows: the chain's C operand
+              load_stats(h);
+#pragma unroll
+              for (int r = 0; r < 16; ++r) c0[r] = stq[r >> 2][r & 3];
+            }
+#pragma unroll
+            for (int kt = 0; kt < PF && kt < NKT; ++kt) rd(kt);
+            if (ROLE == 1) {                                     // fetch A's P of this half early
+              pin[h][0] = *(USP_LDS const u32x4*)(pslot + (2 * h) * 1024);
+              pin[h][1] = *(USP_LDS const u32x4*)(pslot + (2 * h + 1) * 1024);
+            }
+            if (ROLE == 0 && vh >= 0) load_stats(vh);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int kt = 0; kt < NKT; ++kt) {
+              if (kt + PF < NKT) rd(kt + PF);
+              sc[h] = E::mfma(f[kt], rf[kt], kt == 0 ? c0 : sc[h]);
+              if (vh >= 0) {
+#pragma unroll
+                for (int e = kt * 16 / NKT; e < (kt + 1) * 16 / NKT; ++e) elem(vh, e);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          };
+          auto grad_phase = [&](int h, int vh) {
+            u32x4 xa[NGR];
+            auto rd = [&](int i) {
+              const int k2 = i / NDJ, dj = i % NDJ;
+              USP_LDS const char* xb = xg + (2 * h + k2) * 16 * ROWB;
+              const u32x2 a0 = lds_read_tr16(xb + tr_addr[dj][0]);
+              const u32x2 a1 = lds_read_tr16(xb + tr_addr[dj][1]);
+              xa[i] = u32x4{a0[0], a0[1], a1[0], a1[1]};
+            };
+#pragma unroll
+            for (int i = 0; i < PF && i < NGR; ++i) rd(i);
+            if (ROLE == 0 && vh >= 0) load_stats(vh);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < NGR; ++i) {
+              if (i + PF < NGR) rd(i + PF);
+              acc[i % NDJ] = E::mfma(xa[i], pk[h][i / NDJ], acc[i % NDJ]);
+              if (vh >= 0) {
+#pragma unroll
+                for (int e = i * 16 / NGR; e < (i + 1) * 16 / NGR; ++e) elem(vh, e);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          };
+          auto apply_mask = [&](int h) {                         // role A only: query row i sees key j iff j <= i + off
+            if (CAUSAL) {
+              const int d = orow - off - s0 - 4 * hi;            // one VGPR; thresholds are inline constants
+#pragma unroll
+              for (int r = 0; r < 16; ++r)
+                if (d > 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
+            }
+            if (p.win_on) {                                      // ... and only if j >= i + win_lo
+              const int dl = orow - p.win_lo - s0 - 4 * hi;
+#pragma unroll
+              for (int r = 0; r < 16; ++r)
+                if (dl < 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
+            }
+          };
+
+          chain_phase(0, -1);
+          if (ROLE == 0 && need_mask) apply_mask(0);
+          chain_phase(1, 0);
+          if (ROLE == 0 && need_mask) apply_mask(1);
+          grad_phase(0, 1);
+          grad_phase(1, -1);
+        }
+      }
+
+      if (prefetch) stage_stats(buf_n);
+      buf_b = buf_a;
+      buf_a = buf_n;
+      dma_drain();            // this wave's DMA pieces of the staged tile have landed (usp_common.hpp)
+      __syncthreads();
+    }
+
+  };
+  if (role == 0) stream(std::integral_constant<int, 0>{});
+  else stream(std::integral_constant<int, 1>{});
+
+  // ---- epilogue ------------------------------------------------------------------------------------------
+  if (orow < p.Sk) {
+    float* o32;
+    char* o16 = nullptr;
+    int accf;
+    const float mul = role == 0 ? 1.f : p.scale;
+    if (p.split) {
+      const int64_t wo = (((int64_t)(g * p.qsplit + cut) * p.ws_rows + ws_row0 + orow) * p.Hkv + hkv) * D;
+      o32 = (role == 0 ? p.ws_dv : p.ws_dk) + wo; accf = 0;
+    } else if (role == 0) {
+      o32 = p.dv + b * p.dv_sb + (int64_t)orow * p.dv_ss + hkv * p.dv_sh; accf = p.accum_dv;
+      if (p.dv16) o16 = p.dv16 + 2 * (b * p.dv16_sb + (int64_t)orow * p.dv16_ss + hkv * p.dv16_sh);
+    } else {
+      o32 = p.dk + b * p.dk_sb + (int64_t)orow * p.dk_ss + hkv * p.dk_sh; accf = p.accum_dk;
+      if (p.dk16) o16 = p.dk16 + 2 * (b * p.dk16_sb + (int64_t)orow * p.dk16_ss + hkv * p.dk16_sh);
+    }
+#pragma unroll
+    for (int dj = 0; dj < NDJ; ++dj)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const int d0 = 32 * dj + 8 * g4 + 4 * hi;
+        f32x4 v = {acc[dj][4 * g4] * mul, acc[dj][4 * g4 + 1] * mul, acc[dj][4 * g4 + 2] * mul,
+                   acc[dj][4 * g4 + 3] * mul};
+        if (accf) v += *(const f32x4*)(o32 + d0);
+        if (o16) *(u32x2*)(o16 + 2 * d0) = u32x2{E::pack2(v[0], v[1]), E::pack2(v[2], v[3])};
+        else *(f32x4*)(o32 + d0) = v;
+      }
+  }
+  if (p_in.sched && p_in.interleave) break;   // one item per workgroup: leave room for other streams' kernels
+  }  // next item
+  if (p_in.sched && threadIdx.x == 0) item_queue_release(queue);

@@ -39,6 +39,14 @@ struct FwdSplit {
 };
 template <bool KS> struct FwdArgsT : FwdParams {};
 template <> struct FwdArgsT<true> : FwdParams, FwdSplit {};
+// Logit soft-capping (USP_ATTN_SOFTCAP): kernel arguments of the softcap instantiations only (flash_fwd_softcap_kernel, built on
+// the split instantiation's generic loop); the plain and split kernels keep their argument blocks and machine code.
+struct FwdSoftcap {
+  int cap_on;                           // host: the call caps its scores (selects the softcap kernel)
+  float cap_log2;                       // cap * log2(e): the capped score in exp2 units is cap_log2 * tanh(..)
+  float tanh_k2;                        // 2 * scale * log2(e) / cap (usp_common.hpp: softcap_tanh)
+};
+struct FwdArgsSC : FwdArgsT<true>, FwdSoftcap {};
 
 constexpr int kBN = 64;    // keys per KV tile
 

@@ -18,6 +18,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
+from .._C import softcap_value
 from ..comm import all_to_all as A
 from ..comm.link import link_bytes_per_s
 from ..kernels.attention import kernel_head_dim, pad_head_dim
@@ -453,7 +454,8 @@ class _AsyncUSPFunc(torch.autograd.Function):
     sequential order (one packed exchange in, attention, one exchange out)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, softmax_scale, causal, ulysses_pg, ring_pg, impl, ng_cap=None):
+    def forward(ctx, q, k, v, softmax_scale, causal, ulysses_pg, ring_pg, impl, ng_cap=None, softcap=None):
+        # softcap (flash-attn's logit cap, > 0 or None): carried to every block launch; it changes no schedule decision below
         fwd, _ = _RING_FWD_BWD[impl]
         P = dist.get_world_size(ulysses_pg)
         B, Sl, Hq, D = q.shape
@@ -492,7 +494,7 @@ class _AsyncUSPFunc(torch.autograd.Function):
                     (qi, ki, vi), ev, send_i = ins[i]
                     own = _self_views(send_i, u, (kvh * g, kvh, kvh))
                     gens[i] = zigzag_forward_phases(ring_pg, qi, ki, vi, softmax_scale, overlap,
-                                                    (u, own, lambda ev=ev: lane.wait(ev)), tail_of(i))
+                                                    (u, own, lambda ev=ev: lane.wait(ev)), tail_of(i), softcap)
                     next(gens[i])             # allocations + the launch on the owned chunk; stops in front of the wait
             for i in range(ng):
                 (qi, ki, vi), ev, send_i = ins[i]
@@ -505,17 +507,19 @@ class _AsyncUSPFunc(torch.autograd.Function):
                 elif split0 and i == 0:       # ring degree 1: the one causal block, split in the layer
                     from ..kernels.attention import get_block_backend
                     own = _self_views(send_i, u, (kvh * g, kvh, kvh))
-                    oi, lse_i = _split_first_forward(get_block_backend(beside_transfers=True), u, own, (qi, ki, vi),
+                    oi, lse_i = _split_first_forward(get_block_backend(beside_transfers=True, softcap=softcap), u, own, (qi, ki, vi),
                                                      lambda ev=ev: lane.wait(ev), softmax_scale)
                 elif ring == 1 and tail_of(i) is not None:       # the 2-GPU grid: the last group's one causal block in row pieces
                     from ..kernels.attention import get_block_backend
                     lane.wait(ev)
-                    oi, lse_i = _tail_last_forward(get_block_backend(beside_transfers=True), qi, ki, vi, softmax_scale, *tail_of(i))
+                    oi, lse_i = _tail_last_forward(get_block_backend(beside_transfers=True, softcap=softcap), qi, ki, vi, softmax_scale,
+                                                   *tail_of(i))
                 else:
                     lane.wait(ev)
                     t = tail_of(i)
                     kw = {} if t is None else {"tail": t}
-                    oi, lse_i = fwd(ring_pg, qi, ki, vi, softmax_scale=softmax_scale, causal=causal, overlap=overlap, **kw)
+                    oi, lse_i = fwd(ring_pg, qi, ki, vi, softmax_scale=softmax_scale, causal=causal, softcap=softcap,
+                                    overlap=overlap, **kw)
                 saved += [qi, ki, vi, oi, lse_i]
                 if tail_of(i) is not None:
                     outs.append(None)         # (travelled in `pieces`)
@@ -536,12 +540,14 @@ class _AsyncUSPFunc(torch.autograd.Function):
         ctx.meta = (softmax_scale, causal, ulysses_pg, ring_pg, impl, P, ng, kvh, g, Hq, Hkv)
         ctx.split0 = (split0, u, ring)
         ctx.n_tail = n_tail if tail_of(ng - 1) is not None else 0
+        ctx.softcap = softcap
         return out
 
     @staticmethod
     def backward(ctx, dout):
         softmax_scale, causal, ulysses_pg, ring_pg, impl, P, ng, kvh, g, Hq, Hkv = ctx.meta
         _, bwd = _RING_FWD_BWD[impl]
+        softcap = ctx.softcap
         saved = ctx.saved_tensors
         B, Sl, _, D = dout.shape
         overlap = ng > 1
@@ -562,22 +568,24 @@ class _AsyncUSPFunc(torch.autograd.Function):
                     do_own = _self_views(send_i, u, (kvh * g,))[0]
                     tail = []
                     if ring == 1:
-                        dqi, dki, dvi = _split_first_backward(get_block_backend(beside_transfers=True), u, do_own, doi,
+                        dqi, dki, dvi = _split_first_backward(get_block_backend(beside_transfers=True, softcap=softcap), u, do_own, doi,
                                                               lambda ev=ev: lane.wait(ev), qi, ki, vi, oi, lse_i, softmax_scale)
                     else:
                         dqi, dki, dvi = bwd(ring_pg, doi, qi, ki, vi, oi, lse_i, softmax_scale=softmax_scale, causal=causal,
-                                            overlap=overlap, tail=tail, first=(u, do_own, lambda ev=ev: lane.wait(ev)), **kw)
+                                            softcap=softcap, overlap=overlap, tail=tail,
+                                            first=(u, do_own, lambda ev=ev: lane.wait(ev)), **kw)
                 elif ring == 1 and kw:         # the 2-GPU grid's last group: dQ launch, dq exchange, dK/dV launch
                     from ..kernels.attention import get_block_backend
                     lane.wait(ev)
                     tail = []
-                    dqi, dki, dvi = _tail_last_backward(get_block_backend(beside_transfers=True), doi, qi, ki, vi, oi, lse_i,
+                    dqi, dki, dvi = _tail_last_backward(get_block_backend(beside_transfers=True, softcap=softcap), doi, qi, ki, vi,
+                                                        oi, lse_i,
                                                         softmax_scale, kw["dq_first"])
                 else:
                     lane.wait(ev)
                     tail = []                  # the ring backward's last dK/dV hop, left pending (ring/utils.py:travel_dkdv)
                     dqi, dki, dvi = bwd(ring_pg, doi, qi, ki, vi, oi, lse_i, softmax_scale=softmax_scale,
-                                        causal=causal, overlap=overlap, tail=tail, **kw)
+                                        causal=causal, softcap=softcap, overlap=overlap, tail=tail, **kw)
                 if dq_sent:                    # two exchanges: dq (posted inside the ring backward), then dk | dv
                     pend.append((dq_sent[0], _grads_to_heads_issue(lane, None, dki, dvi, tail, P, ulysses_pg)))
                 else:
@@ -602,7 +610,7 @@ class _AsyncUSPFunc(torch.autograd.Function):
                 A.unpack_head_group(recv, q5[:, :, :, i], 0)
                 A.unpack_head_group(recv, k5[:, :, :, i], hq)
                 A.unpack_head_group(recv, v5[:, :, :, i], hq + kvh)
-        return dq, dk, dv, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 class AsyncLongContextAttention(torch.nn.Module):
@@ -632,5 +640,5 @@ class AsyncLongContextAttention(torch.nn.Module):
             query, key, value = pad_head_dim(query, key, value)
             softmax_scale = D ** -0.5 if softmax_scale is None else softmax_scale
         out = _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
-                                  self.ring_impl_type)
+                                  self.ring_impl_type, None, softcap_value(softcap))
         return out[..., :D]

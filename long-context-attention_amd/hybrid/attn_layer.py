@@ -14,6 +14,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
+from .._C import softcap_value
 from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll5D
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
@@ -124,7 +125,7 @@ class LongContextAttention(_USPLayer):
             assert alibi_slopes is None
             _check_hot_path_args(dropout_p, window_size, softcap)
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
-                                       self.ring_impl_type, ng_cap)
+                                       self.ring_impl_type, ng_cap, softcap_value(softcap))
         options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                                      deterministic, return_attn_probs)
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)

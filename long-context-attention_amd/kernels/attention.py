@@ -78,29 +78,30 @@ class HipBlockBackend:
         return self._beside
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
-            final_begin=0, final_end=None, window=None, k_splits=None):
+            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
-                     interleave=self.interleave, window=window, k_splits=k_splits)
+                     interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
 
     def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq=False,
-            accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None):
+            accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None, softcap=None):
         _C.flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq,
-                     accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only)
+                     accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only,
+                     softcap=softcap)
 
     def fwd_packed(self, q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out=None,
-                   acc=None, merge_in=False, final_begin=0, final_end=2):
+                   acc=None, merge_in=False, final_begin=0, final_end=2, softcap=None):
         _C.flash_fwd_packed(q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out, acc,
-                            merge_in, final_begin, final_end, interleave=self.interleave)
+                            merge_in, final_begin, final_end, interleave=self.interleave, softcap=softcap)
 
     def bwd_packed(self, dout, q, k, v, lse, delta, seq_q, seq_k, max_q, max_k, dq, dk, dv,
                    softmax_scale, causal, accum_dq=False, accum_dk=False, accum_dv=False, dq16=None,
-                   dk16=None, dv16=None):
+                   dk16=None, dv16=None, softcap=None):
         _C.flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q, max_k, dq, dk, dv,
                             softmax_scale, causal, accum_dq, accum_dk, accum_dv, dq16, dk16, dv16,
-                            interleave=self.interleave)
+                            interleave=self.interleave, softcap=softcap)
 
     def merge(self, acc, lse, blk_out, blk_lse, first):
         _C.lse_merge(acc, lse, blk_out, blk_lse, first)
@@ -118,14 +119,41 @@ class HipBlockBackend:
 _BACKEND = HipBlockBackend()
 
 
-def get_block_backend(beside_transfers: bool = False):
+class _SoftcapBackend:
+    """A block backend whose flash calls (fwd, bwd, fwd_packed, bwd_packed) all carry `softcap=cap`; everything else is
+    the wrapped backend's.  Softcap is a per-score transform, so the ring schedules, LSE merges and gradient folds are
+    unchanged: only the block kernels see it."""
+
+    def __init__(self, be, cap: float):
+        self._be, self._cap = be, cap
+
+    def fwd(self, *args, **kw):
+        self._be.fwd(*args, softcap=self._cap, **kw)
+
+    def bwd(self, *args, **kw):
+        self._be.bwd(*args, softcap=self._cap, **kw)
+
+    def fwd_packed(self, *args, **kw):
+        self._be.fwd_packed(*args, softcap=self._cap, **kw)
+
+    def bwd_packed(self, *args, **kw):
+        self._be.bwd_packed(*args, softcap=self._cap, **kw)
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+
+def get_block_backend(beside_transfers: bool = False, softcap=None):
     """The block backend; `beside_transfers=True` asks for launches that leave room for collectives queued on
     other streams (a persistent flash launch holds every CU until it ends: DESIGN.md section 5).  Test
-    backends without that notion are returned as they are."""
+    backends without that notion are returned as they are.  `softcap` > 0 (flash-attn's logit cap): every flash
+    call of the returned backend carries it; None / 0: the backend itself, whose calls carry no softcap keyword
+    (backends written before softcap existed keep working)."""
     be = _BACKEND
     if beside_transfers and hasattr(be, "beside_transfers"):
-        return be.beside_transfers()
-    return be
+        be = be.beside_transfers()
+    cap = _C.softcap_value(softcap)
+    return be if cap is None else _SoftcapBackend(be, cap)
 
 
 def set_block_backend(backend):
@@ -142,15 +170,15 @@ def _default_scale(q, softmax_scale):
 
 
 def _check_plain(dropout_p, softcap, alibi_slopes):
-    # the hot path only ever passes these defaults (zigzag_ring_flash_attn.py:207,
-    # hybrid/attn_layer.py:132-147); anything else is outside this package's scope.  (window_size IS served: the
-    # block kernels take flash-attn's (left, right) window -- include/usp_hip.h, USP_ATTN_WINDOW.)
+    """Refuses what the kernels do not serve and returns the softcap as the kernels take it (None = off).
+    window_size and softcap ARE served: the block kernels take flash-attn's (left, right) window and its tanh logit cap
+    (include/usp_hip.h, USP_ATTN_WINDOW / USP_ATTN_SOFTCAP).  A negative, NaN or infinite softcap raises ValueError
+    (flash-attn ignores a negative one silently)."""
     if dropout_p not in (0, 0.0):
         raise NotImplementedError("dropout_p != 0 is not supported by the HIP attention kernel")
-    if softcap not in (None, 0, 0.0):
-        raise NotImplementedError("softcap is not supported by the HIP attention kernel")
     if alibi_slopes is not None:
         raise NotImplementedError("alibi_slopes is not supported by the HIP attention kernel")
+    return _C.softcap_value(softcap)
 
 
 def window_of(window_size):
@@ -164,15 +192,16 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
     Unlike the TORCH_* wrappers (attention.py:135) the LSE is NOT rounded to q.dtype."""
-    _check_plain(dropout_p, softcap, alibi_slopes)
+    cap = _check_plain(dropout_p, softcap, alibi_slopes)
     B, Sq, Hq, D = q.shape
     scale = _default_scale(q, softmax_scale)
     if kernel_head_dim(D) != D:                 # e.g. 96: on zero-padded copies (kernel_head_dim)
-        out, lse = hip_attn_forward(*pad_head_dim(q, k, v), softmax_scale=scale, causal=causal, window_size=window_size)
+        out, lse = hip_attn_forward(*pad_head_dim(q, k, v), softmax_scale=scale, causal=causal, window_size=window_size,
+                                    softcap=cap)
         return out[..., :D].contiguous(), lse
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
-    get_block_backend().fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size))
+    get_block_backend(softcap=cap).fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size))
     return out, lse
 
 
@@ -183,15 +212,15 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
     (zigzag_ring_flash_attn.py:115-137)."""
-    _check_plain(dropout_p, softcap, alibi_slopes)
-    be = get_block_backend()
+    cap = _check_plain(dropout_p, softcap, alibi_slopes)
+    be = get_block_backend(softcap=cap)
     B, Sq, Hq, D = q.shape
     dev = q.device
     if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
         pdo, pq, pk, pv, po = pad_head_dim(dout, q, k, v, out)
         g = [torch.empty_like(t) for t in (pq, pk, pv)]
         hip_attn_backward(pdo, pq, pk, pv, po, softmax_lse, g[0], g[1], g[2], dropout_p, _default_scale(q, softmax_scale),
-                          bwd_causal, window_size, softcap, alibi_slopes, deterministic, rng_state)
+                          bwd_causal, window_size, cap, alibi_slopes, deterministic, rng_state)
         for dst, src in zip((block_dq_buffer, block_dk_buffer, block_dv_buffer), g):
             dst.copy_(src[..., :D])
         return
@@ -217,12 +246,12 @@ class _HipAttnFunc(torch.autograd.Function):
     yunchang/ulysses/attn_layer.py:48,101-113)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1)):
+    def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
-        out, lse = hip_attn_forward(q, k, v, softmax_scale=scale, causal=causal, window_size=window_size)
+        out, lse = hip_attn_forward(q, k, v, softmax_scale=scale, causal=causal, window_size=window_size, softcap=softcap)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.scale, ctx.causal, ctx.window_size = scale, bool(causal), window_size
+        ctx.scale, ctx.causal, ctx.window_size, ctx.softcap = scale, bool(causal), window_size, softcap
         if return_lse:
             ctx.mark_non_differentiable(lse)
             return out, lse
@@ -233,22 +262,23 @@ class _HipAttnFunc(torch.autograd.Function):
         q, k, v, out, lse = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, 0.0, ctx.scale, ctx.causal,
-                          ctx.window_size)
-        return dq, dk, dv, None, None, None, None
+                          ctx.window_size, ctx.softcap)
+        return dq, dk, dv, None, None, None, None, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                   *args, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
-    return_attn_probs (the probabilities themselves are never materialised: dropout is 0)."""
-    _check_plain(dropout_p, softcap, alibi_slopes)
+    return_attn_probs (the probabilities themselves are never materialised: dropout is 0).  `softcap` > 0: flash-attn's
+    tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError."""
+    cap = _check_plain(dropout_p, softcap, alibi_slopes)
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)
         res = hip_attn_func(*pad_head_dim(q, k, v), softmax_scale=_default_scale(q, softmax_scale), causal=causal,
-                            window_size=window_size, return_attn_probs=return_attn_probs)
+                            window_size=window_size, softcap=cap, return_attn_probs=return_attn_probs)
         return (res[0][..., :D], res[1], None) if return_attn_probs else res[..., :D]
     if return_attn_probs:
-        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size)
+        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap)
         return out, lse, None
-    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size)
+    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap)

@@ -55,7 +55,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                             attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False):
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap)
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
@@ -78,7 +78,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
                              alibi_slopes=None, deterministic=False,
                              attn_type: AttnType = AttnType.HIP, overlap=False, tail=None):
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap)
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
     B, S, H, D = q.shape
     dev = q.device
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)
@@ -176,7 +176,7 @@ def ring_flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=Fals
         out, lse = ring_flash_attn_forward(
             group, kernel_operand(q), kernel_operand(k), kernel_operand(v),
             softmax_scale=q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale, causal=causal,
-            window_size=window_size, attn_type=attn_type, attn_processor=attn_processor)
+            window_size=window_size, softcap=softcap, attn_type=attn_type, attn_processor=attn_processor)
         return out if not return_attn_probs else (out, lse, None)
     return RingFlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
                                    alibi_slopes, deterministic, return_attn_probs, group, attn_type,

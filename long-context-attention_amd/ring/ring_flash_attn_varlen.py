@@ -40,7 +40,7 @@ def ring_flash_attn_varlen_forward(process_group, q, k, v, cu_seqlens, max_seqle
                                    alibi_slopes=None, deterministic=False):
     """Returns (out (T,H,D), lse (H,T) fp32)."""
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1)
+    be = get_block_backend(beside_transfers=P > 1, softcap=softcap)
     T, H, D = q.shape
     tb = SeqTables(cu_seqlens, max_seqlen, q.device)
     out = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
@@ -59,7 +59,7 @@ def ring_flash_attn_varlen_backward(process_group, dout, q, k, v, out, softmax_l
                                     window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                                     deterministic=False):
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1)
+    be = get_block_backend(beside_transfers=P > 1, softcap=softcap)
     T, H, D = q.shape
     dev, f32 = q.device, torch.float32
     tb = SeqTables(cu_seqlens, max_seqlen, dev)

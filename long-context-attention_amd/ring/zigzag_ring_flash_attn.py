@@ -21,6 +21,7 @@ MI355X-first differences (results identical up to fp32 rounding order):
 import torch
 import torch.distributed as dist
 
+from .._C import softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
 from .utils import FULL, KVRelay, group_info, ZigzagKVFetch, final_grads, kv_relay_mode, travel_dkdv, zigzag_fetch_pieces
@@ -198,12 +199,13 @@ def _final_rows(be, q, kp, vp, softmax_scale, lse, out, acc, lo, hi, tail):
         emit(j, out)
 
 
-def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None):
+def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None):
     """The zigzag ring forward as a generator of two phases.  With `first` it yields ONCE, behind the launch on the owned chunk
     and in front of the wait for the caller's exchange -- the caller may start other head groups' owned chunks there -- and
-    returns (out, lse) through StopIteration; without `first` it never yields.  zigzag_ring_flash_attn_forward drives it to the end."""
+    returns (out, lse) through StopIteration; without `first` it never yields.  zigzag_ring_flash_attn_forward drives it to the end.
+    `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same."""
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap)
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
     B, S2, H, D = q.shape
     assert S2 % 2 == 0, "zigzag layout needs an even local sequence length"
     dev = q.device
@@ -266,7 +268,7 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
     `tail` = (n, emit): the launch that finalises the last rows runs in n row pieces, `emit(j, out)` behind piece j (_final_rows);
     ring degree > 1 only."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
-    gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail)
+    gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap)
     try:
         while True:
             next(gen)
@@ -291,7 +293,7 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     real devices that stalls here should set USP_SELF_CHUNK=0."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap)
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
     B, S2, H, D = q.shape
     c = S2 // 2
     dev = q.device
@@ -380,12 +382,13 @@ class ZigZagRingFlashAttnFunc(torch.autograd.Function):
 
 
 def _check_hot_path_args(dropout_p, window_size, softcap):
+    """Refuses what the ring schedules do not serve.  softcap IS served (a per-score transform: every block launch carries
+    it, get_block_backend); a negative, NaN or infinite one raises ValueError (flash-attn ignores a negative one)."""
     if dropout_p not in (0, 0.0):
         raise NotImplementedError("dropout_p != 0 is not supported by the HIP ring attention")
     if window_size is not None and tuple(window_size) != (-1, -1):
         raise NotImplementedError("sliding-window attention is not supported by the HIP ring attention")
-    if softcap not in (None, 0, 0.0):
-        raise NotImplementedError("softcap is not supported by the HIP ring attention")
+    softcap_value(softcap)
 
 
 def zigzag_ring_flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False,
@@ -421,7 +424,7 @@ def zigzag_ring_flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, caus
         out, lse = zigzag_ring_flash_attn_forward(
             group, kernel_operand(q), kernel_operand(k), kernel_operand(v),
             softmax_scale=q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale, causal=causal,
-            attn_type=attn_type)
+            softcap=softcap, attn_type=attn_type)
         return out if not return_attn_probs else (out, lse, None)
     return ZigZagRingFlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal, window_size,
                                          softcap, alibi_slopes, deterministic, return_attn_probs,

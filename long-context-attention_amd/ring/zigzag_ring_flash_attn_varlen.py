@@ -66,7 +66,7 @@ def zigzag_ring_flash_attn_varlen_forward(process_group, q, k, v, cu_seqlens, ma
     """Returns (out (T,H,D), lse (H,T) fp32)."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1)
+    be = get_block_backend(beside_transfers=P > 1, softcap=softcap)
     T, H, D = q.shape
     tb = SeqTables(cu_seqlens, max_seqlen, q.device)
     out = torch.empty((T, H, D), dtype=q.dtype, device=q.device)
@@ -86,7 +86,7 @@ def zigzag_ring_flash_attn_varlen_backward(process_group, dout, q, k, v, out, so
     """`softmax_lse` is the flattened (H,T) fp32 LSE of the forward."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1)
+    be = get_block_backend(beside_transfers=P > 1, softcap=softcap)
     T, H, D = q.shape
     dev, f32 = q.device, torch.float32
     tb = SeqTables(cu_seqlens, max_seqlen, dev)
