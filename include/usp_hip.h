@@ -270,6 +270,20 @@ int usp_copy_rows(void* dst, const void* src, int64_t row_bytes,
                   int64_t ds0, int64_t ds1, int64_t ds2, int64_t ds3,
                   int64_t ss0, int64_t ss1, int64_t ss2, int64_t ss3, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Row-gather with an r-term sum: the dK/dV return of a Ulysses exchange whose KV heads are shared by
+ * r = P / Hkv ranks (each rank sends its partial sum over its own query heads; the owner adds them).
+ *   for i0<n0, i1<n1, i2<n2:
+ *     dst[i0*ds0 + i1*ds1 + i2*ds2 + (0..row_bytes)] =
+ *         round( sum_{t=0..r-1} src[t*term_stride + i0*ss0 + i1*ss1 + i2*ss2 + (0..row_bytes)] )
+ * Elements of `dtype` (USP_BF16 / USP_FP16), accumulated in fp32 in ascending t and rounded once.
+ * Strides in BYTES; row_bytes, term_stride, all strides and both pointers must be multiples of 16
+ * (USP_EUNSUPPORTED); null pointers, r < 1 or non-positive sizes are USP_EINVAL.
+ * -------------------------------------------------------------------------------------------- */
+int usp_sum_rows(int32_t dtype, void* dst, const void* src, int64_t row_bytes, int32_t r, int64_t term_stride,
+                 int64_t n0, int64_t n1, int64_t n2, int64_t ds0, int64_t ds1, int64_t ds2,
+                 int64_t ss0, int64_t ss1, int64_t ss2, void* stream);
+
 /* dst16[i] = round(src32[i]) for i < n, `rows` rows of `n` contiguous elements with row strides
  * (elements) -- the `.to(q.dtype)` casts at zigzag_ring_flash_attn.py:74,183. */
 int usp_cast_from_f32(int32_t dtype, void* dst, int64_t dst_row_stride, const float* src,

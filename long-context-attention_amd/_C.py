@@ -105,7 +105,7 @@ class UspBwdArgs(ctypes.Structure):
 
 
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
-           "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
+           "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
            "usp_attn_features")
 
 
@@ -147,11 +147,12 @@ def load():
     L.usp_lse_merge.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(UspTensor), vp, i64, i64,
                                 ctypes.POINTER(UspTensor), vp, i64, i64, i32, vp]
     L.usp_copy_rows.argtypes = [vp, vp] + [i64] * 13 + [vp]
+    L.usp_sum_rows.argtypes = [i32, vp, vp, i64, i32] + [i64] * 10 + [vp]
     L.usp_cast_from_f32.argtypes = [i32, vp, i64, vp, i64, i64, i64, vp]
     L.usp_add_f32.argtypes = [vp, i64, vp, i64, vp, i64, i64, i64, vp]
     L.usp_mfma_probe.argtypes = [vp, i64, i32, i32, vp, vp, vp]
     L.usp_mfma_probe.restype = ctypes.c_int
-    for name in ("usp_flash_fwd", "usp_flash_bwd", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
+    for name in ("usp_flash_fwd", "usp_flash_bwd", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows", "usp_sum_rows",
                  "usp_cast_from_f32", "usp_add_f32"):
         getattr(L, name).restype = ctypes.c_int
     _lib = L
@@ -568,6 +569,21 @@ def copy_rows(dst, src, row_bytes, sizes, dst_strides, src_strides):
     ss = list(src_strides) + [0] * (4 - len(src_strides))
     _check(load().usp_copy_rows(ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()),
                                 row_bytes, *n, *ds, *ss, _stream()), "usp_copy_rows")
+
+
+def sum_rows(dst, src, row_bytes, r, term_stride, sizes, dst_strides, src_strides):
+    """usp_sum_rows: dst rows = round(sum of r source rows `term_stride` bytes apart), fp32 in ascending term order.
+    Strides in BYTES, up to 3 outer dims; dst and src of one 16-bit dtype."""
+    _require_cuda(dst, src)
+    if dst.dtype != src.dtype:
+        raise TypeError(f"usp_sum_rows: dst {dst.dtype} and src {src.dtype} differ")
+    if len(sizes) > 3 or len(dst_strides) != len(sizes) or len(src_strides) != len(sizes):
+        raise ValueError(f"usp_sum_rows takes up to 3 outer dims with one stride each: {sizes} {dst_strides} {src_strides}")
+    n = list(sizes) + [1] * (3 - len(sizes))
+    ds = list(dst_strides) + [0] * (3 - len(dst_strides))
+    ss = list(src_strides) + [0] * (3 - len(src_strides))
+    _check(load().usp_sum_rows(dtype_code(dst.dtype), ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(src.data_ptr()),
+                               int(row_bytes), int(r), int(term_stride), *n, *ds, *ss, _stream()), "usp_sum_rows")
 
 
 def _rows2d(t: torch.Tensor):

@@ -52,6 +52,27 @@ def _copy_rows(dst: Tensor, src: Tensor, row_elems: int, sizes, dst_strides, src
         d.copy_(s)
 
 
+def _sum_rows(dst: Tensor, src: Tensor, row_elems: int, r: int, term_stride: int, sizes, dst_strides, src_strides):
+    """dst rows = the sum of r src rows `term_stride` elements apart (fp32, ascending term order, rounded once).  Device
+    tensors -> usp_sum_rows; host tensors (gloo orchestration tests) -> the same sum over as_strided views."""
+    es = src.element_size()
+    if src.is_cuda:
+        get_block_backend().sum_rows(dst, src, row_elems * es, r, term_stride * es, list(sizes),
+                                     [s * es for s in dst_strides], [s * es for s in src_strides])
+    else:
+        # host tensors: the constraints of usp_sum_rows (include/usp_hip.h), as _copy_rows holds copies to usp_copy_rows'
+        assert (row_elems * es) % 16 == 0 and (term_stride * es) % 16 == 0 \
+            and all((st * es) % 16 == 0 for st in list(dst_strides) + list(src_strides)) \
+            and (dst.storage_offset() * es) % 16 == 0 and (src.storage_offset() * es) % 16 == 0, \
+            f"usp_sum_rows needs 16-byte rows / strides / pointers: row {row_elems * es} B, strides {dst_strides} {src_strides}"
+        d = torch.as_strided(dst, list(sizes) + [row_elems], list(dst_strides) + [1], dst.storage_offset())
+        acc = torch.zeros(d.shape, dtype=torch.float32)
+        for t in range(r):
+            acc = acc + torch.as_strided(src, list(sizes) + [row_elems], list(src_strides) + [1],
+                                         src.storage_offset() + t * term_stride).float()
+        d.copy_(acc)
+
+
 def _exchange(send: Tensor, group, use_sync: bool) -> Tensor:
     if relay_exchange.applicable(send, group):       # a pair's exchange striped over the idle mesh links (opt-in)
         recv = relay_exchange.exchange_relayed(send, group)
@@ -218,6 +239,103 @@ class SeqAllToAll4D(torch.autograd.Function):
                 SeqAllToAll4D.apply(ctx.group, grad_output[0], ctx.gather_idx, ctx.scatter_idx,
                                     ctx.use_sync, ctx.contiguous),
                 None, None, None, None)
+
+
+# --------------------------------------------------------------------------------------------------
+# KV heads shared by several Ulysses ranks: Hkv < P, P % Hkv == 0 (MQA, or 4 KV heads at ulysses degree 8)
+# --------------------------------------------------------------------------------------------------
+def kv_replicas(Hkv: int, P: int) -> int:
+    """r, the number of Ulysses ranks that share one KV head after the head-scatter exchange -- THE rank -> KV-head map
+    of this package (every pack, unpack and layer below asks here):
+        Hkv % P == 0           r = 1: rank p owns KV heads [p Hkv/P, (p+1) Hkv/P), the exchange as ever;
+        Hkv < P, P % Hkv == 0  r = P / Hkv: rank p gets KV head p // r, a REPLICA, beside its query heads
+                               [p Hq/P, (p+1) Hq/P) (they all use that head when Hq % P == 0: Hq/P divides G = Hq/Hkv).
+                               Forward: every rank sends its rows of head h to ranks h r .. h r + r - 1.  Backward: a
+                               rank's dK/dV is a partial sum over its own query heads; each sequence owner sums the r
+                               partials of a head in fp32, in ascending Ulysses rank order, and rounds once;
+        otherwise              0: not served."""
+    if Hkv % P == 0:
+        return 1
+    return P // Hkv if P % Hkv == 0 else 0
+
+
+def pack_kv_replicated(send: Tensor, h0: int, x: Tensor, r: int) -> None:
+    """(B, S/P, Hkv, D) with Hkv r == P -> head h0 of the send buffer (P, S/P, B, Ht, D): chunk p (destination rank p)
+    gets KV head p // r (kv_replicas).  ONE usp_copy_rows launch whose source stride over the r replicas is zero."""
+    P, Sl, B, Ht, D = send.shape
+    Hkv = x.shape[2]
+    assert r > 1 and Hkv * r == P and x.shape == (B, Sl, Hkv, D) and send.is_contiguous() and h0 < Ht
+    if x.stride(3) != 1:
+        x = x.contiguous()
+    dst = send.as_strided((1,), (1,), send.storage_offset() + h0 * D)
+    base = x.as_strided((1,), (1,), x.storage_offset())
+    chunk = Sl * B * Ht * D
+    _copy_rows(dst, base, D, (Hkv, r, Sl, B), (r * chunk, chunk, B * Ht * D, Ht * D),
+               (x.stride(2), 0, x.stride(1), x.stride(0)))
+
+
+def unpack_kv_sum(recv: Tensor, dst: Tensor, h0: int, r: int) -> None:
+    """The inverse for gradients: head h0 of the receive buffer (P, S/P, B, Ht, D) [chunk p = rank p's partial of KV head
+    p // r over this rank's rows] -> dst (B, S/P, Hkv, D), head h = the sum of chunks h r .. h r + r - 1 (usp_sum_rows)."""
+    P, Sl, B, Ht, D = recv.shape
+    Hkv = dst.shape[2]
+    assert r > 1 and Hkv * r == P and dst.shape == (B, Sl, Hkv, D) and dst.stride(3) == 1 and h0 < Ht
+    src = recv.as_strided((1,), (1,), recv.storage_offset() + h0 * D)
+    base = dst.as_strided((1,), (1,), dst.storage_offset())
+    chunk = Sl * B * Ht * D
+    _sum_rows(base, src, D, r, chunk, (Hkv, Sl, B), (dst.stride(2), dst.stride(1), dst.stride(0)),
+              (r * chunk, B * Ht * D, Ht * D))
+
+
+def kv_heads_to_seq(x: Tensor, group, use_sync: bool = False, contiguous: bool = False) -> Tensor:
+    """heads_to_seq for K or V: (B, S/P, Hkv, D) -> (B, S, Hkv/P, D), or (B, S, 1, D) = KV head p // r on rank p when the
+    head is shared (kv_replicas)."""
+    P = dist.get_world_size(group)
+    r = kv_replicas(x.shape[2], P) if P > 1 else 1
+    if r <= 1:
+        return heads_to_seq(x, group, use_sync, contiguous)
+    B, Sl, _, D = x.shape
+    send = torch.empty((P, Sl, B, 1, D), dtype=x.dtype, device=x.device)
+    pack_kv_replicated(send, 0, x, r)
+    out = view_seq(_exchange(send, group, use_sync))
+    return out.contiguous() if contiguous else out
+
+
+def kv_seq_to_heads(x: Tensor, group, Hkv: int, use_sync: bool = False) -> Tensor:
+    """The gradient direction of kv_heads_to_seq: (B, S, h, D) -> (B, S/P, Hkv, D); with a shared head the r partials of
+    every KV head are summed (unpack_kv_sum)."""
+    P = dist.get_world_size(group)
+    r = kv_replicas(Hkv, P) if P > 1 else 1
+    if r <= 1:
+        return seq_to_heads(x, group, use_sync)
+    B, S, _, D = x.shape
+    recv = _exchange(pack_seq(x, P), group, use_sync)
+    out = torch.empty((B, S // P, Hkv, D), dtype=x.dtype, device=x.device)
+    unpack_kv_sum(recv, out, 0, r)
+    return out
+
+
+class SeqAllToAll4DKV(torch.autograd.Function):
+    """SeqAllToAll4D for K and V (same arguments): where the KV heads divide among the ranks (kv_replicas = 1) -- and for
+    any other direction or head count -- it IS SeqAllToAll4D (same collectives, launches and errors); where r ranks share a
+    head, the forward sends every rank its replica and the backward sums the r gradient partials of each head."""
+
+    @staticmethod
+    def forward(ctx: Any, group, input: Tensor, scatter_idx: int, gather_idx: int,
+                use_sync: bool = False, contiguous: bool = True) -> Tensor:
+        P = dist.get_world_size(group)
+        r = kv_replicas(input.shape[2], P) if P > 1 and (scatter_idx, gather_idx) == (2, 1) else 1
+        ctx.kv_heads = input.shape[2] if r > 1 else 0
+        if r <= 1:
+            return SeqAllToAll4D.forward(ctx, group, input, scatter_idx, gather_idx, use_sync, contiguous)
+        ctx.group, ctx.use_sync = group, use_sync
+        return kv_heads_to_seq(input, group, use_sync, contiguous)
+
+    @staticmethod
+    def backward(ctx: Any, *grad_output: Tensor) -> Tuple[None, Tensor, None, None, None, None]:
+        if not ctx.kv_heads:
+            return SeqAllToAll4D.backward(ctx, *grad_output)
+        return (None, kv_seq_to_heads(grad_output[0], ctx.group, ctx.kv_heads, ctx.use_sync), None, None, None, None)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // HBM-bound helper kernels of libusp_hip.so: backward delta, stand-alone LSE merge, the row-gather
-// copy behind the Ulysses all-to-all pack/unpack, fp32 -> 16-bit cast and fp32 add.
+// copy behind the Ulysses all-to-all pack/unpack, its r-term summing form (KV heads shared by r ranks),
+// fp32 -> 16-bit cast and fp32 add.
 // All are pure streaming kernels: 16-byte accesses per lane, grid-stride loops capped at
 // 256 CUs x 8 blocks (cdna_hip_programming.md Guideline 11/13).
 #include "usp_common.hpp"
@@ -120,6 +121,50 @@ __global__ __launch_bounds__(kEwThreads) void copy_rows_kernel(
   }
 }
 
+// ---- row-gather with an r-term sum -----------------------------------------------------------------
+// dst row = round(sum_t src row of term t), fp32 accumulation in ascending t: the dK/dV partials of the r Ulysses ranks
+// that share one KV head (comm/all_to_all.py:unpack_kv_sum).  Terms are loaded four at a time so that up to four 16-byte
+// reads per lane are in flight before the first add; the adds keep the ascending order.
+template <int DT>
+__global__ __launch_bounds__(kEwThreads) void sum_rows_kernel(
+    char* dst, const char* src, int64_t chunks_per_row, int64_t n1, int64_t n2, int64_t total_chunks, int r,
+    int64_t term_stride, int64_t ds0, int64_t ds1, int64_t ds2, int64_t ss0, int64_t ss1, int64_t ss2) {
+  for (int64_t i = (int64_t)blockIdx.x * kEwThreads + threadIdx.x; i < total_chunks;
+       i += (int64_t)gridDim.x * kEwThreads) {
+    const int64_t cc = i % chunks_per_row;
+    int64_t row = i / chunks_per_row;
+    const int64_t i2 = row % n2; row /= n2;
+    const int64_t i1 = row % n1;
+    const int64_t i0 = row / n1;
+    const char* sp = src + i0 * ss0 + i1 * ss1 + i2 * ss2 + 16 * cc;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    int t = 0;
+    for (; t + 4 <= r; t += 4) {
+      u32x4 w[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) w[j] = *(const u32x4*)(sp + (t + j) * term_stride);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float f[8];
+        unpack8<DT>(w[j], f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += f[e];
+      }
+    }
+    for (; t < r; ++t) {
+      float f[8];
+      unpack8<DT>(*(const u32x4*)(sp + t * term_stride), f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += f[e];
+    }
+    const u32x4 o = {Elem<DT>::pack2(acc[0], acc[1]), Elem<DT>::pack2(acc[2], acc[3]),
+                     Elem<DT>::pack2(acc[4], acc[5]), Elem<DT>::pack2(acc[6], acc[7])};
+    *(u32x4*)(dst + i0 * ds0 + i1 * ds1 + i2 * ds2 + 16 * cc) = o;
+  }
+}
+
 // ---- fp32 -> 16-bit cast ---------------------------------------------------------------------------
 template <int DT>
 __global__ __launch_bounds__(kEwThreads) void cast_kernel(char* dst, int64_t d_rs, const float* src,
@@ -229,6 +274,25 @@ extern "C" int usp_copy_rows(void* dst, const void* src, int64_t row_bytes, int6
   hipLaunchKernelGGL(copy_rows_kernel, dim3(ew_grid(total)), dim3(kEwThreads), 0,
                      (hipStream_t)stream, (char*)dst, (const char*)src, cpr, n1, n2, n3, total, ds0,
                      ds1, ds2, ds3, ss0, ss1, ss2, ss3);
+  return launched();
+}
+
+extern "C" int usp_sum_rows(int32_t dtype, void* dst, const void* src, int64_t row_bytes, int32_t r,
+                            int64_t term_stride, int64_t n0, int64_t n1, int64_t n2, int64_t ds0, int64_t ds1,
+                            int64_t ds2, int64_t ss0, int64_t ss1, int64_t ss2, void* stream) {
+  if (!dst || !src || row_bytes <= 0 || r <= 0 || n0 <= 0 || n1 <= 0 || n2 <= 0) return USP_EINVAL;
+  if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
+  const int64_t all = row_bytes | term_stride | ds0 | ds1 | ds2 | ss0 | ss1 | ss2;
+  if ((all & 15) || !al16(dst) || !al16(src)) return USP_EUNSUPPORTED;
+  const int64_t cpr = row_bytes / 16;
+  const int64_t total = cpr * n0 * n1 * n2;
+  const int grid = ew_grid(total);
+  if (dtype == USP_BF16)
+    hipLaunchKernelGGL(sum_rows_kernel<0>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream, (char*)dst,
+                       (const char*)src, cpr, n1, n2, total, (int)r, term_stride, ds0, ds1, ds2, ss0, ss1, ss2);
+  else
+    hipLaunchKernelGGL(sum_rows_kernel<1>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream, (char*)dst,
+                       (const char*)src, cpr, n1, n2, total, (int)r, term_stride, ds0, ds1, ds2, ss0, ss1, ss2);
   return launched();
 }
 

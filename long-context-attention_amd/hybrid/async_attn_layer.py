@@ -337,9 +337,11 @@ def fill_items(link_bound=False, k_split=False):
 
 def _link_bound(Hq, Hkv, P, B, S, D, itemsize, ring, causal):
     """Is the Ulysses exchange of one forward pass at least half as long as the attention it surrounds?  Every rank
-    sends 1/P of its local q|k|v to each of its P-1 peers over that peer's own link, and gets 1/P of the output back."""
+    sends 1/P of its local q|k|v to each of its P-1 peers over that peer's own link, and gets 1/P of the output back.
+    A KV head shared by r ranks (A.kv_replicas) travels r times."""
     rows = B * (S // P)                                              # local rows before the exchange
-    t_comm = rows * (2 * Hq + 2 * Hkv) * D * itemsize / P / (_LINK_BYTES_PER_S or link_bytes_per_s())
+    kv_sent = 2 * Hkv * max(1, A.kv_replicas(Hkv, P))
+    t_comm = rows * (2 * Hq + kv_sent) * D * itemsize / P / (_LINK_BYTES_PER_S or link_bytes_per_s())
     flops = 4.0 * B * (Hq // P) * S * (S * ring) * D * (0.5 if causal else 1.0)
     from ..comm.link import kernel_flops_per_s
     return t_comm >= 0.5 * flops / (_KERNEL_FLOPS_PER_S or kernel_flops_per_s())
@@ -351,8 +353,12 @@ def _groups(Hq, Hkv, P, B=None, S=None, max_groups=None, link_bound=False, k_spl
     size (B, S = sequence after the exchange) given, the pipeline is kept shallow enough that every group's
     attention launch still has `fill_items` 256-row work items (two per CU; one when the caller found the exchange long
     against the attention, `_link_bound`; half of one when, in addition, the forward kernel will cut such launches along
-    K, `k_split`)."""
-    assert Hq % P == 0 and Hkv % P == 0, f"heads ({Hq}, {Hkv}) not divisible by ulysses degree {P}"
+    K, `k_split`).  KV heads shared by r > 1 ranks (A.kv_replicas: Hkv < P, P % Hkv == 0): ONE group, the rank's one KV
+    head (a replica) and its Hq/P query heads -- one packed exchange in, one out."""
+    r = A.kv_replicas(Hkv, P)
+    assert Hq % P == 0 and r, f"heads ({Hq}, {Hkv}) not divisible by ulysses degree {P}"
+    if r > 1:
+        return 1, 1, Hq // P
     per_rank = Hkv // P
     ng = 1
     if P > 1:                       # nothing to hide without an exchange
@@ -380,9 +386,11 @@ def _qkv_to_seq(lane, q, k, v, P, ng, kvh, g, i, group):
     """ONE exchange for head group i of q, k and v (B, S/P, H{q,kv}, D): the send buffer is
     (P, S/P, B, kvh*g + 2*kvh, D) = [q heads | k heads | v heads] of (destination rank, group i) -- the
     GQA-capable form of the reference's packed exchange (async_attn_layer.py:100-128 stacks q|k|v of one head
-    per rank, which needs Hkv == Hq).  Returns ((q, k, v) as (B, S, h, D) strided views of the receive buffer,
-    event, the send buffer)."""
+    per rank, which needs Hkv == Hq).  KV heads shared by r > 1 ranks: destination p gets KV head p // r
+    (A.pack_kv_replicated).  Returns ((q, k, v) as (B, S, h, D) strided views of the receive buffer, event, the send
+    buffer)."""
     hq = kvh * g
+    r = A.kv_replicas(k.shape[2], P)
     send = None
     for x, h, h0 in ((q, hq, 0), (k, kvh, hq), (v, kvh, hq + kvh)):
         B, Sl, _, D = x.shape
@@ -390,7 +398,10 @@ def _qkv_to_seq(lane, q, k, v, P, ng, kvh, g, i, group):
             x = x.contiguous()
         if send is None:
             send = torch.empty((P, Sl, B, hq + 2 * kvh, D), dtype=x.dtype, device=x.device)
-        A.pack_head_group(x.view(B, Sl, P, ng, h, D)[:, :, :, i], send, h0)    # heads p*(ng*h) + i*h + (0..h)
+        if h0 and r > 1:
+            A.pack_kv_replicated(send, h0, x, r)
+        else:
+            A.pack_head_group(x.view(B, Sl, P, ng, h, D)[:, :, :, i], send, h0)    # heads p*(ng*h) + i*h + (0..h)
     recv, ev = lane.exchange(send, group)
     full = A.view_seq(recv)                                        # (B, S, hq + 2 kvh, D)
     return (full[:, :, :hq], full[:, :, hq:hq + kvh], full[:, :, hq + kvh:]), ev, send
@@ -424,7 +435,8 @@ def _to_heads_issue(lane, xs, P, group):
 
 def _grads_to_heads_issue(lane, dq, dk, dv, tail, P, group):
     """ONE exchange dq | dk | dv of a head group back to sequence sharding (dq None: dk | dv alone -- dq went ahead in an
-    exchange of its own, `dq_first`), with the ring backward's LAST dK/dV hop
+    exchange of its own, `dq_first`; with a KV head shared by r ranks dk | dv are this rank's partials, which the
+    sequence owners sum when they unpack, A.unpack_kv_sum), with the ring backward's LAST dK/dV hop
     still in flight (`tail`: the pending RingComm of travel_dkdv's `defer`): dq is packed on the compute stream, which
     then goes on to the next group's kernels; the lane waits for the hop, packs dk and dv behind it and runs the
     collective.  What the compute stream used to wait for (16 MiB of fp32 per KV head over one link, 0.26 ms at 64 GB/s
@@ -594,22 +606,30 @@ class _AsyncUSPFunc(torch.autograd.Function):
             dk = torch.empty((B, Sl, Hkv, D), dtype=dout.dtype, device=dout.device)
             dv = torch.empty_like(dk)
             q5 = dq.view(B, Sl, P, ng, kvh * g, D)
-            k5, v5 = dk.view(B, Sl, P, ng, kvh, D), dv.view(B, Sl, P, ng, kvh, D)
+            r = A.kv_replicas(Hkv, P)
+            if r == 1:
+                k5, v5 = dk.view(B, Sl, P, ng, kvh, D), dv.view(B, Sl, P, ng, kvh, D)
             hq = kvh * g
+
+            def unpack_kv(recv, h0, i):
+                if r > 1:                               # (one group) the r partials of every KV head, summed
+                    A.unpack_kv_sum(recv, dk, h0, r)
+                    A.unpack_kv_sum(recv, dv, h0 + kvh, r)
+                else:
+                    A.unpack_head_group(recv, k5[:, :, :, i], h0)
+                    A.unpack_head_group(recv, v5[:, :, :, i], h0 + kvh)
             for i, item in enumerate(pend):
                 if isinstance(item[0], tuple):          # (dq exchange, dk | dv exchange)
                     (rq, eq), (recv, ev) = item
                     lane.wait(eq)
                     A.unpack_head_group(rq, q5[:, :, :, i], 0)
                     lane.wait(ev)
-                    A.unpack_head_group(recv, k5[:, :, :, i], 0)
-                    A.unpack_head_group(recv, v5[:, :, :, i], kvh)
+                    unpack_kv(recv, 0, i)
                     continue
                 recv, ev = item
                 lane.wait(ev)
                 A.unpack_head_group(recv, q5[:, :, :, i], 0)
-                A.unpack_head_group(recv, k5[:, :, :, i], hq)
-                A.unpack_head_group(recv, v5[:, :, :, i], hq + kvh)
+                unpack_kv(recv, hq, i)
         return dq, dk, dv, None, None, None, None, None, None, None
 
 

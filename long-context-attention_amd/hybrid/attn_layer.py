@@ -15,7 +15,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from .._C import softcap_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll5D
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
@@ -103,7 +103,7 @@ class LongContextAttention(_USPLayer):
         if (self.scatter_idx, self.gather_idx) != (2, 1) or self.ring_impl_type not in _RING_FWD_BWD:
             return None
         P = self.ulysses_size
-        if query.shape[2] % P or key.shape[2] % P:
+        if query.shape[2] % P or not kv_replicas(key.shape[2], P):     # (KV heads shared by P / Hkv ranks: served)
             return None
         return _MAX_GROUPS if pipeline_mode(self.ring_size) else 1
 
@@ -130,9 +130,10 @@ class LongContextAttention(_USPLayer):
                                      deterministic, return_attn_probs)
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
-        # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d)
-        q, k, v = (SeqAllToAll4D.apply(self.ulysses_pg, t, self.scatter_idx, self.gather_idx, self.use_sync, False)
-                   for t in (query, key, value))
+        # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
+        # form (a KV head shared by several ranks travels to each of them, and their gradients are summed)
+        q, k, v = (fn.apply(self.ulysses_pg, t, self.scatter_idx, self.gather_idx, self.use_sync, False)
+                   for fn, t in ((SeqAllToAll4D, query), (SeqAllToAll4DKV, key), (SeqAllToAll4DKV, value)))
         context = _first(self.ring_attn_fn(q, k, v, attn_processor=self.attn_processor, **options))
         # ... and back: (bs, seq_len, heads/N, d) -> (bs, seq_len/N, heads, d)
         return SeqAllToAll4D.apply(self.ulysses_pg, context, self.gather_idx, self.scatter_idx, self.use_sync, False)

@@ -115,6 +115,9 @@ class HipBlockBackend:
     def copy_rows(self, dst, src, row_bytes, sizes, dst_strides, src_strides):
         _C.copy_rows(dst, src, row_bytes, sizes, dst_strides, src_strides)
 
+    def sum_rows(self, dst, src, row_bytes, r, term_stride, sizes, dst_strides, src_strides):
+        _C.sum_rows(dst, src, row_bytes, r, term_stride, sizes, dst_strides, src_strides)
+
 
 _BACKEND = HipBlockBackend()
 

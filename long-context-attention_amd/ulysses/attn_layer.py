@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from ..comm.all_to_all import SeqAllToAll4D
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV
 from ..kernels import AttnType, select_flash_attn_impl
 
 
@@ -26,8 +26,9 @@ class UlyssesAttention(torch.nn.Module):
         self.scatter_idx, self.gather_idx = scatter_idx, gather_idx
         self.attn_fn = select_flash_attn_impl(attn_type, stage="fwd-bwd")
 
-    def _to_heads(self, x: Tensor) -> Tensor:      # (bs, seq/N, heads, d) -> (bs, seq, heads/N, d)
-        return SeqAllToAll4D.apply(self.spg, x, self.scatter_idx, self.gather_idx, self.use_sync, False)
+    def _to_heads(self, x: Tensor, kv: bool = False) -> Tensor:      # (bs, seq/N, heads, d) -> (bs, seq, heads/N, d)
+        fn = SeqAllToAll4DKV if kv else SeqAllToAll4D            # (k, v: a KV head shared by several ranks is replicated)
+        return fn.apply(self.spg, x, self.scatter_idx, self.gather_idx, self.use_sync, False)
 
     def _to_seq(self, x: Tensor) -> Tensor:        # (bs, seq, heads/N, d) -> (bs, seq/N, heads, d)
         return SeqAllToAll4D.apply(self.spg, x, self.gather_idx, self.scatter_idx, self.use_sync, False)
@@ -35,7 +36,7 @@ class UlyssesAttention(torch.nn.Module):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any) -> Tensor:
-        q, k, v = (self._to_heads(t) for t in (query, key, value))
+        q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
                        softmax_scale=q.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale)

@@ -7,6 +7,7 @@ size, on the same side streams).  The result is the compute-only iteration of th
 config before any link time -- measurable on a 1-GPU box.
 
     python tools/rank_emulation.py --gpus 8 [--rank 0] [--iters 5] [--env USP_PIPELINE_ULYSSES=0]
+    python tools/rank_emulation.py --gpus 8 --ud 8 --rd 1 --impl basic      # another grid for the same workload
 """
 import argparse
 import os
@@ -63,6 +64,9 @@ def main():
     ap.add_argument("--rank", type=int, default=0)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--env", action="append", default=[])
+    ap.add_argument("--ud", type=int, default=None, help="ulysses degree (with --rd: a grid other than the workload's)")
+    ap.add_argument("--rd", type=int, default=None, help="ring degree")
+    ap.add_argument("--impl", default=None, help="ring implementation (default: the workload's)")
     args = ap.parse_args()
     for kv in args.env:
         k, v = kv.split("=", 1)
@@ -79,7 +83,13 @@ def main():
     fake = FakeDist()
     for mod in (A, AL, HL, RB, RS, U, RZ):
         mod.dist = fake
-    cfg = (bench.CONFIG_WORKLOADS if os.environ.get("USP_BENCH_WORKLOAD") == "configs" else bench.WORKLOADS)[args.gpus]
+    cfg = dict((bench.CONFIG_WORKLOADS if os.environ.get("USP_BENCH_WORKLOAD") == "configs" else bench.WORKLOADS)[args.gpus])
+    if args.ud is not None or args.rd is not None:
+        cfg["ud"], cfg["rd"] = args.ud or cfg["ud"], args.rd or cfg["rd"]
+        assert cfg["ud"] * cfg["rd"] == args.gpus, f"grid {cfg['ud']} x {cfg['rd']} is not {args.gpus} ranks"
+        cfg["name"] += f" -- grid overridden: ulysses={cfg['ud']} ring={cfg['rd']}"
+    if args.impl is not None:
+        cfg["impl"] = args.impl
     ud, rd = cfg["ud"], cfg["rd"]
     u_rank, r_rank = args.rank % ud, args.rank // ud
     Y.PROCESS_GROUP.ULYSSES_PG, Y.PROCESS_GROUP.RING_PG = Group(ud, u_rank), Group(rd, r_rank)
