@@ -302,8 +302,9 @@ static int device_cus() {
 // choice for A/B runs.
 static int dkdv_heads_of(const usp_bwd_args* a) {
   const int G = a->Hq / a->Hkv;
-  if (G <= 1) return 1;
+  // an explicit value must divide G whatever G is: MHA (G = 1) accepts 1 only, as usp_hip.h states
   if (a->dkdv_heads > 0) return (G % a->dkdv_heads == 0) ? a->dkdv_heads : -1;
+  if (G <= 1) return 1;
   if (a->seq_q || a->seq_k) return 1;
   static const int forced = [] { const char* e = getenv("USP_BWD_GSUB"); return e ? atoi(e) : 0; }();
   if (forced > 0) {

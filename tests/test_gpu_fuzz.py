@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from golden_util import TOL, assert_close, round_to
+from golden_util import TOL, assert_close, long_sum_atol, round_to
 from oracle import usp_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -120,18 +120,9 @@ def _run_dense(dev, rs, case):
     for a_, b_, n_ in zip(grads[0], grads[1], ("dq", "dk", "dv")):
         assert np.array_equal(a_, b_), f"{what}: {n_} differs between two launches"
     for g_, r_, n_ in zip(grads[0], (rdq, rdk, rdv), ("dq", "dk", "dv")):
-        # A gradient entry is a sum of N products whose 16-bit factors (P, dS) carry a relative rounding error of
-        # 2^-9 / sqrt(3) each: the absolute error of the SUM is about 1.1e-3 x rms(entry) per sigma, whatever the entry's own
-        # value -- an entry near a zero crossing of a tensor whose entries are ~20 (1000+ rows per key, ten keys: P is not
-        # small) misses `atol + rtol |want|` by 2x in the 8-wave AND the 64-row kernels alike.  So for LONG sums only
-        # (>= 1000 products per entry: dK / dV sum Sq * G rows, dQ sums Sk keys) the absolute part of the bound does not drop
-        # below ~7 sigma of that noise; every other case keeps the stated tolerance.  Pinned by
-        # tests/test_gpu_row64.py::test_long_sum_gradient_noise_is_that_of_16bit_products (both families miss the
-        # un-floored bound by the same amount on that case and pass it against 16-bit-rounded products).
+        # long sums of 16-bit-rounded products (dK / dV sum Sq * G rows, dQ sums Sk keys): golden_util.long_sum_atol
         atol, rtol = TOL[dt]["grad"]
-        n_sum = Sk if n_ == "dq" else Sq * (Hq // Hkv)
-        if n_sum >= 1000:
-            atol = max(atol, 8e-3 * float(np.sqrt(np.mean(np.square(r_, dtype=np.float64)))))
+        atol = long_sum_atol(atol, Sk if n_ == "dq" else Sq * (Hq // Hkv), r_)
         assert_close(g_, r_, atol, rtol, f"{what} {n_}")
 
 

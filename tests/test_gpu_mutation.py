@@ -153,6 +153,52 @@ def test_bench_sampled_parity_fails_on_nan(dev):
         assert not (err[name] < 1.0)
 
 
+@pytest.mark.parametrize("target,kind", [(FWD, "elem"), (FWD, "row"), (BWD_DQ, "row"), (BWD_DK, "elem"), (BWD_DV, "row")],
+                         ids=["out-elem", "out-row", "dq-row", "dk-elem", "dv-row"])
+def test_large_launch_family_fails_on_nan(dev, target, kind):
+    """The every-element checks at multi-pass launch sizes (tests/test_gpu_large_launch.py) can fail (case J: the cheapest
+    reference of the table)."""
+    import test_gpu_large_launch as LL
+    _must_fail(target, kind, LL.run_case, dev, LL._BY_ID["J"])
+
+
+@contextlib.contextmanager
+def copied_head_block(fn_name, arg_names):
+    """Patch yunchang_amd._C.<fn_name>: after the real launch, copy a 64-row block of head 1 over head 0 in the middle of
+    the sequence of the first result tensor among `arg_names` -- finite values, the image of an item walk that ran the wrong
+    head."""
+    from yunchang_amd import _C
+    real = getattr(_C, fn_name)
+    sig = inspect.signature(real)
+    fired = []
+
+    def wrapper(*args, **kwargs):
+        real(*args, **kwargs)
+        bound = sig.bind(*args, **kwargs)
+        for n in arg_names:
+            t = bound.arguments.get(n)
+            if t is not None:
+                torch.cuda.current_stream().synchronize()
+                mid = t.shape[1] // 2
+                t[:, mid:mid + 64, 0] = t[:, mid:mid + 64, 1]
+                fired.append(n)
+                break
+    setattr(_C, fn_name, wrapper)
+    try:
+        yield fired
+    finally:
+        setattr(_C, fn_name, real)
+
+
+@pytest.mark.parametrize("target", [FWD, BWD_DQ], ids=["out", "dq"])
+def test_large_launch_family_fails_on_a_wrong_head(dev, target):
+    import test_gpu_large_launch as LL
+    with copied_head_block(*target) as fired:
+        with pytest.raises(AssertionError):
+            LL.run_case(dev, LL._BY_ID["J"])
+    assert fired, f"the mutation of {target} never fired"
+
+
 def test_comparator_itself():
     """The comparator on host arrays (also covered without a GPU by tests/test_oracle_golden.py)."""
     want = np.array([1.0, -np.inf, 2.0])

@@ -49,6 +49,19 @@ def test_argument_validation_without_launch():
     assert L.usp_flash_fwd(ctypes.byref(a), None) == -1
     assert L.usp_copy_rows(addr, addr, 24, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, None) == -2
     assert L.usp_flash_bwd(None, None) == -1
+    # dkdv_heads (ABI v7) must divide Hq / Hkv.  The call is otherwise valid up to the family check: forced onto the 64-row
+    # family at head dim 64 it stops there with USP_EUNSUPPORTED (no launch), so a USP_EINVAL below is the dkdv_heads check.
+    b = _C.UspBwdArgs()
+    b.dtype, b.B, b.Sq, b.Sk, b.Hq, b.Hkv, b.D, b.causal, b.softmax_scale = 0, 1, 16, 16, 4, 1, 64, 1, 0.125
+    t = _C.UspTensor(addr, 0, 64, 64 * 4)
+    b.dout = b.q = b.dq16 = t
+    b.k = b.v = b.dk16 = b.dv16 = _C.UspTensor(addr, 0, 64, 64)
+    b.lse = b.delta = addr
+    b.flags = _C.USP_FORCE_ROW64
+    for heads, rc in ((0, -2), (2, -2), (4, -2), (3, -1), (8, -1), (-1, -1)):
+        b.dkdv_heads = heads
+        assert L.usp_flash_bwd(ctypes.byref(b), None) == rc, heads
+        assert L.usp_last_launch_kinds() == 0
 
 
 def test_attn_type_surface():
