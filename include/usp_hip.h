@@ -60,7 +60,18 @@ enum {
  *                     serve (head dim != 128, packed batch, window) returns USP_EUNSUPPORTED and launches nothing
  *                     (unforced, the library picks the 64-row forward K split only for long cuts);
  *   USP_FORCE_WAVE32  every flash kernel of the call comes from the 32-rows-per-wave family.
- * Both bits at once: USP_EINVAL.  usp_last_launch_kinds() reports what a call actually launched. */
+ * Both bits at once: USP_EINVAL.  usp_last_launch_kinds() reports what a call actually launched.
+ * Layouts the 64-row family serves (beyond the alignment every call needs): its LDS-DMA pieces XOR a swizzle into a per-lane
+ * byte offset whose row part must be a multiple of 256 bytes, and address 64 rows by 32-bit offsets, so
+ *   forward            k.stride_s % 128 == 0 (elements);  k.stride_s, v.stride_s < 2^24   (v.stride_s % 128 is NOT needed:
+ *                      the V pieces' offsets are sums -- tests/test_gpu_layouts.py::test_row64_stride_conditions_forward);
+ *   backward, dQ       k.stride_s % 128 == 0 and v.stride_s % 128 == 0;  both < 2^24;
+ *   backward, dK/dV    q.stride_s % 128 == 0 and dout.stride_s % 128 == 0;  both < 2^24;  fp16: softmax_scale * log2(e) <= 8.
+ * Any other layout: USP_EUNSUPPORTED with USP_FORCE_ROW64 (nothing is launched or written), the other family's kernel for
+ * that launch without it.  The 32-rows-per-wave family takes every aligned layout, with one bound: its dK/dV kernel
+ * addresses the rows of a head by a 32-bit byte offset, so Sq * q.stride_s * 2 and Sq * dout.stride_s * 2 must stay below
+ * 2^31 (USP_EUNSUPPORTED at or above it, when the 64-row dK/dV kernel does not take the launch).
+ * Pinned by tests/test_gpu_layouts.py (test_row64_stride_conditions_*, test_wave8_dkdv_32bit_offset_bound). */
 #define USP_FORCE_ROW64 4
 #define USP_FORCE_WAVE32 8
 /* usp_flash_bwd only (ABI v6): issue only one of the backward's two launches -- the dK/dV launch (+ its head / cut reduce)

@@ -436,10 +436,11 @@ def sched_block(device) -> torch.Tensor:
 
 def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scale: float,
                      causal: bool, lse, out=None, acc=None, merge_in: bool = False,
-                     final_begin: int = 0, final_end: int = 2, interleave: bool = False, softcap=None):
+                     final_begin: int = 0, final_end: int = 2, interleave: bool = False, softcap=None, sched: bool = True):
     """usp_flash_fwd in packed variable-length mode.  q/out/acc (T,Hq,D), k/v (T',Hkv,D), lse (Hq,T)
     fp32; seq_q/seq_k (num_seq,2) int32 device tables of (first_row, rows); final_begin/final_end
-    count half sequences (0,1,2); `softcap` as flash_fwd."""
+    count half sequences (0,1,2); `softcap` as flash_fwd.  `sched=False` passes no control block: the workgroups walk their
+    static item lists instead of the dynamic queue (include/usp_hip.h `sched`; tests and A/B runs)."""
     _require_cuda(q, k, v, lse, out, acc)
     cap = softcap_value(softcap)
     n = seq_q.shape[0]
@@ -453,7 +454,7 @@ def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scal
     a.merge_in = 1 if merge_in else 0
     a.final_begin, a.final_end = int(final_begin), int(final_end)
     a.seq_q, a.seq_k = _seq(seq_q, n), _seq(seq_k, n)
-    a.sched = sched_block(q.device).data_ptr()
+    a.sched = sched_block(q.device).data_ptr() if sched else None
     a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
     _set_softcap(a, cap)
     _check(load().usp_flash_fwd(ctypes.byref(a), _stream()), "usp_flash_fwd")
@@ -461,9 +462,10 @@ def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scal
 
 def flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q: int, max_k: int, dq, dk, dv,
                      softmax_scale: float, causal: bool, accum_dq=False, accum_dk=False,
-                     accum_dv=False, dq16=None, dk16=None, dv16=None, interleave: bool = False, softcap=None):
-    """usp_flash_bwd in packed variable-length mode (layouts as flash_fwd_packed; lse/delta (Hq,T); `softcap` as
-    flash_fwd)."""
+                     accum_dv=False, dq16=None, dk16=None, dv16=None, interleave: bool = False, softcap=None,
+                     sched: bool = True):
+    """usp_flash_bwd in packed variable-length mode (layouts as flash_fwd_packed; lse/delta (Hq,T); `softcap` and `sched`
+    as flash_fwd_packed)."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     n = seq_q.shape[0]
@@ -482,7 +484,7 @@ def flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q: int, max_k:
     a.dq16, a.dk16, a.dv16 = _t3(dq16), _t3(dk16), _t3(dv16)
     a.accum_dq, a.accum_dk, a.accum_dv = int(bool(accum_dq)), int(bool(accum_dk)), int(bool(accum_dv))
     a.seq_q, a.seq_k = _seq(seq_q, n), _seq(seq_k, n)
-    a.sched = sched_block(q.device).data_ptr()
+    a.sched = sched_block(q.device).data_ptr() if sched else None
     a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
     _set_softcap(a, cap)
     a.total_k = k.shape[0]

@@ -633,7 +633,10 @@ bool launch_fwd64(const FwdArgsT<true>& p_in, int dtype, bool causal, hipStream_
     return n;
   }();
   // the K pieces' swizzle is XORed into the per-lane byte offset (row part a multiple of 256 bytes); per-lane offsets and the
-  // pieces' scalar offsets are 32-bit: 64 rows of K / V must span less than 2^31 bytes
+  // pieces' scalar offsets are 32-bit: 64 rows of K / V must span less than 2^31 bytes.  V needs no 256-byte rows: v_voff and
+  // v_step are sums, nothing is XORed into them (unlike launch_dq64, whose V pieces are swizzled) -- a V with
+  // stride_s % 128 != 0 beside a K with stride_s % 128 == 0 is served bit-identically to the contiguous launch:
+  // tests/test_gpu_layouts.py::test_row64_stride_conditions_forward
   if ((p_in.k_ss * 2) % 256 != 0 || p_in.k_ss * 128 >= (1LL << 31) || p_in.v_ss * 128 >= (1LL << 31)) return false;
   if (p_in.win_on || p_in.seq_q) return false;
   const size_t lds = 2 * 2 * kBN * 128 * 2;

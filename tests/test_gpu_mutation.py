@@ -199,6 +199,48 @@ def test_large_launch_family_fails_on_a_wrong_head(dev, target):
     assert fired, f"the mutation of {target} never fired"
 
 
+@pytest.mark.parametrize("kind", ["nan", "head"])
+@pytest.mark.parametrize("target", ["out", "dq", "dk", "dv"])
+def test_layout_family_fails_on_an_injection_into_the_strided_run(dev, target, kind):
+    """The layout sweeps (tests/test_gpu_layouts.py) run every case contiguous and strided and compare the bits.  Here the
+    STRIDED run's result gets one NaN (a computed one, not the arena's sentinel: the "was it written" checks pass) or a
+    64-row block of head 1 copied over head 0 after the real launch: the unmodified runner must fail, in its bit comparison."""
+    import layout_util as LU
+    import test_gpu_layouts as G
+
+    class Injected(G.HipOps):
+        """The second flash call of the runner is the strided one."""
+        calls = fired = 0
+
+        def _inject(self, t):
+            self.calls += 1
+            if self.calls != 2:
+                return
+            torch.cuda.synchronize()
+            if kind == "nan":
+                t[0, -1, 0, 0] = float("nan")
+            else:
+                mid = t.shape[1] // 2
+                t[:, mid:mid + 64, 0] = t[:, mid:mid + 64, 1]
+            self.fired += 1
+
+        def fwd(self, q, k, v, scale, causal, lse, out=None, **kw):
+            G.HipOps.fwd(self, q, k, v, scale, causal, lse, out=out, **kw)
+            self._inject(out)
+
+        def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, *a, **kw):
+            G.HipOps.bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, *a, **kw)
+            self._inject({"dq": kw["dq16"], "dk": kw["dk16"], "dv": kw["dv16"]}[target])
+
+    case = LU.Case(2, 200, 260, 4, 2, 64, True, "bfloat16", family="wave32")
+    check = LU.check_fwd_case if target == "out" else LU.check_bwd_case
+    check(G.HipOps(), case, 5, dev)                            # the case itself passes
+    ops = Injected()
+    with pytest.raises(AssertionError, match="differ in their bits"):
+        check(ops, case, 5, dev)
+    assert ops.fired == 1, "the injection never fired"
+
+
 def test_comparator_itself():
     """The comparator on host arrays (also covered without a GPU by tests/test_oracle_golden.py)."""
     want = np.array([1.0, -np.inf, 2.0])

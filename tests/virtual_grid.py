@@ -214,9 +214,13 @@ class VirtualGridPairwise(VirtualGrid):
 
     def __init__(self, ud, rd, real_dist=None, jitter=None):
         super().__init__(ud, rd, real_dist)
-        import collections
         import queue
-        self.box = collections.defaultdict(queue.Queue)          # (src, dst) -> messages in posting order
+        # (src, dst) -> messages in posting order.  Every mailbox exists before the rank threads start: created on first
+        # use (a defaultdict) the sender and the receiver of a pair could both find the key missing, each make a queue,
+        # and the second store replaced the first -- the message sat in a queue nobody read and the grid "deadlocked"
+        # once in some hundred runs (more often on a loaded host) although every rank posted in the same order
+        ws = ud * rd
+        self.box = {(s, d): queue.Queue() for s in range(ws) for d in range(ws)}
         self.jitter = jitter
         self.aborted = threading.Event()
 
