@@ -18,17 +18,18 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
+from .. import _C
 from .._C import softcap_value
 from ..comm import all_to_all as A
-from ..comm.link import link_bytes_per_s
+from ..comm.link import device_cus, kernel_flops_per_s, link_bytes_per_s
 from ..kernels.attention import kernel_head_dim, pad_head_dim
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..ring.ring_flash_attn import ring_flash_attn_backward, ring_flash_attn_forward
 from ..ring.stripe_flash_attn import stripe_flash_attn_backward, stripe_flash_attn_forward
+from ..ring.front_end import _check_hot_path_args
 from ..ring.utils import _side_stream
-from ..ring.zigzag_ring_flash_attn import (_check_hot_path_args, zigzag_forward_phases, zigzag_ring_flash_attn_backward,
-                                           zigzag_ring_flash_attn_forward)
+from ..ring.zigzag_ring_flash_attn import zigzag_forward_phases, zigzag_ring_flash_attn_backward, zigzag_ring_flash_attn_forward
 
 _RING_FWD_BWD = {
     "basic": (ring_flash_attn_forward, ring_flash_attn_backward),
@@ -134,7 +135,7 @@ def self_chunk_mode(P: int, ring: int, causal, impl: str, rows_local: int) -> bo
     exchange (forward: 1/4 resp. 1/4 of the group's work in front of the wait; backward, where K and V are already there and
     only dO travels: 1/4 resp. 3/4).  That hides the one exchange of each pass nothing else can hide -- the first.
     At ring degree 1 (the 2-GPU grid) the ring function is ONE causal block, split here into two or three launches joined
-    by the kernel's fused LSE merge / fp32 accumulation (_split_first_forward / _split_first_backward).  Beside a zigzag
+    by the kernel's fused LSE merge / fp32 accumulation (ring/block_pieces.py: split_first_forward / _backward).  Beside a zigzag
     ring (the 8-GPU grid: ulysses 2 x ring 4) the same split applies to STEP 0 of the ring schedule -- the exchange
     delivers exactly one zigzag chunk, rank u = 0 owns the front chunk and u = 1 the back one -- and the ring's K/V
     transfers, which read the exchanged tensors, are posted behind the wait (ring/zigzag_ring_flash_attn.py: `first`).
@@ -161,8 +162,8 @@ def tails_mode(P: int, ring: int, causal, impl: str, rows_local: int, pipelined:
     gradient exchange's bytes at G = 8 -- travels beside the step's dK/dV launch (`dq_first`); what stays exposed is the last
     dK/dV hop and the small dk | dv exchange.  Ulysses degree 2 beside a zigzag ring (the 8-GPU grid), pipelined mode only (in
     the safe mode a second communicator must not start inside a ring pass), and at ring degree 1 (the 2-GPU grid), where the
-    last group's one causal block is issued in the layer as 2 n row-range launches (_tail_last_forward) and its backward dQ
-    first (_tail_last_backward); USP_TAILS=0 | n overrides (default 4)."""
+    last group's one causal block is issued as 2 n row-range launches (ring/block_pieces.py: tail_last_forward) and its backward
+    dQ first (tail_last_backward); USP_TAILS=0 | n overrides (default 4)."""
     mode = _COMM_OVERRIDE.get("tails", os.environ.get("USP_TAILS", "4"))
     n = int(mode)
     ok = P == 2 and bool(causal) and pipelined and (impl == "zigzag" if ring > 1 else impl in ("basic", "zigzag"))
@@ -177,7 +178,6 @@ def tails_mode(P: int, ring: int, causal, impl: str, rows_local: int, pipelined:
     # (2 GPUs, S16384 H16, two-head groups of 64 items) keeps its one launch per group, the metric's 2-GPU grid (1024 items per
     # chunk and group) gets 4 pieces, the 8-GPU grid (256 items per chunk, x 4 cuts per piece) gets 4.
     if chunk_items is not None:
-        from ..comm.link import device_cus
         per_cu = device_cus() // (8 if ring > 1 else 2)
         n = min(n, chunk_items // max(1, per_cu))
     return n if n > 1 else 0
@@ -199,97 +199,6 @@ def _self_views(send, u, splits):
         out.append(full[:, :, h0:h0 + h])
         h0 += h
     return out
-
-
-def _split_first_forward(be, u, selfs, full, wait, scale):
-    """The first head group's causal block at ring degree 1, ulysses degree 2, started on the self chunk (self_chunk_mode).
-    `selfs` = (q, k, v) of this rank's own rows (views of the send buffer), `full` = (q, k, v) over all 2c rows (views of the
-    receive buffer, valid behind `wait()`).  Returns (out, lse) as the ring forward would."""
-    qs, ks, vs = selfs
-    q, k, v = full
-    B, S, hq, D = q.shape
-    c = S // 2
-    out = torch.empty((B, S, hq, D), dtype=q.dtype, device=q.device)
-    lse = torch.empty((B, hq, S), dtype=torch.float32, device=q.device)
-    if u == 0:       # own rows [0, c): they see own keys only -- complete and final at once
-        be.fwd(qs, ks, vs, scale, True, lse[:, :, :c], out[:, :c])
-        wait()
-        be.fwd(q[:, c:], k, v, scale, True, lse[:, :, c:], out[:, c:])          # c rows x 2c keys, bottom-right causal
-    else:            # own rows [c, 2c): the diagonal block now, the peer's keys merged in behind the exchange
-        acc = torch.empty((B, c, hq, D), dtype=torch.float32, device=q.device)
-        be.fwd(qs, ks, vs, scale, True, lse[:, :, c:], None, acc, False, 0, 0)
-        wait()
-        be.fwd(q[:, c:], k[:, :c], v[:, :c], scale, False, lse[:, :, c:], out[:, c:], acc, True, 0, c)
-        be.fwd(q[:, :c], k[:, :c], v[:, :c], scale, True, lse[:, :, :c], out[:, :c])
-    return out, lse
-
-
-def _split_first_backward(be, u, do_self, do_full, wait, q, k, v, o, lse, scale):
-    """The backward of the same block: K, V, out and the LSE are there (saved), only dO travels -- the rows this rank owns
-    start at once, the peer's rows follow behind the exchange; dK / dV accumulate in fp32 across the two launches and are
-    rounded by the last one that touches a row.  Returns (dq, dk, dv) in q.dtype."""
-    B, S, hq, D = q.shape
-    kvh = k.shape[2]
-    c = S // 2
-    dev = q.device
-    delta = torch.empty((B, hq, S), dtype=torch.float32, device=dev)
-    dq = torch.empty((B, S, hq, D), dtype=q.dtype, device=dev)
-    dk = torch.empty((B, S, kvh, D), dtype=k.dtype, device=dev)
-    dv = torch.empty_like(dk)
-    dk32 = torch.empty((B, S, kvh, D), dtype=torch.float32, device=dev)
-    dv32 = torch.empty_like(dk32)
-    if u == 0:       # rows [0, c) x keys [0, c) first; then rows [c, 2c) x all keys on top
-        be.delta(do_self, o[:, :c], delta[:, :, :c])
-        dk32[:, c:].zero_()
-        dv32[:, c:].zero_()
-        be.bwd(do_self, q[:, :c], k[:, :c], v[:, :c], lse[:, :, :c], delta[:, :, :c], None, dk32[:, :c], dv32[:, :c], scale, True,
-               dq16=dq[:, :c])
-        wait()
-        be.delta(do_full[:, c:], o[:, c:], delta[:, :, c:])
-        be.bwd(do_full[:, c:], q[:, c:], k, v, lse[:, :, c:], delta[:, :, c:], None, dk32, dv32, scale, True,
-               accum_dk=True, accum_dv=True, dq16=dq[:, c:], dk16=dk, dv16=dv)
-    else:            # rows [c, 2c) x all keys first (3/4 of the block); then rows [0, c) x keys [0, c) on top
-        be.delta(do_self, o[:, c:], delta[:, :, c:])
-        be.bwd(do_self, q[:, c:], k, v, lse[:, :, c:], delta[:, :, c:], None, dk32, dv32, scale, True, dq16=dq[:, c:])
-        wait()
-        be.delta(do_full[:, :c], o[:, :c], delta[:, :, :c])
-        be.bwd(do_full[:, :c], q[:, :c], k[:, :c], v[:, :c], lse[:, :, :c], delta[:, :, :c], None, dk32[:, :c], dv32[:, :c], scale,
-               True, accum_dk=True, accum_dv=True, dq16=dq[:, :c], dk16=dk[:, :c], dv16=dv[:, :c])
-        be.cast(dk[:, c:], dk32[:, c:])              # keys [c, 2c) got gradients from the first launch only
-        be.cast(dv[:, c:], dv32[:, c:])
-    return dq, dk, dv
-
-
-def _tail_last_forward(be, q, k, v, scale, n, emit):
-    """The LAST head group's causal block at ring degree 1 (ulysses degree 2) in row pieces: piece j of the front chunk, piece j
-    of the back chunk (each a bottom-right-aligned causal launch over the keys its rows see), then `emit(j, out)` -- the piece's
-    output exchange runs beside the next piece's launches.  Same rows x keys as one launch; returns (out, lse)."""
-    B, S, hq, D = q.shape
-    c = S // 2
-    out = torch.empty((B, S, hq, D), dtype=q.dtype, device=q.device)
-    lse = torch.empty((B, hq, S), dtype=torch.float32, device=q.device)
-    for j in range(n):
-        for ch in (0, 1):
-            a, b = ch * c + j * c // n, ch * c + (j + 1) * c // n
-            if b > a:
-                be.fwd(q[:, a:b], k[:, :b], v[:, :b], scale, True, lse[:, :, a:b], out[:, a:b])
-        emit(j, out)
-    return out, lse
-
-
-def _tail_last_backward(be, dout, q, k, v, o, lse, scale, dq_first):
-    """... and its backward: delta, the dQ launch (rounded in its epilogue), `dq_first(dq)` -- dq travels beside the dK/dV launch
-    --, the dK/dV launch.  Returns (dq, dk, dv) in q.dtype."""
-    B, S, hq, D = q.shape
-    delta = torch.empty((B, hq, S), dtype=torch.float32, device=q.device)
-    dq = torch.empty((B, S, hq, D), dtype=q.dtype, device=q.device)
-    dk = torch.empty((B, S, k.shape[2], D), dtype=k.dtype, device=q.device)
-    dv = torch.empty_like(dk)
-    be.delta(dout, o, delta)
-    be.bwd(dout, q, k, v, lse, delta, None, None, None, scale, True, dq16=dq, only="dq")
-    dq_first(dq)
-    be.bwd(dout, q, k, v, lse, delta, None, None, None, scale, True, dk16=dk, dv16=dv, only="dkdv")
-    return dq, dk, dv
 
 
 # The default beside a ring.  Round 2 turned it on without any run through RCCL (ADVICE.md, round 2); round 3 first
@@ -330,7 +239,6 @@ def fill_items(link_bound=False, k_split=False):
     """Work items a head group's launch must still have (see the three per-CU figures above)."""
     if _FILL_ITEMS is not None:
         return _FILL_ITEMS
-    from ..comm.link import device_cus
     per_cu = _FILL_PER_CU if not link_bound else (_FILL_PER_CU_LINK_BOUND_KSPLIT if k_split else _FILL_PER_CU_LINK_BOUND)
     return max(1, int(per_cu * device_cus()))
 
@@ -343,7 +251,6 @@ def _link_bound(Hq, Hkv, P, B, S, D, itemsize, ring, causal):
     kv_sent = 2 * Hkv * max(1, A.kv_replicas(Hkv, P))
     t_comm = rows * (2 * Hq + kv_sent) * D * itemsize / P / (_LINK_BYTES_PER_S or link_bytes_per_s())
     flops = 4.0 * B * (Hq // P) * S * (S * ring) * D * (0.5 if causal else 1.0)
-    from ..comm.link import kernel_flops_per_s
     return t_comm >= 0.5 * flops / (_KERNEL_FLOPS_PER_S or kernel_flops_per_s())
 
 
@@ -376,7 +283,6 @@ def _groups(Hq, Hkv, P, B=None, S=None, max_groups=None, link_bound=False, k_spl
 def _k_split_groups(ctx, B, S, causal):
     """May the head groups be sized for launches the forward kernel cuts along K?  Only where that cut is on (the staged
     USP_FWD_KSPLIT policy answers for a 2-head launch of this length) and no backward will follow."""
-    from .. import _C
     if ctx is not None and any(ctx.needs_input_grad[:3]):
         return False
     return _C.fwd_k_splits(B, S, 2, bool(causal)) > 1
@@ -481,93 +387,77 @@ class _AsyncUSPFunc(torch.autograd.Function):
         overlap = ng > 1                # kernels run beside later groups' exchanges
         split0 = self_chunk_mode(P, ring, causal, impl, Sl)          # groups start on this rank's own rows
         u = dist.get_rank(ulysses_pg) if split0 else 0
+        # What each group gets, decided once.  `first` (the group starts on the rows this rank holds, in front of the wait for its
+        # exchange): the first group; beside a ring with USP_SELF_CHUNK=all every group (the first exchange of the pass takes
+        # longer than one group's owned chunk, and the other groups' owned chunks are the only other work that needs no exchanged
+        # byte -- self_chunk_all_groups for what that buys).  `tail` (the output leaves in row pieces): the last group -- unless
+        # that is the one group of a ring of degree 1 and starts on its own rows: the split owns that block, and its output
+        # and its gradients travel in one exchange each.
+        n_first = 0 if not split0 else (ng if ring > 1 and self_chunk_all_groups() else 1)
         n_tail = tails_mode(P, ring, causal, impl, Sl, ng_cap is None or ng_cap > 1, B * kvh * g * ((Sl + 255) // 256))
+        if ring == 1 and n_first == ng:
+            n_tail = 0
         saved, outs = [], []
         with _Lane(q) as lane:
             # every input exchange is queued before any attention runs
             ins = [_qkv_to_seq(lane, q, k, v, P, ng, kvh, g, i, ulysses_pg) for i in range(ng)]
             pieces = []                       # the last group's output exchange in row pieces: (recv, event, lo, hi)
 
-            def tail_of(i):
-                if not n_tail or i != ng - 1 or (ring == 1 and split0 and i == 0):     # (ring degree 1, one group: the self-chunk
-                    return None                                                      #  split owns that block)
+            def emit(j, out_i):               # piece j of both chunks is final on this stream: its exchange starts now
+                lo, hi = j * Sl // n_tail, (j + 1) * Sl // n_tail
+                if hi > lo:
+                    pieces.append(lane.exchange(A.pack_seq_rows(out_i, P, lo, hi), ulysses_pg) + (lo, hi))
 
-                def emit(j, out_i):           # piece j of both chunks is final on this stream: its exchange starts now
-                    lo, hi = j * Sl // n_tail, (j + 1) * Sl // n_tail
-                    if hi > lo:
-                        pieces.append(lane.exchange(A.pack_seq_rows(out_i, P, lo, hi), ulysses_pg) + (lo, hi))
-                return n_tail, emit
-            # Beside a ring the first group's owned chunk is launched before the first wait (round 5); USP_SELF_CHUNK=all: every
-            # group's (the first exchange of the pass takes longer than one group's owned chunk, and the other groups' owned
-            # chunks are the only other work that needs no exchanged byte -- self_chunk_all_groups for what that buys).
+            def pieces_of(i):                 # the `first` / `tail` arguments of group i's ring forward
+                (_, ev, send_i), kw = ins[i], {}
+                if i < n_first:
+                    kw["first"] = (u, _self_views(send_i, u, (kvh * g, kvh, kvh)), lambda: lane.wait(ev))
+                if n_tail and i == ng - 1:
+                    kw["tail"] = (n_tail, emit)
+                return kw
+            plan = [pieces_of(i) for i in range(ng)]
+            # Several groups start in front of the first wait: only the two-phase form of the forward can stop there.
             gens = {}
-            if split0 and ring > 1:
-                for i in range(ng if self_chunk_all_groups() else 1):
-                    (qi, ki, vi), ev, send_i = ins[i]
-                    own = _self_views(send_i, u, (kvh * g, kvh, kvh))
-                    gens[i] = zigzag_forward_phases(ring_pg, qi, ki, vi, softmax_scale, overlap,
-                                                    (u, own, lambda ev=ev: lane.wait(ev)), tail_of(i), softcap)
-                    next(gens[i])             # allocations + the launch on the owned chunk; stops in front of the wait
+            for i in range(n_first if n_first > 1 else 0):
+                gens[i] = zigzag_forward_phases(ring_pg, *ins[i][0], softmax_scale, overlap, plan[i]["first"], plan[i].get("tail"),
+                                                softcap)
+                next(gens[i])                 # allocations + the launch on the owned chunk; stops in front of the wait
             for i in range(ng):
-                (qi, ki, vi), ev, send_i = ins[i]
+                (qi, ki, vi), ev, _ = ins[i]
                 if i in gens:                 # the rest of the ring schedule, behind this group's exchange
                     try:
                         next(gens[i])
                         raise AssertionError("zigzag_forward_phases yields once")
                     except StopIteration as done:
                         oi, lse_i = done.value
-                elif split0 and i == 0:       # ring degree 1: the one causal block, split in the layer
-                    from ..kernels.attention import get_block_backend
-                    own = _self_views(send_i, u, (kvh * g, kvh, kvh))
-                    oi, lse_i = _split_first_forward(get_block_backend(beside_transfers=True, softcap=softcap), u, own, (qi, ki, vi),
-                                                     lambda ev=ev: lane.wait(ev), softmax_scale)
-                elif ring == 1 and tail_of(i) is not None:       # the 2-GPU grid: the last group's one causal block in row pieces
-                    from ..kernels.attention import get_block_backend
-                    lane.wait(ev)
-                    oi, lse_i = _tail_last_forward(get_block_backend(beside_transfers=True, softcap=softcap), qi, ki, vi, softmax_scale,
-                                                   *tail_of(i))
                 else:
-                    lane.wait(ev)
-                    t = tail_of(i)
-                    kw = {} if t is None else {"tail": t}
+                    if "first" not in plan[i]:          # (a group that starts on its own rows waits inside the ring forward)
+                        lane.wait(ev)
                     oi, lse_i = fwd(ring_pg, qi, ki, vi, softmax_scale=softmax_scale, causal=causal, softcap=softcap,
-                                    overlap=overlap, **kw)
+                                    overlap=overlap, **plan[i])
                 saved += [qi, ki, vi, oi, lse_i]
-                if tail_of(i) is not None:
-                    outs.append(None)         # (travelled in `pieces`)
-                else:
-                    outs.append(_to_heads_issue(lane, [oi], P, ulysses_pg))
+                # (a group with a tail: its output travelled in `pieces`)
+                outs.append(None if "tail" in plan[i] else _to_heads_issue(lane, [oi], P, ulysses_pg))
             out = torch.empty((B, Sl, Hq, D), dtype=q.dtype, device=q.device)
             o5 = out.view(B, Sl, P, ng, kvh * g, D)
             for i, pending in enumerate(outs):
-                if pending is None:
-                    for recv, ev, lo, hi in pieces:
-                        lane.wait(ev)
-                        A.unpack_head_group(recv, o5[:, lo:hi, :, i])
-                    continue
-                recv, ev = pending
-                lane.wait(ev)
-                A.unpack_head_group(recv, o5[:, :, :, i])
+                for recv, ev, lo, hi in (pieces if pending is None else [pending + (0, Sl)]):
+                    lane.wait(ev)
+                    A.unpack_head_group(recv, o5[:, lo:hi, :, i])
         ctx.save_for_backward(*saved)
-        ctx.meta = (softmax_scale, causal, ulysses_pg, ring_pg, impl, P, ng, kvh, g, Hq, Hkv)
-        ctx.split0 = (split0, u, ring)
-        ctx.n_tail = n_tail if tail_of(ng - 1) is not None else 0
-        ctx.softcap = softcap
+        ctx.meta = (softmax_scale, causal, ulysses_pg, ring_pg, impl, P, ng, kvh, g, Hq, Hkv, softcap, split0, u, n_tail)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        softmax_scale, causal, ulysses_pg, ring_pg, impl, P, ng, kvh, g, Hq, Hkv = ctx.meta
+        softmax_scale, causal, ulysses_pg, ring_pg, impl, P, ng, kvh, g, Hq, Hkv, softcap, split0, u, n_tail = ctx.meta
         _, bwd = _RING_FWD_BWD[impl]
-        softcap = ctx.softcap
         saved = ctx.saved_tensors
         B, Sl, _, D = dout.shape
         overlap = ng > 1
         with _Lane(dout) as lane:
             douts = [_to_seq(lane, dout, P, ng, kvh * g, i, ulysses_pg) for i in range(ng)]
-            pend = []
-            split0, u, ring = getattr(ctx, "split0", (False, 0, 1))
-            n_tail = getattr(ctx, "n_tail", 0)
+            pend = []                          # per group: (the dq exchange | None, the [dq |] dk | dv exchange)
             for i in range(ng):
                 qi, ki, vi, oi, lse_i = saved[5 * i:5 * i + 5]
                 doi, ev, send_i = douts[i]
@@ -575,33 +465,17 @@ class _AsyncUSPFunc(torch.autograd.Function):
                 dq_sent = []
                 if n_tail and i == ng - 1:     # the last group: dq leaves between the last step's two launches (tails_mode)
                     kw["dq_first"] = lambda dq16: dq_sent.append(_to_heads_issue(lane, [dq16], P, ulysses_pg))
-                if split0 and i == 0:
-                    from ..kernels.attention import get_block_backend
-                    do_own = _self_views(send_i, u, (kvh * g,))[0]
-                    tail = []
-                    if ring == 1:
-                        dqi, dki, dvi = _split_first_backward(get_block_backend(beside_transfers=True, softcap=softcap), u, do_own, doi,
-                                                              lambda ev=ev: lane.wait(ev), qi, ki, vi, oi, lse_i, softmax_scale)
-                    else:
-                        dqi, dki, dvi = bwd(ring_pg, doi, qi, ki, vi, oi, lse_i, softmax_scale=softmax_scale, causal=causal,
-                                            softcap=softcap, overlap=overlap, tail=tail,
-                                            first=(u, do_own, lambda ev=ev: lane.wait(ev)), **kw)
-                elif ring == 1 and kw:         # the 2-GPU grid's last group: dQ launch, dq exchange, dK/dV launch
-                    from ..kernels.attention import get_block_backend
-                    lane.wait(ev)
-                    tail = []
-                    dqi, dki, dvi = _tail_last_backward(get_block_backend(beside_transfers=True, softcap=softcap), doi, qi, ki, vi,
-                                                        oi, lse_i,
-                                                        softmax_scale, kw["dq_first"])
+                if split0 and i == 0:          # the first group starts on the rows whose dO this rank holds
+                    kw["first"] = (u, _self_views(send_i, u, (kvh * g,))[0], lambda ev=ev: lane.wait(ev))
                 else:
                     lane.wait(ev)
-                    tail = []                  # the ring backward's last dK/dV hop, left pending (ring/utils.py:travel_dkdv)
-                    dqi, dki, dvi = bwd(ring_pg, doi, qi, ki, vi, oi, lse_i, softmax_scale=softmax_scale,
-                                        causal=causal, softcap=softcap, overlap=overlap, tail=tail, **kw)
+                defer = []                     # the ring backward's last dK/dV hop, left pending (ring/utils.py:travel_dkdv)
+                dqi, dki, dvi = bwd(ring_pg, doi, qi, ki, vi, oi, lse_i, softmax_scale=softmax_scale, causal=causal,
+                                    softcap=softcap, overlap=overlap, defer=defer, **kw)
                 if dq_sent:                    # two exchanges: dq (posted inside the ring backward), then dk | dv
-                    pend.append((dq_sent[0], _grads_to_heads_issue(lane, None, dki, dvi, tail, P, ulysses_pg)))
-                else:
-                    pend.append(_grads_to_heads_issue(lane, dqi, dki, dvi, tail, P, ulysses_pg))   # ONE exchange: dq | dk | dv
+                    pend.append((dq_sent[0], _grads_to_heads_issue(lane, None, dki, dvi, defer, P, ulysses_pg)))
+                else:                          # ONE exchange: dq | dk | dv
+                    pend.append((None, _grads_to_heads_issue(lane, dqi, dki, dvi, defer, P, ulysses_pg)))
             dq = torch.empty((B, Sl, Hq, D), dtype=dout.dtype, device=dout.device)
             dk = torch.empty((B, Sl, Hkv, D), dtype=dout.dtype, device=dout.device)
             dv = torch.empty_like(dk)
@@ -609,27 +483,19 @@ class _AsyncUSPFunc(torch.autograd.Function):
             r = A.kv_replicas(Hkv, P)
             if r == 1:
                 k5, v5 = dk.view(B, Sl, P, ng, kvh, D), dv.view(B, Sl, P, ng, kvh, D)
-            hq = kvh * g
-
-            def unpack_kv(recv, h0, i):
+            for i, (dq_x, (recv, ev)) in enumerate(pend):
+                rq, eq = (recv, ev) if dq_x is None else dq_x
+                lane.wait(eq)
+                A.unpack_head_group(rq, q5[:, :, :, i], 0)
+                if dq_x is not None:
+                    lane.wait(ev)
+                h0 = kvh * g if dq_x is None else 0     # dk | dv lie behind dq where the three travelled together
                 if r > 1:                               # (one group) the r partials of every KV head, summed
                     A.unpack_kv_sum(recv, dk, h0, r)
                     A.unpack_kv_sum(recv, dv, h0 + kvh, r)
                 else:
                     A.unpack_head_group(recv, k5[:, :, :, i], h0)
                     A.unpack_head_group(recv, v5[:, :, :, i], h0 + kvh)
-            for i, item in enumerate(pend):
-                if isinstance(item[0], tuple):          # (dq exchange, dk | dv exchange)
-                    (rq, eq), (recv, ev) = item
-                    lane.wait(eq)
-                    A.unpack_head_group(rq, q5[:, :, :, i], 0)
-                    lane.wait(ev)
-                    unpack_kv(recv, 0, i)
-                    continue
-                recv, ev = item
-                lane.wait(ev)
-                A.unpack_head_group(recv, q5[:, :, :, i], 0)
-                unpack_kv(recv, hq, i)
         return dq, dk, dv, None, None, None, None, None, None, None
 
 

@@ -19,7 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..ring.zigzag_ring_flash_attn import _check_hot_path_args
+from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
 from .utils import RING_IMPL_DICT, RING_IMPL_QKVPACKED_DICT
 

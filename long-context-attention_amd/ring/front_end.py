@@ -1,0 +1,135 @@
+"""The public front end of every ring: ONE autograd Function and ONE *_func / *_kvpacked_func / *_qkvpacked_func trio,
+made per ring from its (forward, backward) pair.  The ring modules keep their schedules and bind their public names to what
+`ring_front_end` returns; the surfaces are the reference's (yunchang/ring/*.py), argument for argument."""
+import torch
+
+from .._C import softcap_value
+from ..kernels import AttnType
+from ..kernels.attention import kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
+from .varlen_utils import unflatten_lse
+
+
+def _check_hot_path_args(dropout_p, window_size, softcap):
+    """Refuses what the ring schedules do not serve.  softcap IS served (a per-score transform: every block launch carries
+    it, get_block_backend); a negative, NaN or infinite one raises ValueError (flash-attn ignores a negative one)."""
+    if dropout_p not in (0, 0.0):
+        raise NotImplementedError("dropout_p != 0 is not supported by the HIP ring attention")
+    if window_size is not None and tuple(window_size) != (-1, -1):
+        raise NotImplementedError("sliding-window attention is not supported by the HIP ring attention")
+    softcap_value(softcap)
+
+
+def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False):
+    """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
+
+        packed             the variable-length form: q / k / v are (T, H, D) token tensors followed by `cu_seqlens, max_seqlen`;
+                           k and v are made contiguous (the dense form takes any view the kernels can address, kernel_operand),
+                           there is no `attn_type`, and `return_attn_probs` hands the flattened (H, T) LSE back in the
+                           reference's padded (num_seq, H, max_seqlen) layout;
+        attn_processor     the Function carries `attn_processor` to the forward (the basic ring);
+        window_in_forward  `window_size` is judged by the forward, not here (the basic ring serves a window at ring degree 1
+                           and refuses beyond).
+    The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
+    grad; both exist here only."""
+    n_lead = 2 if packed else 0
+    extra = () if packed else (("attn_type", "attn_processor") if attn_processor else ("attn_type",))
+    n_args = n_lead + 9 + len(extra)
+
+    def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw):
+        """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse)."""
+        if softmax_scale is None:
+            softmax_scale = q.shape[-1] ** (-0.5)
+        assert alibi_slopes is None
+        _check_hot_path_args(dropout_p, (-1, -1) if window_in_forward else window_size, softcap)
+        if packed:
+            k, v = k.contiguous(), v.contiguous()
+        else:
+            q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
+        out, lse = forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+                           window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw)
+        return q, k, v, softmax_scale, out, lse
+
+    def result(out, lse, lead, return_softmax):
+        if not return_softmax:
+            return out
+        return out, (unflatten_lse(lse, *lead) if packed else lse), None
+
+    class Func(torch.autograd.Function):
+        """forward(ctx, q, k, v, [cu_seqlens, max_seqlen,] dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
+        deterministic, return_softmax, group[, attn_type[, attn_processor]])"""
+
+        @staticmethod
+        def forward(ctx, q, k, v, *args):
+            assert len(args) == n_args, f"{class_name}: {n_args + 3} arguments expected"
+            lead, extra_kw = args[:n_lead], dict(zip(extra, args[n_lead + 9:]))
+            dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, return_softmax, group = \
+                args[n_lead:n_lead + 9]
+            q, k, v, softmax_scale, out, lse = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap,
+                                                           alibi_slopes, group, extra_kw)
+            ctx.save_for_backward(q, k, v, out, lse, *lead[:1])                   # (cu_seqlens is a tensor)
+            extra_kw.pop("attn_processor", None)                                  # (the backwards take none)
+            ctx.call = (group, lead[1:], dict(softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+                                              window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes,
+                                              deterministic=deterministic, **extra_kw))
+            return result(out, lse, lead, return_softmax)
+
+        @staticmethod
+        def backward(ctx, dout, *args):
+            group, lead_rest, kw = ctx.call
+            if not packed:
+                dout = kernel_operand(dout)
+            return tuple(backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * n_args
+
+    Func.__name__ = Func.__qualname__ = class_name
+
+    if packed:
+        def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
+                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
+            return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
+                              alibi_slopes, deterministic, return_attn_probs, group)
+
+        def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
+                          window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
+                          group=None):
+            return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
+                              softcap, alibi_slopes, deterministic, return_attn_probs, group)
+
+        def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
+                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
+                           group=None):
+            return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
+                              window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group)
+    else:
+        def last(attn_type, processor=None):      # the Function's trailing arguments
+            return (attn_type, processor)[:len(extra)]
+
+        def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
+                 alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
+                 attn_type: AttnType = AttnType.HIP, attn_processor=None):
+            D = q.shape[-1]
+            if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
+                res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
+                           window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor)
+                return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
+            if not needs_grad(q, k, v):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
+                out, lse = run_forward(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group,
+                                       dict(zip(extra, last(attn_type, attn_processor))))[4:]
+                return result(out, lse, (), return_attn_probs)
+            return Func.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
+                              return_attn_probs, group, *last(attn_type, attn_processor))
+
+        def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
+                          alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
+                          attn_type: AttnType = AttnType.HIP):
+            return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
+                              deterministic, return_attn_probs, group, *last(attn_type))
+
+        def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
+                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
+                           attn_type: AttnType = AttnType.HIP):
+            return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
+                              alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type))
+
+    for fn, suffix in ((func, "_func"), (kvpacked_func, "_kvpacked_func"), (qkvpacked_func, "_qkvpacked_func")):
+        fn.__name__ = fn.__qualname__ = stem + suffix
+    return Func, func, kvpacked_func, qkvpacked_func

@@ -10,10 +10,10 @@ import torch
 import torch.distributed as dist
 
 from ..kernels import AttnType
-from ..kernels.attention import get_block_backend, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim, window_of
+from ..kernels.attention import get_block_backend, window_of
+from . import block_pieces
+from .front_end import ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
-from .zigzag_ring_flash_attn import _check_hot_path_args
-
 
 
 def _ring_window(window_size, P):
@@ -53,9 +53,15 @@ def basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, lse, delta, softmax
 
 def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                            attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False):
+                            attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None):
+    """`overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
+    zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
+    pieces = first is not None or tail is not None
+    assert not pieces or (P == 1 and causal and window_of(window_size) is None)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    if pieces:
+        return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
@@ -76,9 +82,15 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
 def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                              dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                              alibi_slopes=None, deterministic=False,
-                             attn_type: AttnType = AttnType.HIP, overlap=False, tail=None):
+                             attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None):
+    """`defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
+    ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
+    pieces = first is not None or dq_first is not None
+    assert not pieces or (P == 1 and causal and window_of(window_size) is None)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    if pieces:
+        return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S, H, D = q.shape
     dev = q.device
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)
@@ -100,84 +112,11 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
         be.add(dv_acc, dv_acc, dv_blk)
 
     # under causal only steps <= rank compute (:93-122)
-    dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=tail,
+    dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: None if (causal and step > rank) else FULL)
     return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
 
 
-class RingFlashAttnFunc(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                deterministic, return_softmax, group, attn_type, attn_processor):
-        if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
-        assert alibi_slopes is None
-        q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
-        _check_hot_path_args(dropout_p, (-1, -1), softcap)                    # (the window: ring_flash_attn_forward)
-        out, softmax_lse = ring_flash_attn_forward(
-            group, q, k, v, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-            window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False,
-            attn_type=attn_type, attn_processor=attn_processor)
-        ctx.save_for_backward(q, k, v, out, softmax_lse)
-        ctx.dropout_p = dropout_p
-        ctx.softmax_scale = softmax_scale
-        ctx.causal = causal
-        ctx.window_size = window_size
-        ctx.softcap = softcap
-        ctx.alibi_slopes = alibi_slopes
-        ctx.deterministic = deterministic
-        ctx.group = group
-        ctx.attn_type = attn_type
-        ctx.attn_processor = attn_processor
-        return out if not return_softmax else (out, softmax_lse, None)
-
-    @staticmethod
-    def backward(ctx, dout, *args):
-        dout = kernel_operand(dout)
-        q, k, v, out, softmax_lse = ctx.saved_tensors
-        dq, dk, dv = ring_flash_attn_backward(
-            ctx.group, dout, q, k, v, out, softmax_lse, softmax_scale=ctx.softmax_scale,
-            dropout_p=ctx.dropout_p, causal=ctx.causal, window_size=ctx.window_size,
-            softcap=ctx.softcap, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
-            attn_type=ctx.attn_type)
-        return dq, dk, dv, None, None, None, None, None, None, None, None, None, None, None
-
-
-def ring_flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False,
-                                   window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                   deterministic=False, return_attn_probs=False, group=None,
-                                   attn_type: AttnType = AttnType.HIP):
-    return RingFlashAttnFunc.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale,
-                                   causal, window_size, softcap, alibi_slopes, deterministic,
-                                   return_attn_probs, group, attn_type, None)
-
-
-def ring_flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False,
-                                  window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                  deterministic=False, return_attn_probs=False, group=None,
-                                  attn_type: AttnType = AttnType.HIP):
-    return RingFlashAttnFunc.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal,
-                                   window_size, softcap, alibi_slopes, deterministic,
-                                   return_attn_probs, group, attn_type, None)
-
-
-def ring_flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False,
-                         window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                         return_attn_probs=False, group=None, attn_type: AttnType = AttnType.HIP,
-                         attn_processor=None):
-    D = q.shape[-1]
-    if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
-        res = ring_flash_attn_func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
-                                   window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor)
-        return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
-    if not needs_grad(q, k, v):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
-        assert alibi_slopes is None
-        _check_hot_path_args(dropout_p, (-1, -1), softcap)
-        out, lse = ring_flash_attn_forward(
-            group, kernel_operand(q), kernel_operand(k), kernel_operand(v),
-            softmax_scale=q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale, causal=causal,
-            window_size=window_size, softcap=softcap, attn_type=attn_type, attn_processor=attn_processor)
-        return out if not return_attn_probs else (out, lse, None)
-    return RingFlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
-                                   alibi_slopes, deterministic, return_attn_probs, group, attn_type,
-                                   attn_processor)
+(RingFlashAttnFunc, ring_flash_attn_func, ring_flash_attn_kvpacked_func, ring_flash_attn_qkvpacked_func) = ring_front_end(
+    "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, attn_processor=True,
+    window_in_forward=True)

@@ -13,9 +13,9 @@ import torch
 import torch.distributed as dist
 
 from ..kernels import AttnType
-from ..kernels.attention import get_block_backend, kernel_head_dim, kernel_operand, pad_head_dim
+from ..kernels.attention import get_block_backend
+from .front_end import ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
-from .zigzag_ring_flash_attn import _check_hot_path_args
 
 
 def stripe_fwd_step(be, r, P, step, q, kk, vv, softmax_scale, lse, out, acc):
@@ -70,7 +70,7 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
 def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                                dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                                alibi_slopes=None, deterministic=False, attn_type: AttnType = AttnType.HIP,
-                               overlap=False, tail=None):
+                               overlap=False, defer=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, ring flash attn instead"
     P, r = group_info(dist, process_group)
     be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
@@ -93,74 +93,10 @@ def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, s
         stripe_bwd_fold(be, r, step, dk_acc, dv_acc, dk_blk, dv_blk)
 
     # steps > rank see k[:, :-1] only (:137-160, :179-181); a one-token shard has nothing to do there
-    dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=tail,
+    dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: FULL if step <= rank else (slice(0, S - 1) if S > 1 else None))
     return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
 
 
-class StripeFlashAttnFunc(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                deterministic, return_softmax, group, attn_type):
-        if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
-        assert alibi_slopes is None
-        q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
-        _check_hot_path_args(dropout_p, window_size, softcap)
-        out, softmax_lse = stripe_flash_attn_forward(
-            group, q, k, v, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-            window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False,
-            attn_type=attn_type)
-        ctx.save_for_backward(q, k, v, out, softmax_lse)
-        ctx.dropout_p = dropout_p
-        ctx.softmax_scale = softmax_scale
-        ctx.causal = causal
-        ctx.window_size = window_size
-        ctx.softcap = softcap
-        ctx.alibi_slopes = alibi_slopes
-        ctx.deterministic = deterministic
-        ctx.group = group
-        ctx.attn_type = attn_type
-        return out if not return_softmax else (out, softmax_lse, None)
-
-    @staticmethod
-    def backward(ctx, dout, *args):
-        dout = kernel_operand(dout)
-        q, k, v, out, softmax_lse = ctx.saved_tensors
-        dq, dk, dv = stripe_flash_attn_backward(
-            ctx.group, dout, q, k, v, out, softmax_lse, softmax_scale=ctx.softmax_scale,
-            dropout_p=ctx.dropout_p, causal=ctx.causal, window_size=ctx.window_size,
-            softcap=ctx.softcap, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
-            attn_type=ctx.attn_type)
-        return dq, dk, dv, None, None, None, None, None, None, None, None, None, None
-
-
-def stripe_flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False,
-                                     window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                     deterministic=False, return_attn_probs=False, group=None,
-                                     attn_type: AttnType = AttnType.HIP):
-    return StripeFlashAttnFunc.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale,
-                                     causal, window_size, softcap, alibi_slopes, deterministic,
-                                     return_attn_probs, group, attn_type)
-
-
-def stripe_flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False,
-                                    window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                    deterministic=False, return_attn_probs=False, group=None,
-                                    attn_type: AttnType = AttnType.HIP):
-    return StripeFlashAttnFunc.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal,
-                                     window_size, softcap, alibi_slopes, deterministic,
-                                     return_attn_probs, group, attn_type)
-
-
-def stripe_flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False,
-                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                           return_attn_probs=False, group=None, attn_type: AttnType = AttnType.HIP,
-                           attn_processor=None):
-    D = q.shape[-1]
-    if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
-        res = stripe_flash_attn_func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
-                                     window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor)
-        return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
-    return StripeFlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap,
-                                     alibi_slopes, deterministic, return_attn_probs, group, attn_type)
+(StripeFlashAttnFunc, stripe_flash_attn_func, stripe_flash_attn_kvpacked_func, stripe_flash_attn_qkvpacked_func) = ring_front_end(
+    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward)

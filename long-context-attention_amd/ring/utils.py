@@ -6,6 +6,7 @@ xGMI on ROCm; gloo on CPU for the orchestration tests).
 """
 import os
 from collections import OrderedDict
+from contextlib import nullcontext
 from typing import List, Optional, Tuple
 
 import torch
@@ -79,7 +80,8 @@ def group_info(dist_mod, process_group):
 
 class RingComm:
     """ring/utils.py:118-161.  send_recv queues an isend to ring rank+1 and an irecv from ring
-    rank-1; commit posts them as one batch; wait blocks (stream-wise on a GPU) until done."""
+    rank-1; commit posts them as one batch; wait blocks (stream-wise on a GPU) until done.  `send` / `recv` queue one
+    transfer to / from ANY ring rank (taken modulo the ring degree) for the mesh transports."""
 
     def __init__(self, process_group: dist.ProcessGroup):
         self._process_group = process_group
@@ -98,6 +100,16 @@ class RingComm:
         self._ops.append(dist.P2POp(dist.isend, to_send, self.send_rank, group=self._process_group))
         self._ops.append(dist.P2POp(dist.irecv, res, self.recv_rank, group=self._process_group))
         return res
+
+    def _global(self, ring_rank: int) -> int:
+        ring_rank %= self.world_size
+        return ring_rank if self._process_group is None else dist.get_global_rank(self._process_group, ring_rank)
+
+    def send(self, tensor: torch.Tensor, ring_rank: int):
+        self._ops.append(dist.P2POp(dist.isend, tensor, self._global(ring_rank), group=self._process_group))
+
+    def recv(self, tensor: torch.Tensor, ring_rank: int):
+        self._ops.append(dist.P2POp(dist.irecv, tensor, self._global(ring_rank), group=self._process_group))
 
     def commit(self):
         if self._reqs is not None:
@@ -194,19 +206,17 @@ class KVRelay:
         self._pending = None
         cuda = k.is_cuda
         recv = self._recv_slots(k, v, dist.get_rank(process_group))
-        ctx = torch.cuda.stream(self._stream) if cuda else _NullCtx()
+        ctx = torch.cuda.stream(self._stream) if cuda else nullcontext()
         if kv_relay_mode(self.P) == "direct":
             with ctx:
                 r = dist.get_rank(process_group)
-                to_global = lambda i: dist.get_global_rank(process_group, i % self.P) if process_group is not None else i % self.P
                 comm = RingComm(process_group)          # one grouped send/recv to and from every peer
                 for s in range(1, self.P):
                     nk, nv = recv[s - 1]
-                    dst, src = to_global(r + s), to_global(r - s)
-                    comm._ops += [dist.P2POp(dist.isend, k, dst, group=process_group),
-                                  dist.P2POp(dist.irecv, nk, src, group=process_group),
-                                  dist.P2POp(dist.isend, v, dst, group=process_group),
-                                  dist.P2POp(dist.irecv, nv, src, group=process_group)]
+                    comm.send(k, r + s)
+                    comm.recv(nk, r - s)
+                    comm.send(v, r + s)
+                    comm.recv(nv, r - s)
                     self.slots.append((nk, nv))
                 comm.commit()
                 comm.wait()
@@ -338,17 +348,17 @@ class ZigzagKVFetch:
             self._pending = None
         P, r, W = self.P, self.r, self.pieces
         slots, cuda = self.slots, self._stream is not None
-        to_global = lambda i: dist.get_global_rank(process_group, i % P) if process_group is not None else i % P
-        with (torch.cuda.stream(self._stream) if cuda else _NullCtx()):
+        with (torch.cuda.stream(self._stream) if cuda else nullcontext()):
             for w in range(first, upto):
                 send_steps, recv_steps = zigzag_wave_steps(P, r, w < W)
                 comm = RingComm(process_group)
                 for s in range(1, P):
                     if s in send_steps:
-                        comm._ops += [dist.P2POp(dist.isend, t, to_global(r + s), group=process_group) for t in mine[w]]
+                        for t in mine[w]:
+                            comm.send(t, r + s)
                     if s in recv_steps:
-                        comm._ops += [dist.P2POp(dist.irecv, t, to_global(r - s), group=process_group)
-                                      for t in slots[w][s - 1]]
+                        for t in slots[w][s - 1]:
+                            comm.recv(t, r - s)
                 comm.commit()
                 comm.wait()
                 if cuda:
@@ -537,7 +547,6 @@ def return_dkdv_direct(process_group, k, v, block, extent, be, zero: bool = Fals
     r = dist.get_rank(process_group)
     new = (lambda shape, dev: torch.zeros(shape, dtype=torch.float32, device=dev)) if zero else \
           (lambda shape, dev: torch.empty(shape, dtype=torch.float32, device=dev))
-    to_global = (lambda i: dist.get_global_rank(process_group, i % P)) if process_group is not None else (lambda i: i % P)
 
     def rows(t, sl):                                    # the rows of a block that carry gradients
         return t if sl == FULL else t[:, sl]
@@ -559,12 +568,14 @@ def return_dkdv_direct(process_group, k, v, block, extent, be, zero: bool = Fals
                 dk_blk, dv_blk = new(k.shape, k.device), new(v.shape, v.device)      # one pair per step: the send
                 block(step, kk, vv, dk_blk, dv_blk)                                  # reads it beside later steps
                 keep = (wire(dk_blk, out_sl), wire(dv_blk, out_sl))
-                comm._ops += [dist.P2POp(dist.isend, t, to_global(r - step), group=process_group) for t in keep]
+                for t in keep:
+                    comm.send(t, r - step)
             got = None
             if in_sl is not None:
                 got = tuple(new(rows(t, in_sl).shape, t.device) for t in (k, v))
-                comm._ops += [dist.P2POp(dist.irecv, t, to_global(r + step), group=process_group) for t in got]
-            if comm._ops:
+                for t in got:
+                    comm.recv(t, r + step)
+            if keep is not None or got is not None:
                 comm.commit()
                 pending.append((comm, in_sl, got, keep))
         for comm, in_sl, got, _keep in pending:         # step order == the relay's summation order
@@ -588,14 +599,6 @@ def final_grads(be, refs, accs):
         be.cast(g, acc)
         out.append(g)
     return tuple(out)
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 _SIDE_STREAMS = {}

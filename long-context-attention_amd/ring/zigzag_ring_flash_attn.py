@@ -18,14 +18,16 @@ MI355X-first differences (results identical up to fp32 rounding order):
     16-bit dq/dk/dv buffers + fp32 adds of :115-170;
   * K/V are relayed ahead of the kernels on a side HIP stream (ring/utils.py KVRelay).
 """
+import os
+
 import torch
 import torch.distributed as dist
 
-from .._C import softcap_value
 from ..kernels import AttnType
-from ..kernels.attention import get_block_backend, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
+from ..kernels.attention import get_block_backend
+from . import block_pieces
+from .front_end import _check_hot_path_args, ring_front_end      # (_check_hot_path_args: still importable from here)
 from .utils import FULL, KVRelay, group_info, ZigzagKVFetch, final_grads, kv_relay_mode, travel_dkdv, zigzag_fetch_pieces
-
 
 
 def zigzag_fwd_step(be, r, P, step, q, kk, vv, softmax_scale, lse, out, acc):
@@ -124,7 +126,6 @@ def zigzag_bwd_block(be, r, P, step, dout, q, kk, vv, lse, delta, softmax_scale,
 def split_steps() -> bool:
     """USP_BWD_SPLIT_STEPS=0: one dK/dV + dQ call per ring step as in rounds 1-5 (A/B switch; the default issues the dQ launch of
     a step behind the posting of the step's hop)."""
-    import os
     return os.environ.get("USP_BWD_SPLIT_STEPS", "1") != "0"
 
 
@@ -200,14 +201,18 @@ def _final_rows(be, q, kp, vp, softmax_scale, lse, out, acc, lo, hi, tail):
 
 
 def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None):
-    """The zigzag ring forward as a generator of two phases.  With `first` it yields ONCE, behind the launch on the owned chunk
-    and in front of the wait for the caller's exchange -- the caller may start other head groups' owned chunks there -- and
-    returns (out, lse) through StopIteration; without `first` it never yields.  zigzag_ring_flash_attn_forward drives it to the end.
+    """The zigzag ring forward as a generator of two phases.  With `first` beside a ring (degree > 1) it yields ONCE, behind the
+    launch on the owned chunk and in front of the wait for the caller's exchange -- the caller may start other head groups' owned
+    chunks there -- and returns (out, lse) through StopIteration; otherwise it never yields.  zigzag_ring_flash_attn_forward drives it
+    to the end.
     `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same."""
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
+    pieces = first is not None or tail is not None          # (the caller has exchanges in flight by definition)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
     B, S2, H, D = q.shape
     assert S2 % 2 == 0, "zigzag layout needs an even local sequence length"
+    if P == 1 and pieces:
+        return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     dev = q.device
     out = torch.empty((B, S2, H, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, S2), dtype=torch.float32, device=dev)
@@ -264,9 +269,10 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
     `first` = (u, (q, k, v) of the owned chunk, wait): q / k / v are still in flight (the caller's Ulysses exchange at degree
     2; `wait()` orders the calling stream behind it) and step 0 starts on the chunk this rank owns (zigzag_fwd_step0_own).
     The K/V transfers of the ring are posted BEHIND the wait -- they read the exchanged k / v -- i.e. no later than without
-    the split, where everything waits for the exchange.  Ring degree > 1 only (degree 1: _split_first_forward).
-    `tail` = (n, emit): the launch that finalises the last rows runs in n row pieces, `emit(j, out)` behind piece j (_final_rows);
-    ring degree > 1 only."""
+    the split, where everything waits for the exchange.
+    `tail` = (n, emit): the launch that finalises the last rows runs in n row pieces, `emit(j, out)` behind piece j (_final_rows).
+    At ring degree 1 the ring is ONE causal block and both are served by ring/block_pieces.py (`first` where both are given).
+    Either one means transfers in flight: the kernels are launched as under `overlap`."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap)
     try:
@@ -279,27 +285,32 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
 def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                                     dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                                     alibi_slopes=None, deterministic=False,
-                                    attn_type: AttnType = AttnType.HIP, overlap=False, tail=None, first=None, dq_first=None):
+                                    attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None):
     """`dq_first(dq)`: the LAST ring step issues its dQ launch in front of its dK/dV launch and rounds dQ in that launch's
     epilogue (rows the step does not touch are cast from the accumulator); `dq_first` is called with the final 16-bit dq
     between the two launches, so that the caller's exchange of dq -- most of the bytes of the gradient exchange -- runs beside
-    the dK/dV launch instead of behind the whole step.  Ring degree > 1 only.
+    the dK/dV launch instead of behind the whole step.
     `first` = (u, dO of the owned chunk, wait): dO is still in flight (see the forward); step 0 starts on the owned
-    rows (zigzag_bwd_step0_split).  Ring degree > 1 only.  Ordering differs from the forward's: k and v are SAVED tensors
+    rows (zigzag_bwd_step0_split).  Ordering differs from the forward's: k and v are SAVED tensors
     here, so travel_dkdv enters the K/V relay -- which posts the ring's transfers -- BEFORE block(0) calls `wait()` on the dO
     exchange; the ring's and the Ulysses communicator therefore have transfers in flight together from step 0 on (in the forward
     the ring's transfers read exchanged tensors and are posted behind the wait).  Correct either way -- nothing the relay moves
     depends on dO -- and exercised through RCCL on one-device virtual grids only (tests/test_gpu_rccl_order.py); a first run on
-    real devices that stalls here should set USP_SELF_CHUNK=0."""
+    real devices that stalls here should set USP_SELF_CHUNK=0.
+    At ring degree 1 both are served by ring/block_pieces.py; with both given `first` wins and `dq_first` is never called (dq comes
+    back with dk and dv).  Either one means transfers in flight: the kernels are launched as under `overlap`.
+    `defer`: travel_dkdv's list for the pending last hop."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
+    pieces = first is not None or dq_first is not None      # (the caller has exchanges in flight by definition)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    if P == 1 and pieces:
+        return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S2, H, D = q.shape
     c = S2 // 2
     dev = q.device
     lse = softmax_lse
     delta = torch.empty((B, H, S2), dtype=torch.float32, device=dev)
-    assert first is None or P > 1
     if first is None:
         be.delta(dout, out, delta)
     if P == 1:   # one block: the kernels round the gradients to q.dtype in their epilogues
@@ -339,93 +350,11 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
         zigzag_bwd_fold(be, r, step, c, dk_acc, dv_acc, dk_blk, dv_blk)
 
     # steps s <= rank carry gradients for the front-half K/V rows only (:151-155, :161-170)
-    dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=tail,
+    dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: slice(0, c) if step <= rank else FULL, split_block=split_steps())
     return final_grads(be, (q, k, v), (dq_done[0] if dq_done else dq_acc, dk_acc, dv_acc))
 
 
-class ZigZagRingFlashAttnFunc(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                deterministic, return_softmax, group, attn_type):
-        if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
-        assert alibi_slopes is None
-        q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
-        _check_hot_path_args(dropout_p, window_size, softcap)
-        out, softmax_lse = zigzag_ring_flash_attn_forward(
-            group, q, k, v, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-            window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False,
-            attn_type=attn_type)
-        ctx.save_for_backward(q, k, v, out, softmax_lse)
-        ctx.dropout_p = dropout_p
-        ctx.softmax_scale = softmax_scale
-        ctx.causal = causal
-        ctx.window_size = window_size
-        ctx.softcap = softcap
-        ctx.alibi_slopes = alibi_slopes
-        ctx.deterministic = deterministic
-        ctx.group = group
-        ctx.attn_type = attn_type
-        return out if not return_softmax else (out, softmax_lse, None)
-
-    @staticmethod
-    def backward(ctx, dout, *args):
-        dout = kernel_operand(dout)
-        q, k, v, out, softmax_lse = ctx.saved_tensors
-        dq, dk, dv = zigzag_ring_flash_attn_backward(
-            ctx.group, dout, q, k, v, out, softmax_lse, softmax_scale=ctx.softmax_scale,
-            dropout_p=ctx.dropout_p, causal=ctx.causal, window_size=ctx.window_size,
-            softcap=ctx.softcap, alibi_slopes=ctx.alibi_slopes, deterministic=ctx.deterministic,
-            attn_type=ctx.attn_type)
-        return dq, dk, dv, None, None, None, None, None, None, None, None, None, None
-
-
-def _check_hot_path_args(dropout_p, window_size, softcap):
-    """Refuses what the ring schedules do not serve.  softcap IS served (a per-score transform: every block launch carries
-    it, get_block_backend); a negative, NaN or infinite one raises ValueError (flash-attn ignores a negative one)."""
-    if dropout_p not in (0, 0.0):
-        raise NotImplementedError("dropout_p != 0 is not supported by the HIP ring attention")
-    if window_size is not None and tuple(window_size) != (-1, -1):
-        raise NotImplementedError("sliding-window attention is not supported by the HIP ring attention")
-    softcap_value(softcap)
-
-
-def zigzag_ring_flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False,
-                                          window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                          deterministic=False, return_attn_probs=False, group=None,
-                                          attn_type: AttnType = AttnType.HIP):
-    return ZigZagRingFlashAttnFunc.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p,
-                                         softmax_scale, causal, window_size, softcap, alibi_slopes,
-                                         deterministic, return_attn_probs, group, attn_type)
-
-
-def zigzag_ring_flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False,
-                                         window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                         deterministic=False, return_attn_probs=False, group=None,
-                                         attn_type: AttnType = AttnType.HIP):
-    return ZigZagRingFlashAttnFunc.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale,
-                                         causal, window_size, softcap, alibi_slopes, deterministic,
-                                         return_attn_probs, group, attn_type)
-
-
-def zigzag_ring_flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False,
-                                window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                deterministic=False, return_attn_probs=False, group=None,
-                                attn_type: AttnType = AttnType.HIP, attn_processor=None):
-    D = q.shape[-1]
-    if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
-        res = zigzag_ring_flash_attn_func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
-                                          window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor)
-        return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
-    if not needs_grad(q, k, v):      # inference / forward-only benchmarks: no autograd node, no saved tensors
-        assert alibi_slopes is None
-        _check_hot_path_args(dropout_p, window_size, softcap)
-        out, lse = zigzag_ring_flash_attn_forward(
-            group, kernel_operand(q), kernel_operand(k), kernel_operand(v),
-            softmax_scale=q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale, causal=causal,
-            softcap=softcap, attn_type=attn_type)
-        return out if not return_attn_probs else (out, lse, None)
-    return ZigZagRingFlashAttnFunc.apply(q, k, v, dropout_p, softmax_scale, causal, window_size,
-                                         softcap, alibi_slopes, deterministic, return_attn_probs,
-                                         group, attn_type)
+(ZigZagRingFlashAttnFunc, zigzag_ring_flash_attn_func, zigzag_ring_flash_attn_kvpacked_func,
+ zigzag_ring_flash_attn_qkvpacked_func) = ring_front_end(
+    "zigzag_ring_flash_attn", "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward)

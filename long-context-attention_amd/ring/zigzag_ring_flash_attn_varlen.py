@@ -23,9 +23,9 @@ import torch
 import torch.distributed as dist
 
 from ..kernels.attention import get_block_backend
+from .front_end import ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
-from .varlen_utils import SeqTables, unflatten_lse
-from .zigzag_ring_flash_attn import _check_hot_path_args
+from .varlen_utils import SeqTables
 
 
 def zigzag_varlen_fwd_step(be, r, P, step, tb: SeqTables, q, kk, vv, softmax_scale, lse, out, acc):
@@ -117,67 +117,6 @@ def zigzag_ring_flash_attn_varlen_backward(process_group, dout, q, k, v, out, so
     return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
 
 
-class ZigZagRingFlashAttnVarlenFunc(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
-                softcap, alibi_slopes, deterministic, return_softmax, group):
-        if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
-        assert alibi_slopes is None
-        _check_hot_path_args(dropout_p, window_size, softcap)
-        k = k.contiguous()
-        v = v.contiguous()
-        out, lse = zigzag_ring_flash_attn_varlen_forward(
-            group, q, k, v, cu_seqlens, max_seqlen, softmax_scale=softmax_scale, dropout_p=dropout_p,
-            causal=causal, window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes,
-            deterministic=False)
-        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens)
-        ctx.max_seqlen = max_seqlen
-        ctx.dropout_p = dropout_p
-        ctx.softmax_scale = softmax_scale
-        ctx.causal = causal
-        ctx.window_size = window_size
-        ctx.softcap = softcap
-        ctx.alibi_slopes = alibi_slopes
-        ctx.deterministic = deterministic
-        ctx.group = group
-        if not return_softmax:
-            return out
-        return out, unflatten_lse(lse, cu_seqlens, max_seqlen), None
-
-    @staticmethod
-    def backward(ctx, dout, *args):
-        q, k, v, out, lse, cu_seqlens = ctx.saved_tensors
-        dq, dk, dv = zigzag_ring_flash_attn_varlen_backward(
-            ctx.group, dout, q, k, v, out, lse, cu_seqlens, ctx.max_seqlen,
-            softmax_scale=ctx.softmax_scale, dropout_p=ctx.dropout_p, causal=ctx.causal,
-            window_size=ctx.window_size, softcap=ctx.softcap, alibi_slopes=ctx.alibi_slopes,
-            deterministic=ctx.deterministic)
-        return dq, dk, dv, None, None, None, None, None, None, None, None, None, None, None
-
-
-def zigzag_ring_flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
-                                                 softmax_scale=None, causal=False, window_size=(-1, -1),
-                                                 softcap=0.0, alibi_slopes=None, deterministic=False,
-                                                 return_attn_probs=False, group=None):
-    return ZigZagRingFlashAttnVarlenFunc.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen,
-                                               dropout_p, softmax_scale, causal, window_size, softcap,
-                                               alibi_slopes, deterministic, return_attn_probs, group)
-
-
-def zigzag_ring_flash_attn_varlen_kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0,
-                                                softmax_scale=None, causal=False, window_size=(-1, -1),
-                                                softcap=0.0, alibi_slopes=None, deterministic=False,
-                                                return_attn_probs=False, group=None):
-    return ZigZagRingFlashAttnVarlenFunc.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p,
-                                               softmax_scale, causal, window_size, softcap, alibi_slopes,
-                                               deterministic, return_attn_probs, group)
-
-
-def zigzag_ring_flash_attn_varlen_func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0,
-                                       softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
-                                       alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                                       group=None):
-    return ZigZagRingFlashAttnVarlenFunc.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale,
-                                               causal, window_size, softcap, alibi_slopes, deterministic,
-                                               return_attn_probs, group)
+(ZigZagRingFlashAttnVarlenFunc, zigzag_ring_flash_attn_varlen_func, zigzag_ring_flash_attn_varlen_kvpacked_func,
+ zigzag_ring_flash_attn_varlen_qkvpacked_func) = ring_front_end(
+    "zigzag_ring_flash_attn_varlen", "ZigZagRingFlashAttnVarlenFunc", zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward, packed=True)

@@ -202,6 +202,7 @@ def _self_chunk_worker(rank, ws, impl, Hq, Hkv, B, S, rd=1, env=None):
     backend sees must START before the exchange is waited for."""
     import yunchang_amd as Y
     import yunchang_amd.hybrid.async_attn_layer as AL
+    import yunchang_amd.ring.block_pieces as BP
     import yunchang_amd.ring.zigzag_ring_flash_attn as ZZ
     from yunchang_amd.kernels import set_block_backend
     from oracle_backend import OracleBlockBackend
@@ -222,7 +223,7 @@ def _self_chunk_worker(rank, ws, impl, Hq, Hkv, B, S, rd=1, env=None):
              for t in (ro,) + tuple(O.block_bwd(don, qn, kn, vn, ro, rl, None, True))]
     res, order = [], []
     real_wait = AL._Lane.wait
-    real = (AL._split_first_forward, AL._split_first_backward, ZZ.zigzag_fwd_step0_own, ZZ.zigzag_bwd_step0_split)
+    real = (BP.split_first_forward, BP.split_first_backward, ZZ.zigzag_fwd_step0_own, ZZ.zigzag_bwd_step0_split)
     AL._Lane.wait = lambda self, ev: (order.append("wait"), real_wait(self, ev))[1]
 
     def spy(name, fn):
@@ -230,7 +231,7 @@ def _self_chunk_worker(rank, ws, impl, Hq, Hkv, B, S, rd=1, env=None):
             order.append(name)
             return fn(*a, **kw)
         return f
-    AL._split_first_forward, AL._split_first_backward = spy("split-forward", real[0]), spy("split-backward", real[1])
+    BP.split_first_forward, BP.split_first_backward = spy("split-forward", real[0]), spy("split-backward", real[1])
     ZZ.zigzag_fwd_step0_own, ZZ.zigzag_bwd_step0_split = spy("split-forward", real[2]), spy("split-backward", real[3])
     try:
         for on in (False, True):
@@ -253,7 +254,7 @@ def _self_chunk_worker(rank, ws, impl, Hq, Hkv, B, S, rd=1, env=None):
     finally:
         AL._COMM_OVERRIDE.pop("self_chunk", None)
         AL._Lane.wait = real_wait
-        AL._split_first_forward, AL._split_first_backward, ZZ.zigzag_fwd_step0_own, ZZ.zigzag_bwd_step0_split = real
+        BP.split_first_forward, BP.split_first_backward, ZZ.zigzag_fwd_step0_own, ZZ.zigzag_bwd_step0_split = real
     close = all(torch.allclose(a, b, atol=tol, rtol=tol) for a, b, tol in zip(res[0], res[1], (8e-3, 3e-2, 3e-2, 3e-2)))
     right = all(torch.allclose(a, t, atol=tol, rtol=tol) for a, t, tol in zip(res[1], truth, (2e-2, 5e-2, 5e-2, 5e-2)))
     return close and right

@@ -103,9 +103,10 @@ def _batch2_worker(rank, ws, ud, rd, impl, Hq, Hkv, D, self_chunk=False, tails=N
         real_pack = A_.pack_seq_rows
         A_.pack_seq_rows = lambda *a: (pieces.append(a[2:]), real_pack(*a))[1]
     if self_chunk and rd == 1:
-        real_f, real_b = AL._split_first_forward, AL._split_first_backward
-        AL._split_first_forward = lambda *a: (calls.append("f"), real_f(*a))[1]
-        AL._split_first_backward = lambda *a: (calls.append("b"), real_b(*a))[1]
+        import yunchang_amd.ring.block_pieces as BP
+        real_f, real_b = BP.split_first_forward, BP.split_first_backward
+        BP.split_first_forward = lambda *a: (calls.append("f"), real_f(*a))[1]
+        BP.split_first_backward = lambda *a: (calls.append("b"), real_b(*a))[1]
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     Y.set_seq_parallel_pg(ud, rd, rank, ws)

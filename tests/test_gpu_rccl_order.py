@@ -311,9 +311,10 @@ def test_baseline_configs_at_full_size_on_a_virtual_grid(nccl_single, monkeypatc
         import yunchang_amd.comm.all_to_all as A_    # the last group's output leaves in row pieces, its dq ahead of dk | dv
         real_pack = A_.pack_seq_rows
         monkeypatch.setattr(A_, "pack_seq_rows", lambda *a: (tail_calls.append(a[2:]), real_pack(*a))[1])
-        real_f, real_b = AL._split_first_forward, AL._split_first_backward
-        monkeypatch.setattr(AL, "_split_first_forward", lambda *a: (split_calls.append("f"), real_f(*a))[1])
-        monkeypatch.setattr(AL, "_split_first_backward", lambda *a: (split_calls.append("b"), real_b(*a))[1])
+        import yunchang_amd.ring.block_pieces as BP                     # ring degree 1: the one causal block is split
+        real_f, real_b = BP.split_first_forward, BP.split_first_backward
+        monkeypatch.setattr(BP, "split_first_forward", lambda *a: (split_calls.append("f"), real_f(*a))[1])
+        monkeypatch.setattr(BP, "split_first_backward", lambda *a: (split_calls.append("b"), real_b(*a))[1])
         import yunchang_amd.ring.zigzag_ring_flash_attn as ZZ           # beside a ring: step 0 of the ring schedule is split
         real_zf, real_zb = ZZ.zigzag_fwd_step0_own, ZZ.zigzag_bwd_step0_split
         monkeypatch.setattr(ZZ, "zigzag_fwd_step0_own", lambda *a: (split_calls.append("f"), real_zf(*a))[1])
