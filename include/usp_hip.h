@@ -61,6 +61,7 @@ enum {
  *                     (unforced, the library picks the 64-row forward K split only for long cuts);
  *   USP_FORCE_WAVE32  every flash kernel of the call comes from the 32-rows-per-wave family.
  * Both bits at once: USP_EINVAL.  usp_last_launch_kinds() reports what a call actually launched.
+ * The library reads no environment variable: a call's behaviour comes from its argument block alone.
  * Layouts the 64-row family serves (beyond the alignment every call needs): its LDS-DMA pieces XOR a swizzle into a per-lane
  * byte offset whose row part must be a multiple of 256 bytes, and address 64 rows by 32-bit offsets, so
  *   forward            k.stride_s % 128 == 0 (elements);  k.stride_s, v.stride_s < 2^24   (v.stride_s % 128 is NOT needed:

@@ -56,11 +56,6 @@ struct BwdSoftcap {
 };
 struct BwdArgsSC : BwdParams, BwdSoftcap {};
 
-// rows of a 16-bit output tensor start on 16-byte boundaries (base pointer and every stride)
-inline bool rows16_aligned(const char* ptr, int64_t sb, int64_t ss, int64_t sh) {
-  return ptr && (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && sb % 8 == 0 && ss % 8 == 0 && sh % 8 == 0;
-}
-
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the
 // sequence is empty on either side; *ws_row0 = first row of the sequence in the dK/dV workspace slabs.

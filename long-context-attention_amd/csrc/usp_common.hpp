@@ -152,10 +152,6 @@ USP_DEV float softcap_tanh(float x, float k2) {
   return __builtin_fmaf(-2.f, __builtin_amdgcn_rcpf(fast_exp2(x * k2) + 1.f), 1.f);
 }
 
-// Host side: record which kernels a flash call launches (usp_last_launch_kinds; defined in usp_elementwise.hip)
-void launch_kinds_reset();
-void launch_kinds_note(int kind);
-
 // Persistent workgroups: a launch has min(items, resident workgroup slots) workgroups and each walks a
 // static list of work items.  The dispatcher places workgroup id on XCD id % 8; every XCD owns a
 // contiguous run of the item list (all sharers of one K/V sit behind one L2) and deals it out to its

@@ -3,8 +3,7 @@
 // fp32 -> 16-bit cast and fp32 add.
 // All are pure streaming kernels: 16-byte accesses per lane, grid-stride loops capped at
 // 256 CUs x 8 blocks (cdna_hip_programming.md Guideline 11/13).
-#include "usp_common.hpp"
-#include "usp_hip.h"
+#include "usp_host.hpp"
 
 namespace usp {
 
@@ -195,14 +194,6 @@ __global__ __launch_bounds__(kEwThreads) void add_kernel(float* dst, int64_t d_r
   }
 }
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool t16(const usp_tensor* t, int esize) {
-  const int m = 16 / esize;
-  return t && t->ptr && al16(t->ptr) && t->stride_b % m == 0 && t->stride_s % m == 0 &&
-         t->stride_h % m == 0;
-}
-static int launched() { return hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH; }
-
 }  // namespace usp
 
 using namespace usp;
@@ -213,25 +204,16 @@ extern "C" int usp_bwd_delta(int32_t dtype, int32_t B, int32_t S, int32_t H, int
   if (!dout || !out || !delta || B <= 0 || S <= 0 || H <= 0) return USP_EINVAL;
   if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
   if (D != 32 && D != 64 && D != 128) return USP_EUNSUPPORTED;
-  if (!t16(dout, 2) || !t16(out, 2)) return USP_EUNSUPPORTED;
+  if (!tensor_aligned(*dout, 16, 8) || !tensor_aligned(*out, 16, 8)) return USP_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)B * S * H;
   const int grid = ew_grid(rows * (D / 8));
-#define USP_DELTA(DD, TT)                                                                         \
-  hipLaunchKernelGGL((delta_kernel<DD, TT>), dim3(grid), dim3(kEwThreads), 0, st,                 \
-                     (const char*)dout->ptr, dout->stride_b, dout->stride_s, dout->stride_h,      \
-                     (const char*)out->ptr, out->stride_b, out->stride_s, out->stride_h, delta,   \
-                     d_sb, d_sh, B, S, H)
-  switch (D * 2 + dtype) {
-    case 64: USP_DELTA(32, 0); break;
-    case 65: USP_DELTA(32, 1); break;
-    case 128: USP_DELTA(64, 0); break;
-    case 129: USP_DELTA(64, 1); break;
-    case 256: USP_DELTA(128, 0); break;
-    case 257: USP_DELTA(128, 1); break;
-  }
-#undef USP_DELTA
-  return launched();
+  return with_head_dim_dtype(D, dtype, [&](auto d, auto dt) {
+    hipLaunchKernelGGL((delta_kernel<decltype(d)::value, decltype(dt)::value>), dim3(grid), dim3(kEwThreads), 0, st,
+                       (const char*)dout->ptr, dout->stride_b, dout->stride_s, dout->stride_h,
+                       (const char*)out->ptr, out->stride_b, out->stride_s, out->stride_h, delta, d_sb, d_sh, B, S, H);
+    return launched();
+  });
 }
 
 extern "C" int usp_lse_merge(int32_t dtype, int32_t B, int32_t S, int32_t H, int32_t D,
@@ -241,25 +223,16 @@ extern "C" int usp_lse_merge(int32_t dtype, int32_t B, int32_t S, int32_t H, int
   if (!acc || !lse || !bo || !bl || B <= 0 || S <= 0 || H <= 0) return USP_EINVAL;
   if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
   if (D != 32 && D != 64 && D != 128) return USP_EUNSUPPORTED;
-  if (!t16(acc, 4) || !t16(bo, 2)) return USP_EUNSUPPORTED;
+  if (!tensor_aligned(*acc, 16, 4) || !tensor_aligned(*bo, 16, 8)) return USP_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)B * S * H;
   const int grid = ew_grid(rows * (D / 8));
-#define USP_MERGE(DD, TT)                                                                         \
-  hipLaunchKernelGGL((merge_kernel<DD, TT>), dim3(grid), dim3(kEwThreads), 0, st,                 \
-                     (float*)acc->ptr, acc->stride_b, acc->stride_s, acc->stride_h, lse, l_sb,    \
-                     l_sh, (const char*)bo->ptr, bo->stride_b, bo->stride_s, bo->stride_h, bl,    \
-                     bl_sb, bl_sh, B, S, H, first ? 1 : 0)
-  switch (D * 2 + dtype) {
-    case 64: USP_MERGE(32, 0); break;
-    case 65: USP_MERGE(32, 1); break;
-    case 128: USP_MERGE(64, 0); break;
-    case 129: USP_MERGE(64, 1); break;
-    case 256: USP_MERGE(128, 0); break;
-    case 257: USP_MERGE(128, 1); break;
-  }
-#undef USP_MERGE
-  return launched();
+  return with_head_dim_dtype(D, dtype, [&](auto d, auto dt) {
+    hipLaunchKernelGGL((merge_kernel<decltype(d)::value, decltype(dt)::value>), dim3(grid), dim3(kEwThreads), 0, st,
+                       (float*)acc->ptr, acc->stride_b, acc->stride_s, acc->stride_h, lse, l_sb, l_sh,
+                       (const char*)bo->ptr, bo->stride_b, bo->stride_s, bo->stride_h, bl, bl_sb, bl_sh, B, S, H, first ? 1 : 0);
+    return launched();
+  });
 }
 
 extern "C" int usp_copy_rows(void* dst, const void* src, int64_t row_bytes, int64_t n0, int64_t n1,
@@ -268,7 +241,7 @@ extern "C" int usp_copy_rows(void* dst, const void* src, int64_t row_bytes, int6
                              void* stream) {
   if (!dst || !src || row_bytes <= 0 || n0 <= 0 || n1 <= 0 || n2 <= 0 || n3 <= 0) return USP_EINVAL;
   const int64_t all = row_bytes | ds0 | ds1 | ds2 | ds3 | ss0 | ss1 | ss2 | ss3;
-  if ((all & 15) || !al16(dst) || !al16(src)) return USP_EUNSUPPORTED;
+  if ((all & 15) || !aligned(dst, 16) || !aligned(src, 16)) return USP_EUNSUPPORTED;
   const int64_t cpr = row_bytes / 16;
   const int64_t total = cpr * n0 * n1 * n2 * n3;
   hipLaunchKernelGGL(copy_rows_kernel, dim3(ew_grid(total)), dim3(kEwThreads), 0,
@@ -283,16 +256,14 @@ extern "C" int usp_sum_rows(int32_t dtype, void* dst, const void* src, int64_t r
   if (!dst || !src || row_bytes <= 0 || r <= 0 || n0 <= 0 || n1 <= 0 || n2 <= 0) return USP_EINVAL;
   if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
   const int64_t all = row_bytes | term_stride | ds0 | ds1 | ds2 | ss0 | ss1 | ss2;
-  if ((all & 15) || !al16(dst) || !al16(src)) return USP_EUNSUPPORTED;
+  if ((all & 15) || !aligned(dst, 16) || !aligned(src, 16)) return USP_EUNSUPPORTED;
   const int64_t cpr = row_bytes / 16;
   const int64_t total = cpr * n0 * n1 * n2;
   const int grid = ew_grid(total);
-  if (dtype == USP_BF16)
-    hipLaunchKernelGGL(sum_rows_kernel<0>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream, (char*)dst,
+  with_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(sum_rows_kernel<decltype(dt)::value>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream, (char*)dst,
                        (const char*)src, cpr, n1, n2, total, (int)r, term_stride, ds0, ds1, ds2, ss0, ss1, ss2);
-  else
-    hipLaunchKernelGGL(sum_rows_kernel<1>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream, (char*)dst,
-                       (const char*)src, cpr, n1, n2, total, (int)r, term_stride, ds0, ds1, ds2, ss0, ss1, ss2);
+  });
   return launched();
 }
 
@@ -300,22 +271,20 @@ extern "C" int usp_cast_from_f32(int32_t dtype, void* dst, int64_t d_rs, const f
                                  int64_t s_rs, int64_t rows, int64_t n, void* stream) {
   if (!dst || !src || rows <= 0 || n <= 0) return USP_EINVAL;
   if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
-  if ((n & 7) || (d_rs & 7) || (s_rs & 3) || !al16(dst) || !al16(src)) return USP_EUNSUPPORTED;
+  if ((n & 7) || (d_rs & 7) || (s_rs & 3) || !aligned(dst, 16) || !aligned(src, 16)) return USP_EUNSUPPORTED;
   const int64_t n8 = n / 8;
   const int grid = ew_grid(rows * n8);
-  if (dtype == USP_BF16)
-    hipLaunchKernelGGL(cast_kernel<0>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream,
+  with_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(cast_kernel<decltype(dt)::value>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream,
                        (char*)dst, d_rs, src, s_rs, rows, n8);
-  else
-    hipLaunchKernelGGL(cast_kernel<1>, dim3(grid), dim3(kEwThreads), 0, (hipStream_t)stream,
-                       (char*)dst, d_rs, src, s_rs, rows, n8);
+  });
   return launched();
 }
 
 extern "C" int usp_add_f32(float* dst, int64_t d_rs, const float* a, int64_t a_rs, const float* b,
                            int64_t b_rs, int64_t rows, int64_t n, void* stream) {
   if (!dst || !a || !b || rows <= 0 || n <= 0) return USP_EINVAL;
-  if ((n & 3) || (d_rs & 3) || (a_rs & 3) || (b_rs & 3) || !al16(dst) || !al16(a) || !al16(b))
+  if ((n & 3) || (d_rs & 3) || (a_rs & 3) || (b_rs & 3) || !aligned(dst, 16) || !aligned(a, 16) || !aligned(b, 16))
     return USP_EUNSUPPORTED;
   const int64_t n4 = n / 4;
   hipLaunchKernelGGL(add_kernel, dim3(ew_grid(rows * n4)), dim3(kEwThreads), 0, (hipStream_t)stream,
@@ -367,11 +336,8 @@ extern "C" int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32
                               float* sink, uint64_t* clocks, void* stream) {
   using namespace usp;
   if (!operands || operand_bytes < 16 * 4096 || iters <= 0 || !sink || (waves_per_simd != 1 && waves_per_simd != 2)) return USP_EINVAL;
-  if (!al16(operands)) return USP_EUNSUPPORTED;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  hipLaunchKernelGGL(mfma_probe_kernel, dim3(cus), dim3(256 * waves_per_simd), 0, (hipStream_t)stream,
+  if (!aligned(operands, 16)) return USP_EUNSUPPORTED;
+  hipLaunchKernelGGL(mfma_probe_kernel, dim3(device_cus()), dim3(256 * waves_per_simd), 0, (hipStream_t)stream,
                      (const u32x4*)operands, (int)(operand_bytes / 16), (int)iters, sink, (unsigned long long*)clocks);
   return launched();
 }

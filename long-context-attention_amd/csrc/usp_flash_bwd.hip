@@ -12,13 +12,8 @@
 // register-resident fragment sets R1,R2, S = X1 R1^T, T = X2 R2^T, and tr-read "X^T" operands for
 // the gradient MFMAs.  As in the forward, no cross-lane shuffle is needed for P / dS: the k-step
 // order of the gradient MFMAs is defined as the order the S accumulator holds rows.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "usp_bwd_params.hpp"
-#include "usp_common.hpp"
-#include "usp_hip.h"
+#include "usp_host.hpp"
 
 namespace usp {
 
@@ -149,140 +144,94 @@ __global__ __launch_bounds__(256) void reduce_cuts_kernel(const BwdParams p) {
   }
 }
 
+static int reduce_grid(int64_t items) { return (int)((items + 255) / 256 > 2048 ? 2048 : (items + 255) / 256); }
+
+// dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
+// the launch, the 8-wave kernel otherwise; then the sum over the partial slabs of a head-split / cut launch.
 template <int D, int DT>
-static int launch_bwd(BwdArgsSC p, bool causal, hipStream_t st, int force, int skip) {
-  constexpr size_t lds0 = 2 * (2 * kTile * D * 2);
-  // dK,dV
-  // persistent launches: one workgroup per CU (both kernels fit once per CU), each walks n_items / grid items
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  static const bool persist = [] { const char* e = getenv("USP_BWD_PERSIST"); return !(e && e[0] == '0'); }();
+static int launch_dkdv(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
   p.nblk = (p.Sk + 127) / 128;
   p.n_items = p.B * p.Hkv * p.nblk * p.ngrp * p.qsplit;
-  const bool pers = (persist || p.sched) && !p.interleave;
-  int grid = (pers && p.n_items > cus) ? cus : p.n_items;
-  const size_t qx = p.sched ? 16 : 0;            // LDS for the item queue's two slots
-  // dK/dV: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where it applies; USP_BWD_WAVES=8 forces
-  // the 8-wave kernel below
-  // (per call: `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32, include/usp_hip.h)
-  static const int forced_env = [] { const char* e = getenv("USP_BWD_WAVES"); return e ? atoi(e) : 0; }();
-  const int forced_waves = (force & USP_FORCE_WAVE32) ? 8 : ((force & USP_FORCE_ROW64) ? 0 : forced_env);
-  if ((force & USP_FORCE_ROW64) && !(D == 128 && ((skip & USP_BWD_SKIP_DKDV) || dkdv64_serves(p, DT)) && ((skip & USP_BWD_SKIP_DQ) || dq64_serves(p))))
-    return USP_EUNSUPPORTED;     // (only the launches that will run have to be served)
-  bool dkdv_done = (skip & USP_BWD_SKIP_DKDV) != 0;
-  const bool row64_ok = !p.cap_on;               // the 64-row kernels' hand-pinned pipelines have no softcap step
-  if (!dkdv_done && D == 128 && forced_waves != 8 && row64_ok) {
-    int rc64 = USP_ELAUNCH;
-    if (launch_dkdv64(p, DT, causal, st, &rc64)) {
-      if (rc64 != USP_OK) return rc64;
-      dkdv_done = true;
-      launch_kinds_note(USP_KIND_DKDV_ROW64);
-    }
-  }
-  if (!dkdv_done) {
+  int rc = USP_ELAUNCH;
+  if (row64 && launch_dkdv64(p, DT, causal, st, &rc)) {
+    if (rc != USP_OK) return rc;
+    launch_kinds_note(USP_KIND_DKDV_ROW64);
+  } else {
     // the 8-wave dK/dV kernel addresses the Q / dO tiles of a head by a 32-bit byte offset from the head's first row
     if ((int64_t)p.Sq * p.q_ss * 2 >= (1LL << 31) || (int64_t)p.Sq * p.do_ss * 2 >= (1LL << 31)) return USP_EUNSUPPORTED;
-  {
-    constexpr size_t lds2 = 3 * (2 * kTile * D * 2 + 2 * kTile * 4) + 4 * 2 * 4096;
-    p.sched_lds = (int)lds2;
-    const BwdParams pb = p;
-    if (p.cap_on) {
-      if (causal)
-        hipLaunchKernelGGL((flash_bwd_dkdv_softcap_kernel<D, DT, true>), dim3(grid), dim3(512), lds2 + qx, st, p);
-      else
-        hipLaunchKernelGGL((flash_bwd_dkdv_softcap_kernel<D, DT, false>), dim3(grid), dim3(512), lds2 + qx, st, p);
-    } else if (causal)
-      hipLaunchKernelGGL((flash_bwd_dkdv_kernel<D, DT, true>), dim3(grid), dim3(512), lds2 + qx, st, pb);
-    else
-      hipLaunchKernelGGL((flash_bwd_dkdv_kernel<D, DT, false>), dim3(grid), dim3(512), lds2 + qx, st, pb);
+    // persistent: one workgroup per CU (the kernel fits once per CU)
+    const int grid = persistent_grid(p.n_items, device_cus(), p.interleave);
+    constexpr size_t lds = 3 * (2 * kTile * D * 2 + 2 * kTile * 4) + 4 * 2 * 4096;
+    p.sched_lds = (int)lds;
+    const size_t lds_q = lds + (p.sched ? 16 : 0);   // + the item queue's two slots
+    const BwdParams pb = p;                        // the argument block of the kernels without softcap
+    with_causal(causal, [&](auto c) {
+      constexpr bool C = decltype(c)::value;
+      if (p.cap_on) hipLaunchKernelGGL((flash_bwd_dkdv_softcap_kernel<D, DT, C>), dim3(grid), dim3(512), lds_q, st, p);
+      else hipLaunchKernelGGL((flash_bwd_dkdv_kernel<D, DT, C>), dim3(grid), dim3(512), lds_q, st, pb);
+    });
     launch_kinds_note(USP_KIND_DKDV_WAVE8);
+    if (launched() != USP_OK) return USP_ELAUNCH;
   }
-  }
-  if (hipGetLastError() != hipSuccess) return USP_ELAUNCH;
-  if (p.split && !(skip & USP_BWD_SKIP_DKDV)) {
-    const int64_t items = (int64_t)p.B * p.Sk * p.Hkv * (D / 4);
-    int64_t rg = (items + 255) / 256;
-    rg = rg > 2048 ? 2048 : rg;
-    const BwdParams pb = p;
-    hipLaunchKernelGGL((reduce_heads_kernel<D, DT>), dim3((int)rg), dim3(256), 0, st, pb);
-    if (hipGetLastError() != hipSuccess) return USP_ELAUNCH;
-    launch_kinds_note(USP_KIND_REDUCE_HEADS);
-  }
-  if (skip & USP_BWD_SKIP_DQ) return USP_OK;
-  // dQ: the one-wave-per-SIMD kernel (4 waves x 64 query rows, usp_flash_bwd_dq64.hip) where it applies
-  static const int forced_dq_env = [] { const char* e = getenv("USP_BWD_DQ_WAVES"); return e ? atoi(e) : 0; }();
-  const int forced_dq = force ? 0 : forced_dq_env;
-  if (D == 128 && forced_waves != 8 && forced_dq != 8 && row64_ok) {
-    int rc64 = USP_ELAUNCH;
-    if (launch_dq64(p, DT, causal, st, &rc64)) {
-      if (rc64 != USP_OK) return rc64;
-      launch_kinds_note(USP_KIND_DQ_ROW64);
-      if (p.ksplit > 1) {          // same stream: the cuts' partials are complete when this starts
-        const int64_t items = (int64_t)p.B * p.Sq * p.Hq * (D / 4);
-        int64_t rg = (items + 255) / 256;
-        rg = rg > 2048 ? 2048 : rg;
-        const BwdParams pb = p;
-        hipLaunchKernelGGL((reduce_cuts_kernel<D, DT>), dim3((int)rg), dim3(256), 0, st, pb);
-        launch_kinds_note(USP_KIND_REDUCE_CUTS);
-      }
-      return hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH;
-    }
+  if (!p.split) return USP_OK;
+  const BwdParams pb = p;
+  hipLaunchKernelGGL((reduce_heads_kernel<D, DT>), dim3(reduce_grid((int64_t)p.B * p.Sk * p.Hkv * (D / 4))), dim3(256), 0, st, pb);
+  if (launched() != USP_OK) return USP_ELAUNCH;
+  launch_kinds_note(USP_KIND_REDUCE_HEADS);
+  return USP_OK;
+}
+
+// dQ of a call: the one-wave-per-SIMD kernel (4 waves x 64 query rows, usp_flash_bwd_dq64.hip) or the 8-wave kernel, as above
+template <int D, int DT>
+static int launch_dq(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
+  int rc = USP_ELAUNCH;
+  if (row64 && launch_dq64(p, DT, causal, st, &rc)) {
+    if (rc == USP_OK) launch_kinds_note(USP_KIND_DQ_ROW64);
+    return rc;
   }
   p.nblk = (p.Sq + 255) / 256;
   p.n_items = p.B * p.Hq * p.nblk * p.ksplit;
-  grid = (pers && p.n_items > cus) ? cus : p.n_items;
-  p.sched_lds = (int)lds0;
+  const int grid = persistent_grid(p.n_items, device_cus(), p.interleave);
+  constexpr size_t lds = 2 * (2 * kTile * D * 2);
+  p.sched_lds = (int)lds;
+  const size_t lds_q = lds + (p.sched ? 16 : 0);   // + the item queue's two slots
   const BwdParams pb = p;
-  if (p.cap_on) {
-    if (causal)
-      hipLaunchKernelGGL((flash_bwd_softcap_kernel<D, DT, true>), dim3(grid), dim3(512), lds0 + qx, st, p);
-    else
-      hipLaunchKernelGGL((flash_bwd_softcap_kernel<D, DT, false>), dim3(grid), dim3(512), lds0 + qx, st, p);
-  } else if (causal)
-    hipLaunchKernelGGL((flash_bwd_kernel<D, DT, true>), dim3(grid), dim3(512), lds0 + qx, st, pb);
-  else
-    hipLaunchKernelGGL((flash_bwd_kernel<D, DT, false>), dim3(grid), dim3(512), lds0 + qx, st, pb);
-  if (hipGetLastError() != hipSuccess) return USP_ELAUNCH;
+  with_causal(causal, [&](auto c) {
+    constexpr bool C = decltype(c)::value;
+    if (p.cap_on) hipLaunchKernelGGL((flash_bwd_softcap_kernel<D, DT, C>), dim3(grid), dim3(512), lds_q, st, p);
+    else hipLaunchKernelGGL((flash_bwd_kernel<D, DT, C>), dim3(grid), dim3(512), lds_q, st, pb);
+  });
+  if (launched() != USP_OK) return USP_ELAUNCH;
   launch_kinds_note(USP_KIND_DQ_WAVE8);
-  if (p.ksplit > 1) {            // same stream: the partials are complete when this starts
-    const int64_t items = (int64_t)p.B * p.Sq * p.Hq * (D / 4);
-    int64_t rg = (items + 255) / 256;
-    rg = rg > 2048 ? 2048 : rg;
-    hipLaunchKernelGGL((reduce_cuts_kernel<D, DT>), dim3((int)rg), dim3(256), 0, st, pb);
-    launch_kinds_note(USP_KIND_REDUCE_CUTS);
-  }
-  return hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH;
+  return USP_OK;
 }
 
-static bool ok16(const usp_tensor& t, int esize) {
-  const int m = 16 / esize;
-  return t.ptr && (reinterpret_cast<uintptr_t>(t.ptr) & 15) == 0 && t.stride_b % m == 0 &&
-         t.stride_s % m == 0 && t.stride_h % m == 0;
+// the sum over the dQ partials of a key-cut launch; same stream: the cuts' partials are complete when this starts
+template <int D, int DT>
+static int launch_reduce_cuts(const BwdParams& p, hipStream_t st) {
+  hipLaunchKernelGGL((reduce_cuts_kernel<D, DT>), dim3(reduce_grid((int64_t)p.B * p.Sq * p.Hq * (D / 4))), dim3(256), 0, st, p);
+  launch_kinds_note(USP_KIND_REDUCE_CUTS);
+  return launched();
+}
+
+template <int D, int DT>
+static int launch_bwd(BwdArgsSC p, bool causal, hipStream_t st, int force, int skip) {
+  const bool want_dkdv = !(skip & USP_BWD_SKIP_DKDV), want_dq = !(skip & USP_BWD_SKIP_DQ);
+  // per call, `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32 (include/usp_hip.h) picks the family; forced onto the 64-row
+  // family, only the launches that will run have to be served
+  if ((force & USP_FORCE_ROW64) && !(D == 128 && (!want_dkdv || dkdv64_serves(p, DT)) && (!want_dq || dq64_serves(p))))
+    return USP_EUNSUPPORTED;
+  // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
+  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on;
+  int rc = USP_OK;
+  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, causal, st, row64)) != USP_OK) return rc;
+  if (want_dq && (rc = launch_dq<D, DT>(p, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
+  return rc;
 }
 
 }  // namespace usp
 
-static int64_t ws_rows_of(const usp_bwd_args* a) {
-  return (a->seq_q || a->seq_k) ? a->total_k : (int64_t)a->B * a->Sk;
-}
-
 static int cuts_of(int32_t n, bool packed) { return (packed || n < 2) ? 1 : (n > 8 ? 8 : n); }
-
-static int device_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
-}
 
 // Query heads of a KV group that ONE dK/dV work item streams into its accumulators (ABI v7: usp_bwd_args.dkdv_heads; a divisor
 // of G = Hq / Hkv).  More heads per item: K / V fragments, their pre-scale and the epilogue once per run of heads, fewer fp32
@@ -298,23 +247,16 @@ static int device_cus() {
 // handful of long items) and, for CAUSAL launches, at 2: the 32 workgroups an XCD runs side by side hold 32 consecutive key
 // blocks, whose first visible tiles lie up to 62 tiles apart; head after head inside an item that lead adds up, and from three
 // heads on the window of Q / dO tiles they stream together (62 tiles x 32 KiB x heads) no longer fits the XCD's 4 MiB L2 -- the
-// fetch triples for a time gain inside the noise.  Packed batches keep 1.  USP_BWD_GSUB=n (read once) overrides the automatic
-// choice for A/B runs.
+// fetch triples for a time gain inside the noise.  Packed batches keep 1.
 static int dkdv_heads_of(const usp_bwd_args* a) {
   const int G = a->Hq / a->Hkv;
   // an explicit value must divide G whatever G is: MHA (G = 1) accepts 1 only, as usp_hip.h states
   if (a->dkdv_heads > 0) return (G % a->dkdv_heads == 0) ? a->dkdv_heads : -1;
   if (G <= 1) return 1;
   if (a->seq_q || a->seq_k) return 1;
-  static const int forced = [] { const char* e = getenv("USP_BWD_GSUB"); return e ? atoi(e) : 0; }();
-  if (forced > 0) {
-    int g = forced > G ? G : forced;
-    while (G % g != 0) --g;
-    return g;
-  }
   const int64_t base = (int64_t)a->B * a->Hkv * ((a->Sk + 127) / 128) * cuts_of(a->dkdv_splits, false);
-  const bool triangles = a->causal || ((a->flags & USP_ATTN_WINDOW) && a->window_right >= 0);
-  const int64_t want = (triangles ? 2LL : 1LL) * device_cus();
+  const bool triangles = usp::decode_mask(*a).causal;
+  const int64_t want = (triangles ? 2LL : 1LL) * usp::device_cus();
   int best = 1;
   const int cap = triangles ? 2 : 4;
   for (int g = 2; g <= G && g <= cap; ++g)
@@ -322,62 +264,62 @@ static int dkdv_heads_of(const usp_bwd_args* a) {
   return best;
 }
 
-// [dK partials | dV partials | dQ partials]: ((G / dkdv_heads) * dkdv_splits) slabs of ws_rows x Hkv x D each for dK and for dV
-// (none when that is one slab: the whole group in one item and no cut), dq_splits slabs of B x Sq x Hq x D for dQ (none without a cut)
-static int64_t dkdv_part_bytes(const usp_bwd_args* a) {
-  const int gsub = dkdv_heads_of(a);
-  if (gsub < 1) return 0;
-  const int64_t slabs = (int64_t)((a->Hq / a->Hkv) / gsub) * cuts_of(a->dkdv_splits, a->seq_q || a->seq_k);
-  return slabs > 1 ? 2 * slabs * ws_rows_of(a) * a->Hkv * a->D * 4 : 0;
+// The plan of a backward call, and with it the layout of its workspace [dK partials | dV partials | dQ partials]:
+// (ngrp * qsplit) slabs of ws_rows x Hkv x D each for dK and for dV (none when that is one slab: the whole group in one item
+// and no cut), ksplit slabs of B x Sq x Hq x D for dQ (none without a cut).  Needs Hkv > 0 and Hq % Hkv == 0.
+struct BwdPlan {
+  int gsub, ngrp;                  // query heads per dK/dV item (< 1: dkdv_heads does not divide the group), items per KV group
+  int qsplit, ksplit;              // cuts of the dK/dV launch, of the dQ launch
+  int64_t ws_rows;                 // key rows of a dK/dV slab
+  int64_t dkdv_bytes, dq_bytes;
+};
+static BwdPlan plan_bwd(const usp_bwd_args* a) {
+  const bool packed = a->seq_q || a->seq_k;
+  BwdPlan pl;
+  pl.gsub = dkdv_heads_of(a);
+  pl.ngrp = pl.gsub < 1 ? 0 : (a->Hq / a->Hkv) / pl.gsub;
+  pl.qsplit = cuts_of(a->dkdv_splits, packed);
+  pl.ksplit = cuts_of(a->dq_splits, packed);
+  pl.ws_rows = packed ? a->total_k : (int64_t)a->B * a->Sk;
+  const int64_t slabs = (int64_t)pl.ngrp * pl.qsplit;
+  pl.dkdv_bytes = slabs > 1 ? 2 * slabs * pl.ws_rows * a->Hkv * a->D * 4 : 0;
+  pl.dq_bytes = pl.ksplit > 1 ? (int64_t)pl.ksplit * a->B * a->Sq * a->Hq * a->D * 4 : 0;
+  return pl;
 }
 
 extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
   if (!a || a->Hkv <= 0 || a->Hq < a->Hkv || a->Hq % a->Hkv != 0) return 0;
-  const int nq = cuts_of(a->dq_splits, a->seq_q || a->seq_k);
-  return dkdv_part_bytes(a) + (nq > 1 ? (int64_t)nq * a->B * a->Sq * a->Hq * a->D * 4 : 0);
+  const BwdPlan pl = plan_bwd(a);
+  return pl.dkdv_bytes + pl.dq_bytes;
 }
 
 extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) {
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse || !a->delta) return USP_EINVAL;
-  const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
-  if (force == (USP_FORCE_ROW64 | USP_FORCE_WAVE32)) return USP_EINVAL;
+  if (int rc = check_force(a->flags)) return rc;
   const int skip = a->flags & (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV);
   if (skip == (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV)) return USP_EINVAL;
-  if (a->dtype != USP_BF16 && a->dtype != USP_FP16) return USP_EINVAL;
-  if (a->B <= 0 || a->Sq <= 0 || a->Sk <= 0 || a->Hq <= 0 || a->Hkv <= 0) return USP_EINVAL;
-  if (!(a->softmax_scale > 0.f)) return USP_EINVAL;
-  const bool has_cap = (a->flags & USP_ATTN_SOFTCAP) != 0;     // (the field is read only with the bit)
-  if (has_cap && !(__builtin_isfinite(a->softcap) && a->softcap > 0.f)) return USP_EINVAL;
-  if (has_cap && (force & USP_FORCE_ROW64)) return USP_EUNSUPPORTED;   // the 64-row family declines softcap
-  if (a->D != 32 && a->D != 64 && a->D != 128) return USP_EUNSUPPORTED;
-  if (a->Hq % a->Hkv != 0) return USP_EUNSUPPORTED;
+  if (int rc = check_problem(*a)) return rc;
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
   // an fp32 tensor may be absent only if its 16-bit final output is given and nothing is accumulated
   auto need32 = [](const usp_tensor& t32, const usp_tensor& t16, int accum) { return !t16.ptr || accum; };
-  const bool want_dq = !(a->flags & USP_BWD_SKIP_DQ), want_dkdv = !(a->flags & USP_BWD_SKIP_DKDV);   // (a skipped launch needs no outputs)
+  const bool want_dq = !(skip & USP_BWD_SKIP_DQ), want_dkdv = !(skip & USP_BWD_SKIP_DKDV);   // (a skipped launch needs no outputs)
   if ((want_dq && need32(a->dq, a->dq16, a->accum_dq) && !a->dq.ptr) || (want_dkdv && need32(a->dk, a->dk16, a->accum_dk) && !a->dk.ptr) ||
       (want_dkdv && need32(a->dv, a->dv16, a->accum_dv) && !a->dv.ptr))
     return USP_EINVAL;
-  auto ok32 = [](const usp_tensor& t) { return !t.ptr || ok16(t, 4); };
-  auto okh = [](const usp_tensor& t) {
-    return !t.ptr || ((reinterpret_cast<uintptr_t>(t.ptr) & 7) == 0 && t.stride_b % 4 == 0 &&
-                      t.stride_s % 4 == 0 && t.stride_h % 4 == 0);
-  };
-  if (!ok16(a->dout, 2) || !ok16(a->q, 2) || !ok16(a->k, 2) || !ok16(a->v, 2) || !ok32(a->dq) ||
-      !ok32(a->dk) || !ok32(a->dv) || !okh(a->dq16) || !okh(a->dk16) || !okh(a->dv16))
+  auto ok32 = [](const usp_tensor& t) { return !t.ptr || tensor_aligned(t, 16, 4); };      // optional fp32 / 16-bit outputs
+  auto ok16 = [](const usp_tensor& t) { return !t.ptr || tensor_aligned(t, 8, 4); };
+  if (!tensor_aligned(a->dout, 16, 8) || !tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8) ||
+      !ok32(a->dq) || !ok32(a->dk) || !ok32(a->dv) || !ok16(a->dq16) || !ok16(a->dk16) || !ok16(a->dv16))
     return USP_EUNSUPPORTED;
-  // sliding window (flash-attn's window_size), as in usp_flash_fwd: causal caps the right bound at 0, a right bound is
-  // the causal limit with a shifted offset, a left bound is a second mask term + a shorter streamed range
-  const bool has_win = (a->flags & USP_ATTN_WINDOW) != 0;
-  const int wl = has_win ? a->window_left : -1;
-  const int wr = a->causal ? 0 : (has_win ? a->window_right : -1);
-  if ((a->seq_q || a->seq_k) && (wl >= 0 || wr > 0)) return USP_EUNSUPPORTED;       // dense launches only
+  const Mask mask = decode_mask(*a);
+  if (packed && mask.windowed) return USP_EUNSUPPORTED;        // dense launches only
   if (a->dq_splits < 0 || a->dq_splits > 8 || a->dkdv_splits < 0 || a->dkdv_splits > 8) return USP_EINVAL;
-  if (a->dkdv_heads < 0 || dkdv_heads_of(a) < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
+  const BwdPlan plan = plan_bwd(a);
+  if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
   BwdArgsSC p;
   p.dout = (const char*)a->dout.ptr; p.q = (const char*)a->q.ptr;
   p.k = (const char*)a->k.ptr; p.v = (const char*)a->v.ptr;
@@ -394,64 +336,44 @@ extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) {
   p.dv_sb = a->dv.stride_b; p.dv_ss = a->dv.stride_s; p.dv_sh = a->dv.stride_h;
   p.B = a->B; p.Sq = a->Sq; p.Sk = a->Sk; p.Hq = a->Hq; p.Hkv = a->Hkv; p.G = a->Hq / a->Hkv;
   p.nblk = 0;
-  p.causal_off = a->Sk - a->Sq + (wr > 0 ? wr : 0);
-  p.win_on = wl >= 0 ? 1 : 0; p.win_lo = a->Sk - a->Sq - (wl >= 0 ? wl : 0);
+  mask.store(p);
   p.scale = a->softmax_scale;
   p.scale_log2 = a->softmax_scale * kLog2e;
-  p.cap_on = has_cap ? 1 : 0;
-  p.cap_log2 = has_cap ? a->softcap * kLog2e : 0.f;
-  p.tanh_k2 = has_cap ? 2.f * a->softmax_scale * kLog2e / a->softcap : 0.f;
   p.accum_dq = a->accum_dq ? 1 : 0; p.accum_dk = a->accum_dk ? 1 : 0; p.accum_dv = a->accum_dv ? 1 : 0;
   p.dq16 = (char*)a->dq16.ptr; p.dk16 = (char*)a->dk16.ptr; p.dv16 = (char*)a->dv16.ptr;
   p.dq16_sb = a->dq16.stride_b; p.dq16_ss = a->dq16.stride_s; p.dq16_sh = a->dq16.stride_h;
   p.dk16_sb = a->dk16.stride_b; p.dk16_ss = a->dk16.stride_s; p.dk16_sh = a->dk16.stride_h;
   p.dv16_sb = a->dv16.stride_b; p.dv16_ss = a->dv16.stride_s; p.dv16_sh = a->dv16.stride_h;
-  // GQA head split: with a workspace, every query head of a KV group gets its own workgroups and the
-  // per-head partials are summed afterwards; without one the group's heads are looped inside a workgroup.
   p.seq_q = a->seq_q; p.seq_k = a->seq_k;
   p.sched = packed ? a->sched : nullptr;
   p.sched_lds = 0;
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
-  {   // USP_ITEM_GROUP=0 (read once): the head-major item walk of rounds 1-5 instead of a KV group's heads side by side
-    static const bool group_heads = [] { const char* e = getenv("USP_ITEM_GROUP"); return !(e && e[0] == '0'); }();
-    p.walk_g = group_heads ? p.G : 1;
-  }
+  p.walk_g = p.G;                                 // a KV group's heads side by side in the item walk
   p.wide16 = 0;                                   // (set by the 64-row launches for their own copy)
-  p.ws_rows = ws_rows_of(a);
+  p.ws_rows = plan.ws_rows;
   if (packed) {
     p.do_sb = p.q_sb = p.k_sb = p.v_sb = p.lse_sb = p.dl_sb = 0;
     p.dq_sb = p.dk_sb = p.dv_sb = p.dq16_sb = p.dk16_sb = p.dv16_sb = 0;
   }
-  // Workspace present and large enough: the dK/dV items of dkdv_heads_of() query heads each and / or the requested cuts;
-  // otherwise neither (the whole KV group inside one workgroup, one item per key block) -- results are identical up to fp32
-  // summation order either way.
-  const int64_t need = usp_flash_bwd_workspace_bytes(a);
+  // Workspace present and large enough: the dK/dV items of plan.gsub query heads each and / or the requested cuts, partials
+  // summed afterwards; otherwise neither (the whole KV group inside one workgroup, one item per key block) -- results are
+  // identical up to fp32 summation order either way.
   p.split = 0; p.qsplit = 1; p.ksplit = 1; p.nslab = 1; p.ws_dk = nullptr; p.ws_dv = nullptr; p.ws_dq = nullptr;
   p.gsub = p.G; p.ngrp = 1;
-  if (need > 0 && a->workspace && a->workspace_bytes >= need &&
-      (reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0) {
-    const int64_t part = dkdv_part_bytes(a);
-    if (part > 0) {
+  const int64_t need = plan.dkdv_bytes + plan.dq_bytes;
+  if (need > 0 && a->workspace && a->workspace_bytes >= need && aligned(a->workspace, 16)) {
+    if (plan.dkdv_bytes > 0) {
       p.split = 1;
-      p.gsub = dkdv_heads_of(a);
-      p.ngrp = p.G / p.gsub;
-      p.qsplit = cuts_of(a->dkdv_splits, packed);
+      p.gsub = plan.gsub; p.ngrp = plan.ngrp; p.qsplit = plan.qsplit;
       p.nslab = p.ngrp * p.qsplit;
       p.ws_dk = (float*)a->workspace;
-      p.ws_dv = p.ws_dk + part / 8;
+      p.ws_dv = p.ws_dk + plan.dkdv_bytes / 8;
     }
-    p.ksplit = cuts_of(a->dq_splits, packed);
-    if (p.ksplit > 1) p.ws_dq = (float*)((char*)a->workspace + part);
+    p.ksplit = plan.ksplit;
+    if (p.ksplit > 1) p.ws_dq = (float*)((char*)a->workspace + plan.dkdv_bytes);
   }
-  hipStream_t st = (hipStream_t)stream;
-  const bool causal = wr >= 0;                    // (a->causal, or a right window bound)
-  switch (a->D * 2 + a->dtype) {
-    case 64: return launch_bwd<32, 0>(p, causal, st, force, skip);
-    case 65: return launch_bwd<32, 1>(p, causal, st, force, skip);
-    case 128: return launch_bwd<64, 0>(p, causal, st, force, skip);
-    case 129: return launch_bwd<64, 1>(p, causal, st, force, skip);
-    case 256: return launch_bwd<128, 0>(p, causal, st, force, skip);
-    case 257: return launch_bwd<128, 1>(p, causal, st, force, skip);
-  }
-  return USP_EUNSUPPORTED;
+  const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
+  return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
+    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, mask.causal, (hipStream_t)stream, force, skip);
+  });
 }

@@ -17,13 +17,8 @@
 // gradient MFMAs need them, the tile's 8 LDS-DMA pieces (Q / dO tile two iterations ahead of B) through slots 0 .. 15.
 // MFMAs are inline asm (see usp_mfma64.hpp for why and for the hazards hipcc cannot see); tools/mfma_hazards.py checks
 // the emitted stream.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "usp_bwd_params.hpp"
-#include "usp_common.hpp"
-#include "usp_hip.h"
+#include "usp_host.hpp"
 #include "usp_mfma64.hpp"
 
 namespace usp {
@@ -622,31 +617,18 @@ bool dkdv64_serves(const BwdParams& p_in, int dtype) {
 }
 
 bool launch_dkdv64(const BwdParams& p_in, int dtype, bool causal, hipStream_t st, int* rc) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
   if (!dkdv64_serves(p_in, dtype)) return false;
   BwdParams p = p_in;
-  p.wide16 = ((p.dk16 && !p.accum_dk && rows16_aligned(p.dk16, p.dk16_sb, p.dk16_ss, p.dk16_sh)) ? 2 : 0) |
-             ((p.dv16 && !p.accum_dv && rows16_aligned(p.dv16, p.dv16_sb, p.dv16_ss, p.dv16_sh)) ? 4 : 0);
+  p.wide16 = ((p.dk16 && !p.accum_dk && tensor_aligned(p.dk16, p.dk16_sb, p.dk16_ss, p.dk16_sh, 16, 8)) ? 2 : 0) |
+             ((p.dv16 && !p.accum_dv && tensor_aligned(p.dv16, p.dv16_sb, p.dv16_ss, p.dv16_sh, 16, 8)) ? 4 : 0);
   p.nblk = (p.Sk + 127) / 128;
   p.n_items = p.B * p.Hkv * p.nblk * p.ngrp * p.qsplit;
-  // persistent: one workgroup per CU; USP_LAUNCH_INTERLEAVE: one workgroup per item (the same kernel: a workgroup's item
-  // list then has one entry)
-  const int grid = (!p.interleave && p.n_items > cus) ? cus : p.n_items;
+  const int grid = persistent_grid(p.n_items, device_cus(), p.interleave);      // persistent: one workgroup per CU
   constexpr size_t lds = 3 * (2 * kTile * 128 * 2 + 2 * kTile * 4) + 2 * 2 * 8192;
-  if (dtype == USP_BF16) {
-    if (causal) hipLaunchKernelGGL((flash_bwd_dkdv64_kernel<0, true>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((flash_bwd_dkdv64_kernel<0, false>), dim3(grid), dim3(256), lds, st, p);
-  } else {
-    if (causal) hipLaunchKernelGGL((flash_bwd_dkdv64_kernel<1, true>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((flash_bwd_dkdv64_kernel<1, false>), dim3(grid), dim3(256), lds, st, p);
-  }
-  *rc = hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH;
+  with_dtype_causal(dtype, causal, [&](auto dt, auto c) {
+    hipLaunchKernelGGL((flash_bwd_dkdv64_kernel<decltype(dt)::value, decltype(c)::value>), dim3(grid), dim3(256), lds, st, p);
+  });
+  *rc = launched();
   return true;
 }
 

@@ -21,13 +21,8 @@
 // MFMA: the stream stays under the five issue slots a lone wave hides per MFMA (profiles/r04_ubench_issue.txt), which the
 // 64-MFMA tiles of the forward and of the dK/dV kernel do not.
 // MFMAs are inline asm (usp_mfma64.hpp); tools/mfma_hazards.py checks the emitted stream.
-#include <stdlib.h>
-
-#include <type_traits>
-
 #include "usp_bwd_params.hpp"
-#include "usp_common.hpp"
-#include "usp_hip.h"
+#include "usp_host.hpp"
 #include "usp_mfma64.hpp"
 
 namespace usp {
@@ -412,28 +407,17 @@ bool dq64_serves(const BwdParams& p_in) {
 }
 
 bool launch_dq64(const BwdParams& p_in, int dtype, bool causal, hipStream_t st, int* rc) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
   if (!dq64_serves(p_in)) return false;
   BwdParams p = p_in;
   p.nblk = (p.Sq + 255) / 256;
   p.n_items = p.B * p.Hq * p.nblk * p.ksplit;
-  p.wide16 = (p.ksplit <= 1 && p.dq16 && !p.accum_dq && rows16_aligned(p.dq16, p.dq16_sb, p.dq16_ss, p.dq16_sh)) ? 1 : 0;
-  const int grid = (!p.interleave && p.n_items > cus) ? cus : p.n_items;      // persistent: one workgroup per CU
+  p.wide16 = (p.ksplit <= 1 && p.dq16 && !p.accum_dq && tensor_aligned(p.dq16, p.dq16_sb, p.dq16_ss, p.dq16_sh, 16, 8)) ? 1 : 0;
+  const int grid = persistent_grid(p.n_items, device_cus(), p.interleave);      // persistent: one workgroup per CU
   const size_t lds = 4 * kTile * 128 * 2;
-  if (dtype == USP_BF16) {
-    if (causal) hipLaunchKernelGGL((flash_bwd_dq64_kernel<0, true>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((flash_bwd_dq64_kernel<0, false>), dim3(grid), dim3(256), lds, st, p);
-  } else {
-    if (causal) hipLaunchKernelGGL((flash_bwd_dq64_kernel<1, true>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((flash_bwd_dq64_kernel<1, false>), dim3(grid), dim3(256), lds, st, p);
-  }
-  *rc = hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH;
+  with_dtype_causal(dtype, causal, [&](auto dt, auto c) {
+    hipLaunchKernelGGL((flash_bwd_dq64_kernel<decltype(dt)::value, decltype(c)::value>), dim3(grid), dim3(256), lds, st, p);
+  });
+  *rc = launched();
   return true;
 }
 

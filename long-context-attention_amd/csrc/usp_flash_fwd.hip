@@ -16,11 +16,8 @@
 //   * K/V tiles are double-buffered in LDS and filled by LDS-DMA (buffer_load ... lds) one tile (V) /
 //     two tiles (K) ahead: no staging registers, no ds_write; one barrier per tile.
 //   * exp2 with softmax_scale*log2(e) folded into one FMA per score.
-#include <stdlib.h>
-
-#include "usp_common.hpp"
 #include "usp_fwd_params.hpp"
-#include "usp_hip.h"
+#include "usp_host.hpp"
 
 namespace usp {
 
@@ -109,9 +106,10 @@ int launch_split_merge(const FwdArgsT<true>& p, int dtype, int D, hipStream_t st
   if (64 % (D / 4) != 0) return USP_EUNSUPPORTED;           // (the D/4 lanes of a row must share a wavefront: D = 64, 128)
   const int64_t work = (int64_t)p.B * p.Sq * p.Hq * (D / 4);
   const int blocks = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-  if (dtype == USP_BF16) hipLaunchKernelGGL((split_merge_kernel<0>), dim3(blocks), dim3(256), 0, st, p, D);
-  else hipLaunchKernelGGL((split_merge_kernel<1>), dim3(blocks), dim3(256), 0, st, p, D);
-  return hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH;
+  with_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL((split_merge_kernel<decltype(dt)::value>), dim3(blocks), dim3(256), 0, st, p, D);
+  });
+  return launched();
 }
 
 template <int D, int DT, int NWAVES>
@@ -119,37 +117,21 @@ static int launch_fwd_w(FwdArgsSC p, bool causal, hipStream_t st) {
   p.nq = (p.Sq + 32 * NWAVES - 1) / (32 * NWAVES);
   p.n_items = p.B * p.Hq * p.nq * p.ksplit;
   // persistent launch: one workgroup per resident slot (8 waves: 1 per CU, 4 waves: 2 per CU)
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  static const bool persist = [] { const char* e = getenv("USP_FWD_PERSIST"); return !(e && e[0] == '0'); }();
-  const int slots = cus * (NWAVES == 8 ? 1 : 2);
-  const int grid = (((persist || p.sched) && !p.interleave) && p.n_items > slots) ? slots : p.n_items;
+  const int grid = persistent_grid(p.n_items, device_cus() * (NWAVES == 8 ? 1 : 2), p.interleave);
   const size_t lds = 2 * 2 * kBN * D * 2 + (p.sched ? 16 : 0);
   const FwdArgsT<true> ps = p;                               // the argument block of the split kernels
-  if (p.cap_on) {
-    if (causal)
-      hipLaunchKernelGGL((flash_fwd_softcap_kernel<D, DT, true, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, p);
+  FwdArgsT<false> plain;                                     // the argument block of the plain kernels: FwdParams alone
+  static_cast<FwdParams&>(plain) = p;
+  with_causal(causal, [&](auto c) {
+    constexpr bool C = decltype(c)::value;
+    if (p.cap_on)
+      hipLaunchKernelGGL((flash_fwd_softcap_kernel<D, DT, C, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, p);
+    else if (p.ksplit > 1 || p.win_on)
+      hipLaunchKernelGGL((flash_fwd_kernel<D, DT, C, NWAVES, true>), dim3(grid), dim3(64 * NWAVES), lds, st, ps);
     else
-      hipLaunchKernelGGL((flash_fwd_softcap_kernel<D, DT, false, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, p);
-  } else if (p.ksplit > 1 || p.win_on) {
-    if (causal)
-      hipLaunchKernelGGL((flash_fwd_kernel<D, DT, true, NWAVES, true>), dim3(grid), dim3(64 * NWAVES), lds, st, ps);
-    else
-      hipLaunchKernelGGL((flash_fwd_kernel<D, DT, false, NWAVES, true>), dim3(grid), dim3(64 * NWAVES), lds, st, ps);
-  } else {
-    FwdArgsT<false> plain;                                   // the argument block of the plain kernels: FwdParams alone
-    static_cast<FwdParams&>(plain) = p;
-    if (causal)
-      hipLaunchKernelGGL((flash_fwd_kernel<D, DT, true, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, plain);
-    else
-      hipLaunchKernelGGL((flash_fwd_kernel<D, DT, false, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, plain);
-  }
-  if (hipGetLastError() != hipSuccess) return USP_ELAUNCH;
+      hipLaunchKernelGGL((flash_fwd_kernel<D, DT, C, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, plain);
+  });
+  if (launched() != USP_OK) return USP_ELAUNCH;
   if (p.ksplit > 1) {
     static_assert(64 % (D / 4) == 0 && 256 % (D / 4) == 0, "split_merge_kernel: the D/4 lanes of a row must share a wavefront");
     return launch_split_merge(ps, DT, D, st);
@@ -163,22 +145,12 @@ static int launch_fwd(const FwdArgsSC& p, bool causal, hipStream_t st, int force
   // 3-4 % whenever they can give every CU work; 4 waves (128 rows, two workgroups per CU) are used only
   // when the 8-wave item list is shorter than the CU count, or for short causal sequences (<= 1024 rows:
   // +3...8 %) (measured with persistent workgroups, profiles/).  Per call, `force` (USP_FORCE_ROW64 / USP_FORCE_WAVE32,
-  // include/usp_hip.h) picks the family; per process, USP_FWD_WAVES=4|8|64 forces a shape for A/B runs (64 = the
-  // 4 x 64-row kernel of usp_flash_fwd64.hip, where it applies).
-  static const int forced_env = [] { const char* e = getenv("USP_FWD_WAVES"); return e ? atoi(e) : 0; }();
+  // include/usp_hip.h) picks the family.  `waves` = 4 | 8, or 64: the 4 x 64-row kernel of usp_flash_fwd64.hip.
   // what usp_flash_fwd64.hip serves (plain and K-split launches; its hand-pinned pipeline has no softcap step)
   const bool fwd64_ok = D == 128 && !p.seq_q && !p.win_on && !p.cap_on;
   const int split_kind = p.ksplit > 1 ? USP_KIND_FWD_SPLIT_MERGE : 0;
-  if (force & USP_FORCE_ROW64) {
-    int rc = USP_ELAUNCH;
-    if (fwd64_ok && launch_fwd64(p, DT, causal, st, &rc)) {
-      if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_ROW64 | split_kind);
-      return rc;
-    }
-    return USP_EUNSUPPORTED;
-  }
-  int waves = (force & USP_FORCE_WAVE32) ? 0 : forced_env;
-  if (waves != 4 && waves != 8 && waves != 64) {
+  int waves = 64;
+  if (!(force & USP_FORCE_ROW64)) {
     const int64_t grid8 = (int64_t)p.B * p.Hq * ((p.Sq + 255) / 256) * p.ksplit;
     // short causal sequences: less diagonal waste (dense only: in packed mode twice the items cost more to fetch)
     // beside a transfer (interleave) RCCL's resident workgroups take a few CUs: with ONE 256-row item per CU a lost
@@ -204,18 +176,12 @@ static int launch_fwd(const FwdArgsSC& p, bool causal, hipStream_t st, int force
       if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_ROW64 | split_kind);
       return rc;
     }
-    waves = 8;
+    if (force & USP_FORCE_ROW64) return USP_EUNSUPPORTED;
+    waves = 8;                                               // (a layout the 64-row kernel declines)
   }
   const int rc = waves == 4 ? launch_fwd_w<D, DT, 4>(p, causal, st) : launch_fwd_w<D, DT, 8>(p, causal, st);
   if (rc == USP_OK) launch_kinds_note((waves == 4 ? USP_KIND_FWD_WAVE4 : USP_KIND_FWD_WAVE8) | split_kind);
   return rc;
-}
-
-static bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
-static bool tensor16_ok(const usp_tensor& t, int esize) {
-  const int m = 16 / esize;
-  return t.ptr && aligned16(t.ptr) && t.stride_b % m == 0 && t.stride_s % m == 0 &&
-         t.stride_h % m == 0;
 }
 
 }  // namespace usp
@@ -230,37 +196,21 @@ extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) {
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse) return USP_EINVAL;
-  const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
-  if (force == (USP_FORCE_ROW64 | USP_FORCE_WAVE32)) return USP_EINVAL;
-  if (a->dtype != USP_BF16 && a->dtype != USP_FP16) return USP_EINVAL;
-  if (a->B <= 0 || a->Sq <= 0 || a->Sk <= 0 || a->Hq <= 0 || a->Hkv <= 0) return USP_EINVAL;
-  if (!(a->softmax_scale > 0.f)) return USP_EINVAL;
-  const bool has_cap = (a->flags & USP_ATTN_SOFTCAP) != 0;     // (the field is read only with the bit)
-  if (has_cap && !(__builtin_isfinite(a->softcap) && a->softcap > 0.f)) return USP_EINVAL;
-  if (has_cap && (force & USP_FORCE_ROW64)) return USP_EUNSUPPORTED;   // the 64-row family declines softcap
-  if (a->D != 32 && a->D != 64 && a->D != 128) return USP_EUNSUPPORTED;
-  if (a->Hq % a->Hkv != 0) return USP_EUNSUPPORTED;
-  if (!tensor16_ok(a->q, 2) || !tensor16_ok(a->k, 2) || !tensor16_ok(a->v, 2))
+  if (int rc = check_force(a->flags)) return rc;
+  if (int rc = check_problem(*a)) return rc;
+  if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k)) return USP_EINVAL;
-  // sliding window (flash-attn's window_size): causal caps the right bound at 0; a right bound is the causal limit with
-  // a shifted offset; a left bound runs in the split instantiation (FwdSplit)
-  const bool has_win = (a->flags & USP_ATTN_WINDOW) != 0;
-  const int wl = has_win ? a->window_left : -1;
-  const int wr = a->causal ? 0 : (has_win ? a->window_right : -1);
-  if (packed && (wl >= 0 || wr > 0)) return USP_EUNSUPPORTED;       // dense launches only
+  const Mask mask = decode_mask(*a);
+  if (packed && mask.windowed) return USP_EUNSUPPORTED;        // dense launches only
   const int f_all = packed ? 2 : a->Sq;          // packed: final_begin/_end count half sequences (0,1,2)
   int fb = a->final_begin < 0 ? 0 : a->final_begin;
   int fe = a->final_end > f_all ? f_all : a->final_end;
   if (fe < fb) fe = fb;
   const bool any_final = fe > fb, any_acc = (fb > 0 || fe < f_all);
-  if (any_final && !(a->out.ptr && (reinterpret_cast<uintptr_t>(a->out.ptr) & 7) == 0 &&
-                     a->out.stride_b % 4 == 0 && a->out.stride_s % 4 == 0 &&
-                     a->out.stride_h % 4 == 0))
-    return a->out.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
-  if ((any_acc || a->merge_in) && !tensor16_ok(a->acc, 4))
-    return a->acc.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
+  if (any_final && !tensor_aligned(a->out, 8, 4)) return a->out.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
+  if ((any_acc || a->merge_in) && !tensor_aligned(a->acc, 16, 4)) return a->acc.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
 
   FwdArgsSC p;
   p.q = (const char*)a->q.ptr; p.k = (const char*)a->k.ptr; p.v = (const char*)a->v.ptr;
@@ -274,43 +224,28 @@ extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) {
   p.B = a->B; p.Sq = a->Sq; p.Sk = a->Sk; p.Hq = a->Hq; p.Hkv = a->Hkv;
   p.G = a->Hq / a->Hkv;
   p.nq = 0;   // set per workgroup shape in launch_fwd_w
-  p.causal_off = a->Sk - a->Sq + (wr > 0 ? wr : 0);
+  mask.store(p);
   p.scale = a->softmax_scale;
   p.scale_log2 = a->softmax_scale * kLog2e;
   p.merge_in = a->merge_in ? 1 : 0;
   p.final_begin = fb; p.final_end = fe;
-  p.out_wide = (a->out.ptr && (reinterpret_cast<uintptr_t>(a->out.ptr) & 15) == 0 && a->out.stride_b % 8 == 0 &&
-                a->out.stride_s % 8 == 0 && a->out.stride_h % 8 == 0) ? 1 : 0;
+  p.out_wide = tensor_aligned(a->out, 16, 8) ? 1 : 0;
   p.seq_q = a->seq_q; p.seq_k = a->seq_k;
   p.sched = packed ? a->sched : nullptr;
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
-  {   // USP_ITEM_GROUP=0 (read once): the head-major item walk of rounds 1-5 instead of a KV group's heads side by side
-    static const bool group_heads = [] { const char* e = getenv("USP_ITEM_GROUP"); return !(e && e[0] == '0'); }();
-    p.walk_g = group_heads ? p.G : 1;
-  }
+  p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  p.win_on = wl >= 0 ? 1 : 0; p.win_lo = a->Sk - a->Sq - (wl >= 0 ? wl : 0);
-  p.cap_on = has_cap ? 1 : 0;
-  p.cap_log2 = has_cap ? a->softcap * kLog2e : 0.f;
-  p.tanh_k2 = has_cap ? 2.f * a->softmax_scale * kLog2e / a->softcap : 0.f;
   if (a->k_splits > 1 && a->workspace != nullptr) {
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
-    if (a->k_splits > 8 || !aligned16(a->workspace)) return USP_EINVAL;
+    if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
     p.ksplit = a->k_splits;
     p.ws_o = (float*)a->workspace;
     p.ws_lse = p.ws_o + (int64_t)p.ksplit * a->B * a->Sq * a->Hq * a->D;
   }
   if (packed) p.q_sb = p.k_sb = p.v_sb = p.o_sb = p.a_sb = p.lse_sb = 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool causal = wr >= 0;                    // (a->causal, or a right window bound)
-  switch (a->D * 2 + a->dtype) {
-    case 32 * 2 + 0: return launch_fwd<32, 0>(p, causal, st, force);
-    case 32 * 2 + 1: return launch_fwd<32, 1>(p, causal, st, force);
-    case 64 * 2 + 0: return launch_fwd<64, 0>(p, causal, st, force);
-    case 64 * 2 + 1: return launch_fwd<64, 1>(p, causal, st, force);
-    case 128 * 2 + 0: return launch_fwd<128, 0>(p, causal, st, force);
-    case 128 * 2 + 1: return launch_fwd<128, 1>(p, causal, st, force);
-  }
-  return USP_EUNSUPPORTED;
+  const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
+  return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
+    return launch_fwd<decltype(d)::value, decltype(dt)::value>(p, mask.causal, (hipStream_t)stream, force);
+  });
 }

@@ -19,13 +19,8 @@
 // so the hazards are met by construction: a chain's result is read at least 16 MFMA slots after its last MFMA in the
 // pipelined loop, and behind an explicit s_nop in the unpipelined paths; operands written by VALU (packed P) are
 // complete at least one MFMA slot before the MFMA that reads them.
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "usp_common.hpp"
 #include "usp_fwd_params.hpp"
-#include "usp_hip.h"
+#include "usp_host.hpp"
 #include "usp_mfma64.hpp"
 
 namespace usp {
@@ -614,24 +609,19 @@ USP_TM(
 }
 
 template <bool SPLIT>
-static void launch64(const FwdArgsT<SPLIT>& p, int grid, size_t lds, int dtype, bool causal, hipStream_t st) {
-  if (dtype == USP_BF16) {
-    if (causal) hipLaunchKernelGGL((flash_fwd64_kernel<0, true, SPLIT>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((flash_fwd64_kernel<0, false, SPLIT>), dim3(grid), dim3(256), lds, st, p);
-  } else {
-    if (causal) hipLaunchKernelGGL((flash_fwd64_kernel<1, true, SPLIT>), dim3(grid), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((flash_fwd64_kernel<1, false, SPLIT>), dim3(grid), dim3(256), lds, st, p);
-  }
+static int launch64(FwdArgsT<SPLIT>& p, int dtype, bool causal, hipStream_t st) {
+  p.nq = (p.Sq + 255) / 256;
+  p.n_items = p.B * p.Hq * p.nq;
+  if constexpr (SPLIT) p.n_items *= p.ksplit;
+  const int grid = persistent_grid(p.n_items, device_cus(), p.interleave);      // persistent: one workgroup per CU
+  const size_t lds = 2 * 2 * kBN * 128 * 2;
+  with_dtype_causal(dtype, causal, [&](auto dt, auto c) {
+    hipLaunchKernelGGL((flash_fwd64_kernel<decltype(dt)::value, decltype(c)::value, SPLIT>), dim3(grid), dim3(256), lds, st, p);
+  });
+  return launched();
 }
 
 bool launch_fwd64(const FwdArgsT<true>& p_in, int dtype, bool causal, hipStream_t st, int* rc) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
   // the K pieces' swizzle is XORed into the per-lane byte offset (row part a multiple of 256 bytes); per-lane offsets and the
   // pieces' scalar offsets are 32-bit: 64 rows of K / V must span less than 2^31 bytes.  V needs no 256-byte rows: v_voff and
   // v_step are sums, nothing is XORed into them (unlike launch_dq64, whose V pieces are swizzled) -- a V with
@@ -639,29 +629,21 @@ bool launch_fwd64(const FwdArgsT<true>& p_in, int dtype, bool causal, hipStream_
   // tests/test_gpu_layouts.py::test_row64_stride_conditions_forward
   if ((p_in.k_ss * 2) % 256 != 0 || p_in.k_ss * 128 >= (1LL << 31) || p_in.v_ss * 128 >= (1LL << 31)) return false;
   if (p_in.win_on || p_in.seq_q) return false;
-  const size_t lds = 2 * 2 * kBN * 128 * 2;
   if (p_in.ksplit > 1) {
     FwdArgsT<true> p = p_in;
-    p.nq = (p.Sq + 255) / 256;
-    p.n_items = p.B * p.Hq * p.nq * p.ksplit;
-    const int grid = (!p.interleave && p.n_items > cus) ? cus : p.n_items;
     // the cuts write partials: the epilogue's fp32 destination is cut 0 of the workspace (the kernel adds the cut)
     p.acc = p.ws_o;
     p.a_sb = (int64_t)p.Sq * p.Hq * 128; p.a_ss = (int64_t)p.Hq * 128; p.a_sh = 128;
     p.lse = p.ws_lse;
     p.lse_sb = (int64_t)p.Hq * p.Sq; p.lse_sh = p.Sq;
     p.merge_in = 0; p.final_begin = 0; p.final_end = 0; p.out_wide = 0;
-    launch64<true>(p, grid, lds, dtype, causal, st);
-    *rc = hipGetLastError() == hipSuccess ? launch_split_merge(p_in, dtype, 128, st) : USP_ELAUNCH;
-    return true;
+    *rc = launch64(p, dtype, causal, st);
+    if (*rc == USP_OK) *rc = launch_split_merge(p_in, dtype, 128, st);
+  } else {
+    FwdArgsT<false> p;
+    static_cast<FwdParams&>(p) = p_in;
+    *rc = launch64(p, dtype, causal, st);
   }
-  FwdArgsT<false> p;
-  static_cast<FwdParams&>(p) = p_in;
-  p.nq = (p.Sq + 255) / 256;
-  p.n_items = p.B * p.Hq * p.nq;
-  const int grid = (!p.interleave && p.n_items > cus) ? cus : p.n_items;      // persistent: one workgroup per CU
-  launch64<false>(p, grid, lds, dtype, causal, st);
-  *rc = hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH;
   return true;
 }
 

@@ -1,0 +1,113 @@
+// Host side of libusp_hip.so: what sits between the C ABI (include/usp_hip.h) and the kernel launches, once.
+// Everything here is host code (it names HIP runtime calls); nothing in it is reachable from a __device__ path.
+// A call's behaviour comes from its argument block alone: the library reads no environment.
+#pragma once
+#include <atomic>
+#include <type_traits>
+
+#include "usp_common.hpp"
+#include "usp_hip.h"
+
+namespace usp {
+
+// Record which kernels a flash call launches (usp_last_launch_kinds; defined in usp_elementwise.hip)
+void launch_kinds_reset();
+void launch_kinds_note(int kind);
+
+// Result of the launch just issued on this thread.
+inline int launched() { return hipGetLastError() == hipSuccess ? USP_OK : USP_ELAUNCH; }
+
+// Compute units of the CURRENT device, asked once per device id (two threads asking at once both get the answer and store
+// the same value); 256 where there is no device.
+inline int device_cus() {
+  constexpr int kMaxDevices = 64;
+  static std::atomic<int> cached[kMaxDevices];     // 0 = not asked yet
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  const bool slot = dev >= 0 && dev < kMaxDevices;
+  if (slot && (n = cached[dev].load(std::memory_order_relaxed)) > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  if (slot) cached[dev].store(n, std::memory_order_relaxed);
+  return n;
+}
+
+// Persistent launch: one workgroup per resident slot, each walking a list of items; USP_LAUNCH_INTERLEAVE, or fewer items
+// than slots: one workgroup per item (the same kernel: its list then has one entry).
+inline int persistent_grid(int n_items, int slots, int interleave) {
+  return (!interleave && n_items > slots) ? slots : n_items;
+}
+
+// ---- alignment: base pointer on a `bytes` boundary, every stride a multiple of `elems` elements ----
+inline bool aligned(const void* ptr, int bytes) { return (reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)(bytes - 1)) == 0; }
+inline bool tensor_aligned(const void* ptr, int64_t sb, int64_t ss, int64_t sh, int bytes, int elems) {
+  return ptr && aligned(ptr, bytes) && sb % elems == 0 && ss % elems == 0 && sh % elems == 0;
+}
+inline bool tensor_aligned(const usp_tensor& t, int bytes, int elems) {
+  return tensor_aligned(t.ptr, t.stride_b, t.stride_s, t.stride_h, bytes, elems);
+}
+
+// ---- run-time (dtype, causal, head dim) -> template arguments: f receives std::integral_constants ----
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> auto with_dtype(int dtype, F&& f) { return dtype == USP_BF16 ? f(Int<0>{}) : f(Int<1>{}); }
+template <class F> auto with_causal(bool causal, F&& f) { return causal ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> auto with_dtype_causal(int dtype, bool causal, F&& f) {
+  return with_dtype(dtype, [&](auto dt) { return with_causal(causal, [&](auto c) { return f(dt, c); }); });
+}
+// f(Int<D>, Int<DT>) -> int; USP_EUNSUPPORTED for a head dim without kernels
+template <class F> int with_head_dim_dtype(int D, int dtype, F&& f) {
+  return with_dtype(dtype, [&](auto dt) -> int {
+    switch (D) {
+      case 32: return f(Int<32>{}, dt);
+      case 64: return f(Int<64>{}, dt);
+      case 128: return f(Int<128>{}, dt);
+    }
+    return USP_EUNSUPPORTED;
+  });
+}
+
+// ---- what usp_flash_fwd and usp_flash_bwd check alike (Args = usp_fwd_args / usp_bwd_args), in the order they check it ----
+inline int check_force(int flags) {
+  return (flags & USP_FORCE_ROW64) && (flags & USP_FORCE_WAVE32) ? USP_EINVAL : USP_OK;
+}
+template <class Args> int check_problem(const Args& a) {
+  if (a.dtype != USP_BF16 && a.dtype != USP_FP16) return USP_EINVAL;
+  if (a.B <= 0 || a.Sq <= 0 || a.Sk <= 0 || a.Hq <= 0 || a.Hkv <= 0) return USP_EINVAL;
+  if (!(a.softmax_scale > 0.f)) return USP_EINVAL;
+  const bool has_cap = (a.flags & USP_ATTN_SOFTCAP) != 0;     // (the field is read only with the bit)
+  if (has_cap && !(__builtin_isfinite(a.softcap) && a.softcap > 0.f)) return USP_EINVAL;
+  if (has_cap && (a.flags & USP_FORCE_ROW64)) return USP_EUNSUPPORTED;   // the 64-row family declines softcap
+  if (a.D != 32 && a.D != 64 && a.D != 128) return USP_EUNSUPPORTED;
+  if (a.Hq % a.Hkv != 0) return USP_EUNSUPPORTED;
+  return USP_OK;
+}
+
+// Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound
+// at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
+// (forward: the split instantiation, FwdSplit).
+struct Mask {
+  bool causal;                  // the causal instantiation runs: a.causal, or a right window bound
+  bool windowed;                // a bound beyond plain causal: dense launches only
+  int causal_off, win_on, win_lo, cap_on;
+  float cap_log2, tanh_k2;
+  template <class Params> void store(Params& p) const {
+    p.causal_off = causal_off; p.win_on = win_on; p.win_lo = win_lo;
+    p.cap_on = cap_on; p.cap_log2 = cap_log2; p.tanh_k2 = tanh_k2;
+  }
+};
+template <class Args> Mask decode_mask(const Args& a) {
+  const bool has_win = (a.flags & USP_ATTN_WINDOW) != 0, has_cap = (a.flags & USP_ATTN_SOFTCAP) != 0;
+  const int wl = has_win ? a.window_left : -1;
+  const int wr = a.causal ? 0 : (has_win ? a.window_right : -1);
+  Mask m;
+  m.causal = wr >= 0;
+  m.windowed = wl >= 0 || wr > 0;
+  m.causal_off = a.Sk - a.Sq + (wr > 0 ? wr : 0);
+  m.win_on = wl >= 0 ? 1 : 0;
+  m.win_lo = a.Sk - a.Sq - (wl >= 0 ? wl : 0);
+  m.cap_on = has_cap ? 1 : 0;
+  m.cap_log2 = has_cap ? a.softcap * kLog2e : 0.f;
+  m.tanh_k2 = has_cap ? 2.f * a.softmax_scale * kLog2e / a.softcap : 0.f;
+  return m;
+}
+
+}  // namespace usp

@@ -16,7 +16,7 @@ def _put(dst, arr):
 
 
 def _operand(t, what, ptr_align=16, stride_align_bytes=16):
-    """The operand constraints of the device kernels (csrc/usp_flash_fwd.hip:tensor16_ok, usp_flash_bwd.hip): unit
+    """The operand constraints of the device kernels (csrc/usp_host.hpp:tensor_aligned, usp_flash_fwd.hip, usp_flash_bwd.hip): unit
     head-dim stride, pointer and every other stride a multiple of 16 bytes (8 for 16-bit outputs).  Asserted here so
     that the CPU orchestration tests fail where the HIP path would return USP_EUNSUPPORTED."""
     if t is None:

@@ -24,6 +24,8 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"libusp_hip.so does not export {name}"
     assert set(_C.EXPORTS) == declared
+    # behaviour comes from the argument block alone (usp_hip.h): the library does not even import getenv
+    assert b"getenv" not in open(_C.lib_path(), "rb").read()
     L = _C.load()
     assert L.usp_abi_version() == _C.ABI_VERSION == 7
     assert L.usp_last_launch_kinds() == 0                        # nothing launched on this thread

@@ -1,6 +1,7 @@
 """Identity of a kernel's MACHINE CODE inside libusp_hip.so (DEV / bench helper, no GPU needed).
 
     python tools/kernel_isa.py [path/to/libusp_hip.so]      -> sha16 of the roofline kernel + of all plain forward kernels
+    ... --all / --every                                     -> + one sha16 line per flash kernel / per function in the code objects
 
 A profile (profiles/*_rocprof_summary.txt) belongs to the kernel sources it was taken from; bench.py refuses to quote
 its PMC figures when the sources have changed.  Sources can change without the profiled kernel changing (round 2 added
@@ -82,7 +83,10 @@ if __name__ == "__main__":
     r, a, n = isa_identity(lib)
     print(f"roofline_kernel_isa_sha16: {r}")
     print(f"plain_forward_kernels_isa_sha16: {a}  ({n} kernels)")
-    if "--all" in sys.argv:                      # every flash kernel of the library, one line each (refactoring proofs)
-        for name, body in sorted(_disassemble(lib).items()):
-            if "flash_" in name and "kernel" in name:
+    if "--all" in sys.argv or "--every" in sys.argv:   # one line per flash kernel (--all) or per function of the code objects,
+        for name, body in sorted(_disassemble(lib).items()):   # element-wise, merge and reduce kernels included (--every): refactoring proofs
+            # ("...": objdump's mark for the zero padding up to the NEXT function -- which kernel is last in its code object
+            # depends on the order the host code instantiates them in, not on the kernel)
+            body = [ins for ins in body if ins != "..."]
+            if "--every" in sys.argv or ("flash_" in name and "kernel" in name):
                 print(f"{_sha16(body)}  {len(body):6d}  {name[:110]}")
