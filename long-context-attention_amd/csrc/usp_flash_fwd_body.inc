@@ -444,7 +444,11 @@
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (!keep) rescale(mt);
+    // S(n_main) is the first tile of the generic tail: its scores are still UNMASKED here, and the tail's softmax takes its
+    // row max itself, behind the mask.  Raising the reference to the score of a key the row must not see costs no
+    // correctness but, in fp16, the precision of every visible P (a masked score 20 above the visible ones leaves them
+    // subnormal: `out` off by 5e-3 with lse exact; tests/test_gpu_needle.py, wave4-d64-fp16) -- so that tile decides nothing.
+    if (!keep && jj + 1 < n_main) rescale(mt);
     dma_drain();                 // this wave's pieces of K(jj+2), V(jj+1) have landed ...
     __syncthreads();             // ... and so have everybody else's
   };

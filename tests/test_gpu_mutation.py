@@ -241,6 +241,100 @@ def test_layout_family_fails_on_an_injection_into_the_strided_run(dev, target, k
     assert ops.fired == 1, "the injection never fired"
 
 
+# ------------------------------------------------------------------------------------------------
+# needle inputs (tests/test_gpu_needle.py): the REAL kernel on altered operands -- finite, plausible, subtly wrong results
+# ------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def altered(fn_name, alter):
+    """Patch yunchang_amd._C.<fn_name>: `alter(arguments)` edits the bound arguments (a dict; tensors must be replaced by
+    altered COPIES, never written to), then the real launch runs on them.  Yields the list of the calls it altered."""
+    from yunchang_amd import _C
+    real = getattr(_C, fn_name)
+    sig = inspect.signature(real)
+    fired = []
+
+    def wrapper(*args, **kwargs):
+        bound = sig.bind(*args, **kwargs)
+        alter(bound.arguments)
+        fired.append(fn_name)
+        return real(*bound.args, **bound.kwargs)
+    setattr(_C, fn_name, wrapper)
+    try:
+        yield fired
+    finally:
+        setattr(_C, fn_name, real)
+
+
+def _zero_keys(k0, k1):
+    def alter(a):
+        k = a["k"].clone()
+        k[:, k0:k1] = 0
+        a["k"] = k
+    return alter
+
+
+def _swap_key_tiles(t):
+    def alter(a):
+        k = a["k"].clone()
+        k[:, t:t + 64], k[:, t + 64:t + 128] = a["k"][:, t + 64:t + 128], a["k"][:, t:t + 64]
+        a["k"] = k                                          # (V is left alone: K tile t meets V tile t + 1)
+    return alter
+
+
+def _window_left_off_by_one(a):
+    a["window"] = (a["window"][0] + 1, a["window"][1])
+
+
+def _swap_dout_heads(a):
+    do = a["dout"].clone()
+    do[:, 256:512, 0], do[:, 256:512, 1] = a["dout"][:, 256:512, 1], a["dout"][:, 256:512, 0]
+    a["dout"] = do                                          # (heads 0 and 1 share a KV group)
+
+
+def _needle_must_fail(dev, fn_name, alter, cfg_id):
+    import test_gpu_needle as GN
+    c = GN._CFG[cfg_id]
+    GN.run_dense(dev, c)                                    # the case itself passes
+    with altered(fn_name, alter) as fired:
+        with pytest.raises(AssertionError, match="out of tolerance"):
+            GN.run_dense(dev, c)
+    assert fired, f"the alteration of {fn_name} never fired in {cfg_id}"
+
+
+@pytest.mark.parametrize("fn_name", ["flash_fwd", "flash_bwd"])
+@pytest.mark.parametrize("cfg_id", ["row64-causal", "wave4-d128"])
+def test_needle_family_fails_on_a_zeroed_key_tile(dev, cfg_id, fn_name):
+    """The 64-key tile [128, 192) of K reads as zeros (the image of a tile the kernel never loaded): every result stays
+    finite and on N(0,1) inputs within tolerance at depth; the needle test must fail, forward and backward."""
+    _needle_must_fail(dev, fn_name, _zero_keys(128, 192), cfg_id)
+
+
+@pytest.mark.parametrize("fn_name", ["flash_fwd", "flash_bwd"])
+def test_needle_family_fails_on_swapped_key_tiles(dev, fn_name):
+    """K tiles [256, 320) and [320, 384) swapped, V left alone: every key is counted once, with the neighbour's V."""
+    _needle_must_fail(dev, fn_name, _swap_key_tiles(256), "row64-causal")
+
+
+@pytest.mark.parametrize("fn_name", ["flash_fwd", "flash_bwd"])
+def test_needle_family_fails_on_a_window_left_bound_off_by_one(dev, fn_name):
+    _needle_must_fail(dev, fn_name, _window_left_off_by_one, "win-causal")
+
+
+def test_needle_family_fails_on_a_zeroed_key_at_a_k_split_run_boundary(dev):
+    """The first key of the second of the three runs the LAST query tile's keys are cut into reads as zeros."""
+    import needle_inputs as NI
+    import test_gpu_needle as GN
+    c = GN._CFG["ksplit3-row64"]
+    q0 = (c.Sq - 1) // 256 * 256
+    t0, nt = NI.key_tiles_of_query_tile(q0, 256, c.Sq, c.Sk, c.causal)
+    kb = NI.run_bounds(t0, nt, c.k_splits, "floor")[0] * 64
+    _needle_must_fail(dev, "flash_fwd", _zero_keys(kb, kb + 1), "ksplit3-row64")
+
+
+def test_needle_family_fails_on_dout_heads_swapped_inside_a_gqa_group(dev):
+    _needle_must_fail(dev, "flash_bwd", _swap_dout_heads, "gqa8-heads2")
+
+
 def test_comparator_itself():
     """The comparator on host arrays (also covered without a GPU by tests/test_oracle_golden.py)."""
     want = np.array([1.0, -np.inf, 2.0])
