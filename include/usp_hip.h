@@ -67,7 +67,8 @@ enum {
  *   forward            k.stride_s % 128 == 0 (elements);  k.stride_s, v.stride_s < 2^24   (v.stride_s % 128 is NOT needed:
  *                      the V pieces' offsets are sums -- tests/test_gpu_layouts.py::test_row64_stride_conditions_forward);
  *   backward, dQ       k.stride_s % 128 == 0 and v.stride_s % 128 == 0;  both < 2^24;
- *   backward, dK/dV    q.stride_s % 128 == 0 and dout.stride_s % 128 == 0;  both < 2^24;  fp16: softmax_scale * log2(e) <= 8.
+ *   backward, dK/dV    q.stride_s % 128 == 0 and dout.stride_s % 128 == 0;  both < 2^24   (either 16-bit type, any softmax_scale: K
+ *                      is never multiplied by the scale in the 16-bit type -- tests/test_gpu_range.py::test_fp16_edge).
  * Any other layout: USP_EUNSUPPORTED with USP_FORCE_ROW64 (nothing is launched or written), the other family's kernel for
  * that launch without it.  The 32-rows-per-wave family takes every aligned layout, with one bound: its dK/dV kernel
  * addresses the rows of a head by a 32-bit byte offset, so Sq * q.stride_s * 2 and Sq * dout.stride_s * 2 must stay below

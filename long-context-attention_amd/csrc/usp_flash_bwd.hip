@@ -219,7 +219,7 @@ static int launch_bwd(BwdArgsSC p, bool causal, hipStream_t st, int force, int s
   const bool want_dkdv = !(skip & USP_BWD_SKIP_DKDV), want_dq = !(skip & USP_BWD_SKIP_DQ);
   // per call, `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32 (include/usp_hip.h) picks the family; forced onto the 64-row
   // family, only the launches that will run have to be served
-  if ((force & USP_FORCE_ROW64) && !(D == 128 && (!want_dkdv || dkdv64_serves(p, DT)) && (!want_dq || dq64_serves(p))))
+  if ((force & USP_FORCE_ROW64) && !(D == 128 && (!want_dkdv || dkdv64_serves(p)) && (!want_dq || dq64_serves(p))))
     return USP_EUNSUPPORTED;
   // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
   const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on;
@@ -234,7 +234,7 @@ static int launch_bwd(BwdArgsSC p, bool causal, hipStream_t st, int force, int s
 static int cuts_of(int32_t n, bool packed) { return (packed || n < 2) ? 1 : (n > 8 ? 8 : n); }
 
 // Query heads of a KV group that ONE dK/dV work item streams into its accumulators (ABI v7: usp_bwd_args.dkdv_heads; a divisor
-// of G = Hq / Hkv).  More heads per item: K / V fragments, their pre-scale and the epilogue once per run of heads, fewer fp32
+// of G = Hq / Hkv).  More heads per item: K / V fragments and the epilogue once per run of heads, fewer fp32
 // partial slabs (none when the item takes the whole group and nothing is cut) and a shorter reduce; fewer heads: more items,
 // which is what balances a causal launch of few (batch, KV head, key block) triangles.  0 = the library decides, from what
 // was measured on MI355X (profiles/r06_gqa_loop.txt; dK/dV launch + reduce alone, G = 8):

@@ -13,7 +13,7 @@
 //   v[...]     S / dP of the two 32-row halves of the streamed tile x 2 key blocks (64), packed P / dS (32), fragments
 // so that every Q / dO fragment read from LDS serves TWO MFMAs (0.75 reads per MFMA) and the element work is 2.5 VALU per
 // MFMA.  A tile is 64 MFMA slots per wave:  chain(h0) | chain(h1) | grad(h0) | grad(h1)  (16 each); the 64 elements
-// (P = exp2(S c - lse) for A, dS = P (dP - delta) for B, + the 16-bit packs) stream through slots 16 .. 53 in the order the
+// (P = exp2((S - lse / scale) c) for A, dS = P (dP - delta) for B, + the 16-bit packs) stream through slots 16 .. 53 in the order the
 // gradient MFMAs need them, the tile's 8 LDS-DMA pieces (Q / dO tile two iterations ahead of B) through slots 0 .. 15.
 // MFMAs are inline asm (see usp_mfma64.hpp for why and for the hazards hipcc cannot see); tools/mfma_hazards.py checks
 // the emitted stream.
@@ -161,22 +161,18 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
 #endif
   }
 
-  // Role A's K fragments are pre-multiplied by scale * log2(e) (rounded to the 16-bit type once per item), so that the S
-  // chain, started from -lse * log2(e), ends in the exponent itself: P = exp2(chain) with no per-element multiply-add.
-  // Role B runs the same code with factor 1 (exact): no branch around registers the asm statements own.
+  // The fragments stay as loaded: K times scale * log2(e), rounded to the 16-bit type, carries an error of q_d k_d c 2^-9 per
+  // channel that does not cancel when one channel holds a large part of every score (and overflows fp16 for large K).  The S
+  // chain runs on K itself, started from -lse / scale, and the element stream multiplies by c = scale * log2(e) in fp32 in
+  // front of the exp2: P = exp2((q . k - lse / scale) c).
   {
-    const float kf = role == 0 ? p->scale_log2 : 1.f;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int t = 0; t < NKT; ++t) {
-        u32x4 x = rf[kb][t];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) x[e] = E::pack2(E::lo(x[e]) * kf, E::hi(x[e]) * kf);
-        rf[kb][t] = x;
-        pin_agpr4(rf[kb][t]);
-      }
+      for (int t = 0; t < NKT; ++t) pin_agpr4(rf[kb][t]);
   }
+  const float c2 = p->scale_log2;
+  const float neg_inv_scale = -__builtin_amdgcn_rcpf(p->scale);    // (1 ulp: 1e-5 in an exponent of 100)
 
   int t_begin = 0, t_end = (p->Sq + kTile - 1) / kTile;
   if (CAUSAL) {
@@ -190,7 +186,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
     t_end = t_begin + per < t_end ? t_begin + per : t_end;
   }
   // The item streams the tiles [t_begin, t_end) of `gsub` query heads of its KV group, one head behind the other, into
-  // the same accumulators (round 6: the GQA loop inside the workgroup -- K / V fragments, their pre-scale and the epilogue
+  // the same accumulators (round 6: the GQA loop inside the workgroup -- K / V fragments and the epilogue
   // once per KV head instead of once per query head, and with gsub == G no fp32 per-head partials and no reduce launch).
   // Head by head: the two-stage pipeline (role B one tile behind role A, the DMA one tile ahead) drains and refills between
   // heads -- about two tile times per head, against >= 64 tiles -- so that the streaming loops carry no head state at all:
@@ -259,12 +255,12 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
     else lds_dma16_asm(do_rs, lds_d + 4096 + dma_buf * BUFB, do_voff ^ (16 * i), 4096 + 4 * do_step + i * do_step, i);
   };
   // ... and behind the wave's vmcnt(0) at the end of the iteration stores what the roles consume, the constants their
-  // chains START from (the C operand of a chain's first MFMA): -lse * log2(e) for role A (-inf for a row without visible
+  // chains START from (the C operand of a chain's first MFMA): -lse / scale for role A (-inf for a row without visible
   // keys: P = 0) and -delta for role B
   auto stats_store = [&](int buf) {
     if (stat_wave) {
       asm volatile("" : "+v"(st_lse), "+v"(st_delta));         // (written by the asm loads above, complete behind dma_drain)
-      const float l2 = (st_in && st_lse != USP_NEG_INF) ? -st_lse * kLog2e : -__builtin_inff();
+      const float l2 = (st_in && st_lse != USP_NEG_INF) ? st_lse * neg_inv_scale : -__builtin_inff();
       *(USP_LDS float*)(smem + buf * BUFB + 2 * TILEB + 4 * lane) = l2;
       *(USP_LDS float*)(smem + buf * BUFB + 2 * TILEB + 4 * kTile + 4 * lane) = st_in ? -st_delta : 0.f;
     }
@@ -357,12 +353,12 @@ USP_TM(
         }
       };
       // element n of half h, in the order the gradient k-steps need them: n = 16*k2 + 8*kb + r8 -> sc[h][kb][8*k2 + r8]
-      // role A: P = exp2(S*c - lse2); role B: dS = P * (dP - delta) -- the dP chain STARTS from -delta (its C operand)
+      // role A: P = exp2((S - lse / scale) c); role B: dS = P * (dP - delta) -- the dP chain STARTS from -delta (its C operand)
       auto elem = [&](int h, int n) {
         const int k2 = n >> 4, kb = (n >> 3) & 1, r = 8 * k2 + (n & 7);
         float val;
         if (ROLE == 0) {
-          val = fast_exp2(sc[h][kb][r]);       // the chain computed (K * scale * log2 e) . q - lse * log2 e
+          val = fast_exp2(sc[h][kb][r] * c2);  // the chain computed k . q - lse / scale (-inf where masked: c2 > 0)
         } else {
           const uint32_t wd = pin[h][kb][k2][(r & 7) >> 1];
           val = ((r & 1) ? E::hi(wd) : E::lo(wd)) * sc[h][kb][r];
@@ -602,12 +598,10 @@ USP_TM(
   }  // next item
 }
 
-bool dkdv64_serves(const BwdParams& p_in, int dtype) {
+bool dkdv64_serves(const BwdParams& p_in) {
   if (p_in.seq_q || p_in.seq_k || p_in.sched || p_in.win_on) return false;
   // (fp16: round 4's first build of that instantiation copied accumulators between the register files inside the loop; with the
   // chains started from the row constants it compiles like the bf16 one -- tools/mfma_hazards.py: 0 -- and is served here too)
-  // role A keeps K * scale * log2(e) in the 16-bit type: with fp16 an unusually large softmax scale could overflow it
-  if (dtype != USP_BF16 && !(p_in.scale_log2 <= 8.f)) return false;
   // the pieces' swizzle is XORed into the per-lane byte offset (row part a multiple of 256 bytes); per-lane offsets and the
   // pieces' scalar offsets are 32-bit: 64 rows of Q / dO must span less than 2^31 bytes.  (Base pointer and remaining
   // bytes are 64-bit: no sequence length is refused -- the 8-wave kernel addresses a head by a 32-bit offset and is.)
@@ -617,7 +611,7 @@ bool dkdv64_serves(const BwdParams& p_in, int dtype) {
 }
 
 bool launch_dkdv64(const BwdParams& p_in, int dtype, bool causal, hipStream_t st, int* rc) {
-  if (!dkdv64_serves(p_in, dtype)) return false;
+  if (!dkdv64_serves(p_in)) return false;
   BwdParams p = p_in;
   p.wide16 = ((p.dk16 && !p.accum_dk && tensor_aligned(p.dk16, p.dk16_sb, p.dk16_ss, p.dk16_sh, 16, 8)) ? 2 : 0) |
              ((p.dv16 && !p.accum_dv && tensor_aligned(p.dv16, p.dv16_sb, p.dv16_ss, p.dv16_sh, 16, 8)) ? 4 : 0);

@@ -335,6 +335,25 @@ def test_needle_family_fails_on_dout_heads_swapped_inside_a_gqa_group(dev):
     _needle_must_fail(dev, "flash_bwd", _swap_dout_heads, "gqa8-heads2")
 
 
+# ------------------------------------------------------------------------------------------------
+# value-range inputs (tests/test_gpu_range.py): the REAL kernel is handed softmax_scale * 1.02, the reference keeps the scale
+# ------------------------------------------------------------------------------------------------
+def _scale_times_1_02(a):
+    a["softmax_scale"] = a["softmax_scale"] * 1.02
+
+
+@pytest.mark.parametrize("fn_name", ["flash_fwd", "flash_bwd"])
+@pytest.mark.parametrize("cid", ["offset-causal", "scale-0.3-w32"])
+def test_range_family_fails_on_a_scale_two_percent_off(dev, cid, fn_name):
+    import test_gpu_range as GR
+    run = GR.run_forward if fn_name == "flash_fwd" else GR.run_backward
+    run(dev, cid)                                           # the case itself passes
+    with altered(fn_name, _scale_times_1_02) as fired:
+        with pytest.raises(AssertionError, match="out of tolerance"):
+            run(dev, cid)
+    assert fired, f"the alteration of {fn_name} never fired in {cid}"
+
+
 def test_comparator_itself():
     """The comparator on host arrays (also covered without a GPU by tests/test_oracle_golden.py)."""
     want = np.array([1.0, -np.inf, 2.0])

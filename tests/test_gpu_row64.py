@@ -20,6 +20,7 @@ import torch
 
 from golden_util import TOL, assert_close, long_sum_atol, round_to
 from oracle import usp_oracle as O
+from rounding_models import bwd_16bit_model as _bwd_16bit_model
 
 pytestmark = pytest.mark.gpu
 
@@ -368,36 +369,6 @@ def test_default_dispatch_at_the_bench_shapes(dev):
 # ------------------------------------------------------------------------------------------------
 # the gradient tolerance floor of the fuzz sweeps, pinned (review of round 4, "a tolerance was widened")
 # ------------------------------------------------------------------------------------------------
-def _bwd_16bit_model(do, q, k, v, o16, lse, scale, causal, dt, prescale_k):
-    """fp64 restatement of the block backward WITH the two roundings every 16-bit flash backward performs: P is rounded
-    to the 16-bit type before dV = P^T dO (and dS is formed from that rounded P), dS is rounded before dQ = dS K and
-    dK = dS^T Q.  `prescale_k`: the 64-row dK/dV kernel also rounds K * scale * log2(e) once per item (usp_flash_bwd64.hip)."""
-    B, Sq, Hq, D = q.shape
-    Sk, Hkv = k.shape[1], k.shape[2]
-    g = Hq // Hkv
-    kk, vv = np.repeat(k, g, axis=2).astype(np.float64), np.repeat(v, g, axis=2).astype(np.float64)
-    qd, dod = q.astype(np.float64), do.astype(np.float64)
-    log2e = 1.4426950408889634
-    if prescale_k:
-        k2 = round_to((kk * (scale * log2e)).astype(np.float32), dt).astype(np.float64)
-        s2 = np.einsum("bthd,bshd->bhts", qd, k2, optimize=True)                 # exponent, base 2
-    else:
-        s2 = np.einsum("bthd,bshd->bhts", qd, kk, optimize=True) * (scale * log2e)
-    if causal:
-        row, col = np.arange(Sq)[:, None], np.arange(Sk)[None, :]
-        s2 = np.where(col > row + Sk - Sq, -np.inf, s2)
-    lse_safe = np.where(np.isfinite(lse), lse, 0.0)
-    p = np.where(np.isfinite(lse)[..., None], np.exp2(s2 - lse_safe[..., None] * log2e), 0.0)
-    p16 = round_to(p.astype(np.float32), dt).astype(np.float64)
-    dv = np.einsum("bhts,bthd->bshd", p16, dod, optimize=True).reshape(B, Sk, Hkv, g, D).sum(3)
-    dp = np.einsum("bthd,bshd->bhts", dod, vv, optimize=True)
-    delta = np.einsum("bthd,bthd->bht", dod, o16.astype(np.float64))
-    ds16 = round_to((p16 * (dp - delta[..., None])).astype(np.float32), dt).astype(np.float64)
-    dq = np.einsum("bhts,bshd->bthd", ds16, kk, optimize=True) * scale
-    dk = (np.einsum("bhts,bthd->bshd", ds16, qd, optimize=True) * scale).reshape(B, Sk, Hkv, g, D).sum(3)
-    return dq, dk, dv
-
-
 def test_long_sum_gradient_noise_is_that_of_16bit_products(dev):
     """Seed 5000+x of the round-4 sweep (B2 Sq1191 Sk10 Hq8 Hkv2 D128, full attention) misses `atol + rtol |want|` on dK:
     every dK entry sums Sq * G = 4764 products of 16-bit-rounded factors (ten keys: P is not small), so its absolute
@@ -406,8 +377,9 @@ def test_long_sum_gradient_noise_is_that_of_16bit_products(dev):
       (1) BOTH kernel families miss the un-floored bound on this case, and by the same amount (within 35 %);
       (2) against the same arithmetic with P and dS rounded to 16 bits (`_bwd_16bit_model`) both pass the UN-FLOORED
           bound with half of it to spare -- the miss is the rounding of the products, not the kernels' sums;
-      (3) the 64-row dK/dV kernel's extra rounding (K * scale * log2 e in bf16) stays below 1.6x the other family's dV
-          error against exact arithmetic (round 4 measured 3.2e-2 -> 5.3e-2 at S = 65536, G = 8; this is its guard)."""
+      (3) the 64-row dK/dV kernel's dV error against exact arithmetic stays below 1.6x the other family's (the guard of the
+          extra rounding that kernel had until tests/test_gpu_range.py -- K * scale * log2 e in bf16, round 4 measured
+          3.2e-2 -> 5.3e-2 at S = 65536, G = 8; both families now follow the same model)."""
     from yunchang_amd import _C
     from golden_util import close_mask
     B, Sq, Sk, Hq, Hkv, D, causal, dt = 2, 1191, 10, 8, 2, 128, False, "bfloat16"
@@ -440,8 +412,9 @@ def test_long_sum_gradient_noise_is_that_of_16bit_products(dev):
     assert abs(miss["row64"] - miss["wave32"]) <= 0.35 * max(miss.values()), miss
     # (2) against 16-bit-rounded products both pass the un-floored bound, with room
     for fam in got:
-        model = _bwd_16bit_model(do, q, k, v, o16, rl, scale, causal, dt, prescale_k=fam == "row64")
+        model = _bwd_16bit_model(do, q, k, v, o16, rl, scale, causal, dt, prescale_k=False)
         for g_, m_, n_ in zip(got[fam], model, ("dq", "dk", "dv")):
             assert_close(g_, m_, atol / 2, rtol / 2, f"{fam} {n_} against the 16-bit-product model")
-    # (3) the pre-scaled K of the 64-row dK/dV kernel
+    # (3) the guard of the 64-row dK/dV kernel's former extra rounding (K * scale * log2 e in bf16; gone: the kernel now follows
+    # the same model as the other family, tests/test_gpu_range.py)
     assert err["row64"][2] <= 1.6 * err["wave32"][2] + 1e-3, err

@@ -473,20 +473,17 @@ def test_needle_conditions_of_the_gpu_large_cases(cid):
 # ---------------------------------------------------------------------------------------------------------------------
 # honest 16-bit rounding on needle inputs: the model the amplitude of dout was lowered against
 # ---------------------------------------------------------------------------------------------------------------------
-def bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, causal, dt, prescale_k):
-    """The block backward in fp64 WITH the roundings every 16-bit flash backward performs (as
-    test_gpu_row64._bwd_16bit_model): P is rounded to the 16-bit type before dV = P^T dO and dS is formed from that P,
-    dS is rounded before dQ = dS K and dK = dS^T Q; `prescale_k`: the 64-row dK/dV kernel also rounds K * scale * log2(e)."""
+def bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, causal, dt):
+    """The block backward in fp64 WITH the roundings every 16-bit flash backward performs (rounding_models.bwd_16bit_model
+    without the pre-scaled K, in torch: 5 x faster than the numpy one on the 2^24-score cases of this file): P is rounded to
+    the 16-bit type before dV = P^T dO and dS is formed from that P, dS is rounded before dQ = dS K and dK = dS^T Q."""
     B, Sq, Hq, D = tq.shape
     Sk, Hkv = tk.shape[1], tk.shape[2]
     G = Hq // Hkv
     q, do = tq.double(), tdo.double()
     k, v = tk.double().repeat_interleave(G, 2), tv.double().repeat_interleave(G, 2)
     log2e = 1.4426950408889634
-    if prescale_k:
-        s2 = torch.einsum("bthd,bshd->bhts", q, (k * (scale * log2e)).to(dt).double())
-    else:
-        s2 = torch.einsum("bthd,bshd->bhts", q, k) * (scale * log2e)
+    s2 = torch.einsum("bthd,bshd->bhts", q, k) * (scale * log2e)
     if causal:
         i, j = torch.arange(Sq)[:, None] + Sk - Sq, torch.arange(Sk)[None, :]
         s2 = s2.masked_fill(j > i, float("-inf"))
@@ -521,7 +518,7 @@ def test_16bit_rounding_model_keeps_a_2x_margin_on_the_gpu_cases(c):
     ro, rl = ref_fwd(tq, tk, tv, scale, c.causal)
     o16 = ro.to(dt)
     rdq, rdk, rdv, _ = ref_bwd(tdo, tq, tk, tv, o16, rl, scale, c.causal)
-    got = bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, c.causal, dt, prescale_k=c.bwd is None or "dkdv_row64" in c.bwd)
+    got = bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, c.causal, dt)
     ver = NI.verdicts({n_: t.numpy() for n_, t in got.items()}, dict(dq=rdq.numpy(), dk=rdk.numpy(), dv=rdv.numpy()),
                       c.dt, c.Sq, c.Sk, c.Hq // c.Hkv)
     assert all(ratio <= 0.5 for _, ratio in ver.values()), (c.id, ver)
