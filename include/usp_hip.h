@@ -90,6 +90,18 @@ enum {
  * 64-row family declines it; unforced, such calls run on the two-waves-per-SIMD kernels).  usp_attn_features() tells a
  * binding whether the library it loaded serves the bit. */
 #define USP_ATTN_SOFTCAP 64
+/* USP_ATTN_SHIFT: the `mask_shift` field is valid and the diagonal of the mask moves by it: (Sk - Sq) is replaced by
+ * (Sk - Sq + mask_shift) in the causal bound and in both window bounds, so query row i sees key j iff
+ *     i + (Sk - Sq + mask_shift) - window_left <= j <= i + (Sk - Sq + mask_shift) + window_right      (causal: window_right = 0)
+ * -- the mask of ONE block of a sequence that is split over a ring (the reference has no such argument: it hands the same
+ * `window_size` to every block, yunchang/ring/ring_flash_attn.py:36-48, which is a different function).  Any value with
+ * |mask_shift| < 2^30 is served (USP_EINVAL beyond): rows, or a whole launch, that see no key give out = 0, lse = -inf and
+ * zero gradients, as an empty row does without the bit.  A shift with neither `causal` nor a window bounds nothing and is
+ * ignored.  Dense launches only: a packed batch with the bit is USP_EUNSUPPORTED.  The 64-row family serves a shifted launch
+ * exactly where it serves the same launch unshifted (no left window bound).  Without the bit the field is ignored; a binding
+ * built before it never sets the bit, and the field lies in what was padding (behind softmax_scale), so such a binding's struct
+ * has the same size and offsets and is never read past; usp_attn_features() reports the bit. */
+#define USP_ATTN_SHIFT 128
 
 typedef struct usp_tensor {
   void* ptr;
@@ -141,6 +153,9 @@ typedef struct usp_fwd_args {
   int32_t B, Sq, Sk, Hq, Hkv, D;
   int32_t causal;                /* 0 | 1 (bottom-right aligned) */
   float softmax_scale;           /* > 0 */
+  int32_t mask_shift;            /* read only with USP_ATTN_SHIFT in `flags`: added to (Sk - Sq) in every mask bound (see the
+                                    flag).  It occupies the four bytes that used to be padding in front of the 8-byte aligned
+                                    `q`: every other offset and sizeof are those of ABI v7's first release */
   usp_tensor q, k, v;            /* inputs */
   usp_tensor out;                /* 16-bit output rows (final rows only); ptr may be NULL */
   usp_tensor acc;                /* fp32 running output; ptr may be NULL */
@@ -206,6 +221,7 @@ typedef struct usp_bwd_args {
   int32_t B, Sq, Sk, Hq, Hkv, D;
   int32_t causal;
   float softmax_scale;
+  int32_t mask_shift;            /* as in usp_fwd_args, in the same former padding; read only with USP_ATTN_SHIFT in `flags` */
   usp_tensor dout, q, k, v;      /* 16-bit inputs */
   const float* lse;              /* (B,Hq,Sq), seq stride 1 */
   const float* delta;            /* (B,Hq,Sq), seq stride 1 */
@@ -336,7 +352,7 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
                    float* sink, uint64_t* clocks, void* stream);
 
 int usp_abi_version(void);
-/* The USP_ATTN_* flag bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP).  Unknown flag bits are not rejected by
+/* The USP_ATTN_* flag bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -26,6 +26,7 @@ USP_FORCE_WAVE32 = 8           # ... or by the two-waves-per-SIMD (32 rows per w
 USP_BWD_SKIP_DQ = 16           # usp_flash_bwd: only the dK/dV launch ...
 USP_BWD_SKIP_DKDV = 32         # ... only the dQ launch
 USP_ATTN_SOFTCAP = 64          # the softcap field is valid: scores are capped to softcap * tanh(S / softcap)
+USP_ATTN_SHIFT = 128           # the mask_shift field is valid: (Sk - Sq) + mask_shift places the diagonal of every mask bound
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -70,7 +71,7 @@ class UspFwdArgs(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Sq", ctypes.c_int32),
                 ("Sk", ctypes.c_int32), ("Hq", ctypes.c_int32), ("Hkv", ctypes.c_int32),
                 ("D", ctypes.c_int32), ("causal", ctypes.c_int32),
-                ("softmax_scale", ctypes.c_float),
+                ("softmax_scale", ctypes.c_float), ("mask_shift", ctypes.c_int32),
                 ("q", UspTensor), ("k", UspTensor), ("v", UspTensor),
                 ("out", UspTensor), ("acc", UspTensor),
                 ("lse", ctypes.c_void_p), ("lse_stride_b", ctypes.c_int64),
@@ -87,7 +88,7 @@ class UspBwdArgs(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("B", ctypes.c_int32), ("Sq", ctypes.c_int32),
                 ("Sk", ctypes.c_int32), ("Hq", ctypes.c_int32), ("Hkv", ctypes.c_int32),
                 ("D", ctypes.c_int32), ("causal", ctypes.c_int32),
-                ("softmax_scale", ctypes.c_float),
+                ("softmax_scale", ctypes.c_float), ("mask_shift", ctypes.c_int32),
                 ("dout", UspTensor), ("q", UspTensor), ("k", UspTensor), ("v", UspTensor),
                 ("lse", ctypes.c_void_p), ("delta", ctypes.c_void_p),
                 ("lse_stride_b", ctypes.c_int64), ("lse_stride_h", ctypes.c_int64),
@@ -327,14 +328,37 @@ def _set_softcap(a, cap: Optional[float]):
     a.softcap = cap
 
 
+def _set_shift(a, shift: Optional[int]):
+    """Set USP_ATTN_SHIFT + the field on an argument block (None = off); a library that does not report the bit would
+    ignore it silently and compute another mask, so it is refused here."""
+    if shift is None:
+        return
+    L = load()
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_SHIFT):
+        raise RuntimeError(f"{_LIB_PATH} does not serve a mask shift (USP_ATTN_SHIFT): rebuild it")
+    a.flags |= USP_ATTN_SHIFT
+    a.mask_shift = int(shift)
+
+
+def _shift(shift) -> Optional[int]:
+    """`shift` argument -> int, or None when it is off.  (0 is a valid shift and sets the bit: the call decodes like an
+    unshifted one.)"""
+    if shift is None:
+        return None
+    s = int(shift)
+    if abs(s) >= 1 << 30:
+        raise ValueError(f"shift must lie inside (-2^30, 2^30), got {shift!r}")
+    return s
+
+
 def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end, interleave, n, window=None,
-              family_flag=0, softcap=None):
+              family_flag=0, softcap=None, shift=None):
     """The filled usp_fwd_args block of a dense launch.  Everything but the seven pointers is a function of
     (dtype, shapes, strides, flags), and a training loop issues the same few launches over and over: the block is
     cached per thread under that signature and only the pointers are patched (filling 27 ctypes fields and five
     usp_tensor structs costs ~35 us of host time per launch, tools/host_step_cpu.py; a hit costs ~8)."""
     key = (q.dtype, q.shape, q.stride(), k.shape, k.stride(), v.stride(), lse.stride(), _strides(out), _strides(acc),
-           softmax_scale, causal, merge_in, final_begin, final_end, interleave, n, window, family_flag, softcap)
+           softmax_scale, causal, merge_in, final_begin, final_end, interleave, n, window, family_flag, softcap, shift)
     cache = _TLS.__dict__.setdefault("fwd", {})
     a = cache.get(key)
     if a is None:
@@ -354,6 +378,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
             a.flags |= USP_ATTN_WINDOW
             a.window_left, a.window_right = window
         _set_softcap(a, softcap)
+        _set_shift(a, shift)
         a.k_splits = n if n > 1 else 0
         if len(cache) >= _ARGS_CACHE_MAX:
             cache.clear()
@@ -367,20 +392,27 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
-              interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None):
+              interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
     window_size (left, right), None / (-1, -1) = none.  `family`: "row64" | "wave32" pins the kernel family of this call
     (ABI v6; None: set_kernel_family's default, normally "auto"); both families serve a K split.  `softcap`: flash-attn's
-    logit soft-capping, None / 0 = off (softcap_value; the 64-row family declines it: family="row64" then fails)."""
+    logit soft-capping, None / 0 = off (softcap_value; the 64-row family declines it: family="row64" then fails).
+    `shift` (None | int, USP_ATTN_SHIFT): moves the diagonal of the causal and window bounds, row i sees key j iff
+    i + (Sk - Sq + shift) - left <= j <= i + (Sk - Sq + shift) + right -- the mask of one block of a ring (ring/window_blocks.py).
+    A shifted launch gets no automatic K split (fwd_k_splits sizes cuts for a causal triangle)."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
     cap = softcap_value(softcap)
     ff = _family_flag(family)
-    n = fwd_k_splits(B, Sq, Hq, causal) if k_splits is None else int(k_splits)
+    win, sh = _window(window), _shift(shift)
+    if k_splits is None:
+        n = 0 if sh is not None else fwd_k_splits(B, Sq, Hq, causal)
+    else:
+        n = int(k_splits)
     a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
-                  bool(interleave), n, _window(window), ff, cap)
+                  bool(interleave), n, win, ff, cap, sh)
     L = load()
     if n > 1:
         # scratch for the partial results: one buffer per (device, stream), grown on demand; launches on one stream
@@ -509,13 +541,14 @@ def bwd_delta(dout, out, delta):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None):
+              softcap=None, shift=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
     flash-attn's window_size (left, right), None / (-1, -1) = none.  `family`: as flash_fwd.  `only`: "dkdv" | "dq" issues
     just that launch of the two (ABI v6: USP_BWD_SKIP_DQ / USP_BWD_SKIP_DKDV).  `dkdv_heads` (ABI v7): query heads of a KV
-    group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`: as flash_fwd."""
+    group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`, `shift`: as flash_fwd (a
+    shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle)."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -536,13 +569,18 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     a.accum_dq, a.accum_dk, a.accum_dv = int(bool(accum_dq)), int(bool(accum_dk)), int(bool(accum_dv))
     ff = _family_flag(family)
     a.flags = (USP_LAUNCH_INTERLEAVE if interleave else 0) | ff | {None: 0, "dkdv": USP_BWD_SKIP_DQ, "dq": USP_BWD_SKIP_DKDV}[only]
-    a.dq_splits, a.dkdv_splits = bwd_splits(B, Sq, Sk, Hq, bool(causal)) if splits is None else splits
+    sh = _shift(shift)
+    if splits is None:
+        a.dq_splits, a.dkdv_splits = (0, 0) if sh is not None else bwd_splits(B, Sq, Sk, Hq, bool(causal))
+    else:
+        a.dq_splits, a.dkdv_splits = splits
     a.dkdv_heads = int(dkdv_heads)
     win = _window(window)
     if win is not None:
         a.flags |= USP_ATTN_WINDOW
         a.window_left, a.window_right = win
     _set_softcap(a, cap)
+    _set_shift(a, sh)
     L = load()
     need = L.usp_flash_bwd_workspace_bytes(ctypes.byref(a))     # GQA head split and / or cuts of few-item launches
     ws = None

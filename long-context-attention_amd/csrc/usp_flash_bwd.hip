@@ -316,7 +316,7 @@ extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) {
       !ok32(a->dq) || !ok32(a->dk) || !ok32(a->dv) || !ok16(a->dq16) || !ok16(a->dk16) || !ok16(a->dv16))
     return USP_EUNSUPPORTED;
   const Mask mask = decode_mask(*a);
-  if (packed && mask.windowed) return USP_EUNSUPPORTED;        // dense launches only
+  if (packed && (mask.windowed || mask.shifted)) return USP_EUNSUPPORTED;        // dense launches only
   if (a->dq_splits < 0 || a->dq_splits > 8 || a->dkdv_splits < 0 || a->dkdv_splits > 8) return USP_EINVAL;
   const BwdPlan plan = plan_bwd(a);
   if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)

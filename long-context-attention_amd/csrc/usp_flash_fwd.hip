@@ -29,17 +29,27 @@ namespace usp {
 // which replaces the raw score tile by cap*tanh(S/cap) (in exp2 units) BEFORE the mask -- tanh(-inf) = -1, a key masked
 // first would keep a weight -- and runs the online softmax with c = 1.  The body is shared by two __global__ templates
 // so that the kernels without softcap keep their symbol names and machine code.
+// WIN: a left window bound (USP_ATTN_WINDOW with window_left >= 0) has its own instantiation, flash_fwd_window_kernel (KSPLIT
+// form): there the tiles no bound cuts for a wave take the hand-pinned main loop (rotated tile walk, see the body); in the
+// other kernels a left bound -- softcap launches still carry one -- sends every tile through the generic loop.
 
 template <int D, int DT, bool CAUSAL, int NWAVES, bool KSPLIT = false>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_kernel(const FwdArgsT<KSPLIT> p_in) {
-  constexpr bool SC = false;
+  constexpr bool SC = false, WIN = false;
+  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
+#include "usp_flash_fwd_body.inc"
+}
+
+template <int D, int DT, bool CAUSAL, int NWAVES>
+__global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_window_kernel(const FwdArgsT<true> p_in) {
+  constexpr bool KSPLIT = true, SC = false, WIN = true;
   constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
 #include "usp_flash_fwd_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_softcap_kernel(const FwdArgsSC p_in) {
-  constexpr bool KSPLIT = true, SC = true;
+  constexpr bool KSPLIT = true, SC = true, WIN = false;
   const float sc_cl2 = p_in.cap_log2, sc_k2 = p_in.tanh_k2;
 #include "usp_flash_fwd_body.inc"
 }
@@ -126,7 +136,9 @@ static int launch_fwd_w(FwdArgsSC p, bool causal, hipStream_t st) {
     constexpr bool C = decltype(c)::value;
     if (p.cap_on)
       hipLaunchKernelGGL((flash_fwd_softcap_kernel<D, DT, C, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, p);
-    else if (p.ksplit > 1 || p.win_on)
+    else if (p.win_on)
+      hipLaunchKernelGGL((flash_fwd_window_kernel<D, DT, C, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, ps);
+    else if (p.ksplit > 1)
       hipLaunchKernelGGL((flash_fwd_kernel<D, DT, C, NWAVES, true>), dim3(grid), dim3(64 * NWAVES), lds, st, ps);
     else
       hipLaunchKernelGGL((flash_fwd_kernel<D, DT, C, NWAVES>), dim3(grid), dim3(64 * NWAVES), lds, st, plain);
@@ -203,7 +215,7 @@ extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) {
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k)) return USP_EINVAL;
   const Mask mask = decode_mask(*a);
-  if (packed && mask.windowed) return USP_EUNSUPPORTED;        // dense launches only
+  if (packed && (mask.windowed || mask.shifted)) return USP_EUNSUPPORTED;        // dense launches only
   const int f_all = packed ? 2 : a->Sq;          // packed: final_begin/_end count half sequences (0,1,2)
   int fb = a->final_begin < 0 ? 0 : a->final_begin;
   int fe = a->final_end > f_all ? f_all : a->final_end;

@@ -1,7 +1,8 @@
 // Body of flash_fwd_kernel / flash_fwd_softcap_kernel (usp_flash_fwd.hip): one workgroup = NWAVES x 32 query rows.
 // Included as the body of the kernel templates in usp_flash_fwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps.  The including kernel defines `p_in`, KSPLIT / SC and sc_cl2 / sc_k2.
+// the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones.  The including kernel defines `p_in`,
+// KSPLIT / SC / WIN and sc_cl2 / sc_k2.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int kThreads = 64 * NWAVES;
@@ -135,9 +136,28 @@
     n_full = nf < n_full ? nf : n_full;
   }
   if (qw + 32 > p.Sq) n_full = 0;                         // ragged / inactive waves take the generic loop
-  if constexpr (KSPLIT) { if (win) n_full = 0; }          // a left window bound: every tile through the masked loop
+  if constexpr (KSPLIT && !WIN) { if (win) n_full = 0; }  // a left window bound outside the window kernel: every tile through the masked loop
   if constexpr (SC) n_full = 0;                           // softcap: every tile through the generic loop
   if (n_full > nt) n_full = nt;
+  // WIN (flash_fwd_window_kernel: every launch has a left bound): the tiles are walked in the ROTATED order [rot, nt) then
+  // [0, rot) -- online softmax does not care -- where rot is the workgroup-uniform number of leading tiles the left bound
+  // cuts for ANY wave of the workgroup (kt0 < last row + win_lo).  Walk index j holds tile tmap(j); the tiles [rot, n_full) of
+  // the unrotated count are then cut by no bound for this wave and take the pipelined main loop as walk indices
+  // [0, n_full - rot); the generic tail takes the diagonal tiles and then the `rot` leading ones.  Every wave walks the same
+  // order (the barriers and the K/V buffers are per walk index), only n_full differs per wave, as ever.
+  int rot = 0;
+  if constexpr (WIN) {
+    const int lcut = q0 + kBM - 1 + win_lo;
+    rot = lcut > 0 ? (lcut + kBN - 1) / kBN : 0;
+    if (rot >= nt) { rot = 0; n_full = 0; }               // the left bound cuts every tile
+    else n_full = n_full > rot ? n_full - rot : 0;
+  }
+  auto tmap = [&](int j) {
+    if constexpr (WIN) { const int t = j + rot; return t < nt ? t : t - nt; }
+    else return j;
+  };
+  // does this wave have a visible key in the tile that starts at key kt0?  (WIN only: also skips tiles wholly left of the wave's window)
+  auto tile_live = [&](int kt0) { return kt0 < wave_kv_end && kt0 + kBN > qw + win_lo; };
 
   // ---- Q fragments (B operand: lane holds Q[row][16t + 8hi .. +7]) ---------------------------
   u32x4 qf[NKT];
@@ -306,12 +326,13 @@
 #pragma unroll
   for (int r = 0; r < 16; ++r) { sa[r] = 0.f; sb[r] = 0.f; }
   if (nt > 0) {
-    dma_k(0, 0); dma_v(0, 0);
-    if (nt > 1) dma_k(1, 1);
+    dma_k(tmap(0), 0); dma_v(tmap(0), 0);
+    if (nt > 1) dma_k(tmap(1), 1);
   }
   dma_drain();
   __syncthreads();
-  if (nt > 0 && wave_kv_end > 0) qk(0, sa, sb);
+  if constexpr (WIN) { if (nt > 0 && tile_live(tmap(0) * kBN)) qk(0, sa, sb); }
+  else { if (nt > 0 && wave_kv_end > 0) qk(0, sa, sb); }
   // K(0) must have been read by EVERY wave before the first loop iteration refills Kbuf[0] with K(2): a
   // wave that skips qk(0) (no valid rows) reaches that DMA at once, and a mostly out-of-range K(2) tile
   // (short sequences) lands immediately -- observed as rare small errors on ragged shapes.
@@ -357,8 +378,8 @@
   // one pipelined iteration: softmax + PV of tile jj (scores in ca/cb), scores of tile jj+1 into na/nb
   auto iter = [&](int jj, f32x16& ca, f32x16& cb, f32x16& na, f32x16& nb) {
     const int jk = jj + 2 < nt ? jj + 2 : nt - 1;           // clamped prefetch (redundant load at the end)
-    dma_k(jk, jj & 1);            // Kbuf[jj&1] held K(jj): last read in the previous iteration
-    dma_v(jj + 1, (jj + 1) & 1);  // Vbuf[(jj+1)&1] held V(jj-1): last read in the previous iteration
+    dma_k(tmap(jk), jj & 1);            // Kbuf[jj&1] held K(jj): last read in the previous iteration
+    dma_v(tmap(jj + 1), (jj + 1) & 1);  // Vbuf[(jj+1)&1] held V(jj-1): last read in the previous iteration
     // ---------------- phase A ----------------
     USP_LDS const char* kb = smem + ((jj + 1) & 1) * KBYTES + k_rd_row;
     u32x4 ka[NKT], kc[NKT];
@@ -473,14 +494,21 @@
   }
   // ---- generic tail: masked and/or inactive tiles ---------------------------------------------------
   for (; j < nt; ++j) {
-    const int kt0 = j * kBN;
-    if (j + 2 < nt) dma_k(j + 2, j & 1);
-    if (j + 1 < nt) dma_v(j + 1, (j + 1) & 1);
+    const int kt0 = tmap(j) * kBN;
+    if (j + 2 < nt) dma_k(tmap(j + 2), j & 1);
+    if (j + 1 < nt) dma_v(tmap(j + 1), (j + 1) & 1);
     f32x16 na, nb;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { na[r] = 0.f; nb[r] = 0.f; }
-    if (j + 1 < nt && kt0 + kBN < wave_kv_end) qk((j + 1) & 1, na, nb);
-    if (kt0 < wave_kv_end) {
+    bool live;
+    if constexpr (WIN) {
+      if (j + 1 < nt && tile_live(tmap(j + 1) * kBN)) qk((j + 1) & 1, na, nb);
+      live = tile_live(kt0);
+    } else {
+      if (j + 1 < nt && kt0 + kBN < wave_kv_end) qk((j + 1) & 1, na, nb);
+      live = kt0 < wave_kv_end;
+    }
+    if (live) {
       bool need_mask = (kt0 + kBN > p.Sk) || (CAUSAL && kt0 + kBN - 1 > qw + off);
       if constexpr (KSPLIT) need_mask = need_mask || (win && kt0 < qw + 31 + win_lo);
       if constexpr (SC) {

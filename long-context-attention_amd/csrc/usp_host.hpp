@@ -76,6 +76,7 @@ template <class Args> int check_problem(const Args& a) {
   const bool has_cap = (a.flags & USP_ATTN_SOFTCAP) != 0;     // (the field is read only with the bit)
   if (has_cap && !(__builtin_isfinite(a.softcap) && a.softcap > 0.f)) return USP_EINVAL;
   if (has_cap && (a.flags & USP_FORCE_ROW64)) return USP_EUNSUPPORTED;   // the 64-row family declines softcap
+  if ((a.flags & USP_ATTN_SHIFT) && (a.mask_shift >= (1 << 30) || a.mask_shift <= -(1 << 30))) return USP_EINVAL;
   if (a.D != 32 && a.D != 64 && a.D != 128) return USP_EUNSUPPORTED;
   if (a.Hq % a.Hkv != 0) return USP_EUNSUPPORTED;
   return USP_OK;
@@ -86,6 +87,7 @@ template <class Args> int check_problem(const Args& a) {
 // (forward: the split instantiation, FwdSplit).
 struct Mask {
   bool causal;                  // the causal instantiation runs: a.causal, or a right window bound
+  bool shifted;                 // USP_ATTN_SHIFT is set: dense launches only
   bool windowed;                // a bound beyond plain causal: dense launches only
   int causal_off, win_on, win_lo, cap_on;
   float cap_log2, tanh_k2;
@@ -104,6 +106,13 @@ template <class Args> Mask decode_mask(const Args& a) {
   m.causal_off = a.Sk - a.Sq + (wr > 0 ? wr : 0);
   m.win_on = wl >= 0 ? 1 : 0;
   m.win_lo = a.Sk - a.Sq - (wl >= 0 ? wl : 0);
+  // USP_ATTN_SHIFT moves the diagonal both bounds hang on, and nothing else: to the kernels it is another causal_off / win_lo
+  // (they clamp every tile range they derive from the two, so offsets below -Sq or above Sk are empty / unmasked ranges).
+  // Without a bound there is nothing to move.
+  const int shift = ((a.flags & USP_ATTN_SHIFT) && (m.causal || m.win_on)) ? a.mask_shift : 0;
+  m.causal_off += shift;
+  m.win_lo += shift;
+  m.shifted = (a.flags & USP_ATTN_SHIFT) != 0;
   m.cap_on = has_cap ? 1 : 0;
   m.cap_log2 = has_cap ? a.softcap * kLog2e : 0.f;
   m.tanh_k2 = has_cap ? 2.f * a.softmax_scale * kLog2e / a.softcap : 0.f;

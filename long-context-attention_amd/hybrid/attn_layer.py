@@ -119,8 +119,8 @@ class LongContextAttention(_USPLayer):
             return out[..., :D]
         ng_cap = self._packed_exchange(query, key)
         if ng_cap is not None and window_of(window_size) is not None:
-            ng_cap = None         # a sliding window: the reference's structure (three exchanges); the ring function
-                                  # serves it at ring degree 1 and refuses beyond (ring/ring_flash_attn.py)
+            ng_cap = None         # a sliding window: the reference's structure (three exchanges); the basic ring function
+                                  # serves it at ring degree 1 and, with USP_RING_WINDOW=global, beyond (ring/ring_flash_attn.py)
         if ng_cap is not None:
             assert alibi_slopes is None
             _check_hot_path_args(dropout_p, window_size, softcap)

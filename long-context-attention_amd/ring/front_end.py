@@ -15,7 +15,10 @@ def _check_hot_path_args(dropout_p, window_size, softcap):
     if dropout_p not in (0, 0.0):
         raise NotImplementedError("dropout_p != 0 is not supported by the HIP ring attention")
     if window_size is not None and tuple(window_size) != (-1, -1):
-        raise NotImplementedError("sliding-window attention is not supported by the HIP ring attention")
+        raise NotImplementedError("sliding-window attention is not supported by this HIP ring attention (zigzag, stripe and "
+                                  "varlen rings, the async layer): use the basic ring (ring_impl_type=\"basic\", "
+                                  "ring_flash_attn_func), which serves a window at ring degree 1 and, with "
+                                  "USP_RING_WINDOW=global, across ring steps")
     softcap_value(softcap)
 
 

@@ -5,7 +5,13 @@ ring rank r-s; under causal only steps <= r compute and only step 0 is causal.  
 (BASELINE configs C2, C3) this is one kernel call.  The MI355X-first differences are those listed
 in zigzag_ring_flash_attn.py (fused merge, fp32 in-place gradient accumulation, K/V relay on a
 side stream); additionally dq is returned in q.dtype (the reference hard-codes bfloat16 at :147).
+
+A sliding window (`window_size`) is one windowed block at ring degree 1; at ring degree > 1 it is served on request
+(USP_RING_WINDOW=global) over GLOBAL positions: only the blocks the window touches are fetched, launched and returned, each
+with its own shifted bounds (ring/window_blocks.py).
 """
+import os
+
 import torch
 import torch.distributed as dist
 
@@ -13,18 +19,32 @@ from ..kernels import AttnType
 from ..kernels.attention import get_block_backend, window_of
 from . import block_pieces
 from .front_end import ring_front_end
-from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
+from .utils import FULL, KVRelay, group_info, final_grads, return_dkdv_direct, travel_dkdv
+from .window_blocks import WindowPlan
+
+
+def ring_window_mode() -> str:
+    """USP_RING_WINDOW, read per call: "global" serves a sliding window at ring degree > 1 with GLOBAL semantics (row i of
+    the whole sequence sees key j iff i - left <= j <= i + right); anything else (the default) refuses."""
+    return os.environ.get("USP_RING_WINDOW", "").strip().lower()
 
 
 def _ring_window(window_size, P):
     """flash-attn's window_size -> (left, right) | None.  A window is served where the ring has ONE block (ring degree
-    1: the Ulysses-only layouts, the single-GPU path); across ring steps every block would need its own shifted bounds
-    (the reference hands the same `window_size` to every block, kernels/attention.py:165-202 -- correct at ring degree
-    1 only) and this package refuses instead of computing something else."""
+    1: the Ulysses-only layouts, the single-GPU path).  Across ring steps every block needs its own shifted bounds
+    (ring/window_blocks.py; the reference hands the same `window_size` to every block, kernels/attention.py:165-202 --
+    correct at ring degree 1 only, a different function beyond).  That is served on request, USP_RING_WINDOW=global: a
+    caller who comes from the reference gets an error, not other numbers, until they ask."""
     win = window_of(window_size)
-    if win is not None and P > 1:
-        raise NotImplementedError("sliding-window attention across ring steps (ring degree > 1) is not supported")
+    if win is not None and P > 1 and ring_window_mode() != "global":
+        raise NotImplementedError("sliding-window attention across ring steps (ring degree > 1) is not supported by default: "
+                                  "set USP_RING_WINDOW=global for a window over GLOBAL positions on the basic ring (the "
+                                  "reference applies the same window to every block instead, a different function)")
     return win
+
+
+def _window_plan(win, P, r, c, causal):
+    return WindowPlan(P, c, bool(causal), win[0], win[1], r)
 
 
 def _window_kw(win):
@@ -67,8 +87,19 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=dev)
     win = _ring_window(window_size, P)
-    if win is not None:              # ring degree 1: one block, the kernels take flash-attn's window (left, right)
+    if win is not None and P == 1:   # ring degree 1: one block, the kernels take flash-attn's window (left, right)
         be.fwd(q, k, v, softmax_scale, bool(causal), lse, out, window=win)
+        return out, lse
+    if win is not None:              # USP_RING_WINDOW=global: only the blocks the window touches, each with its own bounds
+        assert k.shape[1] == S, "the basic ring holds equally long chunks of q and k"
+        plan = _window_plan(win, P, r, S, causal)
+        acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if len(plan.steps) > 1 else None
+        with KVRelay(process_group, k, v, recv_steps=plan.recv, send_steps=plan.send) as relay:
+            for i, step in enumerate(plan.steps):
+                kk, vv = relay.get(step)
+                blk = plan.block(step)
+                be.fwd(q, kk, vv, softmax_scale, blk.causal, lse, out, acc, i > 0, 0, S if step == plan.steps[-1] else 0,
+                       **blk.launch_kw())
         return out, lse
     last_compute = r if causal else P - 1
     acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if last_compute > 0 else None
@@ -100,8 +131,21 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
         be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale, bool(causal),
                dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)))
         return dq, dk, dv
-    _ring_window(window_size, P)
+    win = _ring_window(window_size, P)
     dq_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev)
+    if win is not None:              # USP_RING_WINDOW=global: every block straight to its owner, only the rows it has gradients for
+        # (`defer` is not used here: it hands the travelling accumulators' last hop to the head-group pipeline, which takes no
+        # window; every transfer of this path is waited for on this stream before it returns)
+        plan = _window_plan(win, P, r, S, causal)
+
+        def win_block(step, kk, vv, dk_dst, dv_dst):
+            blk = plan.block(step)
+            be.bwd(dout, q, kk, vv, softmax_lse, delta, dq_acc, dk_dst, dv_dst, softmax_scale, blk.causal,
+                   accum_dq=step > 0, **blk.launch_kw())       # (step 0 is never empty: it is the first to write dq)
+
+        dk_acc, dv_acc = return_dkdv_direct(process_group, k, v, win_block, plan.key_extent, be,
+                                            relay_kw=dict(recv_steps=plan.recv, send_steps=plan.send))
+        return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
 
     def block(step, kk, vv, dk_dst, dv_dst):
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,

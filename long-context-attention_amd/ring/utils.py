@@ -168,22 +168,36 @@ class KVRelay:
     the compute stream behind the side stream at its end (`finish`), so a slot is never rewritten while a
     kernel of the previous call still reads it.  On host tensors (gloo tests) the same runs inline.
 
+    `recv_steps` / `send_steps` (default None = all, the above): the steps s whose K/V (of rank r-s) this rank receives and the
+    steps s at which it sends its own to rank r+s -- a sliding window needs only the neighbouring chunks (ring/window_blocks.py;
+    both ends derive their sets from one function, so every send has its receive).  Such a relay always takes the direct form
+    (ONE grouped send/recv; USP_KV_RELAY does not apply: a chain would carry K/V through ranks that never read them), skips the
+    group call when the rank has nothing to post, holds slots for the received steps only, and `get()` of a step that was never
+    requested raises.
+
     Use as a context manager: `finish` must run on every exit path (it re-joins the side stream).
     """
 
     _SLOTS = OrderedDict()   # (shape, dtype, device, P, rank) -> [(k_slot, v_slot)] * (P-1), device tensors only
 
-    def __init__(self, process_group, k: torch.Tensor, v: torch.Tensor):
+    def __init__(self, process_group, k: torch.Tensor, v: torch.Tensor, recv_steps=None, send_steps=None):
         self.P = group_info(dist, process_group)[0]
+        self._steps = None
+        if recv_steps is not None or send_steps is not None:
+            every = range(1, self.P)
+            self._steps = tuple(sorted({int(s) for s in (every if steps is None else steps)}) for steps in (recv_steps, send_steps))
+            assert all(1 <= s < self.P for steps in self._steps for s in steps), self._steps
         if self.P > 1:
             # point-to-point transfers need contiguous buffers (the reference makes K/V contiguous at
             # zigzag_ring_flash_attn.py:208-209); views stay views at ring degree 1
             k, v = k.contiguous(), v.contiguous()
         self.slots: List[Tuple[torch.Tensor, torch.Tensor]] = [(k, v)]
         self.events = [None]
+        if self._steps is not None:                   # by step: only the requested ones exist
+            self.slots, self.events = {0: (k, v)}, {0: None}
         self._stream = None
         self._pending = None
-        if self.P == 1:
+        if self.P == 1 or (self._steps is not None and not (self._steps[0] or self._steps[1])):
             return
         if k.is_cuda:
             self._main = torch.cuda.current_stream()
@@ -205,8 +219,32 @@ class KVRelay:
         process_group, k, v = self._pending
         self._pending = None
         cuda = k.is_cuda
-        recv = self._recv_slots(k, v, dist.get_rank(process_group))
         ctx = torch.cuda.stream(self._stream) if cuda else nullcontext()
+        if self._steps is not None:
+            recv_steps, send_steps = self._steps
+            r = dist.get_rank(process_group)
+            recv = self._recv_slots(k, v, r, recv_steps)
+            with ctx:
+                comm = RingComm(process_group)          # one grouped send/recv with the peers of the plan only
+                for s in range(1, self.P):              # (K then V per peer on both ends: gloo matches in posting order)
+                    if s in send_steps:
+                        comm.send(k, r + s)
+                        comm.send(v, r + s)
+                    if s in recv_steps:
+                        nk, nv = recv[recv_steps.index(s)]
+                        comm.recv(nk, r - s)
+                        comm.recv(nv, r - s)
+                        self.slots[s] = (nk, nv)
+                comm.commit()
+                comm.wait()
+                ev = None
+                if cuda:
+                    ev = torch.cuda.Event()
+                    ev.record(self._stream)
+                for s in recv_steps:
+                    self.events[s] = ev
+            return
+        recv = self._recv_slots(k, v, dist.get_rank(process_group))
         if kv_relay_mode(self.P) == "direct":
             with ctx:
                 r = dist.get_rank(process_group)
@@ -242,9 +280,14 @@ class KVRelay:
                 self.events.append(ev)
                 cur_k, cur_v = nk, nv
 
-    def _recv_slots(self, k, v, rank):
+    def _recv_slots(self, k, v, rank, steps=None):
+        n = self.P - 1 if steps is None else len(steps)
         if not k.is_cuda:
-            return [(torch.empty_like(k), torch.empty_like(v)) for _ in range(self.P - 1)]
+            return [(torch.empty_like(k), torch.empty_like(v)) for _ in range(n)]
+        if steps is not None:                     # (as below; the set of steps is part of the key)
+            key = (tuple(k.shape), tuple(v.shape), k.dtype, k.device.index, self.P, rank,
+                   torch.cuda.current_stream().cuda_stream, tuple(steps))
+            return _cached_slots(KVRelay._SLOTS, key, lambda: [(torch.empty_like(k), torch.empty_like(v)) for _ in range(n)])
         # the compute stream is part of the key: the no-rewrite guarantee (side stream ordered behind the compute stream
         # at the start of a relay, the compute stream behind the side stream at its end) holds between calls on ONE stream
         key = (tuple(k.shape), tuple(v.shape), k.dtype, k.device.index, self.P, rank,
@@ -254,6 +297,9 @@ class KVRelay:
 
     def get(self, step: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """K, V held after `step` hops; makes the current stream wait for that hop."""
+        if self._steps is not None and step not in self.slots:
+            raise RuntimeError(f"KVRelay.get({step}): the K/V of that ring step were never requested "
+                               f"(received steps: {list(self._steps[0])})")
         ev = self.events[step]
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
@@ -530,7 +576,7 @@ def _rounded(be, acc, dtype):
     return out
 
 
-def return_dkdv_direct(process_group, k, v, block, extent, be, zero: bool = False):
+def return_dkdv_direct(process_group, k, v, block, extent, be, zero: bool = False, relay_kw=None):
     """dK/dV without the relay (USP_DKDV_RETURN=direct): ring rank r computes at step s the block of the K/V owned
     by rank r-s and sends it STRAIGHT to that owner, which adds the P-1 arriving blocks to its own step-0 block in
     step order -- the order the relay adds them in, so the result is bit-identical to it.
@@ -542,7 +588,10 @@ def return_dkdv_direct(process_group, k, v, block, extent, be, zero: bool = Fals
     is never sent).  At the 8-GPU BASELINE config either form hides behind 3.4 ms of kernels per step; an MHA ring
     (2 x 64 MiB of fp32 per hop at ring 4 x 8192 tokens x 16 heads, ~2 ms per link against ~0.9 ms of kernels) is
     link-bound in the relay and not here.  Costs P-1 receive buffers instead of one (sized for 288 GB).
-    Every step's send is posted from the compute stream behind that step's kernels, like the relay's hops."""
+    Every step's send is posted from the compute stream behind that step's kernels, like the relay's hops.
+    A step with nothing to compute, send or receive (`extent` is None on both ends) is skipped entirely -- its K/V are not
+    even asked of the relay, which `relay_kw` (KVRelay's recv_steps / send_steps) may therefore leave out.  The owner adds the
+    arriving blocks in ascending step order whatever steps there are: two identical calls give bit-identical results."""
     P = dist.get_world_size(process_group)
     r = dist.get_rank(process_group)
     new = (lambda shape, dev: torch.zeros(shape, dtype=torch.float32, device=dev)) if zero else \
@@ -555,16 +604,18 @@ def return_dkdv_direct(process_group, k, v, block, extent, be, zero: bool = Fals
         return rows(t, sl).contiguous()
 
     pending = []
-    with KVRelay(process_group, k, v) as relay:
+    with KVRelay(process_group, k, v, **(relay_kw or {})) as relay:
         kk, vv = relay.get(0)
         dk_acc, dv_acc = new(k.shape, k.device), new(v.shape, v.device)
         block(0, kk, vv, dk_acc, dv_acc)
         for step in range(1, P):
-            kk, vv = relay.get(step)
             out_sl, in_sl = extent(r, step), extent((r + step) % P, step)
+            if out_sl is None and in_sl is None:
+                continue
             comm = RingComm(process_group)
             keep = None
             if out_sl is not None:
+                kk, vv = relay.get(step)
                 dk_blk, dv_blk = new(k.shape, k.device), new(v.shape, v.device)      # one pair per step: the send
                 block(step, kk, vv, dk_blk, dv_blk)                                  # reads it beside later steps
                 keep = (wire(dk_blk, out_sl), wire(dv_blk, out_sl))

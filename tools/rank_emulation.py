@@ -8,6 +8,9 @@ config before any link time -- measurable on a 1-GPU box.
 
     python tools/rank_emulation.py --gpus 8 [--rank 0] [--iters 5] [--env USP_PIPELINE_ULYSSES=0]
     python tools/rank_emulation.py --gpus 8 --ud 8 --rd 1 --impl basic      # another grid for the same workload
+    python tools/rank_emulation.py --gpus 4 --ud 1 --rd 4 --impl basic --rank 3 --S 65536 --heads 8 1 --window 4096 0
+        # a sliding window over global positions on the basic ring (sets USP_RING_WINDOW=global): forward and backward timed
+        # apart, flash launches issued, K/V bytes received and dK/dV bytes sent per iteration
 """
 import argparse
 import os
@@ -46,8 +49,14 @@ class FakeDist:
     def P2POp(self, op, tensor, peer, group=None):
         return (op, tensor)
 
+    # bytes posted per kind since the last reset, on the class (one FakeDist per run), told apart by dtype alone: fp32 sends are
+    # dK/dV, 16-bit receives are K/V.  That holds here because nothing else travels a ring: dq and lse (fp32) stay on their rank.
+    sent = recv = 0
+
     def batch_isend_irecv(self, ops):
         sends = [t for o, t in ops if o == "send"]
+        FakeDist.sent += sum(t.numel() * t.element_size() for t in sends if t.dtype == torch.float32)
+        FakeDist.recv += sum(t.numel() * t.element_size() for o, t in ops if o == "recv" and t.dtype != torch.float32)
         for i, (o, t) in enumerate(x for x in ops if x[0] == "recv"):
             src = next((s for s in sends[i % max(1, len(sends)):] + sends if s.shape == t.shape), None)
             if src is not None:
@@ -67,6 +76,11 @@ def main():
     ap.add_argument("--ud", type=int, default=None, help="ulysses degree (with --rd: a grid other than the workload's)")
     ap.add_argument("--rd", type=int, default=None, help="ring degree")
     ap.add_argument("--impl", default=None, help="ring implementation (default: the workload's)")
+    ap.add_argument("--S", type=int, default=None, help="global sequence length (default: the workload's)")
+    ap.add_argument("--heads", type=int, nargs=2, default=None, metavar=("HQ", "HKV"))
+    ap.add_argument("--window", type=int, nargs=2, default=None, metavar=("LEFT", "RIGHT"),
+                    help="flash-attn's window_size over global positions (basic ring; sets USP_RING_WINDOW=global)")
+    ap.add_argument("--split-timing", action="store_true", help="forward and backward timed apart, launches and bytes counted")
     args = ap.parse_args()
     for kv in args.env:
         k, v = kv.split("=", 1)
@@ -90,6 +104,15 @@ def main():
         cfg["name"] += f" -- grid overridden: ulysses={cfg['ud']} ring={cfg['rd']}"
     if args.impl is not None:
         cfg["impl"] = args.impl
+    if args.S is not None:
+        cfg["S"] = args.S
+    if args.heads is not None:
+        cfg["Hq"], cfg["Hkv"] = args.heads
+    window = (-1, -1)
+    if args.window is not None:
+        window = tuple(args.window)
+        os.environ["USP_RING_WINDOW"] = "global"
+        cfg["name"] += f" -- window {window}"
     ud, rd = cfg["ud"], cfg["rd"]
     u_rank, r_rank = args.rank % ud, args.rank // ud
     Y.PROCESS_GROUP.ULYSSES_PG, Y.PROCESS_GROUP.RING_PG = Group(ud, u_rank), Group(rd, r_rank)
@@ -104,6 +127,31 @@ def main():
         for t in (lq, lk, lv):
             t.requires_grad_(True)
     attn = Y.LongContextAttention(ring_impl_type=cfg["impl"], attn_type=Y.AttnType.HIP)
+
+    if args.window is not None or args.split_timing:
+        from yunchang_amd import _C
+        n_launch = [0]
+        for name in ("flash_fwd", "flash_bwd"):
+            real = getattr(_C, name)
+            setattr(_C, name, (lambda real: lambda *a, **k: (n_launch.__setitem__(0, n_launch[0] + 1), real(*a, **k))[1])(real))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        t_f = t_b = 0.0
+        for it in range(3 + args.iters):
+            n_launch[0] = FakeDist.sent = FakeDist.recv = 0
+            ev[0].record()
+            out = attn(lq, lk, lv, causal=True, window_size=window)
+            ev[1].record()
+            out.backward(ldo)
+            ev[2].record()
+            lq.grad = lk.grad = lv.grad = None
+            torch.cuda.synchronize()
+            if it >= 3:
+                t_f += ev[0].elapsed_time(ev[1]) / args.iters
+                t_b += ev[1].elapsed_time(ev[2]) / args.iters
+        print(f"{cfg['name']}\n  rank {args.rank} (ulysses {u_rank}/{ud}, ring {r_rank}/{rd}), wire = local copies: "
+              f"forward {t_f:8.3f} ms, backward {t_b:8.3f} ms; per iteration {n_launch[0]} flash calls, "
+              f"K/V received {FakeDist.recv / 2**20:8.1f} MiB, dK/dV sent {FakeDist.sent / 2**20:8.1f} MiB")
+        return
 
     def step():
         out = attn(lq, lk, lv, causal=True)
