@@ -98,7 +98,12 @@ enum {
  * |mask_shift| < 2^30 is served (USP_EINVAL beyond): rows, or a whole launch, that see no key give out = 0, lse = -inf and
  * zero gradients, as an empty row does without the bit.  A shift with neither `causal` nor a window bounds nothing and is
  * ignored.  Dense launches only: a packed batch with the bit is USP_EUNSUPPORTED.  The 64-row family serves a shifted launch
- * exactly where it serves the same launch unshifted (no left window bound).  Without the bit the field is ignored; a binding
+ * exactly where it serves the same launch unshifted (no left window bound).
+ * Served range: window_left and window_right may be ANY int32 (INT32_MAX as "unbounded" included), with or without a shift;
+ * the bounds are formed in 64 bits (csrc/usp_mask_decode.h).  A bound that cuts no (row, key) pair of the launch at this
+ * (Sq, Sk, mask_shift) is dropped -- the launch is then served as the same launch without that bound, by every family that
+ * serves that one, a left bound that cuts nothing included -- and a bound that cuts every pair gives the empty result above.
+ * The kernels' own index arithmetic needs Sq + Sk < 2^29.  Without the bit the field is ignored; a binding
  * built before it never sets the bit, and the field lies in what was padding (behind softmax_scale), so such a binding's struct
  * has the same size and offsets and is never read past; usp_attn_features() reports the bit. */
 #define USP_ATTN_SHIFT 128

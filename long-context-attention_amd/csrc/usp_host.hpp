@@ -7,6 +7,7 @@
 
 #include "usp_common.hpp"
 #include "usp_hip.h"
+#include "usp_mask_decode.h"
 
 namespace usp {
 
@@ -86,7 +87,7 @@ template <class Args> int check_problem(const Args& a) {
 // at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
 // (forward: the split instantiation, FwdSplit).
 struct Mask {
-  bool causal;                  // the causal instantiation runs: a.causal, or a right window bound
+  bool causal;                  // the causal instantiation runs: a.causal or a right window bound -- where it cuts a (row, key) pair
   bool shifted;                 // USP_ATTN_SHIFT is set: dense launches only
   bool windowed;                // a bound beyond plain causal: dense launches only
   int causal_off, win_on, win_lo, cap_on;
@@ -98,20 +99,18 @@ struct Mask {
 };
 template <class Args> Mask decode_mask(const Args& a) {
   const bool has_win = (a.flags & USP_ATTN_WINDOW) != 0, has_cap = (a.flags & USP_ATTN_SOFTCAP) != 0;
-  const int wl = has_win ? a.window_left : -1;
-  const int wr = a.causal ? 0 : (has_win ? a.window_right : -1);
+  // USP_ATTN_SHIFT moves the diagonal both bounds hang on, and nothing else: to the kernels it is another causal_off / win_lo.
+  // The integer part (64-bit sums; a bound that cuts nothing dropped, one that cuts everything saturated) is plain C and
+  // checked on the host: usp_mask_decode.h.
+  const usp_mask_bounds mb = usp_decode_mask_bounds(a.Sq, a.Sk, a.causal ? 1 : 0, has_win ? 1 : 0, has_win ? a.window_left : -1,
+                                                    has_win ? a.window_right : -1, (a.flags & USP_ATTN_SHIFT) ? 1 : 0,
+                                                    (a.flags & USP_ATTN_SHIFT) ? a.mask_shift : 0);
   Mask m;
-  m.causal = wr >= 0;
-  m.windowed = wl >= 0 || wr > 0;
-  m.causal_off = a.Sk - a.Sq + (wr > 0 ? wr : 0);
-  m.win_on = wl >= 0 ? 1 : 0;
-  m.win_lo = a.Sk - a.Sq - (wl >= 0 ? wl : 0);
-  // USP_ATTN_SHIFT moves the diagonal both bounds hang on, and nothing else: to the kernels it is another causal_off / win_lo
-  // (they clamp every tile range they derive from the two, so offsets below -Sq or above Sk are empty / unmasked ranges).
-  // Without a bound there is nothing to move.
-  const int shift = ((a.flags & USP_ATTN_SHIFT) && (m.causal || m.win_on)) ? a.mask_shift : 0;
-  m.causal_off += shift;
-  m.win_lo += shift;
+  m.causal = mb.causal != 0;
+  m.windowed = mb.windowed != 0;
+  m.causal_off = mb.causal_off;
+  m.win_on = mb.win_on;
+  m.win_lo = mb.win_lo;
   m.shifted = (a.flags & USP_ATTN_SHIFT) != 0;
   m.cap_on = has_cap ? 1 : 0;
   m.cap_log2 = has_cap ? a.softcap * kLog2e : 0.f;

@@ -144,13 +144,20 @@ def sample_rows(Sq, n=24, seed=0):
     return sorted(rows)
 
 
-def mask_edges(rows, Sq, Sk, causal=False, window=None):
-    """(row, key) pairs: the last visible and the first invisible key of each row on every bound of its mask (the causal
-    diagonal with its Sk - Sq offset, the window's left and right bound)."""
+def _bounds(Sq, Sk, causal, window, shift=0):
+    """(left, right, off) of a mask as include/usp_hip.h defines it: row i sees key j iff i + off - left <= j <= i + off + right
+    (each side only where its bound is >= 0), off = Sk - Sq + shift; `causal` sets right = 0.  A shift with neither `causal`
+    nor a window is ignored (there is no bound it could move)."""
     left, right = (-1, -1) if window is None else (int(window[0]), int(window[1]))
     if causal:
         right = 0
-    off = Sk - Sq
+    return left, right, Sk - Sq + (int(shift or 0) if (left >= 0 or right >= 0) else 0)
+
+
+def mask_edges(rows, Sq, Sk, causal=False, window=None, shift=0):
+    """(row, key) pairs: the last visible and the first invisible key of each row on every bound of its mask (the causal
+    diagonal with its Sk - Sq + shift offset, the window's left and right bound)."""
+    left, right, off = _bounds(Sq, Sk, causal, window, shift)
     out = []
     for r in rows:
         if right >= 0:
@@ -160,23 +167,24 @@ def mask_edges(rows, Sq, Sk, causal=False, window=None):
     return [(r, j) for r, j in out if 0 <= j < Sk]
 
 
-def _visible(r, j, Sq, Sk, causal, window):
-    left, right = (-1, -1) if window is None else (int(window[0]), int(window[1]))
-    if causal:
-        right = 0
-    d = j - (r + Sk - Sq)
+def _visible(r, j, Sq, Sk, causal, window, shift=0):
+    left, right, off = _bounds(Sq, Sk, causal, window, shift)
+    d = j - (r + off)
     return (right < 0 or d <= right) and (left < 0 or d >= -left)
 
 
-def key_tiles_of_query_tile(q0, rows, Sq, Sk, causal, window=None):
-    """[t0, nt): the 64-key tiles a query tile [q0, q0 + rows) streams (usp_flash_fwd_body.inc, usp_flash_fwd64.hip)."""
+def key_tiles_of_query_tile(q0, rows, Sq, Sk, causal, window=None, shift=0):
+    """[t0, nt): the 64-key tiles a query tile [q0, q0 + rows) streams (usp_flash_fwd_body.inc, usp_flash_fwd64.hip).  With a
+    `shift` the causal limit and the left bound move with the diagonal; a right window bound without `causal` limits the range
+    as the causal limit does (the causal instantiation serves it, with causal_off = Sk - Sq + shift + right)."""
+    left, right, off = _bounds(Sq, Sk, causal, window, shift)
     e = Sk
-    if causal:
-        e = min(e, min(q0 + rows, Sq) + Sk - Sq)
+    if right >= 0:
+        e = min(e, min(q0 + rows, Sq) + off + right)
     nt = -(-e // TILE) if e > 0 else 0
     t0 = 0
-    if window is not None and window[0] >= 0:
-        t0 = min(nt, max(0, q0 + Sk - Sq - int(window[0])) // TILE)
+    if left >= 0:
+        t0 = min(nt, max(0, q0 + off - left) // TILE)
     return t0, nt
 
 
@@ -200,46 +208,46 @@ def _spread(rows, salt, n):
     return sorted(set(rows[(salt + i * max(1, len(rows) // n)) % len(rows)] for i in range(n)))
 
 
-def key_run_edges(Sq, Sk, causal, n, rule, window=None, tile_rows=256, per=3, tiles=None):
+def key_run_edges(Sq, Sk, causal, n, rule, window=None, tile_rows=256, per=3, tiles=None, shift=0):
     """(row, key) pairs for the first and the last key of every run of a key cut into n (forward `k_splits`: rule "floor";
     `dq_splits`: rule "per"), for every query tile: 2 * `per` rows of the tile that see both keys get a needle on one of them, in turn.  `tiles`: first rows of
     the query tiles to do this for (default: all; every named row sees the needles of the rows that share its private
     direction, so name few in one launch)."""
     out = []
     for q0 in (range(0, Sq, tile_rows) if tiles is None else tiles):
-        t0, nt = key_tiles_of_query_tile(q0, tile_rows, Sq, Sk, causal, window)
+        t0, nt = key_tiles_of_query_tile(q0, tile_rows, Sq, Sk, causal, window, shift)
         for tb in run_bounds(t0, nt, n, rule):
             kb = tb * TILE
-            rows = [r for r in range(q0, min(q0 + tile_rows, Sq))
-                    if kb < Sk and _visible(r, kb, Sq, Sk, causal, window) and _visible(r, kb - 1, Sq, Sk, causal, window)]
+            rows = [r for r in range(q0, min(q0 + tile_rows, Sq)) if kb < Sk and
+                    _visible(r, kb, Sq, Sk, causal, window, shift) and _visible(r, kb - 1, Sq, Sk, causal, window, shift)]
             for i, r in enumerate(_spread(rows, 7 * tb + q0 // tile_rows + (11 if rule == "per" else 0), 2 * per)):
                 out.append((r, kb - 1 + i % 2))              # (one key per row: few needles per row keep P large)
     return out
 
 
-def key_block_edges(Sq, Sk, causal, window=None, block=128, every=1, per=3):
+def key_block_edges(Sq, Sk, causal, window=None, block=128, every=1, per=3, shift=0):
     """(row, key) pairs on the last key of a 128-key dK/dV block and the first of the next (every `every`-th boundary),
     each for `per` rows among the last 256 of the launch that see the pair."""
     out = []
     for kb in range(block, Sk, block * every):
         rows = [r for r in range(max(0, Sq - 256), Sq)
-                if _visible(r, kb, Sq, Sk, causal, window) and _visible(r, kb - 1, Sq, Sk, causal, window)]
+                if _visible(r, kb, Sq, Sk, causal, window, shift) and _visible(r, kb - 1, Sq, Sk, causal, window, shift)]
         for i, r in enumerate(_spread(rows, 5 * (kb // block), 2 * per)):
             out.append((r, kb - 1 + i % 2))
     return out
 
 
-def query_run_edges(Sq, Sk, causal, n, block=128, every=1, per=3):
+def query_run_edges(Sq, Sk, causal, n, block=128, every=1, per=3, shift=0):
     """(row, key) pairs for a dK/dV cut into n (`dkdv_splits`): for (every `every`-th) 128-key block, the last and the
     first query row of adjacent runs (usp_flash_bwd64.hip: 64-row query tiles [t_begin, t_end) in equal runs) each get
     `per` needles inside the block -- the rows whose contribution a wrong run boundary loses or doubles."""
     out = []
     nq = -(-Sq // TILE)
     for kb in range(0, Sk, block * every):
-        t_begin = max(0, kb - (Sk - Sq)) // TILE if causal else 0
+        t_begin = max(0, kb - (Sk - Sq + int(shift or 0))) // TILE if causal else 0
         for t in run_bounds(min(t_begin, nq), nq, n, "per"):
             for i, r in enumerate((t * TILE - 1, t * TILE)):
-                keys = [j for j in range(kb, min(kb + block, Sk)) if 0 <= r < Sq and _visible(r, j, Sq, Sk, causal, None)]
+                keys = [j for j in range(kb, min(kb + block, Sk)) if 0 <= r < Sq and _visible(r, j, Sq, Sk, causal, None, shift)]
                 out += [(r, j) for j in _spread(keys, 29 * (2 * t + i) + 3, per)]
     return out
 

@@ -85,16 +85,61 @@ def test_fuzz_64row_kernels(dev, seed):
     _run_dense(dev, rs, _row64_case(rs))
 
 
-def _run_dense(dev, rs, case):
+_N_SHIFTED = int(os.environ.get("USP_FUZZ_SHIFTED", "16"))  # larger sweeps: USP_FUZZ_SHIFTED=300
+
+
+def _shifted_case(rs):
+    """The shapes of `_dense_case` with a bound always (causal or a window), a shift on tile edges, beside them, half a
+    sequence away and past the last key, K split / cuts in a third of the cases, `dkdv_heads` from the divisors of the group."""
+    B, Sq, Sk, Hq, Hkv, D, causal, dt, win, ks, cuts = _dense_case(rs)
+    if not causal and win is None:
+        if rs.rand() < 0.5:
+            causal = True
+        else:
+            win = (int(rs.choice([0, 1, 17, 64, 200])), int(rs.choice([-1, 0, 3, 40])))
+    shift = int(rs.choice([0, 1, -1, 63, -63, 64, -64, 65, -65, Sq // 2, -(Sq // 2), Sk + 5, -(Sk + 5)]))
+    G = Hq // Hkv
+    heads = int(rs.choice([g for g in range(1, G + 1) if G % g == 0]))
+    family = str(rs.choice(["auto", "wave32", "row64"]))    # (the 64-row family: D 128 without a left bound)
+    if family == "row64" and (D != 128 or (win is not None and win[0] >= 0)):
+        family = "wave32"
+    return (B, Sq, Sk, Hq, Hkv, D, causal, dt, win, ks, cuts), shift, heads, (None if family == "auto" else family)
+
+
+@pytest.mark.parametrize("seed", range(_N_SHIFTED))
+def test_fuzz_shifted(dev, seed):
+    """A shifted diagonal (USP_ATTN_SHIFT) on N(0,1) inputs against tests/shift_ref.py: the bookkeeping of rows, tiles and whole
+    launches without a visible key across every head dim and both dispatches (which key is the last visible one is pinned on
+    needle inputs, tests/test_gpu_needle.py)."""
+    rs = np.random.RandomState(9000 + seed)
+    case, shift, heads, family = _shifted_case(rs)
+    _run_dense(dev, rs, case, shift=shift, dkdv_heads=heads, family=family)
+
+
+def _shift_reference(tq, tk, tv, tdo, scale, causal, win, shift):
+    """(out, lse, dq, dk, dv) in fp64 from tests/shift_ref.py on the device, as numpy; the backward from the 16-bit-rounded out."""
+    import shift_ref
+    ro, rl = shift_ref.ref_fwd(tq, tk, tv, scale, causal, win, shift)
+    g = shift_ref.ref_bwd(tdo, tq, tk, tv, ro.to(tq.dtype), rl, scale, causal, win, shift)
+    return tuple(t.cpu().numpy() for t in (ro, rl) + tuple(g))
+
+
+def _run_dense(dev, rs, case, shift=None, dkdv_heads=0, family=None):
     from yunchang_amd import _C
     B, Sq, Sk, Hq, Hkv, D, causal, dt, win, ks, cuts = case
     what = f"B{B} Sq{Sq} Sk{Sk} Hq{Hq} Hkv{Hkv} D{D} causal={causal} {dt} window={win} k_splits={ks} cuts={cuts}"
     wkw = {} if win is None else {"window": win}
+    if shift is not None:
+        what += f" shift={shift} dkdv_heads={dkdv_heads} family={family}"
     q, k, v, do = (round_to(rs.standard_normal(s).astype(np.float32), dt)
                    for s in [(B, Sq, Hq, D), (B, Sk, Hkv, D), (B, Sk, Hkv, D), (B, Sq, Hq, D)])
     tq, tk, tv, tdo = (_t(x, dt, dev) for x in (q, k, v, do))
     scale = D ** -0.5
-    ro, rl = O.attention_ref(q, k, v, causal, scale, **wkw)
+    if shift is None:
+        ro, rl = O.attention_ref(q, k, v, causal, scale, **wkw)
+    else:
+        ro, rl, rdq, rdk, rdv = _shift_reference(tq, tk, tv, tdo, scale, causal, win, shift)
+        wkw = dict(wkw, shift=shift, family=family)
     runs = []
     for _ in range(2):
         out = torch.full((B, Sq, Hq, D), float("nan"), dtype=tq.dtype, device=dev)
@@ -107,7 +152,8 @@ def _run_dense(dev, rs, case):
     assert_close(runs[0][0], ro, *TOL[dt]["out"], what + " out")
     assert_close(runs[0][1][fin], rl[fin], 2e-3, 1e-4, what + " lse")
     o16 = round_to(ro.astype(np.float32), dt)
-    rdq, rdk, rdv = O.block_bwd(do, q, k, v, o16, rl, scale, causal, **wkw)
+    if shift is None:
+        rdq, rdk, rdv = O.block_bwd(do, q, k, v, o16, rl, scale, causal, **wkw)
     lse_t = torch.from_numpy(np.ascontiguousarray(rl, dtype=np.float32)).to(dev)
     delta = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev)
     _C.bwd_delta(tdo, _t(o16, dt, dev), delta)
@@ -115,7 +161,7 @@ def _run_dense(dev, rs, case):
     for _ in range(2):
         dq, dk, dv = (torch.full_like(t, float("nan")) for t in (tq, tk, tv))
         _C.flash_bwd(tdo, tq, tk, tv, lse_t, delta, None, None, None, scale, causal, dq16=dq, dk16=dk, dv16=dv,
-                     interleave=len(grads) == 1, splits=cuts, **wkw)
+                     interleave=len(grads) == 1, splits=cuts, dkdv_heads=dkdv_heads, **wkw)
         grads.append([_f(x) for x in (dq, dk, dv)])
     for a_, b_, n_ in zip(grads[0], grads[1], ("dq", "dk", "dv")):
         assert np.array_equal(a_, b_), f"{what}: {n_} differs between two launches"

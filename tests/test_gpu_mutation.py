@@ -335,6 +335,32 @@ def test_needle_family_fails_on_dout_heads_swapped_inside_a_gqa_group(dev):
     _needle_must_fail(dev, "flash_bwd", _swap_dout_heads, "gqa8-heads2")
 
 
+def _shift_plus(d):
+    def alter(a):
+        a["shift"] = a["shift"] + d
+    return alter
+
+
+def _window_right_off_by_one(a):
+    a["window"] = (a["window"][0], a["window"][1] + 1)
+
+
+_SHIFT_ALTERED = [("sh-r64-causal+70", "shift+1", _shift_plus(1)), ("sh-r64-causal+70", "shift-1", _shift_plus(-1)),
+                  ("sh-r64-right-70", "right+1", _window_right_off_by_one),
+                  ("sh-w4-both-100", "shift+1", _shift_plus(1)), ("sh-w4-both-100", "shift-1", _shift_plus(-1)),
+                  ("sh-w4-both-100", "left+1", _window_left_off_by_one)]
+
+
+@pytest.mark.parametrize("fn_name", ["flash_fwd", "flash_bwd"])
+@pytest.mark.parametrize("cfg_id,alter", [(c, f) for c, _, f in _SHIFT_ALTERED], ids=[f"{c}:{n}" for c, n, _ in _SHIFT_ALTERED])
+def test_shifted_needle_family_fails_on_a_bound_one_key_off(dev, cfg_id, alter, fn_name):
+    """The REAL kernel is handed shift + 1, shift - 1, or a window bound + 1 with the shift unchanged: one key more or less on
+    one bound of every row -- a few 1e-3 of `out` on N(0,1) inputs at these depths.  The shifted needle cases (64-row: causal +
+    shift; 32-row: both bounds + shift) must fail, forward and backward.  (A causal case has no window to move and the 64-row
+    family serves no left bound that cuts: its third alteration is the RIGHT bound + 1 of `sh-r64-right-70`.)"""
+    _needle_must_fail(dev, fn_name, alter, cfg_id)
+
+
 # ------------------------------------------------------------------------------------------------
 # value-range inputs (tests/test_gpu_range.py): the REAL kernel is handed softmax_scale * 1.02, the reference keeps the scale
 # ------------------------------------------------------------------------------------------------

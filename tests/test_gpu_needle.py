@@ -24,6 +24,7 @@ import pytest
 import torch
 
 import needle_inputs as NI
+import shift_ref
 from attn_ref_torch import ref_bwd, ref_delta, ref_fwd
 from golden_util import TOL
 
@@ -53,6 +54,8 @@ class Cfg(NamedTuple):
     splits: Tuple[int, int] = (0, 0)
     dkdv_heads: int = 0
     seed: int = 0
+    shift: Optional[int] = None           # USP_ATTN_SHIFT: the diagonal of every bound at Sk - Sq + shift (None: the bit is off)
+    do_mul: Optional[float] = None        # dout on ordinary rows (None: needle_inputs.do_mul_for)
 
 
 _R64 = ("dkdv_row64", "dq_row64")
@@ -104,7 +107,83 @@ DENSE = [
     Cfg("softcap", 1, 1024, 1024, 4, 2, 128, True, "bfloat16", None, None, _W8 + ("reduce_heads",), softcap=30.0, q_mul=4.0),
     Cfg("softcap-d64", 1, 900, 1200, 2, 2, 64, False, "bfloat16", None, None, _W8, softcap=30.0, q_mul=4.0),
 ]
-_CFG = {c.id: c for c in DENSE}
+
+
+# ---- a shifted diagonal (USP_ATTN_SHIFT) under the causal bound and both window bounds: what one block of a windowed ring is.
+# Shapes: >= 3 query tiles of 256 rows, >= 2 dK/dV blocks of 128 keys, >= 8 key tiles (2048 only where the keys are cut).
+# tests/test_needle_cpu.py asserts from this table that it covers every kernel x bound x shift kind it is meant to.
+def _bwd_kinds(family, G, heads=1, splits=(0, 0)):
+    """dkdv_heads query heads per dK/dV item (1 where the library decides at these sizes) -> G / heads items per KV group;
+    more than one slab (items x dK/dV cuts) is summed by `reduce_heads`, a cut dQ by `reduce_cuts`."""
+    k = _R64 if family == "row64" else _W8
+    if (G // max(1, heads)) * max(1, splits[1]) > 1:
+        k += ("reduce_heads",)
+    if splits[0] > 1:
+        k += ("reduce_cuts",)
+    return k
+
+
+def _sh(id, B, Sq, Sk, Hq, Hkv, D, causal, dt, family, fwd, window, shift, **kw):
+    G = Hq // Hkv
+    bwd = None if family is None else _bwd_kinds(family, G, kw.get("dkdv_heads", 0) or 1, kw.get("splits", (0, 0)))
+    return Cfg(id, B, Sq, Sk, Hq, Hkv, D, causal, dt, family, fwd, bwd, window=window, shift=shift, **kw)
+
+
+_F64, _F4, _F8 = ("fwd_row64",), ("fwd_wave4",), ("fwd_wave8",)
+SHIFTED = [
+    # ---- the 64-row family: right bounds only (causal, or window_right > 0), D 128
+    _sh("sh-r64-causal+70", 1, 768, 1024, 4, 2, 128, True, "bfloat16", "row64", _F64, None, 70),
+    _sh("sh-r64-causal-333", 1, 1024, 768, 2, 1, 128, True, "float16", "row64", _F64, None, -333),     # rows < 589 see no key
+    _sh("sh-r64-causal+128", 2, 768, 768, 2, 2, 128, True, "bfloat16", "row64", _F64, None, 128),
+    _sh("sh-r64-causal-256", 1, 1024, 1280, 2, 2, 128, True, "bfloat16", "row64", _F64, None, -256),
+    _sh("sh-r64-right-70", 1, 768, 900, 2, 1, 128, False, "float16", "row64", _F64, (-1, 200), -70),
+    _sh("sh-r64-all-visible", 1, 640, 768, 2, 2, 128, True, "bfloat16", "row64", _F64, None, 800),     # shift >= Sk: cuts nothing
+    _sh("sh-r64-ksplit3", 1, 2048, 2048, 2, 1, 128, True, "bfloat16", "row64", _F64 + (_SM,), None, 192, k_splits=3),
+    _sh("sh-r64-cuts-3-2", 1, 1280, 1280, 2, 1, 128, True, "bfloat16", "row64", _F64, None, -70, splits=(3, 2)),
+    _sh("sh-r64-heads1", 1, 768, 768, 4, 1, 128, True, "bfloat16", "row64", _F64, None, 64, dkdv_heads=1),
+    _sh("sh-r64-heads4", 1, 768, 768, 4, 1, 128, True, "bfloat16", "row64", _F64, None, 64, dkdv_heads=4),
+    # ---- the 32-row family: a left bound (the window instantiation of the forward), both bounds, causal alone; D 128, 64, 32
+    _sh("sh-w4-both-100", 1, 768, 1024, 4, 2, 128, False, "bfloat16", "wave32", _F4, (200, 50), -100),
+    _sh("sh-w4-left+70-d64", 1, 1024, 640, 2, 2, 64, False, "float16", "wave32", _F4, (300, -1), 70),
+    _sh("sh-w4-causal-333-d32", 1, 1024, 768, 2, 1, 32, True, "bfloat16", "wave32", _F4, None, -333),
+    _sh("sh-w4-narrow+37", 1, 700, 700, 2, 2, 128, True, "bfloat16", "wave32", _F4, (20, 0), 37),     # narrower than a tile
+    _sh("sh-w4-all-visible-d64", 1, 640, 768, 2, 1, 64, True, "float16", "wave32", _F4, None, 768),
+    _sh("sh-w4-both+256", 1, 768, 768, 2, 2, 128, True, "bfloat16", "wave32", _F4, (256, 0), 256),
+    _sh("sh-w4-ksplit4-window", 1, 2048, 2048, 2, 2, 128, True, "bfloat16", "wave32", _F4 + (_SM,), (700, 0), -128, k_splits=4),
+    _sh("sh-w32-cuts-5-3", 1, 1100, 1300, 2, 2, 128, True, "bfloat16", "wave32", None, None, 70, splits=(5, 3)),
+    _sh("sh-w8-left-64", 2, 1024, 1024, 32, 8, 128, False, "bfloat16", "wave32", _F8, (300, -1), -64,
+        do_mul=0.125),                                     # (G = 4 over 1024 rows: the rounding model's dK at 0.58 of the bound at 0.25)
+    _sh("sh-w32-heads2", 1, 768, 768, 4, 1, 128, True, "bfloat16", "wave32", _F4, None, 64, dkdv_heads=2),
+    # ---- the library's own dispatch
+    _sh("sh-default-70", 1, 900, 900, 2, 2, 128, True, "bfloat16", None, None, None, -70, do_mul=0.125),   # (model dK 0.53 at 0.25)
+]
+
+
+def ring_block_cases(P=4, c=640, windows=(((639, 0), True), ((640, 0), True), ((641, 0), True), ((100, 60), False))):
+    """What the basic ring really launches under a global window (ring/window_blocks.py): every distinct launch description
+    (causal, window, shift) of a block that is not full, over all ranks and steps, at Sq = Sk = c -- derived from the planner,
+    so a change of its decisions changes the cases."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_window_blocks", os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "long-context-attention_amd", "ring", "window_blocks.py"))
+    wb = importlib.util.module_from_spec(spec)             # (by path: pure Python, importable where the package is not)
+    spec.loader.exec_module(wb)
+    seen = {}
+    for (wl, wr), causal in windows:
+        for rank in range(P):
+            for step in range(P):
+                blk = wb.plan_block(P, c, causal, wl, wr, rank, step)
+                if blk is not None and not blk.full:
+                    seen.setdefault((blk.causal, blk.window, blk.shift), None)
+    out = []
+    for causal, window, shift in seen:
+        name = f"ring-{'causal' if causal else 'full'}-{window}-{shift}".replace(" ", "").replace("(", "").replace(")", "")
+        out.append(Cfg(name, 1, c, c, 4, 2, 128, causal, "bfloat16", None, None, None, window=window, shift=shift))
+    return out
+
+
+RING_BLOCKS = ring_block_cases()
+_CFG = {c.id: c for c in DENSE + SHIFTED + RING_BLOCKS}
 
 
 def classes_for(keys_seen, D):
@@ -113,12 +192,18 @@ def classes_for(keys_seen, D):
     return c if c % 2 else c - 1
 
 
-def _keys_seen(Sq, Sk, causal, window):
+def _keys_seen(Sq, Sk, causal, window, shift=0):
     left, right = (-1, -1) if window is None else window
     if causal:
         right = 0
     span = (Sk if left < 0 else left) + (Sk if right < 0 else right) + 1
-    return max(1, min(Sk, span))
+    seen = max(1, min(Sk, span))
+    if shift and (left >= 0 or right >= 0):                # the deepest row of the shifted mask, never more than unshifted
+        i = np.arange(Sq) + (Sk - Sq + int(shift))
+        hi = np.minimum(Sk - 1, i + right) if right >= 0 else np.full(Sq, Sk - 1)
+        lo = np.maximum(0, i - left) if left >= 0 else np.zeros(Sq, dtype=np.int64)
+        seen = max(1, min(seen, int((hi - lo + 1).max())))
+    return seen
 
 
 def _tiles(Sq):
@@ -129,33 +214,38 @@ def edges_for(c, k_splits=None, splits=None):
     """The edge needles of a dense case: the mask edges of sampled rows, the ends of the runs of its key and query cuts,
     the ends of 128-key dK/dV blocks."""
     rows = NI.sample_rows(c.Sq, 10, c.seed)
-    e = NI.mask_edges(rows, c.Sq, c.Sk, c.causal, c.window)
+    sh = getattr(c, "shift", None) or 0
+    e = NI.mask_edges(rows, c.Sq, c.Sk, c.causal, c.window, sh)
     ks = c.k_splits if k_splits is None else k_splits
     dqs, kvs = c.splits if splits is None else splits
     if ks > 1:
-        e += NI.key_run_edges(c.Sq, c.Sk, c.causal, ks, "floor", c.window, tiles=_tiles(c.Sq), per=2)
+        e += NI.key_run_edges(c.Sq, c.Sk, c.causal, ks, "floor", c.window, tiles=_tiles(c.Sq), per=2, shift=sh)
     if dqs > 1:
-        e += NI.key_run_edges(c.Sq, c.Sk, c.causal, dqs, "per", c.window, tiles=_tiles(c.Sq), per=2)
+        e += NI.key_run_edges(c.Sq, c.Sk, c.causal, dqs, "per", c.window, tiles=_tiles(c.Sq), per=2, shift=sh)
     if kvs > 1:
-        e += NI.query_run_edges(c.Sq, c.Sk, c.causal, kvs, every=max(1, c.Sk // 128 // 4), per=2)
-    e += NI.key_block_edges(c.Sq, c.Sk, c.causal, c.window, every=max(1, c.Sk // 128 // 5), per=2)
+        e += NI.query_run_edges(c.Sq, c.Sk, c.causal, kvs, every=max(1, c.Sk // 128 // 4), per=2, shift=sh)
+    e += NI.key_block_edges(c.Sq, c.Sk, c.causal, c.window, every=max(1, c.Sk // 128 // 5), per=2, shift=sh)
     return e
 
 
 def make_inputs(c, k_splits=None, splits=None):
-    C = classes_for(_keys_seen(c.Sq, c.Sk, c.causal, c.window), c.D)
+    C = classes_for(_keys_seen(c.Sq, c.Sk, c.causal, c.window, getattr(c, "shift", None) or 0), c.D)
     return NI.make(c.Sq, c.Sk, c.Hq, c.Hkv, c.D, c.dt, C, seed=c.seed, B=c.B, edges=edges_for(c, k_splits, splits),
-                   q_mul=getattr(c, "q_mul", 1.0) if isinstance(c, Cfg) else 1.0)
+                   q_mul=getattr(c, "q_mul", 1.0) if isinstance(c, Cfg) else 1.0, do_mul=getattr(c, "do_mul", None))
 
 
-def visible_fn(c):
+def visible_fn(c, shift=None):
+    """r -> bool (Sk,): the keys row r sees.  `shift`: the case's own (None), or another one (the mutants of test_needle_cpu)."""
     left, right = (-1, -1) if c.window is None else c.window
     if c.causal:
         right = 0
     j = np.arange(c.Sk)
+    sh = (getattr(c, "shift", None) or 0) if shift is None else shift
+    if left < 0 and right < 0:
+        sh = 0
 
     def vis(r):
-        d = j - (r + c.Sk - c.Sq)
+        d = j - (r + c.Sk - c.Sq + sh)
         return (d <= right if right >= 0 else np.ones(c.Sk, bool)) & (d >= -left if left >= 0 else np.ones(c.Sk, bool))
     return vis
 
@@ -202,18 +292,24 @@ def run_dense(dev, c):
     from test_gpu_row64 import _Arena
     from yunchang_amd import _C
     what = f"{c.id}: B{c.B} Sq{c.Sq} Sk{c.Sk} Hq{c.Hq} Hkv{c.Hkv} D{c.D} causal={c.causal} {c.dt} window={c.window} " \
-           f"softcap={c.softcap} family={c.family} k_splits={c.k_splits} splits={c.splits} dkdv_heads={c.dkdv_heads}"
+           f"softcap={c.softcap} family={c.family} k_splits={c.k_splits} splits={c.splits} dkdv_heads={c.dkdv_heads}" \
+           + ("" if c.shift is None else f" shift={c.shift}")
     nd = make_inputs(c)
     scale, G = c.D ** -0.5, c.Hq // c.Hkv
     qs, ks = (c.B, c.Sq, c.Hq, c.D), (c.B, c.Sk, c.Hkv, c.D)
     ar = _Arena(c.dt, dev, [qs, ks, ks, qs] + [qs] * 2 + [qs, ks, ks] * 2)
     tq, tk, tv, tdo = (ar.put(x) for x in (nd.q, nd.k, nd.v, nd.do))
-    ro, rl = ref_fwd(tq, tk, tv, scale, c.causal, c.window, c.softcap)
+    if c.shift is None:
+        ro, rl = ref_fwd(tq, tk, tv, scale, c.causal, c.window, c.softcap)
+    else:                                                  # the shifted truth (pinned to attn_ref_torch at shift 0 on the CPU)
+        ro, rl = shift_ref.ref_fwd(tq, tk, tv, scale, c.causal, c.window, c.shift, c.softcap)
     if c.softcap:                                          # the cap bites: capped and uncapped exact outputs differ
         ro0, _ = ref_fwd(tq, tk, tv, scale, c.causal, c.window, None)
         diff = float((ro0 - ro).abs().max())
         assert diff > 10 * TOL[c.dt]["out"][0], f"{what}: the cap does not bite (max |capped - uncapped| = {diff:.3e})"
     kw = dict(window=c.window, softcap=c.softcap, family=c.family)
+    if c.shift is not None:
+        kw["shift"] = c.shift
     # ---- forward, twice ---------------------------------------------------------------------------------------------
     runs = []
     for _ in range(2):
@@ -233,7 +329,11 @@ def run_dense(dev, c):
     judge(what, dict(out=out, lse=lse), dict(out=ro, lse=rl), c.dt, c.Sq, c.Sk, G)
     # ---- backward (exact lse, delta from the 16-bit-rounded reference out), twice ----------------------------------------
     o16 = ro.to(tq.dtype)
-    rdq, rdk, rdv, delta = ref_bwd(tdo, tq, tk, tv, o16, rl, scale, c.causal, c.window, c.softcap)
+    if c.shift is None:
+        rdq, rdk, rdv, delta = ref_bwd(tdo, tq, tk, tv, o16, rl, scale, c.causal, c.window, c.softcap)
+    else:
+        rdq, rdk, rdv = shift_ref.ref_bwd(tdo, tq, tk, tv, o16, rl, scale, c.causal, c.window, c.shift, c.softcap)
+        delta = ref_delta(tdo, o16)
     lse_t, delta_t = rl.float().contiguous(), delta.float().contiguous()
     grads = []
     for _ in range(2):
@@ -261,6 +361,19 @@ def test_dense_kernels_on_needle_inputs(dev, c):
     above the visible ones) became the reference max and every visible P went through the PV MFMA as an fp16 subnormal
     (a quantum of ~7e-4 on weights of ~1e-2).  bf16 has the range and never showed it; on N(0,1) inputs a masked score is
     never that far above the visible ones."""
+    run_dense(dev, c)
+
+
+@pytest.mark.parametrize("c", SHIFTED + RING_BLOCKS, ids=[c.id for c in SHIFTED + RING_BLOCKS])
+def test_shifted_kernels_on_needle_inputs(dev, c):
+    """The same run (kinds asserted, NaN arena, two bit-identical launches, lse = -inf / out = 0 / dq = 0 exactly on the rows
+    without a visible key -- inside live launches too -- and `needle_inputs.verdicts`) with a shifted diagonal, against
+    tests/shift_ref.py: an off-by-one in causal_off + shift or win_lo + shift loses or adds the private needle of a sampled
+    row, a 100 % error on that row and on that key's dK / dV (tests/test_needle_cpu.py: the shift mutants).  RING_BLOCKS: the
+    launches of a basic ring of 4 x 640 under the windows at which its planner's decisions flip.
+    Measured on MI355X (worst error / bound; a record, not a gate -- profiles/needle_shift.txt): SHIFTED bf16 out <= 0.27,
+    lse <= 0.002, dq <= 0.17, dk <= 0.48, dv <= 0.24; fp16 out <= 0.15, lse <= 0.001, dq <= 0.06, dk <= 0.21, dv <= 0.21;
+    RING_BLOCKS (bf16) out <= 0.26, lse <= 0.001, dq <= 0.09, dk <= 0.25, dv <= 0.23."""
     run_dense(dev, c)
 
 

@@ -3,8 +3,13 @@
 the ring forward / backward of USP_RING_WINDOW=global on virtual ranks (real kernels, real RCCL self send/recv) and on two
 processes sharing the GPU.
 
-Inputs are N(0,1): with at most 1280 keys per row a lost 64-key tile is at least 5 % of a row's mass, far outside TOL
-(SURVEY.md section 8(c)), so white noise is not blind at these sizes."""
+Inputs are N(0,1): with at most 1280 keys per row a lost 64-key TILE is at least 5 % of a row's mass, far outside TOL
+(SURVEY.md section 8(c)), so white noise is not blind to tiles at these sizes.  It IS blind to single keys: with windows of
+327, 500 or 700 keys one key is 0.14 - 0.3 % of a row's mass, so an off-by-one in causal_off + shift or win_lo + shift passes
+every N(0,1) test of this file.  Key-exactness of the shifted masks is pinned on needle inputs, in tests/test_gpu_needle.py
+(`SHIFTED`, `RING_BLOCKS`) and tests/test_gpu_mutation.py, not here; the ring itself runs on needle inputs in
+`test_global_window_on_virtual_ranks_with_needle_inputs` below.  The extreme window bounds and shifts at the end of the file
+are O(1) effects (everything or nothing visible): white noise suffices there."""
 import os
 
 import pytest
@@ -170,10 +175,10 @@ def nccl_single():
         dist.destroy_process_group()
 
 
-def _virtual_run(monkeypatch, nccl_single, dev, ud, rd, c, window, causal, softcap=0.0, repeat_backward=False):
+def _virtual_run(monkeypatch, nccl_single, dev, ud, rd, c, window, causal, softcap=0.0, repeat_backward=False, inputs=None):
     """Every rank of a ud x rd grid as a thread: Ulysses exchange by hand (autograd cannot run the ranks' backwards side by
     side), the ring forward and backward of the package with the real HipBlockBackend.  Returns per rank (out, dq, dk, dv
-    [, dk, dv of a second backward]) and the unsharded inputs."""
+    [, dk, dv of a second backward]) and the unsharded inputs (`inputs`: S -> (q, k, v, do) in place of the N(0,1) draw)."""
     import yunchang_amd.comm.all_to_all as A
     import yunchang_amd.ring.ring_flash_attn as R
     from yunchang_amd.kernels import get_block_backend
@@ -184,7 +189,7 @@ def _virtual_run(monkeypatch, nccl_single, dev, ud, rd, c, window, causal, softc
     patch_dist(monkeypatch, grid)
     ws, Hq, Hkv, D = ud * rd, 4, 2, 128
     S = c * rd
-    q, k, v, do = _case(dev, 1, S, S, Hq, Hkv, D, "bfloat16", seed=4)
+    q, k, v, do = _case(dev, 1, S, S, Hq, Hkv, D, "bfloat16", seed=4) if inputs is None else inputs(S)
     rows = S // ws
     loc = [[t[:, r * rows:(r + 1) * rows].contiguous() for t in (q, k, v, do)] for r in range(ws)]
     streams = [torch.cuda.Stream(device=dev) for _ in range(ws)]
@@ -231,6 +236,53 @@ def test_global_window_on_virtual_ranks(dev, nccl_single, monkeypatch, ud, rd, w
             assert torch.equal(res[r][2], res[r][4]) and torch.equal(res[r][3], res[r][5]), f"{what}: dk / dv of two identical calls"
 
 
+RING_NEEDLE = [(ud, rd, w, causal) for ud, rd in ((1, 4), (2, 2))
+               for w, causal in (("c-1", True), ("c", True), ("c+1", True), ((100, 60), False))]
+
+
+def ring_needle_inputs(S, c, window, causal, Hq=4, Hkv=2, D=128, dt="bfloat16"):
+    """Needle inputs (tests/needle_inputs.py) over the GLOBAL sequence of a ring of chunks of c rows: private needles on the
+    mask edges of sampled global rows and of the last / first row of every rank block, and on the last key of a block and the
+    first of the next for rows that see both."""
+    import needle_inputs as NI
+    import test_gpu_needle as GN
+    rows = sorted(set(NI.sample_rows(S, 10, 3)) | {r for m in range(1, S // c) for r in (m * c - 1, m * c)})
+    edges = NI.mask_edges(rows, S, S, causal, window)
+    for kb in range(c, S, c):
+        for r in (kb + 9, min(S - 1, kb + c - 1)):
+            if all(NI._visible(r, j, S, S, causal, window) for j in (kb - 1, kb)):
+                edges += [(r, kb - 1), (r, kb)]
+    C = GN.classes_for(GN._keys_seen(S, S, causal, window), D)
+    return NI.make(S, S, Hq, Hkv, D, dt, C, seed=90, edges=edges)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("ud,rd,w,causal", RING_NEEDLE, ids=lambda v: str(v).replace(" ", ""))
+def test_global_window_on_virtual_ranks_with_needle_inputs(dev, nccl_single, monkeypatch, ud, rd, w, causal):
+    """The same ring runs on needle inputs, at the windows where the planner's empty / `keys` / `rows` decisions flip (c - 1, c,
+    c + 1: the block two ranks back holds no, no, one visible (row, key) pair), judged per rank with `needle_inputs.verdicts`
+    against the GLOBAL fp64 reference: a ring block that loses or adds the one key on a bound is a 100 % error on a sampled row."""
+    import needle_inputs as NI
+    c = 320 if rd == 4 else 640
+    window = {"c-1": (c - 1, 0), "c": (c, 0), "c+1": (c + 1, 0)}.get(w, w)
+    made = {}
+
+    def inputs(S):
+        made["nd"] = nd = ring_needle_inputs(S, c, window, causal)
+        return [torch.from_numpy(x).to(torch.bfloat16).to(dev) for x in (nd.q, nd.k, nd.v, nd.do)]
+    res, (q, k, v, do), rows, scale = _virtual_run(monkeypatch, nccl_single, dev, ud, rd, c, window, causal, inputs=inputs)
+    S = q.shape[1]
+    ref = _reference(("needle", ud, rd, window), q, k, v, do, scale, causal, window, 0)
+    for r in range(ud * rd):
+        sl = slice(r * rows, (r + 1) * rows)
+        got = dict(zip(("out", "dq", "dk", "dv"), res[r][:4]))
+        want = {n_: t[:, sl] for n_, t in zip(("out", "dq", "dk", "dv"), (ref[0], ref[2], ref[3], ref[4]))}
+        ver = NI.verdicts(got, want, "bfloat16", S, S, 2)
+        print(f"[needle-ring] {ud}x{rd} window {window} rank {r}: " + " ".join(f"{n_}={x:.3f}" for n_, (_, x) in ver.items()))
+        bad = {n_: round(x, 3) for n_, (ok, x) in ver.items() if not ok}
+        assert not bad, f"{ud}x{rd} window {window} rank {r}: out of tolerance, worst error / bound {bad}"
+
+
 # ---- 4. two processes sharing the GPU ------------------------------------------------------------------------------------------
 def _two_process_worker(rank, ws):
     """(RCCL refuses two ranks on one device: the transport is gloo, ordered like RCCL, as in tests/test_gpu_multiproc.py.)"""
@@ -263,3 +315,71 @@ def test_global_window_two_processes_one_gpu():
         for a, t, name in zip(got, truth, ("out", "dq", "dk", "dv")):
             tol = TOL["bfloat16"]["out"] if name == "out" else grad_tol("bfloat16", 2)
             assert_close(a, t, *tol, f"two processes, rank {rank}: {name}")
+
+
+# ---- 5. extreme window bounds and shifts: everything or nothing visible -----------------------------------------------------------------
+_IMAX, _SMAX = (1 << 31) - 1, (1 << 30) - 1
+# (causal, window, shift, what the mask leaves: "all" | "none" | "causal", a left bound that cuts -> not for the 64-row family)
+EXTREME = [(False, (_IMAX, -1), None, "all", False), (False, (-1, _IMAX), None, "all", False), (True, (_IMAX, 0), None, "causal", False),
+           (False, (_IMAX, _IMAX), None, "all", False), (False, (_IMAX, -1), _SMAX, "all", False), (False, (_IMAX, -1), -_SMAX, "all", False),
+           (False, (-1, _IMAX), _SMAX, "all", False), (False, (-1, _IMAX), -_SMAX, "all", False), (False, (_IMAX, _IMAX), -_SMAX, "all", False),
+           (True, None, _SMAX, "all", False), (True, None, -_SMAX, "none", False), (True, (_IMAX, 0), -_SMAX, "none", False),
+           (False, (5, -1), _SMAX, "none", True), (False, (-1, 5), -_SMAX, "none", False), (False, (_IMAX, 5), _SMAX, "all", False)]
+
+
+@pytest.mark.parametrize("Sq,Sk", [(320, 320), (200, 320), (320, 200)])
+def test_extreme_window_bounds_and_shifts(dev, Sq, Sk):
+    """window_left / window_right = INT32_MAX (a caller's "unbounded"), alone and with a shift of +-(2^30 - 1), where the result
+    is every key, no key, or plain causal: both families and the default dispatch against tests/shift_ref.py at the stated
+    tolerances; an empty result is exactly out = 0, lse = -inf, zero gradients.  (The host decode of these values is swept on
+    the CPU first, tests/test_host_api.py: the sums are formed in 64 bits, a bound that cuts nothing is dropped -- which is what
+    lets the 64-row family take a call whose left bound is INT32_MAX.)"""
+    dt, D = "bfloat16", 128
+    q, k, v, do = _case(dev, 2, Sq, Sk, 4, 2, D, dt, seed=7)
+    scale = D ** -0.5
+    for causal, window, shift, left_over, left_cuts in EXTREME:
+        vis = shift_ref.visible(Sq, Sk, causal, window, shift or 0)
+        plain = shift_ref.visible(Sq, Sk, left_over == "causal")
+        assert torch.equal(vis, plain if left_over != "none" else torch.zeros_like(vis)), (causal, window, shift)
+        ref = _reference(("extreme", Sq, Sk, causal, window, shift), q, k, v, do, scale, causal, window, shift or 0)
+        for family in ("row64", "wave32", None):
+            if family == "row64" and left_cuts:
+                continue
+            what = f"{Sq}x{Sk} causal {causal} window {window} shift {shift} family {family}"
+            out, lse, kinds = _run_fwd(q, k, v, scale, causal, window, shift, family=family)
+            if family == "row64":
+                assert kinds == ("fwd_row64",), (what, kinds)
+            _check_fwd(out, lse, ref, dt, what)
+            grads, kinds = _run_bwd(do, q, k, v, ref, scale, causal, window, shift, family=family)
+            if family == "row64":
+                assert "dkdv_row64" in kinds and "dq_row64" in kinds, (what, kinds)
+            for g, r, name in zip(grads, ref[2:], ("dq", "dk", "dv")):
+                assert_close(g, r, *grad_tol(dt, 2), f"{what} {name}")
+            if left_over == "none":
+                assert bool((out == 0).all()) and bool(torch.isinf(lse).all()) and bool((lse < 0).all()), what
+                assert all(bool((g == 0).all()) for g in grads), what
+
+
+def test_python_entry_points_pass_an_int32_max_window_through(dev):
+    """hip_attn_forward / hip_attn_backward / hip_attn_func with window_size = (2^31 - 1, 0), causal: the unwindowed causal result."""
+    from yunchang_amd.kernels.attention import hip_attn_backward, hip_attn_forward, hip_attn_func
+    dt = "bfloat16"
+    q, k, v, do = _case(dev, 1, 320, 200, 4, 2, 128, dt, seed=8)
+    win = ((1 << 31) - 1, 0)
+    out0, lse0 = hip_attn_forward(q, k, v, causal=True)
+    out1, lse1 = hip_attn_forward(q, k, v, causal=True, window_size=win)
+    assert_close(out1, out0.double(), *TOL[dt]["out"], "hip_attn_forward out")
+    assert_close(lse1, lse0.double(), *TOL[dt]["out"], "hip_attn_forward lse")
+    g0, g1 = ([torch.full_like(t, float("nan")) for t in (q, k, v)] for _ in range(2))
+    hip_attn_backward(do, q, k, v, out0, lse0, *g0, bwd_causal=True)
+    hip_attn_backward(do, q, k, v, out0, lse0, *g1, bwd_causal=True, window_size=win)
+    for a, b, name in zip(g1, g0, ("dq", "dk", "dv")):
+        assert_close(a, b.double(), *grad_tol(dt, 2), f"hip_attn_backward {name}")
+    res = []
+    for w in ((-1, -1), win):
+        leaves = [t.detach().clone().requires_grad_(True) for t in (q, k, v)]
+        o = hip_attn_func(*leaves, causal=True, window_size=w)
+        o.backward(do)
+        res.append([o.detach()] + [t.grad for t in leaves])
+    for a, b, name in zip(res[1], res[0], ("out", "dq", "dk", "dv")):
+        assert_close(a, b.double(), *(TOL[dt]["out"] if name == "out" else grad_tol(dt, 2)), f"hip_attn_func {name}")

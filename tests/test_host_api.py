@@ -564,3 +564,61 @@ def test_relay_plan_is_a_partition_and_an_involution():
                 assert spans[0][0] == 0 and spans[-1][1] == rows and all(a[1] == b[0] for a, b in zip(spans, spans[1:]))
     assert R.pair_and_helpers(0, (4, 2, 8, True)) is None and R.pair_and_helpers(0, (2, 1, 2, True)) is None
     assert R.pair_and_helpers(0, None) is None or R.GRID is not None
+
+
+def test_mask_decode_serves_every_int32_window_and_shift(tmp_path):
+    """csrc/usp_mask_decode.h (the integer part of usp_host.hpp: decode_mask) compiled for the host and swept against Python
+    integers: window bounds up to INT32_MAX (a caller's "unbounded"), shifts up to +-(2^30 - 1), Sq and Sk from 1 to 2^20 in
+    both orders.  The decoded (causal, causal_off, win_on, win_lo) must select exactly the (row, key) pairs of the definition
+    in include/usp_hip.h -- checked on the corner rows and keys and on the keys beside every bound of those rows --, stay inside
+    |x| <= 2^30 + Sq + Sk (the range in which the kernels' own sums stay in `int`; the header lists them), and drop a bound
+    that cuts nothing at this (Sq, Sk, shift).  The arithmetic this replaces formed Sk - Sq - window_left + mask_shift in
+    `int`: window_left = INT32_MAX overflowed with Sq > Sk or a negative shift."""
+    import subprocess
+    src = tmp_path / "mask.c"
+    src.write_text('#define USP_MASK_FN\n#include "usp_mask_decode.h"\n')
+    lib = tmp_path / "libmask.so"
+    subprocess.check_call(["gcc", "-O1", "-shared", "-fPIC", "-I", os.path.join(ROOT, "long-context-attention_amd", "csrc"),
+                           str(src), "-o", str(lib)])
+
+    class Bounds(ctypes.Structure):
+        _fields_ = [(n, ctypes.c_int) for n in ("causal", "windowed", "causal_off", "win_on", "win_lo")]
+    decode = ctypes.CDLL(str(lib)).usp_decode_mask_bounds
+    decode.restype = Bounds
+    decode.argtypes = [ctypes.c_int] * 8
+    big = [-1, 0, 1, (1 << 30) - 1, 1 << 30, (1 << 31) - 1]
+    shifts = [None, 0, 1, -1, (1 << 30) - 1, -((1 << 30) - 1)]
+    sizes = [1, 320, 1 << 20]
+    n = dropped = saturated = 0
+    for Sq in sizes:
+        for Sk in sizes:
+            rows = sorted({r for r in (0, 1, Sq // 2, Sq - 2, Sq - 1) if 0 <= r < Sq})
+            keys0 = {j for j in (0, 1, Sk // 2, Sk - 2, Sk - 1) if 0 <= j < Sk}
+            for causal in (0, 1):
+                for has_win, wl_, wr_ in [(1, a, b) for a in big for b in big] + [(0, (1 << 31) - 1, 5), (0, 7, (1 << 31) - 1)]:
+                    for shift in shifts:
+                        m = decode(Sq, Sk, causal, has_win, wl_, wr_, shift is not None, shift or 0)
+                        # ---- the definition, in Python integers
+                        left = wl_ if has_win else -1
+                        right = 0 if causal else (wr_ if has_win else -1)
+                        has_l, has_r = left >= 0, right >= 0
+                        off = Sk - Sq + ((shift or 0) if (has_l or has_r) else 0)
+                        what = (Sq, Sk, causal, has_win, wl_, wr_, shift, (m.causal, m.causal_off, m.win_on, m.win_lo))
+                        for r in rows:
+                            keys = set(keys0)
+                            for edge in ([r + off + right] if has_r else []) + ([r + off - left] if has_l else []):
+                                keys |= {j for j in (edge - 1, edge, edge + 1) if 0 <= j < Sk}
+                            for j in keys:
+                                want = (not has_r or j <= r + off + right) and (not has_l or j >= r + off - left)
+                                got = (not m.causal or j <= r + m.causal_off) and (not m.win_on or j >= r + m.win_lo)
+                                assert got == want, (what, r, j)
+                        lim = (1 << 30) + Sq + Sk
+                        assert abs(m.causal_off) <= lim and abs(m.win_lo) <= lim, what
+                        # ---- a bound that cuts no pair is dropped (row 0 loses key Sk - 1 first, row Sq - 1 key 0)
+                        assert bool(m.causal) == (has_r and off + right < Sk - 1), what
+                        assert bool(m.win_on) == (has_l and off - left > 1 - Sq), what
+                        assert bool(m.windowed) == (has_l or right > 0), what
+                        dropped += (has_r and not m.causal) + (has_l and not m.win_on)
+                        saturated += (m.causal and m.causal_off != off + right) + (m.win_on and m.win_lo != off - left)
+                        n += 1
+    assert n == 9 * 2 * 38 * 6 and dropped > 1000 and saturated > 100, (n, dropped, saturated)

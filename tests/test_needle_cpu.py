@@ -27,10 +27,12 @@ class Mask:
     """Visibility of key j to row i: causal (bottom-right), window, packed sequences (causal inside each), with optional
     off-by-one shifts for the mutants."""
 
-    def __init__(self, Sq, Sk, causal=False, window=None, seqs=None):
-        self.Sq, self.Sk, self.causal, self.window, self.seqs = Sq, Sk, causal, window, seqs
+    def __init__(self, Sq, Sk, causal=False, window=None, seqs=None, shift=0):
+        self.Sq, self.Sk, self.causal, self.window, self.seqs, self.shift = Sq, Sk, causal, window, seqs, int(shift or 0)
 
-    def vis(self, r0, r1, d_right=0, d_left=0, d_first=0, d_half=0):
+    def vis(self, r0, r1, d_right=0, d_left=0, d_first=0, d_half=0, shift_right=None, shift_left=None):
+        """`shift_right` / `shift_left`: the shift one bound is computed with, in place of the mask's own (the mutants that
+        move one bound only, or the wrong way)."""
         i = torch.arange(r0, r1)[:, None]
         j = torch.arange(self.Sk)[None, :]
         if self.seqs is not None:                        # (first, len) per sequence, same table for rows and keys
@@ -49,11 +51,13 @@ class Mask:
         if self.causal:
             right = 0
         off = self.Sk - self.Sq
+        sr = self.shift if shift_right is None else shift_right
+        sl = self.shift if shift_left is None else shift_left
         v = torch.ones(r1 - r0, self.Sk, dtype=torch.bool)
         if right >= 0:
-            v &= j <= i + off + right + d_right
+            v &= j <= i + off + sr + right + d_right
         if left >= 0:
-            v &= j >= i + off - left + d_left
+            v &= j >= i + off + sl - left + d_left
         return v
 
 
@@ -473,10 +477,11 @@ def test_needle_conditions_of_the_gpu_large_cases(cid):
 # ---------------------------------------------------------------------------------------------------------------------
 # honest 16-bit rounding on needle inputs: the model the amplitude of dout was lowered against
 # ---------------------------------------------------------------------------------------------------------------------
-def bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, causal, dt):
+def bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, causal, dt, vis=None):
     """The block backward in fp64 WITH the roundings every 16-bit flash backward performs (rounding_models.bwd_16bit_model
     without the pre-scaled K, in torch: 5 x faster than the numpy one on the 2^24-score cases of this file): P is rounded to
-    the 16-bit type before dV = P^T dO and dS is formed from that P, dS is rounded before dQ = dS K and dK = dS^T Q."""
+    the 16-bit type before dV = P^T dO and dS is formed from that P, dS is rounded before dQ = dS K and dK = dS^T Q.
+    `vis`: (Sq, Sk) bool, the mask in place of `causal`."""
     B, Sq, Hq, D = tq.shape
     Sk, Hkv = tk.shape[1], tk.shape[2]
     G = Hq // Hkv
@@ -484,7 +489,9 @@ def bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, causal, dt):
     k, v = tk.double().repeat_interleave(G, 2), tv.double().repeat_interleave(G, 2)
     log2e = 1.4426950408889634
     s2 = torch.einsum("bthd,bshd->bhts", q, k) * (scale * log2e)
-    if causal:
+    if vis is not None:
+        s2 = s2.masked_fill(~vis, float("-inf"))
+    elif causal:
         i, j = torch.arange(Sq)[:, None] + Sk - Sq, torch.arange(Sk)[None, :]
         s2 = s2.masked_fill(j > i, float("-inf"))
     fin = torch.isfinite(rl)
@@ -522,6 +529,267 @@ def test_16bit_rounding_model_keeps_a_2x_margin_on_the_gpu_cases(c):
     ver = NI.verdicts({n_: t.numpy() for n_, t in got.items()}, dict(dq=rdq.numpy(), dk=rdk.numpy(), dv=rdv.numpy()),
                       c.dt, c.Sq, c.Sk, c.Hq // c.Hkv)
     assert all(ratio <= 0.5 for _, ratio in ver.values()), (c.id, ver)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a shifted diagonal (USP_ATTN_SHIFT): the helpers, the tables of tests/test_gpu_needle.py, the mutants
+# ---------------------------------------------------------------------------------------------------------------------
+import hashlib  # noqa: E402
+
+import shift_ref  # noqa: E402
+
+SHIFT_CASES = GN.SHIFTED + GN.RING_BLOCKS
+
+
+def _old_mask_edges(rows, Sq, Sk, causal=False, window=None):
+    """needle_inputs.mask_edges as it was before it took a shift (the diagonal hard-coded at Sk - Sq), kept here frozen."""
+    left, right = (-1, -1) if window is None else (int(window[0]), int(window[1]))
+    if causal:
+        right = 0
+    off = Sk - Sq
+    out = []
+    for r in rows:
+        if right >= 0:
+            out += [(r, r + off + right), (r, r + off + right + 1)]
+        if left >= 0:
+            out += [(r, r + off - left), (r, r + off - left - 1)]
+    return [(r, j) for r, j in out if 0 <= j < Sk]
+
+
+# sha256 of repr((classes, edge list)) of three DENSE cases, taken from the helpers BEFORE they knew a shift: the inputs are a
+# deterministic function of (shape, seed, classes, edges), so equal lists are bit-identical inputs.  (The tensors themselves
+# are not hashed: a BLAS that sums in another order may round one noise element the other way.)
+_PINNED_EDGES = {"row64-causal": "6b15691e8eace31e", "ksplit4-window": "e501c9e2c9dc3b76", "cuts-5-3-w32": "09acd1f110e54e9d"}
+
+
+def _edge_hash(c):
+    C = GN.classes_for(GN._keys_seen(c.Sq, c.Sk, c.causal, c.window), c.D)
+    return hashlib.sha256(repr((C, [(int(r), int(j)) for r, j in GN.edges_for(c)])).encode()).hexdigest()[:16]
+
+
+def test_unshifted_inputs_are_what_they_were():
+    """`shift=0` everywhere: the edge needles and class counts of three DENSE cases hash to the values recorded before the
+    helpers took a shift; for EVERY dense case the mask edges equal the frozen pre-shift formula, an explicit shift of 0 changes
+    nothing, and a shift without a bound is ignored."""
+    for cid, want in _PINNED_EDGES.items():
+        assert _edge_hash(GN._CFG[cid]) == want, cid
+    for c in GN.DENSE:
+        rows = NI.sample_rows(c.Sq, 10, c.seed)
+        assert NI.mask_edges(rows, c.Sq, c.Sk, c.causal, c.window) == _old_mask_edges(rows, c.Sq, c.Sk, c.causal, c.window), c.id
+        assert GN.edges_for(c) == GN.edges_for(c._replace(shift=0)), c.id
+        assert GN._keys_seen(c.Sq, c.Sk, c.causal, c.window) == GN._keys_seen(c.Sq, c.Sk, c.causal, c.window, 0)
+        if not c.causal and c.window is None:
+            assert GN.edges_for(c) == GN.edges_for(c._replace(shift=77)), c.id
+            assert (GN.visible_fn(c._replace(shift=77))(5) == GN.visible_fn(c)(5)).all()
+    a, b = GN.make_inputs(GN._CFG["more-rows"]), GN.make_inputs(GN._CFG["more-rows"]._replace(shift=0))
+    assert all(np.array_equal(getattr(a, n), getattr(b, n)) for n in ("q", "k", "v", "do"))
+
+
+@pytest.mark.parametrize("c", SHIFT_CASES, ids=[c.id for c in SHIFT_CASES])
+def test_shifted_helpers_agree_with_the_shifted_reference(c):
+    """needle_inputs._visible / test_gpu_needle.visible_fn / Mask against tests/shift_ref.py (the GPU tests' truth); the mask
+    edges are the last visible and the first invisible key of their row; the streamed key tiles of every 256-row query tile
+    are exactly the tiles that hold a visible key (another range would mark the wrong cut boundaries)."""
+    want = shift_ref.visible(c.Sq, c.Sk, c.causal, c.window, c.shift or 0).numpy()
+    vis = GN.visible_fn(c)
+    m = Mask(c.Sq, c.Sk, c.causal, c.window, shift=c.shift)
+    for r in NI.sample_rows(c.Sq, 10, c.seed):
+        assert (vis(r) == want[r]).all() and (m.vis(r, r + 1)[0].numpy() == want[r]).all(), (c.id, r)
+        assert all(NI._visible(r, j, c.Sq, c.Sk, c.causal, c.window, c.shift or 0) == want[r, j] for j in range(0, c.Sk, 37))
+    for r, j in NI.mask_edges(NI.sample_rows(c.Sq, 10, c.seed), c.Sq, c.Sk, c.causal, c.window, c.shift or 0):
+        beside = [want[r, jj] for jj in (j - 1, j + 1) if 0 <= jj < c.Sk]
+        assert len(beside) < 2 or any(b != want[r, j] for b in beside), (c.id, r, j)
+    for q0 in range(0, c.Sq, 256):
+        t0, nt = NI.key_tiles_of_query_tile(q0, 256, c.Sq, c.Sk, c.causal, c.window, c.shift or 0)
+        seen = np.flatnonzero(want[q0:q0 + 256].any(0))
+        if seen.size:
+            assert t0 == seen[0] // 64 and nt == seen[-1] // 64 + 1, (c.id, q0, t0, nt, seen[0], seen[-1])
+        else:
+            assert t0 == nt, (c.id, q0, t0, nt)
+
+
+@pytest.mark.parametrize("c", SHIFT_CASES, ids=[c.id for c in SHIFT_CASES])
+def test_needle_conditions_of_the_gpu_shifted_tables(c):
+    nd = GN.make_inputs(c)
+    NI.assert_needle_conditions(nd, NI.sample_rows(c.Sq, 24, c.seed), c.D ** -0.5, GN.visible_fn(c), c.id)
+    # the edge needles of the sampled rows lie on the SHIFTED mask's edges: the row sees one key of a pair and not the other
+    vis = GN.visible_fn(c)
+    pairs = NI.mask_edges(NI.sample_rows(c.Sq, 10, c.seed), c.Sq, c.Sk, c.causal, c.window, c.shift or 0)
+    if not c.id.endswith(("all-visible", "all-visible-d64")):
+        assert any(vis(r)[j] for r, j in pairs) and not all(vis(r)[j] for r, j in pairs), c.id
+
+
+def test_shifted_table_covers_what_it_is_meant_to():
+    """Asserted from the table itself: a deleted row fails here, on the CPU."""
+    T = GN.SHIFTED
+    assert all(c.shift is not None and (c.causal or c.window is not None) for c in T)
+    for c in T:                                            # the shapes: >= 3 query tiles, >= 2 dK/dV blocks, >= 8 key tiles
+        cut = c.k_splits > 1 or c.splits != (0, 0)
+        assert c.Sq > 512 and c.Sk >= 512 and 600 <= max(c.Sq, c.Sk) <= (2048 if cut else 1300), c.id
+    fam = lambda f: [c for c in T if c.family == f]
+    left = lambda c: c.window is not None and c.window[0] >= 0
+    right_win = lambda c: not c.causal and c.window is not None and c.window[1] > 0
+    fwd = lambda k, split: any(c.fwd is not None and k in c.fwd and ((GN._SM in c.fwd) == split) for c in T)
+    # ---- kernel: every launch kind that decodes the mask
+    assert fwd("fwd_row64", False) and fwd("fwd_row64", True) and fwd("fwd_wave4", False) and fwd("fwd_wave8", False)
+    assert any(left(c) and c.family == "wave32" and c.k_splits <= 1 for c in T)              # the window instantiation
+    assert any(left(c) and c.family == "wave32" and c.k_splits > 1 for c in T)
+    for k in ("dq_row64", "dq_wave8", "dkdv_row64", "dkdv_wave8"):
+        assert any(c.bwd is not None and k in c.bwd for c in T), k
+    assert any(c.family is None for c in T)
+    # ---- bound
+    assert any(c.causal and not left(c) for c in fam("row64")) and any(right_win(c) for c in fam("row64"))
+    assert any(left(c) and not c.causal and c.window[1] < 0 for c in fam("wave32"))
+    assert any(left(c) and (c.causal or c.window[1] >= 0) for c in fam("wave32"))
+    assert not any(left(c) for c in fam("row64"))          # (the 64-row family declines a left bound that cuts)
+    # ---- shift kinds, each in both families
+    for f in ("row64", "wave32"):
+        S = fam(f)
+        assert any(c.shift > 0 for c in S) and any(c.shift < 0 for c in S), f
+        assert any(c.shift % 64 for c in S), f
+        for m in (64, 128, 256):
+            assert any(c.shift and c.shift % m == 0 for c in S), (f, m)
+        # a negative shift that empties whole leading 256-row tiles and part of the next
+        assert any(c.causal and 256 < -(c.Sk - c.Sq + c.shift) < c.Sq and (c.Sk - c.Sq + c.shift) % 256 for c in S), f
+        assert any(c.causal and not left(c) and c.shift >= c.Sk for c in S), f             # every key visible
+    assert any(left(c) and c.window[0] < 64 and c.shift % 2 for c in fam("wave32"))          # narrower than a tile, odd shift
+    # ---- rest
+    assert {c.D for c in T} == {32, 64, 128} and {c.dt for c in T} == {"bfloat16", "float16"}
+    assert any(c.Sq > c.Sk for c in T) and any(c.Sq < c.Sk for c in T) and any(c.B == 2 for c in T)
+    assert any(c.k_splits == 3 and c.family == "row64" and c.causal for c in T)
+    assert any(c.k_splits == 4 and left(c) for c in T)
+    assert any(c.splits == (3, 2) and c.family == "row64" for c in T) and any(c.splits == (5, 3) and c.family == "wave32" for c in T)
+    assert {c.dkdv_heads for c in T if c.Hq // c.Hkv == 4 and c.dkdv_heads} == {1, 2, 4}
+    # ---- what the ring really launches: from the planner, the values at which its decisions flip
+    R = GN.RING_BLOCKS
+    assert all(c.Sq == c.Sk == 640 for c in R) and len({(c.causal, c.window, c.shift) for c in R}) == len(R) >= 6
+    assert {c.shift for c in R} >= {None, 640, -640, 1280}
+    assert any(c.window == (641, -1) and c.shift == 1280 for c in R)       # one (row, key) pair is left of that block
+    assert not any(c.window in ((639, -1), (640, -1)) and c.shift == 1280 for c in R)      # ... and none at 639 / 640
+
+
+def test_needle_conditions_of_the_gpu_ring_window_cases():
+    """tests/test_gpu_ring_window.py: the needle inputs of the global-window ring, every window of its table."""
+    import test_gpu_ring_window as RW
+    from types import SimpleNamespace
+    for ud, rd, w, causal in RW.RING_NEEDLE:
+        c = 320 if rd == 4 else 640
+        window = {"c-1": (c - 1, 0), "c": (c, 0), "c+1": (c + 1, 0)}.get(w, w)
+        S = c * rd
+        nd = RW.ring_needle_inputs(S, c, window, causal)
+        vis = GN.visible_fn(SimpleNamespace(Sq=S, Sk=S, causal=causal, window=window))
+        NI.assert_needle_conditions(nd, NI.sample_rows(S, 24, 3), 128 ** -0.5, vis, f"ring {ud}x{rd} {window}")
+
+
+def _model_ratios(c, do_mul=None):
+    """Worst error / bound of the honest 16-bit rounding model over a shifted case, one KV group of one batch entry at a time."""
+    nd = GN.make_inputs(c if do_mul is None else c._replace(do_mul=do_mul))
+    dt = getattr(torch, c.dt)
+    G, scale = c.Hq // c.Hkv, c.D ** -0.5
+    vis = shift_ref.visible(c.Sq, c.Sk, c.causal, c.window, c.shift or 0)
+    worst = {}
+    for b in range(c.B):
+        for hk in range(c.Hkv):
+            hs = slice(hk * G, (hk + 1) * G)
+            tq, tdo = (torch.from_numpy(x[b:b + 1, :, hs]).to(dt) for x in (nd.q, nd.do))
+            tk, tv = (torch.from_numpy(x[b:b + 1, :, hk:hk + 1]).to(dt) for x in (nd.k, nd.v))
+            ro, rl = shift_ref.ref_fwd(tq, tk, tv, scale, c.causal, c.window, c.shift or 0)
+            o16 = ro.to(dt)
+            rdq, rdk, rdv = shift_ref.ref_bwd(tdo, tq, tk, tv, o16, rl, scale, c.causal, c.window, c.shift or 0)
+            got = bwd_16bit_model(tdo, tq, tk, tv, o16, rl, scale, c.causal, dt, vis=vis)
+            ver = NI.verdicts({n_: t.numpy() for n_, t in got.items()}, dict(dq=rdq.numpy(), dk=rdk.numpy(), dv=rdv.numpy()),
+                              c.dt, c.Sq, c.Sk, G)
+            for n_, (_, ratio) in ver.items():
+                worst[n_] = max(worst.get(n_, 0.0), ratio)
+    return worst
+
+
+@pytest.mark.parametrize("c", SHIFT_CASES, ids=[c.id for c in SHIFT_CASES])
+def test_16bit_rounding_model_keeps_a_2x_margin_on_the_shifted_cases(c):
+    """As for the dense table: honest rounding of P and dS stays inside HALF of every stated bound on every shifted case (where it
+    did not at the default amplitude of dout, the case carries a lower `do_mul`: the tolerance is never widened)."""
+    worst = _model_ratios(c)
+    assert all(r <= 0.5 for r in worst.values()), (c.id, worst)
+
+
+# ---- the shift mutants: one 256-row query tile of every head computes its mask from a wrong shift ----------------------------
+def _shift_case(cid):
+    if ("shift", cid) not in _CACHE:
+        c = GN._CFG[cid]
+        nd = GN.make_inputs(c)
+        ex = Exact(nd.q[0], nd.k[0], nd.v[0], nd.do[0], c.dt, Mask(c.Sq, c.Sk, c.causal, c.window, shift=c.shift), c.D ** -0.5)
+        _CACHE[("shift", cid)] = (c, ex)
+    return _CACHE[("shift", cid)]
+
+
+def _tile_all_heads(ex, r0, r1, mut):
+    """Rows [r0, r1) of EVERY head under `mut` (a wrong mask decode is the same for all heads of a launch)."""
+    res = {n: t.clone() for n, t in ex.want().items()}
+    for h in range(ex.out.shape[1]):
+        base, got = ex._tile(h, r0, r1), ex._tile(h, r0, r1, mut)
+        res["out"][r0:r1, h], res["lse"][h, r0:r1], res["dq"][r0:r1, h] = got[0], got[1], got[2]
+        res["dk"][:, h // ex.G] += got[3] - base[3]
+        res["dv"][:, h // ex.G] += got[4] - base[4]
+    return res
+
+
+_A, _B2, _K4 = "sh-r64-causal+70", "sh-w4-both-100", "sh-w4-ksplit4-window"
+
+
+def _shift_mutants():
+    """(id, case, function cfg -> the mutation of tile_fwd_bwd).  The tile holds the sampled rows Sq // 2 - 1 and Sq // 2."""
+    M = []
+    for d in (1, -1):
+        sg = "+1" if d > 0 else "-1"
+        M.append((f"shift{sg}-right-only", _A, lambda c, d=d: dict(vis=dict(d_right=d))))
+        M.append((f"shift{sg}-right-only-of-both", _B2, lambda c, d=d: dict(vis=dict(d_right=d))))
+        M.append((f"shift{sg}-left-only", _B2, lambda c, d=d: dict(vis=dict(d_left=d))))
+        M.append((f"shift{sg}-both", _B2, lambda c, d=d: dict(vis=dict(d_right=d, d_left=d))))
+        M.append((f"shift{sg}-both-causal-window", _K4, lambda c, d=d: dict(vis=dict(d_right=d, d_left=d))))
+    M.append(("shift-on-right-not-on-left", _B2, lambda c: dict(vis=dict(shift_left=0))))
+    M.append(("shift-on-left-not-on-right", _B2, lambda c: dict(vis=dict(shift_right=0))))
+    M.append(("shift-wrong-sign", _A, lambda c: dict(vis=dict(shift_right=-c.shift, shift_left=-c.shift))))
+    M.append(("shift-wrong-sign-both", _B2, lambda c: dict(vis=dict(shift_right=-c.shift, shift_left=-c.shift))))
+
+    def unshifted_t0(c):
+        """k_splits: the first streamed tile taken from the UNSHIFTED left bound -- with a negative shift it lies behind the
+        true one, and the tiles between are never streamed."""
+        q0 = (c.Sq // 2) // QT * QT
+        t_true, _ = NI.key_tiles_of_query_tile(q0, QT, c.Sq, c.Sk, c.causal, c.window, c.shift)
+        t_wrong, _ = NI.key_tiles_of_query_tile(q0, QT, c.Sq, c.Sk, c.causal, c.window, 0)
+        assert t_wrong > t_true
+        return dict(mult=(t_true * 64, t_wrong * 64, 0.0))
+    M.append(("k_splits-run-start-from-the-unshifted-t0", _K4, unshifted_t0))
+    return M
+
+
+SHIFT_MUTANTS = _shift_mutants()
+
+
+@pytest.mark.parametrize("mid", [m[0] for m in SHIFT_MUTANTS])
+def test_every_shift_mutant_fails_on_a_shifted_case(mid):
+    _, cid, fn = next(m for m in SHIFT_MUTANTS if m[0] == mid)
+    c, ex = _shift_case(cid)
+    q0 = (c.Sq // 2) // QT * QT
+    ver = ex.verdicts(_tile_all_heads(ex, q0, min(c.Sq, q0 + QT), fn(c)))
+    for n_ in ALL5:
+        ok, ratio = ver[n_]
+        assert not ok, f"{mid} on {cid}: {n_} passes the suite's check ({ratio:.2f} of its bound)"
+        assert ratio >= MARGIN, f"{mid} on {cid}: {n_} fails by {ratio:.2f}x its bound only (< {MARGIN}x)"
+
+
+@pytest.mark.parametrize("cid", [_A, _B2, _K4])
+def test_unmutated_shifted_attention_agrees_with_the_shifted_reference(cid):
+    c, ex = _shift_case(cid)
+    nd = GN.make_inputs(c)
+    q, k, v, do = (torch.from_numpy(x[:1]) for x in (nd.q, nd.k, nd.v, nd.do))
+    ro, rl = shift_ref.ref_fwd(q, k, v, c.D ** -0.5, c.causal, c.window, c.shift)
+    assert float((ro[0] - ex.out).abs().max()) <= 1e-10 and float(torch.nan_to_num(rl[0] - ex.lse, nan=0.0).abs().max()) <= 1e-10
+    o16 = ro.to(getattr(torch, c.dt))
+    for a_, b_ in zip(shift_ref.ref_bwd(do, q, k, v, o16, rl, c.D ** -0.5, c.causal, c.window, c.shift), (ex.dq, ex.dk, ex.dv)):
+        assert float((a_[0] - b_).abs().max()) <= 1e-10 * max(1.0, float(b_.abs().max()))
+    ver = ex.verdicts(ex.want())
+    assert all(ok and ratio == 0.0 for ok, ratio in ver.values()), ver
 
 
 def table():
