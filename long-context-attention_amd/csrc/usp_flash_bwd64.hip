@@ -17,6 +17,9 @@
 // gradient MFMAs need them, the tile's 8 LDS-DMA pieces (Q / dO tile two iterations ahead of B) through slots 0 .. 15.
 // MFMAs are inline asm (see usp_mfma64.hpp for why and for the hazards hipcc cannot see); tools/mfma_hazards.py checks
 // the emitted stream.
+#ifdef USP_B64_TIMING
+#define USP_TIMING
+#endif
 #include "usp_bwd_params.hpp"
 #include "usp_host.hpp"
 #include "usp_mfma64.hpp"
@@ -42,13 +45,7 @@ constexpr int kB64_E0 = USP_B64_E0;      // first and one-past-last slot of the 
 #endif
 constexpr int kB64_E1 = USP_B64_E1;      // gradient MFMAs of k-step (h, k2) start at 32 + 16 h + 8 k2)
 
-// dev build -DUSP_B64_TIMING: where an iteration's time goes (s_memtime stamps summed per wave, printed for a few waves;
-// profiles/r04_run21..23*.log)
-#ifdef USP_B64_TIMING
-#define USP_TM(...) __VA_ARGS__
-#else
-#define USP_TM(...)
-#endif
+// (dev build -DUSP_B64_TIMING: where an iteration's time goes, summed per wave; profiles/r04_run21..23*.log)
 
 template <int DT, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParams /* read through the kernarg segment */) {
@@ -65,10 +62,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
   constexpr int NKT = D / 16, NDJ = D / 32;
 
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  // The dynamic LDS block is the kernel's only LDS object: it starts at LDS address 0.  Addresses are formed from that
-  // integer, not from the symbol -- hipcc does not fold the symbol's value and spends a v_add (of 0) per address on it.
-  if ((uint32_t)(uintptr_t)(USP_LDS char*)smem_raw != 0u) __builtin_trap();
-  USP_LDS char* smem = (USP_LDS char*)(uintptr_t)0;
+  USP_LDS char* smem = lds_block_at_zero(smem_raw);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -83,30 +77,23 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
   asm volatile("" : "+s"(p));
 
   // ---- lane-constant addresses ----------------------------------------------------------------------------------------
-  // LDS-DMA: a tile (64 rows of Q, 64 rows of dO) is 8 GROUPS of 16 rows, a group 4 pieces of 4 rows (1 KiB, one wave
-  // instruction); one M0 write per group, the pieces by immediate offset (usp_mfma64.hpp).  The slot swizzle of row
-  // 16g + 4i + l/16 is ((l/16) << 2) | i: piece i's per-lane offset is piece 0's with 16*i XORed in.  The groups are dealt
-  // UNEVENLY: a role-A wave (whose stream carries the 64 exponentials and is the longer one) stages one group of Q, a
-  // role-B wave one group of Q and two of dO -- a piece costs its wave about 35 cycles (profiles/r04_run18*).
+  // LDS-DMA: a tile (64 rows of Q, 64 rows of dO) is 8 GROUPS of 16 rows, a group 4 pieces of 4 rows; one M0 write per
+  // group, the pieces by immediate offset, piece i's per-lane offset piece 0's with 16*i XORed in (usp_mfma64.hpp).  The
+  // groups are dealt UNEVENLY: a role-A wave (whose stream carries the 64 exponentials and is the longer one) stages one
+  // group of Q, a role-B wave one group of Q and two of dO -- a piece costs its wave about 35 cycles (profiles/r04_run18*).
   const int dma_row = lane >> 4;                 // (+ 16 * group + 4 * piece rows, through the scalar offset)
-  const int dma_c8 = ((lane & 15) ^ ((lane >> 4) << 2)) * 16;
+  const int dma_c8 = ((lane & 15) ^ ((lane >> 4) << 2)) * 16;    // = dma_lane_col (usp_mfma64.hpp): called, one instruction more
   const int q_voff = dma_row * (int)p->q_ss * 2 + dma_c8, do_voff = dma_row * (int)p->do_ss * 2 + dma_c8;
   // row read (A operand of the S / dP chain): tile row 32h + l31, logical slot 2t + hi; the swizzle does not depend on h
   const int rd_base = l31 * ROWB + ((hi ^ tile_swz<D>(l31)) * 16);            // ^ (32 t), + h * 32 * ROWB
-  // transpose read (A operand of the gradient MFMAs) for dim tile dj, element half e, k-step ks: the 16-lane group reads
-  // the [4 rows][16 dims] block rows 16ks + 8e + 4hi + (0..3), dims 32dj + 16*grp + (0..15); lane i supplies row i>>2,
-  // dims 4*(i&3)..+3
+  // transpose read (A operand of the gradient MFMAs) for dim tile dj, element half e (usp_mfma64.hpp)
   int tr_addr[NDJ][2];
   {
     const int i = lane & 15, grp = (lane >> 4) & 1;
 #pragma unroll
     for (int dj = 0; dj < NDJ; ++dj)
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int rr = 8 * e + 4 * hi + (i >> 2);
-        const int slot = 4 * dj + 2 * grp + ((i & 3) >> 1);
-        tr_addr[dj][e] = rr * ROWB + ((slot ^ tile_swz<D>(rr)) * 16) + (i & 1) * 8;
-      }
+      for (int e = 0; e < 2; ++e) tr_addr[dj][e] = tr_read_offset<D>(i, grp, hi, dj, e);
   }
   USP_LDS char* pex = smem + POFF + slice * 2 * PSLOT + lane * 16;   // + slot*PSLOT + ((2h + kb)*2 + k2)*1024
 
@@ -129,10 +116,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
   const int off = p->causal_off;
   const int ow = own0 + slice * 64;              // first key of this wave
 
-  // K (role A) or V (role B) fragments of this wave's 64 keys, loaded straight into the accumulator file.  The loads are
-  // issued from asm and waited for here: with loads hipcc can see, it still counts them as pending at the headers of the
-  // streaming loops and puts a cascade of s_waitcnt vmcnt(20 .. 0) in front of the fragments' first use in EVERY iteration
-  // -- its vmcnt(0) then waits for the statistics wave's fresh loads, a memory round trip per tile.
+  // K (role A) or V (role B) fragments of this wave's 64 keys, loaded straight into the accumulator file
   u32x4 rf[2][NKT];
   {
     const char* pr[2];
@@ -143,22 +127,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
       pr[kb] = (role == 0 ? p->k + 2 * (b * p->k_sb + (int64_t)orow_c * p->k_ss + hkv * p->k_sh)
                           : p->v + 2 * (b * p->v_sb + (int64_t)orow_c * p->v_ss + hkv * p->v_sh)) + 16 * hi;
     }
-#if defined(__HIP_DEVICE_COMPILE__)
-    // (both key blocks' 16 loads, ONE wait: one memory round trip per item instead of two)
-    asm volatile("global_load_dwordx4 %0, %16, off\n\tglobal_load_dwordx4 %1, %16, off offset:32\n\t"
-                 "global_load_dwordx4 %2, %16, off offset:64\n\tglobal_load_dwordx4 %3, %16, off offset:96\n\t"
-                 "global_load_dwordx4 %4, %16, off offset:128\n\tglobal_load_dwordx4 %5, %16, off offset:160\n\t"
-                 "global_load_dwordx4 %6, %16, off offset:192\n\tglobal_load_dwordx4 %7, %16, off offset:224\n\t"
-                 "global_load_dwordx4 %8, %17, off\n\tglobal_load_dwordx4 %9, %17, off offset:32\n\t"
-                 "global_load_dwordx4 %10, %17, off offset:64\n\tglobal_load_dwordx4 %11, %17, off offset:96\n\t"
-                 "global_load_dwordx4 %12, %17, off offset:128\n\tglobal_load_dwordx4 %13, %17, off offset:160\n\t"
-                 "global_load_dwordx4 %14, %17, off offset:192\n\tglobal_load_dwordx4 %15, %17, off offset:224\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : "=&a"(rf[0][0]), "=&a"(rf[0][1]), "=&a"(rf[0][2]), "=&a"(rf[0][3]), "=&a"(rf[0][4]), "=&a"(rf[0][5]),
-                   "=&a"(rf[0][6]), "=&a"(rf[0][7]), "=&a"(rf[1][0]), "=&a"(rf[1][1]), "=&a"(rf[1][2]), "=&a"(rf[1][3]),
-                   "=&a"(rf[1][4]), "=&a"(rf[1][5]), "=&a"(rf[1][6]), "=&a"(rf[1][7])
-                 : "v"(pr[0]), "v"(pr[1]) : "memory");
-#endif
+    load_resident16(rf[0], rf[1], pr[0], pr[1]);
   }
 
   // The fragments stay as loaded: K times scale * log2(e), rounded to the 16-bit type, carries an error of q_d k_d c 2^-9 per
@@ -174,16 +143,13 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
   const float c2 = p->scale_log2;
   const float neg_inv_scale = -__builtin_amdgcn_rcpf(p->scale);    // (1 ulp: 1e-5 in an exponent of 100)
 
-  int t_begin = 0, t_end = (p->Sq + kTile - 1) / kTile;
-  if (CAUSAL) {
-    const int first_q = own0 - off > 0 ? own0 - off : 0;
-    t_begin = first_q / kTile;
-    if (t_begin > t_end) t_begin = t_end;
-  }
+  // query tiles [t_begin, t_end) hold the rows that see this block's keys; the first n_mask of them need the mask (below)
+  int t_end = (p->Sq + kTile - 1) / kTile;
+  int t_begin = usp_first_row_tile(own0, CAUSAL, off, t_end, kTile);
   if (p->qsplit > 1) {                           // this item's cut of the query tiles [t_begin, t_end): equal runs
-    const int per = (t_end - t_begin + p->qsplit - 1) / p->qsplit;
-    t_begin = t_begin + cut * per < t_end ? t_begin + cut * per : t_end;
-    t_end = t_begin + per < t_end ? t_begin + per : t_end;
+    const int per = (t_end - t_begin + p->qsplit - 1) / p->qsplit;   // = usp_run_length: called, the causal streams change
+    t_begin = usp_run_begin(t_begin, t_end, per, cut);
+    t_end = usp_run_end(t_begin, t_end, per);
   }
   // The item streams the tiles [t_begin, t_end) of `gsub` query heads of its KV group, one head behind the other, into
   // the same accumulators (round 6: the GQA loop inside the workgroup -- K / V fragments and the epilogue
@@ -270,11 +236,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
 #pragma unroll
   for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-    for (int dj = 0; dj < NDJ; ++dj) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[kb][dj][r] = 0.f;
-      pin_agpr(acc[kb][dj]);
-    }
+    for (int dj = 0; dj < NDJ; ++dj) zero_pin_agpr(acc[kb][dj]);
 
   // The streaming loop is instantiated per role, with ROLE a compile-time constant, and the role is chosen by ONE branch
   // around the whole loop: both roles execute the same barrier sequence (n_iter + 1 barriers: role B works one tile
@@ -283,12 +245,8 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64_kernel(const BwdParam
   // So nothing in the loop is conditional: a tile no row of which sees the wave's keys (the first tile of a causal range,
   // for the upper key slice) runs like any other, fully masked -- its P is 0 -- and the diagonal tiles, which are the
   // FIRST n_mask tiles of a causal item, run in a loop instance of their own (MASK) that applies the mask to S.
-  int n_mask = 0;                                  // leading tiles in which some (row, key) pair of this wave is masked
-  if (CAUSAL) {
-    const int lim = ow + 63 - off;                 // tiles with s0 < lim need the mask
-    const int tm = lim > 0 ? (lim + kTile - 1) / kTile : 0;
-    n_mask = tm - t_begin < 0 ? 0 : (tm - t_begin > n_iter ? n_iter : tm - t_begin);
-  }
+  // leading tiles in which some (row, key) pair of this wave is masked
+  const int n_mask = usp_masked_row_tiles(ow, CAUSAL, off, t_begin, n_iter, kTile);
   int tile_cur = t_begin, buf_a = 0, buf_b = NBUF - 1;     // role A's tile / LDS buffers of A's and B's tiles
 USP_TM(
   uint64_t tm_body = 0, tm_drain = 0, tm_bar = 0, tm_last = __builtin_amdgcn_s_memtime();
@@ -576,17 +534,7 @@ USP_TM(
         o32 = p->dk + b * p->dk_sb + (int64_t)orow * p->dk_ss + hkv * p->dk_sh; accf = p->accum_dk;
         if (p->dk16) o16 = p->dk16 + 2 * (b * p->dk16_sb + (int64_t)orow * p->dk16_ss + hkv * p->dk16_sh);
       }
-#pragma unroll
-      for (int dj = 0; dj < NDJ; ++dj)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int d0 = 32 * dj + 8 * g4 + 4 * hi;
-          f32x4 v = {acc[kb][dj][4 * g4] * mul, acc[kb][dj][4 * g4 + 1] * mul, acc[kb][dj][4 * g4 + 2] * mul,
-                     acc[kb][dj][4 * g4 + 3] * mul};
-          if (accf) v += *(const f32x4*)(o32 + d0);
-          if (o16) *(u32x2*)(o16 + 2 * d0) = u32x2{E::pack2(v[0], v[1]), E::pack2(v[2], v[3])};
-          else *(f32x4*)(o32 + d0) = v;
-        }
+      store_row32_acc<E, NDJ>(o32, o16, acc[kb], mul, hi, accf);
     }
   }
 USP_TM(
@@ -605,9 +553,7 @@ bool dkdv64_serves(const BwdParams& p_in) {
   // the pieces' swizzle is XORed into the per-lane byte offset (row part a multiple of 256 bytes); per-lane offsets and the
   // pieces' scalar offsets are 32-bit: 64 rows of Q / dO must span less than 2^31 bytes.  (Base pointer and remaining
   // bytes are 64-bit: no sequence length is refused -- the 8-wave kernel addresses a head by a 32-bit offset and is.)
-  if ((p_in.q_ss * 2) % 256 != 0 || (p_in.do_ss * 2) % 256 != 0 || p_in.q_ss * 128 >= (1LL << 31) || p_in.do_ss * 128 >= (1LL << 31))
-    return false;
-  return true;
+  return dma_rows_ok(p_in.q_ss, true) && dma_rows_ok(p_in.do_ss, true);
 }
 
 bool launch_dkdv64(const BwdParams& p_in, int dtype, bool causal, hipStream_t st, int* rc) {

@@ -21,6 +21,9 @@
 // MFMA: the stream stays under the five issue slots a lone wave hides per MFMA (profiles/r04_ubench_issue.txt), which the
 // 64-MFMA tiles of the forward and of the dK/dV kernel do not.
 // MFMAs are inline asm (usp_mfma64.hpp); tools/mfma_hazards.py checks the emitted stream.
+#ifdef USP_Q64_TIMING
+#define USP_TIMING
+#endif
 #include "usp_bwd_params.hpp"
 #include "usp_host.hpp"
 #include "usp_mfma64.hpp"
@@ -37,13 +40,6 @@ constexpr int kQ64_PF = USP_Q64_PF;     // LDS fragments are read this many frag
 constexpr int kQ64_Y1 = USP_Q64_Y1;    // gaps over which the last element stream (dS of query block 1) is spread, from B5 on
                                // (neither moves the kernel by more than 0.5 %: profiles/r04_run26*.log)
 
-// dev build -DUSP_Q64_TIMING: where an item's time goes (s_memtime stamps, printed for a few waves)
-#ifdef USP_Q64_TIMING
-#define USP_TM(...) __VA_ARGS__
-#else
-#define USP_TM(...)
-#endif
-
 template <int DT, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams /* read through the kernarg segment */) {
   using E = Elem<DT>;
@@ -55,11 +51,8 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
   constexpr int NKT = D / 16, NDJ = D / 32;
   constexpr int PF = kQ64_PF;
 
-  // The dynamic LDS block is the kernel's only LDS object and starts at LDS address 0: addresses are formed from that
-  // integer (hipcc does not fold the symbol's value and spends a v_add of 0 per address on it).
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  if ((uint32_t)(uintptr_t)(USP_LDS char*)smem_raw != 0u) __builtin_trap();
-  USP_LDS char* smem = (USP_LDS char*)(uintptr_t)0;
+  USP_LDS char* smem = lds_block_at_zero(smem_raw);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -71,10 +64,9 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
   KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(p));
 
-  // ---- lane-constant addresses (tile layout, LDS-DMA pieces, row and transposed reads: as in usp_flash_bwd64.hip) ------
-  // a tile is 4 groups of 16 rows, a group 4 pieces of 4 rows; wave w stages group w of the K tile and of the V tile
-  const int dma_row = lane >> 4;
-  const int dma_c8 = ((lane & 15) ^ ((lane >> 4) << 2)) * 16;
+  // ---- lane-constant addresses (tile layout, LDS-DMA pieces, row and transposed reads: usp_mfma64.hpp) -----------------
+  // a tile is 4 groups of 16 rows; wave w stages group w of the K tile and of the V tile
+  const int dma_row = lane >> 4, dma_c8 = dma_lane_col(lane & 15, dma_row);
   const int k_voff = dma_row * (int)p->k_ss * 2 + dma_c8, v_voff = dma_row * (int)p->v_ss * 2 + dma_c8;
   const int rd_base = l31 * ROWB + ((hi ^ tile_swz<D>(l31)) * 16);            // ^ (32 kt), + 32 kb rows
   int tr_addr[NDJ][2];
@@ -83,11 +75,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
 #pragma unroll
     for (int dj = 0; dj < NDJ; ++dj)
 #pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int rr = 8 * e + 4 * hi + (i >> 2);
-        const int slot = 4 * dj + 2 * grp + ((i & 3) >> 1);
-        tr_addr[dj][e] = rr * ROWB + ((slot ^ tile_swz<D>(rr)) * 16) + (i & 1) * 8;
-      }
+      for (int e = 0; e < 2; ++e) tr_addr[dj][e] = tr_read_offset<D>(i, grp, hi, dj, e);
   }
   const float c = p->scale_log2;
 
@@ -110,60 +98,26 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
   const int qw = q0 + wave * 64;                          // first row of this wave
   const int off = p->causal_off;
 
-  // ---- key range ---------------------------------------------------------------------------------------------------------
-  int blk_kv_end = p->Sk, wave_kv_end = p->Sk;
-  if (CAUSAL) {
-    const int blk_last = (q0 + kBM < p->Sq ? q0 + kBM : p->Sq) - 1;
-    const int wav_last = (qw + 64 < p->Sq ? qw + 64 : p->Sq) - 1;
-    blk_kv_end = blk_last + off + 1 < p->Sk ? blk_last + off + 1 : p->Sk;
-    wave_kv_end = wav_last + off + 1 < p->Sk ? wav_last + off + 1 : p->Sk;
-  }
-  if (qw >= p->Sq) wave_kv_end = 0;
-  const int nt = blk_kv_end > 0 ? (blk_kv_end + kTile - 1) / kTile : 0;    // tiles the workgroup streams
-  int n_full = p->Sk / kTile;                                               // leading tiles that need no mask for this wave
-  if (CAUSAL) {
-    const int lim = qw + off + 1;                          // keys < lim are visible to EVERY row of the wave
-    const int nf = lim > 0 ? lim / kTile : 0;
-    n_full = nf < n_full ? nf : n_full;
-  }
-  const int n_w = wave_kv_end > 0 ? (wave_kv_end + kTile - 1) / kTile : 0;  // tiles this wave works on
-  if (n_full > n_w) n_full = n_w;
+  // ---- key range (usp_tile_range.h): the workgroup streams nt tiles, this wave works on n_w, the first n_full need no mask
+  const usp_query_tiles kr = usp_query_tiles_of(q0, kBM, qw, 64, p->Sq, p->Sk, CAUSAL, off, kTile);
+  const int nt = kr.nt, n_w = kr.n_w, n_full = kr.n_full;
   // key cut: the workgroup streams tiles [tb, te) of its [0, nt) -- equal runs, as the 8-wave kernel cuts them
-  int tb = 0, te = nt;
-  if (p->ksplit > 1) {
-    const int per = (nt + p->ksplit - 1) / p->ksplit;
-    tb = cut * per < nt ? cut * per : nt;
-    te = tb + per < nt ? tb + per : nt;
-  }
-  const int e_full = n_full < tb ? tb : (n_full > te ? te : n_full);        // [tb, e_full) plain, [e_full, e_own) masked,
-  const int e_own = n_w < tb ? tb : (n_w > te ? te : n_w);                  // [e_own, te) other waves' tiles
+  usp_tile_run run = {0, nt};
+  if (p->ksplit > 1) run = usp_equal_run(0, nt, p->ksplit, cut);
+  const int tb = run.begin, te = run.end;
+  const int e_full = usp_clamp_to_run(n_full, tb, te);                      // [tb, e_full) plain, [e_full, e_own) masked,
+  const int e_own = usp_clamp_to_run(n_w, tb, te);                          // [e_own, te) other waves' tiles
 
-  // ---- resident B operands: Q and dO fragments of the wave's 64 rows, loaded straight into the accumulator file (asm
-  // loads + wait: usp_flash_bwd64.hip explains why hipcc must not see them) ------------------------------------------------
+  // ---- resident B operands: Q and dO fragments of the wave's 64 rows, loaded straight into the accumulator file ------------
   u32x4 qf[2][NKT], df[2][NKT];
   float nl[2], dl[2];                            // -lse * log2(e) (-inf: the row sees no key -> P = 0) and delta per lane
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) {
     const int row = qw + 32 * qb + l31;
     const int row_c = row < p->Sq ? row : p->Sq - 1;
-    [[maybe_unused]] const char* qp = p->q + 2 * (b * p->q_sb + (int64_t)row_c * p->q_ss + h * p->q_sh) + 16 * hi;
-    [[maybe_unused]] const char* dp = p->dout + 2 * (b * p->do_sb + (int64_t)row_c * p->do_ss + h * p->do_sh) + 16 * hi;
-#if defined(__HIP_DEVICE_COMPILE__)
-    // (16 loads, ONE wait: the four groups of an item cost two memory round trips, not four)
-    asm volatile("global_load_dwordx4 %0, %16, off\n\tglobal_load_dwordx4 %1, %16, off offset:32\n\t"
-                 "global_load_dwordx4 %2, %16, off offset:64\n\tglobal_load_dwordx4 %3, %16, off offset:96\n\t"
-                 "global_load_dwordx4 %4, %16, off offset:128\n\tglobal_load_dwordx4 %5, %16, off offset:160\n\t"
-                 "global_load_dwordx4 %6, %16, off offset:192\n\tglobal_load_dwordx4 %7, %16, off offset:224\n\t"
-                 "global_load_dwordx4 %8, %17, off\n\tglobal_load_dwordx4 %9, %17, off offset:32\n\t"
-                 "global_load_dwordx4 %10, %17, off offset:64\n\tglobal_load_dwordx4 %11, %17, off offset:96\n\t"
-                 "global_load_dwordx4 %12, %17, off offset:128\n\tglobal_load_dwordx4 %13, %17, off offset:160\n\t"
-                 "global_load_dwordx4 %14, %17, off offset:192\n\tglobal_load_dwordx4 %15, %17, off offset:224\n\t"
-                 "s_waitcnt vmcnt(0)"
-                 : "=&a"(qf[qb][0]), "=&a"(qf[qb][1]), "=&a"(qf[qb][2]), "=&a"(qf[qb][3]), "=&a"(qf[qb][4]), "=&a"(qf[qb][5]),
-                   "=&a"(qf[qb][6]), "=&a"(qf[qb][7]), "=&a"(df[qb][0]), "=&a"(df[qb][1]), "=&a"(df[qb][2]), "=&a"(df[qb][3]),
-                   "=&a"(df[qb][4]), "=&a"(df[qb][5]), "=&a"(df[qb][6]), "=&a"(df[qb][7])
-                 : "v"(qp), "v"(dp) : "memory");
-#endif
+    const char* qp = p->q + 2 * (b * p->q_sb + (int64_t)row_c * p->q_ss + h * p->q_sh) + 16 * hi;
+    const char* dp = p->dout + 2 * (b * p->do_sb + (int64_t)row_c * p->do_ss + h * p->do_sh) + 16 * hi;
+    load_resident16(qf[qb], df[qb], qp, dp);     // (per query block: the four groups of an item cost two round trips, not four)
     const float lse = p->lse[b * p->lse_sb + h * p->lse_sh + row_c];
     const float dlt = p->delta[b * p->dl_sb + h * p->dl_sh + row_c];
     const bool live = row < p->Sq && lse != USP_NEG_INF;
@@ -200,11 +154,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
-    for (int dj = 0; dj < NDJ; ++dj) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dq[qb][dj][r] = 0.f;
-      pin_agpr(dq[qb][dj]);
-    }
+    for (int dj = 0; dj < NDJ; ++dj) zero_pin_agpr(dq[qb][dj]);
 
   dma_open(tb & 1);                              // (iteration t reads buffer t & 1)
 #pragma unroll
@@ -372,18 +322,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
         h1 = nullptr;
         acc_f = 0;
       }
-      const float sc = p->scale;
-#pragma unroll
-      for (int dj = 0; dj < NDJ; ++dj)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int d0 = 32 * dj + 8 * g4 + 4 * hi;
-          f32x4 v1 = {dq[qb][dj][4 * g4] * sc, dq[qb][dj][4 * g4 + 1] * sc, dq[qb][dj][4 * g4 + 2] * sc,
-                      dq[qb][dj][4 * g4 + 3] * sc};
-          if (acc_f) v1 += *(const f32x4*)(o1 + d0);
-          if (h1) *(u32x2*)(h1 + 2 * d0) = u32x2{E::pack2(v1[0], v1[1]), E::pack2(v1[2], v1[3])};
-          else *(f32x4*)(o1 + d0) = v1;
-        }
+      store_row32_acc<E, NDJ>(o1, h1, dq[qb], p->scale, hi, acc_f);
     }
   }
   __syncthreads();          // the next item's prologue refills the tile buffers
@@ -401,9 +340,7 @@ bool dq64_serves(const BwdParams& p_in) {
   // dense launches (bf16 / fp16) without a window or the dynamic item queue; the pieces' swizzle is XORed into the per-lane byte
   // offset (rows a multiple of 256 bytes apart), 64 rows of K / V span less than 2^31 bytes
   if (p_in.seq_q || p_in.seq_k || p_in.sched || p_in.win_on) return false;
-  if ((p_in.k_ss * 2) % 256 != 0 || (p_in.v_ss * 2) % 256 != 0 || p_in.k_ss * 128 >= (1LL << 31) || p_in.v_ss * 128 >= (1LL << 31))
-    return false;
-  return true;
+  return dma_rows_ok(p_in.k_ss, true) && dma_rows_ok(p_in.v_ss, true);
 }
 
 bool launch_dq64(const BwdParams& p_in, int dtype, bool causal, hipStream_t st, int* rc) {

@@ -19,6 +19,9 @@
 // so the hazards are met by construction: a chain's result is read at least 16 MFMA slots after its last MFMA in the
 // pipelined loop, and behind an explicit s_nop in the unpipelined paths; operands written by VALU (packed P) are
 // complete at least one MFMA slot before the MFMA that reads them.
+#ifdef USP_F64_TIMING
+#define USP_TIMING
+#endif
 #include "usp_fwd_params.hpp"
 #include "usp_host.hpp"
 #include "usp_mfma64.hpp"
@@ -57,12 +60,7 @@ constexpr int kF64_DMA0 = USP_F64_DMA0;    // slot (0..63 over both phases) behi
 #endif
 constexpr int kF64_DMAS = USP_F64_DMAS;    // goes out, and the distance to the next one
 
-// dev build -DUSP_F64_TIMING: where an item's time goes (s_memtime stamps, printed for a few waves; profiles/r04_run28*.log)
-#ifdef USP_F64_TIMING
-#define USP_TM(...) __VA_ARGS__
-#else
-#define USP_TM(...)
-#endif
+// (dev build -DUSP_F64_TIMING: where an item's time goes; profiles/r04_run28*.log)
 
 // SPLIT: the K-split form (usp_fwd_args.k_splits > 1) is its own instantiation with its own argument block (FwdParams +
 // FwdSplit), as in usp_flash_fwd.hip: the plain kernels keep the machine code they were profiled with.  A work item is then
@@ -144,20 +142,20 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(const FwdArgsT<SPLI
   int kb = 0, sk_cut = 0;
   if constexpr (SPLIT) {
     int e = p->Sk;                                        // keys any row of the 256-row tile sees
-    if (CAUSAL) {
-      const int lim = (q0 + kBM < p->Sq ? q0 + kBM : p->Sq) + off;
-      e = lim < e ? lim : e;
-    }
-    const int nt_all = e > 0 ? (e + kBN - 1) / kBN : 0;
-    kb = (ks * nt_all / p->ksplit) * kBN;
-    int ke = (ks == p->ksplit - 1) ? p->Sk : ((ks + 1) * nt_all / p->ksplit) * kBN;
+    if (CAUSAL) e = usp_rows_key_end(q0, kBM, p->Sq, e, 1, off);
+    const int nt_all = usp_tiles_holding(e, kBN);
+    // = usp_prop_cut_keys (usp_tile_range.h), which as ONE call changes this kernel by up to 63 instructions
+    kb = usp_prop_cut_tile(nt_all, p->ksplit, ks) * kBN;
+    int ke = (ks == p->ksplit - 1) ? p->Sk : usp_prop_cut_tile(nt_all, p->ksplit, ks + 1) * kBN;
     ke = ke < p->Sk ? ke : p->Sk;
     sk_cut = ke > kb ? ke - kb : 0;
     off -= kb;
   }
   auto n_keys = [&]() { if constexpr (SPLIT) return sk_cut; else return p->Sk; };
 
-  // ---- KV range -------------------------------------------------------------------------------------------------------
+  // ---- KV range (usp_tile_range.h, in pieces: as the one call usp_query_tiles_of, n_w moves to the top and the stream
+  // changes by up to 43 instructions -- the number and place of the n_keys() / p->Sq reads is part of this kernel's code) -----
+  // (blk_kv_end / wave_kv_end mirror usp_rows_key_end: called here, the causal kernels' streams change)
   int blk_kv_end = n_keys(), wave_kv_end = n_keys();
   if (CAUSAL) {
     const int blk_last = (q0 + kBM < p->Sq ? q0 + kBM : p->Sq) - 1;
@@ -166,13 +164,8 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(const FwdArgsT<SPLI
     wave_kv_end = wav_last + off + 1 < n_keys() ? wav_last + off + 1 : n_keys();
   }
   if (qw >= p->Sq) wave_kv_end = 0;
-  const int nt = blk_kv_end > 0 ? (blk_kv_end + kBN - 1) / kBN : 0;
-  int n_full = n_keys() / kBN;                              // leading tiles that need no mask for this wave
-  if (CAUSAL) {
-    const int lim = qw + off + 1;                          // keys < lim are visible to EVERY row of the wave
-    const int nf = lim > 0 ? lim / kBN : 0;
-    n_full = nf < n_full ? nf : n_full;
-  }
+  const int nt = usp_tiles_holding(blk_kv_end, kBN);
+  int n_full = usp_unmasked_tiles(qw, n_keys(), CAUSAL, off, kBN);    // leading tiles that need no mask for this wave
   if (n_full > nt) n_full = nt;
 
 USP_TM(
@@ -244,11 +237,7 @@ USP_TM(
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
-    for (int dj = 0; dj < NDJ; ++dj) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[qb][dj][r] = 0.f;
-      pin_agpr(o[qb][dj]);
-    }
+    for (int dj = 0; dj < NDJ; ++dj) zero_pin_agpr(o[qb][dj]);
   float m_run[2] = {USP_NEG_INF, USP_NEG_INF};   // running row max, raw score units
   float l_run[2] = {0.f, 0.f};                   // this lane's share of the row sum
 
@@ -471,7 +460,7 @@ USP_TM(
   };
 
   // this wave's tiles: [0, n_w); [0, n_full) need no mask.  Iteration jj is plain while jj + 1 < n_full.
-  const int n_w = wave_kv_end > 0 ? (wave_kv_end + kBN - 1) / kBN : 0;
+  const int n_w = usp_tiles_holding(wave_kv_end, kBN);
   if (n_full > n_w) n_full = n_w;
   int j = 0;
 USP_TM(
@@ -627,7 +616,7 @@ bool launch_fwd64(const FwdArgsT<true>& p_in, int dtype, bool causal, hipStream_
   // v_step are sums, nothing is XORed into them (unlike launch_dq64, whose V pieces are swizzled) -- a V with
   // stride_s % 128 != 0 beside a K with stride_s % 128 == 0 is served bit-identically to the contiguous launch:
   // tests/test_gpu_layouts.py::test_row64_stride_conditions_forward
-  if ((p_in.k_ss * 2) % 256 != 0 || p_in.k_ss * 128 >= (1LL << 31) || p_in.v_ss * 128 >= (1LL << 31)) return false;
+  if (!dma_rows_ok(p_in.k_ss, true) || !dma_rows_ok(p_in.v_ss, false)) return false;
   if (p_in.win_on || p_in.seq_q) return false;
   if (p_in.ksplit > 1) {
     FwdArgsT<true> p = p_in;

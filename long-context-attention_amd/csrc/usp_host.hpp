@@ -47,6 +47,13 @@ inline bool tensor_aligned(const usp_tensor& t, int bytes, int elems) {
   return tensor_aligned(t.ptr, t.stride_b, t.stride_s, t.stride_h, bytes, elems);
 }
 
+// ---- what the 64-row kernels' LDS-DMA asks of a streamed tensor's row stride (`stride_s`, in 16-bit elements): per-lane
+// offsets and the pieces' scalar offsets are 32-bit, so 64 rows span less than 2^31 bytes; where the pieces' slot swizzle is
+// XORed into the per-lane byte offset (`swizzled`), the row pitch is a multiple of 256 bytes ----
+inline bool dma_rows_ok(int64_t stride_s, bool swizzled) {
+  return stride_s * 128 < (1LL << 31) && (!swizzled || (stride_s * 2) % 256 == 0);
+}
+
 // ---- run-time (dtype, causal, head dim) -> template arguments: f receives std::integral_constants ----
 template <int V> using Int = std::integral_constant<int, V>;
 template <class F> auto with_dtype(int dtype, F&& f) { return dtype == USP_BF16 ? f(Int<0>{}) : f(Int<1>{}); }

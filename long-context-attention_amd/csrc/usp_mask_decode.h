@@ -21,7 +21,9 @@
  *   dQ (usp_flash_bwd_dq_body.inc, usp_flash_bwd_dq64.hip):  last + off + 1,  own0 + win_lo,  ow + off,  ow + 31 + win_lo,
  *     orow + win_lo,  orow + off;
  *   dK/dV (usp_flash_bwd_dkdv_body.inc, usp_flash_bwd64.hip):  own0 - off,  own0 + 127 - win_lo,  s0 + off,  ow + 31 - win_lo,
- *     ow - win_lo,  orow - win_lo - s0 - 4 hi,  orow - off.
+ *     ow - win_lo,  orow - win_lo - s0 - 4 hi,  orow - off;
+ *   the tile ranges of the 64-row kernels (usp_tile_range.h, swept on the host like this header):  last + off + 1,
+ *     r0 + off + 1,  own0 - off,  ow + 63 - off.
  * (Before this header the host formed Sk - Sq - window_left and += mask_shift in `int`: window_left = INT_MAX with Sq > Sk
  * or a negative shift overflowed, the dK/dV kernel's `last` wrapped negative and it streamed no row.) */
 #ifndef USP_MASK_DECODE_H

@@ -1,10 +1,29 @@
-// One-wave-per-SIMD building blocks shared by usp_flash_fwd64.hip and usp_flash_bwd64.hip: inline-asm MFMA forms that let
-// ONE kernel keep accumulators and resident operands in the accumulator half of the register file (AGPRs) while the score
-// tiles live in arch VGPRs, the wait-state guards hipcc cannot place around asm MFMAs, and LDS-DMA issued from asm.
+// One-wave-per-SIMD building blocks shared by usp_flash_fwd64.hip, usp_flash_bwd64.hip and usp_flash_bwd_dq64.hip: inline-asm
+// MFMA forms that let ONE kernel keep accumulators and resident operands in the accumulator half of the register file (AGPRs)
+// while the score tiles live in arch VGPRs, the wait-state guards hipcc cannot place around asm MFMAs, LDS-DMA issued from
+// asm, the lane-constant offsets of the tile layout and the row epilogues.  The tile RANGES of an item are plain C, checked on
+// the host: usp_tile_range.h.
 #pragma once
 #include "usp_common.hpp"
+#define USP_RANGE_FN __device__ __forceinline__
+#include "usp_tile_range.h"
+
+// dev builds: where an item's time goes (s_memtime stamps, printed for a few waves).  One -D per kernel -- USP_F64_TIMING,
+// USP_B64_TIMING, USP_Q64_TIMING -- which that kernel's file turns into USP_TIMING in front of this header.
+#ifdef USP_TIMING
+#define USP_TM(...) __VA_ARGS__
+#else
+#define USP_TM(...)
+#endif
 
 namespace usp {
+
+// The dynamic LDS block is a kernel's only LDS object and starts at LDS address 0: addresses are formed from that integer,
+// not from the symbol -- hipcc does not fold the symbol's value and spends a v_add (of 0) per address on it.
+USP_DEV USP_LDS char* lds_block_at_zero(char* smem_raw) {
+  if ((uint32_t)(uintptr_t)(USP_LDS char*)smem_raw != 0u) __builtin_trap();
+  return (USP_LDS char*)(uintptr_t)0;
+}
 
 // ---- asm MFMA forms ---------------------------------------------------------------------------------------------------
 template <int DT> struct M64;
@@ -46,6 +65,35 @@ USP_DEV void pin_agpr4(u32x4& x) {
   asm volatile("" : "+a"(x));
 #endif
 }
+// an accumulator of an item: zero, and at home in the accumulator file.  (No loops in these small pieces: a helper that walks
+// the [2][NDJ] accumulators itself is unrolled at another point of the pipeline than the kernel's own loop, and the machine
+// code of the 64-row kernels comes out different -- tools/kernel_isa.py.)
+USP_DEV void zero_pin_agpr(f32x16& o) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[r] = 0.f;
+  pin_agpr(o);
+}
+// Resident fragments (the B operands of an item's score chains: 2 x 8 k-steps of the rows at `r0` / `r1`, 16 bytes per lane and
+// k-step) loaded straight into the accumulator file.  The loads are issued from asm and waited for here: with loads hipcc can
+// see, it still counts them as pending at the headers of the streaming loops and puts a cascade of s_waitcnt vmcnt(20 .. 0)
+// in front of the fragments' first use in EVERY iteration -- its vmcnt(0) then waits for the statistics wave's fresh loads, a
+// memory round trip per tile.  16 loads, ONE wait: one memory round trip for both row blocks instead of two.
+USP_DEV void load_resident16(u32x4 (&f0)[8], u32x4 (&f1)[8], const char* r0, const char* r1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("global_load_dwordx4 %0, %16, off\n\tglobal_load_dwordx4 %1, %16, off offset:32\n\t"
+               "global_load_dwordx4 %2, %16, off offset:64\n\tglobal_load_dwordx4 %3, %16, off offset:96\n\t"
+               "global_load_dwordx4 %4, %16, off offset:128\n\tglobal_load_dwordx4 %5, %16, off offset:160\n\t"
+               "global_load_dwordx4 %6, %16, off offset:192\n\tglobal_load_dwordx4 %7, %16, off offset:224\n\t"
+               "global_load_dwordx4 %8, %17, off\n\tglobal_load_dwordx4 %9, %17, off offset:32\n\t"
+               "global_load_dwordx4 %10, %17, off offset:64\n\tglobal_load_dwordx4 %11, %17, off offset:96\n\t"
+               "global_load_dwordx4 %12, %17, off offset:128\n\tglobal_load_dwordx4 %13, %17, off offset:160\n\t"
+               "global_load_dwordx4 %14, %17, off offset:192\n\tglobal_load_dwordx4 %15, %17, off offset:224\n\t"
+               "s_waitcnt vmcnt(0)"
+               : "=&a"(f0[0]), "=&a"(f0[1]), "=&a"(f0[2]), "=&a"(f0[3]), "=&a"(f0[4]), "=&a"(f0[5]), "=&a"(f0[6]), "=&a"(f0[7]),
+                 "=&a"(f1[0]), "=&a"(f1[1]), "=&a"(f1[2]), "=&a"(f1[3]), "=&a"(f1[4]), "=&a"(f1[5]), "=&a"(f1[6]), "=&a"(f1[7])
+               : "v"(r0), "v"(r1) : "memory");
+#endif
+}
 // `n` wait states that hipcc cannot move the readers of the accumulators across (it does not know that the asm
 // statements in front of it are MFMAs: "XDL write -> VALU / v_accvgpr read" needs 12 states for an 8-pass MFMA).
 USP_DEV void mfma_settle(f32x16 (&o)[2][4]) {
@@ -60,6 +108,22 @@ USP_DEV void mfma_settle(f32x16 (&s)[2][2]) {
 USP_DEV void mfma_settle(f32x16 (&s)[2]) { asm volatile("s_nop 15" : "+v"(s[0]), "+v"(s[1])); }
 // VALU write (v_cvt_pk / v_accvgpr_write) -> MFMA operand read: 2 wait states, which hipcc does not pad in front of asm
 USP_DEV void operand_settle() { asm volatile("s_nop 3" ::: "memory"); }
+
+// ---- lane-constant offsets of a streamed tile (64 rows of D 16-bit values, 16-byte slots swizzled by tile_swz) -----------
+// LDS-DMA: a tile is groups of 16 rows, a group 4 pieces of 4 rows (1 KiB, one wave instruction).  Lane l of piece i fetches
+// row 4i + l/16 of the group, whose slot swizzle is ((l/16) << 2) | i: piece i's per-lane byte offset is piece 0's -- row
+// l >> 4, column dma_lane_col(l & 15, that row) -- with 16 i XORed in (and 4 i rows, through the scalar offset).
+USP_DEV int dma_lane_col(int l15, int row) { return (l15 ^ (row << 2)) * 16; }
+// Transposed read (ds_read_b64_tr_b16: A operand of the gradient MFMAs) for dim tile dj, element half e, k-step ks: the
+// 16-lane group reads the [4 rows][16 dims] block rows 16 ks + 8 e + 4 hi + (0..3), dims 32 dj + 16 grp + (0..15); lane i
+// supplies row i >> 2, dims 4 (i & 3) .. + 3.  Returns the byte offset inside k-step 0.  i = lane & 15, grp = (lane >> 4) & 1,
+// hi = lane >> 5 are passed, not derived here (from `lane` alone it costs one to three instructions more).
+template <int D> USP_DEV int tile_swz(int row);       // (usp_bwd_params.hpp: the backward kernels' tile layout)
+template <int D> USP_DEV int tr_read_offset(int i, int grp, int hi, int dj, int e) {
+  const int rr = 8 * e + 4 * hi + (i >> 2);
+  const int slot = 4 * dj + 2 * grp + ((i & 3) >> 1);
+  return rr * (D * 2) + ((slot ^ tile_swz<D>(rr)) * 16) + (i & 1) * 8;
+}
 
 // LDS-DMA from inline asm (buffer_load_dwordx4 ... lds: 64 x 16 bytes at rsrc.base + soffset + voffset land linearly at
 // the wave-uniform LDS address M0).  hipcc does not see these loads: it puts no s_waitcnt vmcnt(0) in front of the first
@@ -129,6 +193,21 @@ USP_DEV void store_row16_wide(char* row, const f32x16 (&t)[NDJ], float mul, int 
       if (valid) *(u32x4*)(row + 2 * (32 * dj + 16 * g2 + 8 * hi)) = u32x4{sx[0], sy[0], sx[1], sy[1]};
     }
 #endif
+}
+// Its sibling for everything else: row * mul goes out in fp32 (`o16` null), added to what `o32` holds (`accf`), or -- the sum
+// rounded once -- in 16 bits to `o16`, in 4-dim pieces.  Only lanes with a valid row call it.
+template <class E, int NDJ>
+USP_DEV void store_row32_acc(float* o32, char* o16, const f32x16 (&t)[NDJ], float mul, int hi, int accf) {
+#pragma unroll
+  for (int dj = 0; dj < NDJ; ++dj)
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const int d0 = 32 * dj + 8 * g4 + 4 * hi;
+      f32x4 v = {t[dj][4 * g4] * mul, t[dj][4 * g4 + 1] * mul, t[dj][4 * g4 + 2] * mul, t[dj][4 * g4 + 3] * mul};
+      if (accf) v += *(const f32x4*)(o32 + d0);
+      if (o16) *(u32x2*)(o16 + 2 * d0) = u32x2{E::pack2(v[0], v[1]), E::pack2(v[2], v[3])};
+      else *(f32x4*)(o32 + d0) = v;
+    }
 }
 
 }  // namespace usp
