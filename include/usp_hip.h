@@ -97,7 +97,8 @@ enum {
  * `window_size` to every block, yunchang/ring/ring_flash_attn.py:36-48, which is a different function).  Any value with
  * |mask_shift| < 2^30 is served (USP_EINVAL beyond): rows, or a whole launch, that see no key give out = 0, lse = -inf and
  * zero gradients, as an empty row does without the bit.  A shift with neither `causal` nor a window bounds nothing and is
- * ignored.  Dense launches only: a packed batch with the bit is USP_EUNSUPPORTED.  The 64-row family serves a shifted launch
+ * ignored by the mask; with ALiBi (usp_flash_fwd_alibi / usp_flash_bwd_alibi) it still moves the bias, whose distances are
+ * measured from the same diagonal.  Dense launches only: a packed batch with the bit is USP_EUNSUPPORTED.  The 64-row family serves a shifted launch
  * exactly where it serves the same launch unshifted (no left window bound).
  * Served range: window_left and window_right may be ANY int32 (INT32_MAX as "unbounded" included), with or without a shift;
  * the bounds are formed in 64 bits (csrc/usp_mask_decode.h).  A bound that cuts no (row, key) pair of the launch at this
@@ -107,6 +108,10 @@ enum {
  * built before it never sets the bit, and the field lies in what was padding (behind softmax_scale), so such a binding's struct
  * has the same size and offsets and is never read past; usp_attn_features() reports the bit. */
 #define USP_ATTN_SHIFT 128
+/* USP_ATTN_ALIBI: a FEATURE bit, reported by usp_attn_features() and not read from args->flags: the library exports
+ * usp_flash_fwd_alibi / usp_flash_bwd_alibi (below), which take flash-attn's `alibi_slopes` beside the unchanged argument
+ * blocks (ABI still v7: no struct, field or version changed). */
+#define USP_ATTN_ALIBI 256
 
 typedef struct usp_tensor {
   void* ptr;
@@ -258,6 +263,27 @@ typedef struct usp_bwd_args {
 
 int usp_flash_bwd(const usp_bwd_args* args, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * ALiBi: usp_flash_fwd / usp_flash_bwd with flash-attn's `alibi_slopes` (forwarded by the reference to every block call,
+ * yunchang/kernels/attention.py:165-250).  For query head h of batch b with slope m = alibi_slopes[b * alibi_stride_b + h]
+ * (DEVICE fp32, h < Hq; alibi_stride_b = 0: one (Hq,) vector for the whole batch):
+ *     S[i, j] = softmax_scale * q_i . k_j  -  m * | i + (Sk - Sq + shift) - j |       shift = mask_shift with USP_ATTN_SHIFT, else 0
+ * and the causal / window / ragged mask is applied after.  At shift = 0 this is flash-attn's definition; with the shift of a ring
+ * block the distances are those of GLOBAL positions (the reference hands the same slopes to every block and so measures them
+ * inside each block: a different function).  `lse` is the true logsumexp of these biased scores (flash-attn's causal shortcut
+ * adds m * j instead, which moves its LSE per row; the ring merges by LSE, so that is not copied).  Backward: P = exp(S - lse);
+ * dS, dQ, dK, dV as without the bias, which is additive and has no gradient path to q, k or v.  The slopes get no gradient.
+ * alibi_slopes == NULL is exactly usp_flash_fwd / usp_flash_bwd: the same kernels, bit-identical results.  Everything else is as
+ * the argument block says (k_splits, dq_splits, dkdv_splits, dkdv_heads and the workspace functions, merge_in and the final
+ * rows, USP_LAUNCH_INTERLEAVE, USP_ATTN_WINDOW, USP_ATTN_SHIFT, USP_BWD_SKIP_*).  With non-NULL slopes:
+ *   - a negative alibi_stride_b is USP_EINVAL;
+ *   - USP_ATTN_SOFTCAP, a packed batch (seq_q / seq_k) and USP_FORCE_ROW64 are USP_EUNSUPPORTED, nothing launched or written;
+ *   - every head dim runs on the two-waves-per-SIMD family (ALiBi instantiations of its kernels; unforced D = 128 included, as
+ *     for softcap); usp_last_launch_kinds() reports the wave8 / wave4 / split-merge / reduce bits that were launched.
+ * -------------------------------------------------------------------------------------------- */
+int usp_flash_fwd_alibi(const usp_fwd_args* args, const float* alibi_slopes, int64_t alibi_stride_b, void* stream);
+int usp_flash_bwd_alibi(const usp_bwd_args* args, const float* alibi_slopes, int64_t alibi_stride_b, void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -357,7 +383,8 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
                    float* sink, uint64_t* clocks, void* stream);
 
 int usp_abi_version(void);
-/* The USP_ATTN_* flag bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT).  Unknown flag bits are not rejected by
+/* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI, the last one a
+ * feature bit: the two *_alibi entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

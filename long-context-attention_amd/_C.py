@@ -27,6 +27,7 @@ USP_BWD_SKIP_DQ = 16           # usp_flash_bwd: only the dK/dV launch ...
 USP_BWD_SKIP_DKDV = 32         # ... only the dQ launch
 USP_ATTN_SOFTCAP = 64          # the softcap field is valid: scores are capped to softcap * tanh(S / softcap)
 USP_ATTN_SHIFT = 128           # the mask_shift field is valid: (Sk - Sq) + mask_shift places the diagonal of every mask bound
+USP_ATTN_ALIBI = 256           # feature bit of usp_attn_features(): usp_flash_fwd_alibi / usp_flash_bwd_alibi exist (not an args flag)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -107,7 +108,10 @@ class UspBwdArgs(ctypes.Structure):
 
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
-           "usp_attn_features")
+           "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
+# The two *_alibi entry points are the only exports load() does not insist on: they are looked up and prototyped on first use
+# (_alibi_entry), behind the feature bit, so a library built before them still loads and serves everything else.
+ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
 
 
 def lib_path() -> str:
@@ -126,7 +130,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if not hasattr(L, name):
+        if name not in ALIBI_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -328,6 +332,39 @@ def _set_softcap(a, cap: Optional[float]):
     a.softcap = cap
 
 
+def alibi_value(alibi_slopes, B: int, Hq: int, device):
+    """flash-attn's `alibi_slopes` -> (contiguous fp32 device tensor, batch stride in elements) as usp_flash_fwd_alibi takes
+    them, or None when it is off.  Shape (Hq,) (stride 0: one vector for the whole batch) or (B, Hq); any other shape, a dtype
+    other than float32 (flash-attn requires fp32 too) or a tensor on another device raises ValueError.  (Pure argument check:
+    the CPU orchestration tests call it without a library.)"""
+    if alibi_slopes is None:
+        return None
+    if not isinstance(alibi_slopes, torch.Tensor):
+        raise ValueError(f"alibi_slopes must be a torch.Tensor, got {type(alibi_slopes).__name__}")
+    if alibi_slopes.dtype != torch.float32:
+        raise ValueError(f"alibi_slopes must be float32, got {alibi_slopes.dtype}")
+    if tuple(alibi_slopes.shape) not in ((Hq,), (B, Hq)):
+        raise ValueError(f"alibi_slopes must have shape ({Hq},) or ({B}, {Hq}), got {tuple(alibi_slopes.shape)}")
+    if alibi_slopes.device != torch.device(device):
+        raise ValueError(f"alibi_slopes is on {alibi_slopes.device}, the operands on {device}")
+    t = alibi_slopes.contiguous()
+    return t, (Hq if t.dim() == 2 else 0)
+
+
+def _alibi_entry(name: str):
+    """The *_alibi entry point `name` (one of ALIBI_EXPORTS), prototyped on first use; a library without the feature bit
+    (built before the entry points: it loads, they are not in EXPORTS) is refused."""
+    L = load()
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_ALIBI and hasattr(L, name)):
+        raise NotImplementedError(f"{_LIB_PATH} does not serve alibi_slopes (USP_ATTN_ALIBI): rebuild it")
+    fn = getattr(L, name)
+    if fn.argtypes is None:
+        args = UspFwdArgs if name == "usp_flash_fwd_alibi" else UspBwdArgs
+        fn.argtypes = [ctypes.POINTER(args), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+    return fn
+
+
 def _set_shift(a, shift: Optional[int]):
     """Set USP_ATTN_SHIFT + the field on an argument block (None = off); a library that does not report the bit would
     ignore it silently and compute another mask, so it is refused here."""
@@ -392,7 +429,8 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
-              interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None):
+              interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
+              alibi=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -401,7 +439,9 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     logit soft-capping, None / 0 = off (softcap_value; the 64-row family declines it: family="row64" then fails).
     `shift` (None | int, USP_ATTN_SHIFT): moves the diagonal of the causal and window bounds, row i sees key j iff
     i + (Sk - Sq + shift) - left <= j <= i + (Sk - Sq + shift) + right -- the mask of one block of a ring (ring/window_blocks.py).
-    A shifted launch gets no automatic K split (fwd_k_splits sizes cuts for a causal triangle)."""
+    A shifted launch gets no automatic K split (fwd_k_splits sizes cuts for a causal triangle).
+    `alibi`: flash-attn's alibi_slopes, fp32 (Hq,) or (B, Hq) on q's device (alibi_value), None = off: the score of (row i,
+    key j) gets -slope * |i + (Sk - Sq + shift) - j| before the mask (usp_flash_fwd_alibi; not with softcap or family="row64")."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
     cap = softcap_value(softcap)
@@ -423,6 +463,11 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
         if ws is None or ws.numel() < need:
             ws = _FWD_WS[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
         a.workspace = ws.data_ptr()
+    al = alibi_value(alibi, B, Hq, q.device)
+    if al is not None:
+        _check(_alibi_entry("usp_flash_fwd_alibi")(ctypes.byref(a), ctypes.c_void_p(al[0].data_ptr()), al[1], _stream()),
+               "usp_flash_fwd_alibi")
+        return
     _check(L.usp_flash_fwd(ctypes.byref(a), _stream()), "usp_flash_fwd")
 
 
@@ -541,14 +586,15 @@ def bwd_delta(dout, out, delta):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None):
+              softcap=None, shift=None, alibi=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
     flash-attn's window_size (left, right), None / (-1, -1) = none.  `family`: as flash_fwd.  `only`: "dkdv" | "dq" issues
     just that launch of the two (ABI v6: USP_BWD_SKIP_DQ / USP_BWD_SKIP_DKDV).  `dkdv_heads` (ABI v7): query heads of a KV
     group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`, `shift`: as flash_fwd (a
-    shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle)."""
+    shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle).  `alibi`: as flash_fwd
+    (usp_flash_bwd_alibi)."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -587,6 +633,11 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     if need > 0:
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)   # caching allocator; stream-ordered
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    al = alibi_value(alibi, B, Hq, q.device)
+    if al is not None:
+        _check(_alibi_entry("usp_flash_bwd_alibi")(ctypes.byref(a), ctypes.c_void_p(al[0].data_ptr()), al[1], _stream()),
+               "usp_flash_bwd_alibi")
+        return
     _check(L.usp_flash_bwd(ctypes.byref(a), _stream()), "usp_flash_bwd")
 
 

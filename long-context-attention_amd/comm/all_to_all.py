@@ -99,6 +99,30 @@ def pack_heads(x: Tensor, P: int) -> Tensor:
     return send
 
 
+def local_heads(H: int, P: int, rank: int) -> slice:
+    """THE rank -> query-head map of the head-scatter exchange: pack_heads sends chunk p = heads [p H/P, (p+1) H/P) to
+    ulysses rank p, so that is what rank `rank` holds behind it."""
+    assert H % P == 0, f"head count {H} not divisible by ulysses degree {P}"
+    hp = H // P
+    return slice(rank * hp, (rank + 1) * hp)
+
+
+def local_alibi_slopes(alibi_slopes, H: int, P: int, rank: int):
+    """flash-attn's alibi_slopes for the heads ulysses rank `rank` holds behind the head-scatter exchange of an H-head layer.
+    A tensor over the layer's H heads, (H,) or (B, H), is cut to them (local_heads); one over the local H / P heads -- what
+    the reference requires of its caller (it forwards the tensor untouched to a block of H / P heads) -- is taken as it is;
+    any other length raises ValueError.  None stays None."""
+    if alibi_slopes is None or P == 1:
+        return alibi_slopes
+    n = alibi_slopes.shape[-1] if alibi_slopes.dim() in (1, 2) else -1
+    if n == H:
+        return alibi_slopes[..., local_heads(H, P, rank)].contiguous()
+    if H % P == 0 and n == H // P:
+        return alibi_slopes
+    raise ValueError(f"alibi_slopes must cover the layer's {H} heads or the {H // max(P, 1)} heads of one ulysses rank "
+                     f"(shape (H,) or (B, H)), got {tuple(alibi_slopes.shape)}")
+
+
 def pack_head_group(x5: Tensor, send: Tensor = None, h0: int = 0) -> Tensor:
     """x5: a (B, S/P, P, h, D) VIEW (any strides on the first three dims, (h, D) contiguous) selecting
     h heads per destination rank -> heads [h0, h0+h) of the send buffer (P, S/P, B, Ht, D) (allocated with

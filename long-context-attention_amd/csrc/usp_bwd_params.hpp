@@ -55,6 +55,14 @@ struct BwdSoftcap {
   float tanh_k2;                        // 2 * scale * log2(e) / cap (usp_common.hpp: softcap_tanh)
 };
 struct BwdArgsSC : BwdParams, BwdSoftcap {};
+// ALiBi (usp_flash_bwd_alibi): kernel arguments of the ALiBi instantiations only (usp_flash_bwd_alibi.hip:
+// flash_bwd_alibi_kernel, flash_bwd_dkdv_alibi_kernel); every other kernel keeps its argument block and machine code.
+struct BwdAlibi {
+  const float* al_slopes;               // fp32 slopes: head h of batch b at al_slopes[b * al_sb + h]; NULL = no ALiBi
+  int64_t al_sb;                        // batch stride in elements (0: one (Hq,) vector for the whole batch)
+  int al_diag;                          // Sk - Sq + mask_shift: the bias of (row i, key j) is -slope * |i + al_diag - j|
+};
+struct BwdArgsAL : BwdParams, BwdAlibi {};
 
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the
@@ -97,5 +105,9 @@ bool dkdv64_serves(const BwdParams& p);     // ... whether it would (no launch)
 // (ksplit > 1: partials to ws_dq, the caller launches reduce_cuts_kernel behind it) since round 5.
 bool launch_dq64(const BwdParams& p, int dtype, bool causal, hipStream_t st, int* rc);
 bool dq64_serves(const BwdParams& p);
+// The ALiBi backward launches (usp_flash_bwd_alibi.hip): flash_bwd_dkdv_alibi_kernel / flash_bwd_alibi_kernel <D, dtype, causal> on
+// `grid` workgroups of 512 threads with `lds` bytes; `p` is complete.  USP_OK / USP_ELAUNCH / USP_EUNSUPPORTED.
+int launch_dkdv_alibi(const BwdArgsAL& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+int launch_dq_alibi(const BwdArgsAL& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -21,12 +21,20 @@ namespace usp {
 // P = exp2(cap*log2e*t - lse2) (0 where masked) and dS = P (dP - delta) (1 - t^2), in place; the epilogue's `scale` is
 // unchanged.  The body is shared by two __global__ templates so that the kernel without softcap keeps its symbol name
 // and machine code.
+// AL: ALiBi has instantiations of its own in usp_flash_bwd_alibi.hip (flash_bwd_alibi_kernel, flash_bwd_dkdv_alibi_kernel); the
+// kernels here compile the bodies with AL = false.
+#define USP_BWD_NO_ALIBI                            \
+  constexpr bool AL = false;                        \
+  constexpr const float* al_slopes = nullptr;       \
+  constexpr int64_t al_sb = 0;                      \
+  constexpr int al_diag = 0;
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_kernel(
     const BwdParams p_in) {
   constexpr bool SC = false;
   constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
+  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dq_body.inc"
 }
 
@@ -34,6 +42,7 @@ template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_softcap_kernel(const BwdArgsSC p_in) {
   constexpr bool SC = true;
   const float sc_cl2 = p_in.cap_log2, sc_k2 = p_in.tanh_k2;
+  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dq_body.inc"
 }
 
@@ -60,6 +69,7 @@ template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_kernel(const BwdParams p_in) {
   constexpr bool SC = false;
   constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
+  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 
@@ -67,6 +77,7 @@ template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_softcap_kernel(const BwdArgsSC p_in) {
   constexpr bool SC = true;
   const float sc_cl2 = p_in.cap_log2, sc_k2 = p_in.tanh_k2;
+  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 
@@ -149,7 +160,7 @@ static int reduce_grid(int64_t items) { return (int)((items + 255) / 256 > 2048 
 // dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
 // the launch, the 8-wave kernel otherwise; then the sum over the partial slabs of a head-split / cut launch.
 template <int D, int DT>
-static int launch_dkdv(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
+static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, bool causal, hipStream_t st, bool row64) {
   p.nblk = (p.Sk + 127) / 128;
   p.n_items = p.B * p.Hkv * p.nblk * p.ngrp * p.qsplit;
   int rc = USP_ELAUNCH;
@@ -165,6 +176,12 @@ static int launch_dkdv(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
     p.sched_lds = (int)lds;
     const size_t lds_q = lds + (p.sched ? 16 : 0);   // + the item queue's two slots
     const BwdParams pb = p;                        // the argument block of the kernels without softcap
+    if (al.al_slopes) {                            // ALiBi: instantiations of their own (usp_flash_bwd_alibi.hip)
+      BwdArgsAL pa;
+      static_cast<BwdParams&>(pa) = pb;
+      static_cast<BwdAlibi&>(pa) = al;
+      if (int rc2 = launch_dkdv_alibi(pa, D, DT, causal, grid, lds_q, st)) return rc2;
+    } else
     with_causal(causal, [&](auto c) {
       constexpr bool C = decltype(c)::value;
       if (p.cap_on) hipLaunchKernelGGL((flash_bwd_dkdv_softcap_kernel<D, DT, C>), dim3(grid), dim3(512), lds_q, st, p);
@@ -183,7 +200,7 @@ static int launch_dkdv(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
 
 // dQ of a call: the one-wave-per-SIMD kernel (4 waves x 64 query rows, usp_flash_bwd_dq64.hip) or the 8-wave kernel, as above
 template <int D, int DT>
-static int launch_dq(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
+static int launch_dq(BwdArgsSC& p, const BwdAlibi& al, bool causal, hipStream_t st, bool row64) {
   int rc = USP_ELAUNCH;
   if (row64 && launch_dq64(p, DT, causal, st, &rc)) {
     if (rc == USP_OK) launch_kinds_note(USP_KIND_DQ_ROW64);
@@ -196,6 +213,12 @@ static int launch_dq(BwdArgsSC& p, bool causal, hipStream_t st, bool row64) {
   p.sched_lds = (int)lds;
   const size_t lds_q = lds + (p.sched ? 16 : 0);   // + the item queue's two slots
   const BwdParams pb = p;
+  if (al.al_slopes) {                              // ALiBi: instantiations of their own (usp_flash_bwd_alibi.hip)
+    BwdArgsAL pa;
+    static_cast<BwdParams&>(pa) = pb;
+    static_cast<BwdAlibi&>(pa) = al;
+    if (int rc2 = launch_dq_alibi(pa, D, DT, causal, grid, lds_q, st)) return rc2;
+  } else
   with_causal(causal, [&](auto c) {
     constexpr bool C = decltype(c)::value;
     if (p.cap_on) hipLaunchKernelGGL((flash_bwd_softcap_kernel<D, DT, C>), dim3(grid), dim3(512), lds_q, st, p);
@@ -215,17 +238,17 @@ static int launch_reduce_cuts(const BwdParams& p, hipStream_t st) {
 }
 
 template <int D, int DT>
-static int launch_bwd(BwdArgsSC p, bool causal, hipStream_t st, int force, int skip) {
+static int launch_bwd(BwdArgsSC p, const BwdAlibi& al, bool causal, hipStream_t st, int force, int skip) {
   const bool want_dkdv = !(skip & USP_BWD_SKIP_DKDV), want_dq = !(skip & USP_BWD_SKIP_DQ);
   // per call, `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32 (include/usp_hip.h) picks the family; forced onto the 64-row
   // family, only the launches that will run have to be served
   if ((force & USP_FORCE_ROW64) && !(D == 128 && (!want_dkdv || dkdv64_serves(p)) && (!want_dq || dq64_serves(p))))
     return USP_EUNSUPPORTED;
   // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
-  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on;
+  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !al.al_slopes;   // (... and no ALiBi step)
   int rc = USP_OK;
-  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, causal, st, row64)) != USP_OK) return rc;
-  if (want_dq && (rc = launch_dq<D, DT>(p, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
+  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, al, causal, st, row64)) != USP_OK) return rc;
+  if (want_dq && (rc = launch_dq<D, DT>(p, al, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
   return rc;
 }
 
@@ -293,7 +316,8 @@ extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
   return pl.dkdv_bytes + pl.dq_bytes;
 }
 
-extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) {
+// usp_flash_bwd (alibi_slopes == NULL) and usp_flash_bwd_alibi
+static int flash_bwd_call(const usp_bwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse || !a->delta) return USP_EINVAL;
@@ -301,6 +325,7 @@ extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) {
   const int skip = a->flags & (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV);
   if (skip == (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV)) return USP_EINVAL;
   if (int rc = check_problem(*a)) return rc;
+  if (int rc = check_alibi(*a, alibi_slopes, alibi_stride_b)) return rc;
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
@@ -372,8 +397,15 @@ extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) {
     p.ksplit = plan.ksplit;
     if (p.ksplit > 1) p.ws_dq = (float*)((char*)a->workspace + plan.dkdv_bytes);
   }
+  const BwdAlibi al{alibi_slopes, alibi_stride_b, alibi_diag(*a)};
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
-    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, mask.causal, (hipStream_t)stream, force, skip);
+    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, al, mask.causal, (hipStream_t)stream, force, skip);
   });
+}
+
+extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) { return flash_bwd_call(a, nullptr, 0, stream); }
+
+extern "C" int usp_flash_bwd_alibi(const usp_bwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
+  return flash_bwd_call(a, alibi_slopes, alibi_stride_b, stream);
 }

@@ -1,7 +1,8 @@
 // Body of flash_bwd_dkdv_kernel / flash_bwd_dkdv_softcap_kernel (usp_flash_bwd.hip): the dK/dV launch, role-specialised waves.
 // Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps.  The including kernel defines `p_in`, KSPLIT / SC and sc_cl2 / sc_k2.
+// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones.  The including
+// kernel defines `p_in`, SC / AL, sc_cl2 / sc_k2 and al_slopes / al_sb / al_diag.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NW = 8, OWN = 128;
@@ -195,6 +196,10 @@
     int tile_a = t_begin;                          // streamed tile role A works on in iteration `it`
     int tile_b = t_begin;                          // ... and role B (the previous tile of A)
     int buf_a = 0, buf_b = NBUF - 1;               // LDS buffers of those tiles (it % 3, (it - 1) % 3)
+    // ALiBi, role A: -slope * log2(e) of the query head being streamed; an item streams `gsub` heads one after the other,
+    // so it is read again at the first tile of each
+    [[maybe_unused]] float al_ns2 = 0.f;
+    [[maybe_unused]] int al_hh = 0;
     for (int it = 0; it <= n_iter; ++it) {
       const bool prefetch = it + 1 < n_iter;
       const int buf_n = buf_a + 1 == NBUF ? 0 : buf_a + 1;      // (it + 1) % NBUF
@@ -207,6 +212,9 @@
       tile_a = (tile_a + 1 == t_end) ? t_begin : tile_a + 1;
       const int s0 = tile * kTile;
       const bool valid = my_it >= 0 && my_it < n_iter;
+      if constexpr (AL) {
+        if (ROLE == 0 && valid && tile == t_begin) al_ns2 = -kLog2e * al_slopes[b * al_sb + h0 + al_hh++];
+      }
       const bool active = valid && ow < p.Sk && (!CAUSAL || (s0 + kTile - 1 + off >= ow)) &&
                           (!p.win_on || s0 <= ow + 31 - p.win_lo);
       const bool need_mask = (CAUSAL && (s0 + off < ow + 31)) || (p.win_on && s0 + kTile - 1 > ow - p.win_lo);
@@ -227,6 +235,8 @@
           f32x4 stq[4];
           float pg_prev = 0.f;                                   // softcap, role A: P (1 - t^2) of the previous element
           u32x4 pkg;                                             // ... packed: the k-step handed to B                                          // row statistics of one half, fetched ahead of use
+          // ALiBi: row + diag - key of register 0 of half 0 (query row of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
+          [[maybe_unused]] const int al_d0 = s0 + 4 * hi + al_diag - orow;
           auto load_stat = [&](int h, int j) {
             stq[j] = *(USP_LDS const f32x4*)(stat + (32 * h + 4 * hi) * 4 + 32 * j);
           };
@@ -250,6 +260,9 @@
                 const float pg = val * __builtin_fmaf(-t, t, 1.f);
                 if (r & 1) pkg[(r & 7) >> 1] = E::pack2(pg_prev, pg);
                 else pg_prev = pg;
+              } else if constexpr (AL) {                        // the bias goes into the exponent: P = exp2(S c + bias - lse2)
+                const int d = al_d0 + (32 * h + (r & 3) + 8 * (r >> 2));
+                val = fast_exp2(__builtin_fmaf(sc[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -st4[r & 3])));
               } else {
                 val = fast_exp2(__builtin_fmaf(sc[h][r], c, -st4[r & 3]));
               }

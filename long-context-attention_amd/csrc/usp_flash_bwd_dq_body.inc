@@ -1,7 +1,8 @@
 // Body of flash_bwd_kernel / flash_bwd_softcap_kernel (usp_flash_bwd.hip): the dQ launch, 8 waves x 32 query rows.
 // Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps.  The including kernel defines `p_in`, KSPLIT / SC and sc_cl2 / sc_k2.
+// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones.  The including
+// kernel defines `p_in`, SC / AL, sc_cl2 / sc_k2 and al_slopes / al_sb / al_diag.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
@@ -181,6 +182,9 @@
     for (int r = 0; r < 16; ++r) { acc1[dj][r] = 0.f;  }
   
   const float c = p.scale_log2;
+  // ALiBi: -slope * log2(e) of this item's (batch, head), read per item
+  float al_ns2 = 0.f;
+  if constexpr (AL) al_ns2 = -kLog2e * al_slopes[b * al_sb + h0];
 
   if (n_iter > 0) { stage_setup(0); stage_all(); }
   dma_drain();            // this wave's DMA pieces of the staged tile have landed (usp_common.hpp)
@@ -219,6 +223,8 @@
       USP_LDS const char* x2 = x1 + TILEB;
       f32x16 sS[2], sT[2];
       u32x4 pk_ds[2][2];
+      // ALiBi: row + diag - key of register 0 of half 0 (key of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
+      [[maybe_unused]] const int al_d0 = orow + al_diag - s0 - 4 * hi;
 
       auto apply_mask = [&](int h) {
         const int sr0 = s0 + 32 * h + 4 * hi;           // streamed row of register r: sr0 + 8(r>>2) + (r&3)
@@ -243,6 +249,10 @@
             pr = fast_exp2(__builtin_fmaf(t, sc_cl2, -lse2_l));
             pr = x == USP_NEG_INF ? 0.f : pr;
             ds = pr * (sT[h][r] - delta_l) * __builtin_fmaf(-t, t, 1.f);
+          } else if constexpr (AL) {                    // the bias goes into the exponent: P = exp2(S c + bias - lse2)
+            const int d = al_d0 - (32 * h + (r & 3) + 8 * (r >> 2));
+            pr = fast_exp2(__builtin_fmaf(sS[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -lse2_l)));
+            ds = pr * (sT[h][r] - delta_l);
           } else {
             pr = fast_exp2(__builtin_fmaf(sS[h][r], c, -lse2_l));
             ds = pr * (sT[h][r] - delta_l);

@@ -1,8 +1,9 @@
 // Body of flash_fwd_kernel / flash_fwd_softcap_kernel (usp_flash_fwd.hip): one workgroup = NWAVES x 32 query rows.
 // Included as the body of the kernel templates in usp_flash_fwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones.  The including kernel defines `p_in`,
-// KSPLIT / SC / WIN and sc_cl2 / sc_k2.
+// the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones, the ALiBi kernel (usp_flash_fwd_alibi.hip) the
+// `if constexpr (AL)` ones.  The including kernel defines `p_in`, KSPLIT / SC / WIN / AL, sc_cl2 / sc_k2 and al_slopes / al_sb /
+// al_diag.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int kThreads = 64 * NWAVES;
@@ -76,6 +77,7 @@
   // and the causal offset (the tile loops are untouched, as in packed mode).  Each cut writes its own normalised
   // partial (fp32) and its LSE to the workspace through the ordinary not-final epilogue; split_merge_kernel combines
   // them (and the running result, and the 16-bit emission) afterwards.
+  int al_dg = 0;          // ALiBi: the bias diagonal in this item's key numbering (rebased with the K cut below)
   bool win = false;       // left window bound active (split instantiation only)
   int win_lo = 0;         // row i sees key j only if j >= i + win_lo (in the rebased key numbering)
   if constexpr (KSPLIT) {
@@ -103,6 +105,7 @@
     p.Sk = ke > kb ? ke - kb : 0;
     p.causal_off -= kb;
     win_lo -= kb;
+    if constexpr (AL) al_dg = al_diag - kb;
     if (p_in.ksplit > 1) {
       p.acc = p_in.ws_o + (int64_t)ks * p.B * p.Sq * p.Hq * D;
       p.a_sb = (int64_t)p.Sq * p.Hq * D; p.a_ss = (int64_t)p.Hq * D; p.a_sh = D;
@@ -138,6 +141,7 @@
   if (qw + 32 > p.Sq) n_full = 0;                         // ragged / inactive waves take the generic loop
   if constexpr (KSPLIT && !WIN) { if (win) n_full = 0; }  // a left window bound outside the window kernel: every tile through the masked loop
   if constexpr (SC) n_full = 0;                           // softcap: every tile through the generic loop
+  if constexpr (AL) n_full = 0;                           // ALiBi: likewise (the bias step lives there)
   if (n_full > nt) n_full = nt;
   // WIN (flash_fwd_window_kernel: every launch has a left bound): the tiles are walked in the ROTATED order [rot, nt) then
   // [0, rot) -- online softmax does not care -- where rot is the workgroup-uniform number of leading tiles the left bound
@@ -233,7 +237,10 @@
     for (int r = 0; r < 16; ++r) o[dj][r] = 0.f;
   float m_run = USP_NEG_INF;   // running row max, raw score units
   float l_run = 0.f;           // this lane's share of the row sum
-  const float c = SC ? 1.f : p.scale_log2;   // softcap: the scores arrive capped and in exp2 units
+  const float c = (SC || AL) ? 1.f : p.scale_log2;   // softcap, ALiBi: the scores arrive capped / biased and in exp2 units
+  // ALiBi: -slope * log2(e) of this item's (batch, head), read per item: the persistent walk and the K cuts of a tile change it
+  float al_ns2 = 0.f;
+  if constexpr (AL) al_ns2 = -kLog2e * al_slopes[b * al_sb + h];
 
   // S^T = K Q^T for the K tile in Kbuf[kbuf]
   auto qk = [&](int kbuf, f32x16& s0, f32x16& s1) {
@@ -474,7 +481,7 @@
     __syncthreads();             // ... and so have everybody else's
   };
 
-  if (!SC && n_main > 0) {
+  if (!SC && !AL && n_main > 0) {
     float mt = sa[0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mt = fmaxf(mt, sa[r]);
@@ -516,6 +523,17 @@
         for (int r = 0; r < 16; ++r) {
           sa[r] = sc_cl2 * softcap_tanh(sa[r], sc_k2);
           sb[r] = sc_cl2 * softcap_tanh(sb[r], sc_k2);
+        }
+      }
+      if constexpr (AL) {
+        // S2 = raw * scale_log2 - slope_log2 * |row + diag - key|: the distance is an integer, converted once; before the
+        // mask (a masked score stays -inf).  Register r holds key kt0 + 4 hi + (r & 3) + 8 (r >> 2), sb the key 32 further.
+        const int d0 = row + al_dg - kt0 - 4 * hi;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int da = d0 - ((r & 3) + 8 * (r >> 2)), db = da - 32;
+          sa[r] = __builtin_fmaf(sa[r], p.scale_log2, al_ns2 * (float)(da < 0 ? -da : da));
+          sb[r] = __builtin_fmaf(sb[r], p.scale_log2, al_ns2 * (float)(db < 0 ? -db : db));
         }
       }
       if (need_mask) mask(kt0, sa, sb);

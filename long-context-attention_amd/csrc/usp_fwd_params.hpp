@@ -47,6 +47,16 @@ struct FwdSoftcap {
   float tanh_k2;                        // 2 * scale * log2(e) / cap (usp_common.hpp: softcap_tanh)
 };
 struct FwdArgsSC : FwdArgsT<true>, FwdSoftcap {};
+// ALiBi (usp_flash_fwd_alibi): kernel arguments of the ALiBi instantiations only (usp_flash_fwd_alibi.hip:
+// flash_fwd_alibi_kernel, built on the split instantiation's generic loop like the softcap kernels); every other kernel keeps
+// its argument block and machine code.
+struct FwdAlibi {
+  const float* al_slopes;               // fp32 slopes: head h of batch b at al_slopes[b * al_sb + h]; NULL = no ALiBi
+  int64_t al_sb;                        // batch stride in elements (0: one (Hq,) vector for the whole batch)
+  int al_diag;                          // Sk - Sq + mask_shift: the bias of (row i, key j) is -slope * |i + al_diag - j|.  A field
+                                        // of its own: causal_off also absorbs window_right and is dropped with a bound that cuts nothing
+};
+struct FwdArgsAL : FwdArgsT<true>, FwdAlibi {};
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -62,5 +72,8 @@ template <int D> struct KSwz {
 bool launch_fwd64(const FwdArgsT<true>& p, int dtype, bool causal, hipStream_t st, int* rc);
 // The merge launch behind a K-split forward (usp_flash_fwd.hip: split_merge_kernel), same stream.
 int launch_split_merge(const FwdArgsT<true>& p, int dtype, int D, hipStream_t st);
+// The ALiBi forward (usp_flash_fwd_alibi.hip): flash_fwd_alibi_kernel<D, dtype, causal, waves> (waves = 4 | 8) on `grid`
+// workgroups with `lds` bytes; `p` is complete (nq / n_items included).  Returns USP_OK / USP_ELAUNCH / USP_EUNSUPPORTED.
+int launch_fwd_alibi(const FwdArgsAL& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -90,6 +90,23 @@ template <class Args> int check_problem(const Args& a) {
   return USP_OK;
 }
 
+// ALiBi (usp_flash_fwd_alibi / usp_flash_bwd_alibi): what a call with slopes must not carry -- checked before anything is
+// launched or written.  NULL slopes: the call is usp_flash_fwd / usp_flash_bwd, whatever the stride.
+template <class Args> int check_alibi(const Args& a, const float* slopes, int64_t stride_b) {
+  if (!slopes) return USP_OK;
+  if (stride_b < 0) return USP_EINVAL;
+  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
+  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
+  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
+  return USP_OK;
+}
+// The bias diagonal: the bias of (row i, key j) is -slope * |i + diag - j|, diag = Sk - Sq + mask_shift.  Not taken from the
+// decoded mask: causal_off also absorbs window_right, and a bound that cuts nothing is dropped there -- the bias is not.
+// |mask_shift| < 2^30 (check_problem) and Sq + Sk < 2^29 keep it in int.
+template <class Args> int alibi_diag(const Args& a) {
+  return (int)((int64_t)a.Sk - a.Sq + ((a.flags & USP_ATTN_SHIFT) ? a.mask_shift : 0));
+}
+
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound
 // at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
 // (forward: the split instantiation, FwdSplit).

@@ -519,7 +519,9 @@ class AsyncLongContextAttention(torch.nn.Module):
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any) -> Tensor:
         """query (bs, seqlen/P, hc, hs); key/value (bs, seqlen/P, hc_kv, hs) -> (bs, seqlen/P, hc, hs)."""
-        assert alibi_slopes is None
+        if alibi_slopes is not None:
+            raise NotImplementedError("alibi_slopes is not supported by AsyncLongContextAttention: use LongContextAttention "
+                                      "with the basic ring (ring_impl_type=\"basic\")")
         _check_hot_path_args(dropout_p, window_size, softcap)
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate: zero-padded copies

@@ -15,7 +15,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from .._C import softcap_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_alibi_slopes
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
@@ -55,6 +55,14 @@ class _USPLayer(torch.nn.Module):
         if self._ring_size is None:
             self._ring_size = dist.get_world_size(self.ring_pg) if self.ring_pg is not None else 1
         return self._ring_size
+
+    def _local_slopes(self, alibi_slopes, heads: int, scatter_idx: int):
+        """alibi_slopes for the heads this Ulysses rank holds behind the exchange (comm/all_to_all.py: local_alibi_slopes)."""
+        if alibi_slopes is None or self.ulysses_size == 1:
+            return alibi_slopes
+        if (scatter_idx, self.gather_idx) != (2, 1):
+            raise NotImplementedError("alibi_slopes needs the head-scatter exchange (heads scattered, sequence gathered)")
+        return local_alibi_slopes(alibi_slopes, heads, self.ulysses_size, dist.get_rank(self.ulysses_pg))
 
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                       return_attn_probs):
@@ -121,12 +129,15 @@ class LongContextAttention(_USPLayer):
         if ng_cap is not None and window_of(window_size) is not None:
             ng_cap = None         # a sliding window: the reference's structure (three exchanges); the basic ring function
                                   # serves it at ring degree 1 and, with USP_RING_WINDOW=global, beyond (ring/ring_flash_attn.py)
+        if ng_cap is not None and alibi_slopes is not None:
+            ng_cap = None         # ALiBi: likewise three exchanges -- the pipeline's row pieces and head groups would each need a
+                                  # slice of the slopes and a shift; the ring function serves it (ring/front_end.py: _check_alibi)
         if ng_cap is not None:
-            assert alibi_slopes is None
             _check_hot_path_args(dropout_p, window_size, softcap)
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
                                        self.ring_impl_type, ng_cap, softcap_value(softcap))
-        options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
+        options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap,
+                                     self._local_slopes(alibi_slopes, query.shape[2], self.scatter_idx),
                                      deterministic, return_attn_probs)
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
@@ -159,6 +170,7 @@ class LongContextAttentionQKVPacked(_USPLayer):
                                window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args)
             return out[..., :D]
         exchange = self.ulysses_size > 1
+        alibi_slopes = self._local_slopes(alibi_slopes, qkv.shape[3], self.scatter_idx - 1)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,

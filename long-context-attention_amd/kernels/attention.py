@@ -78,19 +78,19 @@ class HipBlockBackend:
         return self._beside
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
-            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None):
+            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
-                     interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift)
+                     interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
 
     def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq=False,
             accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None, softcap=None,
-            shift=None):
+            shift=None, alibi=None):
         _C.flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq,
                      accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only,
-                     softcap=softcap, shift=shift)
+                     softcap=softcap, shift=shift, alibi=alibi)
 
     def fwd_packed(self, q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out=None,
                    acc=None, merge_in=False, final_begin=0, final_end=2, softcap=None):
@@ -147,16 +147,47 @@ class _SoftcapBackend:
         return getattr(self._be, name)
 
 
-def get_block_backend(beside_transfers: bool = False, softcap=None):
+class _AlibiBackend:
+    """A block backend whose dense flash calls (fwd, bwd) all carry `alibi=slopes`; everything else is the wrapped backend's.
+    The bias of a block depends on WHERE the block lies: a caller whose block is not the whole sequence passes `shift=` with
+    each call (the basic ring does, ring/ring_flash_attn.py).  The packed calls refuse: the kernels serve ALiBi on dense
+    launches only."""
+
+    def __init__(self, be, slopes):
+        self._be, self._slopes = be, slopes
+
+    def fwd(self, *args, **kw):
+        self._be.fwd(*args, alibi=self._slopes, **kw)
+
+    def bwd(self, *args, **kw):
+        self._be.bwd(*args, alibi=self._slopes, **kw)
+
+    def fwd_packed(self, *args, **kw):
+        raise NotImplementedError("alibi_slopes is not supported on packed (variable-length) batches")
+
+    def bwd_packed(self, *args, **kw):
+        raise NotImplementedError("alibi_slopes is not supported on packed (variable-length) batches")
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+
+def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None):
     """The block backend; `beside_transfers=True` asks for launches that leave room for collectives queued on
     other streams (a persistent flash launch holds every CU until it ends: DESIGN.md section 5).  Test
     backends without that notion are returned as they are.  `softcap` > 0 (flash-attn's logit cap): every flash
     call of the returned backend carries it; None / 0: the backend itself, whose calls carry no softcap keyword
-    (backends written before softcap existed keep working)."""
+    (backends written before softcap existed keep working).  `alibi`: flash-attn's alibi_slopes as the block calls take them
+    (an fp32 (Hq,) or (B, Hq) tensor on the operands' device, _C.alibi_value), None = off: every dense flash call carries
+    them; together with softcap: NotImplementedError (no kernel holds both steps)."""
     be = _BACKEND
     if beside_transfers and hasattr(be, "beside_transfers"):
         be = be.beside_transfers()
     cap = _C.softcap_value(softcap)
+    if alibi is not None:
+        if cap is not None:
+            raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
+        return _AlibiBackend(be, alibi)
     return be if cap is None else _SoftcapBackend(be, cap)
 
 
@@ -175,14 +206,22 @@ def _default_scale(q, softmax_scale):
 
 def _check_plain(dropout_p, softcap, alibi_slopes):
     """Refuses what the kernels do not serve and returns the softcap as the kernels take it (None = off).
-    window_size and softcap ARE served: the block kernels take flash-attn's (left, right) window and its tanh logit cap
-    (include/usp_hip.h, USP_ATTN_WINDOW / USP_ATTN_SOFTCAP).  A negative, NaN or infinite softcap raises ValueError
-    (flash-attn ignores a negative one silently)."""
+    window_size, softcap and alibi_slopes ARE served: the block kernels take flash-attn's (left, right) window, its tanh logit
+    cap and its ALiBi slopes (include/usp_hip.h, USP_ATTN_WINDOW / USP_ATTN_SOFTCAP / usp_flash_fwd_alibi) -- ALiBi and
+    softcap not together.  A negative, NaN or infinite softcap raises ValueError (flash-attn ignores a negative one
+    silently)."""
     if dropout_p not in (0, 0.0):
         raise NotImplementedError("dropout_p != 0 is not supported by the HIP attention kernel")
-    if alibi_slopes is not None:
-        raise NotImplementedError("alibi_slopes is not supported by the HIP attention kernel")
-    return _C.softcap_value(softcap)
+    cap = _C.softcap_value(softcap)
+    if alibi_slopes is not None and cap is not None:
+        raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
+    return cap
+
+
+def _alibi_of(alibi_slopes, q):
+    """flash-attn's alibi_slopes, checked against q (B, S, Hq, D) (_C.alibi_value: ValueError), as the block calls take it."""
+    al = _C.alibi_value(alibi_slopes, q.shape[0], q.shape[2], q.device)
+    return None if al is None else al[0]
 
 
 def window_of(window_size):
@@ -201,11 +240,12 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     scale = _default_scale(q, softmax_scale)
     if kernel_head_dim(D) != D:                 # e.g. 96: on zero-padded copies (kernel_head_dim)
         out, lse = hip_attn_forward(*pad_head_dim(q, k, v), softmax_scale=scale, causal=causal, window_size=window_size,
-                                    softcap=cap)
+                                    softcap=cap, alibi_slopes=alibi_slopes)
         return out[..., :D].contiguous(), lse
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
-    get_block_backend(softcap=cap).fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size))
+    get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q)).fwd(q, k, v, scale, bool(causal), lse, out=out,
+                                                                         window=window_of(window_size))
     return out, lse
 
 
@@ -217,7 +257,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
     (zigzag_ring_flash_attn.py:115-137)."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
-    be = get_block_backend(softcap=cap)
+    be = get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q))
     B, Sq, Hq, D = q.shape
     dev = q.device
     if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
@@ -250,12 +290,13 @@ class _HipAttnFunc(torch.autograd.Function):
     yunchang/ulysses/attn_layer.py:48,101-113)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None):
+    def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
-        out, lse = hip_attn_forward(q, k, v, softmax_scale=scale, causal=causal, window_size=window_size, softcap=softcap)
-        ctx.save_for_backward(q, k, v, out, lse)
-        ctx.scale, ctx.causal, ctx.window_size, ctx.softcap = scale, bool(causal), window_size, softcap
+        out, lse = hip_attn_forward(q, k, v, softmax_scale=scale, causal=causal, window_size=window_size, softcap=softcap,
+                                    alibi_slopes=alibi_slopes)
+        ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)))   # (slopes: no gradient,
+        ctx.scale, ctx.causal, ctx.window_size, ctx.softcap = scale, bool(causal), window_size, softcap   # as in flash-attn)
         if return_lse:
             ctx.mark_non_differentiable(lse)
             return out, lse
@@ -263,11 +304,11 @@ class _HipAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *_):
-        q, k, v, out, lse = ctx.saved_tensors
+        q, k, v, out, lse, *slopes = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, 0.0, ctx.scale, ctx.causal,
-                          ctx.window_size, ctx.softcap)
-        return dq, dk, dv, None, None, None, None, None
+                          ctx.window_size, ctx.softcap, slopes[0] if slopes else None)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
@@ -275,14 +316,16 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
                   *args, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised: dropout is 0).  `softcap` > 0: flash-attn's
-    tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError."""
+    tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.  `alibi_slopes`: flash-attn's fp32
+    (Hq,) or (B, Hq) slopes (no gradient), not together with softcap."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)
         res = hip_attn_func(*pad_head_dim(q, k, v), softmax_scale=_default_scale(q, softmax_scale), causal=causal,
-                            window_size=window_size, softcap=cap, return_attn_probs=return_attn_probs)
+                            window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes,
+                            return_attn_probs=return_attn_probs)
         return (res[0][..., :D], res[1], None) if return_attn_probs else res[..., :D]
     if return_attn_probs:
-        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap)
+        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap, alibi_slopes)
         return out, lse, None
-    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap)
+    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap, alibi_slopes)

@@ -2,10 +2,12 @@
 made per ring from its (forward, backward) pair.  The ring modules keep their schedules and bind their public names to what
 `ring_front_end` returns; the surfaces are the reference's (yunchang/ring/*.py), argument for argument."""
 import torch
+import torch.distributed as dist
 
-from .._C import softcap_value
+from .._C import alibi_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
+from .utils import group_info
 from .varlen_utils import unflatten_lse
 
 
@@ -22,7 +24,27 @@ def _check_hot_path_args(dropout_p, window_size, softcap):
     softcap_value(softcap)
 
 
-def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False):
+def _check_alibi(alibi_slopes, q, softcap, group, packed, served_beyond_one_block):
+    """ALiBi (flash-attn's alibi_slopes) on a ring.  The bias of a block depends on where the block lies in the whole sequence,
+    so a ring serves it only where it places every block: the dense rings at ring degree 1 (ONE block: basic, zigzag, stripe)
+    and the basic ring beyond (`served_beyond_one_block`: its forward decides, USP_RING_ALIBI=global).  Everything else refuses;
+    a wrong shape, dtype or device of the slopes is a ValueError (_C.alibi_value)."""
+    if alibi_slopes is None:
+        return
+    if packed:
+        raise NotImplementedError("alibi_slopes is not supported by the variable-length (packed) rings: use the basic ring "
+                                  "(ring_impl_type=\"basic\", ring_flash_attn_func) on dense batches")
+    if softcap_value(softcap) is not None:
+        raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
+    alibi_value(alibi_slopes, q.shape[0], q.shape[2], q.device)
+    if not served_beyond_one_block and group_info(dist, group)[0] > 1:
+        raise NotImplementedError("alibi_slopes across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
+                                  "rings: use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func), which serves "
+                                  "it over global positions with USP_RING_ALIBI=global")
+
+
+def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False,
+                   alibi_in_forward=False):
     """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
 
         packed             the variable-length form: q / k / v are (T, H, D) token tensors followed by `cu_seqlens, max_seqlen`;
@@ -31,7 +53,10 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
                            reference's padded (num_seq, H, max_seqlen) layout;
         attn_processor     the Function carries `attn_processor` to the forward (the basic ring);
         window_in_forward  `window_size` is judged by the forward, not here (the basic ring serves a window at ring degree 1
-                           and refuses beyond).
+                           and refuses beyond);
+        alibi_in_forward   `alibi_slopes` at ring degree > 1 is judged by the forward (the basic ring: USP_RING_ALIBI); every
+                           other dense ring serves it at ring degree 1, where it is one block, and refuses beyond; the packed
+                           rings refuse it (_check_alibi).
     The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
     grad; both exist here only."""
     n_lead = 2 if packed else 0
@@ -42,7 +67,7 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse)."""
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
-        assert alibi_slopes is None
+        _check_alibi(alibi_slopes, q, softcap, group, packed, alibi_in_forward)
         _check_hot_path_args(dropout_p, (-1, -1) if window_in_forward else window_size, softcap)
         if packed:
             k, v = k.contiguous(), v.contiguous()

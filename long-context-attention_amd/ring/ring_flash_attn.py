@@ -6,6 +6,10 @@ ring rank r-s; under causal only steps <= r compute and only step 0 is causal.  
 in zigzag_ring_flash_attn.py (fused merge, fp32 in-place gradient accumulation, K/V relay on a
 side stream); additionally dq is returned in q.dtype (the reference hard-codes bfloat16 at :147).
 
+ALiBi (`alibi_slopes`) is one block at ring degree 1; at ring degree > 1 it is served on request (USP_RING_ALIBI=global) over
+GLOBAL positions: the step that sees the K/V of ring rank kr is launched with the diagonal shift (r - kr) * S, which places the
+bias of the block (include/usp_hip.h: usp_flash_fwd_alibi) -- K/V transport and the dK/dV return are unchanged.
+
 A sliding window (`window_size`) is one windowed block at ring degree 1; at ring degree > 1 it is served on request
 (USP_RING_WINDOW=global) over GLOBAL positions: only the blocks the window touches are fetched, launched and returned, each
 with its own shifted bounds (ring/window_blocks.py).
@@ -43,6 +47,41 @@ def _ring_window(window_size, P):
     return win
 
 
+def ring_alibi_mode() -> str:
+    """USP_RING_ALIBI, read per call: "global" serves alibi_slopes at ring degree > 1 with distances between GLOBAL positions
+    (row i and key j of the whole sequence: -slope * |i - j|); anything else (the default) refuses."""
+    return os.environ.get("USP_RING_ALIBI", "").strip().lower()
+
+
+def _ring_alibi(alibi_slopes, P):
+    """flash-attn's alibi_slopes as the block launches take them, or None.  One block (ring degree 1) is flash-attn's own
+    function.  Across ring steps every block needs its own diagonal (the reference hands the same slopes to every block,
+    yunchang/ring/ring_flash_attn.py:36-48, and so measures distances INSIDE each block: a different function).  Global
+    positions are served on request, USP_RING_ALIBI=global: a caller who comes from the reference gets an error, not other
+    numbers, until they ask."""
+    if alibi_slopes is not None and P > 1 and ring_alibi_mode() != "global":
+        raise NotImplementedError("alibi_slopes across ring steps (ring degree > 1) is not supported by default: set "
+                                  "USP_RING_ALIBI=global for a bias over GLOBAL positions on the basic ring (the reference "
+                                  "applies the same per-block bias to every block instead, a different function)")
+    return alibi_slopes
+
+
+def _alibi_shift(al, r, P, step, S, blk_kw=None):
+    """The `shift` keyword of the launch of ring step `step` under ALiBi: the block holds the K/V of ring rank kr = r - step
+    (mod P), whose keys lie (r - kr) * S rows in front of this rank's queries (behind them: negative, the non-causal ring).
+    The rank's own block (shift 0) carries no keyword: it is an unshifted launch and keeps its automatic K split and cuts.
+    `blk_kw`: the launch keywords of a window planner's block; a bounded block carries its own shift, which places the MASK --
+    the same number by construction (ring/window_blocks.py: (rank - src) * c), asserted because the bias would follow it."""
+    blk_kw = dict(blk_kw or {})
+    if al is None:
+        return blk_kw
+    shift = (r - (r - step) % P) * S
+    assert blk_kw.get("shift", shift) == shift, f"ring step {step}: the window block's shift {blk_kw['shift']} is not the bias's {shift}"
+    if shift != 0:
+        blk_kw["shift"] = shift
+    return blk_kw
+
+
 def _window_plan(win, P, r, c, causal):
     return WindowPlan(P, c, bool(causal), win[0], win[1], r)
 
@@ -51,23 +90,23 @@ def _window_kw(win):
     return {} if win is None else {"window": win}
 
 
-def basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc):
+def basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc, **kw):
     """One step of the contiguous-layout ring forward (ring_flash_attn.py:29-56); pure schedule
-    logic, also driven by the single-GPU tests with virtual ranks."""
+    logic, also driven by the single-GPU tests with virtual ranks.  `kw`: further keywords of the launch (ALiBi: shift)."""
     if causal and step > r:
         return
     last_compute = r if causal else P - 1
     fe = q.shape[1] if step == last_compute else 0
-    be.fwd(q, kk, vv, softmax_scale, bool(causal and step == 0), lse, out, acc, step > 0, 0, fe)
+    be.fwd(q, kk, vv, softmax_scale, bool(causal and step == 0), lse, out, acc, step > 0, 0, fe, **kw)
 
 
 def basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, lse, delta, softmax_scale, dq_acc,
-                    dk_dst, dv_dst):
-    """Block backward of one step (:93-122).  Returns False when the step computes nothing."""
+                    dk_dst, dv_dst, **kw):
+    """Block backward of one step (:93-122).  Returns False when the step computes nothing.  `kw`: as basic_fwd_step."""
     if causal and step > r:
         return False
     be.bwd(dout, q, kk, vv, lse, delta, dq_acc, dk_dst, dv_dst, softmax_scale,
-           bool(causal and step == 0), accum_dq=step > 0)
+           bool(causal and step == 0), accum_dq=step > 0, **kw)
     return True
 
 
@@ -78,8 +117,9 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None
-    assert not pieces or (P == 1 and causal and window_of(window_size) is None)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None)
+    al = _ring_alibi(alibi_slopes, P)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al)
     if pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     B, S, H, D = q.shape
@@ -99,14 +139,14 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
                 kk, vv = relay.get(step)
                 blk = plan.block(step)
                 be.fwd(q, kk, vv, softmax_scale, blk.causal, lse, out, acc, i > 0, 0, S if step == plan.steps[-1] else 0,
-                       **blk.launch_kw())
+                       **_alibi_shift(al, r, P, step, S, blk.launch_kw()))
         return out, lse
     last_compute = r if causal else P - 1
     acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if last_compute > 0 else None
     with KVRelay(process_group, k, v) as relay:
         for step in range(P):
             kk, vv = relay.get(step)
-            basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc)
+            basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc, **_alibi_shift(al, r, P, step, S))
     return out, lse
 
 
@@ -118,8 +158,9 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or dq_first is not None
-    assert not pieces or (P == 1 and causal and window_of(window_size) is None)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None)
+    al = _ring_alibi(alibi_slopes, P)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al)
     if pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S, H, D = q.shape
@@ -141,7 +182,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
         def win_block(step, kk, vv, dk_dst, dv_dst):
             blk = plan.block(step)
             be.bwd(dout, q, kk, vv, softmax_lse, delta, dq_acc, dk_dst, dv_dst, softmax_scale, blk.causal,
-                   accum_dq=step > 0, **blk.launch_kw())       # (step 0 is never empty: it is the first to write dq)
+                   accum_dq=step > 0, **_alibi_shift(al, r, P, step, S, blk.launch_kw()))   # (step 0 is never empty: it is the first to write dq)
 
         dk_acc, dv_acc = return_dkdv_direct(process_group, k, v, win_block, plan.key_extent, be,
                                             relay_kw=dict(recv_steps=plan.recv, send_steps=plan.send))
@@ -149,7 +190,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
     def block(step, kk, vv, dk_dst, dv_dst):
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
-                               dq_acc, dk_dst, dv_dst)
+                               dq_acc, dk_dst, dv_dst, **_alibi_shift(al, r, P, step, S))
 
     def fold(step, dk_acc, dv_acc, dk_blk, dv_blk):
         be.add(dk_acc, dk_acc, dk_blk)
@@ -163,4 +204,4 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
 (RingFlashAttnFunc, ring_flash_attn_func, ring_flash_attn_kvpacked_func, ring_flash_attn_qkvpacked_func) = ring_front_end(
     "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, attn_processor=True,
-    window_in_forward=True)
+    window_in_forward=True, alibi_in_forward=True)

@@ -54,7 +54,8 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
                               attn_type: AttnType = AttnType.HIP, overlap=False):
     assert causal, "stripe flash attn only supports causal attention, if not causal, use ring flash attn instead"
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
+    assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
@@ -73,7 +74,8 @@ def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, s
                                overlap=False, defer=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, ring flash attn instead"
     P, r = group_info(dist, process_group)
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap)
+    assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes)
     B, S, H, D = q.shape
     dev = q.device
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)

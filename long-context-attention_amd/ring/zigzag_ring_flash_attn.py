@@ -200,15 +200,17 @@ def _final_rows(be, q, kp, vp, softmax_scale, lse, out, acc, lo, hi, tail):
         emit(j, out)
 
 
-def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None):
+def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None, alibi=None):
     """The zigzag ring forward as a generator of two phases.  With `first` beside a ring (degree > 1) it yields ONCE, behind the
     launch on the owned chunk and in front of the wait for the caller's exchange -- the caller may start other head groups' owned
     chunks there -- and returns (out, lse) through StopIteration; otherwise it never yields.  zigzag_ring_flash_attn_forward drives it
     to the end.
-    `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same."""
+    `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same.
+    `alibi`: flash-attn's alibi_slopes, served where the ring is ONE block (ring degree 1, no pieces)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None          # (the caller has exchanges in flight by definition)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    assert alibi is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi)
     B, S2, H, D = q.shape
     assert S2 % 2 == 0, "zigzag layout needs an even local sequence length"
     if P == 1 and pieces:
@@ -274,7 +276,7 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
     At ring degree 1 the ring is ONE causal block and both are served by ring/block_pieces.py (`first` where both are given).
     Either one means transfers in flight: the kernels are launched as under `overlap`."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
-    gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap)
+    gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap, alibi_slopes)
     try:
         while True:
             next(gen)
@@ -303,7 +305,8 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     assert causal == True, "zigzag ring is meaningless for causal=False"
     P, r = group_info(dist, process_group)
     pieces = first is not None or dq_first is not None      # (the caller has exchanges in flight by definition)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap)
+    assert alibi_slopes is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi_slopes)
     if P == 1 and pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S2, H, D = q.shape

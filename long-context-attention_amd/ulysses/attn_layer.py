@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_alibi_slopes
 from ..kernels import AttnType, select_flash_attn_impl
 
 
@@ -36,6 +36,10 @@ class UlyssesAttention(torch.nn.Module):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any) -> Tensor:
+        if alibi_slopes is not None:     # slopes over the layer's heads are cut to this rank's (comm/all_to_all.py: local_heads)
+            if (self.scatter_idx, self.gather_idx) != (2, 1):
+                raise NotImplementedError("alibi_slopes needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
+            alibi_slopes = local_alibi_slopes(alibi_slopes, query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
         q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
