@@ -9,6 +9,8 @@
 #include <stdint.h>
 #define USP_DEAL_FN __device__ __forceinline__
 #include "usp_item_deal.h"
+#define USP_RANGE_FN __device__ __forceinline__
+#include "usp_tile_range.h"
 
 namespace usp {
 

@@ -7,11 +7,13 @@
 //                                    lane owns a query row:  S^T = K Q^T, dP^T = V dO^T, dQ^T += K^T dS^T
 //   dK, dV (flash_bwd_dkdv_kernel) : workgroup = 8 waves, 128 keys, two roles (below); the one-wave-per-SIMD form of it
 //                                    lives in usp_flash_bwd64.hip and serves the dense D = 128 launches.
-// Both are one engine: two LDS tiles X1,X2 (row-major, 16-byte-slot XOR swizzle chosen so that
-// BOTH ds_read_b128 row reads and ds_read_b64_tr_b16 column reads are bank-conflict free), two
-// register-resident fragment sets R1,R2, S = X1 R1^T, T = X2 R2^T, and tr-read "X^T" operands for
-// the gradient MFMAs.  As in the forward, no cross-lane shuffle is needed for P / dS: the k-step
-// order of the gradient MFMAs is defined as the order the S accumulator holds rows.
+// Each is a body of its own (usp_flash_bwd_dq_body.inc, usp_flash_bwd_dkdv_body.inc).  What they share is the layout: the
+// streamed pair of tiles -- K and V for dQ, Q and dO for dK/dV -- lies in LDS row-major with a 16-byte-slot XOR swizzle chosen
+// so that BOTH ds_read_b128 row reads and ds_read_b64_tr_b16 column reads are bank-conflict free; the wave's own rows (Q and dO
+// fragments for dQ; K or V fragments, by role, for dK/dV) stay in registers as B operands; the chains S = K Q^T, dP = V dO^T
+// (dQ) and S = Q K^T, dP = dO V^T (dK/dV) read the tiles by rows, the gradient MFMAs read them transposed.  As in the forward,
+// no cross-lane shuffle is needed for P / dS: the k-step order of the gradient MFMAs is defined as the order the S accumulator
+// holds rows.  Which tiles an item streams and which of them are live or masked: usp_tile_range.h.
 #include "usp_bwd_params.hpp"
 #include "usp_host.hpp"
 

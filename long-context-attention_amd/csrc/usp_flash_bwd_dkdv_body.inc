@@ -67,26 +67,18 @@
     for (int t = 0; t < NKT; ++t) rf[t] = *(const u32x4*)(pr + 32 * t + 16 * hi);
   }
 
-  int t_begin = 0, t_end = (p.Sq + kTile - 1) / kTile;
-  if (CAUSAL) {
-    const int first_q = own0 - off > 0 ? own0 - off : 0;
-    t_begin = first_q / kTile;
-    if (t_begin > t_end) t_begin = t_end;
-  }
+  // ---- streamed range: query tiles [t_begin, t_end) of each of the item's gsub heads (usp_tile_range.h) ---------------
+  int t_end = (p.Sq + kTile - 1) / kTile;
+  int t_begin = usp_first_row_tile(own0, CAUSAL, off, t_end, kTile);
   if (p.win_on) {                                // query rows beyond the window of the block's last key: not streamed
-    const int last = own0 + OWN - 1 - p.win_lo;  // row i sees key j only if i <= j - win_lo
-    const int te = last >= 0 ? last / kTile + 1 : 0;
-    t_end = te < t_end ? te : t_end;
+    t_end = usp_last_row_tile(own0, OWN, 1, p.win_lo, t_end, kTile);
     if (t_begin > t_end) t_begin = t_end;
   }
   if (p.qsplit > 1) {                            // this item's cut of the query tiles [t_begin, t_end): equal runs
-    const int per = (t_end - t_begin + p.qsplit - 1) / p.qsplit;
-    t_begin = t_begin + cut * per < t_end ? t_begin + cut * per : t_end;
-    t_end = t_begin + per < t_end ? t_begin + per : t_end;
+    const usp_tile_run run = usp_equal_run(t_begin, t_end, p.qsplit, cut);
+    t_begin = run.begin; t_end = run.end;
   }
-  const int per_head = t_end - t_begin;
-  const int heads_here = p.gsub;
-  const int n_iter = per_head * heads_here;
+  const int n_iter = (t_end - t_begin) * p.gsub;
 
   // ---- LDS-DMA staging of the Q / dO tiles -----------------------------------------------------------------
   // ONE buffer descriptor pair per (item, query head), based on row 0 of that head; a tile is addressed by a scalar byte
@@ -96,34 +88,34 @@
   // (v_readlane) at the head of EVERY iteration of EVERY wave, 40 % of a wave's instruction stream -- the kernel was
   // bound by instruction issue, not by the MFMA pipe: with every element operation removed it still ran at 973 of
   // 1071 us, profiles/r03_bwd_ablations.txt.)  The host guarantees that a head's rows span less than 2^31 bytes.
-  int dma_voff1[CPW], dma_voff2[CPW];
+  int q_voff[CPW], do_voff[CPW];
 #pragma unroll
   for (int i = 0; i < CPW; ++i) {
     const int cidx = wave + NW * i;
     const int r = cidx * RPC + lane / (D / 8);
     const int c8 = (lane % (D / 8)) ^ tile_swz<D>(r);
-    dma_voff1[i] = r * (int)p.q_ss * 2 + c8 * 16;
-    dma_voff2[i] = r * (int)p.do_ss * 2 + c8 * 16;
+    q_voff[i] = r * (int)p.q_ss * 2 + c8 * 16;
+    do_voff[i] = r * (int)p.do_ss * 2 + c8 * 16;
   }
   float st_lse = 0.f, st_delta = 0.f;
   bool st_in = false;
-  decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0)) rs1, rs2;
-  const int tb1 = kTile * (int)p.q_ss * 2, tb2 = kTile * (int)p.do_ss * 2;     // bytes per tile step
-  int pf_tile = t_begin, pf_hh = 0, soff1 = 0, soff2 = 0;
+  decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0)) q_rs, do_rs;
+  const int q_step = kTile * (int)p.q_ss * 2, do_step = kTile * (int)p.do_ss * 2;   // bytes per tile step
+  int pf_tile = t_begin, pf_hh = 0, q_soff = 0, do_soff = 0;
   const float *lse_h = nullptr, *dl_h = nullptr;                             // row statistics of the cursor's head
   const bool stat_wave = wave == 4;              // a role-B wave fetches the tile's statistics: role A is the longer stream
   auto pf_head = [&]() {                         // (re)base the cursor on head h0 + pf_hh, tile t_begin
     auto clampu = [](int64_t r) { return (int)(uint32_t)(r < 0 ? 0 : (r > 0xffffffffLL ? 0xffffffffLL : r)); };
     const int h = h0 + pf_hh;
-    rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.q + 2 * (b * p.q_sb + h * p.q_sh)), 0,
-                                            clampu(((int64_t)(p.Sq - 1) * p.q_ss + D) * 2), 0x00020000);
-    rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dout + 2 * (b * p.do_sb + h * p.do_sh)), 0,
-                                            clampu(((int64_t)(p.Sq - 1) * p.do_ss + D) * 2), 0x00020000);
+    q_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.q + 2 * (b * p.q_sb + h * p.q_sh)), 0,
+                                             clampu(((int64_t)(p.Sq - 1) * p.q_ss + D) * 2), 0x00020000);
+    do_rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dout + 2 * (b * p.do_sb + h * p.do_sh)), 0,
+                                              clampu(((int64_t)(p.Sq - 1) * p.do_ss + D) * 2), 0x00020000);
     lse_h = p.lse + b * p.lse_sb + h * p.lse_sh;
     dl_h = p.delta + b * p.dl_sb + h * p.dl_sh;
     pf_tile = t_begin;
-    soff1 = t_begin * tb1;
-    soff2 = t_begin * tb2;
+    q_soff = t_begin * q_step;
+    do_soff = t_begin * do_step;
   };
   pf_head();
   // issue the cursor's tile into LDS buffer `buf`, fetch its row statistics, advance the cursor
@@ -139,15 +131,15 @@
     for (int i = 0; i < CPW; ++i) {
       const int cidx = wave + NW * i;
       if (CHUNKS % NW == 0 || cidx < CHUNKS) {
-        USP_LDS char* d1 = smem + buf * BUFB + cidx * 1024;
-        lds_dma16(rs1, d1, dma_voff1[i], soff1);
-        lds_dma16(rs2, d1 + TILEB, dma_voff2[i], soff2);
+        USP_LDS char* dst = smem + buf * BUFB + cidx * 1024;
+        lds_dma16(q_rs, dst, q_voff[i], q_soff);
+        lds_dma16(do_rs, dst + TILEB, do_voff[i], do_soff);
       }
     }
     ++pf_tile;
-    soff1 += tb1;
-    soff2 += tb2;
-    if (heads_here > 1 && pf_tile == t_end) { ++pf_hh; pf_head(); }
+    q_soff += q_step;
+    do_soff += do_step;
+    if (p.gsub > 1 && pf_tile == t_end) { ++pf_hh; pf_head(); }
   };
   auto stage_stats = [&](int buf) {
     if (stat_wave) {
@@ -206,7 +198,6 @@
       if (prefetch) stage_next(buf_n);
 
       const int my_it = it - ROLE;
-      const int buf_of_my = ROLE == 0 ? buf_a : buf_b;
       const int tile = ROLE == 0 ? tile_a : tile_b;
       tile_b = tile_a;
       tile_a = (tile_a + 1 == t_end) ? t_begin : tile_a + 1;
@@ -215,143 +206,141 @@
       if constexpr (AL) {
         if (ROLE == 0 && valid && tile == t_begin) al_ns2 = -kLog2e * al_slopes[b * al_sb + h0 + al_hh++];
       }
+      // = usp_row_tile_live, usp_row_tile_masked (usp_tile_range.h): called, either changes every stream
       const bool active = valid && ow < p.Sk && (!CAUSAL || (s0 + kTile - 1 + off >= ow)) &&
                           (!p.win_on || s0 <= ow + 31 - p.win_lo);
       const bool need_mask = (CAUSAL && (s0 + off < ow + 31)) || (p.win_on && s0 + kTile - 1 > ow - p.win_lo);
 
       if (active) {
-        {
-          const int buf = buf_of_my;
-          USP_LDS const char* x1 = smem + buf * BUFB;            // Q tile
-          USP_LDS const char* x2 = x1 + TILEB;                   // dO tile
-          USP_LDS const char* xs = ROLE == 0 ? x1 : x2;          // row-read operand of the S / dP chain
-          USP_LDS const char* xg = ROLE == 0 ? x2 : x1;          // transpose-read operand of the gradient
-          USP_LDS const char* stat = x1 + 2 * TILEB + (ROLE == 0 ? 0 : 4 * kTile);
-          USP_LDS char* pslot = pex + (my_it & 1) * PSLOT;
-          f32x16 sc[2];                                          // S (role A) / dP (role B) of the two halves
-          u32x4 pk[2][2];                                        // packed P (A) / dS (B): B operand of the gradient
-          u32x4 pin[2][2];                                       // role B: P received from A
-          f32x4 st4;
-          f32x4 stq[4];
-          float pg_prev = 0.f;                                   // softcap, role A: P (1 - t^2) of the previous element
-          u32x4 pkg;                                             // ... packed: the k-step handed to B                                          // row statistics of one half, fetched ahead of use
-          // ALiBi: row + diag - key of register 0 of half 0 (query row of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
-          [[maybe_unused]] const int al_d0 = s0 + 4 * hi + al_diag - orow;
-          auto load_stat = [&](int h, int j) {
-            stq[j] = *(USP_LDS const f32x4*)(stat + (32 * h + 4 * hi) * 4 + 32 * j);
-          };
-          auto load_stats = [&](int h) {
+        USP_LDS const char* q_lds = smem + (ROLE == 0 ? buf_a : buf_b) * BUFB;   // Q tile
+        USP_LDS const char* do_lds = q_lds + TILEB;            // dO tile
+        USP_LDS const char* xs = ROLE == 0 ? q_lds : do_lds;   // row-read operand of the S / dP chain
+        USP_LDS const char* xg = ROLE == 0 ? do_lds : q_lds;   // transpose-read operand of the gradient
+        USP_LDS const char* stat = q_lds + 2 * TILEB + (ROLE == 0 ? 0 : 4 * kTile);
+        USP_LDS char* pslot = pex + (my_it & 1) * PSLOT;
+        f32x16 sc[2];                                          // S (role A) / dP (role B) of the two halves
+        u32x4 pk[2][2];                                        // packed P (A) / dS (B): B operand of the gradient
+        u32x4 pin[2][2];                                       // role B: P received from A
+        f32x4 st4;
+        f32x4 stq[4];                                          // row statistics of one half, fetched ahead of use
+        float pg_prev = 0.f;                                   // softcap, role A: P (1 - t^2) of the previous element
+        u32x4 pkg;                                             // ... packed: the k-step handed to B
+        // ALiBi: row + diag - key of register 0 of half 0 (query row of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
+        [[maybe_unused]] const int al_d0 = s0 + 4 * hi + al_diag - orow;
+        auto load_stat = [&](int h, int j) {
+          stq[j] = *(USP_LDS const f32x4*)(stat + (32 * h + 4 * hi) * 4 + 32 * j);
+        };
+        auto load_stats = [&](int h) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) load_stat(h, j);
-          };
+          for (int j = 0; j < 4; ++j) load_stat(h, j);
+        };
 
-          // element r of half h: role A: P = exp2(S*c - lse2); role B: dS = P * (dP - delta), where the dP chain
-          // STARTS from -delta (the MFMA's C operand = the row statistics tuple: one VALU per score less in the role
-          // that has the most of them)
-          auto elem = [&](int h, int r) {
-            if (ROLE == 0 && (r & 3) == 0) st4 = stq[r >> 2];
-            float val;
-            if (ROLE == 0) {
-              if constexpr (SC) {
-                const float x = sc[h][r];                         // raw score, -inf where masked
-                const float t = softcap_tanh(x, sc_k2);
-                val = fast_exp2(__builtin_fmaf(t, sc_cl2, -st4[r & 3]));
-                val = x == USP_NEG_INF ? 0.f : val;
-                const float pg = val * __builtin_fmaf(-t, t, 1.f);
-                if (r & 1) pkg[(r & 7) >> 1] = E::pack2(pg_prev, pg);
-                else pg_prev = pg;
-              } else if constexpr (AL) {                        // the bias goes into the exponent: P = exp2(S c + bias - lse2)
-                const int d = al_d0 + (32 * h + (r & 3) + 8 * (r >> 2));
-                val = fast_exp2(__builtin_fmaf(sc[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -st4[r & 3])));
-              } else {
-                val = fast_exp2(__builtin_fmaf(sc[h][r], c, -st4[r & 3]));
-              }
+        // element r of half h: role A: P = exp2(S*c - lse2); role B: dS = P * (dP - delta), where the dP chain
+        // STARTS from -delta (the MFMA's C operand = the row statistics tuple: one VALU per score less in the role
+        // that has the most of them)
+        auto elem = [&](int h, int r) {
+          if (ROLE == 0 && (r & 3) == 0) st4 = stq[r >> 2];
+          float val;
+          if (ROLE == 0) {
+            if constexpr (SC) {
+              const float x = sc[h][r];                         // raw score, -inf where masked
+              const float t = softcap_tanh(x, sc_k2);
+              val = fast_exp2(__builtin_fmaf(t, sc_cl2, -st4[r & 3]));
+              val = x == USP_NEG_INF ? 0.f : val;
+              const float pg = val * __builtin_fmaf(-t, t, 1.f);
+              if (r & 1) pkg[(r & 7) >> 1] = E::pack2(pg_prev, pg);
+              else pg_prev = pg;
+            } else if constexpr (AL) {                        // the bias goes into the exponent: P = exp2(S c + bias - lse2)
+              const int d = al_d0 + (32 * h + (r & 3) + 8 * (r >> 2));
+              val = fast_exp2(__builtin_fmaf(sc[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -st4[r & 3])));
             } else {
-              const uint32_t wd = pin[h][r >> 3][(r & 7) >> 1];
-              const float pr = (r & 1) ? E::hi(wd) : E::lo(wd);
-              val = pr * sc[h][r];
+              val = fast_exp2(__builtin_fmaf(sc[h][r], c, -st4[r & 3]));
             }
-            sc[h][r] = val;
-            if (r & 1) pk[h][r >> 3][(r & 7) >> 1] = E::pack2(sc[h][r - 1], sc[h][r]);
-            if (ROLE == 0 && (r & 7) == 7)                        // 8 elements done: hand one k-step of P to B
-              *(USP_LDS u32x4*)(pslot + (2 * h + (r >> 3)) * 1024) = SC ? pkg : pk[h][r >> 3];
+          } else {
+            const uint32_t wd = pin[h][r >> 3][(r & 7) >> 1];
+            const float pr = (r & 1) ? E::hi(wd) : E::lo(wd);
+            val = pr * sc[h][r];
+          }
+          sc[h][r] = val;
+          if (r & 1) pk[h][r >> 3][(r & 7) >> 1] = E::pack2(sc[h][r - 1], sc[h][r]);
+          if (ROLE == 0 && (r & 7) == 7)                        // 8 elements done: hand one k-step of P to B
+            *(USP_LDS u32x4*)(pslot + (2 * h + (r >> 3)) * 1024) = SC ? pkg : pk[h][r >> 3];
+        };
+        auto chain_phase = [&](int h, int vh) {
+          u32x4 f[NKT];
+          auto rd = [&](int kt) {
+            f[kt] = *(USP_LDS const u32x4*)(xs + h * 32 * ROWB + rd_row + (((2 * kt) ^ rd_x) * 16));
           };
-          auto chain_phase = [&](int h, int vh) {
-            u32x4 f[NKT];
-            auto rd = [&](int kt) {
-              f[kt] = *(USP_LDS const u32x4*)(xs + h * 32 * ROWB + rd_row + (((2 * kt) ^ rd_x) * 16));
-            };
-            f32x16 c0 = zero16;
-            if (ROLE == 1) {                                     // -delta of this half's 16 rows: the chain's C operand
-              load_stats(h);
+          f32x16 c0 = zero16;
+          if (ROLE == 1) {                                     // -delta of this half's 16 rows: the chain's C operand
+            load_stats(h);
 #pragma unroll
-              for (int r = 0; r < 16; ++r) c0[r] = stq[r >> 2][r & 3];
-            }
+            for (int r = 0; r < 16; ++r) c0[r] = stq[r >> 2][r & 3];
+          }
 #pragma unroll
-            for (int kt = 0; kt < PF && kt < NKT; ++kt) rd(kt);
-            if (ROLE == 1) {                                     // fetch A's P of this half early
-              pin[h][0] = *(USP_LDS const u32x4*)(pslot + (2 * h) * 1024);
-              pin[h][1] = *(USP_LDS const u32x4*)(pslot + (2 * h + 1) * 1024);
+          for (int kt = 0; kt < PF && kt < NKT; ++kt) rd(kt);
+          if (ROLE == 1) {                                     // fetch A's P of this half early
+            pin[h][0] = *(USP_LDS const u32x4*)(pslot + (2 * h) * 1024);
+            pin[h][1] = *(USP_LDS const u32x4*)(pslot + (2 * h + 1) * 1024);
+          }
+          if (ROLE == 0 && vh >= 0) load_stats(vh);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int kt = 0; kt < NKT; ++kt) {
+            if (kt + PF < NKT) rd(kt + PF);
+            sc[h] = E::mfma(f[kt], rf[kt], kt == 0 ? c0 : sc[h]);
+            if (vh >= 0) {
+#pragma unroll
+              for (int e = kt * 16 / NKT; e < (kt + 1) * 16 / NKT; ++e) elem(vh, e);
             }
-            if (ROLE == 0 && vh >= 0) load_stats(vh);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt) {
-              if (kt + PF < NKT) rd(kt + PF);
-              sc[h] = E::mfma(f[kt], rf[kt], kt == 0 ? c0 : sc[h]);
-              if (vh >= 0) {
-#pragma unroll
-                for (int e = kt * 16 / NKT; e < (kt + 1) * 16 / NKT; ++e) elem(vh, e);
-              }
-              __builtin_amdgcn_sched_barrier(0);
-            }
+          }
+        };
+        auto grad_phase = [&](int h, int vh) {
+          u32x4 xa[NGR];
+          auto rd = [&](int i) {
+            const int k2 = i / NDJ, dj = i % NDJ;
+            USP_LDS const char* xb = xg + (2 * h + k2) * 16 * ROWB;
+            const u32x2 a0 = lds_read_tr16(xb + tr_addr[dj][0]);
+            const u32x2 a1 = lds_read_tr16(xb + tr_addr[dj][1]);
+            xa[i] = u32x4{a0[0], a0[1], a1[0], a1[1]};
           };
-          auto grad_phase = [&](int h, int vh) {
-            u32x4 xa[NGR];
-            auto rd = [&](int i) {
-              const int k2 = i / NDJ, dj = i % NDJ;
-              USP_LDS const char* xb = xg + (2 * h + k2) * 16 * ROWB;
-              const u32x2 a0 = lds_read_tr16(xb + tr_addr[dj][0]);
-              const u32x2 a1 = lds_read_tr16(xb + tr_addr[dj][1]);
-              xa[i] = u32x4{a0[0], a0[1], a1[0], a1[1]};
-            };
 #pragma unroll
-            for (int i = 0; i < PF && i < NGR; ++i) rd(i);
-            if (ROLE == 0 && vh >= 0) load_stats(vh);
+          for (int i = 0; i < PF && i < NGR; ++i) rd(i);
+          if (ROLE == 0 && vh >= 0) load_stats(vh);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < NGR; ++i) {
+            if (i + PF < NGR) rd(i + PF);
+            acc[i % NDJ] = E::mfma(xa[i], pk[h][i / NDJ], acc[i % NDJ]);
+            if (vh >= 0) {
+#pragma unroll
+              for (int e = i * 16 / NGR; e < (i + 1) * 16 / NGR; ++e) elem(vh, e);
+            }
             __builtin_amdgcn_sched_barrier(0);
+          }
+        };
+        auto apply_mask = [&](int h) {                         // role A only: query row i sees key j iff j <= i + off
+          if (CAUSAL) {
+            const int d = orow - off - s0 - 4 * hi;            // one VGPR; thresholds are inline constants
 #pragma unroll
-            for (int i = 0; i < NGR; ++i) {
-              if (i + PF < NGR) rd(i + PF);
-              acc[i % NDJ] = E::mfma(xa[i], pk[h][i / NDJ], acc[i % NDJ]);
-              if (vh >= 0) {
+            for (int r = 0; r < 16; ++r)
+              if (d > 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
+          }
+          if (p.win_on) {                                      // ... and only if j >= i + win_lo
+            const int dl = orow - p.win_lo - s0 - 4 * hi;
 #pragma unroll
-                for (int e = i * 16 / NGR; e < (i + 1) * 16 / NGR; ++e) elem(vh, e);
-              }
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          };
-          auto apply_mask = [&](int h) {                         // role A only: query row i sees key j iff j <= i + off
-            if (CAUSAL) {
-              const int d = orow - off - s0 - 4 * hi;            // one VGPR; thresholds are inline constants
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if (d > 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
-            }
-            if (p.win_on) {                                      // ... and only if j >= i + win_lo
-              const int dl = orow - p.win_lo - s0 - 4 * hi;
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if (dl < 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
-            }
-          };
+            for (int r = 0; r < 16; ++r)
+              if (dl < 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
+          }
+        };
 
-          chain_phase(0, -1);
-          if (ROLE == 0 && need_mask) apply_mask(0);
-          chain_phase(1, 0);
-          if (ROLE == 0 && need_mask) apply_mask(1);
-          grad_phase(0, 1);
-          grad_phase(1, -1);
-        }
+        chain_phase(0, -1);
+        if (ROLE == 0 && need_mask) apply_mask(0);
+        chain_phase(1, 0);
+        if (ROLE == 0 && need_mask) apply_mask(1);
+        grad_phase(0, 1);
+        grad_phase(1, -1);
       }
 
       if (prefetch) stage_stats(buf_n);
@@ -360,7 +349,6 @@
       dma_drain();            // this wave's DMA pieces of the staged tile have landed (usp_common.hpp)
       __syncthreads();
     }
-
   };
   if (role == 0) stream(std::integral_constant<int, 0>{});
   else stream(std::integral_constant<int, 1>{});

@@ -6,9 +6,9 @@
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
-  constexpr int OWN = (NT / 64) * 32;           // rows owned by the workgroup (256 q rows / 128 keys)
+  constexpr int OWN = (NT / 64) * 32;           // query rows of the workgroup
   constexpr int ROWB = D * 2;
-  constexpr int TILEB = kTile * ROWB;           // one streamed matrix tile
+  constexpr int TILEB = kTile * ROWB;           // one K (or V) tile
   constexpr int BUFB = 2 * TILEB;
   constexpr int NKT = D / 16;
   constexpr int NDJ = D / 32;
@@ -35,68 +35,48 @@
   if (!p_in.sched) w = walk.dealt(w, p.nblk);
   const int blk_r = w % p.nblk;
   int rest = w / p.nblk;
-  int b, hkv, h0, blk, cut = 0;
-  
-    blk = CAUSAL ? (p.nblk - 1 - blk_r) : blk_r;          // late query blocks see most keys
-    if (p.ksplit > 1) { cut = rest % p.ksplit; rest /= p.ksplit; }
-    const int g = rest % p.G; rest /= p.G;
-    hkv = rest % p.Hkv; b = rest / p.Hkv;
-    h0 = hkv * p.G + g;
-  
+  const int blk = CAUSAL ? (p.nblk - 1 - blk_r) : blk_r;   // late query blocks see most keys
+  int cut = 0;
+  if (p.ksplit > 1) { cut = rest % p.ksplit; rest /= p.ksplit; }
+  const int g = rest % p.G; rest /= p.G;
+  const int hkv = rest % p.Hkv, b = rest / p.Hkv;
+  const int h0 = hkv * p.G + g;
   int64_t ws_row0;
   if (!bind_sequence(p, b, &ws_row0)) continue;
-  const int own0 = blk * OWN;                  // first owned row (query row / key)
+  const int own0 = blk * OWN;                  // first query row of the block
   if (p.seq_q != nullptr && own0 >= (p.Sq)) continue;   // past the end of its sequence
   const int off = p.causal_off;
-  const int ow = own0 + wave * 32;             // first row owned by this wave
+  const int ow = own0 + wave * 32;             // first row of this wave
   const int orow = ow + l31;                   // this lane's row
-  const int own_len = p.Sq;
-  const int orow_c = orow < own_len ? orow : own_len - 1;
+  const int orow_c = orow < p.Sq ? orow : p.Sq - 1;
 
-  // ---- register-resident fragments R1, R2 (B operands: lane holds row[16t + 8hi .. +7]) -----------
-  u32x4 r1[NKT], r2[NKT];
+  // ---- register-resident Q and dO fragments (B operands: lane holds row[16t + 8hi .. +7]) ----------
+  u32x4 qf[NKT], dof[NKT];
   {
-    const char *p1, *p2;
-    
-      p1 = p.q + 2 * (b * p.q_sb + (int64_t)orow_c * p.q_ss + h0 * p.q_sh);
-      p2 = p.dout + 2 * (b * p.do_sb + (int64_t)orow_c * p.do_ss + h0 * p.do_sh);
-    
+    const char* qp = p.q + 2 * (b * p.q_sb + (int64_t)orow_c * p.q_ss + h0 * p.q_sh);
+    const char* dop = p.dout + 2 * (b * p.do_sb + (int64_t)orow_c * p.do_ss + h0 * p.do_sh);
 #pragma unroll
     for (int t = 0; t < NKT; ++t) {
-      r1[t] = *(const u32x4*)(p1 + 32 * t + 16 * hi);
-      r2[t] = *(const u32x4*)(p2 + 32 * t + 16 * hi);
+      qf[t] = *(const u32x4*)(qp + 32 * t + 16 * hi);
+      dof[t] = *(const u32x4*)(dop + 32 * t + 16 * hi);
     }
   }
   // lane-local row statistics
-  float lse2_l = 0.f, delta_l = 0.f;
-  
-    const float l_ = p.lse[b * p.lse_sb + h0 * p.lse_sh + orow_c];
-    lse2_l = (l_ == USP_NEG_INF) ? __builtin_inff() : l_ * kLog2e;
-    delta_l = p.delta[b * p.dl_sb + h0 * p.dl_sh + orow_c];
+  const float l_ = p.lse[b * p.lse_sb + h0 * p.lse_sh + orow_c];
+  const float lse2_l = (l_ == USP_NEG_INF) ? __builtin_inff() : l_ * kLog2e;
+  const float delta_l = p.delta[b * p.dl_sb + h0 * p.dl_sh + orow_c];
 
-  // ---- streamed range ---------------------------------------------------------------------------
-  // key tiles [t_begin, t_end)
-  const int str_len = p.Sk;
-  int t_begin = 0, t_end = (str_len + kTile - 1) / kTile;     // tiles per head
-  if (CAUSAL) {
-    
-      const int last = (own0 + OWN < p.Sq ? own0 + OWN : p.Sq) - 1;
-      const int kv_end = last + off + 1 < p.Sk ? last + off + 1 : p.Sk;
-      t_end = kv_end > 0 ? (kv_end + kTile - 1) / kTile : 0;
-    
-  }
-  if (p.win_on) {                 // key tiles left of the window of the block's first row: not streamed
-    const int first = own0 + p.win_lo;
-    t_begin = first > 0 ? first / kTile : 0;
-    if (t_begin > t_end) t_begin = t_end;
-  }
+  // ---- streamed range: key tiles [t_begin, t_end) (usp_tile_range.h) ---------------------------------
+  int t_end = (p.Sk + kTile - 1) / kTile;
+  if (CAUSAL) t_end = usp_tiles_holding(usp_rows_key_end(own0, OWN, p.Sq, p.Sk, 1, off), kTile);
+  // key tiles left of the window of the block's first row: not streamed
+  int t_begin = usp_first_key_tile(own0, p.win_on, p.win_lo, t_end, kTile);
   if (p.ksplit > 1) {             // this item's cut of the key tiles [t_begin, t_end): equal runs
-    const int per = (t_end - t_begin + p.ksplit - 1) / p.ksplit;
-    t_begin = t_begin + cut * per < t_end ? t_begin + cut * per : t_end;
-    t_end = t_begin + per < t_end ? t_begin + per : t_end;
+    const int per = (t_end - t_begin + p.ksplit - 1) / p.ksplit;   // = usp_run_length: called, every stream changes
+    t_begin = usp_run_begin(t_begin, t_end, per, cut);
+    t_end = usp_run_end(t_begin, t_end, per);
   }
-  const int per_head = t_end - t_begin;
-  const int n_iter = per_head;
+  const int n_iter = t_end - t_begin;
 
   // ---- staging: LDS-DMA (buffer_load ... lds), no staging registers, no ds_write ---------------------
   // One wave-instruction fills 1 KiB of LDS linearly (wave-uniform base + lane*16), i.e. 1024/ROWB
@@ -105,48 +85,43 @@
   // same row: coalescing is unaffected).  Rows past the end of the tensor read as 0 (descriptor
   // bounds); hipcc drains the DMA (vmcnt(0)) in front of the s_barrier that ends the iteration.
   constexpr int NW = NT / 64;                     // waves
-  constexpr int CHUNKS = TILEB / 1024;            // 1 KiB pieces per matrix tile
-  constexpr int CPW = (CHUNKS + NW - 1) / NW;     // pieces per wave per matrix
+  constexpr int CHUNKS = TILEB / 1024;            // 1 KiB pieces per K (or V) tile
+  constexpr int CPW = (CHUNKS + NW - 1) / NW;     // pieces per wave per tile
   constexpr int RPC = 1024 / ROWB;                // tile rows per piece
-  int dma_voff1[CPW], dma_voff2[CPW];
-  const int64_t ss1 = p.k_ss;
-  const int64_t ss2 = p.v_ss;
+  int k_voff[CPW], v_voff[CPW];
 #pragma unroll
   for (int i = 0; i < CPW; ++i) {
     const int cidx = wave + NW * i;
     const int r = cidx * RPC + lane / (D / 8);
     const int c8 = (lane % (D / 8)) ^ tile_swz<D>(r);
-    dma_voff1[i] = r * (int)ss1 * 2 + c8 * 16;
-    dma_voff2[i] = r * (int)ss2 * 2 + c8 * 16;
+    k_voff[i] = r * (int)p.k_ss * 2 + c8 * 16;
+    v_voff[i] = r * (int)p.v_ss * 2 + c8 * 16;
   }
   // Prefetch cursor: running 64-bit tile pointers / remaining-bytes counters, advanced by additions only.
-  decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0)) rs1, rs2;
+  decltype(__builtin_amdgcn_make_buffer_rsrc((void*)nullptr, 0, 0, 0)) k_rs, v_rs;
   int dma_buf = 0;
-  const int64_t tb1 = (int64_t)kTile * ss1 * 2, tb2 = (int64_t)kTile * ss2 * 2;   // bytes per tile step
-  const char *pf_p1 = nullptr, *pf_p2 = nullptr;
-  int64_t pf_rem1 = 0, pf_rem2 = 0;
-  {                                              // base the cursor on tile t_begin of the K / V rows of (b, hkv)
-    pf_p1 = p.k + 2 * (b * p.k_sb + hkv * p.k_sh) + t_begin * tb1;
-    pf_p2 = p.v + 2 * (b * p.v_sb + hkv * p.v_sh) + t_begin * tb2;
-    pf_rem1 = ((int64_t)(str_len - 1 - t_begin * kTile) * ss1 + D) * 2;
-    pf_rem2 = ((int64_t)(str_len - 1 - t_begin * kTile) * ss2 + D) * 2;
-  }
+  const int64_t k_step = (int64_t)kTile * p.k_ss * 2, v_step = (int64_t)kTile * p.v_ss * 2;   // bytes per tile step
+  // the cursor starts at tile t_begin of the K / V rows of (b, hkv)
+  const char* k_next = p.k + 2 * (b * p.k_sb + hkv * p.k_sh) + t_begin * k_step;
+  const char* v_next = p.v + 2 * (b * p.v_sb + hkv * p.v_sh) + t_begin * v_step;
+  int64_t k_rem = ((int64_t)(p.Sk - 1 - t_begin * kTile) * p.k_ss + D) * 2;
+  int64_t v_rem = ((int64_t)(p.Sk - 1 - t_begin * kTile) * p.v_ss + D) * 2;
   // build the descriptors for the cursor's tile, then advance the cursor
   auto stage_setup = [&](int buf) {
     auto clampu = [](int64_t r) { return (int)(uint32_t)(r < 0 ? 0 : (r > 0xffffffffLL ? 0xffffffffLL : r)); };
-    rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)pf_p1, 0, clampu(pf_rem1), 0x00020000);
-    rs2 = __builtin_amdgcn_make_buffer_rsrc((void*)pf_p2, 0, clampu(pf_rem2), 0x00020000);
+    k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)k_next, 0, clampu(k_rem), 0x00020000);
+    v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)v_next, 0, clampu(v_rem), 0x00020000);
     dma_buf = buf;
-    pf_p1 += tb1; pf_p2 += tb2; pf_rem1 -= tb1; pf_rem2 -= tb2;
+    k_next += k_step; v_next += v_step; k_rem -= k_step; v_rem -= v_step;
   };
-  // piece pi in [0, 2*CPW): matrix pi & 1, chunk wave + NW * (pi >> 1)
+  // piece pi in [0, 2*CPW): K (pi even) or V (pi odd), chunk wave + NW * (pi >> 1)
   auto stage_piece = [&](int pi) {
     const int i = pi >> 1;
     const int cidx = wave + NW * i;
     if (CHUNKS % NW == 0 || cidx < CHUNKS) {
-      USP_LDS char* d1 = smem + dma_buf * BUFB + cidx * 1024;
-      if ((pi & 1) == 0) lds_dma16(rs1, d1, dma_voff1[i]);
-      else lds_dma16(rs2, d1 + TILEB, dma_voff2[i]);
+      USP_LDS char* dst = smem + dma_buf * BUFB + cidx * 1024;
+      if ((pi & 1) == 0) lds_dma16(k_rs, dst, k_voff[i]);
+      else lds_dma16(v_rs, dst + TILEB, v_voff[i]);
     }
   };
   auto stage_all = [&]() {
@@ -175,12 +150,11 @@
   }
 
   // ---- accumulators -----------------------------------------------------------------------------
-  f32x16 acc1[NDJ];                      // dQ^T
+  f32x16 dq_acc[NDJ];                    // dQ^T
 #pragma unroll
   for (int dj = 0; dj < NDJ; ++dj)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { acc1[dj][r] = 0.f;  }
-  
+    for (int r = 0; r < 16; ++r) dq_acc[dj][r] = 0.f;
   const float c = p.scale_log2;
   // ALiBi: -slope * log2(e) of this item's (batch, head), read per item
   float al_ns2 = 0.f;
@@ -199,65 +173,57 @@
     const int buf = it & 1;
     const int tile = cur_tile;
     cur_tile = (cur_tile + 1 == t_end) ? t_begin : cur_tile + 1;
-    const int s0 = tile * kTile;                       // first streamed row of this tile
+    const int s0 = tile * kTile;                       // first key of this tile
     const bool prefetch = it + 1 < n_iter;
     if (prefetch) stage_setup(buf ^ 1);
 
-    bool active = true, need_mask = false;
-    
-      // streamed = keys, owned = query rows
-      int wave_kv_end = p.Sk;
-      if (CAUSAL) {
-        const int wl = (ow + 32 < p.Sq ? ow + 32 : p.Sq) - 1;
-        wave_kv_end = wl + off + 1 < p.Sk ? wl + off + 1 : p.Sk;
-      }
-      active = ow < p.Sq && s0 < wave_kv_end && (!p.win_on || s0 + kTile - 1 >= ow + p.win_lo);
-      need_mask = (s0 + kTile > p.Sk) || (CAUSAL && s0 + kTile - 1 > ow + off) || (p.win_on && s0 < ow + 31 + p.win_lo);
+    int wave_kv_end = p.Sk;
+    if (CAUSAL) wave_kv_end = usp_rows_key_end(ow, 32, p.Sq, p.Sk, 1, off);
+    // active = usp_key_tile_live with wave_end = 0 for a wave past Sq, need_mask = usp_key_tile_masked (usp_tile_range.h):
+    // called, either changes every stream
+    const bool active = ow < p.Sq && s0 < wave_kv_end && (!p.win_on || s0 + kTile - 1 >= ow + p.win_lo);
+    const bool need_mask = (s0 + kTile > p.Sk) || (CAUSAL && s0 + kTile - 1 > ow + off) || (p.win_on && s0 < ow + 31 + p.win_lo);
 
     if (active) {
       // Hand-pinned pipeline over the two 32-row halves h0, h1 of the tile (sched_barrier(0) fences;
       // hipcc otherwise emits MFMA clusters and VALU clusters):
       //   ST(h0) | ST(h1) || P,dS(h0) | GRAD(h0) || P,dS(h1) | GRAD(h1)
       // LDS operands are prefetched two MFMAs ahead; the first MFMA of a chain takes C = 0.
-      USP_LDS const char* x1 = smem + buf * BUFB;
-      USP_LDS const char* x2 = x1 + TILEB;
+      USP_LDS const char* k_lds = smem + buf * BUFB;  // K tile
+      USP_LDS const char* v_lds = k_lds + TILEB;      // V tile
       f32x16 sS[2], sT[2];
       u32x4 pk_ds[2][2];
       // ALiBi: row + diag - key of register 0 of half 0 (key of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
       [[maybe_unused]] const int al_d0 = orow + al_diag - s0 - 4 * hi;
 
       auto apply_mask = [&](int h) {
-        const int sr0 = s0 + 32 * h + 4 * hi;           // streamed row of register r: sr0 + 8(r>>2) + (r&3)
-        
-          int klim = p.Sk - 1;
-          if (CAUSAL) klim = orow + off < klim ? orow + off : klim;
-          const int klo = p.win_on ? orow + p.win_lo : -0x40000000;
+        const int k0 = s0 + 32 * h + 4 * hi;            // key of register r: k0 + 8(r>>2) + (r&3)
+        int klim = p.Sk - 1;
+        if (CAUSAL) klim = orow + off < klim ? orow + off : klim;
+        const int klo = p.win_on ? orow + p.win_lo : -0x40000000;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = sr0 + (r & 3) + 8 * (r >> 2);
-            if (key > klim || key < klo) sS[h][r] = USP_NEG_INF;
-          }
-        
+        for (int r = 0; r < 16; ++r) {
+          const int key = k0 + (r & 3) + 8 * (r >> 2);
+          if (key > klim || key < klo) sS[h][r] = USP_NEG_INF;
+        }
       };
       // P and dS of element r of half h (+ pack when a pair completes)
       auto elem = [&](int h, int r) {
         float pr, ds;
-        
-          if constexpr (SC) {
-            const float x = sS[h][r];                   // raw score, -inf where masked
-            const float t = softcap_tanh(x, sc_k2);
-            pr = fast_exp2(__builtin_fmaf(t, sc_cl2, -lse2_l));
-            pr = x == USP_NEG_INF ? 0.f : pr;
-            ds = pr * (sT[h][r] - delta_l) * __builtin_fmaf(-t, t, 1.f);
-          } else if constexpr (AL) {                    // the bias goes into the exponent: P = exp2(S c + bias - lse2)
-            const int d = al_d0 - (32 * h + (r & 3) + 8 * (r >> 2));
-            pr = fast_exp2(__builtin_fmaf(sS[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -lse2_l)));
-            ds = pr * (sT[h][r] - delta_l);
-          } else {
-            pr = fast_exp2(__builtin_fmaf(sS[h][r], c, -lse2_l));
-            ds = pr * (sT[h][r] - delta_l);
-          }
-        
+        if constexpr (SC) {
+          const float x = sS[h][r];                   // raw score, -inf where masked
+          const float t = softcap_tanh(x, sc_k2);
+          pr = fast_exp2(__builtin_fmaf(t, sc_cl2, -lse2_l));
+          pr = x == USP_NEG_INF ? 0.f : pr;
+          ds = pr * (sT[h][r] - delta_l) * __builtin_fmaf(-t, t, 1.f);
+        } else if constexpr (AL) {                    // the bias goes into the exponent: P = exp2(S c + bias - lse2)
+          const int d = al_d0 - (32 * h + (r & 3) + 8 * (r >> 2));
+          pr = fast_exp2(__builtin_fmaf(sS[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -lse2_l)));
+          ds = pr * (sT[h][r] - delta_l);
+        } else {
+          pr = fast_exp2(__builtin_fmaf(sS[h][r], c, -lse2_l));
+          ds = pr * (sT[h][r] - delta_l);
+        }
         sS[h][r] = pr;
         sT[h][r] = ds;
         if (r & 1) {
@@ -267,16 +233,15 @@
           uint32_t w = E::pack2(sT[h][r - 1], sT[h][r]);
           pin_here(w);
           pk_ds[h][r >> 3][(r & 7) >> 1] = w;
-          
         }
       };
       // S/T phase of half h; `vh` >= 0: interleave the element work of half vh
       auto st_phase = [&](int h, int vh) {
-        u32x4 f1[NKT], f2[NKT];
+        u32x4 kf[NKT], vf[NKT];
         auto rd = [&](int kt) {
           const int a = h * 32 * ROWB + rd_row + (((2 * kt) ^ rd_x) * 16);
-          f1[kt] = *(USP_LDS const u32x4*)(x1 + a);
-          f2[kt] = *(USP_LDS const u32x4*)(x2 + a);
+          kf[kt] = *(USP_LDS const u32x4*)(k_lds + a);
+          vf[kt] = *(USP_LDS const u32x4*)(v_lds + a);
         };
         rd(0);
         if (NKT > 1) rd(1);
@@ -286,9 +251,9 @@
           const int kt = sl >> 1;
           if ((sl & 1) == 0) {
             if (kt + 2 < NKT) rd(kt + 2);
-            sS[h] = E::mfma(f1[kt], r1[kt], kt == 0 ? zero16 : sS[h]);
+            sS[h] = E::mfma(kf[kt], qf[kt], kt == 0 ? zero16 : sS[h]);
           } else {
-            sT[h] = E::mfma(f2[kt], r2[kt], kt == 0 ? zero16 : sT[h]);
+            sT[h] = E::mfma(vf[kt], dof[kt], kt == 0 ? zero16 : sT[h]);
           }
           if (vh >= 0) {
 #pragma unroll
@@ -300,9 +265,9 @@
       // gradient phase of half h; `vh` >= 0: interleave the element work of half vh
       auto grad_phase = [&](int h, int vh) {
         u32x4 xa[NGR];
-        auto rd = [&](int i) {                           // i -> (k2, dj): K^T fragments of the tile in x1
+        auto rd = [&](int i) {                           // i -> (k2, dj): K^T fragments of the tile
           const int k2 = i / NDJ, dj = i % NDJ;
-          USP_LDS const char* xb = x1 + (2 * h + k2) * 16 * ROWB;
+          USP_LDS const char* xb = k_lds + (2 * h + k2) * 16 * ROWB;
           const u32x2 a0 = lds_read_tr16(xb + tr_addr[dj][0]);
           const u32x2 a1 = lds_read_tr16(xb + tr_addr[dj][1]);
           xa[i] = u32x4{a0[0], a0[1], a1[0], a1[1]};
@@ -314,7 +279,7 @@
         for (int i = 0; i < NGR; ++i) {
           if (i + 2 < NGR) rd(i + 2);
           const int k2 = i / NDJ, dj = i % NDJ;
-          acc1[dj] = E::mfma(xa[i], pk_ds[h][k2], acc1[dj]);
+          dq_acc[dj] = E::mfma(xa[i], pk_ds[h][k2], dq_acc[dj]);
           if (vh >= 0) {
 #pragma unroll
             for (int e = i * 16 / NGR; e < (i + 1) * 16 / NGR; ++e) elem(vh, e);
@@ -341,27 +306,26 @@
   }
 
   // ---- epilogue: fp32 store / accumulate, or final 16-bit store ---------------------------------------
-  if (orow < own_len) {
-    float* o1;
-    char* h1 = nullptr;                          // 16-bit final destination (row base), if any
-    int acc_f1;
+  if (orow < p.Sq) {
+    float* o32;
+    char* o16 = nullptr;                         // 16-bit final destination (row base), if any
+    int accf;
     if (p.ksplit > 1) {   // partial of this cut, combined (deterministically) by reduce_cuts_kernel
-      o1 = p.ws_dq + ((((int64_t)cut * p.B + b) * p.Sq + orow) * p.Hq + h0) * D; acc_f1 = 0;
+      o32 = p.ws_dq + ((((int64_t)cut * p.B + b) * p.Sq + orow) * p.Hq + h0) * D; accf = 0;
     } else {
-      o1 = p.dq + b * p.dq_sb + (int64_t)orow * p.dq_ss + h0 * p.dq_sh; acc_f1 = p.accum_dq;
-      if (p.dq16) h1 = p.dq16 + 2 * (b * p.dq16_sb + (int64_t)orow * p.dq16_ss + h0 * p.dq16_sh);
+      o32 = p.dq + b * p.dq_sb + (int64_t)orow * p.dq_ss + h0 * p.dq_sh; accf = p.accum_dq;
+      if (p.dq16) o16 = p.dq16 + 2 * (b * p.dq16_sb + (int64_t)orow * p.dq16_ss + h0 * p.dq16_sh);
     }
 #pragma unroll
     for (int dj = 0; dj < NDJ; ++dj)
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int d0 = 32 * dj + 8 * g4 + 4 * hi;
-        f32x4 v1 = {acc1[dj][4 * g4] * p.scale, acc1[dj][4 * g4 + 1] * p.scale,
-                    acc1[dj][4 * g4 + 2] * p.scale, acc1[dj][4 * g4 + 3] * p.scale};
-        if (acc_f1) v1 += *(const f32x4*)(o1 + d0);
-        if (h1) *(u32x2*)(h1 + 2 * d0) = u32x2{E::pack2(v1[0], v1[1]), E::pack2(v1[2], v1[3])};
-        else *(f32x4*)(o1 + d0) = v1;
-        
+        f32x4 v = {dq_acc[dj][4 * g4] * p.scale, dq_acc[dj][4 * g4 + 1] * p.scale,
+                   dq_acc[dj][4 * g4 + 2] * p.scale, dq_acc[dj][4 * g4 + 3] * p.scale};
+        if (accf) v += *(const f32x4*)(o32 + d0);
+        if (o16) *(u32x2*)(o16 + 2 * d0) = u32x2{E::pack2(v[0], v[1]), E::pack2(v[2], v[3])};
+        else *(f32x4*)(o32 + d0) = v;
       }
   }
   if (p_in.sched && p_in.interleave) break;   // one item per workgroup: leave room for other streams' kernels

@@ -85,20 +85,19 @@
     win_lo = p_in.win_lo;
     const int q0s = qt * kBM;
     int e = p.Sk;
-    if (CAUSAL) {
-      const int lim = (q0s + kBM < p.Sq ? q0s + kBM : p.Sq) + p.causal_off;
-      e = lim < e ? lim : e;
-    }
-    const int nt_all = e > 0 ? (e + kBN - 1) / kBN : 0;
+    if (CAUSAL) e = usp_rows_key_end(q0s, kBM, p.Sq, e, 1, p.causal_off);
+    const int nt_all = usp_tiles_holding(e, kBN);
+    // = usp_first_key_tile(q0s, win, win_lo, nt_all, kBN) (usp_tile_range.h): called, every split stream changes
     int t0 = 0;           // first tile any row of this query tile sees (its first row has the smallest left bound)
     if (win) {
       const int first = q0s + win_lo;
       t0 = first > 0 ? first / kBN : 0;
       t0 = t0 < nt_all ? t0 : nt_all;
     }
+    // kb, ke and the rebasing below = usp_prop_cut_keys_from and usp_cut_problem, which as struct-returning calls change the streams
     const int ntw = nt_all - t0;
-    const int kb = (t0 + ks * ntw / p_in.ksplit) * kBN;
-    int ke = (ks == p_in.ksplit - 1) ? p.Sk : (t0 + (ks + 1) * ntw / p_in.ksplit) * kBN;
+    const int kb = (t0 + usp_prop_cut_tile(ntw, p_in.ksplit, ks)) * kBN;
+    int ke = (ks == p_in.ksplit - 1) ? p.Sk : (t0 + usp_prop_cut_tile(ntw, p_in.ksplit, ks + 1)) * kBN;
     ke = ke < p.Sk ? ke : p.Sk;
     p.k += 2 * (int64_t)kb * p.k_ss;
     p.v += 2 * (int64_t)kb * p.v_ss;
@@ -124,14 +123,15 @@
   // ---- KV range -----------------------------------------------------------------------------
   int blk_kv_end = p.Sk, wave_kv_end = p.Sk;
   if (CAUSAL) {
-    const int blk_last = (q0 + kBM < p.Sq ? q0 + kBM : p.Sq) - 1;
+    // (wave_kv_end mirrors usp_rows_key_end: called here, the causal kernels' streams change)
     const int wav_last = (qw + 32 < p.Sq ? qw + 32 : p.Sq) - 1;
-    blk_kv_end = blk_last + off + 1 < p.Sk ? blk_last + off + 1 : p.Sk;
+    blk_kv_end = usp_rows_key_end(q0, kBM, p.Sq, p.Sk, 1, off);
     wave_kv_end = wav_last + off + 1 < p.Sk ? wav_last + off + 1 : p.Sk;
   }
   if (qw >= p.Sq) wave_kv_end = 0;
-  const int nt = blk_kv_end > 0 ? (blk_kv_end + kBN - 1) / kBN : 0;
-  // leading tiles that need neither a causal nor a ragged mask for this wave
+  const int nt = blk_kv_end > 0 ? (blk_kv_end + kBN - 1) / kBN : 0;     // = usp_tiles_holding: called, the softcap streams change
+  // leading tiles that need neither a causal nor a ragged mask for this wave (= usp_unmasked_tiles: called, the causal split
+  // streams change)
   int n_full = p.Sk / kBN;
   if (CAUSAL) {
     const int lim = qw + off + 1;                         // keys < lim are visible to EVERY row of the wave
@@ -149,10 +149,10 @@
   // the unrotated count are then cut by no bound for this wave and take the pipelined main loop as walk indices
   // [0, n_full - rot); the generic tail takes the diagonal tiles and then the `rot` leading ones.  Every wave walks the same
   // order (the barriers and the K/V buffers are per walk index), only n_full differs per wave, as ever.
+  // (rot and the n_full behind it = usp_window_rotation, which as one call changes every window stream.)
   int rot = 0;
   if constexpr (WIN) {
-    const int lcut = q0 + kBM - 1 + win_lo;
-    rot = lcut > 0 ? (lcut + kBN - 1) / kBN : 0;
+    rot = usp_tiles_holding(q0 + kBM - 1 + win_lo, kBN);
     if (rot >= nt) { rot = 0; n_full = 0; }               // the left bound cuts every tile
     else n_full = n_full > rot ? n_full - rot : 0;
   }
@@ -161,6 +161,7 @@
     else return j;
   };
   // does this wave have a visible key in the tile that starts at key kt0?  (WIN only: also skips tiles wholly left of the wave's window)
+  // = usp_key_tile_live (kt0 + kBN - 1 >= qw + win_lo), which changes the window streams when called
   auto tile_live = [&](int kt0) { return kt0 < wave_kv_end && kt0 + kBN > qw + win_lo; };
 
   // ---- Q fragments (B operand: lane holds Q[row][16t + 8hi .. +7]) ---------------------------
@@ -516,6 +517,7 @@
       live = kt0 < wave_kv_end;
     }
     if (live) {
+      // = usp_key_tile_masked (usp_tile_range.h): called, the streams change
       bool need_mask = (kt0 + kBN > p.Sk) || (CAUSAL && kt0 + kBN - 1 > qw + off);
       if constexpr (KSPLIT) need_mask = need_mask || (win && kt0 < qw + 31 + win_lo);
       if constexpr (SC) {

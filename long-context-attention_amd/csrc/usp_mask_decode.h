@@ -14,7 +14,7 @@
  *   - a bound that cuts every pair is SATURATED at the first value that does: causal_off = -Sq, win_lo = Sk.
  * What a kernel receives therefore lies in  -Sq <= causal_off <= Sk - 2  and  2 - Sq <= win_lo <= Sk: far inside
  * |x| <= 2^30 + Sq + Sk, the range inside which every sum the kernels form from the two stays in `int` for Sq + Sk < 2^29
- * (rows run to Sq + 255, keys to Sk + 127, kb <= Sk):
+ * (rows run to Sq + 255, keys to Sk + 127, kb <= Sk + 63):
  *   forward (usp_flash_fwd_body.inc, usp_flash_fwd64.hip):  min(q0 + 256, Sq) + causal_off,  q0 + win_lo,  causal_off - kb,
  *     win_lo - kb,  blk_last + off + 1,  wav_last + off + 1,  qw + off + 1,  q0 + 255 + win_lo + 63,  qw + win_lo,
  *     qw + 31 + win_lo,  row + win_lo,  row + off;
@@ -22,8 +22,11 @@
  *     orow + win_lo,  orow + off;
  *   dK/dV (usp_flash_bwd_dkdv_body.inc, usp_flash_bwd64.hip):  own0 - off,  own0 + 127 - win_lo,  s0 + off,  ow + 31 - win_lo,
  *     ow - win_lo,  orow - win_lo - s0 - 4 hi,  orow - off;
- *   the tile ranges of the 64-row kernels (usp_tile_range.h, swept on the host like this header):  last + off + 1,
- *     r0 + off + 1,  own0 - off,  ow + 63 - off.
+ *   the tile ranges (usp_tile_range.h, swept on the host like this header; the bodies above call it or mirror it line for
+ *     line):  last + off + 1,  r0 + off + 1,  own0 - off,  ow + wave_keys - 1 - off,  r0 + win_lo,  own0 + n_own - 1 - win_lo,
+ *     causal_off - begin,  win_lo - begin (begin <= Sk + 63: an empty cut may start on the tile boundary behind Sk),
+ *     blk_last + win_lo + 63,  qw + win_lo,  qw + wave_rows - 1 + win_lo,  qw + off,  s0 + 63 + off,  s0 + off,
+ *     ow + wave_keys - 1 - win_lo,  ow - win_lo.
  * (Before this header the host formed Sk - Sq - window_left and += mask_shift in `int`: window_left = INT_MAX with Sq > Sk
  * or a negative shift overflowed, the dK/dV kernel's `last` wrapped negative and it streamed no row.) */
 #ifndef USP_MASK_DECODE_H

@@ -2,11 +2,9 @@
 // MFMA forms that let ONE kernel keep accumulators and resident operands in the accumulator half of the register file (AGPRs)
 // while the score tiles live in arch VGPRs, the wait-state guards hipcc cannot place around asm MFMAs, LDS-DMA issued from
 // asm, the lane-constant offsets of the tile layout and the row epilogues.  The tile RANGES of an item are plain C, checked on
-// the host: usp_tile_range.h.
+// the host: usp_tile_range.h (usp_common.hpp includes it).
 #pragma once
 #include "usp_common.hpp"
-#define USP_RANGE_FN __device__ __forceinline__
-#include "usp_tile_range.h"
 
 // dev builds: where an item's time goes (s_memtime stamps, printed for a few waves).  One -D per kernel -- USP_F64_TIMING,
 // USP_B64_TIMING, USP_Q64_TIMING -- which that kernel's file turns into USP_TIMING in front of this header.
