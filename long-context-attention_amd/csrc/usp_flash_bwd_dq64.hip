@@ -15,11 +15,16 @@
 //   B1  S^T[0] = K Q0^T    | B2  S^T[1] = K Q1^T    | B3  dP^T[0] = V dO0^T  | B4  dP^T[1] = V dO1^T
 //   B5  dQ^T[0] += K^T dS^T[0]                      | B6  dQ^T[1] += K^T dS^T[1]
 // Every LDS fragment is read once and serves two MFMAs (the second block of a pair takes it from the registers): 16 + 16
-// row reads (ds_read_b128) and 32 transposed reads (ds_read_b64_tr_b16) per tile = 0.67 per MFMA.  The element streams
-//   X[qb]: P = exp2(S c - lse)   (B2 / B3)        Y[qb]: dS = P (dP - delta), packed to 16 bits   (B4 / B5-B6)
-// ride in the slots of the blocks named, the tile's 8 LDS-DMA pieces in B1.  2.25 VALU + 0.67 transcendental issues per
-// MFMA: the stream stays under the five issue slots a lone wave hides per MFMA (profiles/r04_ubench_issue.txt), which the
-// 64-MFMA tiles of the forward and of the dK/dV kernel do not.
+// row reads (ds_read_b128) and 32 transposed reads (ds_read_b64_tr_b16) per tile = 0.67 per MFMA.  The dP^T chains START FROM
+// -delta (an accumulator tuple per query block, built once per item, the C operand of a chain's first MFMA), so the element
+// streams are
+//   X[qb]: P = exp2(S c - lse)        Y[qb]: dS = P * chain, packed to 16 bits
+// 1.9 VALU + 0.67 transcendental issues per MFMA.  Where they ride is a table by GAP of the tile (q64_gap_x / q64_gap_y,
+// checked at compile time against the chains they read and the k-step of dQ that takes them), levelled so that no block
+// carries more than its MFMAs cover: X[0] over B2 and the head of B3, X[1] over B3 and B4, Y[0] over B4 and the head of B5,
+// Y[1] from the middle of B5 into B6.  The next tile's staging: the descriptors (dma_open, scalar work) under the LDS round
+// trip of B1's first fragments, the 8 LDS-DMA pieces in every other gap of B1 -- back to back they cost 0.8 % of the launch,
+// in B4 / B5 (a block before the drain) 0.8 % more on short key ranges (profiles/dq64_levelled.txt).
 // MFMAs are inline asm (usp_mfma64.hpp); tools/mfma_hazards.py checks the emitted stream.
 #ifdef USP_Q64_TIMING
 #define USP_TIMING
@@ -30,15 +35,67 @@
 
 namespace usp {
 
+#ifdef USP_TIMING
+USP_DEV uint32_t tm_stamp() {           // low half of the clock, fenced against the instruction scheduler
+  __builtin_amdgcn_sched_barrier(0);
+  const uint32_t t = (uint32_t)__builtin_amdgcn_s_memtime();
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#endif
+
 #ifndef USP_Q64_PF
 #define USP_Q64_PF 3
 #endif
 constexpr int kQ64_PF = USP_Q64_PF;     // LDS fragments are read this many fragments ahead of the first MFMA that takes them
-#ifndef USP_Q64_Y1
-#define USP_Q64_Y1 24
+// Where the next tile's staging rides, in gaps of the tile (0 .. 95; block b is gaps 16 b .. 16 b + 15): dma_open in gap
+// OPEN, piece n (K 0-3, V 4-7) in gap P0 + n * PS.
+#ifndef USP_Q64_DMA_OPEN
+#define USP_Q64_DMA_OPEN -1
 #endif
-constexpr int kQ64_Y1 = USP_Q64_Y1;    // gaps over which the last element stream (dS of query block 1) is spread, from B5 on
-                               // (neither moves the kernel by more than 0.5 %: profiles/r04_run26*.log)
+#ifndef USP_Q64_DMA_P0
+#define USP_Q64_DMA_P0 1
+#endif
+#ifndef USP_Q64_DMA_PS
+#define USP_Q64_DMA_PS 2
+#endif
+// The element streams by gap of the tile.  e = 32 qb + n counts a stream's 64 elements in the order the dQ k-steps take them.
+// X (12 issue cycles an element): XB2 elements ride in B2, XB4 in B4, the rest in B3, evenly over the block's 16 gaps.
+// Y (6): the first YB4 elements of Y[0] in B4, then two a gap from B5 on, Y[1] behind Y[0].
+#ifndef USP_Q64_XB2
+#define USP_Q64_XB2 28
+#endif
+#ifndef USP_Q64_XB4
+#define USP_Q64_XB4 20
+#endif
+#ifndef USP_Q64_YB4
+#define USP_Q64_YB4 16
+#endif
+constexpr int kQ64_XB2 = USP_Q64_XB2, kQ64_XB4 = USP_Q64_XB4, kQ64_XB3 = 64 - kQ64_XB2 - kQ64_XB4, kQ64_YB4 = USP_Q64_YB4;
+static_assert(kQ64_XB2 >= 1 && kQ64_XB3 >= 1 && kQ64_XB4 >= 0 && kQ64_YB4 >= 1 && kQ64_YB4 <= 32 && kQ64_YB4 % 2 == 0, "element streams");
+constexpr int q64_gap_x(int e) {
+  if (e < kQ64_XB2) return 16 + e * 16 / kQ64_XB2;
+  if (e < kQ64_XB2 + kQ64_XB3) return 32 + (e - kQ64_XB2) * 16 / kQ64_XB3;
+  return 48 + (e - kQ64_XB2 - kQ64_XB3) * 16 / (kQ64_XB4 > 0 ? kQ64_XB4 : 1);
+}
+constexpr int q64_gap_y(int e) {
+  if (e < kQ64_YB4) return 48 + e * 16 / kQ64_YB4;
+  return 64 + (e - kQ64_YB4) / 2;
+}
+constexpr bool q64_streams_ok() {
+  for (int e = 0; e < 64; ++e) {
+    const int qb = e >> 5, ks = (e & 31) >> 3;
+    if (q64_gap_x(e) < 16 + 16 * qb) return false;                        // S^T[qb] is complete behind block qb + 1
+    if (q64_gap_y(e) < 48 + 16 * qb || q64_gap_y(e) < q64_gap_x(e)) return false;      // dP^T[qb] complete, P there
+    if (q64_gap_y(e) >= 64 + 16 * qb + 4 * ks) return false;              // packed before the k-step's first MFMA
+    if (e && (q64_gap_x(e) < q64_gap_x(e - 1) || q64_gap_y(e) < q64_gap_y(e - 1))) return false;
+  }
+  return true;
+}
+static_assert(q64_streams_ok(), "dS of k-step ks must be packed before gap 16 + 4 ks of its dQ block, from complete chains");
+constexpr int kQ64_DmaOpen = USP_Q64_DMA_OPEN, kQ64_DmaP0 = USP_Q64_DMA_P0, kQ64_DmaPS = USP_Q64_DMA_PS;
+static_assert(kQ64_DmaOpen >= -1 && kQ64_DmaOpen < kQ64_DmaP0 && kQ64_DmaPS >= 1, "the descriptors are made before the first piece");
+static_assert(kQ64_DmaP0 + 7 * kQ64_DmaPS < 80, "every piece is issued a block (16 gaps) or more before the dma_drain");
 
 template <int DT, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams /* read through the kernarg segment */) {
@@ -150,6 +207,16 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
     else lds_dma16_asm(v_rs, lds_w + VOFF + dma_buf * TILEB, v_voff ^ (16 * i), i * v_step, i);
   };
 
+  // the dP^T chains start from -delta (one accumulator tuple per query block, all 16 values the lane's own row's), so the
+  // element stream is left with dS = P * chain.  Opaque: hipcc otherwise re-materialises 16 v_mov per chain and tile.
+  f32x16 cd[2];
+#pragma unroll
+  for (int qb = 0; qb < 2; ++qb) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cd[qb][r] = -dl[qb];
+    asm volatile("" : "+v"(cd[qb]));
+  }
+
   f32x16 dq[2][NDJ];                             // dQ^T: [query block][dim tile]
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb)
@@ -162,13 +229,16 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
   dma_drain();
   __syncthreads();
 
+  USP_TM(uint32_t tm_blk[8] = {0, 0, 0, 0, 0, 0, 0, 0};)     // plain tiles: cycles of B1 .. B6, of drain + barrier, and their number
   // one iteration = one key tile: [stage the next tile] [the six blocks] [publish].  The tile body is STRAIGHT-LINE code
   // (usp_flash_bwd64.hip: anything conditional around the asm MFMAs makes hipcc copy accumulators); a tile that needs the
   // causal / ragged mask runs in a loop instance of its own (MASK) with the mask applied to S^T behind B1 and B2.
   auto iter = [&](auto mask_c, int t, bool work) __attribute__((always_inline)) {
     constexpr bool MASK = decltype(mask_c)::value;
     const int par = t & 1;
+    USP_TM(uint32_t tm_s[8] = {0, 0, 0, 0, 0, 0, 0, 0};)
     if (work) {
+      USP_TM(tm_s[0] = tm_stamp();)
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
@@ -196,8 +266,22 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
       };
       auto Y = [&](int qb, int n) {
         const int ks = n >> 3, kb = ks >> 1, r = 8 * (ks & 1) + (n & 7);
-        bd[qb][kb][r] = (bd[qb][kb][r] - dl[qb]) * bs[qb][kb][r];
+        bd[qb][kb][r] = bd[qb][kb][r] * bs[qb][kb][r];
         if (r & 1) pk[qb][ks][(n & 7) >> 1] = E::pack2(bd[qb][kb][r - 1], bd[qb][kb][r]);
+      };
+      auto elems = [&](int g) {                  // the element work of gap g
+#pragma unroll
+        for (int e = 0; e < 64; ++e)
+          if (q64_gap_x(e) == g) X(e >> 5, e & 31);
+#pragma unroll
+        for (int e = 0; e < 64; ++e)
+          if (q64_gap_y(e) == g) Y(e >> 5, e & 31);
+      };
+      auto stage = [&](int g) {                  // the next tile's staging, by gap of the tile
+        if (g == kQ64_DmaOpen) dma_open(par ^ 1);
+#pragma unroll
+        for (int n = 0; n < 8; ++n)
+          if (g == kQ64_DmaP0 + n * kQ64_DmaPS) dma_piece(n);
       };
       auto mask = [&](int qb) {                  // key j is visible to query row i iff j <= min(i + off, Sk - 1)
         const int row = qw + 32 * qb + l31;
@@ -211,76 +295,81 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
           if (key + 32 > klim) bs[qb][1][r] = USP_NEG_INF;
         }
       };
-      // ---------------- B1: S^T[0], the K row fragments arrive; the next tile's DMA ----------------
+      // ---------------- B1: S^T[0], the K row fragments arrive; the next tile's staging ----------------
 #pragma unroll
       for (int f = 0; f < PF; ++f) rd_k(f);
+      if (kQ64_DmaOpen < 0) dma_open(par ^ 1);   // scalar work under the fragments' LDS round trip
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int kt = i >> 1, kb = i & 1;
         if (kt == 0) M::template s_first<MASK>(bs[0][kb], ka[i], qf[0][0]);
         else M::template s_next<MASK>(bs[0][kb], ka[i], qf[0][kt]);
-        if (i == 0) { __builtin_amdgcn_sched_barrier(0); dma_open(par ^ 1); }
+        if (i == 0) __builtin_amdgcn_sched_barrier(0);
         if (i + PF < 16) rd_k(i + PF);
-        if (i >= 1 && i <= 8) dma_piece(i - 1);
+        stage(i);
         __builtin_amdgcn_sched_barrier(0);
       }
+      USP_TM(tm_s[1] = tm_stamp();)
       if (MASK) { mfma_settle(bs[0]); mask(0); }
-      // ---------------- B2: S^T[1] (fragments from the registers) | X[0]; the first V fragments ----------------
+      // ---------------- B2: S^T[1] (fragments from the registers) | elements by the table; the first V fragments ----------------
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int kt = i >> 1, kb = i & 1;
         if (kt == 0) M::template s_first<MASK>(bs[1][kb], ka[i], qf[1][0]);
         else M::template s_next<MASK>(bs[1][kb], ka[i], qf[1][kt]);
         if (i == 0) __builtin_amdgcn_sched_barrier(0);     // the elements read B1's results: not in front of this MFMA
-        X(0, 2 * i); X(0, 2 * i + 1);
+        elems(16 + i);
         if (i >= 16 - PF) rd_v(i - (16 - PF));
+        stage(16 + i);
         __builtin_amdgcn_sched_barrier(0);
       }
+      USP_TM(tm_s[2] = tm_stamp();)
       if (MASK) { mfma_settle(bs[1]); mask(1); }
-      // ---------------- B3: dP^T[0], the V row fragments arrive | X[1] ----------------
+      // ---------------- B3: dP^T[0] from -delta, the V row fragments arrive | elements ----------------
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int kt = i >> 1, kb = i & 1;
-        if (kt == 0) M::template s_first<MASK>(bd[0][kb], va[i], df[0][0]);
+        if (kt == 0) M::template s_first_c<MASK>(bd[0][kb], va[i], df[0][0], cd[0]);
         else M::template s_next<MASK>(bd[0][kb], va[i], df[0][kt]);
         if (i == 0) __builtin_amdgcn_sched_barrier(0);
         if (i + PF < 16) rd_v(i + PF);
-        X(1, 2 * i); X(1, 2 * i + 1);
+        elems(32 + i);
+        stage(32 + i);
         __builtin_amdgcn_sched_barrier(0);
       }
-      // ---------------- B4: dP^T[1] | Y[0]; the first K^T fragments ----------------
+      USP_TM(tm_s[3] = tm_stamp();)
+      // ---------------- B4: dP^T[1] from -delta | elements; the first K^T fragments ----------------
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int kt = i >> 1, kb = i & 1;
-        if (kt == 0) M::template s_first<MASK>(bd[1][kb], va[i], df[1][0]);
+        if (kt == 0) M::template s_first_c<MASK>(bd[1][kb], va[i], df[1][0], cd[1]);
         else M::template s_next<MASK>(bd[1][kb], va[i], df[1][kt]);
         if (i == 0) __builtin_amdgcn_sched_barrier(0);
-        Y(0, 2 * i); Y(0, 2 * i + 1);
+        elems(48 + i);
         if (i >= 16 - PF) rd_x(i - (16 - PF));
+        stage(48 + i);
         __builtin_amdgcn_sched_barrier(0);
       }
-      // ---------------- B5: dQ^T[0], the K^T fragments arrive | B6: dQ^T[1] | Y[1] over the first Y1 gaps ----------------
-      constexpr int NY1 = kQ64_Y1;
-      static_assert(NY1 >= 16 && NY1 <= 28, "dS of k-step ks must be packed before gap 16 + 4 ks");
+      USP_TM(tm_s[4] = tm_stamp();)
+      // ---------------- B5: dQ^T[0], the K^T fragments arrive | B6: dQ^T[1] | the tail of Y[0], Y[1] ----------------
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         M::template o_acc<MASK>(dq[0][i % NDJ], xa[i], pk[0][i / NDJ]);
         if (i == 0) __builtin_amdgcn_sched_barrier(0);
         if (i + PF < 16) rd_x(i + PF);
-#pragma unroll
-        for (int n = i * 32 / NY1; n < (i + 1) * 32 / NY1; ++n) Y(1, n);
+        elems(64 + i);
+        stage(64 + i);
         __builtin_amdgcn_sched_barrier(0);
       }
+      USP_TM(tm_s[5] = tm_stamp();)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         M::template o_acc<MASK>(dq[1][i % NDJ], xa[i], pk[1][i / NDJ]);
-        if (16 + i < NY1) {
-#pragma unroll
-          for (int n = (16 + i) * 32 / NY1; n < (16 + i + 1) * 32 / NY1; ++n) Y(1, n);
-        }
+        elems(80 + i);
         __builtin_amdgcn_sched_barrier(0);
       }
+      USP_TM(tm_s[6] = tm_stamp();)
     } else {
       dma_open(par ^ 1);
 #pragma unroll
@@ -288,6 +377,11 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
     }
     dma_drain();            // this wave's pieces of the next tile have landed ...
     __syncthreads();        // ... and so have everybody else's; every wave is done with this tile's buffers
+    USP_TM(if (work && !MASK) {
+      tm_s[7] = tm_stamp();
+      _Pragma("unroll") for (int j = 0; j < 7; ++j) tm_blk[j] += tm_s[j + 1] - tm_s[j];
+      ++tm_blk[7];
+    })
   };
   const std::integral_constant<bool, false> plain;
   const std::integral_constant<bool, true> masked;
@@ -327,11 +421,13 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dq64_kernel(const BwdParams 
   }
   __syncthreads();          // the next item's prologue refills the tile buffers
 USP_TM(
+  const uint32_t tm_n = tm_blk[7] ? tm_blk[7] : 1;
   if (pass < 3 && lane == 0 && (blockIdx.x % 61) == 0)
-    printf("TQ wg %3d pass %d wave %d qt %2d tiles own %3d (plain %3d) wg %3d : prologue %6llu own tiles %8llu (%5llu / tile) idle %6llu epilogue %6llu\n",
+    printf("TQ wg %3d pass %d wave %d qt %2d tiles own %3d (plain %3d) wg %3d : prologue %6llu own tiles %8llu (%5llu / tile) idle %6llu epilogue %6llu | plain tile B1-B6, drain + barrier: %u %u %u %u %u %u %u\n",
            (int)blockIdx.x, pass, wave, qt, n_w, (int)tm_plain_n, nt, (unsigned long long)(tm_loop - tm_item),
            (unsigned long long)(tm_own - tm_loop), (unsigned long long)((tm_own - tm_loop) / (n_w > 0 ? n_w : 1)),
-           (unsigned long long)(tm_epi - tm_own), (unsigned long long)(__builtin_amdgcn_s_memtime() - tm_epi));
+           (unsigned long long)(tm_epi - tm_own), (unsigned long long)(__builtin_amdgcn_s_memtime() - tm_epi),
+           tm_blk[0] / tm_n, tm_blk[1] / tm_n, tm_blk[2] / tm_n, tm_blk[3] / tm_n, tm_blk[4] / tm_n, tm_blk[5] / tm_n, tm_blk[6] / tm_n);
 )
   }  // next item
 }
