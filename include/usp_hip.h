@@ -112,6 +112,9 @@ enum {
  * usp_flash_fwd_alibi / usp_flash_bwd_alibi (below), which take flash-attn's `alibi_slopes` beside the unchanged argument
  * blocks (ABI still v7: no struct, field or version changed). */
 #define USP_ATTN_ALIBI 256
+/* USP_ATTN_DROPOUT: a FEATURE bit like USP_ATTN_ALIBI: the library exports usp_flash_fwd_dropout / usp_flash_bwd_dropout (below),
+ * which take flash-attn's `dropout_p` and a seed beside the unchanged argument blocks (ABI still v7). */
+#define USP_ATTN_DROPOUT 512
 
 typedef struct usp_tensor {
   void* ptr;
@@ -284,6 +287,43 @@ int usp_flash_bwd(const usp_bwd_args* args, void* stream);
 int usp_flash_fwd_alibi(const usp_fwd_args* args, const float* alibi_slopes, int64_t alibi_stride_b, void* stream);
 int usp_flash_bwd_alibi(const usp_bwd_args* args, const float* alibi_slopes, int64_t alibi_stride_b, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Dropout: usp_flash_fwd / usp_flash_bwd with flash-attn's `dropout_p` (forwarded by the reference to every block call; its ring
+ * backward passes rng_state=None, yunchang/ring/ring_flash_attn.py:112-119, and so differentiates another mask than its forward
+ * applied).  Here the mask is a PURE FUNCTION OF GLOBAL POSITIONS (csrc/usp_dropout_rng.h), so forward and backward, any kernel,
+ * any tiling and any block of a ring regenerate the same one.  For drop probability p, 64-bit seed and the global position
+ * (row0, key0, head0) of the launch's row 0, key 0 and QUERY head 0:
+ *     t    = min(256, max(1, lrintf((1 - p) * 256)))          keep threshold; the realised keep probability is t / 256
+ *     i    = row0 + local query row    j = key0 + local key    h = head0 + local QUERY head    b = batch index   (all uint32)
+ *     w[4] = Philox4x32-10(counter = (i >> 2, j >> 2, h, b), key = (seed & 0xffffffff, seed >> 32))
+ *     keep(i, j) = ((w[i & 3] >> (8 * (j & 3))) & 0xff) < t
+ * (standard Philox constants: multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85, 10 rounds; one call
+ * gives the 16 keep bytes of a 4-row x 4-key patch: word = row, byte = key).  With P the softmax probabilities of the masked
+ * scores (causal / window / shift exactly as without dropout):
+ *     lse_i = logsumexp_j S_ij                              -- unchanged by dropout
+ *     out_i = (256/t) * sum_j keep_ij P_ij v_j
+ *     delta_i = rowsum(dout_i * out_i)                       -- usp_bwd_delta, unchanged, on the dropped `out`
+ *     dV_j  = (256/t) * sum_i keep_ij P_ij dO_i
+ *     dS_ij = P_ij * ((256/t) * keep_ij * (dO_i . v_j) - delta_i) * scale ;   dQ = dS K ;   dK = dS^T Q     (GQA sums as ever)
+ * The rescale is by the REALISED rate 256/t, not 1/(1-p).  `lse` is that of the un-dropped scores and `out` is linear in the
+ * kept terms, so the ring's LSE merge and the K-split merge are unchanged.  The mask is this library's own: it is not
+ * flash-attn's, which is tied to that kernel's tile layout.
+ *   - p_drop == 0, or a p_drop whose threshold is 256, is exactly usp_flash_fwd / usp_flash_bwd: the same kernels, bit-identical
+ *     results, the offsets ignored;
+ *   - a p_drop that is NaN, negative or >= 1, or a negative row0 / key0 / head0, is USP_EINVAL;
+ *   - row0 % 4 != 0, key0 % 4 != 0, row0 + Sq or key0 + Sk >= 2^31, USP_ATTN_SOFTCAP, a packed batch (seq_q / seq_k) and
+ *     USP_FORCE_ROW64 are USP_EUNSUPPORTED, nothing launched or written;
+ *   - every head dim runs on the two-waves-per-SIMD family (dropout instantiations of its kernels, as for softcap and ALiBi);
+ *     usp_last_launch_kinds() reports the wave8 / wave4 / split-merge / reduce bits that were launched.
+ * Everything else is as the argument block says (k_splits, dq_splits, dkdv_splits, dkdv_heads and the workspace functions,
+ * merge_in and the final rows, USP_LAUNCH_INTERLEAVE, USP_ATTN_WINDOW, USP_ATTN_SHIFT, USP_BWD_SKIP_*, GQA).  Dropout together with
+ * ALiBi has no entry point.  The seed is a launch argument: a captured graph replays the mask it was captured with.
+ * -------------------------------------------------------------------------------------------- */
+int usp_flash_fwd_dropout(const usp_fwd_args* args, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
+                          void* stream);
+int usp_flash_bwd_dropout(const usp_bwd_args* args, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
+                          void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -383,8 +423,8 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
                    float* sink, uint64_t* clocks, void* stream);
 
 int usp_abi_version(void);
-/* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI, the last one a
- * feature bit: the two *_alibi entry points exist).  Unknown flag bits are not rejected by
+/* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
+ * USP_ATTN_DROPOUT, the last two feature bits: the *_alibi / *_dropout entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

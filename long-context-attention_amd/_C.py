@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import struct
 import threading
 from typing import Optional
 
@@ -28,6 +29,7 @@ USP_BWD_SKIP_DKDV = 32         # ... only the dQ launch
 USP_ATTN_SOFTCAP = 64          # the softcap field is valid: scores are capped to softcap * tanh(S / softcap)
 USP_ATTN_SHIFT = 128           # the mask_shift field is valid: (Sk - Sq) + mask_shift places the diagonal of every mask bound
 USP_ATTN_ALIBI = 256           # feature bit of usp_attn_features(): usp_flash_fwd_alibi / usp_flash_bwd_alibi exist (not an args flag)
+USP_ATTN_DROPOUT = 512         # feature bit of usp_attn_features(): usp_flash_fwd_dropout / usp_flash_bwd_dropout exist (not an args flag)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -108,10 +110,12 @@ class UspBwdArgs(ctypes.Structure):
 
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
-           "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
+           "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
 # The two *_alibi entry points are the only exports load() does not insist on: they are looked up and prototyped on first use
 # (_alibi_entry), behind the feature bit, so a library built before them still loads and serves everything else.
 ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
+# ... and so are the two *_dropout entry points (_dropout_entry, USP_ATTN_DROPOUT)
+DROPOUT_EXPORTS = ("usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
 
 
 def lib_path() -> str:
@@ -130,7 +134,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -365,6 +369,60 @@ def _alibi_entry(name: str):
     return fn
 
 
+def dropout_value(dropout_p) -> Optional[float]:
+    """flash-attn's `dropout_p` -> the drop probability as a float, or None when it is off (None / 0).  NaN, a negative value
+    or one >= 1 raises ValueError.  (Pure argument check: the CPU orchestration tests call it without a library.)"""
+    if dropout_p is None:
+        return None
+    p = float(dropout_p)
+    if p == 0.0:
+        return None
+    if not (0.0 < p < 1.0):
+        raise ValueError(f"dropout_p must lie in [0, 1) (0 / None = off), got {dropout_p!r}")
+    return p
+
+
+def dropout_threshold(p: float) -> int:
+    """The keep threshold min(256, max(1, lrintf((1 - p) * 256))) of include/usp_hip.h, formed in float32 as the library does."""
+    f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]
+    return min(256, max(1, round(f32(f32(1.0 - f32(p)) * 256.0))))      # (round: half to even, like lrintf)
+
+
+def dropout_args(dropout):
+    """A block call's `dropout` keyword -> (p, seed, row0, key0, head0) as usp_flash_fwd_dropout takes them, or None when it is
+    off (None, or p = 0).  `dropout` = (p, seed, row0, key0, head0): drop probability, 64-bit seed and the global position of
+    the launch's row 0, key 0 and query head 0 -- the mask is a function of global (batch, head, row, key) alone
+    (include/usp_hip.h).  A p whose keep threshold is 256 (p < 1/512) drops nothing: it is off too, and like the C entry points
+    this function then does not look at the rest.  Otherwise negative numbers and a seed outside 64 bits raise ValueError."""
+    if dropout is None:
+        return None
+    p, seed, row0, key0, head0 = dropout
+    p = dropout_value(p)
+    if p is None or dropout_threshold(p) == 256:
+        return None
+    seed, row0, key0, head0 = int(seed), int(row0), int(key0), int(head0)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"dropout seed must fit 64 unsigned bits, got {seed}")
+    if min(row0, key0, head0) < 0 or max(row0, key0, head0) >= 1 << 31:
+        raise ValueError(f"dropout offsets (row0, key0, head0) must lie in [0, 2^31), got {(row0, key0, head0)}")
+    return p, seed, row0, key0, head0
+
+
+def _dropout_entry(name: str):
+    """The *_dropout entry point `name` (one of DROPOUT_EXPORTS), prototyped on first use; a library without the feature bit
+    (built before the entry points: it loads, they are not insisted on) is refused."""
+    L = load()
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_DROPOUT and hasattr(L, name)):
+        raise NotImplementedError(f"{_LIB_PATH} does not serve dropout_p (USP_ATTN_DROPOUT): rebuild it")
+    fn = getattr(L, name)
+    if fn.argtypes is None:
+        args = UspFwdArgs if name == "usp_flash_fwd_dropout" else UspBwdArgs
+        fn.argtypes = [ctypes.POINTER(args), ctypes.c_float, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+    return fn
+
+
 def _set_shift(a, shift: Optional[int]):
     """Set USP_ATTN_SHIFT + the field on an argument block (None = off); a library that does not report the bit would
     ignore it silently and compute another mask, so it is refused here."""
@@ -430,7 +488,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None):
+              alibi=None, dropout=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -441,7 +499,9 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     i + (Sk - Sq + shift) - left <= j <= i + (Sk - Sq + shift) + right -- the mask of one block of a ring (ring/window_blocks.py).
     A shifted launch gets no automatic K split (fwd_k_splits sizes cuts for a causal triangle).
     `alibi`: flash-attn's alibi_slopes, fp32 (Hq,) or (B, Hq) on q's device (alibi_value), None = off: the score of (row i,
-    key j) gets -slope * |i + (Sk - Sq + shift) - j| before the mask (usp_flash_fwd_alibi; not with softcap or family="row64")."""
+    key j) gets -slope * |i + (Sk - Sq + shift) - j| before the mask (usp_flash_fwd_alibi; not with softcap or family="row64").
+    `dropout`: (p, seed, row0, key0, head0) (dropout_args), None = off: the probabilities are dropped by the position-keyed
+    mask of include/usp_hip.h and the kept ones rescaled (usp_flash_fwd_dropout; not with softcap, alibi or family="row64")."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
     cap = softcap_value(softcap)
@@ -464,6 +524,12 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
             ws = _FWD_WS[key] = torch.empty(need, dtype=torch.uint8, device=q.device)
         a.workspace = ws.data_ptr()
     al = alibi_value(alibi, B, Hq, q.device)
+    dr = dropout_args(dropout)
+    if dr is not None:
+        if al is not None:
+            raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
+        _check(_dropout_entry("usp_flash_fwd_dropout")(ctypes.byref(a), *dr, _stream()), "usp_flash_fwd_dropout")
+        return
     if al is not None:
         _check(_alibi_entry("usp_flash_fwd_alibi")(ctypes.byref(a), ctypes.c_void_p(al[0].data_ptr()), al[1], _stream()),
                "usp_flash_fwd_alibi")
@@ -586,7 +652,7 @@ def bwd_delta(dout, out, delta):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None, alibi=None):
+              softcap=None, shift=None, alibi=None, dropout=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
@@ -594,7 +660,8 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     just that launch of the two (ABI v6: USP_BWD_SKIP_DQ / USP_BWD_SKIP_DKDV).  `dkdv_heads` (ABI v7): query heads of a KV
     group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`, `shift`: as flash_fwd (a
     shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle).  `alibi`: as flash_fwd
-    (usp_flash_bwd_alibi)."""
+    (usp_flash_bwd_alibi).  `dropout`: as flash_fwd (usp_flash_bwd_dropout): the same tuple regenerates the forward's mask;
+    `delta` is that of the dropped `out`."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -634,6 +701,12 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)   # caching allocator; stream-ordered
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
     al = alibi_value(alibi, B, Hq, q.device)
+    dr = dropout_args(dropout)
+    if dr is not None:
+        if al is not None:
+            raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
+        _check(_dropout_entry("usp_flash_bwd_dropout")(ctypes.byref(a), *dr, _stream()), "usp_flash_bwd_dropout")
+        return
     if al is not None:
         _check(_alibi_entry("usp_flash_bwd_alibi")(ctypes.byref(a), ctypes.c_void_p(al[0].data_ptr()), al[1], _stream()),
                "usp_flash_bwd_alibi")

@@ -2,6 +2,7 @@
 // usp_flash_bwd64.hip: 4 waves, one per SIMD, 64 owned rows per wave).
 #pragma once
 #include "usp_common.hpp"
+#include "usp_dropout_rng.h"
 
 namespace usp {
 
@@ -63,6 +64,9 @@ struct BwdAlibi {
   int al_diag;                          // Sk - Sq + mask_shift: the bias of (row i, key j) is -slope * |i + al_diag - j|
 };
 struct BwdArgsAL : BwdParams, BwdAlibi {};
+// Dropout (usp_flash_bwd_dropout): kernel arguments of the dropout instantiations only (usp_flash_bwd_dropout.hip); `Dropout`
+// is the forward's block (usp_dropout_rng.h).
+struct BwdArgsDR : BwdParams, Dropout {};
 
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the
@@ -109,5 +113,8 @@ bool dq64_serves(const BwdParams& p);
 // `grid` workgroups of 512 threads with `lds` bytes; `p` is complete.  USP_OK / USP_ELAUNCH / USP_EUNSUPPORTED.
 int launch_dkdv_alibi(const BwdArgsAL& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 int launch_dq_alibi(const BwdArgsAL& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+// The dropout backward launches (usp_flash_bwd_dropout.hip), likewise.
+int launch_dkdv_dropout(const BwdArgsDR& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+int launch_dq_dropout(const BwdArgsDR& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

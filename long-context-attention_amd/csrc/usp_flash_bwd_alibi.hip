@@ -16,6 +16,8 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_alibi_kernel(const BwdArgsAL
   const float* const al_slopes = p_in.al_slopes;
   const int64_t al_sb = p_in.al_sb;
   const int al_diag = p_in.al_diag;
+  constexpr bool DR = false;
+  constexpr Dropout dr{};
 #include "usp_flash_bwd_dq_body.inc"
 }
 
@@ -26,6 +28,8 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_alibi_kernel(const BwdA
   const float* const al_slopes = p_in.al_slopes;
   const int64_t al_sb = p_in.al_sb;
   const int al_diag = p_in.al_diag;
+  constexpr bool DR = false;
+  constexpr Dropout dr{};
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

@@ -1,8 +1,12 @@
 // Body of flash_bwd_dkdv_kernel / flash_bwd_dkdv_softcap_kernel (usp_flash_bwd.hip): the dK/dV launch, role-specialised waves.
 // Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones.  The including
-// kernel defines `p_in`, SC / AL, sc_cl2 / sc_k2 and al_slopes / al_sb / al_diag.
+// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones, the dropout kernels
+// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones.  The including kernel defines `p_in`, SC / AL / DR, sc_cl2 / sc_k2,
+// al_slopes / al_sb / al_diag and `dr` (usp_dropout_rng.h: Dropout).
+// Dropout: role A forms the un-dropped P, uses P o keep for its dV MFMAs and hands B the un-dropped P with the keep decision in
+// the sign bit (P >= 0: set = dropped; no extra LDS); role B starts its dP chain from -delta t/256 and forms
+// |P| (kept ? chain : -delta t/256); 256/t goes into the epilogue's factor of both outputs.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NW = 8, OWN = 128;
@@ -192,6 +196,9 @@
     // so it is read again at the first tile of each
     [[maybe_unused]] float al_ns2 = 0.f;
     [[maybe_unused]] int al_hh = 0;
+    // dropout, role A: the query head being streamed (the mask's counter holds the QUERY head), counted like al_hh
+    [[maybe_unused]] uint32_t dr_h = 0;
+    [[maybe_unused]] int dr_hh = 0;
     for (int it = 0; it <= n_iter; ++it) {
       const bool prefetch = it + 1 < n_iter;
       const int buf_n = buf_a + 1 == NBUF ? 0 : buf_a + 1;      // (it + 1) % NBUF
@@ -207,6 +214,9 @@
         if (ROLE == 0 && valid && tile == t_begin) al_ns2 = -kLog2e * al_slopes[b * al_sb + h0 + al_hh++];
       }
       // = usp_row_tile_live, usp_row_tile_masked (usp_tile_range.h): called, either changes every stream
+      if constexpr (DR) {
+        if (ROLE == 0 && valid && tile == t_begin) dr_h = dr.head0 + (uint32_t)(h0 + dr_hh++);
+      }
       const bool active = valid && ow < p.Sk && (!CAUSAL || (s0 + kTile - 1 + off >= ow)) &&
                           (!p.win_on || s0 <= ow + 31 - p.win_lo);
       const bool need_mask = (CAUSAL && (s0 + off < ow + 31)) || (p.win_on && s0 + kTile - 1 > ow - p.win_lo);
@@ -227,6 +237,14 @@
         u32x4 pkg;                                             // ... packed: the k-step handed to B
         // ALiBi: row + diag - key of register 0 of half 0 (query row of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
         [[maybe_unused]] const int al_d0 = s0 + 4 * hi + al_diag - orow;
+        // dropout, role A: the keep words of this lane's key against the tile's 64 rows (usp_dropout_rng.h); `active` is
+        // wave-uniform
+        [[maybe_unused]] uint32_t kw[8];
+        if constexpr (DR) {
+          if (ROLE == 0)
+            usp_dropout_tile_words<false>(dr.k0, dr.k1, (uint32_t)b, dr_h, (dr.key0 + (uint32_t)orow) >> 2,
+                                          ((dr.row0 + (uint32_t)s0) >> 2) + (uint32_t)hi, lane, kw);
+        }
         auto load_stat = [&](int h, int j) {
           stq[j] = *(USP_LDS const f32x4*)(stat + (32 * h + 4 * hi) * 4 + 32 * j);
         };
@@ -253,18 +271,32 @@
             } else if constexpr (AL) {                        // the bias goes into the exponent: P = exp2(S c + bias - lse2)
               const int d = al_d0 + (32 * h + (r & 3) + 8 * (r >> 2));
               val = fast_exp2(__builtin_fmaf(sc[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -st4[r & 3])));
+            } else if constexpr (DR) {
+              const float pu = fast_exp2(__builtin_fmaf(sc[h][r], c, -st4[r & 3]));   // the un-dropped P
+              const bool kept = usp_dropout_keep(kw[4 * h + (r >> 2)], r & 3, dr.t);
+              val = kept ? pu : 0.f;                             // dV takes P o keep
+              const float ph = kept ? pu : -pu;                  // B takes P, sign bit = dropped
+              if (r & 1) pkg[(r & 7) >> 1] = E::pack2(pg_prev, ph);
+              else pg_prev = ph;
             } else {
               val = fast_exp2(__builtin_fmaf(sc[h][r], c, -st4[r & 3]));
             }
           } else {
             const uint32_t wd = pin[h][r >> 3][(r & 7) >> 1];
             const float pr = (r & 1) ? E::hi(wd) : E::lo(wd);
-            val = pr * sc[h][r];
+            if constexpr (DR) {
+              // -delta t/256 of the element's row again (the chain's start; the tuple of four rows is re-read from the
+              // statistics in LDS rather than held in 32 registers across the phases)
+              if ((r & 3) == 0) st4 = *(USP_LDS const f32x4*)(stat + (32 * h + 4 * hi) * 4 + 32 * (r >> 2)) * dr.irs;
+              val = __builtin_fabsf(pr) * (__builtin_signbit(pr) ? st4[r & 3] : sc[h][r]);
+            } else {
+              val = pr * sc[h][r];
+            }
           }
           sc[h][r] = val;
           if (r & 1) pk[h][r >> 3][(r & 7) >> 1] = E::pack2(sc[h][r - 1], sc[h][r]);
           if (ROLE == 0 && (r & 7) == 7)                        // 8 elements done: hand one k-step of P to B
-            *(USP_LDS u32x4*)(pslot + (2 * h + (r >> 3)) * 1024) = SC ? pkg : pk[h][r >> 3];
+            *(USP_LDS u32x4*)(pslot + (2 * h + (r >> 3)) * 1024) = (SC || DR) ? pkg : pk[h][r >> 3];
         };
         auto chain_phase = [&](int h, int vh) {
           u32x4 f[NKT];
@@ -275,7 +307,7 @@
           if (ROLE == 1) {                                     // -delta of this half's 16 rows: the chain's C operand
             load_stats(h);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) c0[r] = stq[r >> 2][r & 3];
+            for (int r = 0; r < 16; ++r) c0[r] = DR ? stq[r >> 2][r & 3] * dr.irs : stq[r >> 2][r & 3];
           }
 #pragma unroll
           for (int kt = 0; kt < PF && kt < NKT; ++kt) rd(kt);
@@ -358,7 +390,8 @@
     float* o32;
     char* o16 = nullptr;
     int accf;
-    const float mul = role == 0 ? 1.f : p.scale;
+    const float mul_plain = role == 0 ? 1.f : p.scale;
+    const float mul = DR ? mul_plain * dr.rs : mul_plain;   // dropout: 256 / t of both outputs, in fp32
     if (p.split) {
       const int64_t wo = (((int64_t)(g * p.qsplit + cut) * p.ws_rows + ws_row0 + orow) * p.Hkv + hkv) * D;
       o32 = (role == 0 ? p.ws_dv : p.ws_dk) + wo; accf = 0;

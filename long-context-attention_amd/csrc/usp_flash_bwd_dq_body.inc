@@ -1,8 +1,9 @@
 // Body of flash_bwd_kernel / flash_bwd_softcap_kernel (usp_flash_bwd.hip): the dQ launch, 8 waves x 32 query rows.
 // Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones.  The including
-// kernel defines `p_in`, SC / AL, sc_cl2 / sc_k2 and al_slopes / al_sb / al_diag.
+// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones, the dropout kernels
+// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones.  The including kernel defines `p_in`, SC / AL / DR, sc_cl2 / sc_k2,
+// al_slopes / al_sb / al_diag and `dr` (usp_dropout_rng.h: Dropout).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
@@ -195,6 +196,11 @@
       u32x4 pk_ds[2][2];
       // ALiBi: row + diag - key of register 0 of half 0 (key of register r of half h: s0 + 32 h + 4 hi + (r & 3) + 8 (r >> 2))
       [[maybe_unused]] const int al_d0 = orow + al_diag - s0 - 4 * hi;
+      // dropout: the keep words of this lane's row against the tile's 64 keys (usp_dropout_rng.h); `active` is wave-uniform
+      [[maybe_unused]] uint32_t kw[8];
+      if constexpr (DR)
+        usp_dropout_tile_words<true>(dr.k0, dr.k1, (uint32_t)b, dr.head0 + (uint32_t)h0, (dr.row0 + (uint32_t)orow) >> 2,
+                                     ((dr.key0 + (uint32_t)s0) >> 2) + (uint32_t)hi, lane, kw);
 
       auto apply_mask = [&](int h) {
         const int k0 = s0 + 32 * h + 4 * hi;            // key of register r: k0 + 8(r>>2) + (r&3)
@@ -220,6 +226,10 @@
           const int d = al_d0 - (32 * h + (r & 3) + 8 * (r >> 2));
           pr = fast_exp2(__builtin_fmaf(sS[h][r], c, __builtin_fmaf(al_ns2, (float)(d < 0 ? -d : d), -lse2_l)));
           ds = pr * (sT[h][r] - delta_l);
+        } else if constexpr (DR) {                    // dS = P (256/t keep dP - delta): delta is that of the dropped `out`
+          pr = fast_exp2(__builtin_fmaf(sS[h][r], c, -lse2_l));
+          const float nd = -delta_l;
+          ds = pr * (usp_dropout_keep(kw[4 * h + (r >> 2)], r & 3, dr.t) ? __builtin_fmaf(dr.rs, sT[h][r], nd) : nd);
         } else {
           pr = fast_exp2(__builtin_fmaf(sS[h][r], c, -lse2_l));
           ds = pr * (sT[h][r] - delta_l);

@@ -16,6 +16,8 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_alibi_kernel(const F
   const float* const al_slopes = p_in.al_slopes;
   const int64_t al_sb = p_in.al_sb;
   const int al_diag = p_in.al_diag;
+  constexpr bool DR = false;
+  constexpr Dropout dr{};
 #include "usp_flash_fwd_body.inc"
 }
 

@@ -2,8 +2,8 @@
 // Included as the body of the kernel templates in usp_flash_fwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
 // the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones, the ALiBi kernel (usp_flash_fwd_alibi.hip) the
-// `if constexpr (AL)` ones.  The including kernel defines `p_in`, KSPLIT / SC / WIN / AL, sc_cl2 / sc_k2 and al_slopes / al_sb /
-// al_diag.
+// `if constexpr (AL)` ones, the dropout kernel (usp_flash_fwd_dropout.hip) the `if constexpr (DR)` ones.  The including kernel
+// defines `p_in`, KSPLIT / SC / WIN / AL / DR, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag and `dr` (usp_dropout_rng.h: Dropout).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int kThreads = 64 * NWAVES;
@@ -78,6 +78,7 @@
   // partial (fp32) and its LSE to the workspace through the ordinary not-final epilogue; split_merge_kernel combines
   // them (and the running result, and the 16-bit emission) afterwards.
   int al_dg = 0;          // ALiBi: the bias diagonal in this item's key numbering (rebased with the K cut below)
+  [[maybe_unused]] uint32_t dr_kg = 0;   // dropout: global position of this item's key 0 (rebased with the K cut below)
   bool win = false;       // left window bound active (split instantiation only)
   int win_lo = 0;         // row i sees key j only if j >= i + win_lo (in the rebased key numbering)
   if constexpr (KSPLIT) {
@@ -105,6 +106,7 @@
     p.causal_off -= kb;
     win_lo -= kb;
     if constexpr (AL) al_dg = al_diag - kb;
+    if constexpr (DR) dr_kg = dr.key0 + (uint32_t)kb;
     if (p_in.ksplit > 1) {
       p.acc = p_in.ws_o + (int64_t)ks * p.B * p.Sq * p.Hq * D;
       p.a_sb = (int64_t)p.Sq * p.Hq * D; p.a_ss = (int64_t)p.Hq * D; p.a_sh = D;
@@ -142,6 +144,7 @@
   if constexpr (KSPLIT && !WIN) { if (win) n_full = 0; }  // a left window bound outside the window kernel: every tile through the masked loop
   if constexpr (SC) n_full = 0;                           // softcap: every tile through the generic loop
   if constexpr (AL) n_full = 0;                           // ALiBi: likewise (the bias step lives there)
+  if constexpr (DR) n_full = 0;                           // dropout: likewise (the keep step lives in the generic softmax)
   if (n_full > nt) n_full = nt;
   // WIN (flash_fwd_window_kernel: every launch has a left bound): the tiles are walked in the ROTATED order [rot, nt) then
   // [0, rot) -- online softmax does not care -- where rot is the workgroup-uniform number of leading tiles the left bound
@@ -242,6 +245,7 @@
   // ALiBi: -slope * log2(e) of this item's (batch, head), read per item: the persistent walk and the K cuts of a tile change it
   float al_ns2 = 0.f;
   if constexpr (AL) al_ns2 = -kLog2e * al_slopes[b * al_sb + h];
+  [[maybe_unused]] int dr_kt0 = 0;   // dropout: first key of the tile the generic softmax works on
 
   // S^T = K Q^T for the K tile in Kbuf[kbuf]
   auto qk = [&](int kbuf, f32x16& s0, f32x16& s1) {
@@ -282,6 +286,19 @@
     for (int dj = 0; dj < NDJ; ++dj)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[dj][r] *= alpha;
+    if constexpr (DR) {
+      // dropout: the row sum above took the un-dropped P (the LSE is that of the un-dropped scores); the P packed for the PV
+      // MFMAs is zeroed where dropped, and 256 / t goes into the epilogue's weight in fp32.  The lane's row is fixed, its keys
+      // are the register dimension (usp_dropout_rng.h).
+      uint32_t kw[8];
+      usp_dropout_tile_words<true>(dr.k0, dr.k1, (uint32_t)b, dr.head0 + (uint32_t)h, (dr.row0 + (uint32_t)row) >> 2,
+                                   ((dr_kg + (uint32_t)dr_kt0) >> 2) + (uint32_t)hi, lane, kw);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (!usp_dropout_keep(kw[r >> 2], r & 3, dr.t)) s0[r] = 0.f;
+        if (!usp_dropout_keep(kw[4 + (r >> 2)], r & 3, dr.t)) s1[r] = 0.f;
+      }
+    }
     // P (B operand of V^T P^T): k-step ks = 2*n32 + (r>>3), element e = r & 7
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -482,7 +499,7 @@
     __syncthreads();             // ... and so have everybody else's
   };
 
-  if (!SC && !AL && n_main > 0) {
+  if (!SC && !AL && !DR && n_main > 0) {
     float mt = sa[0];
 #pragma unroll
     for (int r = 1; r < 16; ++r) mt = fmaxf(mt, sa[r]);
@@ -539,6 +556,7 @@
         }
       }
       if (need_mask) mask(kt0, sa, sb);
+      if constexpr (DR) dr_kt0 = kt0;
       u32x4 pf[4];
       softmax(sa, sb, pf);
       pv(j & 1, pf);
@@ -551,7 +569,8 @@
   // ---- epilogue: normalise, merge with the running result, store -------------------------------
   const float l_tot = xhalf_sum(l_run);
   const bool empty = !(l_tot > 0.f);
-  const float inv = empty ? 0.f : 1.f / l_tot;
+  float inv = empty ? 0.f : 1.f / l_tot;
+  if constexpr (DR) inv *= dr.rs;     // dropout: the kept terms are rescaled by 256 / t, in fp32
   const float blk_lse = empty ? USP_NEG_INF : (m_run * c + log2f(l_tot)) * kLn2;
   float w_blk = inv, w_old = 0.f, new_lse = blk_lse;
   float* lse_p = p.lse + b * p.lse_sb + h * p.lse_sh + row;

@@ -2,6 +2,7 @@
 // rows, two waves per SIMD; usp_flash_fwd64.hip: 4 waves x 64 query rows, one wave per SIMD).
 #pragma once
 #include "usp_common.hpp"
+#include "usp_dropout_rng.h"
 
 namespace usp {
 
@@ -57,6 +58,10 @@ struct FwdAlibi {
                                         // of its own: causal_off also absorbs window_right and is dropped with a bound that cuts nothing
 };
 struct FwdArgsAL : FwdArgsT<true>, FwdAlibi {};
+// Dropout (usp_flash_fwd_dropout): kernel arguments of the dropout instantiations only (usp_flash_fwd_dropout.hip:
+// flash_fwd_dropout_kernel, built on the split instantiation's generic loop like the softcap and ALiBi kernels); every other
+// kernel keeps its argument block and machine code.  The mask and the `Dropout` block are csrc/usp_dropout_rng.h.
+struct FwdArgsDR : FwdArgsT<true>, Dropout {};
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -75,5 +80,7 @@ int launch_split_merge(const FwdArgsT<true>& p, int dtype, int D, hipStream_t st
 // The ALiBi forward (usp_flash_fwd_alibi.hip): flash_fwd_alibi_kernel<D, dtype, causal, waves> (waves = 4 | 8) on `grid`
 // workgroups with `lds` bytes; `p` is complete (nq / n_items included).  Returns USP_OK / USP_ELAUNCH / USP_EUNSUPPORTED.
 int launch_fwd_alibi(const FwdArgsAL& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
+// The dropout forward (usp_flash_fwd_dropout.hip), likewise.
+int launch_fwd_dropout(const FwdArgsDR& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -7,6 +7,7 @@
 
 #include "usp_common.hpp"
 #include "usp_hip.h"
+#include "usp_dropout_rng.h"
 #include "usp_mask_decode.h"
 
 namespace usp {
@@ -105,6 +106,36 @@ template <class Args> int check_alibi(const Args& a, const float* slopes, int64_
 // |mask_shift| < 2^30 (check_problem) and Sq + Sk < 2^29 keep it in int.
 template <class Args> int alibi_diag(const Args& a) {
   return (int)((int64_t)a.Sk - a.Sq + ((a.flags & USP_ATTN_SHIFT) ? a.mask_shift : 0));
+}
+
+// Dropout (usp_flash_fwd_dropout / usp_flash_bwd_dropout): validates the scalars and fills the kernels' block.  p_drop == 0, or one
+// whose keep threshold is 256, leaves dr->t = 0: the call is usp_flash_fwd / usp_flash_bwd and the offsets are not looked at.
+// Checked before anything is launched or written.
+// What usp_flash_fwd_dropout / usp_flash_bwd_dropout add to a call (p_drop = 0: nothing)
+struct DropoutCall { float p_drop; uint64_t seed; int32_t row0, key0, head0; };
+
+template <class Args>
+int check_dropout(const Args& a, const DropoutCall& dc, Dropout* dr) {
+  const float p_drop = dc.p_drop;
+  const uint64_t seed = dc.seed;
+  const int32_t row0 = dc.row0, key0 = dc.key0, head0 = dc.head0;
+  *dr = Dropout{};
+  if (!(p_drop >= 0.f) || !(p_drop < 1.f)) return USP_EINVAL;       // NaN, negative, >= 1
+  const int t = usp_dropout_threshold(p_drop);
+  if (p_drop == 0.f || t >= 256) return USP_OK;
+  if (row0 < 0 || key0 < 0 || head0 < 0) return USP_EINVAL;
+  if ((row0 & 3) || (key0 & 3)) return USP_EUNSUPPORTED;             // a DPP quad of lanes shares one 4 x 4 patch
+  if ((int64_t)row0 + a.Sq >= (1LL << 31) || (int64_t)key0 + a.Sk >= (1LL << 31)) return USP_EUNSUPPORTED;
+  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
+  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
+  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
+  dr->k0 = (uint32_t)(seed & 0xffffffffu);
+  dr->k1 = (uint32_t)(seed >> 32);
+  dr->row0 = (uint32_t)row0; dr->key0 = (uint32_t)key0; dr->head0 = (uint32_t)head0;
+  dr->t = (uint32_t)t;
+  dr->rs = 256.f / (float)t;
+  dr->irs = (float)t / 256.f;
+  return USP_OK;
 }
 
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound

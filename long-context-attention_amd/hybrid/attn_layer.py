@@ -14,8 +14,8 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from .._C import softcap_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_alibi_slopes
+from .._C import dropout_value, softcap_value
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_alibi_slopes, local_heads
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
@@ -63,6 +63,17 @@ class _USPLayer(torch.nn.Module):
         if (scatter_idx, self.gather_idx) != (2, 1):
             raise NotImplementedError("alibi_slopes needs the head-scatter exchange (heads scattered, sequence gathered)")
         return local_alibi_slopes(alibi_slopes, heads, self.ulysses_size, dist.get_rank(self.ulysses_pg))
+
+    def _dropout_head0(self, dropout_p, heads: int, scatter_idx: int) -> dict:
+        """The `dropout_head0` keyword of the ring function: the dropout mask is keyed by the layer's GLOBAL query head
+        (include/usp_hip.h: usp_flash_fwd_dropout), and behind the head-scatter exchange this Ulysses rank holds the heads
+        local_heads(H, P, rank) (comm/all_to_all.py) -- KV-replicated grids included: the counter holds the query head.  {} when
+        dropout is off or there is nothing to exchange."""
+        if dropout_value(dropout_p) is None or self.ulysses_size == 1:
+            return {}
+        if (scatter_idx, self.gather_idx) != (2, 1):
+            raise NotImplementedError("dropout_p != 0 needs the head-scatter exchange (heads scattered, sequence gathered)")
+        return dict(dropout_head0=local_heads(heads, self.ulysses_size, dist.get_rank(self.ulysses_pg)).start)
 
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                       return_attn_probs):
@@ -132,6 +143,9 @@ class LongContextAttention(_USPLayer):
         if ng_cap is not None and alibi_slopes is not None:
             ng_cap = None         # ALiBi: likewise three exchanges -- the pipeline's row pieces and head groups would each need a
                                   # slice of the slopes and a shift; the ring function serves it (ring/front_end.py: _check_alibi)
+        if ng_cap is not None and dropout_value(dropout_p) is not None:
+            ng_cap = None         # dropout: likewise three exchanges -- the pipeline's head groups and row pieces would each need
+                                  # their place in the mask; the ring function serves it (ring/front_end.py: _check_dropout)
         if ng_cap is not None:
             _check_hot_path_args(dropout_p, window_size, softcap)
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
@@ -139,6 +153,7 @@ class LongContextAttention(_USPLayer):
         options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap,
                                      self._local_slopes(alibi_slopes, query.shape[2], self.scatter_idx),
                                      deterministic, return_attn_probs)
+        options.update(self._dropout_head0(dropout_p, query.shape[2], self.scatter_idx))
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
         # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
@@ -171,11 +186,12 @@ class LongContextAttentionQKVPacked(_USPLayer):
             return out[..., :D]
         exchange = self.ulysses_size > 1
         alibi_slopes = self._local_slopes(alibi_slopes, qkv.shape[3], self.scatter_idx - 1)
+        head0 = self._dropout_head0(dropout_p, qkv.shape[3], self.scatter_idx - 1)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,
                                                                   softcap, alibi_slopes, deterministic,
-                                                                  return_attn_probs)))
+                                                                  return_attn_probs), **head0))
         if exchange:         # (bs, seq_len, head_cnt/N, head_size) -> (bs, seq_len/N, head_cnt, head_size)
             out = SeqAllToAll4D.apply(self.ulysses_pg, out, self.gather_idx, self.scatter_idx - 1,
                                       self.use_sync, False)

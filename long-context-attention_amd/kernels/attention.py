@@ -78,19 +78,20 @@ class HipBlockBackend:
         return self._beside
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
-            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None):
+            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
-                     interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi)
+                     interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi,
+                     dropout=dropout)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
 
     def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq=False,
             accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None, softcap=None,
-            shift=None, alibi=None):
+            shift=None, alibi=None, dropout=None):
         _C.flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq,
                      accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only,
-                     softcap=softcap, shift=shift, alibi=alibi)
+                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout)
 
     def fwd_packed(self, q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out=None,
                    acc=None, merge_in=False, final_begin=0, final_end=2, softcap=None):
@@ -172,18 +173,72 @@ class _AlibiBackend:
         return getattr(self._be, name)
 
 
-def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None):
+class _DropoutBackend:
+    """A block backend whose dense flash calls (fwd, bwd) all carry `dropout=(p, seed, row0, key0, head0)`; everything else is
+    the wrapped backend's.  It holds (p, seed, head0); the mask is a function of GLOBAL positions (include/usp_hip.h:
+    usp_flash_fwd_dropout), so a caller whose block is not the whole sequence passes `at=(row0, key0)` -- where the block's row 0
+    and key 0 lie -- with each call, the way `shift=` is given (the basic ring does, ring/ring_flash_attn.py); without it the
+    block starts at (0, 0).  The packed calls refuse: the kernels serve dropout on dense launches only."""
+
+    def __init__(self, be, p: float, seed: int, head0: int = 0):
+        self._be, self._p, self._seed, self._head0 = be, p, int(seed), int(head0)
+
+    def _dropout(self, kw):
+        row0, key0 = kw.pop("at", (0, 0))
+        return (self._p, self._seed, int(row0), int(key0), self._head0)
+
+    def fwd(self, *args, **kw):
+        self._be.fwd(*args, dropout=self._dropout(kw), **kw)
+
+    def bwd(self, *args, **kw):
+        self._be.bwd(*args, dropout=self._dropout(kw), **kw)
+
+    def fwd_packed(self, *args, **kw):
+        raise NotImplementedError("dropout_p is not supported on packed (variable-length) batches")
+
+    def bwd_packed(self, *args, **kw):
+        raise NotImplementedError("dropout_p is not supported on packed (variable-length) batches")
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+
+def draw_seed() -> int:
+    """The seed of one call with dropout: one 63-bit draw from torch's default CPU generator -- host side, no device sync,
+    reproducible under torch.manual_seed, advancing with every call.  Drawn in the autograd forward, kept on ctx and reused by the
+    backward.  Ranks that must agree on a mask (a ring, a Ulysses group) are seeded alike by the caller."""
+    return int(torch.randint(0, (1 << 63) - 1, (1,), dtype=torch.int64).item())
+
+
+def rng_state_of(rng_state):
+    """`rng_state` of hip_attn_forward / hip_attn_backward -> (seed, row0, key0, head0): a bare seed is a block at (0, 0, 0)."""
+    if isinstance(rng_state, (tuple, list)):
+        if len(rng_state) != 4:
+            raise ValueError(f"rng_state must be a seed or (seed, row0, key0, head0), got {rng_state!r}")
+        return tuple(int(x) for x in rng_state)
+    return int(rng_state), 0, 0, 0
+
+
+def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, dropout=None):
     """The block backend; `beside_transfers=True` asks for launches that leave room for collectives queued on
     other streams (a persistent flash launch holds every CU until it ends: DESIGN.md section 5).  Test
     backends without that notion are returned as they are.  `softcap` > 0 (flash-attn's logit cap): every flash
     call of the returned backend carries it; None / 0: the backend itself, whose calls carry no softcap keyword
     (backends written before softcap existed keep working).  `alibi`: flash-attn's alibi_slopes as the block calls take them
     (an fp32 (Hq,) or (B, Hq) tensor on the operands' device, _C.alibi_value), None = off: every dense flash call carries
-    them; together with softcap: NotImplementedError (no kernel holds both steps)."""
+    them; together with softcap: NotImplementedError (no kernel holds both steps).  `dropout`: (p, seed, head0), None or
+    p = 0 = off: every dense flash call carries p, the seed and the head offset, and takes `at=(row0, key0)` (_DropoutBackend);
+    together with softcap or alibi: NotImplementedError."""
     be = _BACKEND
     if beside_transfers and hasattr(be, "beside_transfers"):
         be = be.beside_transfers()
     cap = _C.softcap_value(softcap)
+    if dropout is not None and _C.dropout_value(dropout[0]) is not None:
+        if cap is not None:
+            raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
+        if alibi is not None:
+            raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
+        return _DropoutBackend(be, _C.dropout_value(dropout[0]), dropout[1], dropout[2] if len(dropout) > 2 else 0)
     if alibi is not None:
         if cap is not None:
             raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
@@ -208,14 +263,38 @@ def _check_plain(dropout_p, softcap, alibi_slopes):
     """Refuses what the kernels do not serve and returns the softcap as the kernels take it (None = off).
     window_size, softcap and alibi_slopes ARE served: the block kernels take flash-attn's (left, right) window, its tanh logit
     cap and its ALiBi slopes (include/usp_hip.h, USP_ATTN_WINDOW / USP_ATTN_SOFTCAP / usp_flash_fwd_alibi) -- ALiBi and
-    softcap not together.  A negative, NaN or infinite softcap raises ValueError (flash-attn ignores a negative one
-    silently)."""
-    if dropout_p not in (0, 0.0):
-        raise NotImplementedError("dropout_p != 0 is not supported by the HIP attention kernel")
+    softcap not together.  dropout_p is served too (usp_flash_fwd_dropout), but by no kernel that holds a second score-level
+    step: together with softcap or alibi_slopes it is refused here; what a call with dropout needs beyond that (a state) is
+    decided beside this check (_dropout_of).  A negative, NaN or infinite softcap and a dropout_p that is NaN, negative or >= 1
+    raise ValueError (flash-attn ignores a negative softcap silently)."""
+    p = _C.dropout_value(dropout_p)
     cap = _C.softcap_value(softcap)
+    if p is not None and cap is not None:
+        raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
+    if p is not None and alibi_slopes is not None:
+        raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
     if alibi_slopes is not None and cap is not None:
         raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
     return cap
+
+
+def _dropout_of(dropout_p, rng_state, what):
+    """(p, seed, row0, key0, head0) of a block call with dropout, or None when it is off.  The block contracts return no
+    state, so the caller supplies it: dropout_p > 0 without `rng_state` is refused."""
+    p = _C.dropout_value(dropout_p)
+    if p is None:
+        return None
+    if rng_state is None:
+        raise NotImplementedError(f"{what} with dropout_p != 0 needs rng_state=(seed, row0, key0, head0) or a seed: the "
+                                  f"contract returns no state (hip_attn_func draws and keeps one per call)")
+    return (p,) + rng_state_of(rng_state)
+
+
+def _block_backend_for(cap, alibi_slopes, q, dr):
+    """(backend, per-call keywords) of a single-block call: softcap / ALiBi / dropout as given."""
+    if dr is None:
+        return get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q)), {}
+    return get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q), dropout=(dr[0], dr[1], dr[4])), {"at": (dr[2], dr[3])}
 
 
 def _alibi_of(alibi_slopes, q):
@@ -230,22 +309,25 @@ def window_of(window_size):
 
 
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                     softcap=None, alibi_slopes=None, return_softmax=False):
+                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
-    Unlike the TORCH_* wrappers (attention.py:135) the LSE is NOT rounded to q.dtype."""
+    Unlike the TORCH_* wrappers (attention.py:135) the LSE is NOT rounded to q.dtype.
+    `dropout_p` > 0 needs `rng_state` = (seed, row0, key0, head0) or a bare seed (the contract returns no state; without it:
+    NotImplementedError); the same state given to hip_attn_backward regenerates the mask."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
+    dr = _dropout_of(dropout_p, rng_state, "hip_attn_forward")
     B, Sq, Hq, D = q.shape
     scale = _default_scale(q, softmax_scale)
     if kernel_head_dim(D) != D:                 # e.g. 96: on zero-padded copies (kernel_head_dim)
-        out, lse = hip_attn_forward(*pad_head_dim(q, k, v), softmax_scale=scale, causal=causal, window_size=window_size,
-                                    softcap=cap, alibi_slopes=alibi_slopes)
+        out, lse = hip_attn_forward(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=scale, causal=causal,
+                                    window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes, rng_state=rng_state)
         return out[..., :D].contiguous(), lse
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
-    get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q)).fwd(q, k, v, scale, bool(causal), lse, out=out,
-                                                                         window=window_of(window_size))
+    be, kw = _block_backend_for(cap, alibi_slopes, q, dr)
+    be.fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size), **kw)
     return out, lse
 
 
@@ -255,9 +337,9 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
                       rng_state=None, *args, **kwargs):
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
-    (zigzag_ring_flash_attn.py:115-137)."""
+    (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
-    be = get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q))
+    be, at_kw = _block_backend_for(cap, alibi_slopes, q, _dropout_of(dropout_p, rng_state, "hip_attn_backward"))
     B, Sq, Hq, D = q.shape
     dev = q.device
     if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
@@ -279,7 +361,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     tgt = [t if direct(t) else torch.empty(t.shape, dtype=t.dtype, device=dev)
            for t in (block_dq_buffer, block_dk_buffer, block_dv_buffer)]
     be.bwd(dout, q, k, v, lse, delta, None, None, None, _default_scale(q, softmax_scale), bool(bwd_causal),
-           dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], window=window_of(window_size))
+           dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], window=window_of(window_size), **at_kw)
     for t, dst in zip(tgt, (block_dq_buffer, block_dk_buffer, block_dv_buffer)):
         if t is not dst:
             dst.copy_(t)
@@ -290,11 +372,15 @@ class _HipAttnFunc(torch.autograd.Function):
     yunchang/ulysses/attn_layer.py:48,101-113)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None):
+    def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None,
+                dropout_p=0.0, dropout_head0=0):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
-        out, lse = hip_attn_forward(q, k, v, softmax_scale=scale, causal=causal, window_size=window_size, softcap=softcap,
-                                    alibi_slopes=alibi_slopes)
+        # dropout: one seed per call, drawn here, kept for the backward (draw_seed); the block is the whole sequence
+        ctx.dropout_p = _C.dropout_value(dropout_p) or 0.0
+        ctx.rng_state = (draw_seed(), 0, 0, int(dropout_head0)) if ctx.dropout_p else None
+        out, lse = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
+                                    softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state)
         ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)))   # (slopes: no gradient,
         ctx.scale, ctx.causal, ctx.window_size, ctx.softcap = scale, bool(causal), window_size, softcap   # as in flash-attn)
         if return_lse:
@@ -306,26 +392,29 @@ class _HipAttnFunc(torch.autograd.Function):
     def backward(ctx, dout, *_):
         q, k, v, out, lse, *slopes = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, 0.0, ctx.scale, ctx.causal,
-                          ctx.window_size, ctx.softcap, slopes[0] if slopes else None)
-        return dq, dk, dv, None, None, None, None, None, None
+        hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, ctx.dropout_p, ctx.scale, ctx.causal,
+                          ctx.window_size, ctx.softcap, slopes[0] if slopes else None, rng_state=ctx.rng_state)
+        return dq, dk, dv, None, None, None, None, None, None, None, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                  *args, **kwargs):
+                  *args, dropout_head0=0, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
-    return_attn_probs (the probabilities themselves are never materialised: dropout is 0).  `softcap` > 0: flash-attn's
-    tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.  `alibi_slopes`: flash-attn's fp32
-    (Hq,) or (B, Hq) slopes (no gradient), not together with softcap."""
+    return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
+    None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
+    `alibi_slopes`: flash-attn's fp32 (Hq,) or (B, Hq) slopes (no gradient), not together with softcap.  `dropout_p` in (0, 1):
+    the position-keyed mask of include/usp_hip.h under one seed per call from torch's default CPU generator (draw_seed), not
+    together with softcap or alibi_slopes; NaN, a negative value or one >= 1 raises ValueError.  `dropout_head0` (keyword
+    only): the global index of q's head 0 in the mask's counter (a Ulysses rank passes the first head it holds)."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)
-        res = hip_attn_func(*pad_head_dim(q, k, v), softmax_scale=_default_scale(q, softmax_scale), causal=causal,
-                            window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes,
-                            return_attn_probs=return_attn_probs)
+        res = hip_attn_func(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=_default_scale(q, softmax_scale),
+                            causal=causal, window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes,
+                            return_attn_probs=return_attn_probs, dropout_head0=dropout_head0)
         return (res[0][..., :D], res[1], None) if return_attn_probs else res[..., :D]
     if return_attn_probs:
-        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap, alibi_slopes)
+        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap, alibi_slopes, dropout_p, dropout_head0)
         return out, lse, None
-    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap, alibi_slopes)
+    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap, alibi_slopes, dropout_p, dropout_head0)

@@ -4,9 +4,9 @@ made per ring from its (forward, backward) pair.  The ring modules keep their sc
 import torch
 import torch.distributed as dist
 
-from .._C import alibi_value, softcap_value
+from .._C import alibi_value, dropout_value, softcap_value
 from ..kernels import AttnType
-from ..kernels.attention import kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
+from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
 from .utils import group_info
 from .varlen_utils import unflatten_lse
 
@@ -43,8 +43,52 @@ def _check_alibi(alibi_slopes, q, softcap, group, packed, served_beyond_one_bloc
                                   "it over global positions with USP_RING_ALIBI=global")
 
 
+def _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, served, served_beyond_one_block):
+    """Dropout (flash-attn's dropout_p) on a ring: the drop probability as the block launches take it, or None when it is off.
+    The mask is a function of global positions (include/usp_hip.h: usp_flash_fwd_dropout), so a ring serves it where it places
+    every block in the whole sequence: the dense rings at ring degree 1 (ONE block: basic, zigzag, stripe) and the basic ring
+    beyond (`served_beyond_one_block`), by default; `served` = False: a ring whose forward takes no rng_state -- the reference has no competing semantics there (its ring backward drops
+    the rng state).  Everything else refuses; NaN, a negative value or one >= 1 is a ValueError (_C.dropout_value).
+    _check_hot_path_args still refuses dropout for every caller that does not come through here (the async layer)."""
+    p = dropout_value(dropout_p)
+    if p is None:
+        return None
+    if packed:
+        raise NotImplementedError("dropout_p != 0 is not supported by the variable-length (packed) rings: use the basic ring "
+                                  "(ring_impl_type=\"basic\", ring_flash_attn_func) on dense batches")
+    if not served:
+        raise NotImplementedError("dropout_p != 0 is not supported by this HIP ring attention: use the basic ring "
+                                  "(ring_impl_type=\"basic\", ring_flash_attn_func)")
+    if softcap_value(softcap) is not None:
+        raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
+    if alibi_slopes is not None:
+        raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
+    P = group_info(dist, group)[0]
+    if P > 1 and not served_beyond_one_block:
+        raise NotImplementedError("dropout_p != 0 across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
+                                  "rings: use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func), which serves it "
+                                  "over global positions")
+    if P > 1 and q.shape[1] % 4:
+        raise NotImplementedError(f"dropout_p != 0 at ring degree {P} needs a local sequence length that is a multiple of 4 "
+                                  f"(one Philox call covers a 4 x 4 patch of the mask), got {q.shape[1]}")
+    return p
+
+
+def ring_dropout(dropout_p, rng_state):
+    """(p, seed, head0) as get_block_backend takes it, from a ring forward's / backward's `dropout_p` and `rng_state` =
+    (seed, head0); None when dropout is off.  dropout_p > 0 without a state is a caller that did not come through the front
+    end: refused, as ever."""
+    p = dropout_value(dropout_p)
+    if p is None:
+        return None
+    if rng_state is None:
+        raise NotImplementedError("dropout_p != 0 is not supported by the HIP ring attention without rng_state=(seed, head0) "
+                                  "(the ring's *_func draw one per call)")
+    return p, int(rng_state[0]), int(rng_state[1])
+
+
 def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False,
-                   alibi_in_forward=False):
+                   alibi_in_forward=False, dropout=False, dropout_in_forward=False):
     """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
 
         packed             the variable-length form: q / k / v are (T, H, D) token tensors followed by `cu_seqlens, max_seqlen`;
@@ -56,26 +100,36 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
                            and refuses beyond);
         alibi_in_forward   `alibi_slopes` at ring degree > 1 is judged by the forward (the basic ring: USP_RING_ALIBI); every
                            other dense ring serves it at ring degree 1, where it is one block, and refuses beyond; the packed
-                           rings refuse it (_check_alibi).
+                           rings refuse it (_check_alibi);
+        dropout            `forward` / `backward` take `rng_state=(seed, head0)` and serve `dropout_p` at ring degree 1 (every
+                           dense ring); dropout_in_forward: also beyond (the basic ring).  One seed per call is drawn here from
+                           torch's default CPU generator (draw_seed), in the autograd forward, and reused by the backward; the
+                           dense *_func take the keyword-only `dropout_head0` (the global index of the call's query head 0: the
+                           Ulysses layers pass their rank's), the Function an optional trailing argument of that name.
     The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
     grad; both exist here only."""
     n_lead = 2 if packed else 0
     extra = () if packed else (("attn_type", "attn_processor") if attn_processor else ("attn_type",))
     n_args = n_lead + 9 + len(extra)
 
-    def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw):
-        """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse)."""
+    def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw,
+                    head0=0):
+        """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse, the dropout keywords of the
+        backward)."""
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
         _check_alibi(alibi_slopes, q, softcap, group, packed, alibi_in_forward)
-        _check_hot_path_args(dropout_p, (-1, -1) if window_in_forward else window_size, softcap)
+        p = _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, dropout, dropout_in_forward)
+        _check_hot_path_args(dropout_p if p is None else 0.0, (-1, -1) if window_in_forward else window_size, softcap)
         if packed:
             k, v = k.contiguous(), v.contiguous()
         else:
             q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
+        drop_kw = {} if p is None else dict(rng_state=(draw_seed(), int(head0)))  # one seed per call, host side
         out, lse = forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                           window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw)
-        return q, k, v, softmax_scale, out, lse
+                           window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw,
+                           **drop_kw)
+        return q, k, v, softmax_scale, out, lse, drop_kw
 
     def result(out, lse, lead, return_softmax):
         if not return_softmax:
@@ -88,17 +142,19 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
 
         @staticmethod
         def forward(ctx, q, k, v, *args):
-            assert len(args) == n_args, f"{class_name}: {n_args + 3} arguments expected"
-            lead, extra_kw = args[:n_lead], dict(zip(extra, args[n_lead + 9:]))
+            assert len(args) in (n_args, n_args + 1), f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0)"
+            ctx.n_none = len(args)
+            head0 = args[n_args] if len(args) > n_args else 0
+            lead, extra_kw = args[:n_lead], dict(zip(extra, args[n_lead + 9:n_args]))
             dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, return_softmax, group = \
                 args[n_lead:n_lead + 9]
-            q, k, v, softmax_scale, out, lse = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap,
-                                                           alibi_slopes, group, extra_kw)
+            q, k, v, softmax_scale, out, lse, drop_kw = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size,
+                                                                    softcap, alibi_slopes, group, extra_kw, head0)
             ctx.save_for_backward(q, k, v, out, lse, *lead[:1])                   # (cu_seqlens is a tensor)
             extra_kw.pop("attn_processor", None)                                  # (the backwards take none)
             ctx.call = (group, lead[1:], dict(softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
                                               window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes,
-                                              deterministic=deterministic, **extra_kw))
+                                              deterministic=deterministic, **extra_kw, **drop_kw))
             return result(out, lse, lead, return_softmax)
 
         @staticmethod
@@ -106,7 +162,7 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
             group, lead_rest, kw = ctx.call
             if not packed:
                 dout = kernel_operand(dout)
-            return tuple(backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * n_args
+            return tuple(backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * ctx.n_none
 
     Func.__name__ = Func.__qualname__ = class_name
 
@@ -131,32 +187,36 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         def last(attn_type, processor=None):      # the Function's trailing arguments
             return (attn_type, processor)[:len(extra)]
 
+        def head0_arg(dropout_head0):             # ... and the optional one behind them
+            return (dropout_head0,) if dropout_head0 else ()
+
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                 attn_type: AttnType = AttnType.HIP, attn_processor=None):
+                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0):
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
                 res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
-                           window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor)
+                           window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor,
+                           dropout_head0=dropout_head0)
                 return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
             if not needs_grad(q, k, v):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
                 out, lse = run_forward(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group,
-                                       dict(zip(extra, last(attn_type, attn_processor))))[4:]
+                                       dict(zip(extra, last(attn_type, attn_processor))), dropout_head0)[4:6]
                 return result(out, lse, (), return_attn_probs)
             return Func.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
-                              return_attn_probs, group, *last(attn_type, attn_processor))
+                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0))
 
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                          attn_type: AttnType = AttnType.HIP):
+                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0):
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                              deterministic, return_attn_probs, group, *last(attn_type))
+                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0))
 
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                           attn_type: AttnType = AttnType.HIP):
+                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0):
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
-                              alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type))
+                              alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0))
 
     for fn, suffix in ((func, "_func"), (kvpacked_func, "_kvpacked_func"), (qkvpacked_func, "_qkvpacked_func")):
         fn.__name__ = fn.__qualname__ = stem + suffix

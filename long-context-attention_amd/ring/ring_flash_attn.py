@@ -10,6 +10,11 @@ ALiBi (`alibi_slopes`) is one block at ring degree 1; at ring degree > 1 it is s
 GLOBAL positions: the step that sees the K/V of ring rank kr is launched with the diagonal shift (r - kr) * S, which places the
 bias of the block (include/usp_hip.h: usp_flash_fwd_alibi) -- K/V transport and the dK/dV return are unchanged.
 
+Dropout (`dropout_p`) is served at any ring degree, by default: the mask is a function of GLOBAL positions (include/usp_hip.h:
+usp_flash_fwd_dropout), so the step that sees the K/V of ring rank kr is launched with `at=(r * S, kr * S)` -- where its rows and
+keys lie in the whole sequence -- forward and backward alike, and the ring's result is the single-device one for the same seed.
+(The reference forwards dropout_p to every block and drops the rng state in its backward, :112-119.)
+
 A sliding window (`window_size`) is one windowed block at ring degree 1; at ring degree > 1 it is served on request
 (USP_RING_WINDOW=global) over GLOBAL positions: only the blocks the window touches are fetched, launched and returned, each
 with its own shifted bounds (ring/window_blocks.py).
@@ -22,7 +27,7 @@ import torch.distributed as dist
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend, window_of
 from . import block_pieces
-from .front_end import ring_front_end
+from .front_end import ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, return_dkdv_direct, travel_dkdv
 from .window_blocks import WindowPlan
 
@@ -66,13 +71,19 @@ def _ring_alibi(alibi_slopes, P):
     return alibi_slopes
 
 
-def _alibi_shift(al, r, P, step, S, blk_kw=None):
-    """The `shift` keyword of the launch of ring step `step` under ALiBi: the block holds the K/V of ring rank kr = r - step
-    (mod P), whose keys lie (r - kr) * S rows in front of this rank's queries (behind them: negative, the non-causal ring).
-    The rank's own block (shift 0) carries no keyword: it is an unshifted launch and keeps its automatic K split and cuts.
+def _step_launch_kw(al, dr, r, P, step, S, blk_kw=None):
+    """The keywords that place the launch of ring step `step` in the whole sequence.  The block holds the K/V of ring rank
+    kr = r - step (mod P); this rank's queries start at global row r * S, the block's keys at global key kr * S.
+      - dropout (`dr` not None): `at=(r * S, kr * S)`, the global position of the block's row 0 and key 0 -- the mask is a function
+        of global positions (include/usp_hip.h: usp_flash_fwd_dropout), forward and backward alike;
+      - ALiBi (`al` not None): `shift=(r - kr) * S`, by which the block's keys lie in front of this rank's queries (behind them:
+        negative, the non-causal ring).  The rank's own block (shift 0) carries no keyword: it is an unshifted launch and keeps
+        its automatic K split and cuts.
     `blk_kw`: the launch keywords of a window planner's block; a bounded block carries its own shift, which places the MASK --
     the same number by construction (ring/window_blocks.py: (rank - src) * c), asserted because the bias would follow it."""
     blk_kw = dict(blk_kw or {})
+    if dr is not None:
+        blk_kw["at"] = (r * S, ((r - step) % P) * S)
     if al is None:
         return blk_kw
     shift = (r - (r - step) % P) * S
@@ -112,14 +123,16 @@ def basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, lse, delta, softmax
 
 def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                            attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None):
-    """`overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
+                            attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None,
+                            rng_state=None):
+    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None
-    assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None)
+    dr = ring_dropout(dropout_p, rng_state)
+    assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr)
     if pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     B, S, H, D = q.shape
@@ -139,28 +152,31 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
                 kk, vv = relay.get(step)
                 blk = plan.block(step)
                 be.fwd(q, kk, vv, softmax_scale, blk.causal, lse, out, acc, i > 0, 0, S if step == plan.steps[-1] else 0,
-                       **_alibi_shift(al, r, P, step, S, blk.launch_kw()))
+                       **_step_launch_kw(al, dr, r, P, step, S, blk.launch_kw()))
         return out, lse
     last_compute = r if causal else P - 1
     acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if last_compute > 0 else None
     with KVRelay(process_group, k, v) as relay:
         for step in range(P):
             kk, vv = relay.get(step)
-            basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc, **_alibi_shift(al, r, P, step, S))
+            basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc,
+                           **_step_launch_kw(al, dr, r, P, step, S))
     return out, lse
 
 
 def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                              dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                              alibi_slopes=None, deterministic=False,
-                             attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None):
-    """`defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
+                             attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None,
+                             rng_state=None):
+    """`rng_state`: as the forward's (the same state regenerates its mask).  `defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
     ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or dq_first is not None
-    assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None)
+    dr = ring_dropout(dropout_p, rng_state)
+    assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr)
     if pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S, H, D = q.shape
@@ -182,7 +198,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
         def win_block(step, kk, vv, dk_dst, dv_dst):
             blk = plan.block(step)
             be.bwd(dout, q, kk, vv, softmax_lse, delta, dq_acc, dk_dst, dv_dst, softmax_scale, blk.causal,
-                   accum_dq=step > 0, **_alibi_shift(al, r, P, step, S, blk.launch_kw()))   # (step 0 is never empty: it is the first to write dq)
+                   accum_dq=step > 0, **_step_launch_kw(al, dr, r, P, step, S, blk.launch_kw()))   # (step 0 is never empty: it is the first to write dq)
 
         dk_acc, dv_acc = return_dkdv_direct(process_group, k, v, win_block, plan.key_extent, be,
                                             relay_kw=dict(recv_steps=plan.recv, send_steps=plan.send))
@@ -190,7 +206,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
     def block(step, kk, vv, dk_dst, dv_dst):
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
-                               dq_acc, dk_dst, dv_dst, **_alibi_shift(al, r, P, step, S))
+                               dq_acc, dk_dst, dv_dst, **_step_launch_kw(al, dr, r, P, step, S))
 
     def fold(step, dk_acc, dv_acc, dk_blk, dv_blk):
         be.add(dk_acc, dk_acc, dk_blk)
@@ -204,4 +220,4 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
 (RingFlashAttnFunc, ring_flash_attn_func, ring_flash_attn_kvpacked_func, ring_flash_attn_qkvpacked_func) = ring_front_end(
     "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, attn_processor=True,
-    window_in_forward=True, alibi_in_forward=True)
+    window_in_forward=True, alibi_in_forward=True, dropout=True, dropout_in_forward=True)

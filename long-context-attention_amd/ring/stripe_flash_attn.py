@@ -14,7 +14,7 @@ import torch.distributed as dist
 
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend
-from .front_end import ring_front_end
+from .front_end import ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
 
 
@@ -51,11 +51,13 @@ def stripe_bwd_fold(be, r, step, dk_acc, dv_acc, dk_blk, dv_blk):
 
 def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                               window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                              attn_type: AttnType = AttnType.HIP, overlap=False):
+                              attn_type: AttnType = AttnType.HIP, overlap=False, rng_state=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, use ring flash attn instead"
     P, r = group_info(dist, process_group)
     assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes)
+    dr = ring_dropout(dropout_p, rng_state)      # (p, seed, head0) | None: ring degree 1 only (ring/front_end.py: _check_dropout)
+    assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
@@ -71,11 +73,13 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
 def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                                dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                                alibi_slopes=None, deterministic=False, attn_type: AttnType = AttnType.HIP,
-                               overlap=False, defer=None):
+                               overlap=False, defer=None, rng_state=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, ring flash attn instead"
     P, r = group_info(dist, process_group)
     assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes)
+    dr = ring_dropout(dropout_p, rng_state)
+    assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr)
     B, S, H, D = q.shape
     dev = q.device
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)
@@ -101,4 +105,4 @@ def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, s
 
 
 (StripeFlashAttnFunc, stripe_flash_attn_func, stripe_flash_attn_kvpacked_func, stripe_flash_attn_qkvpacked_func) = ring_front_end(
-    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward)
+    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, dropout=True)

@@ -26,7 +26,7 @@ import torch.distributed as dist
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend
 from . import block_pieces
-from .front_end import _check_hot_path_args, ring_front_end      # (_check_hot_path_args: still importable from here)
+from .front_end import _check_hot_path_args, ring_dropout, ring_front_end      # (_check_hot_path_args: still importable from here)
 from .utils import FULL, KVRelay, group_info, ZigzagKVFetch, final_grads, kv_relay_mode, travel_dkdv, zigzag_fetch_pieces
 
 
@@ -200,17 +200,20 @@ def _final_rows(be, q, kp, vp, softmax_scale, lse, out, acc, lo, hi, tail):
         emit(j, out)
 
 
-def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None, alibi=None):
+def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None, alibi=None,
+                          dropout=None):
     """The zigzag ring forward as a generator of two phases.  With `first` beside a ring (degree > 1) it yields ONCE, behind the
     launch on the owned chunk and in front of the wait for the caller's exchange -- the caller may start other head groups' owned
     chunks there -- and returns (out, lse) through StopIteration; otherwise it never yields.  zigzag_ring_flash_attn_forward drives it
     to the end.
     `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same.
-    `alibi`: flash-attn's alibi_slopes, served where the ring is ONE block (ring degree 1, no pieces)."""
+    `alibi`: flash-attn's alibi_slopes, served where the ring is ONE block (ring degree 1, no pieces).
+    `dropout`: (p, seed, head0), likewise (ring/front_end.py: _check_dropout)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None          # (the caller has exchanges in flight by definition)
     assert alibi is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi)
+    assert dropout is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi, dropout=dropout)
     B, S2, H, D = q.shape
     assert S2 % 2 == 0, "zigzag layout needs an even local sequence length"
     if P == 1 and pieces:
@@ -265,8 +268,10 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
 
 def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                                    window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                                   deterministic=False, attn_type: AttnType = AttnType.HIP, overlap=False, first=None, tail=None):
-    """`overlap`: the caller has transfers of its own in flight (pipelined Ulysses exchange), so the kernels are
+                                   deterministic=False, attn_type: AttnType = AttnType.HIP, overlap=False, first=None, tail=None,
+                                   rng_state=None):
+    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it; ring degree 1 only).
+    `overlap`: the caller has transfers of its own in flight (pipelined Ulysses exchange), so the kernels are
     launched so that collectives can run beside them even at ring degree 1.
     `first` = (u, (q, k, v) of the owned chunk, wait): q / k / v are still in flight (the caller's Ulysses exchange at degree
     2; `wait()` orders the calling stream behind it) and step 0 starts on the chunk this rank owns (zigzag_fwd_step0_own).
@@ -276,7 +281,8 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
     At ring degree 1 the ring is ONE causal block and both are served by ring/block_pieces.py (`first` where both are given).
     Either one means transfers in flight: the kernels are launched as under `overlap`."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
-    gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap, alibi_slopes)
+    gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap, alibi_slopes,
+                                ring_dropout(dropout_p, rng_state))
     try:
         while True:
             next(gen)
@@ -287,8 +293,10 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
 def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                                     dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                                     alibi_slopes=None, deterministic=False,
-                                    attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None):
-    """`dq_first(dq)`: the LAST ring step issues its dQ launch in front of its dK/dV launch and rounds dQ in that launch's
+                                    attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None,
+                                    rng_state=None):
+    """`rng_state`: as the forward's.
+    `dq_first(dq)`: the LAST ring step issues its dQ launch in front of its dK/dV launch and rounds dQ in that launch's
     epilogue (rows the step does not touch are cast from the accumulator); `dq_first` is called with the final 16-bit dq
     between the two launches, so that the caller's exchange of dq -- most of the bytes of the gradient exchange -- runs beside
     the dK/dV launch instead of behind the whole step.
@@ -306,7 +314,9 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     P, r = group_info(dist, process_group)
     pieces = first is not None or dq_first is not None      # (the caller has exchanges in flight by definition)
     assert alibi_slopes is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi_slopes)
+    dr = ring_dropout(dropout_p, rng_state)
+    assert dr is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi_slopes, dropout=dr)
     if P == 1 and pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S2, H, D = q.shape
@@ -360,4 +370,5 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
 
 (ZigZagRingFlashAttnFunc, zigzag_ring_flash_attn_func, zigzag_ring_flash_attn_kvpacked_func,
  zigzag_ring_flash_attn_qkvpacked_func) = ring_front_end(
-    "zigzag_ring_flash_attn", "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward)
+    "zigzag_ring_flash_attn", "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward,
+    dropout=True)

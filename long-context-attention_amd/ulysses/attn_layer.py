@@ -11,7 +11,8 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_alibi_slopes
+from .._C import dropout_value
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_alibi_slopes, local_heads
 from ..kernels import AttnType, select_flash_attn_impl
 
 
@@ -44,5 +45,9 @@ class UlyssesAttention(torch.nn.Module):
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
                        softmax_scale=q.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale)
+        if dropout_value(dropout_p) is not None:      # the mask is keyed by the layer's GLOBAL query head (include/usp_hip.h)
+            if (self.scatter_idx, self.gather_idx) != (2, 1):
+                raise NotImplementedError("dropout_p != 0 needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
+            options["dropout_head0"] = local_heads(query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg)).start
         attended = self.attn_fn(q, k, v, **options)
         return self._to_seq(attended[0] if isinstance(attended, tuple) else attended)
