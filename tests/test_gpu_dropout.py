@@ -6,7 +6,12 @@ hip_attn_func; and LongContextAttention's basic ring on virtual ranks against ON
 Tolerances: golden_util.TOL / grad_tol with atol multiplied by 256/t -- every surviving rounded product is scaled by that factor
 -- rtol unchanged; `lse` (that of the un-dropped scores) takes the plain tolerance.  What a wrong mask costs against these
 tolerances is computed without a GPU in tests/test_dropout_cpu.py::test_mutant_references_are_far_away.  Every comparison prints
-its largest error as a fraction of its tolerance ([dropout-err] lines; profiles/dropout_rates.txt quotes them)."""
+its largest error as a fraction of its tolerance ([dropout-err] lines; profiles/dropout_rates.txt quotes them).
+
+What these tolerances cannot see: a few wrong mask bits -- a ragged edge, one DPP quad, one patch at a cut -- cost 0.05 to 0.9 of the
+backward tolerances and sit within 10 % of the forward's either way (dropout: the table of mutants); 256/t scales the
+tolerance, which blinds it at t = 1, and at t = 255 almost nothing differs.  Those are seen in tests/test_gpu_dropout_readout.py,
+which makes the kernels print their mask (tests/mask_readout.py) and compares every (batch, head, row, key) bit for bit."""
 import os
 
 import pytest
