@@ -115,6 +115,9 @@ enum {
 /* USP_ATTN_DROPOUT: a FEATURE bit like USP_ATTN_ALIBI: the library exports usp_flash_fwd_dropout / usp_flash_bwd_dropout (below),
  * which take flash-attn's `dropout_p` and a seed beside the unchanged argument blocks (ABI still v7). */
 #define USP_ATTN_DROPOUT 512
+/* USP_ATTN_SINK: a FEATURE bit like USP_ATTN_ALIBI: the library exports usp_flash_fwd_sink / usp_sink_bwd (below), which take a
+ * learned per-head sink logit beside the unchanged argument blocks (ABI still v7). */
+#define USP_ATTN_SINK 1024
 
 typedef struct usp_tensor {
   void* ptr;
@@ -324,6 +327,47 @@ int usp_flash_fwd_dropout(const usp_fwd_args* args, float p_drop, uint64_t seed,
 int usp_flash_bwd_dropout(const usp_bwd_args* args, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
                           void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Attention sinks: usp_flash_fwd with a learned per-head sink logit (GPT-OSS `sinks`, flash-attn 3's `s_aux` / learnable sink;
+ * "off-by-one softmax" at 0).  sinks[h] (DEVICE fp32, h < Hq) joins the softmax denominator of every row of query head h and
+ * carries no value.  It is in SCORE units: compared with softmax_scale * q.k after the mask, NOT multiplied by softmax_scale.
+ * With S_ij the visible scores of row i (causal / window / shift exactly as without sinks) and s = sinks[h]:
+ *     lse_i   = log( exp(s) + sum_j exp(S_ij) )              ( = s for a row that sees no key; never -inf )
+ *     P_ij    = exp(S_ij - lse_i)                            ( rows sum to 1 - p_sink,i ,  p_sink,i = exp(s - lse_i) )
+ *     out_i   = sum_j P_ij v_j                               ( 0 for a row that sees no key )
+ *     delta_i = rowsum(dout_i * out_i)                       -- usp_bwd_delta, unchanged
+ *     dS_ij   = P_ij * (dP_ij - delta_i) * scale ;  dQ, dK, dV as ever
+ *     ds_h    = - sum_{b,i} exp(s_h - lse_{b,h,i}) * delta_{b,h,i}                                         -- usp_sink_bwd
+ * The returned `lse` INCLUDES the sink (flash-attn's convention for s_aux): it is what a ring merges by and all the backward
+ * needs.  There is no usp_flash_bwd_sink: usp_flash_bwd, handed this lse, IS the backward for dQ, dK and dV (its kernels only
+ * ever need P = exp(S - lse)), and usp_sink_bwd gives the sink's own gradient from the same (lse, delta).
+ * The sink is position-free and must be counted ONCE per row: it belongs to the launch that opens the rows' running state
+ * (merge_in == 0).  Later merge_in launches over further keys, and the K-split merge, then work unchanged on an lse that
+ * already holds it.  In the kernels it is the epilogue's merge with the constant block (o = 0, lse = s): no extra pass.
+ *   - sinks == NULL is exactly usp_flash_fwd: the same kernels, bit-identical results;
+ *   - with sinks, merge_in != 0 is USP_EINVAL;
+ *   - with sinks, USP_ATTN_SOFTCAP, a packed batch (seq_q / seq_k) and USP_FORCE_ROW64 are USP_EUNSUPPORTED, nothing launched
+ *     or written (these checks follow the argument checks every call gets, as for ALiBi and dropout);
+ *   - every head dim runs on the two-waves-per-SIMD family (flash_fwd_sink_kernel: the plain family's tile loops, pipelined
+ *     interior tiles included, with the sink in the epilogue; unforced D = 128 included); usp_last_launch_kinds() reports the
+ *     wave8 / wave4 / split-merge bits that were launched.
+ * Everything else is as the argument block says (k_splits and the workspace -- partial 0 carries the sink --, final_begin /
+ * final_end with acc, USP_LAUNCH_INTERLEAVE, USP_ATTN_WINDOW, USP_ATTN_SHIFT, GQA, any aligned layout).  Sinks together with
+ * ALiBi or dropout have no entry point.
+ *
+ * usp_sink_bwd: dsinks[h] (+)= - sum_{b < B, i < S} exp(sinks[h] - lse[b,h,i]) * delta[b,h,i]  for h < H, "+=" with accum != 0.
+ * lse / delta are (B,H,S) fp32 with seq stride 1 and the given batch / head strides; sinks and dsinks are (H,) fp32.  A term
+ * whose lse is -inf counts as 0.  fp32, deterministic (one workgroup per head, a fixed summation order, no atomics).  Null
+ * pointers and non-positive sizes are USP_EINVAL.
+ * A sink is a parameter REPLICATED over a sequence-parallel group: each rank calls this on its own rows (ring) or heads
+ * (Ulysses) and so holds its SHARE of the gradient; the sum over the group is the gradient, as for any replicated parameter.
+ * Nothing in this library reduces it across ranks.
+ * -------------------------------------------------------------------------------------------- */
+int usp_flash_fwd_sink(const usp_fwd_args* args, const float* sinks, void* stream);
+int usp_sink_bwd(int32_t B, int32_t S, int32_t H, const float* sinks, const float* lse, int64_t lse_stride_b,
+                 int64_t lse_stride_h, const float* delta, int64_t delta_stride_b, int64_t delta_stride_h, float* dsinks,
+                 int32_t accum, void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -424,7 +468,7 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
- * USP_ATTN_DROPOUT, the last two feature bits: the *_alibi / *_dropout entry points exist).  Unknown flag bits are not rejected by
+ * USP_ATTN_DROPOUT | USP_ATTN_SINK, the last three feature bits: the *_alibi / *_dropout / *_sink entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

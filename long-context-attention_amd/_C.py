@@ -30,6 +30,7 @@ USP_ATTN_SOFTCAP = 64          # the softcap field is valid: scores are capped t
 USP_ATTN_SHIFT = 128           # the mask_shift field is valid: (Sk - Sq) + mask_shift places the diagonal of every mask bound
 USP_ATTN_ALIBI = 256           # feature bit of usp_attn_features(): usp_flash_fwd_alibi / usp_flash_bwd_alibi exist (not an args flag)
 USP_ATTN_DROPOUT = 512         # feature bit of usp_attn_features(): usp_flash_fwd_dropout / usp_flash_bwd_dropout exist (not an args flag)
+USP_ATTN_SINK = 1024           # feature bit of usp_attn_features(): usp_flash_fwd_sink / usp_sink_bwd exist (not an args flag)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -110,12 +111,15 @@ class UspBwdArgs(ctypes.Structure):
 
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
-           "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
+           "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
+           "usp_flash_fwd_sink", "usp_sink_bwd")
 # The two *_alibi entry points are the only exports load() does not insist on: they are looked up and prototyped on first use
 # (_alibi_entry), behind the feature bit, so a library built before them still loads and serves everything else.
 ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
 # ... and so are the two *_dropout entry points (_dropout_entry, USP_ATTN_DROPOUT)
 DROPOUT_EXPORTS = ("usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
+# ... and the two sink entry points (_sink_entry, USP_ATTN_SINK)
+SINK_EXPORTS = ("usp_flash_fwd_sink", "usp_sink_bwd")
 
 
 def lib_path() -> str:
@@ -134,7 +138,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -423,6 +427,40 @@ def _dropout_entry(name: str):
     return fn
 
 
+def sinks_value(sinks, Hq: int, device, dtype=None):
+    """A `sinks` argument -> the contiguous fp32 device tensor usp_flash_fwd_sink / usp_sink_bwd take, or None when it is off.
+    One learned logit per query head, in score units: shape (Hq,), float32 or the operands' 16-bit type (`dtype`; None: either
+    16-bit type), on the operands' device; anything else raises ValueError.  (Pure argument check: the CPU orchestration tests
+    call it without a library.)"""
+    if sinks is None:
+        return None
+    if not isinstance(sinks, torch.Tensor):
+        raise ValueError(f"sinks must be a torch.Tensor, got {type(sinks).__name__}")
+    if tuple(sinks.shape) != (Hq,):
+        raise ValueError(f"sinks must have shape ({Hq},): one logit per query head, got {tuple(sinks.shape)}")
+    ok = (torch.float32,) + ((torch.bfloat16, torch.float16) if dtype is None else (dtype,))
+    if sinks.dtype not in ok:
+        raise ValueError(f"sinks must be float32 or the operands' 16-bit type, got {sinks.dtype}")
+    if sinks.device != torch.device(device):
+        raise ValueError(f"sinks is on {sinks.device}, the operands on {device}")
+    return sinks.detach().float().contiguous()
+
+
+def _sink_entry(name: str):
+    """The sink entry point `name` (one of SINK_EXPORTS), prototyped on first use; a library without the feature bit (built
+    before the entry points: it loads, they are not insisted on) is refused."""
+    L = load()
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_SINK and hasattr(L, name)):
+        raise NotImplementedError(f"{_LIB_PATH} does not serve sinks (USP_ATTN_SINK): rebuild it")
+    fn = getattr(L, name)
+    if fn.argtypes is None:
+        i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+        fn.argtypes = ([ctypes.POINTER(UspFwdArgs), vp, vp] if name == "usp_flash_fwd_sink" else
+                       [i32, i32, i32, vp, vp, i64, i64, vp, i64, i64, vp, i32, vp])
+        fn.restype = ctypes.c_int
+    return fn
+
+
 def _set_shift(a, shift: Optional[int]):
     """Set USP_ATTN_SHIFT + the field on an argument block (None = off); a library that does not report the bit would
     ignore it silently and compute another mask, so it is refused here."""
@@ -488,7 +526,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None, dropout=None):
+              alibi=None, dropout=None, sinks=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -501,7 +539,10 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     `alibi`: flash-attn's alibi_slopes, fp32 (Hq,) or (B, Hq) on q's device (alibi_value), None = off: the score of (row i,
     key j) gets -slope * |i + (Sk - Sq + shift) - j| before the mask (usp_flash_fwd_alibi; not with softcap or family="row64").
     `dropout`: (p, seed, row0, key0, head0) (dropout_args), None = off: the probabilities are dropped by the position-keyed
-    mask of include/usp_hip.h and the kept ones rescaled (usp_flash_fwd_dropout; not with softcap, alibi or family="row64")."""
+    mask of include/usp_hip.h and the kept ones rescaled (usp_flash_fwd_dropout; not with softcap, alibi or family="row64").
+    `sinks`: one learned logit per query head (sinks_value), None = off: it joins every row's softmax denominator and carries no
+    value; `lse` includes it (usp_flash_fwd_sink; a launch without merge_in only; not with softcap, alibi, dropout or
+    family="row64")."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
     cap = softcap_value(softcap)
@@ -525,6 +566,12 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
         a.workspace = ws.data_ptr()
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
+    sk = sinks_value(sinks, Hq, q.device, q.dtype)
+    if sk is not None:
+        if al is not None or dr is not None:
+            raise NotImplementedError("sinks together with alibi_slopes or dropout_p is not supported by the HIP attention kernels")
+        _check(_sink_entry("usp_flash_fwd_sink")(ctypes.byref(a), ctypes.c_void_p(sk.data_ptr()), _stream()), "usp_flash_fwd_sink")
+        return
     if dr is not None:
         if al is not None:
             raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
@@ -647,6 +694,27 @@ def bwd_delta(dout, out, delta):
     p, sb, sh = _lse3(delta)
     _check(load().usp_bwd_delta(dtype_code(dout.dtype), B, S, H, D, ctypes.byref(td),
                                 ctypes.byref(to), p, sb, sh, _stream()), "usp_bwd_delta")
+
+
+def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
+    """usp_sink_bwd: out[h] (+)= -sum_{b,i} exp(sinks[h] - lse[b,h,i]) * delta[b,h,i], the gradient of the sink logits from the
+    sink-including `lse` and the backward's `delta` (both (B,H,S) fp32, unit seq stride).  `out`: an fp32 contiguous (H,) buffer
+    (None: a new one), added to with `accum`.  Returns it.  fp32, deterministic."""
+    _require_cuda(sinks, lse, delta, out)
+    B, H, S = lse.shape
+    assert delta.shape == lse.shape, (delta.shape, lse.shape)
+    sk = sinks_value(sinks, H, lse.device)
+    if out is None:
+        if accum:
+            raise ValueError("sink_grad: accum needs the buffer to add to")
+        out = torch.empty(H, dtype=torch.float32, device=lse.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (H,) or not out.is_contiguous():
+        raise ValueError("sink_grad: out must be a contiguous float32 (H,) tensor")
+    pl, lsb, lsh = _lse3(lse)
+    pd, dsb, dsh = _lse3(delta)
+    _check(_sink_entry("usp_sink_bwd")(B, S, H, ctypes.c_void_p(sk.data_ptr()), pl, lsb, lsh, pd, dsb, dsh,
+                                       ctypes.c_void_p(out.data_ptr()), 1 if accum else 0, _stream()), "usp_sink_bwd")
+    return out
 
 
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,

@@ -123,6 +123,22 @@ def local_alibi_slopes(alibi_slopes, H: int, P: int, rank: int):
                      f"(shape (H,) or (B, H)), got {tuple(alibi_slopes.shape)}")
 
 
+def local_sinks(sinks, H: int, P: int, rank: int):
+    """The sink logits (one per query head) of the heads ulysses rank `rank` holds behind the head-scatter exchange of an H-head
+    layer.  A tensor over the layer's H heads is cut to them by SLICING (local_heads), so autograd scatters the rank's gradient
+    back into a (H,) gradient that is zero elsewhere; one over the local H / P heads is taken as it is; any other shape raises
+    ValueError.  None stays None."""
+    if sinks is None or P == 1:
+        return sinks
+    n = sinks.shape[0] if sinks.dim() == 1 else -1
+    if n == H:
+        return sinks[local_heads(H, P, rank)]
+    if H % P == 0 and n == H // P:
+        return sinks
+    raise ValueError(f"sinks must cover the layer's {H} heads or the {H // max(P, 1)} heads of one ulysses rank (shape (H,)), "
+                     f"got {tuple(sinks.shape)}")
+
+
 def pack_head_group(x5: Tensor, send: Tensor = None, h0: int = 0) -> Tensor:
     """x5: a (B, S/P, P, h, D) VIEW (any strides on the first three dims, (h, D) contiguous) selecting
     h heads per destination rank -> heads [h0, h0+h) of the send buffer (P, S/P, B, Ht, D) (allocated with

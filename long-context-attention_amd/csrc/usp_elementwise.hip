@@ -1,6 +1,6 @@
 // HBM-bound helper kernels of libusp_hip.so: backward delta, stand-alone LSE merge, the row-gather
 // copy behind the Ulysses all-to-all pack/unpack, its r-term summing form (KV heads shared by r ranks),
-// fp32 -> 16-bit cast and fp32 add.
+// fp32 -> 16-bit cast, fp32 add and the gradient of the attention sinks.
 // All are pure streaming kernels: 16-byte accesses per lane, grid-stride loops capped at
 // 256 CUs x 8 blocks (cdna_hip_programming.md Guideline 11/13).
 #include "usp_host.hpp"
@@ -194,9 +194,48 @@ __global__ __launch_bounds__(kEwThreads) void add_kernel(float* dst, int64_t d_r
   }
 }
 
+// ---- dsinks[h] (+)= -sum_{b,i} exp(sinks[h] - lse[b,h,i]) * delta[b,h,i] -----------------------------------------------
+// One workgroup per head (B * S * 8 bytes to read): thread t sums the terms t, t + 1024, ... of every batch in that order
+// with a compensated (Kahan) sum, then a fixed LDS tree: deterministic, no atomics.  A term whose lse is -inf counts as 0.
+constexpr int kSinkThreads = 1024;
+__global__ __launch_bounds__(kSinkThreads) void sink_bwd_kernel(const float* sinks, const float* lse, int64_t l_sb, int64_t l_sh,
+                                                                const float* delta, int64_t d_sb, int64_t d_sh, float* dsinks,
+                                                                int B, int S, int accum) {
+  __shared__ float part[kSinkThreads];
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const float s = sinks[h];
+  float sum = 0.f, comp = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float* lp = lse + b * l_sb + h * l_sh;
+    const float* dp = delta + b * d_sb + h * d_sh;
+    for (int i = tid; i < S; i += kSinkThreads) {
+      const float l = lp[i];
+      const float term = l == USP_NEG_INF ? 0.f : expf(s - l) * dp[i];
+      const float y = term - comp;
+      const float t = sum + y;
+      comp = (t - sum) - y;
+      sum = t;
+    }
+  }
+  part[tid] = sum;
+  for (int st = kSinkThreads / 2; st > 0; st >>= 1) {
+    __syncthreads();
+    if (tid < st) part[tid] += part[tid + st];
+  }
+  if (tid == 0) dsinks[h] = accum ? dsinks[h] - part[0] : -part[0];
+}
+
 }  // namespace usp
 
 using namespace usp;
+
+extern "C" int usp_sink_bwd(int32_t B, int32_t S, int32_t H, const float* sinks, const float* lse, int64_t l_sb, int64_t l_sh,
+                            const float* delta, int64_t d_sb, int64_t d_sh, float* dsinks, int32_t accum, void* stream) {
+  if (!sinks || !lse || !delta || !dsinks || B <= 0 || S <= 0 || H <= 0) return USP_EINVAL;
+  hipLaunchKernelGGL(sink_bwd_kernel, dim3(H), dim3(kSinkThreads), 0, (hipStream_t)stream, sinks, lse, l_sb, l_sh, delta, d_sb,
+                     d_sh, dsinks, (int)B, (int)S, accum ? 1 : 0);
+  return launched();
+}
 
 extern "C" int usp_bwd_delta(int32_t dtype, int32_t B, int32_t S, int32_t H, int32_t D,
                              const usp_tensor* dout, const usp_tensor* out, float* delta,
@@ -343,7 +382,7 @@ extern "C" int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32
 }
 
 extern "C" int usp_abi_version(void) { return USP_ABI_VERSION; }
-extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT; }
+extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK; }
 
 // What the calling thread's last flash call launched (include/usp_hip.h: usp_last_launch_kinds).  Thread-local: the entry
 // points share no mutable state.

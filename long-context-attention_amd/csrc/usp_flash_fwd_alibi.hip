@@ -18,6 +18,8 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_alibi_kernel(const F
   const int al_diag = p_in.al_diag;
   constexpr bool DR = false;
   constexpr Dropout dr{};
+  constexpr bool SINK = false;
+  constexpr const float* sink_s = nullptr;
 #include "usp_flash_fwd_body.inc"
 }
 

@@ -2,8 +2,10 @@
 // Included as the body of the kernel templates in usp_flash_fwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
 // the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones, the ALiBi kernel (usp_flash_fwd_alibi.hip) the
-// `if constexpr (AL)` ones, the dropout kernel (usp_flash_fwd_dropout.hip) the `if constexpr (DR)` ones.  The including kernel
-// defines `p_in`, KSPLIT / SC / WIN / AL / DR, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag and `dr` (usp_dropout_rng.h: Dropout).
+// `if constexpr (AL)` ones, the dropout kernel (usp_flash_fwd_dropout.hip) the `if constexpr (DR)` ones, the sink kernel
+// (usp_flash_fwd_sink.hip) the `if constexpr (SINK)` one in the epilogue.  The including kernel
+// defines `p_in`, KSPLIT / SC / WIN / AL / DR / SINK, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr` (usp_dropout_rng.h: Dropout)
+// and sink_s (fp32 (Hq,) sink logits).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int kThreads = 64 * NWAVES;
@@ -591,6 +593,28 @@
         new_lse = mx + log2f(sum) * kLn2;
         w_old = e_old / sum;
         w_blk = e_blk / sum * inv;
+      }
+    }
+    if constexpr (SINK) {
+      // The sink of head h joins the row's denominator and carries no value: the block result merged with (o = 0, lse = s_h),
+      // the arithmetic of the merge above with old = s_h and no acc to read.  Once per row: on the launch that opens the rows'
+      // state, and of a K-split launch on cut 0 alone (p.merge_in is 0 for EVERY cut, so both are read from p_in and ks) --
+      // split_merge_kernel then combines partials of which one holds it.  An empty row, or an empty cut 0, gives (0, s_h):
+      // mx = s_h, e_old = 1, e_blk = 0, log2f(1) = 0.
+      bool carries = !p_in.merge_in;
+      if constexpr (KSPLIT) carries = carries && (p_in.ksplit <= 1 || ks == 0);
+      if (carries) {
+        const float old = sink_s[h];
+        const float mx = fmaxf(old, blk_lse);
+        if (mx == USP_NEG_INF) {
+          new_lse = USP_NEG_INF; w_blk = 0.f;
+        } else {
+          const float e_old = exp2f((old - mx) * kLog2e);
+          const float e_blk = exp2f((blk_lse - mx) * kLog2e);
+          const float sum = e_old + e_blk;
+          new_lse = mx + log2f(sum) * kLn2;
+          w_blk = e_blk / sum * inv;
+        }
       }
     }
     if (hi == 0) *lse_p = new_lse;

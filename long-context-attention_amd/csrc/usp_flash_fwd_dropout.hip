@@ -18,6 +18,8 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_dropout_kernel(const
   constexpr int64_t al_sb = 0;
   constexpr int al_diag = 0;
   const Dropout& dr = p_in;
+  constexpr bool SINK = false;
+  constexpr const float* sink_s = nullptr;
 #include "usp_flash_fwd_body.inc"
 }
 

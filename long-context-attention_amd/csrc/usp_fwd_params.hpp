@@ -62,6 +62,14 @@ struct FwdArgsAL : FwdArgsT<true>, FwdAlibi {};
 // flash_fwd_dropout_kernel, built on the split instantiation's generic loop like the softcap and ALiBi kernels); every other
 // kernel keeps its argument block and machine code.  The mask and the `Dropout` block are csrc/usp_dropout_rng.h.
 struct FwdArgsDR : FwdArgsT<true>, Dropout {};
+// Attention sinks (usp_flash_fwd_sink): kernel arguments of the sink instantiations only (usp_flash_fwd_sink.hip:
+// flash_fwd_sink_kernel, the split and window instantiations' tile loops with the sink merged in the epilogue); every other
+// kernel keeps its argument block and machine code.
+struct FwdSink {
+  const float* sinks;                   // fp32 (Hq,): the sink logit of query head h, in score units (not scaled)
+};
+struct FwdArgsSK : FwdArgsT<true>, FwdSink {};
+struct FwdArgsSKP : FwdArgsT<false>, FwdSink {};      // ... of the sink kernels on the plain (unsplit) argument block
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -82,5 +90,7 @@ int launch_split_merge(const FwdArgsT<true>& p, int dtype, int D, hipStream_t st
 int launch_fwd_alibi(const FwdArgsAL& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 // The dropout forward (usp_flash_fwd_dropout.hip), likewise.
 int launch_fwd_dropout(const FwdArgsDR& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
+// The sink forward (usp_flash_fwd_sink.hip), likewise; p.win_on picks the window form, p.ksplit > 1 the split form, else the plain one.
+int launch_fwd_sink(const FwdArgsSK& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

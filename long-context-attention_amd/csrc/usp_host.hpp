@@ -138,6 +138,17 @@ int check_dropout(const Args& a, const DropoutCall& dc, Dropout* dr) {
   return USP_OK;
 }
 
+// Attention sinks (usp_flash_fwd_sink): what a call with sinks must not carry -- checked before anything is launched or written.
+// NULL sinks: the call is usp_flash_fwd.
+inline int check_sink(const usp_fwd_args& a, const float* sinks) {
+  if (!sinks) return USP_OK;
+  if (a.merge_in) return USP_EINVAL;                                // the sink belongs to the launch that opens the rows' state
+  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
+  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
+  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
+  return USP_OK;
+}
+
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound
 // at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
 // (forward: the split instantiation, FwdSplit).

@@ -517,8 +517,11 @@ class AsyncLongContextAttention(torch.nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                return_attn_probs=False, *args: Any) -> Tensor:
+                return_attn_probs=False, *args: Any, sinks=None) -> Tensor:
         """query (bs, seqlen/P, hc, hs); key/value (bs, seqlen/P, hc_kv, hs) -> (bs, seqlen/P, hc, hs)."""
+        if sinks is not None:
+            raise NotImplementedError("sinks is not supported by AsyncLongContextAttention (its head-group pipeline issues blocks "
+                                      "in pieces): use LongContextAttention")
         if alibi_slopes is not None:
             raise NotImplementedError("alibi_slopes is not supported by AsyncLongContextAttention: use LongContextAttention "
                                       "with the basic ring (ring_impl_type=\"basic\")")

@@ -15,7 +15,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from .._C import dropout_value, softcap_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_alibi_slopes, local_heads
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_alibi_slopes, local_heads, local_sinks
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
@@ -75,6 +75,19 @@ class _USPLayer(torch.nn.Module):
             raise NotImplementedError("dropout_p != 0 needs the head-scatter exchange (heads scattered, sequence gathered)")
         return dict(dropout_head0=local_heads(heads, self.ulysses_size, dist.get_rank(self.ulysses_pg)).start)
 
+    def _local_sinks(self, sinks, heads: int, scatter_idx: int) -> dict:
+        """The `sinks` keyword of the ring function: the layer's sink logits cut to the heads this Ulysses rank holds behind the
+        exchange (comm/all_to_all.py: local_sinks; by slicing, so autograd scatters the gradient back), KV-replicated grids
+        included.  {} when there are none.  The sinks are a parameter replicated over the sequence-parallel group: each rank's
+        gradient is its share (its rows of the ring, its heads under Ulysses, zeros elsewhere), the SUM over the group is the
+        gradient, and the layers do no all-reduce."""
+        if sinks is None:
+            return {}
+        if self.ulysses_size > 1 and (scatter_idx, self.gather_idx) != (2, 1):
+            raise NotImplementedError("sinks needs the head-scatter exchange (heads scattered, sequence gathered)")
+        rank = dist.get_rank(self.ulysses_pg) if self.ulysses_size > 1 else 0
+        return dict(sinks=local_sinks(sinks, heads, self.ulysses_size, rank))
+
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                       return_attn_probs):
         return dict(dropout_p=dropout_p, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
@@ -128,13 +141,14 @@ class LongContextAttention(_USPLayer):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                deterministic=False, return_attn_probs=False, *args: Any) -> Tensor:
+                deterministic=False, return_attn_probs=False, *args: Any, sinks=None) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
-        head_size) -> context (bs, seq_len/N, head_cnt, head_size)."""
+        head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
+        layer, (head_cnt,) fp32 or the operands' type (_USPLayer._local_sinks: the gradient contract)."""
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
-                               causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args)
+                               causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks)
             return out[..., :D]
         ng_cap = self._packed_exchange(query, key)
         if ng_cap is not None and window_of(window_size) is not None:
@@ -146,6 +160,9 @@ class LongContextAttention(_USPLayer):
         if ng_cap is not None and dropout_value(dropout_p) is not None:
             ng_cap = None         # dropout: likewise three exchanges -- the pipeline's head groups and row pieces would each need
                                   # their place in the mask; the ring function serves it (ring/front_end.py: _check_dropout)
+        if ng_cap is not None and sinks is not None:
+            ng_cap = None         # sinks: likewise three exchanges -- the pipeline issues blocks in pieces that open a row range
+                                  # more than once (ring/block_pieces.py); the ring function serves them (ring/front_end.py: _check_sinks)
         if ng_cap is not None:
             _check_hot_path_args(dropout_p, window_size, softcap)
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
@@ -154,6 +171,7 @@ class LongContextAttention(_USPLayer):
                                      self._local_slopes(alibi_slopes, query.shape[2], self.scatter_idx),
                                      deterministic, return_attn_probs)
         options.update(self._dropout_head0(dropout_p, query.shape[2], self.scatter_idx))
+        options.update(self._local_sinks(sinks, query.shape[2], self.scatter_idx))
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
         # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
@@ -178,15 +196,16 @@ class LongContextAttentionQKVPacked(_USPLayer):
 
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                *args: Any) -> Tensor:
+                *args: Any, sinks=None) -> Tensor:
         D = qkv.shape[-1]
         if kernel_head_dim(D) != D:
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
-                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args)
+                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks)
             return out[..., :D]
         exchange = self.ulysses_size > 1
         alibi_slopes = self._local_slopes(alibi_slopes, qkv.shape[3], self.scatter_idx - 1)
         head0 = self._dropout_head0(dropout_p, qkv.shape[3], self.scatter_idx - 1)
+        head0.update(self._local_sinks(sinks, qkv.shape[3], self.scatter_idx - 1))
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,

@@ -78,10 +78,14 @@ class HipBlockBackend:
         return self._beside
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
-            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None):
+            final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None,
+            sinks=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
                      interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi,
-                     dropout=dropout)
+                     dropout=dropout, sinks=sinks)
+
+    def sink_grad(self, sinks, lse, delta, out=None, accum=False):
+        return _C.sink_grad(sinks, lse, delta, out=out, accum=accum)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
@@ -203,6 +207,37 @@ class _DropoutBackend:
         return getattr(self._be, name)
 
 
+class _SinkBackend:
+    """A block backend whose forward launches WITHOUT merge_in carry `sinks=`; everything else is the wrapped backend's.  The
+    sink is position-free and counts once per row: it rides on the launch that opens the rows' running state (every ring opens
+    each row range with exactly one such launch), the later merge_in launches, the merges and the backward kernels then work
+    unchanged on an lse that holds it (include/usp_hip.h: usp_flash_fwd_sink).  `sinks`: (Hq,) over the heads of the block calls.
+    The packed calls refuse: the kernels serve sinks on dense launches only."""
+
+    def __init__(self, be, sinks):
+        self._be, self._sinks = be, sinks
+
+    def fwd(self, *args, **kw):
+        merge_in = kw.get("merge_in", args[8] if len(args) > 8 else False)
+        if merge_in:
+            self._be.fwd(*args, **kw)
+        else:
+            self._be.fwd(*args, sinks=self._sinks, **kw)
+
+    def sink_grad(self, lse, delta, out=None, accum=False):
+        """The rank's share of the sinks' gradient from its rows' global lse and delta (fp32 (Hq,))."""
+        return self._be.sink_grad(self._sinks, lse, delta, out=out, accum=accum)
+
+    def fwd_packed(self, *args, **kw):
+        raise NotImplementedError("sinks is not supported on packed (variable-length) batches")
+
+    def bwd_packed(self, *args, **kw):
+        raise NotImplementedError("sinks is not supported on packed (variable-length) batches")
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+
 def draw_seed() -> int:
     """The seed of one call with dropout: one 63-bit draw from torch's default CPU generator -- host side, no device sync,
     reproducible under torch.manual_seed, advancing with every call.  Drawn in the autograd forward, kept on ctx and reused by the
@@ -219,7 +254,7 @@ def rng_state_of(rng_state):
     return int(rng_state), 0, 0, 0
 
 
-def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, dropout=None):
+def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, dropout=None, sinks=None):
     """The block backend; `beside_transfers=True` asks for launches that leave room for collectives queued on
     other streams (a persistent flash launch holds every CU until it ends: DESIGN.md section 5).  Test
     backends without that notion are returned as they are.  `softcap` > 0 (flash-attn's logit cap): every flash
@@ -228,11 +263,16 @@ def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, 
     (an fp32 (Hq,) or (B, Hq) tensor on the operands' device, _C.alibi_value), None = off: every dense flash call carries
     them; together with softcap: NotImplementedError (no kernel holds both steps).  `dropout`: (p, seed, head0), None or
     p = 0 = off: every dense flash call carries p, the seed and the head offset, and takes `at=(row0, key0)` (_DropoutBackend);
-    together with softcap or alibi: NotImplementedError."""
+    together with softcap or alibi: NotImplementedError.  `sinks`: one logit per query head of the block calls (a (Hq,) tensor on
+    the operands' device, _C.sinks_value), None = off: the forward launches that open a row range carry it (_SinkBackend) and the
+    backend offers sink_grad(lse, delta); together with softcap, alibi or dropout: NotImplementedError."""
     be = _BACKEND
     if beside_transfers and hasattr(be, "beside_transfers"):
         be = be.beside_transfers()
     cap = _C.softcap_value(softcap)
+    if sinks is not None:
+        _check_sinks(cap, alibi, dropout[0] if dropout is not None else None)
+        return _SinkBackend(be, sinks)
     if dropout is not None and _C.dropout_value(dropout[0]) is not None:
         if cap is not None:
             raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
@@ -278,6 +318,21 @@ def _check_plain(dropout_p, softcap, alibi_slopes):
     return cap
 
 
+def _check_sinks(cap, alibi_slopes, dropout_p):
+    """Refuses what no sink kernel holds: a second score-level step."""
+    for on, what in ((cap is not None, "softcap"), (alibi_slopes is not None, "alibi_slopes"),
+                     (_C.dropout_value(dropout_p) is not None, "dropout_p")):
+        if on:
+            raise NotImplementedError(f"sinks together with {what} is not supported by the HIP attention kernels")
+
+
+def sinks_of(sinks, q):
+    """`sinks` checked against q (B, S, Hq, D) (_C.sinks_value: ValueError): the tensor as given (it may require grad), or None."""
+    if sinks is not None:
+        _C.sinks_value(sinks, q.shape[2], q.device, q.dtype)
+    return sinks
+
+
 def _dropout_of(dropout_p, rng_state, what):
     """(p, seed, row0, key0, head0) of a block call with dropout, or None when it is off.  The block contracts return no
     state, so the caller supplies it: dropout_p > 0 without `rng_state` is refused."""
@@ -290,8 +345,11 @@ def _dropout_of(dropout_p, rng_state, what):
     return (p,) + rng_state_of(rng_state)
 
 
-def _block_backend_for(cap, alibi_slopes, q, dr):
-    """(backend, per-call keywords) of a single-block call: softcap / ALiBi / dropout as given."""
+def _block_backend_for(cap, alibi_slopes, q, dr, sinks=None):
+    """(backend, per-call keywords) of a single-block call: softcap / ALiBi / dropout / sinks as given."""
+    if sinks is not None:
+        return get_block_backend(softcap=cap, alibi=alibi_slopes, dropout=None if dr is None else (dr[0], dr[1], dr[4]),
+                                 sinks=sinks_of(sinks, q)), {}
     if dr is None:
         return get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q)), {}
     return get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q), dropout=(dr[0], dr[1], dr[4])), {"at": (dr[2], dr[3])}
@@ -309,24 +367,30 @@ def window_of(window_size):
 
 
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None):
+                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
     Unlike the TORCH_* wrappers (attention.py:135) the LSE is NOT rounded to q.dtype.
     `dropout_p` > 0 needs `rng_state` = (seed, row0, key0, head0) or a bare seed (the contract returns no state; without it:
-    NotImplementedError); the same state given to hip_attn_backward regenerates the mask."""
+    NotImplementedError); the same state given to hip_attn_backward regenerates the mask.
+    `sinks` (keyword only): one learned logit per query head, (Hq,) fp32 or q.dtype, in score units (not scaled): it joins every
+    row's softmax denominator and carries no value; the returned lse includes it (include/usp_hip.h: usp_flash_fwd_sink).  Not
+    together with softcap, alibi_slopes or dropout_p."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
+    if sinks is not None:
+        _check_sinks(cap, alibi_slopes, dropout_p)
     dr = _dropout_of(dropout_p, rng_state, "hip_attn_forward")
     B, Sq, Hq, D = q.shape
     scale = _default_scale(q, softmax_scale)
     if kernel_head_dim(D) != D:                 # e.g. 96: on zero-padded copies (kernel_head_dim)
         out, lse = hip_attn_forward(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=scale, causal=causal,
-                                    window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes, rng_state=rng_state)
+                                    window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes, rng_state=rng_state,
+                                    sinks=sinks)
         return out[..., :D].contiguous(), lse
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
-    be, kw = _block_backend_for(cap, alibi_slopes, q, dr)
+    be, kw = _block_backend_for(cap, alibi_slopes, q, dr, sinks)
     be.fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size), **kw)
     return out, lse
 
@@ -334,19 +398,25 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
 def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk_buffer,
                       block_dv_buffer, dropout_p=0.0, softmax_scale=None, bwd_causal=False,
                       window_size=(-1, -1), softcap=None, alibi_slopes=None, deterministic=False,
-                      rng_state=None, *args, **kwargs):
+                      rng_state=None, *args, sinks=None, dsinks=None, **kwargs):
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
-    (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one."""
+    (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one.
+    `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
+    come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd)."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
-    be, at_kw = _block_backend_for(cap, alibi_slopes, q, _dropout_of(dropout_p, rng_state, "hip_attn_backward"))
+    if sinks is not None:
+        _check_sinks(cap, alibi_slopes, dropout_p)
+        if dsinks is None:
+            raise ValueError("hip_attn_backward with sinks needs the fp32 (Hq,) buffer dsinks")
+    be, at_kw = _block_backend_for(cap, alibi_slopes, q, _dropout_of(dropout_p, rng_state, "hip_attn_backward"), sinks)
     B, Sq, Hq, D = q.shape
     dev = q.device
     if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
         pdo, pq, pk, pv, po = pad_head_dim(dout, q, k, v, out)
         g = [torch.empty_like(t) for t in (pq, pk, pv)]
         hip_attn_backward(pdo, pq, pk, pv, po, softmax_lse, g[0], g[1], g[2], dropout_p, _default_scale(q, softmax_scale),
-                          bwd_causal, window_size, cap, alibi_slopes, deterministic, rng_state)
+                          bwd_causal, window_size, cap, alibi_slopes, deterministic, rng_state, sinks=sinks, dsinks=dsinks)
         for dst, src in zip((block_dq_buffer, block_dk_buffer, block_dv_buffer), g):
             dst.copy_(src[..., :D])
         return
@@ -355,6 +425,8 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     lse = softmax_lse if softmax_lse.dtype == torch.float32 else softmax_lse.float()
     if lse.stride(-1) != 1:
         lse = lse.contiguous()
+    if sinks is not None:
+        be.sink_grad(lse, delta, out=dsinks)
     # the kernels round the final result to 16 bits in their epilogues (no fp32 round trip + cast)
     def direct(t):
         return t.dim() == 4 and t.stride(3) == 1 and all(st % 4 == 0 for st in t.stride()[:3])
@@ -373,15 +445,17 @@ class _HipAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None,
-                dropout_p=0.0, dropout_head0=0):
+                dropout_p=0.0, dropout_head0=0, sinks=None):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
         # dropout: one seed per call, drawn here, kept for the backward (draw_seed); the block is the whole sequence
         ctx.dropout_p = _C.dropout_value(dropout_p) or 0.0
         ctx.rng_state = (draw_seed(), 0, 0, int(dropout_head0)) if ctx.dropout_p else None
         out, lse = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
-                                    softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state)
-        ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)))   # (slopes: no gradient,
+                                    softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks)
+        ctx.has_sinks = sinks is not None          # (never beside slopes: the one optional saved tensor is either)
+        ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)),
+                              *(() if sinks is None else (sinks,)))                                     # (slopes: no gradient,
         ctx.scale, ctx.causal, ctx.window_size, ctx.softcap = scale, bool(causal), window_size, softcap   # as in flash-attn)
         if return_lse:
             ctx.mark_non_differentiable(lse)
@@ -391,30 +465,42 @@ class _HipAttnFunc(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, *_):
         q, k, v, out, lse, *slopes = ctx.saved_tensors
+        sinks = slopes.pop() if ctx.has_sinks else None
+        dsinks = None if sinks is None else torch.empty(sinks.shape, dtype=torch.float32, device=q.device)
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, ctx.dropout_p, ctx.scale, ctx.causal,
-                          ctx.window_size, ctx.softcap, slopes[0] if slopes else None, rng_state=ctx.rng_state)
-        return dq, dk, dv, None, None, None, None, None, None, None, None
+                          ctx.window_size, ctx.softcap, slopes[0] if slopes else None, rng_state=ctx.rng_state, sinks=sinks,
+                          dsinks=dsinks)
+        if dsinks is not None:
+            dsinks = dsinks.to(sinks.dtype) if ctx.needs_input_grad[11] else None
+        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                  *args, dropout_head0=0, **kwargs):
+                  *args, dropout_head0=0, sinks=None, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
     `alibi_slopes`: flash-attn's fp32 (Hq,) or (B, Hq) slopes (no gradient), not together with softcap.  `dropout_p` in (0, 1):
     the position-keyed mask of include/usp_hip.h under one seed per call from torch's default CPU generator (draw_seed), not
     together with softcap or alibi_slopes; NaN, a negative value or one >= 1 raises ValueError.  `dropout_head0` (keyword
-    only): the global index of q's head 0 in the mask's counter (a Ulysses rank passes the first head it holds)."""
+    only): the global index of q's head 0 in the mask's counter (a Ulysses rank passes the first head it holds).
+    `sinks` (keyword only): one learned logit per query head, (Hq,) fp32 or q.dtype (hip_attn_forward); it may require grad, and
+    its gradient comes back in its own dtype and shape.  Not together with softcap, alibi_slopes or dropout_p."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
+    if sinks is not None:
+        _check_sinks(cap, alibi_slopes, dropout_p)
+        sinks_of(sinks, q)
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)
         res = hip_attn_func(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=_default_scale(q, softmax_scale),
                             causal=causal, window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes,
-                            return_attn_probs=return_attn_probs, dropout_head0=dropout_head0)
+                            return_attn_probs=return_attn_probs, dropout_head0=dropout_head0, sinks=sinks)
         return (res[0][..., :D], res[1], None) if return_attn_probs else res[..., :D]
     if return_attn_probs:
-        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap, alibi_slopes, dropout_p, dropout_head0)
+        out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap, alibi_slopes, dropout_p, dropout_head0,
+                                      sinks)
         return out, lse, None
-    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap, alibi_slopes, dropout_p, dropout_head0)
+    return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap, alibi_slopes, dropout_p, dropout_head0,
+                              sinks)

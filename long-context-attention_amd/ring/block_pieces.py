@@ -103,6 +103,14 @@ def tail_last_backward(be, dout, q, k, v, o, lse, scale, dq_first):
     return dq, dk, dv
 
 
+def refuse_sinks(sinks, pieces):
+    """The pieces open a row range with more than one launch without merge_in (split_first_forward, tail_last_forward): a sink
+    riding on those would not be the one block's.  Only the head-group pipeline asks for pieces."""
+    if sinks is not None and pieces:
+        raise NotImplementedError("sinks is not supported with a block issued in pieces (first / tail / dq_first: the head-group "
+                                  "pipeline of AsyncLongContextAttention): use LongContextAttention")
+
+
 def forward_in_pieces(be, q, k, v, scale, first=None, tail=None):
     """A ring forward's degree-1 route for `first` = (u, (q, k, v) of the own rows, wait) or `tail` = (n, emit).  The split
     owns the block where both are given."""

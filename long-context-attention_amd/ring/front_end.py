@@ -4,7 +4,7 @@ made per ring from its (forward, backward) pair.  The ring modules keep their sc
 import torch
 import torch.distributed as dist
 
-from .._C import alibi_value, dropout_value, softcap_value
+from .._C import alibi_value, dropout_value, sinks_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
 from .utils import group_info
@@ -74,6 +74,24 @@ def _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, served, s
     return p
 
 
+def _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed):
+    """Attention sinks (one learned logit per query head, include/usp_hip.h: usp_flash_fwd_sink) on a ring.  The sink is
+    position-free and counts once per row, and every dense ring opens each row's running state with exactly one launch without
+    merge_in: the sink rides on that launch (kernels/attention.py: _SinkBackend), at any ring degree, and the merges and the
+    backward kernels are unchanged.  The packed rings refuse, and so does a second score-level step (softcap, alibi_slopes,
+    dropout_p); a wrong shape, dtype or device is a ValueError (_C.sinks_value)."""
+    if sinks is None:
+        return
+    if packed:
+        raise NotImplementedError("sinks is not supported by the variable-length (packed) rings: use a dense ring "
+                                  "(ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)")
+    for on, what in ((softcap_value(softcap) is not None, "softcap"), (alibi_slopes is not None, "alibi_slopes"),
+                     (dropout_value(dropout_p) is not None, "dropout_p")):
+        if on:
+            raise NotImplementedError(f"sinks together with {what} is not supported by the HIP attention kernels")
+    sinks_value(sinks, q.shape[2], q.device, q.dtype)
+
+
 def ring_dropout(dropout_p, rng_state):
     """(p, seed, head0) as get_block_backend takes it, from a ring forward's / backward's `dropout_p` and `rng_state` =
     (seed, head0); None when dropout is off.  dropout_p > 0 without a state is a caller that did not come through the front
@@ -88,7 +106,7 @@ def ring_dropout(dropout_p, rng_state):
 
 
 def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False,
-                   alibi_in_forward=False, dropout=False, dropout_in_forward=False):
+                   alibi_in_forward=False, dropout=False, dropout_in_forward=False, sinks=False):
     """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
 
         packed             the variable-length form: q / k / v are (T, H, D) token tensors followed by `cu_seqlens, max_seqlen`;
@@ -105,7 +123,13 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
                            dense ring); dropout_in_forward: also beyond (the basic ring).  One seed per call is drawn here from
                            torch's default CPU generator (draw_seed), in the autograd forward, and reused by the backward; the
                            dense *_func take the keyword-only `dropout_head0` (the global index of the call's query head 0: the
-                           Ulysses layers pass their rank's), the Function an optional trailing argument of that name.
+                           Ulysses layers pass their rank's), the Function an optional trailing argument of that name;
+        sinks              `forward` takes `sinks=` and `backward` takes it too and returns (dq, dk, dv, dsinks fp32) with it (the
+                           dense rings, any ring degree: _check_sinks).  The dense *_func take the keyword-only `sinks`, (Hq,)
+                           fp32 or q.dtype, which may require grad; the Function takes it as one more optional trailing
+                           argument (behind dropout_head0) and its backward returns the gradient in that slot, in the sinks'
+                           dtype.  It is THIS rank's share -- its rows; the sum over the ring group is the gradient of the
+                           replicated parameter, and nothing here reduces it.
     The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
     grad; both exist here only."""
     n_lead = 2 if packed else 0
@@ -113,11 +137,14 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
     n_args = n_lead + 9 + len(extra)
 
     def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw,
-                    head0=0):
+                    head0=0, sink_t=None):
         """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse, the dropout keywords of the
         backward)."""
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
+        if sink_t is not None:
+            assert sinks, f"{class_name}: this ring's forward takes no sinks"
+            _check_sinks(sink_t, q, dropout_p, softcap, alibi_slopes, packed)
         _check_alibi(alibi_slopes, q, softcap, group, packed, alibi_in_forward)
         p = _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, dropout, dropout_in_forward)
         _check_hot_path_args(dropout_p if p is None else 0.0, (-1, -1) if window_in_forward else window_size, softcap)
@@ -128,7 +155,7 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         drop_kw = {} if p is None else dict(rng_state=(draw_seed(), int(head0)))  # one seed per call, host side
         out, lse = forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
                            window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw,
-                           **drop_kw)
+                           **drop_kw, **({} if sink_t is None else dict(sinks=sink_t)))
         return q, k, v, softmax_scale, out, lse, drop_kw
 
     def result(out, lse, lead, return_softmax):
@@ -138,19 +165,22 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
 
     class Func(torch.autograd.Function):
         """forward(ctx, q, k, v, [cu_seqlens, max_seqlen,] dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-        deterministic, return_softmax, group[, attn_type[, attn_processor]])"""
+        deterministic, return_softmax, group[, attn_type[, attn_processor]][, dropout_head0[, sinks]])"""
 
         @staticmethod
         def forward(ctx, q, k, v, *args):
-            assert len(args) in (n_args, n_args + 1), f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0)"
+            assert len(args) in (n_args, n_args + 1, n_args + 2), \
+                f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0 (+ sinks))"
             ctx.n_none = len(args)
             head0 = args[n_args] if len(args) > n_args else 0
+            sink_t = args[n_args + 1] if len(args) > n_args + 1 else None
             lead, extra_kw = args[:n_lead], dict(zip(extra, args[n_lead + 9:n_args]))
             dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, return_softmax, group = \
                 args[n_lead:n_lead + 9]
             q, k, v, softmax_scale, out, lse, drop_kw = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size,
-                                                                    softcap, alibi_slopes, group, extra_kw, head0)
-            ctx.save_for_backward(q, k, v, out, lse, *lead[:1])                   # (cu_seqlens is a tensor)
+                                                                    softcap, alibi_slopes, group, extra_kw, head0, sink_t)
+            ctx.has_sinks = sink_t is not None                                    # (dense rings only: `lead` is then empty)
+            ctx.save_for_backward(q, k, v, out, lse, *lead[:1], *(() if sink_t is None else (sink_t,)))   # (cu_seqlens is a tensor)
             extra_kw.pop("attn_processor", None)                                  # (the backwards take none)
             ctx.call = (group, lead[1:], dict(softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
                                               window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes,
@@ -162,61 +192,69 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
             group, lead_rest, kw = ctx.call
             if not packed:
                 dout = kernel_operand(dout)
-            return tuple(backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * ctx.n_none
+            if not ctx.has_sinks:
+                return tuple(backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * ctx.n_none
+            *saved, sink_t = ctx.saved_tensors
+            dq, dk, dv, dsinks = backward(group, dout, *saved, *lead_rest, **kw, sinks=sink_t)
+            return (dq, dk, dv) + (None,) * (ctx.n_none - 1) + (dsinks.to(sink_t.dtype),)
 
     Func.__name__ = Func.__qualname__ = class_name
 
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None):
+                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None):
+            _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed)
             return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group)
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None):
+                          group=None, *, sinks=None):
+            _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed)
             return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
                               softcap, alibi_slopes, deterministic, return_attn_probs, group)
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None):
+                           group=None, *, sinks=None):
+            _check_sinks(sinks, qkv[:, 0], dropout_p, softcap, alibi_slopes, packed)
             return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group)
     else:
         def last(attn_type, processor=None):      # the Function's trailing arguments
             return (attn_type, processor)[:len(extra)]
 
-        def head0_arg(dropout_head0):             # ... and the optional one behind them
-            return (dropout_head0,) if dropout_head0 else ()
+        def head0_arg(dropout_head0, sink_t=None):    # ... and the optional ones behind them
+            return (dropout_head0, sink_t) if sink_t is not None else ((dropout_head0,) if dropout_head0 else ())
 
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0):
+                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None):
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
                 res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                            window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor,
-                           dropout_head0=dropout_head0)
+                           dropout_head0=dropout_head0, sinks=sinks)
                 return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
-            if not needs_grad(q, k, v):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
+            if not needs_grad(q, k, v, *(() if sinks is None else (sinks,))):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
                 out, lse = run_forward(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group,
-                                       dict(zip(extra, last(attn_type, attn_processor))), dropout_head0)[4:6]
+                                       dict(zip(extra, last(attn_type, attn_processor))), dropout_head0, sinks)[4:6]
                 return result(out, lse, (), return_attn_probs)
             return Func.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
-                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0))
+                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0, sinks))
 
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0):
+                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None):
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0))
+                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks))
 
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0):
+                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None):
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
-                              alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0))
+                              alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type),
+                              *head0_arg(dropout_head0, sinks))
 
     for fn, suffix in ((func, "_func"), (kvpacked_func, "_kvpacked_func"), (qkvpacked_func, "_qkvpacked_func")):
         fn.__name__ = fn.__qualname__ = stem + suffix

@@ -124,15 +124,17 @@ def basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, lse, delta, softmax
 def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                             attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None,
-                            rng_state=None):
-    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
+                            rng_state=None, sinks=None):
+    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `sinks`: one logit per query head; it rides on
+    the launch that opens the rows' state (step 0; the window planner's first block), at any ring degree.  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None
     dr = ring_dropout(dropout_p, rng_state)
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr)
+    block_pieces.refuse_sinks(sinks, pieces)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks)
     if pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     B, S, H, D = q.shape
@@ -168,26 +170,29 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
                              dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                              alibi_slopes=None, deterministic=False,
                              attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None,
-                             rng_state=None):
-    """`rng_state`: as the forward's (the same state regenerates its mask).  `defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
+                             rng_state=None, sinks=None):
+    """`rng_state`: as the forward's (the same state regenerates its mask).  `sinks`: as the forward's; `softmax_lse` holds them, the
+    block kernels are unchanged, and this rank's share of their gradient (its rows) is returned as a fourth, fp32 element.  `defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
     ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or dq_first is not None
     dr = ring_dropout(dropout_p, rng_state)
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr)
+    block_pieces.refuse_sinks(sinks, pieces)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks)
     if pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S, H, D = q.shape
     dev = q.device
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)
     be.delta(dout, out, delta)
+    with_dsinks = (lambda g: g) if sinks is None else (lambda g, ds=be.sink_grad(softmax_lse, delta): tuple(g) + (ds,))
     if P == 1:   # one block: the kernels round the gradients to q.dtype in their epilogues
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale, bool(causal),
                dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)))
-        return dq, dk, dv
+        return with_dsinks((dq, dk, dv))
     win = _ring_window(window_size, P)
     dq_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev)
     if win is not None:              # USP_RING_WINDOW=global: every block straight to its owner, only the rows it has gradients for
@@ -202,7 +207,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
         dk_acc, dv_acc = return_dkdv_direct(process_group, k, v, win_block, plan.key_extent, be,
                                             relay_kw=dict(recv_steps=plan.recv, send_steps=plan.send))
-        return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
+        return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
     def block(step, kk, vv, dk_dst, dv_dst):
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
@@ -215,9 +220,9 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     # under causal only steps <= rank compute (:93-122)
     dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: None if (causal and step > rank) else FULL)
-    return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
+    return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
 
 (RingFlashAttnFunc, ring_flash_attn_func, ring_flash_attn_kvpacked_func, ring_flash_attn_qkvpacked_func) = ring_front_end(
     "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, attn_processor=True,
-    window_in_forward=True, alibi_in_forward=True, dropout=True, dropout_in_forward=True)
+    window_in_forward=True, alibi_in_forward=True, dropout=True, dropout_in_forward=True, sinks=True)

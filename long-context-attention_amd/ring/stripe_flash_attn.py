@@ -51,13 +51,14 @@ def stripe_bwd_fold(be, r, step, dk_acc, dv_acc, dk_blk, dv_blk):
 
 def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                               window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                              attn_type: AttnType = AttnType.HIP, overlap=False, rng_state=None):
+                              attn_type: AttnType = AttnType.HIP, overlap=False, rng_state=None, sinks=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, use ring flash attn instead"
     P, r = group_info(dist, process_group)
     assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
     dr = ring_dropout(dropout_p, rng_state)      # (p, seed, head0) | None: ring degree 1 only (ring/front_end.py: _check_dropout)
     assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr)
+    # `sinks`: one logit per query head, on the launch that opens the rows' state (step 0, every row), at any ring degree
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
@@ -73,22 +74,24 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
 def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,
                                dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                                alibi_slopes=None, deterministic=False, attn_type: AttnType = AttnType.HIP,
-                               overlap=False, defer=None, rng_state=None):
+                               overlap=False, defer=None, rng_state=None, sinks=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, ring flash attn instead"
     P, r = group_info(dist, process_group)
     assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
     dr = ring_dropout(dropout_p, rng_state)
     assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr)
+    be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
     B, S, H, D = q.shape
     dev = q.device
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)
     be.delta(dout, out, delta)
+    # sinks: this rank's share of their gradient (its rows) from the global lse, a fourth fp32 element of the result
+    with_dsinks = (lambda g: g) if sinks is None else (lambda g, ds=be.sink_grad(softmax_lse, delta): tuple(g) + (ds,))
     if P == 1:
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale, True,
                dq16=dq, dk16=dk, dv16=dv)
-        return dq, dk, dv
+        return with_dsinks((dq, dk, dv))
     dq_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev)
 
     def block(step, kk, vv, dk_dst, dv_dst):
@@ -101,8 +104,8 @@ def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, s
     # steps > rank see k[:, :-1] only (:137-160, :179-181); a one-token shard has nothing to do there
     dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: FULL if step <= rank else (slice(0, S - 1) if S > 1 else None))
-    return final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc))
+    return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
 
 (StripeFlashAttnFunc, stripe_flash_attn_func, stripe_flash_attn_kvpacked_func, stripe_flash_attn_qkvpacked_func) = ring_front_end(
-    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, dropout=True)
+    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, dropout=True, sinks=True)

@@ -201,19 +201,22 @@ def _final_rows(be, q, kp, vp, softmax_scale, lse, out, acc, lo, hi, tail):
 
 
 def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None, alibi=None,
-                          dropout=None):
+                          dropout=None, sinks=None):
     """The zigzag ring forward as a generator of two phases.  With `first` beside a ring (degree > 1) it yields ONCE, behind the
     launch on the owned chunk and in front of the wait for the caller's exchange -- the caller may start other head groups' owned
     chunks there -- and returns (out, lse) through StopIteration; otherwise it never yields.  zigzag_ring_flash_attn_forward drives it
     to the end.
     `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same.
     `alibi`: flash-attn's alibi_slopes, served where the ring is ONE block (ring degree 1, no pieces).
-    `dropout`: (p, seed, head0), likewise (ring/front_end.py: _check_dropout)."""
+    `dropout`: (p, seed, head0), likewise (ring/front_end.py: _check_dropout).
+    `sinks`: one logit per query head, on the launch that opens the rows' state (step 0, every row), at any ring degree; not with
+    `first` / `tail` (ring/block_pieces.py: refuse_sinks)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None          # (the caller has exchanges in flight by definition)
     assert alibi is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
     assert dropout is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi, dropout=dropout)
+    block_pieces.refuse_sinks(sinks, pieces)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi, dropout=dropout, sinks=sinks)
     B, S2, H, D = q.shape
     assert S2 % 2 == 0, "zigzag layout needs an even local sequence length"
     if P == 1 and pieces:
@@ -269,8 +272,8 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
 def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                                    window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                                    deterministic=False, attn_type: AttnType = AttnType.HIP, overlap=False, first=None, tail=None,
-                                   rng_state=None):
-    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it; ring degree 1 only).
+                                   rng_state=None, sinks=None):
+    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it; ring degree 1 only).  `sinks`: zigzag_forward_phases.
     `overlap`: the caller has transfers of its own in flight (pipelined Ulysses exchange), so the kernels are
     launched so that collectives can run beside them even at ring degree 1.
     `first` = (u, (q, k, v) of the owned chunk, wait): q / k / v are still in flight (the caller's Ulysses exchange at degree
@@ -282,7 +285,7 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
     Either one means transfers in flight: the kernels are launched as under `overlap`."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap, alibi_slopes,
-                                ring_dropout(dropout_p, rng_state))
+                                ring_dropout(dropout_p, rng_state), sinks)
     try:
         while True:
             next(gen)
@@ -294,8 +297,9 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
                                     dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                                     alibi_slopes=None, deterministic=False,
                                     attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None,
-                                    rng_state=None):
-    """`rng_state`: as the forward's.
+                                    rng_state=None, sinks=None):
+    """`rng_state`: as the forward's.  `sinks`: as the forward's; this rank's share of their gradient (its rows, from the global
+    lse) is returned as a fourth, fp32 element.
     `dq_first(dq)`: the LAST ring step issues its dQ launch in front of its dK/dV launch and rounds dQ in that launch's
     epilogue (rows the step does not touch are cast from the accumulator); `dq_first` is called with the final 16-bit dq
     between the two launches, so that the caller's exchange of dq -- most of the bytes of the gradient exchange -- runs beside
@@ -316,7 +320,8 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     assert alibi_slopes is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
     dr = ring_dropout(dropout_p, rng_state)
     assert dr is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi_slopes, dropout=dr)
+    block_pieces.refuse_sinks(sinks, pieces)
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
     if P == 1 and pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S2, H, D = q.shape
@@ -326,10 +331,11 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     delta = torch.empty((B, H, S2), dtype=torch.float32, device=dev)
     if first is None:
         be.delta(dout, out, delta)
+    with_dsinks = (lambda g: g) if sinks is None else (lambda g, ds=be.sink_grad(lse, delta): tuple(g) + (ds,))
     if P == 1:   # one block: the kernels round the gradients to q.dtype in their epilogues
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         be.bwd(dout, q, k, v, lse, delta, None, None, None, softmax_scale, True, dq16=dq, dk16=dk, dv16=dv)
-        return dq, dk, dv
+        return with_dsinks((dq, dk, dv))
     dq_acc = torch.empty((B, S2, H, D), dtype=torch.float32, device=dev)
 
     dq_done = []
@@ -365,10 +371,10 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     # steps s <= rank carry gradients for the front-half K/V rows only (:151-155, :161-170)
     dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: slice(0, c) if step <= rank else FULL, split_block=split_steps())
-    return final_grads(be, (q, k, v), (dq_done[0] if dq_done else dq_acc, dk_acc, dv_acc))
+    return with_dsinks(final_grads(be, (q, k, v), (dq_done[0] if dq_done else dq_acc, dk_acc, dv_acc)))
 
 
 (ZigZagRingFlashAttnFunc, zigzag_ring_flash_attn_func, zigzag_ring_flash_attn_kvpacked_func,
  zigzag_ring_flash_attn_qkvpacked_func) = ring_front_end(
     "zigzag_ring_flash_attn", "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward,
-    dropout=True)
+    dropout=True, sinks=True)

@@ -12,13 +12,16 @@ import torch.distributed as dist
 from torch import Tensor
 
 from .._C import dropout_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_alibi_slopes, local_heads
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_alibi_slopes, local_heads, local_sinks
 from ..kernels import AttnType, select_flash_attn_impl
 
 
 class UlyssesAttention(torch.nn.Module):
     """Constructor arguments as in the reference: sequence_process_group, scatter_idx (2 = heads), gather_idx
-    (1 = sequence), use_sync (synchronise the device after each exchange), attn_type (any dense AttnType)."""
+    (1 = sequence), use_sync (synchronise the device after each exchange), attn_type (any dense AttnType).
+    forward takes the keyword-only `sinks`: one learned logit per head of the layer, (H,) (or per local head, (H / N,)), fp32 or
+    the operands' type, cut to this rank's heads by slicing.  It is a parameter replicated over the group: each rank's gradient
+    holds its own heads and zeros elsewhere, the SUM over the group is the gradient, and the layer does no all-reduce."""
 
     def __init__(self, sequence_process_group: dist.ProcessGroup = None, scatter_idx: int = 2,
                  gather_idx: int = 1, use_sync: bool = False, attn_type: AttnType = AttnType.FA) -> None:
@@ -36,7 +39,7 @@ class UlyssesAttention(torch.nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                return_attn_probs=False, *args: Any) -> Tensor:
+                return_attn_probs=False, *args: Any, sinks=None) -> Tensor:
         if alibi_slopes is not None:     # slopes over the layer's heads are cut to this rank's (comm/all_to_all.py: local_heads)
             if (self.scatter_idx, self.gather_idx) != (2, 1):
                 raise NotImplementedError("alibi_slopes needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
@@ -49,5 +52,9 @@ class UlyssesAttention(torch.nn.Module):
             if (self.scatter_idx, self.gather_idx) != (2, 1):
                 raise NotImplementedError("dropout_p != 0 needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
             options["dropout_head0"] = local_heads(query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg)).start
+        if sinks is not None:
+            if (self.scatter_idx, self.gather_idx) != (2, 1):
+                raise NotImplementedError("sinks needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
+            options["sinks"] = local_sinks(sinks, query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
         attended = self.attn_fn(q, k, v, **options)
         return self._to_seq(attended[0] if isinstance(attended, tuple) else attended)
