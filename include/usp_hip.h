@@ -118,6 +118,9 @@ enum {
 /* USP_ATTN_SINK: a FEATURE bit like USP_ATTN_ALIBI: the library exports usp_flash_fwd_sink / usp_sink_bwd (below), which take a
  * learned per-head sink logit beside the unchanged argument blocks (ABI still v7). */
 #define USP_ATTN_SINK 1024
+/* USP_ATTN_DOC: a FEATURE bit like USP_ATTN_ALIBI: the library exports usp_flash_fwd_doc / usp_flash_bwd_doc (below), which take a
+ * per-row left key bound (the document mask of packed pre-training sequences) beside the unchanged argument blocks (ABI still v7). */
+#define USP_ATTN_DOC 2048
 
 typedef struct usp_tensor {
   void* ptr;
@@ -368,6 +371,44 @@ int usp_sink_bwd(int32_t B, int32_t S, int32_t H, const float* sinks, const floa
                  int64_t lse_stride_h, const float* delta, int64_t delta_stride_b, int64_t delta_stride_h, float* dsinks,
                  int32_t accum, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Document mask: usp_flash_fwd / usp_flash_bwd with a left key bound read per row.  A sequence that packs several documents must
+ * keep every row from attending across a document boundary; for one launch (a whole sequence, or one block of a ring) that is
+ *     row i sees key j   iff   j >= row_lo[i]   and   the mask of the argument block (causal, ragged Sk) lets it,
+ * with row_lo (HOST-computed, DEVICE int32, (Sq,) per batch entry: row i of batch b at row_lo[b * row_lo_stride_b + i]; stride 0:
+ * one array for the whole batch; the arrays are shared by all heads) in the LAUNCH'S OWN key numbering: row_lo[i] in [0, Sk] is
+ * the first key row i sees, Sk = it sees none.  The backward's dK/dV launch owns keys and takes the transpose,
+ *     key_hi[j] in [0, Sq] = one past the last row that sees key j under this bound  ( = #{ i : row_lo[i] <= j } ),
+ * (Sk,) per batch entry with key_hi_stride_b.  BOTH ARRAYS MUST BE NON-DECREASING and describe the same set: that is what makes
+ * an item's streamed tiles and a wave's masked tiles two array reads (csrc/usp_tile_range.h), and it holds for documents laid
+ * out in order.  The library cannot check it.  Arrays that break it give wrong results, never an out-of-range access: every
+ * value read is clamped to [0, Sk] / [0, Sq].
+ * Nothing else about the function changes: `lse` is the logsumexp over the visible keys; a row that sees no key gives out = 0,
+ * lse = -inf and zero gradients, as ever.  A row tile never touches the key tiles in front of its first row's bound, and a
+ * key block never the row tiles behind its last key's: eight equal documents cost about an eighth of the causal triangle.
+ *   - row_lo == NULL (backward: and key_hi == NULL) is exactly usp_flash_fwd / usp_flash_bwd: the same kernels, bit-identical
+ *     results, the strides ignored.  An all-zero row_lo (one document) runs the document kernels and gives the same bits as
+ *     the two-waves-per-SIMD family (USP_FORCE_WAVE32);
+ *   - backward: the dQ launch reads row_lo and the dK/dV launch reads key_hi.  Exactly one of them NULL is USP_EINVAL, unless
+ *     USP_BWD_SKIP_* drops the launch that would read the missing one;
+ *   - causal may be 0 or 1: a ring block that lies wholly below the diagonal is a full block with a left bound;
+ *   - a negative stride is USP_EINVAL;
+ *   - USP_ATTN_SOFTCAP, USP_ATTN_WINDOW, USP_ATTN_SHIFT, a packed batch (seq_q / seq_k) and USP_FORCE_ROW64 are
+ *     USP_EUNSUPPORTED, nothing launched or written (these checks follow the argument checks every call gets, as for ALiBi);
+ *   - k_splits, dq_splits and dkdv_splits are IGNORED with the arrays: the launch is served uncut and never refused for them.
+ *     The workspace functions are unchanged; a workspace sized for cuts is merely not used for them (the dkdv_heads partials
+ *     still are).  Cuts under a per-row bound are later work;
+ *   - every head dim runs on the two-waves-per-SIMD family (document instantiations of its kernels: the forward keeps the
+ *     pipelined loop for the tiles the bound cuts for no row of the item, as the window kernel does); usp_last_launch_kinds()
+ *     reports the wave8 / wave4 / reduce bits that were launched.
+ * Everything else is as the argument block says (dkdv_heads, merge_in, final_begin / final_end with acc, USP_LAUNCH_INTERLEAVE,
+ * USP_BWD_SKIP_*, GQA, dq16 / dk16 / dv16, both 16-bit types, head dims 32 / 64 / 128, any aligned layout).  The document mask
+ * together with ALiBi, dropout or sinks has no entry point.
+ * -------------------------------------------------------------------------------------------- */
+int usp_flash_fwd_doc(const usp_fwd_args* args, const int32_t* row_lo, int64_t row_lo_stride_b, void* stream);
+int usp_flash_bwd_doc(const usp_bwd_args* args, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* key_hi,
+                      int64_t key_hi_stride_b, void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -468,7 +509,7 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
- * USP_ATTN_DROPOUT | USP_ATTN_SINK, the last three feature bits: the *_alibi / *_dropout / *_sink entry points exist).  Unknown flag bits are not rejected by
+ * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC, the last four feature bits: the *_alibi / *_dropout / *_sink / *_doc entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

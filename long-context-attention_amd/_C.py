@@ -31,6 +31,7 @@ USP_ATTN_SHIFT = 128           # the mask_shift field is valid: (Sk - Sq) + mask
 USP_ATTN_ALIBI = 256           # feature bit of usp_attn_features(): usp_flash_fwd_alibi / usp_flash_bwd_alibi exist (not an args flag)
 USP_ATTN_DROPOUT = 512         # feature bit of usp_attn_features(): usp_flash_fwd_dropout / usp_flash_bwd_dropout exist (not an args flag)
 USP_ATTN_SINK = 1024           # feature bit of usp_attn_features(): usp_flash_fwd_sink / usp_sink_bwd exist (not an args flag)
+USP_ATTN_DOC = 2048            # feature bit of usp_attn_features(): usp_flash_fwd_doc / usp_flash_bwd_doc exist (not an args flag)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -112,7 +113,7 @@ class UspBwdArgs(ctypes.Structure):
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
-           "usp_flash_fwd_sink", "usp_sink_bwd")
+           "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc")
 # The two *_alibi entry points are the only exports load() does not insist on: they are looked up and prototyped on first use
 # (_alibi_entry), behind the feature bit, so a library built before them still loads and serves everything else.
 ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
@@ -120,6 +121,8 @@ ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
 DROPOUT_EXPORTS = ("usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
 # ... and the two sink entry points (_sink_entry, USP_ATTN_SINK)
 SINK_EXPORTS = ("usp_flash_fwd_sink", "usp_sink_bwd")
+# ... and the two document-mask entry points (_doc_entry, USP_ATTN_DOC)
+DOC_EXPORTS = ("usp_flash_fwd_doc", "usp_flash_bwd_doc")
 
 
 def lib_path() -> str:
@@ -138,7 +141,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -461,6 +464,50 @@ def _sink_entry(name: str):
     return fn
 
 
+def doc_value(doc, B: int, Sq: int, Sk: int, device):
+    """A block call's `doc` keyword -> ((row_lo, batch stride), (key_hi, batch stride)) as usp_flash_fwd_doc / usp_flash_bwd_doc
+    take them, or None when it is off.  `doc` = (row_lo, key_hi): contiguous int32 DEVICE tensors of shape (Sq,) or (B, Sq) and
+    (Sk,) or (B, Sk) in the launch's own coordinates (include/usp_hip.h; built on the host by ring/doc_blocks.py); either may be
+    None where the call does not read it (the forward reads row_lo alone).  Anything else raises ValueError.  (Pure argument
+    check: the CPU orchestration tests call it without a library.)"""
+    if doc is None:
+        return None
+    row_lo, key_hi = doc
+    if row_lo is None and key_hi is None:
+        return None
+
+    def one(t, n, what):
+        if t is None:
+            return None, 0
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise ValueError(f"doc {what} must be an int32 torch.Tensor")
+        if tuple(t.shape) not in ((n,), (B, n)) or not t.is_contiguous():
+            raise ValueError(f"doc {what} must be contiguous with shape ({n},) or ({B}, {n}), got {tuple(t.shape)}")
+        if t.device != torch.device(device):
+            raise ValueError(f"doc {what} is on {t.device}, the operands on {device}")
+        return t, (n if t.dim() == 2 else 0)
+    return one(row_lo, Sq, "row_lo"), one(key_hi, Sk, "key_hi")
+
+
+def _doc_entry(name: str):
+    """The document-mask entry point `name` (one of DOC_EXPORTS), prototyped on first use; a library without the feature bit
+    (built before the entry points: it loads, they are not insisted on) is refused."""
+    L = load()
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_DOC and hasattr(L, name)):
+        raise NotImplementedError(f"{_LIB_PATH} does not serve cu_doclens (USP_ATTN_DOC): rebuild it")
+    fn = getattr(L, name)
+    if fn.argtypes is None:
+        i64, vp = ctypes.c_int64, ctypes.c_void_p
+        fn.argtypes = ([ctypes.POINTER(UspFwdArgs), vp, i64, vp] if name == "usp_flash_fwd_doc" else
+                       [ctypes.POINTER(UspBwdArgs), vp, i64, vp, i64, vp])
+        fn.restype = ctypes.c_int
+    return fn
+
+
+def _ptr(t):
+    return ctypes.c_void_p(None if t is None else t.data_ptr())
+
+
 def _set_shift(a, shift: Optional[int]):
     """Set USP_ATTN_SHIFT + the field on an argument block (None = off); a library that does not report the bit would
     ignore it silently and compute another mask, so it is refused here."""
@@ -526,7 +573,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None, dropout=None, sinks=None):
+              alibi=None, dropout=None, sinks=None, doc=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -542,14 +589,17 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     mask of include/usp_hip.h and the kept ones rescaled (usp_flash_fwd_dropout; not with softcap, alibi or family="row64").
     `sinks`: one learned logit per query head (sinks_value), None = off: it joins every row's softmax denominator and carries no
     value; `lse` includes it (usp_flash_fwd_sink; a launch without merge_in only; not with softcap, alibi, dropout or
-    family="row64")."""
+    family="row64").
+    `doc`: (row_lo, key_hi) int32 device arrays (doc_value), None = off: row i sees key j only if j >= row_lo[i], the document
+    mask of one launch (usp_flash_fwd_doc; served uncut; not with window, softcap, shift, alibi, dropout, sinks or family="row64")."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
     cap = softcap_value(softcap)
     ff = _family_flag(family)
     win, sh = _window(window), _shift(shift)
+    dc = doc_value(doc, B, Sq, k.shape[1], q.device)     # None: off -- (None, None) included, which is the call without the keyword
     if k_splits is None:
-        n = 0 if sh is not None else fwd_k_splits(B, Sq, Hq, causal)
+        n = 0 if (sh is not None or dc is not None) else fwd_k_splits(B, Sq, Hq, causal)   # (a document launch is served uncut)
     else:
         n = int(k_splits)
     a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
@@ -567,6 +617,12 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
+    if dc is not None:
+        if al is not None or dr is not None or sk is not None:
+            raise NotImplementedError("cu_doclens together with alibi_slopes, dropout_p or sinks is not supported by the HIP attention kernels")
+        (rl, rl_sb), _ = dc
+        _check(_doc_entry("usp_flash_fwd_doc")(ctypes.byref(a), _ptr(rl), rl_sb, _stream()), "usp_flash_fwd_doc")
+        return
     if sk is not None:
         if al is not None or dr is not None:
             raise NotImplementedError("sinks together with alibi_slopes or dropout_p is not supported by the HIP attention kernels")
@@ -720,7 +776,7 @@ def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None, alibi=None, dropout=None):
+              softcap=None, shift=None, alibi=None, dropout=None, doc=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
@@ -729,7 +785,8 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`, `shift`: as flash_fwd (a
     shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle).  `alibi`: as flash_fwd
     (usp_flash_bwd_alibi).  `dropout`: as flash_fwd (usp_flash_bwd_dropout): the same tuple regenerates the forward's mask;
-    `delta` is that of the dropped `out`."""
+    `delta` is that of the dropped `out`.  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
+    key_hi; with `only` the other one may be None."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -751,8 +808,9 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     ff = _family_flag(family)
     a.flags = (USP_LAUNCH_INTERLEAVE if interleave else 0) | ff | {None: 0, "dkdv": USP_BWD_SKIP_DQ, "dq": USP_BWD_SKIP_DKDV}[only]
     sh = _shift(shift)
+    dc = doc_value(doc, B, Sq, Sk, q.device)             # None: off -- (None, None) included
     if splits is None:
-        a.dq_splits, a.dkdv_splits = (0, 0) if sh is not None else bwd_splits(B, Sq, Sk, Hq, bool(causal))
+        a.dq_splits, a.dkdv_splits = (0, 0) if (sh is not None or dc is not None) else bwd_splits(B, Sq, Sk, Hq, bool(causal))
     else:
         a.dq_splits, a.dkdv_splits = splits
     a.dkdv_heads = int(dkdv_heads)
@@ -770,6 +828,12 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
+    if dc is not None:
+        if al is not None or dr is not None:
+            raise NotImplementedError("cu_doclens together with alibi_slopes or dropout_p is not supported by the HIP attention kernels")
+        (rl, rl_sb), (kh, kh_sb) = dc
+        _check(_doc_entry("usp_flash_bwd_doc")(ctypes.byref(a), _ptr(rl), rl_sb, _ptr(kh), kh_sb, _stream()), "usp_flash_bwd_doc")
+        return
     if dr is not None:
         if al is not None:
             raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")

@@ -67,6 +67,14 @@ struct BwdArgsAL : BwdParams, BwdAlibi {};
 // Dropout (usp_flash_bwd_dropout): kernel arguments of the dropout instantiations only (usp_flash_bwd_dropout.hip); `Dropout`
 // is the forward's block (usp_dropout_rng.h).
 struct BwdArgsDR : BwdParams, Dropout {};
+// Document mask (usp_flash_bwd_doc): kernel arguments of the document instantiations only (usp_flash_bwd_doc.hip:
+// flash_bwd_doc_kernel, flash_bwd_dkdv_doc_kernel); every other kernel keeps its argument block and machine code.
+struct BwdDoc {
+  const int* row_lo;                    // int32 (Sq,): the first key row i sees (the dQ launch reads it); NULL with key_hi = no bound
+  const int* key_hi;                    // int32 (Sk,): one past the last row that sees key j (the dK/dV launch reads it)
+  int64_t row_lo_sb, key_hi_sb;         // batch strides in elements (0: one array for the whole batch)
+};
+struct BwdArgsDOC : BwdParams, BwdDoc {};
 
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the
@@ -116,5 +124,8 @@ int launch_dq_alibi(const BwdArgsAL& p, int D, int dtype, bool causal, int grid,
 // The dropout backward launches (usp_flash_bwd_dropout.hip), likewise.
 int launch_dkdv_dropout(const BwdArgsDR& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 int launch_dq_dropout(const BwdArgsDR& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+// The document-mask backward launches (usp_flash_bwd_doc.hip), likewise.
+int launch_dkdv_doc(const BwdArgsDOC& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+int launch_dq_doc(const BwdArgsDOC& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -24,14 +24,19 @@ namespace usp {
 // unchanged.  The body is shared by two __global__ templates so that the kernel without softcap keeps its symbol name
 // and machine code.
 // AL: ALiBi has instantiations of its own in usp_flash_bwd_alibi.hip (flash_bwd_alibi_kernel, flash_bwd_dkdv_alibi_kernel); the
-// kernels here compile the bodies with AL = false.  DR: dropout likewise (usp_flash_bwd_dropout.hip).
+// kernels here compile the bodies with AL = false.  DR: dropout likewise (usp_flash_bwd_dropout.hip).  DOC: the document mask
+// likewise (usp_flash_bwd_doc.hip).
 #define USP_BWD_NO_ALIBI                            \
   constexpr bool AL = false;                        \
   constexpr const float* al_slopes = nullptr;       \
   constexpr int64_t al_sb = 0;                      \
   constexpr int al_diag = 0;                        \
   constexpr bool DR = false;                        \
-  constexpr Dropout dr{};
+  constexpr Dropout dr{};                           \
+  constexpr bool DOC = false;                       \
+  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
+  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
+  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_kernel(
@@ -164,7 +169,7 @@ static int reduce_grid(int64_t items) { return (int)((items + 255) / 256 > 2048 
 // dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
 // the launch, the 8-wave kernel otherwise; then the sum over the partial slabs of a head-split / cut launch.
 template <int D, int DT>
-static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, bool causal, hipStream_t st, bool row64) {
+static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, const BwdDoc& doc, bool causal, hipStream_t st, bool row64) {
   p.nblk = (p.Sk + 127) / 128;
   p.n_items = p.B * p.Hkv * p.nblk * p.ngrp * p.qsplit;
   int rc = USP_ELAUNCH;
@@ -190,6 +195,11 @@ static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, bool
       static_cast<BwdParams&>(pd) = pb;
       static_cast<Dropout&>(pd) = dr;
       if (int rc2 = launch_dkdv_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
+    } else if (doc.key_hi) {                       // document mask: likewise (usp_flash_bwd_doc.hip)
+      BwdArgsDOC pd;
+      static_cast<BwdParams&>(pd) = pb;
+      static_cast<BwdDoc&>(pd) = doc;
+      if (int rc2 = launch_dkdv_doc(pd, D, DT, causal, grid, lds_q, st)) return rc2;
     } else
     with_causal(causal, [&](auto c) {
       constexpr bool C = decltype(c)::value;
@@ -209,7 +219,7 @@ static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, bool
 
 // dQ of a call: the one-wave-per-SIMD kernel (4 waves x 64 query rows, usp_flash_bwd_dq64.hip) or the 8-wave kernel, as above
 template <int D, int DT>
-static int launch_dq(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, bool causal, hipStream_t st, bool row64) {
+static int launch_dq(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, const BwdDoc& doc, bool causal, hipStream_t st, bool row64) {
   int rc = USP_ELAUNCH;
   if (row64 && launch_dq64(p, DT, causal, st, &rc)) {
     if (rc == USP_OK) launch_kinds_note(USP_KIND_DQ_ROW64);
@@ -232,6 +242,11 @@ static int launch_dq(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, bool c
     static_cast<BwdParams&>(pd) = pb;
     static_cast<Dropout&>(pd) = dr;
     if (int rc2 = launch_dq_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
+  } else if (doc.row_lo) {                         // document mask: likewise (usp_flash_bwd_doc.hip)
+    BwdArgsDOC pd;
+    static_cast<BwdParams&>(pd) = pb;
+    static_cast<BwdDoc&>(pd) = doc;
+    if (int rc2 = launch_dq_doc(pd, D, DT, causal, grid, lds_q, st)) return rc2;
   } else
   with_causal(causal, [&](auto c) {
     constexpr bool C = decltype(c)::value;
@@ -252,17 +267,17 @@ static int launch_reduce_cuts(const BwdParams& p, hipStream_t st) {
 }
 
 template <int D, int DT>
-static int launch_bwd(BwdArgsSC p, const BwdAlibi& al, const Dropout& dr, bool causal, hipStream_t st, int force, int skip) {
+static int launch_bwd(BwdArgsSC p, const BwdAlibi& al, const Dropout& dr, const BwdDoc& doc, bool causal, hipStream_t st, int force, int skip) {
   const bool want_dkdv = !(skip & USP_BWD_SKIP_DKDV), want_dq = !(skip & USP_BWD_SKIP_DQ);
   // per call, `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32 (include/usp_hip.h) picks the family; forced onto the 64-row
   // family, only the launches that will run have to be served
   if ((force & USP_FORCE_ROW64) && !(D == 128 && (!want_dkdv || dkdv64_serves(p)) && (!want_dq || dq64_serves(p))))
     return USP_EUNSUPPORTED;
   // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
-  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !al.al_slopes && !dr.t;   // (... and no ALiBi or dropout step)
+  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !al.al_slopes && !dr.t && !doc.row_lo && !doc.key_hi;   // (... and no ALiBi, dropout or document step)
   int rc = USP_OK;
-  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, al, dr, causal, st, row64)) != USP_OK) return rc;
-  if (want_dq && (rc = launch_dq<D, DT>(p, al, dr, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
+  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, al, dr, doc, causal, st, row64)) != USP_OK) return rc;
+  if (want_dq && (rc = launch_dq<D, DT>(p, al, dr, doc, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
   return rc;
 }
 
@@ -330,9 +345,10 @@ extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
   return pl.dkdv_bytes + pl.dq_bytes;
 }
 
-// usp_flash_bwd (alibi_slopes == NULL, p_drop == 0), usp_flash_bwd_alibi and usp_flash_bwd_dropout
-static int flash_bwd_call(const usp_bwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, const usp::DropoutCall& dc,
-                          void* stream) {
+// usp_flash_bwd (alibi_slopes == NULL, p_drop == 0, no document array), usp_flash_bwd_alibi, usp_flash_bwd_dropout and usp_flash_bwd_doc
+static int flash_bwd_call(const usp_bwd_args* a_in, const float* alibi_slopes, int64_t alibi_stride_b, const usp::DropoutCall& dc,
+                          const usp::BwdDoc& doc, void* stream) {
+  const usp_bwd_args* a = a_in;
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse || !a->delta) return USP_EINVAL;
@@ -343,6 +359,10 @@ static int flash_bwd_call(const usp_bwd_args* a, const float* alibi_slopes, int6
   if (int rc = check_alibi(*a, alibi_slopes, alibi_stride_b)) return rc;
   Dropout dr;
   if (int rc = check_dropout(*a, dc, &dr)) return rc;
+  const bool has_doc = doc.row_lo || doc.key_hi;
+  // the dQ launch reads row_lo, the dK/dV launch key_hi: the array of a launch that runs must be there
+  if (has_doc && ((!(skip & USP_BWD_SKIP_DQ) && !doc.row_lo) || (!(skip & USP_BWD_SKIP_DKDV) && !doc.key_hi))) return USP_EINVAL;
+  if (int rc = check_doc(*a, has_doc, doc.row_lo_sb, doc.key_hi_sb)) return rc;
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
@@ -360,6 +380,8 @@ static int flash_bwd_call(const usp_bwd_args* a, const float* alibi_slopes, int6
   const Mask mask = decode_mask(*a);
   if (packed && (mask.windowed || mask.shifted)) return USP_EUNSUPPORTED;        // dense launches only
   if (a->dq_splits < 0 || a->dq_splits > 8 || a->dkdv_splits < 0 || a->dkdv_splits > 8) return USP_EINVAL;
+  usp_bwd_args uncut;                              // a document launch is served uncut (usp_hip.h): the plan of the same call without cuts
+  if (has_doc) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
   const BwdPlan plan = plan_bwd(a);
   if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
   BwdArgsSC p;
@@ -417,17 +439,24 @@ static int flash_bwd_call(const usp_bwd_args* a, const float* alibi_slopes, int6
   const BwdAlibi al{alibi_slopes, alibi_stride_b, alibi_diag(*a)};
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
-    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, al, dr, mask.causal, (hipStream_t)stream, force, skip);
+    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, al, dr, doc, mask.causal, (hipStream_t)stream, force, skip);
   });
 }
 
-extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) { return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{}, stream); }
+extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) { return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{}, usp::BwdDoc{}, stream); }
 
 extern "C" int usp_flash_bwd_alibi(const usp_bwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
-  return flash_bwd_call(a, alibi_slopes, alibi_stride_b, usp::DropoutCall{}, stream);
+  return flash_bwd_call(a, alibi_slopes, alibi_stride_b, usp::DropoutCall{}, usp::BwdDoc{}, stream);
 }
 
 extern "C" int usp_flash_bwd_dropout(const usp_bwd_args* a, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
                                      void* stream) {
-  return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{p_drop, seed, row0, key0, head0}, stream);
+  return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{p_drop, seed, row0, key0, head0}, usp::BwdDoc{}, stream);
+}
+
+extern "C" int usp_flash_bwd_doc(const usp_bwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* key_hi,
+                                 int64_t key_hi_stride_b, void* stream) {
+  const bool any = row_lo || key_hi;
+  return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{}, usp::BwdDoc{row_lo, key_hi, any ? row_lo_stride_b : 0, any ? key_hi_stride_b : 0},
+                        stream);
 }

@@ -18,6 +18,10 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_alibi_kernel(const BwdArgsAL
   const int al_diag = p_in.al_diag;
   constexpr bool DR = false;
   constexpr Dropout dr{};
+  constexpr bool DOC = false;
+  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
+  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;
+  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
 #include "usp_flash_bwd_dq_body.inc"
 }
 
@@ -30,6 +34,10 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_alibi_kernel(const BwdA
   const int al_diag = p_in.al_diag;
   constexpr bool DR = false;
   constexpr Dropout dr{};
+  constexpr bool DOC = false;
+  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
+  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;
+  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

@@ -2,8 +2,9 @@
 // Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
 // the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones, the dropout kernels
-// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones.  The including kernel defines `p_in`, SC / AL / DR, sc_cl2 / sc_k2,
-// al_slopes / al_sb / al_diag and `dr` (usp_dropout_rng.h: Dropout).
+// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones, the document kernels (usp_flash_bwd_doc.hip) the `if constexpr (DOC)`
+// ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
+// (usp_dropout_rng.h: Dropout) and doc_key_hi / doc_kh_sb (int32 key bounds and their batch stride).
 // Dropout: role A forms the un-dropped P, uses P o keep for its dV MFMAs and hands B the un-dropped P with the keep decision in
 // the sign bit (P >= 0: set = dropped; no extra LDS); role B starts its dP chain from -delta t/256 and forms
 // |P| (kept ? chain : -delta t/256); 256/t goes into the epilogue's factor of both outputs.
@@ -81,6 +82,17 @@
   if (p.qsplit > 1) {                            // this item's cut of the query tiles [t_begin, t_end): equal runs
     const usp_tile_run run = usp_equal_run(t_begin, t_end, p.qsplit, cut);
     t_begin = run.begin; t_end = run.end;
+  }
+  // DOC: row i sees key j only if i < key_hi[j] (monotone, usp_tile_range.h): the row tiles behind the last row that sees the
+  // block's last key are not streamed; the lane keeps its own key's bound, the wave the bounds of its first and last valid key
+  [[maybe_unused]] int doc_hi = 0, doc_hi_w0 = 0, doc_hi_w1 = 0;
+  if constexpr (DOC) {
+    const int* const kh = doc_key_hi + b * doc_kh_sb;
+    t_end = usp_doc_last_row_tile(usp_doc_key_hi(kh, own0 + OWN - 1, p.Sq, p.Sk), t_end, kTile);
+    if (t_begin > t_end) t_begin = t_end;
+    doc_hi = usp_doc_key_hi(kh, orow, p.Sq, p.Sk);
+    doc_hi_w0 = usp_doc_key_hi(kh, ow, p.Sq, p.Sk);
+    doc_hi_w1 = usp_doc_key_hi(kh, ow + 31, p.Sq, p.Sk);
   }
   const int n_iter = (t_end - t_begin) * p.gsub;
 
@@ -217,9 +229,13 @@
       if constexpr (DR) {
         if (ROLE == 0 && valid && tile == t_begin) dr_h = dr.head0 + (uint32_t)(h0 + dr_hh++);
       }
-      const bool active = valid && ow < p.Sk && (!CAUSAL || (s0 + kTile - 1 + off >= ow)) &&
-                          (!p.win_on || s0 <= ow + 31 - p.win_lo);
-      const bool need_mask = (CAUSAL && (s0 + off < ow + 31)) || (p.win_on && s0 + kTile - 1 > ow - p.win_lo);
+      bool active = valid && ow < p.Sk && (!CAUSAL || (s0 + kTile - 1 + off >= ow)) &&
+                    (!p.win_on || s0 <= ow + 31 - p.win_lo);
+      bool need_mask = (CAUSAL && (s0 + off < ow + 31)) || (p.win_on && s0 + kTile - 1 > ow - p.win_lo);
+      if constexpr (DOC) {
+        active = active && usp_doc_row_tile_live(s0, doc_hi_w1);
+        need_mask = need_mask || usp_doc_row_tile_masked(s0, kTile, doc_hi_w0);
+      }
 
       if (active) {
         USP_LDS const char* q_lds = smem + (ROLE == 0 ? buf_a : buf_b) * BUFB;   // Q tile
@@ -364,6 +380,12 @@
 #pragma unroll
             for (int r = 0; r < 16; ++r)
               if (dl < 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
+          }
+          if constexpr (DOC) {                                 // ... and only if i < key_hi[j]
+            const int dh = doc_hi - s0 - 4 * hi;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (dh <= 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
           }
         };
 

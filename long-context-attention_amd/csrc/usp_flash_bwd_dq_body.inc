@@ -2,8 +2,9 @@
 // Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
 // the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
 // the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones, the dropout kernels
-// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones.  The including kernel defines `p_in`, SC / AL / DR, sc_cl2 / sc_k2,
-// al_slopes / al_sb / al_diag and `dr` (usp_dropout_rng.h: Dropout).
+// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones, the document kernels (usp_flash_bwd_doc.hip) the `if constexpr (DOC)`
+// ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
+// (usp_dropout_rng.h: Dropout) and doc_row_lo / doc_rl_sb (int32 row bounds and their batch stride).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
@@ -76,6 +77,16 @@
     const int per = (t_end - t_begin + p.ksplit - 1) / p.ksplit;   // = usp_run_length: called, every stream changes
     t_begin = usp_run_begin(t_begin, t_end, per, cut);
     t_end = usp_run_end(t_begin, t_end, per);
+  }
+  // DOC: row i sees key j only if j >= row_lo[i] (monotone, usp_tile_range.h): the key tiles in front of the first key of the
+  // block's first row are not streamed; the lane keeps its own row's bound, the wave the bounds of its first and last valid row
+  [[maybe_unused]] int doc_lo = 0, doc_lo_w0 = 0, doc_lo_w1 = 0;
+  if constexpr (DOC) {
+    const int* const rl = doc_row_lo + b * doc_rl_sb;
+    t_begin = usp_doc_first_key_tile(usp_doc_row_lo(rl, own0, p.Sq, p.Sk), t_end, kTile);
+    doc_lo = usp_doc_row_lo(rl, orow, p.Sq, p.Sk);
+    doc_lo_w0 = usp_doc_row_lo(rl, ow, p.Sq, p.Sk);
+    doc_lo_w1 = usp_doc_row_lo(rl, ow + 31, p.Sq, p.Sk);
   }
   const int n_iter = t_end - t_begin;
 
@@ -182,8 +193,12 @@
     if (CAUSAL) wave_kv_end = usp_rows_key_end(ow, 32, p.Sq, p.Sk, 1, off);
     // active = usp_key_tile_live with wave_end = 0 for a wave past Sq, need_mask = usp_key_tile_masked (usp_tile_range.h):
     // called, either changes every stream
-    const bool active = ow < p.Sq && s0 < wave_kv_end && (!p.win_on || s0 + kTile - 1 >= ow + p.win_lo);
-    const bool need_mask = (s0 + kTile > p.Sk) || (CAUSAL && s0 + kTile - 1 > ow + off) || (p.win_on && s0 < ow + 31 + p.win_lo);
+    bool active = ow < p.Sq && s0 < wave_kv_end && (!p.win_on || s0 + kTile - 1 >= ow + p.win_lo);
+    bool need_mask = (s0 + kTile > p.Sk) || (CAUSAL && s0 + kTile - 1 > ow + off) || (p.win_on && s0 < ow + 31 + p.win_lo);
+    if constexpr (DOC) {
+      active = active && s0 + kTile > doc_lo_w0;                 // (usp_doc_key_tile_live's left-bound term)
+      need_mask = need_mask || usp_doc_key_tile_masked(s0, doc_lo_w1);
+    }
 
     if (active) {
       // Hand-pinned pipeline over the two 32-row halves h0, h1 of the tile (sched_barrier(0) fences;
@@ -206,7 +221,8 @@
         const int k0 = s0 + 32 * h + 4 * hi;            // key of register r: k0 + 8(r>>2) + (r&3)
         int klim = p.Sk - 1;
         if (CAUSAL) klim = orow + off < klim ? orow + off : klim;
-        const int klo = p.win_on ? orow + p.win_lo : -0x40000000;
+        int klo = p.win_on ? orow + p.win_lo : -0x40000000;
+        if constexpr (DOC) klo = doc_lo;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = k0 + (r & 3) + 8 * (r >> 2);

@@ -18,7 +18,11 @@ namespace usp {
   constexpr const float* al_slopes = nullptr;       \
   constexpr int64_t al_sb = 0;                      \
   constexpr int al_diag = 0;                        \
-  const Dropout& dr = p_in;
+  const Dropout& dr = p_in;                         \
+  constexpr bool DOC = false;                       \
+  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
+  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
+  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dropout_kernel(const BwdArgsDR p_in) {

@@ -35,6 +35,7 @@ namespace usp {
 // AL: ALiBi has instantiations of its own in usp_flash_fwd_alibi.hip (flash_fwd_alibi_kernel); the kernels here compile the body
 // with AL = false.  DR: dropout likewise (usp_flash_fwd_dropout.hip: flash_fwd_dropout_kernel).  SINK: attention sinks likewise
 // (usp_flash_fwd_sink.hip: flash_fwd_sink_kernel, the loops of the split and window kernels here with one more epilogue step).
+// DOC: the document mask likewise (usp_flash_fwd_doc.hip: flash_fwd_doc_kernel, the plain kernel's loops under the window walk).
 #define USP_FWD_NO_ALIBI                            \
   constexpr bool AL = false;                        \
   constexpr const float* al_slopes = nullptr;       \
@@ -43,7 +44,10 @@ namespace usp {
   constexpr bool DR = false;                        \
   constexpr Dropout dr{};                           \
   constexpr bool SINK = false;                      \
-  constexpr const float* sink_s = nullptr;
+  constexpr const float* sink_s = nullptr;          \
+  constexpr bool DOC = false;                       \
+  constexpr const int* doc_row_lo = nullptr;        \
+  constexpr int64_t doc_sb = 0;
 
 template <int D, int DT, bool CAUSAL, int NWAVES, bool KSPLIT = false>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_kernel(const FwdArgsT<KSPLIT> p_in) {
@@ -138,7 +142,7 @@ int launch_split_merge(const FwdArgsT<true>& p, int dtype, int D, hipStream_t st
 }
 
 template <int D, int DT, int NWAVES>
-static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, const float* sinks, bool causal, hipStream_t st) {
+static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, const float* sinks, const FwdDoc& doc, bool causal, hipStream_t st) {
   p.nq = (p.Sq + 32 * NWAVES - 1) / (32 * NWAVES);
   p.n_items = p.B * p.Hq * p.nq * p.ksplit;
   // persistent launch: one workgroup per resident slot (8 waves: 1 per CU, 4 waves: 2 per CU)
@@ -162,6 +166,11 @@ static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, cons
     static_cast<FwdArgsT<true>&>(pk) = ps;
     pk.sinks = sinks;
     if (int rc = launch_fwd_sink(pk, D, DT, causal, NWAVES, grid, lds, st)) return rc;
+  } else if (doc.row_lo) {                                   // document mask: likewise (usp_flash_fwd_doc.hip)
+    FwdArgsDOC pd;
+    static_cast<FwdParams&>(pd) = p;
+    static_cast<FwdDoc&>(pd) = doc;
+    if (int rc = launch_fwd_doc(pd, D, DT, causal, NWAVES, grid, lds, st)) return rc;
   } else
   with_causal(causal, [&](auto c) {
     constexpr bool C = decltype(c)::value;
@@ -183,14 +192,15 @@ static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, cons
 }
 
 template <int D, int DT>
-static int launch_fwd(const FwdArgsSC& p, const FwdAlibi& al, const Dropout& dr, const float* sinks, bool causal, hipStream_t st, int force) {
+static int launch_fwd(const FwdArgsSC& p, const FwdAlibi& al, const Dropout& dr, const float* sinks, const FwdDoc& doc, bool causal, hipStream_t st,
+                      int force) {
   // Workgroup shape: 8 waves (256 query rows, one workgroup per CU) stage K/V once per 256 rows and win by
   // 3-4 % whenever they can give every CU work; 4 waves (128 rows, two workgroups per CU) are used only
   // when the 8-wave item list is shorter than the CU count, or for short causal sequences (<= 1024 rows:
   // +3...8 %) (measured with persistent workgroups, profiles/).  Per call, `force` (USP_FORCE_ROW64 / USP_FORCE_WAVE32,
   // include/usp_hip.h) picks the family.  `waves` = 4 | 8, or 64: the 4 x 64-row kernel of usp_flash_fwd64.hip.
   // what usp_flash_fwd64.hip serves (plain and K-split launches; its hand-pinned pipeline has no softcap step)
-  const bool fwd64_ok = D == 128 && !p.seq_q && !p.win_on && !p.cap_on && !al.al_slopes && !dr.t && !sinks;   // (... and no ALiBi, dropout or sink step)
+  const bool fwd64_ok = D == 128 && !p.seq_q && !p.win_on && !p.cap_on && !al.al_slopes && !dr.t && !sinks && !doc.row_lo;   // (... and no ALiBi, dropout, sink or document step)
   const int split_kind = p.ksplit > 1 ? USP_KIND_FWD_SPLIT_MERGE : 0;
   int waves = 64;
   if (!(force & USP_FORCE_ROW64)) {
@@ -222,7 +232,7 @@ static int launch_fwd(const FwdArgsSC& p, const FwdAlibi& al, const Dropout& dr,
     if (force & USP_FORCE_ROW64) return USP_EUNSUPPORTED;
     waves = 8;                                               // (a layout the 64-row kernel declines)
   }
-  const int rc = waves == 4 ? launch_fwd_w<D, DT, 4>(p, al, dr, sinks, causal, st) : launch_fwd_w<D, DT, 8>(p, al, dr, sinks, causal, st);
+  const int rc = waves == 4 ? launch_fwd_w<D, DT, 4>(p, al, dr, sinks, doc, causal, st) : launch_fwd_w<D, DT, 8>(p, al, dr, sinks, doc, causal, st);
   if (rc == USP_OK) launch_kinds_note((waves == 4 ? USP_KIND_FWD_WAVE4 : USP_KIND_FWD_WAVE8) | split_kind);
   return rc;
 }
@@ -235,9 +245,10 @@ extern "C" int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* a, int32_t 
   return (int64_t)k_splits * (rows * a->D + rows) * 4;         // partial outputs + partial LSEs, fp32 (a->D % 4 == 0)
 }
 
-// usp_flash_fwd (alibi_slopes == NULL, p_drop == 0, sinks == NULL), usp_flash_fwd_alibi, usp_flash_fwd_dropout and usp_flash_fwd_sink
+// usp_flash_fwd (alibi_slopes == NULL, p_drop == 0, sinks == NULL, row_lo == NULL), usp_flash_fwd_alibi, usp_flash_fwd_dropout,
+// usp_flash_fwd_sink and usp_flash_fwd_doc
 static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, const usp::DropoutCall& dc,
-                          const float* sinks, void* stream) {
+                          const float* sinks, const usp::FwdDoc& doc, void* stream) {
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse) return USP_EINVAL;
@@ -247,6 +258,7 @@ static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int6
   Dropout dr;
   if (int rc = check_dropout(*a, dc, &dr)) return rc;
   if (int rc = check_sink(*a, sinks)) return rc;
+  if (int rc = check_doc(*a, doc.row_lo != nullptr, doc.row_lo_sb, 0)) return rc;
   if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
@@ -284,7 +296,7 @@ static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int6
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  if (a->k_splits > 1 && a->workspace != nullptr) {
+  if (a->k_splits > 1 && a->workspace != nullptr && !doc.row_lo) {   // (a document launch is served uncut: usp_hip.h)
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
     if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
@@ -296,21 +308,25 @@ static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int6
   const FwdAlibi al{alibi_slopes, alibi_stride_b, alibi_diag(*a)};
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
-    return launch_fwd<decltype(d)::value, decltype(dt)::value>(p, al, dr, sinks, mask.causal, (hipStream_t)stream, force);
+    return launch_fwd<decltype(d)::value, decltype(dt)::value>(p, al, dr, sinks, doc, mask.causal, (hipStream_t)stream, force);
   });
 }
 
-extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) { return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, nullptr, stream); }
+extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) { return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, nullptr, usp::FwdDoc{}, stream); }
 
 extern "C" int usp_flash_fwd_alibi(const usp_fwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
-  return flash_fwd_call(a, alibi_slopes, alibi_stride_b, usp::DropoutCall{}, nullptr, stream);
+  return flash_fwd_call(a, alibi_slopes, alibi_stride_b, usp::DropoutCall{}, nullptr, usp::FwdDoc{}, stream);
 }
 
 extern "C" int usp_flash_fwd_dropout(const usp_fwd_args* a, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
                                      void* stream) {
-  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{p_drop, seed, row0, key0, head0}, nullptr, stream);
+  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{p_drop, seed, row0, key0, head0}, nullptr, usp::FwdDoc{}, stream);
 }
 
 extern "C" int usp_flash_fwd_sink(const usp_fwd_args* a, const float* sinks, void* stream) {
-  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, sinks, stream);
+  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, sinks, usp::FwdDoc{}, stream);
+}
+
+extern "C" int usp_flash_fwd_doc(const usp_fwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, void* stream) {
+  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, nullptr, usp::FwdDoc{row_lo, row_lo ? row_lo_stride_b : 0}, stream);
 }

@@ -20,6 +20,9 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_alibi_kernel(const F
   constexpr Dropout dr{};
   constexpr bool SINK = false;
   constexpr const float* sink_s = nullptr;
+  constexpr bool DOC = false;
+  constexpr const int* doc_row_lo = nullptr;
+  constexpr int64_t doc_sb = 0;
 #include "usp_flash_fwd_body.inc"
 }
 

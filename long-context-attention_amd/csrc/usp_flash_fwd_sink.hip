@@ -24,6 +24,9 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_sink_kernel(const st
   constexpr int al_diag = 0;
   constexpr Dropout dr{};
   const float* const sink_s = p_in.sinks;
+  constexpr bool DOC = false;
+  constexpr const int* doc_row_lo = nullptr;
+  constexpr int64_t doc_sb = 0;
 #include "usp_flash_fwd_body.inc"
 }
 

@@ -70,6 +70,14 @@ struct FwdSink {
 };
 struct FwdArgsSK : FwdArgsT<true>, FwdSink {};
 struct FwdArgsSKP : FwdArgsT<false>, FwdSink {};      // ... of the sink kernels on the plain (unsplit) argument block
+// Document mask (usp_flash_fwd_doc): kernel arguments of the document instantiations only (usp_flash_fwd_doc.hip:
+// flash_fwd_doc_kernel, the plain kernel's loops under the window kernel's rotated walk); every other kernel keeps its
+// argument block and machine code.
+struct FwdDoc {
+  const int* row_lo;                    // int32 (Sq,): the first key row i sees, in the launch's key numbering; NULL = no bound
+  int64_t row_lo_sb;                    // batch stride in elements (0: one array for the whole batch)
+};
+struct FwdArgsDOC : FwdArgsT<false>, FwdDoc {};
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -92,5 +100,7 @@ int launch_fwd_alibi(const FwdArgsAL& p, int D, int dtype, bool causal, int wave
 int launch_fwd_dropout(const FwdArgsDR& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 // The sink forward (usp_flash_fwd_sink.hip), likewise; p.win_on picks the window form, p.ksplit > 1 the split form, else the plain one.
 int launch_fwd_sink(const FwdArgsSK& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
+// The document-mask forward (usp_flash_fwd_doc.hip), likewise; `lds` is the plain kernel's, the launch adds the bounds' room.
+int launch_fwd_doc(const FwdArgsDOC& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -149,6 +149,17 @@ inline int check_sink(const usp_fwd_args& a, const float* sinks) {
   return USP_OK;
 }
 
+// Document mask (usp_flash_fwd_doc / usp_flash_bwd_doc): what a call with the arrays must not carry -- checked before anything
+// is launched or written.  No array: the call is usp_flash_fwd / usp_flash_bwd, whatever the strides.
+template <class Args> int check_doc(const Args& a, bool has_doc, int64_t row_lo_stride_b, int64_t key_hi_stride_b) {
+  if (!has_doc) return USP_OK;
+  if (row_lo_stride_b < 0 || key_hi_stride_b < 0) return USP_EINVAL;
+  if (a.flags & (USP_ATTN_SOFTCAP | USP_ATTN_WINDOW | USP_ATTN_SHIFT)) return USP_EUNSUPPORTED;   // no second bound or step beside it
+  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
+  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
+  return USP_OK;
+}
+
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound
 // at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
 // (forward: the split instantiation, FwdSplit).

@@ -54,6 +54,33 @@
  *   usp_row_tile_masked  ... a tile that holds a (row, key of the wave) pair which a bound hides is masked.  EXACT for the
  *                        rectangle taken whole; CONSERVATIVE in that rows past Sq and keys past n_keys count (n_keys itself
  *                        needs no mask on this side: a key past it is never stored)
+ * The document bound (usp_flash_fwd_doc / usp_flash_bwd_doc): a left key bound read per row instead of i + win_lo.  Two int32 arrays
+ * in the launch's own coordinates, both non-decreasing and describing the same set: row_lo[i] in [0, n_keys] = the first key
+ * row i sees (n_keys: none), key_hi[j] in [0, Sq] = one past the last row that sees key j under this bound (= #{i : row_lo[i]
+ * <= j}).  Row i sees key j iff row_lo[i] <= j (equally: i < key_hi[j]) and the mask above without its window term holds.
+ * Monotone arrays make every range two reads: the first row of a tile or wave has the smallest bound, its last valid row the
+ * largest.  Values are clamped as they are read (usp_doc_clamp), so arrays that break the contract give wrong results and
+ * never an index out of range.
+ *   usp_doc_clamp        x cut to [0, n]
+ *   usp_doc_row_lo       row_lo of row min(i, Sq - 1), clamped to [0, n_keys]   (usp_doc_key_hi: key_hi of key min(j, n_keys - 1),
+ *                        clamped to [0, Sq])
+ *   usp_doc_first_key_tile  query side: no key tile below it holds a key that a row from r0 on sees; EXACT for row r0; never
+ *                        above t_end
+ *   usp_doc_uncut_key_tile  query side: from this tile on the bound hides no key from any valid row of [r0, r0 + n_rows); EXACT
+ *                        (the tile before it, if any, holds a key the last valid row does not see)
+ *   usp_doc_key_tile_live   query side, wave of rows from qw with wave_end as for usp_key_tile_live, lo_first = usp_doc_row_lo
+ *                        of its first row: a tile with a visible pair is live.  CONSERVATIVE: live when each bound alone
+ *                        leaves the wave a pair in the tile taken whole (keys past n_keys count); EXACT inside n_keys where the key intervals of consecutive valid rows are not
+ *                        empty and touch or overlap (a document mask on the diagonal block: every row sees itself)
+ *   usp_doc_key_tile_masked ... the left-bound term of usp_key_tile_masked: some valid row of the wave does not see some key
+ *                        of the tile, lo_last = usp_doc_row_lo of the wave's last valid row.  EXACT
+ *   usp_doc_last_row_tile   key side: no row tile from it on holds a row that sees a key of [own0, own0 + n_own) under this
+ *                        bound; EXACT for the last key of the block below n_keys; never above t_end
+ *   usp_doc_row_tile_live   key side, wave of keys from ow, hi_last = usp_doc_key_hi of its last key below n_keys: the tile of
+ *                        rows from s0 holds a row that this bound lets see a key of the wave.  EXACT for this bound alone
+ *                        (the caller ANDs the causal term of usp_row_tile_live)
+ *   usp_doc_row_tile_masked ... holds a (row, key of the wave) pair this bound hides, hi_first = usp_doc_key_hi of key ow.
+ *                        EXACT for this bound alone; CONSERVATIVE in that rows past Sq count
  * Every sum stays in `int` for Sq + Sk < 2^29 (usp_mask_decode.h lists them). */
 #ifndef USP_TILE_RANGE_H
 #define USP_TILE_RANGE_H
@@ -212,5 +239,41 @@ USP_RANGE_FN int usp_row_tile_live(int s0, int tile, int ow, int wave_keys, int 
 USP_RANGE_FN int usp_row_tile_masked(int s0, int tile, int ow, int wave_keys, int causal, int off, int win_on, int win_lo) {
   return (causal && s0 + off < ow + wave_keys - 1) || (win_on && s0 + tile - 1 > ow - win_lo);
 }
+
+/* ---- the document bound: a left key bound per row (row_lo) and its transpose (key_hi), both monotone ---- */
+USP_RANGE_FN int usp_doc_clamp(int x, int n) { return x < 0 ? 0 : (x > n ? n : x); }
+
+USP_RANGE_FN int usp_doc_row_lo(const int* row_lo, int i, int Sq, int n_keys) {
+  return usp_doc_clamp(row_lo[i < Sq ? i : Sq - 1], n_keys);
+}
+
+USP_RANGE_FN int usp_doc_key_hi(const int* key_hi, int j, int Sq, int n_keys) {
+  return usp_doc_clamp(key_hi[j < n_keys ? j : n_keys - 1], Sq);
+}
+
+/* lo_first = usp_doc_row_lo of the item's first row */
+USP_RANGE_FN int usp_doc_first_key_tile(int lo_first, int t_end, int tile) {
+  const int t0 = lo_first / tile;
+  return t0 < t_end ? t0 : t_end;
+}
+
+/* lo_last = usp_doc_row_lo of the last valid row of the item or wave */
+USP_RANGE_FN int usp_doc_uncut_key_tile(int lo_last, int tile) { return (lo_last + tile - 1) / tile; }
+
+USP_RANGE_FN int usp_doc_key_tile_live(int kt0, int tile, int wave_end, int lo_first) {
+  return kt0 < wave_end && kt0 + tile > lo_first;
+}
+
+USP_RANGE_FN int usp_doc_key_tile_masked(int kt0, int lo_last) { return kt0 < lo_last; }
+
+/* hi_last = usp_doc_key_hi of the block's last key below n_keys */
+USP_RANGE_FN int usp_doc_last_row_tile(int hi_last, int t_end, int tile) {
+  const int te = (hi_last + tile - 1) / tile;
+  return te < t_end ? te : t_end;
+}
+
+USP_RANGE_FN int usp_doc_row_tile_live(int s0, int hi_last) { return s0 < hi_last; }
+
+USP_RANGE_FN int usp_doc_row_tile_masked(int s0, int tile, int hi_first) { return s0 + tile - 1 >= hi_first; }
 
 #endif

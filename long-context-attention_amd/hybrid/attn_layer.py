@@ -19,6 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
+from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
 from .utils import RING_IMPL_DICT, RING_IMPL_QKVPACKED_DICT
@@ -88,6 +89,25 @@ class _USPLayer(torch.nn.Module):
         rank = dist.get_rank(self.ulysses_pg) if self.ulysses_size > 1 else 0
         return dict(sinks=local_sinks(sinks, heads, self.ulysses_size, rank))
 
+    def _docs(self, cu_doclens, batch: int, local_len: int):
+        """`cu_doclens` checked against the WHOLE sequence (ring/doc_blocks.py: parse; a rank holds local_len of its
+        ulysses_size x ring_size x local_len positions): the parsed lists, or None when it is off or names the single document
+        [0, S_total] -- which is exactly the call without it, the same exchange and the same launches."""
+        if cu_doclens is None:
+            return None
+        docs = doc_blocks.parse(cu_doclens, batch, self.ulysses_size * self.ring_size * local_len)
+        return None if docs is doc_blocks.SINGLE else docs
+
+    def _doc_option(self, cu_doclens, scatter_idx: int) -> dict:
+        """The `cu_doclens` keyword of the ring function: the list describes the WHOLE sequence and is the same on every rank.
+        Behind the head-scatter exchange a rank holds the ring rank's whole rows of some heads, so the arrays are those of the
+        ring rank alone and the ring function plans them (ring/doc_blocks.py).  {} when there is none."""
+        if cu_doclens is None:
+            return {}
+        if self.ulysses_size > 1 and (scatter_idx, self.gather_idx) != (2, 1):
+            raise NotImplementedError("cu_doclens needs the head-scatter exchange (heads scattered, sequence gathered)")
+        return dict(cu_doclens=cu_doclens)
+
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                       return_attn_probs):
         return dict(dropout_p=dropout_p, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
@@ -141,16 +161,24 @@ class LongContextAttention(_USPLayer):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                deterministic=False, return_attn_probs=False, *args: Any, sinks=None) -> Tensor:
+                deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
-        layer, (head_cnt,) fp32 or the operands' type (_USPLayer._local_sinks: the gradient contract)."""
+        layer, (head_cnt,) fp32 or the operands' type (_USPLayer._local_sinks: the gradient contract).  `cu_doclens` (keyword
+        only): the cumulative document lengths of the WHOLE sequence, host data, the same on every rank (ring/doc_blocks.py):
+        global row i sees global key j iff start(i) <= j <= i.  Needs causal=True; served with the basic ring at any ring
+        degree, with the zigzag and stripe rings at ring degree 1."""
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
-                               causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks)
+                               causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
+                               cu_doclens=cu_doclens)
             return out[..., :D]
+        cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1])     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
+        if ng_cap is not None and cu_doclens is not None:
+            ng_cap = None         # a document mask: likewise three exchanges -- the pipeline issues blocks in pieces, each of which
+                                  # would need its own arrays; the ring function serves it (ring/front_end.py: _check_doc)
         if ng_cap is not None and window_of(window_size) is not None:
             ng_cap = None         # a sliding window: the reference's structure (three exchanges); the basic ring function
                                   # serves it at ring degree 1 and, with USP_RING_WINDOW=global, beyond (ring/ring_flash_attn.py)
@@ -172,6 +200,7 @@ class LongContextAttention(_USPLayer):
                                      deterministic, return_attn_probs)
         options.update(self._dropout_head0(dropout_p, query.shape[2], self.scatter_idx))
         options.update(self._local_sinks(sinks, query.shape[2], self.scatter_idx))
+        options.update(self._doc_option(cu_doclens, self.scatter_idx))
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
         # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
@@ -196,16 +225,19 @@ class LongContextAttentionQKVPacked(_USPLayer):
 
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                *args: Any, sinks=None) -> Tensor:
+                *args: Any, sinks=None, cu_doclens=None) -> Tensor:
         D = qkv.shape[-1]
         if kernel_head_dim(D) != D:
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
-                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks)
+                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
+                               cu_doclens=cu_doclens)
             return out[..., :D]
         exchange = self.ulysses_size > 1
+        cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1])
         alibi_slopes = self._local_slopes(alibi_slopes, qkv.shape[3], self.scatter_idx - 1)
         head0 = self._dropout_head0(dropout_p, qkv.shape[3], self.scatter_idx - 1)
         head0.update(self._local_sinks(sinks, qkv.shape[3], self.scatter_idx - 1))
+        head0.update(self._doc_option(cu_doclens, self.scatter_idx - 1))
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,

@@ -79,10 +79,10 @@ class HipBlockBackend:
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
             final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None,
-            sinks=None):
+            sinks=None, doc=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
                      interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi,
-                     dropout=dropout, sinks=sinks)
+                     dropout=dropout, sinks=sinks, doc=doc)
 
     def sink_grad(self, sinks, lse, delta, out=None, accum=False):
         return _C.sink_grad(sinks, lse, delta, out=out, accum=accum)
@@ -92,10 +92,10 @@ class HipBlockBackend:
 
     def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq=False,
             accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None, softcap=None,
-            shift=None, alibi=None, dropout=None):
+            shift=None, alibi=None, dropout=None, doc=None):
         _C.flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq,
                      accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only,
-                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout)
+                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout, doc=doc)
 
     def fwd_packed(self, q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out=None,
                    acc=None, merge_in=False, final_begin=0, final_end=2, softcap=None):
@@ -238,6 +238,36 @@ class _SinkBackend:
         return getattr(self._be, name)
 
 
+class _DocBackend:
+    """A block backend of a call under a document mask (`cu_doclens`).  The bound of a launch depends on WHERE the launch lies,
+    and only the schedule knows that: `fwd` and `bwd` take the per-launch arrays as the keyword `doc=(row_lo, key_hi)` from the
+    schedule (ring/doc_blocks.py builds them on the host and uploads them once per call) and hand it on; a launch without the
+    keyword is refused, so that no block of such a call can run unmasked by oversight.  Everything else is the wrapped
+    backend's.  The packed calls refuse: the kernels serve the mask on dense launches only."""
+
+    def __init__(self, be):
+        self._be = be
+
+    def fwd(self, *args, doc=None, **kw):
+        if doc is None:
+            raise RuntimeError("a launch under cu_doclens carries its doc=(row_lo, key_hi) arrays (ring/doc_blocks.py)")
+        self._be.fwd(*args, doc=doc, **kw)
+
+    def bwd(self, *args, doc=None, **kw):
+        if doc is None:
+            raise RuntimeError("a launch under cu_doclens carries its doc=(row_lo, key_hi) arrays (ring/doc_blocks.py)")
+        self._be.bwd(*args, doc=doc, **kw)
+
+    def fwd_packed(self, *args, **kw):
+        raise NotImplementedError("cu_doclens is not supported on packed (variable-length) batches")
+
+    def bwd_packed(self, *args, **kw):
+        raise NotImplementedError("cu_doclens is not supported on packed (variable-length) batches")
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+
 def draw_seed() -> int:
     """The seed of one call with dropout: one 63-bit draw from torch's default CPU generator -- host side, no device sync,
     reproducible under torch.manual_seed, advancing with every call.  Drawn in the autograd forward, kept on ctx and reused by the
@@ -254,7 +284,7 @@ def rng_state_of(rng_state):
     return int(rng_state), 0, 0, 0
 
 
-def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, dropout=None, sinks=None):
+def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, dropout=None, sinks=None, doc=None):
     """The block backend; `beside_transfers=True` asks for launches that leave room for collectives queued on
     other streams (a persistent flash launch holds every CU until it ends: DESIGN.md section 5).  Test
     backends without that notion are returned as they are.  `softcap` > 0 (flash-attn's logit cap): every flash
@@ -265,11 +295,17 @@ def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, 
     p = 0 = off: every dense flash call carries p, the seed and the head offset, and takes `at=(row0, key0)` (_DropoutBackend);
     together with softcap or alibi: NotImplementedError.  `sinks`: one logit per query head of the block calls (a (Hq,) tensor on
     the operands' device, _C.sinks_value), None = off: the forward launches that open a row range carry it (_SinkBackend) and the
-    backend offers sink_grad(lse, delta); together with softcap, alibi or dropout: NotImplementedError."""
+    backend offers sink_grad(lse, delta); together with softcap, alibi or dropout: NotImplementedError.  `doc`: anything but
+    None / False = the call runs under a document mask: fwd and bwd take the per-launch `doc=(row_lo, key_hi)` keyword from the
+    schedule (_DocBackend); together with softcap, alibi, dropout or sinks: NotImplementedError."""
     be = _BACKEND
     if beside_transfers and hasattr(be, "beside_transfers"):
         be = be.beside_transfers()
     cap = _C.softcap_value(softcap)
+    if doc is not None and doc is not False:
+        from ..ring import doc_blocks
+        doc_blocks.refuse_beside(None, cap, alibi, None if dropout is None else _C.dropout_value(dropout[0]), sinks)
+        return _DocBackend(be)
     if sinks is not None:
         _check_sinks(cap, alibi, dropout[0] if dropout is not None else None)
         return _SinkBackend(be, sinks)
@@ -361,13 +397,32 @@ def _alibi_of(alibi_slopes, q):
     return None if al is None else al[0]
 
 
+def docs_of(cu_doclens, q, k, causal, window_size, cap, alibi_slopes, dropout_p, sinks):
+    """`cu_doclens` of a single-block call checked against its operands (ring/doc_blocks.py: parse, ValueError): None when it
+    is off or names one document (exactly the call without it), else the parsed lists.  causal=False, whole q and k of
+    different lengths, or a second mask or score-level step beside it: NotImplementedError."""
+    if cu_doclens is None:
+        return None
+    from ..ring import doc_blocks
+    docs = doc_blocks.parse(cu_doclens, q.shape[0], q.shape[1])
+    doc_blocks.refuse_not_causal_self(causal, q.shape[1], k.shape[1])
+    doc_blocks.refuse_beside(window_of(window_size), cap, alibi_slopes, _C.dropout_value(dropout_p), sinks)
+    return None if docs is doc_blocks.SINGLE else docs
+
+
+def _whole_doc(docs, q):
+    """The `doc=` keyword of the one launch of a single-block call."""
+    from ..ring import doc_blocks
+    return doc_blocks.whole_call(docs, q.shape[1], q.device).doc(0)
+
+
 def window_of(window_size):
     """flash-attn's `window_size` -> (left, right) or None when it selects no window ((-1, -1), None)."""
     return _C._window(window_size)
 
 
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None):
+                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -376,20 +431,27 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     NotImplementedError); the same state given to hip_attn_backward regenerates the mask.
     `sinks` (keyword only): one learned logit per query head, (Hq,) fp32 or q.dtype, in score units (not scaled): it joins every
     row's softmax denominator and carries no value; the returned lse includes it (include/usp_hip.h: usp_flash_fwd_sink).  Not
-    together with softcap, alibi_slopes or dropout_p."""
+    together with softcap, alibi_slopes or dropout_p.
+    `cu_doclens` (keyword only): the cumulative document lengths [0, e1, ..., Sq] of the sequence, host data (ring/doc_blocks.py):
+    row i sees key j iff start(i) <= j <= i.  Needs causal=True and equally long q and k; not together with window_size, softcap,
+    alibi_slopes, dropout_p or sinks.  None or the single document [0, Sq]: exactly the call without it."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
     if sinks is not None:
         _check_sinks(cap, alibi_slopes, dropout_p)
+    docs = docs_of(cu_doclens, q, k, causal, window_size, cap, alibi_slopes, dropout_p, sinks)
     dr = _dropout_of(dropout_p, rng_state, "hip_attn_forward")
     B, Sq, Hq, D = q.shape
     scale = _default_scale(q, softmax_scale)
     if kernel_head_dim(D) != D:                 # e.g. 96: on zero-padded copies (kernel_head_dim)
         out, lse = hip_attn_forward(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=scale, causal=causal,
                                     window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes, rng_state=rng_state,
-                                    sinks=sinks)
+                                    sinks=sinks, cu_doclens=docs)
         return out[..., :D].contiguous(), lse
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+    if docs is not None:
+        get_block_backend(doc=True).fwd(q, k, v, scale, True, lse, out=out, doc=_whole_doc(docs, q))
+        return out, lse
     be, kw = _block_backend_for(cap, alibi_slopes, q, dr, sinks)
     be.fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size), **kw)
     return out, lse
@@ -398,25 +460,31 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
 def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk_buffer,
                       block_dv_buffer, dropout_p=0.0, softmax_scale=None, bwd_causal=False,
                       window_size=(-1, -1), softcap=None, alibi_slopes=None, deterministic=False,
-                      rng_state=None, *args, sinks=None, dsinks=None, **kwargs):
+                      rng_state=None, *args, sinks=None, dsinks=None, cu_doclens=None, **kwargs):
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
     (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one.
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
-    come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd)."""
+    come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
+    `cu_doclens` (keyword only): as hip_attn_forward took it."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
     if sinks is not None:
         _check_sinks(cap, alibi_slopes, dropout_p)
         if dsinks is None:
             raise ValueError("hip_attn_backward with sinks needs the fp32 (Hq,) buffer dsinks")
-    be, at_kw = _block_backend_for(cap, alibi_slopes, q, _dropout_of(dropout_p, rng_state, "hip_attn_backward"), sinks)
+    docs = docs_of(cu_doclens, q, k, bwd_causal, window_size, cap, alibi_slopes, dropout_p, sinks)
+    if docs is not None:
+        be, at_kw = get_block_backend(doc=True), {}
+    else:
+        be, at_kw = _block_backend_for(cap, alibi_slopes, q, _dropout_of(dropout_p, rng_state, "hip_attn_backward"), sinks)
     B, Sq, Hq, D = q.shape
     dev = q.device
     if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
         pdo, pq, pk, pv, po = pad_head_dim(dout, q, k, v, out)
         g = [torch.empty_like(t) for t in (pq, pk, pv)]
         hip_attn_backward(pdo, pq, pk, pv, po, softmax_lse, g[0], g[1], g[2], dropout_p, _default_scale(q, softmax_scale),
-                          bwd_causal, window_size, cap, alibi_slopes, deterministic, rng_state, sinks=sinks, dsinks=dsinks)
+                          bwd_causal, window_size, cap, alibi_slopes, deterministic, rng_state, sinks=sinks, dsinks=dsinks,
+                          cu_doclens=docs)
         for dst, src in zip((block_dq_buffer, block_dk_buffer, block_dv_buffer), g):
             dst.copy_(src[..., :D])
         return
@@ -432,6 +500,8 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
         return t.dim() == 4 and t.stride(3) == 1 and all(st % 4 == 0 for st in t.stride()[:3])
     tgt = [t if direct(t) else torch.empty(t.shape, dtype=t.dtype, device=dev)
            for t in (block_dq_buffer, block_dk_buffer, block_dv_buffer)]
+    if docs is not None:
+        at_kw = {"doc": _whole_doc(docs, q)}
     be.bwd(dout, q, k, v, lse, delta, None, None, None, _default_scale(q, softmax_scale), bool(bwd_causal),
            dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], window=window_of(window_size), **at_kw)
     for t, dst in zip(tgt, (block_dq_buffer, block_dk_buffer, block_dv_buffer)):
@@ -445,14 +515,16 @@ class _HipAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None,
-                dropout_p=0.0, dropout_head0=0, sinks=None):
+                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
         # dropout: one seed per call, drawn here, kept for the backward (draw_seed); the block is the whole sequence
         ctx.dropout_p = _C.dropout_value(dropout_p) or 0.0
         ctx.rng_state = (draw_seed(), 0, 0, int(dropout_head0)) if ctx.dropout_p else None
         out, lse = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
-                                    softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks)
+                                    softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks,
+                                    cu_doclens=cu_doclens)
+        ctx.cu_doclens = cu_doclens
         ctx.has_sinks = sinks is not None          # (never beside slopes: the one optional saved tensor is either)
         ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)),
                               *(() if sinks is None else (sinks,)))                                     # (slopes: no gradient,
@@ -470,15 +542,15 @@ class _HipAttnFunc(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, ctx.dropout_p, ctx.scale, ctx.causal,
                           ctx.window_size, ctx.softcap, slopes[0] if slopes else None, rng_state=ctx.rng_state, sinks=sinks,
-                          dsinks=dsinks)
+                          dsinks=dsinks, cu_doclens=ctx.cu_doclens)
         if dsinks is not None:
             dsinks = dsinks.to(sinks.dtype) if ctx.needs_input_grad[11] else None
-        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks
+        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                  *args, dropout_head0=0, sinks=None, **kwargs):
+                  *args, dropout_head0=0, sinks=None, cu_doclens=None, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -487,20 +559,22 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     together with softcap or alibi_slopes; NaN, a negative value or one >= 1 raises ValueError.  `dropout_head0` (keyword
     only): the global index of q's head 0 in the mask's counter (a Ulysses rank passes the first head it holds).
     `sinks` (keyword only): one learned logit per query head, (Hq,) fp32 or q.dtype (hip_attn_forward); it may require grad, and
-    its gradient comes back in its own dtype and shape.  Not together with softcap, alibi_slopes or dropout_p."""
+    its gradient comes back in its own dtype and shape.  Not together with softcap, alibi_slopes or dropout_p.
+    `cu_doclens` (keyword only): the document mask of a packed sequence (hip_attn_forward), padded head dims included."""
     cap = _check_plain(dropout_p, softcap, alibi_slopes)
     if sinks is not None:
         _check_sinks(cap, alibi_slopes, dropout_p)
         sinks_of(sinks, q)
+    cu_doclens = docs_of(cu_doclens, q, k, causal, window_size, cap, alibi_slopes, dropout_p, sinks)
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)
         res = hip_attn_func(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=_default_scale(q, softmax_scale),
                             causal=causal, window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes,
-                            return_attn_probs=return_attn_probs, dropout_head0=dropout_head0, sinks=sinks)
+                            return_attn_probs=return_attn_probs, dropout_head0=dropout_head0, sinks=sinks, cu_doclens=cu_doclens)
         return (res[0][..., :D], res[1], None) if return_attn_probs else res[..., :D]
     if return_attn_probs:
         out, lse = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, True, window_size, cap, alibi_slopes, dropout_p, dropout_head0,
-                                      sinks)
+                                      sinks, cu_doclens)
         return out, lse, None
     return _HipAttnFunc.apply(q, k, v, softmax_scale, causal, False, window_size, cap, alibi_slopes, dropout_p, dropout_head0,
-                              sinks)
+                              sinks, cu_doclens)

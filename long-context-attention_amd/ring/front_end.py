@@ -7,6 +7,7 @@ import torch.distributed as dist
 from .._C import alibi_value, dropout_value, sinks_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
+from . import doc_blocks
 from .utils import group_info
 from .varlen_utils import unflatten_lse
 
@@ -92,6 +93,37 @@ def _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed):
     sinks_value(sinks, q.shape[2], q.device, q.dtype)
 
 
+def _check_doc(cu_doclens, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, served_beyond_one_block):
+    """The document mask (`cu_doclens`, ring/doc_blocks.py) on a ring: the parsed lists, or None when it is off or names one
+    document (exactly the call without it).  `cu_doclens` describes the WHOLE sequence, ring degree x the local length, and is
+    the same on every rank.  Served by the basic ring at any ring degree and by the zigzag and stripe rings at ring degree 1,
+    where they are one block over the natural order; the packed rings refuse.  causal=False, whole q and k of different lengths
+    and a second mask or score-level step beside it are refused; a malformed list is a ValueError."""
+    if cu_doclens is None:
+        return None
+    if packed:
+        raise NotImplementedError("cu_doclens is not supported by the variable-length (packed) rings: use LongContextAttention "
+                                  "(ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches")
+    P = group_info(dist, group)[0]
+    docs = doc_blocks.parse(cu_doclens, q.shape[0], P * q.shape[1])
+    doc_blocks.refuse_not_causal_self(causal, P * q.shape[1], P * k.shape[1])
+    window = None if window_size is None or tuple(window_size) == (-1, -1) else tuple(window_size)
+    doc_blocks.refuse_beside(window, softcap_value(softcap), alibi_slopes, dropout_value(dropout_p), sinks)
+    if docs is doc_blocks.SINGLE:
+        return None
+    if P > 1 and not served_beyond_one_block:
+        raise NotImplementedError("cu_doclens across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
+                                  "rings: use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func)")
+    return docs
+
+
+def _basic_ring():
+    """The basic ring's (forward, backward): what a one-block zigzag or stripe call under a document mask runs (at ring degree 1
+    every dense ring is one block over the natural order)."""
+    from .ring_flash_attn import ring_flash_attn_backward, ring_flash_attn_forward
+    return ring_flash_attn_forward, ring_flash_attn_backward
+
+
 def ring_dropout(dropout_p, rng_state):
     """(p, seed, head0) as get_block_backend takes it, from a ring forward's / backward's `dropout_p` and `rng_state` =
     (seed, head0); None when dropout is off.  dropout_p > 0 without a state is a caller that did not come through the front
@@ -106,7 +138,7 @@ def ring_dropout(dropout_p, rng_state):
 
 
 def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False,
-                   alibi_in_forward=False, dropout=False, dropout_in_forward=False, sinks=False):
+                   alibi_in_forward=False, dropout=False, dropout_in_forward=False, sinks=False, doc=False):
     """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
 
         packed             the variable-length form: q / k / v are (T, H, D) token tensors followed by `cu_seqlens, max_seqlen`;
@@ -130,14 +162,23 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
                            argument (behind dropout_head0) and its backward returns the gradient in that slot, in the sinks'
                            dtype.  It is THIS rank's share -- its rows; the sum over the ring group is the gradient of the
                            replicated parameter, and nothing here reduces it.
+        doc                `forward` / `backward` take `cu_doclens=` (the parsed lists) and serve the document mask at any ring
+                           degree (the basic ring).  Every dense *_func takes the keyword-only `cu_doclens` (_check_doc); a ring
+                           without `doc` serves it at ring degree 1 by the basic ring's one-block call and refuses beyond.  The
+                           Function takes it as one more optional trailing argument (behind sinks).
     The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
     grad; both exist here only."""
     n_lead = 2 if packed else 0
     extra = () if packed else (("attn_type", "attn_processor") if attn_processor else ("attn_type",))
     n_args = n_lead + 9 + len(extra)
 
+    def ring_pair(docs):
+        """The (forward, backward) that run a call: this ring's, or -- under a document mask on a ring without `doc`, which
+        _check_doc lets through at ring degree 1 only -- the basic ring's one-block call."""
+        return (forward, backward) if doc or docs is None else _basic_ring()
+
     def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw,
-                    head0=0, sink_t=None):
+                    head0=0, sink_t=None, cu_doc=None):
         """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse, the dropout keywords of the
         backward)."""
         if softmax_scale is None:
@@ -145,6 +186,7 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         if sink_t is not None:
             assert sinks, f"{class_name}: this ring's forward takes no sinks"
             _check_sinks(sink_t, q, dropout_p, softcap, alibi_slopes, packed)
+        docs = _check_doc(cu_doc, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sink_t, group, packed, doc)
         _check_alibi(alibi_slopes, q, softcap, group, packed, alibi_in_forward)
         p = _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, dropout, dropout_in_forward)
         _check_hot_path_args(dropout_p if p is None else 0.0, (-1, -1) if window_in_forward else window_size, softcap)
@@ -153,9 +195,12 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         else:
             q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
         drop_kw = {} if p is None else dict(rng_state=(draw_seed(), int(head0)))  # one seed per call, host side
-        out, lse = forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                           window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw,
-                           **drop_kw, **({} if sink_t is None else dict(sinks=sink_t)))
+        if docs is not None:                      # (kept with the backward's keywords: drop_kw is what the backward adds)
+            drop_kw = dict(drop_kw, cu_doclens=docs)
+        ring_forward = ring_pair(docs)[0]
+        out, lse = ring_forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+                                window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw,
+                                **drop_kw, **({} if sink_t is None else dict(sinks=sink_t)))
         return q, k, v, softmax_scale, out, lse, drop_kw
 
     def result(out, lse, lead, return_softmax):
@@ -169,16 +214,17 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
 
         @staticmethod
         def forward(ctx, q, k, v, *args):
-            assert len(args) in (n_args, n_args + 1, n_args + 2), \
-                f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0 (+ sinks))"
+            assert len(args) in (n_args, n_args + 1, n_args + 2, n_args + 3), \
+                f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0 (+ sinks (+ cu_doclens)))"
             ctx.n_none = len(args)
             head0 = args[n_args] if len(args) > n_args else 0
             sink_t = args[n_args + 1] if len(args) > n_args + 1 else None
+            cu_doc = args[n_args + 2] if len(args) > n_args + 2 else None
             lead, extra_kw = args[:n_lead], dict(zip(extra, args[n_lead + 9:n_args]))
             dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, return_softmax, group = \
                 args[n_lead:n_lead + 9]
             q, k, v, softmax_scale, out, lse, drop_kw = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size,
-                                                                    softcap, alibi_slopes, group, extra_kw, head0, sink_t)
+                                                                    softcap, alibi_slopes, group, extra_kw, head0, sink_t, cu_doc)
             ctx.has_sinks = sink_t is not None                                    # (dense rings only: `lead` is then empty)
             ctx.save_for_backward(q, k, v, out, lse, *lead[:1], *(() if sink_t is None else (sink_t,)))   # (cu_seqlens is a tensor)
             extra_kw.pop("attn_processor", None)                                  # (the backwards take none)
@@ -193,7 +239,8 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
             if not packed:
                 dout = kernel_operand(dout)
             if not ctx.has_sinks:
-                return tuple(backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * ctx.n_none
+                ring_backward = ring_pair(kw.get("cu_doclens"))[1]
+                return tuple(ring_backward(group, dout, *ctx.saved_tensors, *lead_rest, **kw)) + (None,) * ctx.n_none
             *saved, sink_t = ctx.saved_tensors
             dq, dk, dv, dsinks = backward(group, dout, *saved, *lead_rest, **kw, sinks=sink_t)
             return (dq, dk, dv) + (None,) * (ctx.n_none - 1) + (dsinks.to(sink_t.dtype),)
@@ -202,21 +249,25 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
 
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None):
+                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
+                 cu_doclens=None):
+            _check_doc(cu_doclens, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, doc)
             _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed)
             return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group)
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None, *, sinks=None):
+                          group=None, *, sinks=None, cu_doclens=None):
+            _check_doc(cu_doclens, q, kv[:, 0], causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, doc)
             _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed)
             return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
                               softcap, alibi_slopes, deterministic, return_attn_probs, group)
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None, *, sinks=None):
+                           group=None, *, sinks=None, cu_doclens=None):
+            _check_doc(cu_doclens, qkv[:, 0], qkv[:, 1], causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, doc)
             _check_sinks(sinks, qkv[:, 0], dropout_p, softcap, alibi_slopes, packed)
             return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group)
@@ -224,37 +275,39 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         def last(attn_type, processor=None):      # the Function's trailing arguments
             return (attn_type, processor)[:len(extra)]
 
-        def head0_arg(dropout_head0, sink_t=None):    # ... and the optional ones behind them
+        def head0_arg(dropout_head0, sink_t=None, cu_doc=None):    # ... and the optional ones behind them
+            if cu_doc is not None:
+                return (dropout_head0, sink_t, cu_doc)
             return (dropout_head0, sink_t) if sink_t is not None else ((dropout_head0,) if dropout_head0 else ())
 
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None):
+                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None):
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
                 res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                            window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor,
-                           dropout_head0=dropout_head0, sinks=sinks)
+                           dropout_head0=dropout_head0, sinks=sinks, cu_doclens=cu_doclens)
                 return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
             if not needs_grad(q, k, v, *(() if sinks is None else (sinks,))):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
                 out, lse = run_forward(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group,
-                                       dict(zip(extra, last(attn_type, attn_processor))), dropout_head0, sinks)[4:6]
+                                       dict(zip(extra, last(attn_type, attn_processor))), dropout_head0, sinks, cu_doclens)[4:6]
                 return result(out, lse, (), return_attn_probs)
             return Func.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
-                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0, sinks))
+                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0, sinks, cu_doclens))
 
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None):
+                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None):
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks))
+                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks, cu_doclens))
 
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None):
+                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None):
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type),
-                              *head0_arg(dropout_head0, sinks))
+                              *head0_arg(dropout_head0, sinks, cu_doclens))
 
     for fn, suffix in ((func, "_func"), (kvpacked_func, "_kvpacked_func"), (qkvpacked_func, "_qkvpacked_func")):
         fn.__name__ = fn.__qualname__ = stem + suffix

@@ -18,6 +18,12 @@ keys lie in the whole sequence -- forward and backward alike, and the ring's res
 A sliding window (`window_size`) is one windowed block at ring degree 1; at ring degree > 1 it is served on request
 (USP_RING_WINDOW=global) over GLOBAL positions: only the blocks the window touches are fetched, launched and returned, each
 with its own shifted bounds (ring/window_blocks.py).
+
+A document mask (`cu_doclens`, ring/doc_blocks.py) is served at any ring degree, by default: rank r holds the global rows
+[r S, (r + 1) S), and the step that sees the K/V of ring rank kr is launched with the (row_lo, key_hi) arrays of (those rows, the
+keys [kr S, (kr + 1) S)) -- the diagonal block causal, the blocks below it full with a left bound.  A block in which nothing is
+visible (start(r S) >= (kr + 1) S) is not launched: the rows' running state is untouched and its dK/dV block is zero.  The
+diagonal block always sees something and stays first, so it opens the rows' state; the transfers stay as they are.
 """
 import os
 
@@ -26,7 +32,7 @@ import torch.distributed as dist
 
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend, window_of
-from . import block_pieces
+from . import block_pieces, doc_blocks
 from .front_end import ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, return_dkdv_direct, travel_dkdv
 from .window_blocks import WindowPlan
@@ -124,8 +130,9 @@ def basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, lse, delta, softmax
 def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                             attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None,
-                            rng_state=None, sinks=None):
-    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `sinks`: one logit per query head; it rides on
+                            rng_state=None, sinks=None, cu_doclens=None):
+    """`cu_doclens`: the parsed document lists of the whole sequence (ring/front_end.py: _check_doc), None = off.
+    `rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `sinks`: one logit per query head; it rides on
     the launch that opens the rows' state (step 0; the window planner's first block), at any ring degree.  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
@@ -134,13 +141,27 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
     block_pieces.refuse_sinks(sinks, pieces)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks)
+    assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _check_doc"
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks,
+                           doc=cu_doclens)
     if pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=dev)
+    if cu_doclens is not None:       # the document mask: the steps with something visible, each with its own arrays
+        assert k.shape[1] == S, "the basic ring holds equally long chunks of q and k"
+        call = doc_blocks.ring_call(cu_doclens, S, P, r, dev)
+        steps = [s for s in range(r + 1) if call.visible(s)]          # (step 0, the diagonal block, is always among them)
+        acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if len(steps) > 1 else None
+        with KVRelay(process_group, k, v) as relay:
+            for step in range(P):
+                kk, vv = relay.get(step)
+                if step in steps:
+                    be.fwd(q, kk, vv, softmax_scale, step == 0, lse, out, acc, step > 0, 0, S if step == steps[-1] else 0,
+                           doc=call.doc(step))
+        return out, lse
     win = _ring_window(window_size, P)
     if win is not None and P == 1:   # ring degree 1: one block, the kernels take flash-attn's window (left, right)
         be.fwd(q, k, v, softmax_scale, bool(causal), lse, out, window=win)
@@ -170,8 +191,8 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
                              dropout_p=0, causal=True, window_size=(-1, -1), softcap=0.0,
                              alibi_slopes=None, deterministic=False,
                              attn_type: AttnType = AttnType.HIP, overlap=False, defer=None, first=None, dq_first=None,
-                             rng_state=None, sinks=None):
-    """`rng_state`: as the forward's (the same state regenerates its mask).  `sinks`: as the forward's; `softmax_lse` holds them, the
+                             rng_state=None, sinks=None, cu_doclens=None):
+    """`cu_doclens`: as the forward's.  `rng_state`: as the forward's (the same state regenerates its mask).  `sinks`: as the forward's; `softmax_lse` holds them, the
     block kernels are unchanged, and this rank's share of their gradient (its rows) is returned as a fourth, fp32 element.  `defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
     ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
@@ -180,7 +201,9 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
     block_pieces.refuse_sinks(sinks, pieces)
-    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks)
+    assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _check_doc"
+    be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks,
+                           doc=cu_doclens)
     if pieces:
         return block_pieces.backward_in_pieces(be, dout, q, k, v, out, softmax_lse, softmax_scale, first, dq_first)
     B, S, H, D = q.shape
@@ -188,10 +211,11 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     delta = torch.empty((B, H, S), dtype=torch.float32, device=dev)
     be.delta(dout, out, delta)
     with_dsinks = (lambda g: g) if sinks is None else (lambda g, ds=be.sink_grad(softmax_lse, delta): tuple(g) + (ds,))
+    call = None if cu_doclens is None else doc_blocks.ring_call(cu_doclens, S, P, r, dev)
     if P == 1:   # one block: the kernels round the gradients to q.dtype in their epilogues
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale, bool(causal),
-               dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)))
+               dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)), **({} if call is None else {"doc": call.doc(0)}))
         return with_dsinks((dq, dk, dv))
     win = _ring_window(window_size, P)
     dq_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev)
@@ -210,6 +234,11 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
         return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
     def block(step, kk, vv, dk_dst, dv_dst):
+        if call is not None:          # the document mask: a step in which nothing is visible computes nothing
+            if step > r or not call.visible(step):
+                return False
+            return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
+                                   dq_acc, dk_dst, dv_dst, doc=call.doc(step))
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
                                dq_acc, dk_dst, dv_dst, **_step_launch_kw(al, dr, r, P, step, S))
 
@@ -219,10 +248,11 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
     # under causal only steps <= rank compute (:93-122)
     dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
-                                 extent=lambda rank, step: None if (causal and step > rank) else FULL)
+                                 extent=lambda rank, step: None if (causal and step > rank) or
+                                 (cu_doclens is not None and not doc_blocks.ring_visible(cu_doclens, S, rank, step)) else FULL)
     return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
 
 (RingFlashAttnFunc, ring_flash_attn_func, ring_flash_attn_kvpacked_func, ring_flash_attn_qkvpacked_func) = ring_front_end(
     "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, attn_processor=True,
-    window_in_forward=True, alibi_in_forward=True, dropout=True, dropout_in_forward=True, sinks=True)
+    window_in_forward=True, alibi_in_forward=True, dropout=True, dropout_in_forward=True, sinks=True, doc=True)

@@ -39,7 +39,7 @@ class UlyssesAttention(torch.nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                return_attn_probs=False, *args: Any, sinks=None) -> Tensor:
+                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None) -> Tensor:
         if alibi_slopes is not None:     # slopes over the layer's heads are cut to this rank's (comm/all_to_all.py: local_heads)
             if (self.scatter_idx, self.gather_idx) != (2, 1):
                 raise NotImplementedError("alibi_slopes needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
@@ -56,5 +56,9 @@ class UlyssesAttention(torch.nn.Module):
             if (self.scatter_idx, self.gather_idx) != (2, 1):
                 raise NotImplementedError("sinks needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
             options["sinks"] = local_sinks(sinks, query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
+        if cu_doclens is not None:     # the whole sequence's document lists, the same on every rank: behind the exchange a rank
+            if (self.scatter_idx, self.gather_idx) != (2, 1):     # holds whole sequences of some heads, so it is one block's mask
+                raise NotImplementedError("cu_doclens needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
+            options["cu_doclens"] = cu_doclens     # (checked against the whole sequence q now holds: kernels/attention.py: docs_of)
         attended = self.attn_fn(q, k, v, **options)
         return self._to_seq(attended[0] if isinstance(attended, tuple) else attended)
