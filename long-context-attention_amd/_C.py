@@ -114,14 +114,12 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc")
-# The two *_alibi entry points are the only exports load() does not insist on: they are looked up and prototyped on first use
-# (_alibi_entry), behind the feature bit, so a library built before them still loads and serves everything else.
+# The entry points of ALiBi, dropout, the sinks and the document mask are the only exports load() does not insist on: they are
+# looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
+# and serves everything else.
 ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
-# ... and so are the two *_dropout entry points (_dropout_entry, USP_ATTN_DROPOUT)
 DROPOUT_EXPORTS = ("usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
-# ... and the two sink entry points (_sink_entry, USP_ATTN_SINK)
 SINK_EXPORTS = ("usp_flash_fwd_sink", "usp_sink_bwd")
-# ... and the two document-mask entry points (_doc_entry, USP_ATTN_DOC)
 DOC_EXPORTS = ("usp_flash_fwd_doc", "usp_flash_bwd_doc")
 
 
@@ -362,20 +360,6 @@ def alibi_value(alibi_slopes, B: int, Hq: int, device):
     return t, (Hq if t.dim() == 2 else 0)
 
 
-def _alibi_entry(name: str):
-    """The *_alibi entry point `name` (one of ALIBI_EXPORTS), prototyped on first use; a library without the feature bit
-    (built before the entry points: it loads, they are not in EXPORTS) is refused."""
-    L = load()
-    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_ALIBI and hasattr(L, name)):
-        raise NotImplementedError(f"{_LIB_PATH} does not serve alibi_slopes (USP_ATTN_ALIBI): rebuild it")
-    fn = getattr(L, name)
-    if fn.argtypes is None:
-        args = UspFwdArgs if name == "usp_flash_fwd_alibi" else UspBwdArgs
-        fn.argtypes = [ctypes.POINTER(args), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    return fn
-
-
 def dropout_value(dropout_p) -> Optional[float]:
     """flash-attn's `dropout_p` -> the drop probability as a float, or None when it is off (None / 0).  NaN, a negative value
     or one >= 1 raises ValueError.  (Pure argument check: the CPU orchestration tests call it without a library.)"""
@@ -415,21 +399,6 @@ def dropout_args(dropout):
     return p, seed, row0, key0, head0
 
 
-def _dropout_entry(name: str):
-    """The *_dropout entry point `name` (one of DROPOUT_EXPORTS), prototyped on first use; a library without the feature bit
-    (built before the entry points: it loads, they are not insisted on) is refused."""
-    L = load()
-    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_DROPOUT and hasattr(L, name)):
-        raise NotImplementedError(f"{_LIB_PATH} does not serve dropout_p (USP_ATTN_DROPOUT): rebuild it")
-    fn = getattr(L, name)
-    if fn.argtypes is None:
-        args = UspFwdArgs if name == "usp_flash_fwd_dropout" else UspBwdArgs
-        fn.argtypes = [ctypes.POINTER(args), ctypes.c_float, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                       ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    return fn
-
-
 def sinks_value(sinks, Hq: int, device, dtype=None):
     """A `sinks` argument -> the contiguous fp32 device tensor usp_flash_fwd_sink / usp_sink_bwd take, or None when it is off.
     One learned logit per query head, in score units: shape (Hq,), float32 or the operands' 16-bit type (`dtype`; None: either
@@ -447,21 +416,6 @@ def sinks_value(sinks, Hq: int, device, dtype=None):
     if sinks.device != torch.device(device):
         raise ValueError(f"sinks is on {sinks.device}, the operands on {device}")
     return sinks.detach().float().contiguous()
-
-
-def _sink_entry(name: str):
-    """The sink entry point `name` (one of SINK_EXPORTS), prototyped on first use; a library without the feature bit (built
-    before the entry points: it loads, they are not insisted on) is refused."""
-    L = load()
-    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_SINK and hasattr(L, name)):
-        raise NotImplementedError(f"{_LIB_PATH} does not serve sinks (USP_ATTN_SINK): rebuild it")
-    fn = getattr(L, name)
-    if fn.argtypes is None:
-        i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-        fn.argtypes = ([ctypes.POINTER(UspFwdArgs), vp, vp] if name == "usp_flash_fwd_sink" else
-                       [i32, i32, i32, vp, vp, i64, i64, vp, i64, i64, vp, i32, vp])
-        fn.restype = ctypes.c_int
-    return fn
 
 
 def doc_value(doc, B: int, Sq: int, Sk: int, device):
@@ -489,19 +443,39 @@ def doc_value(doc, B: int, Sq: int, Sk: int, device):
     return one(row_lo, Sq, "row_lo"), one(key_hi, Sk, "key_hi")
 
 
-def _doc_entry(name: str):
-    """The document-mask entry point `name` (one of DOC_EXPORTS), prototyped on first use; a library without the feature bit
-    (built before the entry points: it loads, they are not insisted on) is refused."""
+def _feature_entries():
+    """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
+    does not insist on."""
+    i32, i64, u64, f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
+    fwd, bwd = ctypes.POINTER(UspFwdArgs), ctypes.POINTER(UspBwdArgs)
+    return {"usp_flash_fwd_alibi": (USP_ATTN_ALIBI, "alibi_slopes (USP_ATTN_ALIBI)", [fwd, vp, i64, vp]),
+            "usp_flash_bwd_alibi": (USP_ATTN_ALIBI, "alibi_slopes (USP_ATTN_ALIBI)", [bwd, vp, i64, vp]),
+            "usp_flash_fwd_dropout": (USP_ATTN_DROPOUT, "dropout_p (USP_ATTN_DROPOUT)", [fwd, f32, u64, i32, i32, i32, vp]),
+            "usp_flash_bwd_dropout": (USP_ATTN_DROPOUT, "dropout_p (USP_ATTN_DROPOUT)", [bwd, f32, u64, i32, i32, i32, vp]),
+            "usp_flash_fwd_sink": (USP_ATTN_SINK, "sinks (USP_ATTN_SINK)", [fwd, vp, vp]),
+            "usp_sink_bwd": (USP_ATTN_SINK, "sinks (USP_ATTN_SINK)", [i32, i32, i32, vp, vp, i64, i64, vp, i64, i64, vp, i32, vp]),
+            "usp_flash_fwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [fwd, vp, i64, vp]),
+            "usp_flash_bwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [bwd, vp, i64, vp, i64, vp])}
+
+
+_FEATURE_ENTRIES = _feature_entries()
+
+
+def _feature_entry(name: str):
+    """The entry point `name` of _FEATURE_ENTRIES, prototyped on first use; a library without the feature bit (built before
+    the entry points: it loads, they are not insisted on) is refused."""
+    bit, option, argtypes = _FEATURE_ENTRIES[name]
     L = load()
-    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & USP_ATTN_DOC and hasattr(L, name)):
-        raise NotImplementedError(f"{_LIB_PATH} does not serve cu_doclens (USP_ATTN_DOC): rebuild it")
+    if not (hasattr(L, "usp_attn_features") and L.usp_attn_features() & bit and hasattr(L, name)):
+        raise NotImplementedError(f"{_LIB_PATH} does not serve {option}: rebuild it")
     fn = getattr(L, name)
     if fn.argtypes is None:
-        i64, vp = ctypes.c_int64, ctypes.c_void_p
-        fn.argtypes = ([ctypes.POINTER(UspFwdArgs), vp, i64, vp] if name == "usp_flash_fwd_doc" else
-                       [ctypes.POINTER(UspBwdArgs), vp, i64, vp, i64, vp])
+        fn.argtypes = argtypes
         fn.restype = ctypes.c_int
     return fn
+
+
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):
@@ -529,6 +503,30 @@ def _shift(shift) -> Optional[int]:
     if abs(s) >= 1 << 30:
         raise ValueError(f"shift must lie inside (-2^30, 2^30), got {shift!r}")
     return s
+
+
+def _flash_call(which: str, a, al, dr, sk, dc):
+    """Issues the flash launch `which` ("fwd" | "bwd") of the filled argument block `a` with the decoded extras (alibi_value,
+    dropout_args, sinks_value, doc_value; None = off): through the entry point of the one that is on -- two of them are
+    refused (kernels/features.py) -- or the plain one."""
+    if al is None and dr is None and sk is None and dc is None:
+        name, extra = "usp_flash_" + which, ()
+        fn = getattr(load(), name)
+    else:
+        from .kernels.features import Features
+        Features(alibi=al, dropout=dr, sinks=sk, doc=dc).check()
+        if dc is not None:
+            (rl, rl_sb), (kh, kh_sb) = dc
+            name = f"usp_flash_{which}_doc"          # (the forward reads row_lo alone)
+            extra = (_ptr(rl), rl_sb) if which == "fwd" else (_ptr(rl), rl_sb, _ptr(kh), kh_sb)
+        elif sk is not None:
+            name, extra = "usp_flash_fwd_sink", (_ptr(sk),)
+        elif dr is not None:
+            name, extra = f"usp_flash_{which}_dropout", dr
+        else:
+            name, extra = f"usp_flash_{which}_alibi", (_ptr(al[0]), al[1])
+        fn = _feature_entry(name)
+    _check(fn(ctypes.byref(a), *extra, _stream()), name)
 
 
 def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end, interleave, n, window=None,
@@ -617,27 +615,7 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
-    if dc is not None:
-        if al is not None or dr is not None or sk is not None:
-            raise NotImplementedError("cu_doclens together with alibi_slopes, dropout_p or sinks is not supported by the HIP attention kernels")
-        (rl, rl_sb), _ = dc
-        _check(_doc_entry("usp_flash_fwd_doc")(ctypes.byref(a), _ptr(rl), rl_sb, _stream()), "usp_flash_fwd_doc")
-        return
-    if sk is not None:
-        if al is not None or dr is not None:
-            raise NotImplementedError("sinks together with alibi_slopes or dropout_p is not supported by the HIP attention kernels")
-        _check(_sink_entry("usp_flash_fwd_sink")(ctypes.byref(a), ctypes.c_void_p(sk.data_ptr()), _stream()), "usp_flash_fwd_sink")
-        return
-    if dr is not None:
-        if al is not None:
-            raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
-        _check(_dropout_entry("usp_flash_fwd_dropout")(ctypes.byref(a), *dr, _stream()), "usp_flash_fwd_dropout")
-        return
-    if al is not None:
-        _check(_alibi_entry("usp_flash_fwd_alibi")(ctypes.byref(a), ctypes.c_void_p(al[0].data_ptr()), al[1], _stream()),
-               "usp_flash_fwd_alibi")
-        return
-    _check(L.usp_flash_fwd(ctypes.byref(a), _stream()), "usp_flash_fwd")
+    _flash_call("fwd", a, al, dr, sk, dc)
 
 
 def _t3(t: Optional[torch.Tensor]) -> UspTensor:
@@ -768,7 +746,7 @@ def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
         raise ValueError("sink_grad: out must be a contiguous float32 (H,) tensor")
     pl, lsb, lsh = _lse3(lse)
     pd, dsb, dsh = _lse3(delta)
-    _check(_sink_entry("usp_sink_bwd")(B, S, H, ctypes.c_void_p(sk.data_ptr()), pl, lsb, lsh, pd, dsb, dsh,
+    _check(_feature_entry("usp_sink_bwd")(B, S, H, ctypes.c_void_p(sk.data_ptr()), pl, lsb, lsh, pd, dsb, dsh,
                                        ctypes.c_void_p(out.data_ptr()), 1 if accum else 0, _stream()), "usp_sink_bwd")
     return out
 
@@ -828,22 +806,7 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
-    if dc is not None:
-        if al is not None or dr is not None:
-            raise NotImplementedError("cu_doclens together with alibi_slopes or dropout_p is not supported by the HIP attention kernels")
-        (rl, rl_sb), (kh, kh_sb) = dc
-        _check(_doc_entry("usp_flash_bwd_doc")(ctypes.byref(a), _ptr(rl), rl_sb, _ptr(kh), kh_sb, _stream()), "usp_flash_bwd_doc")
-        return
-    if dr is not None:
-        if al is not None:
-            raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
-        _check(_dropout_entry("usp_flash_bwd_dropout")(ctypes.byref(a), *dr, _stream()), "usp_flash_bwd_dropout")
-        return
-    if al is not None:
-        _check(_alibi_entry("usp_flash_bwd_alibi")(ctypes.byref(a), ctypes.c_void_p(al[0].data_ptr()), al[1], _stream()),
-               "usp_flash_bwd_alibi")
-        return
-    _check(L.usp_flash_bwd(ctypes.byref(a), _stream()), "usp_flash_bwd")
+    _flash_call("bwd", a, al, dr, None, dc)
 
 
 def lse_merge(acc, lse, blk_out, blk_lse, first: bool):

@@ -17,6 +17,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
+from .._C import dropout_value
 from ..kernels.attention import get_block_backend
 from . import relay_exchange
 
@@ -137,6 +138,35 @@ def local_sinks(sinks, H: int, P: int, rank: int):
         return sinks
     raise ValueError(f"sinks must cover the layer's {H} heads or the {H // max(P, 1)} heads of one ulysses rank (shape (H,)), "
                      f"got {tuple(sinks.shape)}")
+
+
+def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, rank: int, head_scatter: bool, how: str):
+    """What a layer of H heads hands its attention function for the options that depend on WHICH heads ulysses rank `rank` of P
+    holds behind the exchange: (keyword dict, local slopes).
+      alibi_slopes  cut to the rank's heads (local_alibi_slopes);
+      dropout_p     `dropout_head0`: the mask is keyed by the layer's GLOBAL query head (include/usp_hip.h:
+                    usp_flash_fwd_dropout), KV-replicated grids included -- the counter holds the query head;
+      sinks         cut to the rank's heads by slicing (local_sinks), so autograd scatters the gradient back.  The sinks are a
+                    parameter replicated over the sequence-parallel group: each rank's gradient is its share (its rows of the
+                    ring, its heads under Ulysses, zeros elsewhere), the SUM over the group is the gradient, and the layers do
+                    no all-reduce;
+      cu_doclens    as given: the list describes the WHOLE sequence and is the same on every rank; behind the exchange a rank
+                    holds whole rows of some heads, so the attention function plans its arrays alone (ring/doc_blocks.py).
+    Each of them needs an exchange that scatters heads and gathers the sequence (`head_scatter`; `how`: that, in the layer's
+    words): NotImplementedError otherwise."""
+    p = dropout_value(dropout_p)
+    if not head_scatter:
+        for name, value in (("alibi_slopes", alibi_slopes), ("dropout_p != 0", p), ("sinks", sinks), ("cu_doclens", cu_doclens)):
+            if value is not None:
+                raise NotImplementedError(f"{name} needs the head-scatter exchange ({how})")
+    kw = {}
+    if p is not None and P > 1:
+        kw["dropout_head0"] = local_heads(H, P, rank).start
+    if sinks is not None:
+        kw["sinks"] = local_sinks(sinks, H, P, rank)
+    if cu_doclens is not None:
+        kw["cu_doclens"] = cu_doclens
+    return kw, local_alibi_slopes(alibi_slopes, H, P, rank)
 
 
 def pack_head_group(x5: Tensor, send: Tensor = None, h0: int = 0) -> Tensor:

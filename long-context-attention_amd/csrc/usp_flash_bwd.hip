@@ -166,10 +166,21 @@ __global__ __launch_bounds__(256) void reduce_cuts_kernel(const BwdParams p) {
 
 static int reduce_grid(int64_t items) { return (int)((items + 255) / 256 > 2048 ? 2048 : (items + 255) / 256); }
 
+// What usp_flash_bwd_alibi / _dropout / _doc add to a plain call; nothing set: usp_flash_bwd.  The entry points fill the slopes and
+// their stride, dc and doc as given; flash_bwd_call checks them and fills al.al_diag and dr, the kernels' dropout block (dr.t == 0:
+// off).
+struct BwdExtras {
+  BwdAlibi al{};
+  DropoutCall dc{};
+  BwdDoc doc{};
+  Dropout dr{};
+  bool any() const { return al.al_slopes || dr.t || doc.row_lo || doc.key_hi; }
+};
+
 // dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
 // the launch, the 8-wave kernel otherwise; then the sum over the partial slabs of a head-split / cut launch.
 template <int D, int DT>
-static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, const BwdDoc& doc, bool causal, hipStream_t st, bool row64) {
+static int launch_dkdv(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_t st, bool row64) {
   p.nblk = (p.Sk + 127) / 128;
   p.n_items = p.B * p.Hkv * p.nblk * p.ngrp * p.qsplit;
   int rc = USP_ELAUNCH;
@@ -185,20 +196,20 @@ static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, cons
     p.sched_lds = (int)lds;
     const size_t lds_q = lds + (p.sched ? 16 : 0);   // + the item queue's two slots
     const BwdParams pb = p;                        // the argument block of the kernels without softcap
-    if (al.al_slopes) {                            // ALiBi: instantiations of their own (usp_flash_bwd_alibi.hip)
+    if (x.al.al_slopes) {                          // ALiBi: instantiations of their own (usp_flash_bwd_alibi.hip)
       BwdArgsAL pa;
       static_cast<BwdParams&>(pa) = pb;
-      static_cast<BwdAlibi&>(pa) = al;
+      static_cast<BwdAlibi&>(pa) = x.al;
       if (int rc2 = launch_dkdv_alibi(pa, D, DT, causal, grid, lds_q, st)) return rc2;
-    } else if (dr.t) {                             // dropout: likewise (usp_flash_bwd_dropout.hip)
+    } else if (x.dr.t) {                           // dropout: likewise (usp_flash_bwd_dropout.hip)
       BwdArgsDR pd;
       static_cast<BwdParams&>(pd) = pb;
-      static_cast<Dropout&>(pd) = dr;
+      static_cast<Dropout&>(pd) = x.dr;
       if (int rc2 = launch_dkdv_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
-    } else if (doc.key_hi) {                       // document mask: likewise (usp_flash_bwd_doc.hip)
+    } else if (x.doc.key_hi) {                     // document mask: likewise (usp_flash_bwd_doc.hip)
       BwdArgsDOC pd;
       static_cast<BwdParams&>(pd) = pb;
-      static_cast<BwdDoc&>(pd) = doc;
+      static_cast<BwdDoc&>(pd) = x.doc;
       if (int rc2 = launch_dkdv_doc(pd, D, DT, causal, grid, lds_q, st)) return rc2;
     } else
     with_causal(causal, [&](auto c) {
@@ -219,7 +230,7 @@ static int launch_dkdv(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, cons
 
 // dQ of a call: the one-wave-per-SIMD kernel (4 waves x 64 query rows, usp_flash_bwd_dq64.hip) or the 8-wave kernel, as above
 template <int D, int DT>
-static int launch_dq(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, const BwdDoc& doc, bool causal, hipStream_t st, bool row64) {
+static int launch_dq(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_t st, bool row64) {
   int rc = USP_ELAUNCH;
   if (row64 && launch_dq64(p, DT, causal, st, &rc)) {
     if (rc == USP_OK) launch_kinds_note(USP_KIND_DQ_ROW64);
@@ -232,20 +243,20 @@ static int launch_dq(BwdArgsSC& p, const BwdAlibi& al, const Dropout& dr, const 
   p.sched_lds = (int)lds;
   const size_t lds_q = lds + (p.sched ? 16 : 0);   // + the item queue's two slots
   const BwdParams pb = p;
-  if (al.al_slopes) {                              // ALiBi: instantiations of their own (usp_flash_bwd_alibi.hip)
+  if (x.al.al_slopes) {                            // ALiBi: instantiations of their own (usp_flash_bwd_alibi.hip)
     BwdArgsAL pa;
     static_cast<BwdParams&>(pa) = pb;
-    static_cast<BwdAlibi&>(pa) = al;
+    static_cast<BwdAlibi&>(pa) = x.al;
     if (int rc2 = launch_dq_alibi(pa, D, DT, causal, grid, lds_q, st)) return rc2;
-  } else if (dr.t) {                               // dropout: likewise (usp_flash_bwd_dropout.hip)
+  } else if (x.dr.t) {                             // dropout: likewise (usp_flash_bwd_dropout.hip)
     BwdArgsDR pd;
     static_cast<BwdParams&>(pd) = pb;
-    static_cast<Dropout&>(pd) = dr;
+    static_cast<Dropout&>(pd) = x.dr;
     if (int rc2 = launch_dq_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
-  } else if (doc.row_lo) {                         // document mask: likewise (usp_flash_bwd_doc.hip)
+  } else if (x.doc.row_lo) {                       // document mask: likewise (usp_flash_bwd_doc.hip)
     BwdArgsDOC pd;
     static_cast<BwdParams&>(pd) = pb;
-    static_cast<BwdDoc&>(pd) = doc;
+    static_cast<BwdDoc&>(pd) = x.doc;
     if (int rc2 = launch_dq_doc(pd, D, DT, causal, grid, lds_q, st)) return rc2;
   } else
   with_causal(causal, [&](auto c) {
@@ -267,17 +278,17 @@ static int launch_reduce_cuts(const BwdParams& p, hipStream_t st) {
 }
 
 template <int D, int DT>
-static int launch_bwd(BwdArgsSC p, const BwdAlibi& al, const Dropout& dr, const BwdDoc& doc, bool causal, hipStream_t st, int force, int skip) {
+static int launch_bwd(BwdArgsSC p, const BwdExtras& x, bool causal, hipStream_t st, int force, int skip) {
   const bool want_dkdv = !(skip & USP_BWD_SKIP_DKDV), want_dq = !(skip & USP_BWD_SKIP_DQ);
   // per call, `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32 (include/usp_hip.h) picks the family; forced onto the 64-row
   // family, only the launches that will run have to be served
   if ((force & USP_FORCE_ROW64) && !(D == 128 && (!want_dkdv || dkdv64_serves(p)) && (!want_dq || dq64_serves(p))))
     return USP_EUNSUPPORTED;
   // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
-  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !al.al_slopes && !dr.t && !doc.row_lo && !doc.key_hi;   // (... and no ALiBi, dropout or document step)
+  const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !x.any();   // (... and no ALiBi, dropout or document step)
   int rc = USP_OK;
-  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, al, dr, doc, causal, st, row64)) != USP_OK) return rc;
-  if (want_dq && (rc = launch_dq<D, DT>(p, al, dr, doc, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
+  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, x, causal, st, row64)) != USP_OK) return rc;
+  if (want_dq && (rc = launch_dq<D, DT>(p, x, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
   return rc;
 }
 
@@ -346,8 +357,7 @@ extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
 }
 
 // usp_flash_bwd (alibi_slopes == NULL, p_drop == 0, no document array), usp_flash_bwd_alibi, usp_flash_bwd_dropout and usp_flash_bwd_doc
-static int flash_bwd_call(const usp_bwd_args* a_in, const float* alibi_slopes, int64_t alibi_stride_b, const usp::DropoutCall& dc,
-                          const usp::BwdDoc& doc, void* stream) {
+static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stream) {
   const usp_bwd_args* a = a_in;
   using namespace usp;
   launch_kinds_reset();
@@ -356,9 +366,9 @@ static int flash_bwd_call(const usp_bwd_args* a_in, const float* alibi_slopes, i
   const int skip = a->flags & (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV);
   if (skip == (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV)) return USP_EINVAL;
   if (int rc = check_problem(*a)) return rc;
-  if (int rc = check_alibi(*a, alibi_slopes, alibi_stride_b)) return rc;
-  Dropout dr;
-  if (int rc = check_dropout(*a, dc, &dr)) return rc;
+  if (int rc = check_alibi(*a, x.al.al_slopes, x.al.al_sb)) return rc;
+  if (int rc = check_dropout(*a, x.dc, &x.dr)) return rc;
+  const BwdDoc& doc = x.doc;
   const bool has_doc = doc.row_lo || doc.key_hi;
   // the dQ launch reads row_lo, the dK/dV launch key_hi: the array of a launch that runs must be there
   if (has_doc && ((!(skip & USP_BWD_SKIP_DQ) && !doc.row_lo) || (!(skip & USP_BWD_SKIP_DKDV) && !doc.key_hi))) return USP_EINVAL;
@@ -436,27 +446,32 @@ static int flash_bwd_call(const usp_bwd_args* a_in, const float* alibi_slopes, i
     p.ksplit = plan.ksplit;
     if (p.ksplit > 1) p.ws_dq = (float*)((char*)a->workspace + plan.dkdv_bytes);
   }
-  const BwdAlibi al{alibi_slopes, alibi_stride_b, alibi_diag(*a)};
+  x.al.al_diag = alibi_diag(*a);
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
-    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, al, dr, doc, mask.causal, (hipStream_t)stream, force, skip);
+    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, x, mask.causal, (hipStream_t)stream, force, skip);
   });
 }
 
-extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) { return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{}, usp::BwdDoc{}, stream); }
+extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) { return flash_bwd_call(a, usp::BwdExtras{}, stream); }
 
 extern "C" int usp_flash_bwd_alibi(const usp_bwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
-  return flash_bwd_call(a, alibi_slopes, alibi_stride_b, usp::DropoutCall{}, usp::BwdDoc{}, stream);
+  usp::BwdExtras x;
+  x.al.al_slopes = alibi_slopes; x.al.al_sb = alibi_stride_b;
+  return flash_bwd_call(a, x, stream);
 }
 
 extern "C" int usp_flash_bwd_dropout(const usp_bwd_args* a, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
                                      void* stream) {
-  return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{p_drop, seed, row0, key0, head0}, usp::BwdDoc{}, stream);
+  usp::BwdExtras x;
+  x.dc = usp::DropoutCall{p_drop, seed, row0, key0, head0};
+  return flash_bwd_call(a, x, stream);
 }
 
 extern "C" int usp_flash_bwd_doc(const usp_bwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* key_hi,
                                  int64_t key_hi_stride_b, void* stream) {
   const bool any = row_lo || key_hi;
-  return flash_bwd_call(a, nullptr, 0, usp::DropoutCall{}, usp::BwdDoc{row_lo, key_hi, any ? row_lo_stride_b : 0, any ? key_hi_stride_b : 0},
-                        stream);
+  usp::BwdExtras x;
+  x.doc = usp::BwdDoc{row_lo, key_hi, any ? row_lo_stride_b : 0, any ? key_hi_stride_b : 0};
+  return flash_bwd_call(a, x, stream);
 }

@@ -141,8 +141,20 @@ int launch_split_merge(const FwdArgsT<true>& p, int dtype, int D, hipStream_t st
   return launched();
 }
 
+// What usp_flash_fwd_alibi / _dropout / _sink / _doc add to a plain call; nothing set: usp_flash_fwd.  The entry points fill the
+// slopes and their stride, dc, sinks and doc as given; flash_fwd_call checks them and fills al.al_diag and dr, the kernels'
+// dropout block (dr.t == 0: off).
+struct FwdExtras {
+  FwdAlibi al{};
+  DropoutCall dc{};
+  const float* sinks = nullptr;
+  FwdDoc doc{};
+  Dropout dr{};
+  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo; }
+};
+
 template <int D, int DT, int NWAVES>
-static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, const float* sinks, const FwdDoc& doc, bool causal, hipStream_t st) {
+static int launch_fwd_w(FwdArgsSC p, const FwdExtras& x, bool causal, hipStream_t st) {
   p.nq = (p.Sq + 32 * NWAVES - 1) / (32 * NWAVES);
   p.n_items = p.B * p.Hq * p.nq * p.ksplit;
   // persistent launch: one workgroup per resident slot (8 waves: 1 per CU, 4 waves: 2 per CU)
@@ -151,25 +163,25 @@ static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, cons
   const FwdArgsT<true> ps = p;                               // the argument block of the split kernels
   FwdArgsT<false> plain;                                     // the argument block of the plain kernels: FwdParams alone
   static_cast<FwdParams&>(plain) = p;
-  if (al.al_slopes) {                                        // ALiBi: instantiations of their own (usp_flash_fwd_alibi.hip)
+  if (x.al.al_slopes) {                                      // ALiBi: instantiations of their own (usp_flash_fwd_alibi.hip)
     FwdArgsAL pa;
     static_cast<FwdArgsT<true>&>(pa) = ps;
-    static_cast<FwdAlibi&>(pa) = al;
+    static_cast<FwdAlibi&>(pa) = x.al;
     if (int rc = launch_fwd_alibi(pa, D, DT, causal, NWAVES, grid, lds, st)) return rc;
-  } else if (dr.t) {                                         // dropout: likewise (usp_flash_fwd_dropout.hip)
+  } else if (x.dr.t) {                                       // dropout: likewise (usp_flash_fwd_dropout.hip)
     FwdArgsDR pd;
     static_cast<FwdArgsT<true>&>(pd) = ps;
-    static_cast<Dropout&>(pd) = dr;
+    static_cast<Dropout&>(pd) = x.dr;
     if (int rc = launch_fwd_dropout(pd, D, DT, causal, NWAVES, grid, lds, st)) return rc;
-  } else if (sinks) {                                        // attention sinks: likewise (usp_flash_fwd_sink.hip)
+  } else if (x.sinks) {                                      // attention sinks: likewise (usp_flash_fwd_sink.hip)
     FwdArgsSK pk;
     static_cast<FwdArgsT<true>&>(pk) = ps;
-    pk.sinks = sinks;
+    pk.sinks = x.sinks;
     if (int rc = launch_fwd_sink(pk, D, DT, causal, NWAVES, grid, lds, st)) return rc;
-  } else if (doc.row_lo) {                                   // document mask: likewise (usp_flash_fwd_doc.hip)
+  } else if (x.doc.row_lo) {                                 // document mask: likewise (usp_flash_fwd_doc.hip)
     FwdArgsDOC pd;
     static_cast<FwdParams&>(pd) = p;
-    static_cast<FwdDoc&>(pd) = doc;
+    static_cast<FwdDoc&>(pd) = x.doc;
     if (int rc = launch_fwd_doc(pd, D, DT, causal, NWAVES, grid, lds, st)) return rc;
   } else
   with_causal(causal, [&](auto c) {
@@ -192,15 +204,14 @@ static int launch_fwd_w(FwdArgsSC p, const FwdAlibi& al, const Dropout& dr, cons
 }
 
 template <int D, int DT>
-static int launch_fwd(const FwdArgsSC& p, const FwdAlibi& al, const Dropout& dr, const float* sinks, const FwdDoc& doc, bool causal, hipStream_t st,
-                      int force) {
+static int launch_fwd(const FwdArgsSC& p, const FwdExtras& x, bool causal, hipStream_t st, int force) {
   // Workgroup shape: 8 waves (256 query rows, one workgroup per CU) stage K/V once per 256 rows and win by
   // 3-4 % whenever they can give every CU work; 4 waves (128 rows, two workgroups per CU) are used only
   // when the 8-wave item list is shorter than the CU count, or for short causal sequences (<= 1024 rows:
   // +3...8 %) (measured with persistent workgroups, profiles/).  Per call, `force` (USP_FORCE_ROW64 / USP_FORCE_WAVE32,
   // include/usp_hip.h) picks the family.  `waves` = 4 | 8, or 64: the 4 x 64-row kernel of usp_flash_fwd64.hip.
   // what usp_flash_fwd64.hip serves (plain and K-split launches; its hand-pinned pipeline has no softcap step)
-  const bool fwd64_ok = D == 128 && !p.seq_q && !p.win_on && !p.cap_on && !al.al_slopes && !dr.t && !sinks && !doc.row_lo;   // (... and no ALiBi, dropout, sink or document step)
+  const bool fwd64_ok = D == 128 && !p.seq_q && !p.win_on && !p.cap_on && !x.any();   // (... and no ALiBi, dropout, sink or document step)
   const int split_kind = p.ksplit > 1 ? USP_KIND_FWD_SPLIT_MERGE : 0;
   int waves = 64;
   if (!(force & USP_FORCE_ROW64)) {
@@ -232,7 +243,7 @@ static int launch_fwd(const FwdArgsSC& p, const FwdAlibi& al, const Dropout& dr,
     if (force & USP_FORCE_ROW64) return USP_EUNSUPPORTED;
     waves = 8;                                               // (a layout the 64-row kernel declines)
   }
-  const int rc = waves == 4 ? launch_fwd_w<D, DT, 4>(p, al, dr, sinks, doc, causal, st) : launch_fwd_w<D, DT, 8>(p, al, dr, sinks, doc, causal, st);
+  const int rc = waves == 4 ? launch_fwd_w<D, DT, 4>(p, x, causal, st) : launch_fwd_w<D, DT, 8>(p, x, causal, st);
   if (rc == USP_OK) launch_kinds_note((waves == 4 ? USP_KIND_FWD_WAVE4 : USP_KIND_FWD_WAVE8) | split_kind);
   return rc;
 }
@@ -247,18 +258,16 @@ extern "C" int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* a, int32_t 
 
 // usp_flash_fwd (alibi_slopes == NULL, p_drop == 0, sinks == NULL, row_lo == NULL), usp_flash_fwd_alibi, usp_flash_fwd_dropout,
 // usp_flash_fwd_sink and usp_flash_fwd_doc
-static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, const usp::DropoutCall& dc,
-                          const float* sinks, const usp::FwdDoc& doc, void* stream) {
+static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream) {
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse) return USP_EINVAL;
   if (int rc = check_force(a->flags)) return rc;
   if (int rc = check_problem(*a)) return rc;
-  if (int rc = check_alibi(*a, alibi_slopes, alibi_stride_b)) return rc;
-  Dropout dr;
-  if (int rc = check_dropout(*a, dc, &dr)) return rc;
-  if (int rc = check_sink(*a, sinks)) return rc;
-  if (int rc = check_doc(*a, doc.row_lo != nullptr, doc.row_lo_sb, 0)) return rc;
+  if (int rc = check_alibi(*a, x.al.al_slopes, x.al.al_sb)) return rc;
+  if (int rc = check_dropout(*a, x.dc, &x.dr)) return rc;
+  if (int rc = check_sink(*a, x.sinks)) return rc;
+  if (int rc = check_doc(*a, x.doc.row_lo != nullptr, x.doc.row_lo_sb, 0)) return rc;
   if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
@@ -296,7 +305,7 @@ static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int6
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  if (a->k_splits > 1 && a->workspace != nullptr && !doc.row_lo) {   // (a document launch is served uncut: usp_hip.h)
+  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo) {   // (a document launch is served uncut: usp_hip.h)
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
     if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
@@ -305,28 +314,36 @@ static int flash_fwd_call(const usp_fwd_args* a, const float* alibi_slopes, int6
     p.ws_lse = p.ws_o + (int64_t)p.ksplit * a->B * a->Sq * a->Hq * a->D;
   }
   if (packed) p.q_sb = p.k_sb = p.v_sb = p.o_sb = p.a_sb = p.lse_sb = 0;
-  const FwdAlibi al{alibi_slopes, alibi_stride_b, alibi_diag(*a)};
+  x.al.al_diag = alibi_diag(*a);
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
-    return launch_fwd<decltype(d)::value, decltype(dt)::value>(p, al, dr, sinks, doc, mask.causal, (hipStream_t)stream, force);
+    return launch_fwd<decltype(d)::value, decltype(dt)::value>(p, x, mask.causal, (hipStream_t)stream, force);
   });
 }
 
-extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) { return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, nullptr, usp::FwdDoc{}, stream); }
+extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) { return flash_fwd_call(a, usp::FwdExtras{}, stream); }
 
 extern "C" int usp_flash_fwd_alibi(const usp_fwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
-  return flash_fwd_call(a, alibi_slopes, alibi_stride_b, usp::DropoutCall{}, nullptr, usp::FwdDoc{}, stream);
+  usp::FwdExtras x;
+  x.al.al_slopes = alibi_slopes; x.al.al_sb = alibi_stride_b;
+  return flash_fwd_call(a, x, stream);
 }
 
 extern "C" int usp_flash_fwd_dropout(const usp_fwd_args* a, float p_drop, uint64_t seed, int32_t row0, int32_t key0, int32_t head0,
                                      void* stream) {
-  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{p_drop, seed, row0, key0, head0}, nullptr, usp::FwdDoc{}, stream);
+  usp::FwdExtras x;
+  x.dc = usp::DropoutCall{p_drop, seed, row0, key0, head0};
+  return flash_fwd_call(a, x, stream);
 }
 
 extern "C" int usp_flash_fwd_sink(const usp_fwd_args* a, const float* sinks, void* stream) {
-  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, sinks, usp::FwdDoc{}, stream);
+  usp::FwdExtras x;
+  x.sinks = sinks;
+  return flash_fwd_call(a, x, stream);
 }
 
 extern "C" int usp_flash_fwd_doc(const usp_fwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, void* stream) {
-  return flash_fwd_call(a, nullptr, 0, usp::DropoutCall{}, nullptr, usp::FwdDoc{row_lo, row_lo ? row_lo_stride_b : 0}, stream);
+  usp::FwdExtras x;
+  x.doc = usp::FwdDoc{row_lo, row_lo ? row_lo_stride_b : 0};
+  return flash_fwd_call(a, x, stream);
 }

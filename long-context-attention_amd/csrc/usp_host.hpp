@@ -91,15 +91,21 @@ template <class Args> int check_problem(const Args& a) {
   return USP_OK;
 }
 
-// ALiBi (usp_flash_fwd_alibi / usp_flash_bwd_alibi): what a call with slopes must not carry -- checked before anything is
-// launched or written.  NULL slopes: the call is usp_flash_fwd / usp_flash_bwd, whatever the stride.
+// What every extra of a call -- ALiBi, dropout, sinks, the document mask: the entry points beside usp_flash_fwd / usp_flash_bwd --
+// declines alike.  The checks below run in the order alibi, dropout, sink, doc, each with its own USP_EINVAL cases and declines
+// first and this last, before anything is launched or written.
+template <class Args> int check_extras(const Args& a) {
+  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
+  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
+  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines them
+  return USP_OK;
+}
+
+// ALiBi (usp_flash_fwd_alibi / usp_flash_bwd_alibi).  NULL slopes: the call is usp_flash_fwd / usp_flash_bwd, whatever the stride.
 template <class Args> int check_alibi(const Args& a, const float* slopes, int64_t stride_b) {
   if (!slopes) return USP_OK;
   if (stride_b < 0) return USP_EINVAL;
-  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
-  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
-  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
-  return USP_OK;
+  return check_extras(a);
 }
 // The bias diagonal: the bias of (row i, key j) is -slope * |i + diag - j|, diag = Sk - Sq + mask_shift.  Not taken from the
 // decoded mask: causal_off also absorbs window_right, and a bound that cuts nothing is dropped there -- the bias is not.
@@ -110,7 +116,6 @@ template <class Args> int alibi_diag(const Args& a) {
 
 // Dropout (usp_flash_fwd_dropout / usp_flash_bwd_dropout): validates the scalars and fills the kernels' block.  p_drop == 0, or one
 // whose keep threshold is 256, leaves dr->t = 0: the call is usp_flash_fwd / usp_flash_bwd and the offsets are not looked at.
-// Checked before anything is launched or written.
 // What usp_flash_fwd_dropout / usp_flash_bwd_dropout add to a call (p_drop = 0: nothing)
 struct DropoutCall { float p_drop; uint64_t seed; int32_t row0, key0, head0; };
 
@@ -126,9 +131,7 @@ int check_dropout(const Args& a, const DropoutCall& dc, Dropout* dr) {
   if (row0 < 0 || key0 < 0 || head0 < 0) return USP_EINVAL;
   if ((row0 & 3) || (key0 & 3)) return USP_EUNSUPPORTED;             // a DPP quad of lanes shares one 4 x 4 patch
   if ((int64_t)row0 + a.Sq >= (1LL << 31) || (int64_t)key0 + a.Sk >= (1LL << 31)) return USP_EUNSUPPORTED;
-  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
-  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
-  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
+  if (int rc = check_extras(a)) return rc;
   dr->k0 = (uint32_t)(seed & 0xffffffffu);
   dr->k1 = (uint32_t)(seed >> 32);
   dr->row0 = (uint32_t)row0; dr->key0 = (uint32_t)key0; dr->head0 = (uint32_t)head0;
@@ -138,26 +141,19 @@ int check_dropout(const Args& a, const DropoutCall& dc, Dropout* dr) {
   return USP_OK;
 }
 
-// Attention sinks (usp_flash_fwd_sink): what a call with sinks must not carry -- checked before anything is launched or written.
-// NULL sinks: the call is usp_flash_fwd.
+// Attention sinks (usp_flash_fwd_sink).  NULL sinks: the call is usp_flash_fwd.
 inline int check_sink(const usp_fwd_args& a, const float* sinks) {
   if (!sinks) return USP_OK;
   if (a.merge_in) return USP_EINVAL;                                // the sink belongs to the launch that opens the rows' state
-  if (a.flags & USP_ATTN_SOFTCAP) return USP_EUNSUPPORTED;          // no instantiation holds both steps
-  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
-  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
-  return USP_OK;
+  return check_extras(a);
 }
 
-// Document mask (usp_flash_fwd_doc / usp_flash_bwd_doc): what a call with the arrays must not carry -- checked before anything
-// is launched or written.  No array: the call is usp_flash_fwd / usp_flash_bwd, whatever the strides.
+// Document mask (usp_flash_fwd_doc / usp_flash_bwd_doc).  No array: the call is usp_flash_fwd / usp_flash_bwd, whatever the strides.
 template <class Args> int check_doc(const Args& a, bool has_doc, int64_t row_lo_stride_b, int64_t key_hi_stride_b) {
   if (!has_doc) return USP_OK;
   if (row_lo_stride_b < 0 || key_hi_stride_b < 0) return USP_EINVAL;
-  if (a.flags & (USP_ATTN_SOFTCAP | USP_ATTN_WINDOW | USP_ATTN_SHIFT)) return USP_EUNSUPPORTED;   // no second bound or step beside it
-  if (a.seq_q || a.seq_k) return USP_EUNSUPPORTED;                  // dense launches only
-  if (a.flags & USP_FORCE_ROW64) return USP_EUNSUPPORTED;           // the 64-row family declines it
-  return USP_OK;
+  if (a.flags & (USP_ATTN_WINDOW | USP_ATTN_SHIFT)) return USP_EUNSUPPORTED;   // no second bound beside it
+  return check_extras(a);
 }
 
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound

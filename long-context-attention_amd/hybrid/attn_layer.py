@@ -15,7 +15,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from .._C import dropout_value, softcap_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_alibi_slopes, local_heads, local_sinks
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_options
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
@@ -57,37 +57,12 @@ class _USPLayer(torch.nn.Module):
             self._ring_size = dist.get_world_size(self.ring_pg) if self.ring_pg is not None else 1
         return self._ring_size
 
-    def _local_slopes(self, alibi_slopes, heads: int, scatter_idx: int):
-        """alibi_slopes for the heads this Ulysses rank holds behind the exchange (comm/all_to_all.py: local_alibi_slopes)."""
-        if alibi_slopes is None or self.ulysses_size == 1:
-            return alibi_slopes
-        if (scatter_idx, self.gather_idx) != (2, 1):
-            raise NotImplementedError("alibi_slopes needs the head-scatter exchange (heads scattered, sequence gathered)")
-        return local_alibi_slopes(alibi_slopes, heads, self.ulysses_size, dist.get_rank(self.ulysses_pg))
-
-    def _dropout_head0(self, dropout_p, heads: int, scatter_idx: int) -> dict:
-        """The `dropout_head0` keyword of the ring function: the dropout mask is keyed by the layer's GLOBAL query head
-        (include/usp_hip.h: usp_flash_fwd_dropout), and behind the head-scatter exchange this Ulysses rank holds the heads
-        local_heads(H, P, rank) (comm/all_to_all.py) -- KV-replicated grids included: the counter holds the query head.  {} when
-        dropout is off or there is nothing to exchange."""
-        if dropout_value(dropout_p) is None or self.ulysses_size == 1:
-            return {}
-        if (scatter_idx, self.gather_idx) != (2, 1):
-            raise NotImplementedError("dropout_p != 0 needs the head-scatter exchange (heads scattered, sequence gathered)")
-        return dict(dropout_head0=local_heads(heads, self.ulysses_size, dist.get_rank(self.ulysses_pg)).start)
-
-    def _local_sinks(self, sinks, heads: int, scatter_idx: int) -> dict:
-        """The `sinks` keyword of the ring function: the layer's sink logits cut to the heads this Ulysses rank holds behind the
-        exchange (comm/all_to_all.py: local_sinks; by slicing, so autograd scatters the gradient back), KV-replicated grids
-        included.  {} when there are none.  The sinks are a parameter replicated over the sequence-parallel group: each rank's
-        gradient is its share (its rows of the ring, its heads under Ulysses, zeros elsewhere), the SUM over the group is the
-        gradient, and the layers do no all-reduce."""
-        if sinks is None:
-            return {}
-        if self.ulysses_size > 1 and (scatter_idx, self.gather_idx) != (2, 1):
-            raise NotImplementedError("sinks needs the head-scatter exchange (heads scattered, sequence gathered)")
-        rank = dist.get_rank(self.ulysses_pg) if self.ulysses_size > 1 else 0
-        return dict(sinks=local_sinks(sinks, heads, self.ulysses_size, rank))
+    def _head_options(self, alibi_slopes, dropout_p, sinks, cu_doclens, heads: int, scatter_idx: int):
+        """(the ring function's keywords dropout_head0 / sinks / cu_doclens, the slopes) for the heads this Ulysses rank holds
+        behind the exchange (comm/all_to_all.py: local_options); with nothing to exchange any layout serves."""
+        P = self.ulysses_size
+        return local_options(alibi_slopes, dropout_p, sinks, cu_doclens, heads, P, dist.get_rank(self.ulysses_pg) if P > 1 else 0,
+                             P == 1 or (scatter_idx, self.gather_idx) == (2, 1), "heads scattered, sequence gathered")
 
     def _docs(self, cu_doclens, batch: int, local_len: int):
         """`cu_doclens` checked against the WHOLE sequence (ring/doc_blocks.py: parse; a rank holds local_len of its
@@ -97,16 +72,6 @@ class _USPLayer(torch.nn.Module):
             return None
         docs = doc_blocks.parse(cu_doclens, batch, self.ulysses_size * self.ring_size * local_len)
         return None if docs is doc_blocks.SINGLE else docs
-
-    def _doc_option(self, cu_doclens, scatter_idx: int) -> dict:
-        """The `cu_doclens` keyword of the ring function: the list describes the WHOLE sequence and is the same on every rank.
-        Behind the head-scatter exchange a rank holds the ring rank's whole rows of some heads, so the arrays are those of the
-        ring rank alone and the ring function plans them (ring/doc_blocks.py).  {} when there is none."""
-        if cu_doclens is None:
-            return {}
-        if self.ulysses_size > 1 and (scatter_idx, self.gather_idx) != (2, 1):
-            raise NotImplementedError("cu_doclens needs the head-scatter exchange (heads scattered, sequence gathered)")
-        return dict(cu_doclens=cu_doclens)
 
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                       return_attn_probs):
@@ -164,7 +129,7 @@ class LongContextAttention(_USPLayer):
                 deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
-        layer, (head_cnt,) fp32 or the operands' type (_USPLayer._local_sinks: the gradient contract).  `cu_doclens` (keyword
+        layer, (head_cnt,) fp32 or the operands' type (comm/all_to_all.py: local_options: the gradient contract).  `cu_doclens` (keyword
         only): the cumulative document lengths of the WHOLE sequence, host data, the same on every rank (ring/doc_blocks.py):
         global row i sees global key j iff start(i) <= j <= i.  Needs causal=True; served with the basic ring at any ring
         degree, with the zigzag and stripe rings at ring degree 1."""
@@ -176,31 +141,23 @@ class LongContextAttention(_USPLayer):
             return out[..., :D]
         cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1])     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
-        if ng_cap is not None and cu_doclens is not None:
-            ng_cap = None         # a document mask: likewise three exchanges -- the pipeline issues blocks in pieces, each of which
-                                  # would need its own arrays; the ring function serves it (ring/front_end.py: _check_doc)
-        if ng_cap is not None and window_of(window_size) is not None:
-            ng_cap = None         # a sliding window: the reference's structure (three exchanges); the basic ring function
-                                  # serves it at ring degree 1 and, with USP_RING_WINDOW=global, beyond (ring/ring_flash_attn.py)
-        if ng_cap is not None and alibi_slopes is not None:
-            ng_cap = None         # ALiBi: likewise three exchanges -- the pipeline's row pieces and head groups would each need a
-                                  # slice of the slopes and a shift; the ring function serves it (ring/front_end.py: _check_alibi)
-        if ng_cap is not None and dropout_value(dropout_p) is not None:
-            ng_cap = None         # dropout: likewise three exchanges -- the pipeline's head groups and row pieces would each need
-                                  # their place in the mask; the ring function serves it (ring/front_end.py: _check_dropout)
-        if ng_cap is not None and sinks is not None:
-            ng_cap = None         # sinks: likewise three exchanges -- the pipeline issues blocks in pieces that open a row range
-                                  # more than once (ring/block_pieces.py); the ring function serves them (ring/front_end.py: _check_sinks)
+        if ng_cap is not None and (cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
+                                   or dropout_value(dropout_p) is not None or sinks is not None):
+            # Any of them: the reference's structure (three exchanges), and the ring function serves it (ring/front_end.py: _place).
+            # The pipeline issues blocks in row pieces and head groups: under a document mask each piece would need its own
+            # arrays; a sliding window is served by the basic ring function at ring degree 1 and, with USP_RING_WINDOW=global,
+            # beyond (ring/ring_flash_attn.py); ALiBi would need a slice of the slopes and a shift per piece and group; dropout
+            # their place in the mask; and the pieces open a row range more than once (ring/block_pieces.py), where a sink
+            # must count once.
+            ng_cap = None
         if ng_cap is not None:
             _check_hot_path_args(dropout_p, window_size, softcap)
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
                                        self.ring_impl_type, ng_cap, softcap_value(softcap))
-        options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap,
-                                     self._local_slopes(alibi_slopes, query.shape[2], self.scatter_idx),
-                                     deterministic, return_attn_probs)
-        options.update(self._dropout_head0(dropout_p, query.shape[2], self.scatter_idx))
-        options.update(self._local_sinks(sinks, query.shape[2], self.scatter_idx))
-        options.update(self._doc_option(cu_doclens, self.scatter_idx))
+        head_kw, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2], self.scatter_idx)
+        options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
+                                     return_attn_probs)
+        options.update(head_kw)
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
         # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
@@ -234,10 +191,7 @@ class LongContextAttentionQKVPacked(_USPLayer):
             return out[..., :D]
         exchange = self.ulysses_size > 1
         cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1])
-        alibi_slopes = self._local_slopes(alibi_slopes, qkv.shape[3], self.scatter_idx - 1)
-        head0 = self._dropout_head0(dropout_p, qkv.shape[3], self.scatter_idx - 1)
-        head0.update(self._local_sinks(sinks, qkv.shape[3], self.scatter_idx - 1))
-        head0.update(self._doc_option(cu_doclens, self.scatter_idx - 1))
+        head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,

@@ -14,6 +14,7 @@ from __future__ import annotations
 import torch
 
 from .. import _C
+from .features import Features
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -128,141 +129,60 @@ class HipBlockBackend:
 _BACKEND = HipBlockBackend()
 
 
-class _SoftcapBackend:
-    """A block backend whose flash calls (fwd, bwd, fwd_packed, bwd_packed) all carry `softcap=cap`; everything else is
-    the wrapped backend's.  Softcap is a per-score transform, so the ring schedules, LSE merges and gradient folds are
-    unchanged: only the block kernels see it."""
+class _FeatureBackend:
+    """A block backend whose flash calls carry the keywords of the features that are on in `f` (kernels/features.py), and no
+    others: a backend written before a feature existed never sees its keyword.  Everything else is the wrapped backend's.
+      softcap  a per-score transform: every flash call carries `softcap=`, the packed ones too; the ring schedules, LSE merges and
+               gradient folds are unchanged.
+      alibi    every dense flash call carries `alibi=slopes`.  The bias of a block depends on WHERE the block lies: a caller whose
+               block is not the whole sequence passes `shift=` with each call (the basic ring does, ring/ring_flash_attn.py).
+      dropout  every dense flash call carries `dropout=(p, seed, row0, key0, head0)`.  The mask is a function of GLOBAL positions
+               (include/usp_hip.h: usp_flash_fwd_dropout), so such a caller passes `at=(row0, key0)` -- where the block's row 0 and
+               key 0 lie -- the way `shift=` is given; without it the block starts at (0, 0).
+      sinks    the forward launches WITHOUT merge_in carry `sinks=`: the sink is position-free and counts once per row, so it rides
+               on the launch that opens the rows' running state (every ring opens each row range with exactly one such launch);
+               the later merge_in launches, the merges and the backward kernels work unchanged on an lse that holds it
+               (usp_flash_fwd_sink).  (Hq,) over the heads of the block calls; sink_grad(lse, delta) binds them.
+      doc      the bound of a launch depends on WHERE the launch lies, and only the schedule knows that: fwd and bwd take the
+               per-launch arrays as `doc=(row_lo, key_hi)` from the schedule (ring/doc_blocks.py) and hand them on; a launch without
+               the keyword is refused, so that no block of such a call can run unmasked by oversight.
+    The packed calls serve softcap alone and refuse the rest (Features.refuse_packed)."""
 
-    def __init__(self, be, cap: float):
-        self._be, self._cap = be, cap
+    def __init__(self, be, f: Features, seed: int = 0, head0: int = 0):
+        self._be, self._f, self._seed, self._head0 = be, f, int(seed), int(head0)
+
+    def _with(self, kw):
+        f = self._f
+        if f.softcap is not None:
+            kw["softcap"] = f.softcap
+        if f.alibi is not None:
+            kw["alibi"] = f.alibi
+        if f.dropout is not None:
+            row0, key0 = kw.pop("at", (0, 0))
+            kw["dropout"] = (f.dropout, self._seed, int(row0), int(key0), self._head0)
+        if f.doc is not None and kw.get("doc") is None:
+            raise RuntimeError("a launch under cu_doclens carries its doc=(row_lo, key_hi) arrays (ring/doc_blocks.py)")
+        return kw
 
     def fwd(self, *args, **kw):
-        self._be.fwd(*args, softcap=self._cap, **kw)
+        if self._f.sinks is not None and not kw.get("merge_in", args[8] if len(args) > 8 else False):
+            kw["sinks"] = self._f.sinks
+        self._be.fwd(*args, **self._with(kw))
 
     def bwd(self, *args, **kw):
-        self._be.bwd(*args, softcap=self._cap, **kw)
-
-    def fwd_packed(self, *args, **kw):
-        self._be.fwd_packed(*args, softcap=self._cap, **kw)
-
-    def bwd_packed(self, *args, **kw):
-        self._be.bwd_packed(*args, softcap=self._cap, **kw)
-
-    def __getattr__(self, name):
-        return getattr(self._be, name)
-
-
-class _AlibiBackend:
-    """A block backend whose dense flash calls (fwd, bwd) all carry `alibi=slopes`; everything else is the wrapped backend's.
-    The bias of a block depends on WHERE the block lies: a caller whose block is not the whole sequence passes `shift=` with
-    each call (the basic ring does, ring/ring_flash_attn.py).  The packed calls refuse: the kernels serve ALiBi on dense
-    launches only."""
-
-    def __init__(self, be, slopes):
-        self._be, self._slopes = be, slopes
-
-    def fwd(self, *args, **kw):
-        self._be.fwd(*args, alibi=self._slopes, **kw)
-
-    def bwd(self, *args, **kw):
-        self._be.bwd(*args, alibi=self._slopes, **kw)
-
-    def fwd_packed(self, *args, **kw):
-        raise NotImplementedError("alibi_slopes is not supported on packed (variable-length) batches")
-
-    def bwd_packed(self, *args, **kw):
-        raise NotImplementedError("alibi_slopes is not supported on packed (variable-length) batches")
-
-    def __getattr__(self, name):
-        return getattr(self._be, name)
-
-
-class _DropoutBackend:
-    """A block backend whose dense flash calls (fwd, bwd) all carry `dropout=(p, seed, row0, key0, head0)`; everything else is
-    the wrapped backend's.  It holds (p, seed, head0); the mask is a function of GLOBAL positions (include/usp_hip.h:
-    usp_flash_fwd_dropout), so a caller whose block is not the whole sequence passes `at=(row0, key0)` -- where the block's row 0
-    and key 0 lie -- with each call, the way `shift=` is given (the basic ring does, ring/ring_flash_attn.py); without it the
-    block starts at (0, 0).  The packed calls refuse: the kernels serve dropout on dense launches only."""
-
-    def __init__(self, be, p: float, seed: int, head0: int = 0):
-        self._be, self._p, self._seed, self._head0 = be, p, int(seed), int(head0)
-
-    def _dropout(self, kw):
-        row0, key0 = kw.pop("at", (0, 0))
-        return (self._p, self._seed, int(row0), int(key0), self._head0)
-
-    def fwd(self, *args, **kw):
-        self._be.fwd(*args, dropout=self._dropout(kw), **kw)
-
-    def bwd(self, *args, **kw):
-        self._be.bwd(*args, dropout=self._dropout(kw), **kw)
-
-    def fwd_packed(self, *args, **kw):
-        raise NotImplementedError("dropout_p is not supported on packed (variable-length) batches")
-
-    def bwd_packed(self, *args, **kw):
-        raise NotImplementedError("dropout_p is not supported on packed (variable-length) batches")
-
-    def __getattr__(self, name):
-        return getattr(self._be, name)
-
-
-class _SinkBackend:
-    """A block backend whose forward launches WITHOUT merge_in carry `sinks=`; everything else is the wrapped backend's.  The
-    sink is position-free and counts once per row: it rides on the launch that opens the rows' running state (every ring opens
-    each row range with exactly one such launch), the later merge_in launches, the merges and the backward kernels then work
-    unchanged on an lse that holds it (include/usp_hip.h: usp_flash_fwd_sink).  `sinks`: (Hq,) over the heads of the block calls.
-    The packed calls refuse: the kernels serve sinks on dense launches only."""
-
-    def __init__(self, be, sinks):
-        self._be, self._sinks = be, sinks
-
-    def fwd(self, *args, **kw):
-        merge_in = kw.get("merge_in", args[8] if len(args) > 8 else False)
-        if merge_in:
-            self._be.fwd(*args, **kw)
-        else:
-            self._be.fwd(*args, sinks=self._sinks, **kw)
+        self._be.bwd(*args, **self._with(kw))
 
     def sink_grad(self, lse, delta, out=None, accum=False):
         """The rank's share of the sinks' gradient from its rows' global lse and delta (fp32 (Hq,))."""
-        return self._be.sink_grad(self._sinks, lse, delta, out=out, accum=accum)
+        return self._be.sink_grad(self._f.sinks, lse, delta, out=out, accum=accum)
 
     def fwd_packed(self, *args, **kw):
-        raise NotImplementedError("sinks is not supported on packed (variable-length) batches")
+        self._f.refuse_packed()
+        self._be.fwd_packed(*args, softcap=self._f.softcap, **kw)
 
     def bwd_packed(self, *args, **kw):
-        raise NotImplementedError("sinks is not supported on packed (variable-length) batches")
-
-    def __getattr__(self, name):
-        return getattr(self._be, name)
-
-
-class _DocBackend:
-    """A block backend of a call under a document mask (`cu_doclens`).  The bound of a launch depends on WHERE the launch lies,
-    and only the schedule knows that: `fwd` and `bwd` take the per-launch arrays as the keyword `doc=(row_lo, key_hi)` from the
-    schedule (ring/doc_blocks.py builds them on the host and uploads them once per call) and hand it on; a launch without the
-    keyword is refused, so that no block of such a call can run unmasked by oversight.  Everything else is the wrapped
-    backend's.  The packed calls refuse: the kernels serve the mask on dense launches only."""
-
-    def __init__(self, be):
-        self._be = be
-
-    def fwd(self, *args, doc=None, **kw):
-        if doc is None:
-            raise RuntimeError("a launch under cu_doclens carries its doc=(row_lo, key_hi) arrays (ring/doc_blocks.py)")
-        self._be.fwd(*args, doc=doc, **kw)
-
-    def bwd(self, *args, doc=None, **kw):
-        if doc is None:
-            raise RuntimeError("a launch under cu_doclens carries its doc=(row_lo, key_hi) arrays (ring/doc_blocks.py)")
-        self._be.bwd(*args, doc=doc, **kw)
-
-    def fwd_packed(self, *args, **kw):
-        raise NotImplementedError("cu_doclens is not supported on packed (variable-length) batches")
-
-    def bwd_packed(self, *args, **kw):
-        raise NotImplementedError("cu_doclens is not supported on packed (variable-length) batches")
+        self._f.refuse_packed()
+        self._be.bwd_packed(*args, softcap=self._f.softcap, **kw)
 
     def __getattr__(self, name):
         return getattr(self._be, name)
@@ -291,35 +211,23 @@ def get_block_backend(beside_transfers: bool = False, softcap=None, alibi=None, 
     call of the returned backend carries it; None / 0: the backend itself, whose calls carry no softcap keyword
     (backends written before softcap existed keep working).  `alibi`: flash-attn's alibi_slopes as the block calls take them
     (an fp32 (Hq,) or (B, Hq) tensor on the operands' device, _C.alibi_value), None = off: every dense flash call carries
-    them; together with softcap: NotImplementedError (no kernel holds both steps).  `dropout`: (p, seed, head0), None or
-    p = 0 = off: every dense flash call carries p, the seed and the head offset, and takes `at=(row0, key0)` (_DropoutBackend);
-    together with softcap or alibi: NotImplementedError.  `sinks`: one logit per query head of the block calls (a (Hq,) tensor on
-    the operands' device, _C.sinks_value), None = off: the forward launches that open a row range carry it (_SinkBackend) and the
-    backend offers sink_grad(lse, delta); together with softcap, alibi or dropout: NotImplementedError.  `doc`: anything but
-    None / False = the call runs under a document mask: fwd and bwd take the per-launch `doc=(row_lo, key_hi)` keyword from the
-    schedule (_DocBackend); together with softcap, alibi, dropout or sinks: NotImplementedError."""
+    them.  `dropout`: (p, seed, head0), None or p = 0 = off: every dense flash call carries p, the seed and the head offset, and
+    takes `at=(row0, key0)`.  `sinks`: one logit per query head of the block calls (a (Hq,) tensor on the operands' device,
+    _C.sinks_value), None = off: the forward launches that open a row range carry it and the backend offers
+    sink_grad(lse, delta).  `doc`: anything but None / False = the call runs under a document mask: fwd and bwd take the
+    per-launch `doc=(row_lo, key_hi)` keyword from the schedule.  What each feature does to the calls: _FeatureBackend; which
+    of them go together (NotImplementedError otherwise): kernels/features.py."""
     be = _BACKEND
     if beside_transfers and hasattr(be, "beside_transfers"):
         be = be.beside_transfers()
     cap = _C.softcap_value(softcap)
-    if doc is not None and doc is not False:
-        from ..ring import doc_blocks
-        doc_blocks.refuse_beside(None, cap, alibi, None if dropout is None else _C.dropout_value(dropout[0]), sinks)
-        return _DocBackend(be)
-    if sinks is not None:
-        _check_sinks(cap, alibi, dropout[0] if dropout is not None else None)
-        return _SinkBackend(be, sinks)
-    if dropout is not None and _C.dropout_value(dropout[0]) is not None:
-        if cap is not None:
-            raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
-        if alibi is not None:
-            raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
-        return _DropoutBackend(be, _C.dropout_value(dropout[0]), dropout[1], dropout[2] if len(dropout) > 2 else 0)
-    if alibi is not None:
-        if cap is not None:
-            raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
-        return _AlibiBackend(be, alibi)
-    return be if cap is None else _SoftcapBackend(be, cap)
+    p = None if dropout is None else _C.dropout_value(dropout[0])
+    if doc is False:
+        doc = None
+    if cap is None and alibi is None and p is None and sinks is None and doc is None:
+        return be                                  # nothing on (the plain call): no record
+    f = Features(None, cap, alibi, p, sinks, doc).check()
+    return _FeatureBackend(be, f, *(dropout[1:3] if p is not None else ()))
 
 
 def set_block_backend(backend):
@@ -335,44 +243,9 @@ def _default_scale(q, softmax_scale):
     return q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale
 
 
-def _check_plain(dropout_p, softcap, alibi_slopes):
-    """Refuses what the kernels do not serve and returns the softcap as the kernels take it (None = off).
-    window_size, softcap and alibi_slopes ARE served: the block kernels take flash-attn's (left, right) window, its tanh logit
-    cap and its ALiBi slopes (include/usp_hip.h, USP_ATTN_WINDOW / USP_ATTN_SOFTCAP / usp_flash_fwd_alibi) -- ALiBi and
-    softcap not together.  dropout_p is served too (usp_flash_fwd_dropout), but by no kernel that holds a second score-level
-    step: together with softcap or alibi_slopes it is refused here; what a call with dropout needs beyond that (a state) is
-    decided beside this check (_dropout_of).  A negative, NaN or infinite softcap and a dropout_p that is NaN, negative or >= 1
-    raise ValueError (flash-attn ignores a negative softcap silently)."""
-    p = _C.dropout_value(dropout_p)
-    cap = _C.softcap_value(softcap)
-    if p is not None and cap is not None:
-        raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
-    if p is not None and alibi_slopes is not None:
-        raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
-    if alibi_slopes is not None and cap is not None:
-        raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
-    return cap
-
-
-def _check_sinks(cap, alibi_slopes, dropout_p):
-    """Refuses what no sink kernel holds: a second score-level step."""
-    for on, what in ((cap is not None, "softcap"), (alibi_slopes is not None, "alibi_slopes"),
-                     (_C.dropout_value(dropout_p) is not None, "dropout_p")):
-        if on:
-            raise NotImplementedError(f"sinks together with {what} is not supported by the HIP attention kernels")
-
-
-def sinks_of(sinks, q):
-    """`sinks` checked against q (B, S, Hq, D) (_C.sinks_value: ValueError): the tensor as given (it may require grad), or None."""
-    if sinks is not None:
-        _C.sinks_value(sinks, q.shape[2], q.device, q.dtype)
-    return sinks
-
-
-def _dropout_of(dropout_p, rng_state, what):
-    """(p, seed, row0, key0, head0) of a block call with dropout, or None when it is off.  The block contracts return no
-    state, so the caller supplies it: dropout_p > 0 without `rng_state` is refused."""
-    p = _C.dropout_value(dropout_p)
+def _dropout_of(p, rng_state, what):
+    """(p, seed, row0, key0, head0) of a block call with dropout, or None when it is off (`p`: the decoded probability).  The
+    block contracts return no state, so the caller supplies it: dropout_p > 0 without `rng_state` is refused."""
     if p is None:
         return None
     if rng_state is None:
@@ -381,33 +254,16 @@ def _dropout_of(dropout_p, rng_state, what):
     return (p,) + rng_state_of(rng_state)
 
 
-def _block_backend_for(cap, alibi_slopes, q, dr, sinks=None):
-    """(backend, per-call keywords) of a single-block call: softcap / ALiBi / dropout / sinks as given."""
-    if sinks is not None:
-        return get_block_backend(softcap=cap, alibi=alibi_slopes, dropout=None if dr is None else (dr[0], dr[1], dr[4]),
-                                 sinks=sinks_of(sinks, q)), {}
-    if dr is None:
-        return get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q)), {}
-    return get_block_backend(softcap=cap, alibi=_alibi_of(alibi_slopes, q), dropout=(dr[0], dr[1], dr[4])), {"at": (dr[2], dr[3])}
-
-
-def _alibi_of(alibi_slopes, q):
-    """flash-attn's alibi_slopes, checked against q (B, S, Hq, D) (_C.alibi_value: ValueError), as the block calls take it."""
-    al = _C.alibi_value(alibi_slopes, q.shape[0], q.shape[2], q.device)
-    return None if al is None else al[0]
-
-
-def docs_of(cu_doclens, q, k, causal, window_size, cap, alibi_slopes, dropout_p, sinks):
-    """`cu_doclens` of a single-block call checked against its operands (ring/doc_blocks.py: parse, ValueError): None when it
-    is off or names one document (exactly the call without it), else the parsed lists.  causal=False, whole q and k of
-    different lengths, or a second mask or score-level step beside it: NotImplementedError."""
-    if cu_doclens is None:
-        return None
-    from ..ring import doc_blocks
-    docs = doc_blocks.parse(cu_doclens, q.shape[0], q.shape[1])
-    doc_blocks.refuse_not_causal_self(causal, q.shape[1], k.shape[1])
-    doc_blocks.refuse_beside(window_of(window_size), cap, alibi_slopes, _C.dropout_value(dropout_p), sinks)
-    return None if docs is doc_blocks.SINGLE else docs
+def _block_call(f: Features, q, dr):
+    """(backend, per-call keywords) of the one launch of a single-block call with the features `f` and the dropout state `dr`."""
+    be = get_block_backend(softcap=f.softcap, alibi=f.alibi, dropout=None if dr is None else (dr[0], dr[1], dr[4]),
+                           sinks=f.sinks, doc=f.doc)
+    kw = {"window": f.window}
+    if dr is not None:
+        kw["at"] = (dr[2], dr[3])
+    if f.doc is not None:
+        kw["doc"] = _whole_doc(f.doc, q)
+    return be, kw
 
 
 def _whole_doc(docs, q):
@@ -435,25 +291,19 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     `cu_doclens` (keyword only): the cumulative document lengths [0, e1, ..., Sq] of the sequence, host data (ring/doc_blocks.py):
     row i sees key j iff start(i) <= j <= i.  Needs causal=True and equally long q and k; not together with window_size, softcap,
     alibi_slopes, dropout_p or sinks.  None or the single document [0, Sq]: exactly the call without it."""
-    cap = _check_plain(dropout_p, softcap, alibi_slopes)
-    if sinks is not None:
-        _check_sinks(cap, alibi_slopes, dropout_p)
-    docs = docs_of(cu_doclens, q, k, causal, window_size, cap, alibi_slopes, dropout_p, sinks)
-    dr = _dropout_of(dropout_p, rng_state, "hip_attn_forward")
+    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens)
+    dr = _dropout_of(f.dropout, rng_state, "hip_attn_forward")
     B, Sq, Hq, D = q.shape
     scale = _default_scale(q, softmax_scale)
     if kernel_head_dim(D) != D:                 # e.g. 96: on zero-padded copies (kernel_head_dim)
         out, lse = hip_attn_forward(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=scale, causal=causal,
-                                    window_size=window_size, softcap=cap, alibi_slopes=alibi_slopes, rng_state=rng_state,
-                                    sinks=sinks, cu_doclens=docs)
+                                    window_size=window_size, softcap=f.softcap, alibi_slopes=alibi_slopes, rng_state=rng_state,
+                                    sinks=sinks, cu_doclens=f.doc)
         return out[..., :D].contiguous(), lse
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
-    if docs is not None:
-        get_block_backend(doc=True).fwd(q, k, v, scale, True, lse, out=out, doc=_whole_doc(docs, q))
-        return out, lse
-    be, kw = _block_backend_for(cap, alibi_slopes, q, dr, sinks)
-    be.fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size), **kw)
+    be, kw = _block_call(f, q, dr)
+    be.fwd(q, k, v, scale, bool(causal), lse, out=out, **kw)
     return out, lse
 
 
@@ -467,27 +317,22 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
     `cu_doclens` (keyword only): as hip_attn_forward took it."""
-    cap = _check_plain(dropout_p, softcap, alibi_slopes)
-    if sinks is not None:
-        _check_sinks(cap, alibi_slopes, dropout_p)
-        if dsinks is None:
-            raise ValueError("hip_attn_backward with sinks needs the fp32 (Hq,) buffer dsinks")
-    docs = docs_of(cu_doclens, q, k, bwd_causal, window_size, cap, alibi_slopes, dropout_p, sinks)
-    if docs is not None:
-        be, at_kw = get_block_backend(doc=True), {}
-    else:
-        be, at_kw = _block_backend_for(cap, alibi_slopes, q, _dropout_of(dropout_p, rng_state, "hip_attn_backward"), sinks)
+    f = Features.of(q, k, bwd_causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens)
+    if sinks is not None and dsinks is None:
+        raise ValueError("hip_attn_backward with sinks needs the fp32 (Hq,) buffer dsinks")
+    dr = _dropout_of(f.dropout, rng_state, "hip_attn_backward")
     B, Sq, Hq, D = q.shape
     dev = q.device
     if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
         pdo, pq, pk, pv, po = pad_head_dim(dout, q, k, v, out)
         g = [torch.empty_like(t) for t in (pq, pk, pv)]
         hip_attn_backward(pdo, pq, pk, pv, po, softmax_lse, g[0], g[1], g[2], dropout_p, _default_scale(q, softmax_scale),
-                          bwd_causal, window_size, cap, alibi_slopes, deterministic, rng_state, sinks=sinks, dsinks=dsinks,
-                          cu_doclens=docs)
+                          bwd_causal, window_size, f.softcap, alibi_slopes, deterministic, rng_state, sinks=sinks, dsinks=dsinks,
+                          cu_doclens=f.doc)
         for dst, src in zip((block_dq_buffer, block_dk_buffer, block_dv_buffer), g):
             dst.copy_(src[..., :D])
         return
+    be, kw = _block_call(f, q, dr)
     delta = torch.empty((B, Hq, Sq), dtype=torch.float32, device=dev)
     be.delta(dout, out, delta)
     lse = softmax_lse if softmax_lse.dtype == torch.float32 else softmax_lse.float()
@@ -500,10 +345,8 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
         return t.dim() == 4 and t.stride(3) == 1 and all(st % 4 == 0 for st in t.stride()[:3])
     tgt = [t if direct(t) else torch.empty(t.shape, dtype=t.dtype, device=dev)
            for t in (block_dq_buffer, block_dk_buffer, block_dv_buffer)]
-    if docs is not None:
-        at_kw = {"doc": _whole_doc(docs, q)}
     be.bwd(dout, q, k, v, lse, delta, None, None, None, _default_scale(q, softmax_scale), bool(bwd_causal),
-           dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], window=window_of(window_size), **at_kw)
+           dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], **kw)
     for t, dst in zip(tgt, (block_dq_buffer, block_dk_buffer, block_dv_buffer)):
         if t is not dst:
             dst.copy_(t)
@@ -561,11 +404,8 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     `sinks` (keyword only): one learned logit per query head, (Hq,) fp32 or q.dtype (hip_attn_forward); it may require grad, and
     its gradient comes back in its own dtype and shape.  Not together with softcap, alibi_slopes or dropout_p.
     `cu_doclens` (keyword only): the document mask of a packed sequence (hip_attn_forward), padded head dims included."""
-    cap = _check_plain(dropout_p, softcap, alibi_slopes)
-    if sinks is not None:
-        _check_sinks(cap, alibi_slopes, dropout_p)
-        sinks_of(sinks, q)
-    cu_doclens = docs_of(cu_doclens, q, k, causal, window_size, cap, alibi_slopes, dropout_p, sinks)
+    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens)
+    cap, cu_doclens = f.softcap, f.doc
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)
         res = hip_attn_func(*pad_head_dim(q, k, v), dropout_p=dropout_p, softmax_scale=_default_scale(q, softmax_scale),

@@ -1,0 +1,76 @@
+"""The optional features of one attention call -- window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens -- as ONE
+record, and the ONE table of which of them the kernels serve together.  Pure argument logic: nothing here loads the library,
+so the CPU orchestration tests import it as it is."""
+from typing import NamedTuple
+
+from .._C import _window, alibi_value, dropout_value, sinks_value, softcap_value
+
+# field of the record -> the flash-attn-style argument the messages name
+ARGUMENT = dict(window="window_size", softcap="softcap", alibi="alibi_slopes", dropout="dropout_p", sinks="sinks", doc="cu_doclens")
+# The combination table, a precedence list: the first feature that is on owns the call (its kernels run it), and beside it the
+# listed ones are refused, in this order -- no kernel holds a second mask or score-level step.  A window goes with everything
+# but the document mask.
+REFUSES = (("doc", ("window", "softcap", "alibi", "dropout", "sinks")),
+           ("sinks", ("softcap", "alibi", "dropout")),
+           ("dropout", ("softcap", "alibi")),
+           ("alibi", ("softcap",)),
+           ("softcap", ()))
+PACKED = ("softcap",)         # what the packed (variable-length) launches serve
+
+
+class Features(NamedTuple):
+    """The decoded options of one call; None = off.  window: (left, right); softcap: the cap, a float > 0; alibi: the slopes as
+    the block calls take them; dropout: the drop probability in (0, 1); sinks: the logits as given (they may require grad);
+    doc: the parsed document lists (ring/doc_blocks.py) -- or any marker where only "on" matters."""
+    window: object = None
+    softcap: object = None
+    alibi: object = None
+    dropout: object = None
+    sinks: object = None
+    doc: object = None
+
+    @classmethod
+    def of(cls, q, k, causal, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
+           ring_degree: int = 1):
+        """The checked record of a call with flash-attn-style arguments on q (B, Sq, Hq, D) and k, each rank holding 1 /
+        ring_degree of the sequence.  ValueError: a malformed value (_C.softcap_value, dropout_value, alibi_value, sinks_value,
+        doc_blocks.parse); NotImplementedError: a refused combination -- judged first, on what is given --, a document mask that is
+        not causal self-attention.  A cu_doclens of one document is exactly the call without it: off -- after the checks."""
+        f = cls(_window(window_size), softcap_value(softcap), alibi_slopes, dropout_value(dropout_p), sinks, cu_doclens)
+        f.check()                                  # (on what is on and off: a refused pair is refused before a tensor or list is read)
+        if cu_doclens is not None:
+            from ..ring import doc_blocks
+            docs = doc_blocks.parse(cu_doclens, q.shape[0], ring_degree * q.shape[1])
+            doc_blocks.refuse_not_causal_self(causal, ring_degree * q.shape[1], ring_degree * k.shape[1])
+            return f._replace(doc=None if docs is doc_blocks.SINGLE else docs)
+        if alibi_slopes is not None:
+            f = f._replace(alibi=alibi_value(alibi_slopes, q.shape[0], q.shape[2], q.device)[0])
+        if sinks is not None:
+            sinks_value(sinks, q.shape[2], q.device, q.dtype)
+        return f
+
+    def any(self) -> bool:                         # (by identity: `==` on a tensor field costs tens of microseconds)
+        return not (self.window is None and self.softcap is None and self.alibi is None and self.dropout is None
+                    and self.sinks is None and self.doc is None)
+
+    def check(self):
+        """Refuses what the table refuses; returns the record."""
+        for owner, refused in _REFUSES_AT:
+            if self[owner] is not None:
+                for other in refused:
+                    if self[other] is not None:
+                        a, b = ARGUMENT[self._fields[owner]], ARGUMENT[self._fields[other]]
+                        raise NotImplementedError(f"{a} together with {b} is not supported by the HIP attention kernels")
+                break
+        return self
+
+    def refuse_packed(self):
+        """Refuses what the packed (variable-length) launches do not serve."""
+        for field, name in ARGUMENT.items():
+            if field != "window" and field not in PACKED and getattr(self, field) is not None:
+                raise NotImplementedError(f"{name} is not supported on packed (variable-length) batches")
+
+
+# REFUSES by position in the record (check runs on every call, the plain one too)
+_REFUSES_AT = tuple((Features._fields.index(owner), tuple(Features._fields.index(other) for other in refused))
+                    for owner, refused in REFUSES)

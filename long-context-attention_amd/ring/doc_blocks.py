@@ -71,15 +71,6 @@ def parse(cu_doclens, B: int, S_total: int):
     return Docs(docs)
 
 
-def refuse_beside(window, softcap, alibi_slopes, dropout_p, sinks):
-    """cu_doclens beside a second mask or score-level step: no kernel holds both.  The arguments are the already decoded
-    ones: None = off."""
-    for on, what in ((window is not None, "window_size"), (softcap is not None, "softcap"), (alibi_slopes is not None, "alibi_slopes"),
-                     (dropout_p is not None, "dropout_p"), (sinks is not None, "sinks")):
-        if on:
-            raise NotImplementedError(f"cu_doclens together with {what} is not supported by the HIP attention kernels")
-
-
 def refuse_not_causal_self(causal, Sq_total: int, Sk_total: int):
     """The document mask is intra-document CAUSAL self-attention."""
     if not causal:

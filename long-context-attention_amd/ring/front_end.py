@@ -1,13 +1,15 @@
 """The public front end of every ring: ONE autograd Function and ONE *_func / *_kvpacked_func / *_qkvpacked_func trio,
 made per ring from its (forward, backward) pair.  The ring modules keep their schedules and bind their public names to what
 `ring_front_end` returns; the surfaces are the reference's (yunchang/ring/*.py), argument for argument."""
+from typing import NamedTuple
+
 import torch
 import torch.distributed as dist
 
-from .._C import alibi_value, dropout_value, sinks_value, softcap_value
+from .._C import dropout_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
-from . import doc_blocks
+from ..kernels.features import Features
 from .utils import group_info
 from .varlen_utils import unflatten_lse
 
@@ -25,96 +27,79 @@ def _check_hot_path_args(dropout_p, window_size, softcap):
     softcap_value(softcap)
 
 
-def _check_alibi(alibi_slopes, q, softcap, group, packed, served_beyond_one_block):
-    """ALiBi (flash-attn's alibi_slopes) on a ring.  The bias of a block depends on where the block lies in the whole sequence,
-    so a ring serves it only where it places every block: the dense rings at ring degree 1 (ONE block: basic, zigzag, stripe)
-    and the basic ring beyond (`served_beyond_one_block`: its forward decides, USP_RING_ALIBI=global).  Everything else refuses;
-    a wrong shape, dtype or device of the slopes is a ValueError (_C.alibi_value)."""
-    if alibi_slopes is None:
-        return
-    if packed:
-        raise NotImplementedError("alibi_slopes is not supported by the variable-length (packed) rings: use the basic ring "
-                                  "(ring_impl_type=\"basic\", ring_flash_attn_func) on dense batches")
-    if softcap_value(softcap) is not None:
-        raise NotImplementedError("alibi_slopes together with softcap is not supported by the HIP attention kernels")
-    alibi_value(alibi_slopes, q.shape[0], q.shape[2], q.device)
-    if not served_beyond_one_block and group_info(dist, group)[0] > 1:
-        raise NotImplementedError("alibi_slopes across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
-                                  "rings: use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func), which serves "
-                                  "it over global positions with USP_RING_ALIBI=global")
+NOT_SERVED, ONE_BLOCK, ANY_DEGREE = 0, 1, 2
 
 
-def _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, served, served_beyond_one_block):
-    """Dropout (flash-attn's dropout_p) on a ring: the drop probability as the block launches take it, or None when it is off.
-    The mask is a function of global positions (include/usp_hip.h: usp_flash_fwd_dropout), so a ring serves it where it places
-    every block in the whole sequence: the dense rings at ring degree 1 (ONE block: basic, zigzag, stripe) and the basic ring
-    beyond (`served_beyond_one_block`), by default; `served` = False: a ring whose forward takes no rng_state -- the reference has no competing semantics there (its ring backward drops
-    the rng state).  Everything else refuses; NaN, a negative value or one >= 1 is a ValueError (_C.dropout_value).
-    _check_hot_path_args still refuses dropout for every caller that does not come through here (the async layer)."""
+class RingServes(NamedTuple):
+    """What one ring serves of the features whose block launches depend on where the block lies (kernels/features.py), each
+    NOT_SERVED, ONE_BLOCK (at ring degree 1, where every dense ring is one block over the natural order) or ANY_DEGREE (the
+    ring's forward places every block, or refuses by its own rules: the basic ring's USP_RING_WINDOW / USP_RING_ALIBI).  With
+    it goes what `forward` / `backward` take: `rng_state=(seed, head0)` where dropout is served, `sinks=` where sinks are (the
+    backward then returns (dq, dk, dv, dsinks fp32)), `cu_doclens=` (the parsed lists) where the document mask is served at
+    ANY_DEGREE -- a ring with ONE_BLOCK there hands such a call to the basic ring's one-block call.  ONE_BLOCK has a meaning for
+    alibi, dropout and doc only: a window is either left to the ring's forward (ANY_DEGREE) or refused, and the sinks, being
+    position-free, are served at any degree or not at all (ring_front_end asserts both)."""
+    window: int = NOT_SERVED
+    alibi: int = NOT_SERVED
+    dropout: int = NOT_SERVED
+    sinks: int = NOT_SERVED
+    doc: int = NOT_SERVED
+
+
+PACKED_RING = RingServes()
+DENSE_RING = RingServes(alibi=ONE_BLOCK, dropout=ONE_BLOCK, sinks=ANY_DEGREE, doc=ONE_BLOCK)       # zigzag, stripe
+BASIC_RING = RingServes(*(ANY_DEGREE,) * 5)
+
+# feature -> (its name in the refusals, what the packed rings advise, what a ONE_BLOCK ring advises beyond ring degree 1)
+_BASIC = "use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func)"
+_ADVICE = {
+    "doc": ("cu_doclens", "use LongContextAttention (ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches", _BASIC),
+    "sinks": ("sinks", "use a dense ring (ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)", None),
+    "alibi": ("alibi_slopes", _BASIC + " on dense batches", _BASIC + ", which serves it over global positions with "
+                                                                      "USP_RING_ALIBI=global"),
+    "dropout": ("dropout_p != 0", _BASIC + " on dense batches", _BASIC + ", which serves it over global positions"),
+}
+
+
+def _refuse_unserved(serves, doc=None, sinks=None, alibi=None, dropout=None):
+    """NOT_SERVED is what the packed rings are: the first of the given ones that is on and not served is refused in their name."""
+    for feature, value in (("doc", doc), ("sinks", sinks), ("alibi", alibi), ("dropout", dropout)):
+        if value is not None and not getattr(serves, feature):
+            name, advice, _ = _ADVICE[feature]
+            raise NotImplementedError(f"{name} is not supported by the variable-length (packed) rings: {advice}")
+
+
+def _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, group):
+    """(the drop probability, the parsed document lists) of one ring call, None = off, or the refusal of what this ring does not
+    serve or the kernels do not serve together (kernels/features.py: Features).
+    The block launches of ALiBi, dropout and the document mask depend on where the block lies in the WHOLE sequence (ring degree
+    x the local length; `cu_doclens` describes all of it and is the same on every rank), so a ring serves them only where it
+    places every block; the sink is position-free and rides on the one launch without merge_in with which every dense ring opens
+    a row range, at any ring degree.  For each feature that is on: the packed rings refuse, every dense ring serves ring degree
+    1, beyond it only a ring that declares so (`serves`).  Then the combination table; a malformed value is a ValueError
+    (Features.of).  A window that the ring's forward does not judge, and dropout from callers that do not come through here (the
+    async layer), stay with _check_hot_path_args."""
     p = dropout_value(dropout_p)
-    if p is None:
-        return None
-    if packed:
-        raise NotImplementedError("dropout_p != 0 is not supported by the variable-length (packed) rings: use the basic ring "
-                                  "(ring_impl_type=\"basic\", ring_flash_attn_func) on dense batches")
-    if not served:
-        raise NotImplementedError("dropout_p != 0 is not supported by this HIP ring attention: use the basic ring "
-                                  "(ring_impl_type=\"basic\", ring_flash_attn_func)")
-    if softcap_value(softcap) is not None:
-        raise NotImplementedError("dropout_p together with softcap is not supported by the HIP attention kernels")
-    if alibi_slopes is not None:
-        raise NotImplementedError("dropout_p together with alibi_slopes is not supported by the HIP attention kernels")
-    P = group_info(dist, group)[0]
-    if P > 1 and not served_beyond_one_block:
-        raise NotImplementedError("dropout_p != 0 across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
-                                  "rings: use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func), which serves it "
-                                  "over global positions")
-    if P > 1 and q.shape[1] % 4:
-        raise NotImplementedError(f"dropout_p != 0 at ring degree {P} needs a local sequence length that is a multiple of 4 "
-                                  f"(one Philox call covers a 4 x 4 patch of the mask), got {q.shape[1]}")
-    return p
-
-
-def _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed):
-    """Attention sinks (one learned logit per query head, include/usp_hip.h: usp_flash_fwd_sink) on a ring.  The sink is
-    position-free and counts once per row, and every dense ring opens each row's running state with exactly one launch without
-    merge_in: the sink rides on that launch (kernels/attention.py: _SinkBackend), at any ring degree, and the merges and the
-    backward kernels are unchanged.  The packed rings refuse, and so does a second score-level step (softcap, alibi_slopes,
-    dropout_p); a wrong shape, dtype or device is a ValueError (_C.sinks_value)."""
-    if sinks is None:
-        return
-    if packed:
-        raise NotImplementedError("sinks is not supported by the variable-length (packed) rings: use a dense ring "
-                                  "(ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)")
-    for on, what in ((softcap_value(softcap) is not None, "softcap"), (alibi_slopes is not None, "alibi_slopes"),
-                     (dropout_value(dropout_p) is not None, "dropout_p")):
-        if on:
-            raise NotImplementedError(f"sinks together with {what} is not supported by the HIP attention kernels")
-    sinks_value(sinks, q.shape[2], q.device, q.dtype)
-
-
-def _check_doc(cu_doclens, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, served_beyond_one_block):
-    """The document mask (`cu_doclens`, ring/doc_blocks.py) on a ring: the parsed lists, or None when it is off or names one
-    document (exactly the call without it).  `cu_doclens` describes the WHOLE sequence, ring degree x the local length, and is
-    the same on every rank.  Served by the basic ring at any ring degree and by the zigzag and stripe rings at ring degree 1,
-    where they are one block over the natural order; the packed rings refuse.  causal=False, whole q and k of different lengths
-    and a second mask or score-level step beside it are refused; a malformed list is a ValueError."""
-    if cu_doclens is None:
-        return None
-    if packed:
-        raise NotImplementedError("cu_doclens is not supported by the variable-length (packed) rings: use LongContextAttention "
-                                  "(ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches")
-    P = group_info(dist, group)[0]
-    docs = doc_blocks.parse(cu_doclens, q.shape[0], P * q.shape[1])
-    doc_blocks.refuse_not_causal_self(causal, P * q.shape[1], P * k.shape[1])
-    window = None if window_size is None or tuple(window_size) == (-1, -1) else tuple(window_size)
-    doc_blocks.refuse_beside(window, softcap_value(softcap), alibi_slopes, dropout_value(dropout_p), sinks)
-    if docs is doc_blocks.SINGLE:
-        return None
-    if P > 1 and not served_beyond_one_block:
-        raise NotImplementedError("cu_doclens across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
-                                  "rings: use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func)")
-    return docs
+    if cu_doclens is None and sinks is None and alibi_slopes is None and p is None:
+        # the hot path: nothing to place, and nothing the table refuses (a window and softcap go with each other) -- no record
+        _check_hot_path_args(dropout_p, (-1, -1) if serves.window else window_size, softcap)
+        return None, None
+    _refuse_unserved(serves, doc=cu_doclens, sinks=sinks, alibi=alibi_slopes, dropout=p)
+    # (the ring degree is asked only where a feature needs it: a refusal by the table needs no process group)
+    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, p, sinks, cu_doclens,
+                    1 if cu_doclens is None else group_info(dist, group)[0])
+    if f.doc is not None or f.alibi is not None or p is not None:
+        P = group_info(dist, group)[0]
+        for feature in ("doc", "alibi", "dropout"):
+            if P > 1 and getattr(f, feature) is not None and getattr(serves, feature) != ANY_DEGREE:
+                name, _, advice = _ADVICE[feature]
+                raise NotImplementedError(f"{name} across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
+                                          f"rings: {advice}")
+        if P > 1 and p is not None and q.shape[1] % 4:
+            raise NotImplementedError(f"dropout_p != 0 at ring degree {P} needs a local sequence length that is a multiple of 4 "
+                                      f"(one Philox call covers a 4 x 4 patch of the mask), got {q.shape[1]}")
+    _check_hot_path_args(dropout_p if p is None else 0.0, (-1, -1) if serves.window else window_size, softcap)
+    return p, f.doc
 
 
 def _basic_ring():
@@ -137,45 +122,37 @@ def ring_dropout(dropout_p, rng_state):
     return p, int(rng_state[0]), int(rng_state[1])
 
 
-def ring_front_end(stem, class_name, forward, backward, packed=False, attn_processor=False, window_in_forward=False,
-                   alibi_in_forward=False, dropout=False, dropout_in_forward=False, sinks=False, doc=False):
+def ring_front_end(stem, class_name, forward, backward, serves: RingServes, packed=False, attn_processor=False):
     """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
 
+        serves             what the ring serves of window_size, alibi_slopes, dropout_p, sinks and cu_doclens, and with it what
+                           `forward` / `backward` take (RingServes; the refusals: _place).
+                           dropout: one seed per call is drawn here from torch's default CPU generator (draw_seed), in the
+                           autograd forward, and reused by the backward; the dense *_func take the keyword-only `dropout_head0`
+                           (the global index of the call's query head 0: the Ulysses layers pass their rank's), the Function an
+                           optional trailing argument of that name.
+                           sinks: the dense *_func take the keyword-only `sinks`, (Hq,) fp32 or q.dtype, which may require grad;
+                           the Function takes it as one more optional trailing argument (behind dropout_head0) and its backward
+                           returns the gradient in that slot, in the sinks' dtype.  It is THIS rank's share -- its rows; the sum
+                           over the ring group is the gradient of the replicated parameter, and nothing here reduces it.
+                           cu_doclens: every dense *_func takes the keyword-only `cu_doclens`; the Function takes it as one more
+                           optional trailing argument (behind sinks).
         packed             the variable-length form: q / k / v are (T, H, D) token tensors followed by `cu_seqlens, max_seqlen`;
                            k and v are made contiguous (the dense form takes any view the kernels can address, kernel_operand),
                            there is no `attn_type`, and `return_attn_probs` hands the flattened (H, T) LSE back in the
                            reference's padded (num_seq, H, max_seqlen) layout;
-        attn_processor     the Function carries `attn_processor` to the forward (the basic ring);
-        window_in_forward  `window_size` is judged by the forward, not here (the basic ring serves a window at ring degree 1
-                           and refuses beyond);
-        alibi_in_forward   `alibi_slopes` at ring degree > 1 is judged by the forward (the basic ring: USP_RING_ALIBI); every
-                           other dense ring serves it at ring degree 1, where it is one block, and refuses beyond; the packed
-                           rings refuse it (_check_alibi);
-        dropout            `forward` / `backward` take `rng_state=(seed, head0)` and serve `dropout_p` at ring degree 1 (every
-                           dense ring); dropout_in_forward: also beyond (the basic ring).  One seed per call is drawn here from
-                           torch's default CPU generator (draw_seed), in the autograd forward, and reused by the backward; the
-                           dense *_func take the keyword-only `dropout_head0` (the global index of the call's query head 0: the
-                           Ulysses layers pass their rank's), the Function an optional trailing argument of that name;
-        sinks              `forward` takes `sinks=` and `backward` takes it too and returns (dq, dk, dv, dsinks fp32) with it (the
-                           dense rings, any ring degree: _check_sinks).  The dense *_func take the keyword-only `sinks`, (Hq,)
-                           fp32 or q.dtype, which may require grad; the Function takes it as one more optional trailing
-                           argument (behind dropout_head0) and its backward returns the gradient in that slot, in the sinks'
-                           dtype.  It is THIS rank's share -- its rows; the sum over the ring group is the gradient of the
-                           replicated parameter, and nothing here reduces it.
-        doc                `forward` / `backward` take `cu_doclens=` (the parsed lists) and serve the document mask at any ring
-                           degree (the basic ring).  Every dense *_func takes the keyword-only `cu_doclens` (_check_doc); a ring
-                           without `doc` serves it at ring degree 1 by the basic ring's one-block call and refuses beyond.  The
-                           Function takes it as one more optional trailing argument (behind sinks).
+        attn_processor     the Function carries `attn_processor` to the forward (the basic ring).
     The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
     grad; both exist here only."""
+    assert ONE_BLOCK not in (serves.window, serves.sinks), f"{class_name}: RingServes has no ONE_BLOCK for window and sinks"
     n_lead = 2 if packed else 0
     extra = () if packed else (("attn_type", "attn_processor") if attn_processor else ("attn_type",))
     n_args = n_lead + 9 + len(extra)
 
     def ring_pair(docs):
-        """The (forward, backward) that run a call: this ring's, or -- under a document mask on a ring without `doc`, which
-        _check_doc lets through at ring degree 1 only -- the basic ring's one-block call."""
-        return (forward, backward) if doc or docs is None else _basic_ring()
+        """The (forward, backward) that run a call: this ring's, or -- under a document mask on a ring that serves it as
+        ONE_BLOCK, which _place lets through at ring degree 1 only -- the basic ring's one-block call."""
+        return (forward, backward) if serves.doc == ANY_DEGREE or docs is None else _basic_ring()
 
     def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw,
                     head0=0, sink_t=None, cu_doc=None):
@@ -183,13 +160,7 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         backward)."""
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
-        if sink_t is not None:
-            assert sinks, f"{class_name}: this ring's forward takes no sinks"
-            _check_sinks(sink_t, q, dropout_p, softcap, alibi_slopes, packed)
-        docs = _check_doc(cu_doc, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sink_t, group, packed, doc)
-        _check_alibi(alibi_slopes, q, softcap, group, packed, alibi_in_forward)
-        p = _check_dropout(dropout_p, q, softcap, alibi_slopes, group, packed, dropout, dropout_in_forward)
-        _check_hot_path_args(dropout_p if p is None else 0.0, (-1, -1) if window_in_forward else window_size, softcap)
+        p, docs = _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sink_t, cu_doc, group)
         if packed:
             k, v = k.contiguous(), v.contiguous()
         else:
@@ -251,24 +222,21 @@ def ring_front_end(stem, class_name, forward, backward, packed=False, attn_proce
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
                  cu_doclens=None):
-            _check_doc(cu_doclens, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, doc)
-            _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed)
+            _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group)
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                           group=None, *, sinks=None, cu_doclens=None):
-            _check_doc(cu_doclens, q, kv[:, 0], causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, doc)
-            _check_sinks(sinks, q, dropout_p, softcap, alibi_slopes, packed)
+            _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
                               softcap, alibi_slopes, deterministic, return_attn_probs, group)
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                            group=None, *, sinks=None, cu_doclens=None):
-            _check_doc(cu_doclens, qkv[:, 0], qkv[:, 1], causal, window_size, softcap, alibi_slopes, dropout_p, sinks, group, packed, doc)
-            _check_sinks(sinks, qkv[:, 0], dropout_p, softcap, alibi_slopes, packed)
+            _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group)
     else:

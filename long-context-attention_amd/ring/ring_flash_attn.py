@@ -33,7 +33,7 @@ import torch.distributed as dist
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend, window_of
 from . import block_pieces, doc_blocks
-from .front_end import ring_dropout, ring_front_end
+from .front_end import BASIC_RING, ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, return_dkdv_direct, travel_dkdv
 from .window_blocks import WindowPlan
 
@@ -131,7 +131,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                             attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None,
                             rng_state=None, sinks=None, cu_doclens=None):
-    """`cu_doclens`: the parsed document lists of the whole sequence (ring/front_end.py: _check_doc), None = off.
+    """`cu_doclens`: the parsed document lists of the whole sequence (ring/front_end.py: _place), None = off.
     `rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `sinks`: one logit per query head; it rides on
     the launch that opens the rows' state (step 0; the window planner's first block), at any ring degree.  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
@@ -141,7 +141,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
     block_pieces.refuse_sinks(sinks, pieces)
-    assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _check_doc"
+    assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _place"
     be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks,
                            doc=cu_doclens)
     if pieces:
@@ -201,7 +201,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
     block_pieces.refuse_sinks(sinks, pieces)
-    assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _check_doc"
+    assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _place"
     be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks,
                            doc=cu_doclens)
     if pieces:
@@ -254,5 +254,5 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
 
 
 (RingFlashAttnFunc, ring_flash_attn_func, ring_flash_attn_kvpacked_func, ring_flash_attn_qkvpacked_func) = ring_front_end(
-    "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, attn_processor=True,
-    window_in_forward=True, alibi_in_forward=True, dropout=True, dropout_in_forward=True, sinks=True, doc=True)
+    "ring_flash_attn", "RingFlashAttnFunc", ring_flash_attn_forward, ring_flash_attn_backward, BASIC_RING,
+    attn_processor=True)

@@ -12,7 +12,7 @@ import torch
 import torch.distributed as dist
 
 from ..kernels.attention import get_block_backend
-from .front_end import ring_front_end
+from .front_end import PACKED_RING, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
 from .varlen_utils import SeqTables
 
@@ -89,4 +89,4 @@ def ring_flash_attn_varlen_backward(process_group, dout, q, k, v, out, softmax_l
 
 (RingFlashAttnVarlenFunc, ring_flash_attn_varlen_func, ring_flash_attn_varlen_kvpacked_func,
  ring_flash_attn_varlen_qkvpacked_func) = ring_front_end(
-    "ring_flash_attn_varlen", "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, packed=True)
+    "ring_flash_attn_varlen", "RingFlashAttnVarlenFunc", ring_flash_attn_varlen_forward, ring_flash_attn_varlen_backward, PACKED_RING, packed=True)

@@ -14,7 +14,7 @@ import torch.distributed as dist
 
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend
-from .front_end import ring_dropout, ring_front_end
+from .front_end import DENSE_RING, ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
 
 
@@ -54,9 +54,9 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
                               attn_type: AttnType = AttnType.HIP, overlap=False, rng_state=None, sinks=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, use ring flash attn instead"
     P, r = group_info(dist, process_group)
-    assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
-    dr = ring_dropout(dropout_p, rng_state)      # (p, seed, head0) | None: ring degree 1 only (ring/front_end.py: _check_dropout)
-    assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _place)"
+    dr = ring_dropout(dropout_p, rng_state)      # (p, seed, head0) | None: ring degree 1 only (ring/front_end.py: _place)
+    assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _place)"
     # `sinks`: one logit per query head, on the launch that opens the rows' state (step 0, every row), at any ring degree
     be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
     B, S, H, D = q.shape
@@ -77,9 +77,9 @@ def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, s
                                overlap=False, defer=None, rng_state=None, sinks=None):
     assert causal, "stripe flash attn only supports causal attention, if not causal, ring flash attn instead"
     P, r = group_info(dist, process_group)
-    assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
+    assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _place)"
     dr = ring_dropout(dropout_p, rng_state)
-    assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _place)"
     be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
     B, S, H, D = q.shape
     dev = q.device
@@ -108,4 +108,4 @@ def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, s
 
 
 (StripeFlashAttnFunc, stripe_flash_attn_func, stripe_flash_attn_kvpacked_func, stripe_flash_attn_qkvpacked_func) = ring_front_end(
-    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, dropout=True, sinks=True)
+    "stripe_flash_attn", "StripeFlashAttnFunc", stripe_flash_attn_forward, stripe_flash_attn_backward, DENSE_RING)

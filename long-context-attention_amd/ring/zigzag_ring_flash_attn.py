@@ -26,7 +26,7 @@ import torch.distributed as dist
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend
 from . import block_pieces
-from .front_end import _check_hot_path_args, ring_dropout, ring_front_end      # (_check_hot_path_args: still importable from here)
+from .front_end import DENSE_RING, _check_hot_path_args, ring_dropout, ring_front_end      # (_check_hot_path_args: still importable from here)
 from .utils import FULL, KVRelay, group_info, ZigzagKVFetch, final_grads, kv_relay_mode, travel_dkdv, zigzag_fetch_pieces
 
 
@@ -208,13 +208,13 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
     to the end.
     `softcap` > 0: every block launch caps its scores (flash-attn's softcap); the schedule is the same.
     `alibi`: flash-attn's alibi_slopes, served where the ring is ONE block (ring degree 1, no pieces).
-    `dropout`: (p, seed, head0), likewise (ring/front_end.py: _check_dropout).
+    `dropout`: (p, seed, head0), likewise (ring/front_end.py: _place).
     `sinks`: one logit per query head, on the launch that opens the rows' state (step 0, every row), at any ring degree; not with
     `first` / `tail` (ring/block_pieces.py: refuse_sinks)."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None          # (the caller has exchanges in flight by definition)
-    assert alibi is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
-    assert dropout is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    assert alibi is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _place)"
+    assert dropout is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _place)"
     block_pieces.refuse_sinks(sinks, pieces)
     be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi, dropout=dropout, sinks=sinks)
     B, S2, H, D = q.shape
@@ -317,9 +317,9 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
     assert causal == True, "zigzag ring is meaningless for causal=False"
     P, r = group_info(dist, process_group)
     pieces = first is not None or dq_first is not None      # (the caller has exchanges in flight by definition)
-    assert alibi_slopes is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _check_alibi)"
+    assert alibi_slopes is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _place)"
     dr = ring_dropout(dropout_p, rng_state)
-    assert dr is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _check_dropout)"
+    assert dr is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _place)"
     block_pieces.refuse_sinks(sinks, pieces)
     be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
     if P == 1 and pieces:
@@ -377,4 +377,4 @@ def zigzag_ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_l
 (ZigZagRingFlashAttnFunc, zigzag_ring_flash_attn_func, zigzag_ring_flash_attn_kvpacked_func,
  zigzag_ring_flash_attn_qkvpacked_func) = ring_front_end(
     "zigzag_ring_flash_attn", "ZigZagRingFlashAttnFunc", zigzag_ring_flash_attn_forward, zigzag_ring_flash_attn_backward,
-    dropout=True, sinks=True)
+    DENSE_RING)

@@ -23,7 +23,7 @@ import torch
 import torch.distributed as dist
 
 from ..kernels.attention import get_block_backend
-from .front_end import ring_front_end
+from .front_end import PACKED_RING, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
 from .varlen_utils import SeqTables
 
@@ -119,4 +119,5 @@ def zigzag_ring_flash_attn_varlen_backward(process_group, dout, q, k, v, out, so
 
 (ZigZagRingFlashAttnVarlenFunc, zigzag_ring_flash_attn_varlen_func, zigzag_ring_flash_attn_varlen_kvpacked_func,
  zigzag_ring_flash_attn_varlen_qkvpacked_func) = ring_front_end(
-    "zigzag_ring_flash_attn_varlen", "ZigZagRingFlashAttnVarlenFunc", zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward, packed=True)
+    "zigzag_ring_flash_attn_varlen", "ZigZagRingFlashAttnVarlenFunc", zigzag_ring_flash_attn_varlen_forward, zigzag_ring_flash_attn_varlen_backward,
+    PACKED_RING, packed=True)

@@ -11,8 +11,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from .._C import dropout_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_alibi_slopes, local_heads, local_sinks
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_options
 from ..kernels import AttnType, select_flash_attn_impl
 
 
@@ -40,25 +39,14 @@ class UlyssesAttention(torch.nn.Module):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None) -> Tensor:
-        if alibi_slopes is not None:     # slopes over the layer's heads are cut to this rank's (comm/all_to_all.py: local_heads)
-            if (self.scatter_idx, self.gather_idx) != (2, 1):
-                raise NotImplementedError("alibi_slopes needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
-            alibi_slopes = local_alibi_slopes(alibi_slopes, query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
+        # what depends on the heads this rank holds behind the exchange (comm/all_to_all.py: local_options; cu_doclens is checked
+        # against the whole sequence q then holds: kernels/features.py)
+        head_kw, alibi_slopes = local_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2],
+                                              dist.get_world_size(self.spg), dist.get_rank(self.spg),
+                                              (self.scatter_idx, self.gather_idx) == (2, 1), "scatter_idx=2, gather_idx=1")
         q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
-                       softmax_scale=q.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale)
-        if dropout_value(dropout_p) is not None:      # the mask is keyed by the layer's GLOBAL query head (include/usp_hip.h)
-            if (self.scatter_idx, self.gather_idx) != (2, 1):
-                raise NotImplementedError("dropout_p != 0 needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
-            options["dropout_head0"] = local_heads(query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg)).start
-        if sinks is not None:
-            if (self.scatter_idx, self.gather_idx) != (2, 1):
-                raise NotImplementedError("sinks needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
-            options["sinks"] = local_sinks(sinks, query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
-        if cu_doclens is not None:     # the whole sequence's document lists, the same on every rank: behind the exchange a rank
-            if (self.scatter_idx, self.gather_idx) != (2, 1):     # holds whole sequences of some heads, so it is one block's mask
-                raise NotImplementedError("cu_doclens needs the head-scatter exchange (scatter_idx=2, gather_idx=1)")
-            options["cu_doclens"] = cu_doclens     # (checked against the whole sequence q now holds: kernels/attention.py: docs_of)
+                       softmax_scale=q.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale, **head_kw)
         attended = self.attn_fn(q, k, v, **options)
         return self._to_seq(attended[0] if isinstance(attended, tuple) else attended)

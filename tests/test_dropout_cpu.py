@@ -332,7 +332,7 @@ def test_python_refusals_and_validation(monkeypatch):
             with pytest.raises(NotImplementedError, match=other):
                 call()
     with pytest.raises(NotImplementedError):
-        KA._check_plain(0.1, 30.0, None)
+        KA.Features.of(None, None, False, softcap=30.0, alibi_slopes=None, dropout_p=0.1)
     with pytest.raises(NotImplementedError):
         FE._check_hot_path_args(0.1, (-1, -1), 0.0)                # still refuses: dropout is decided beside it
     # the fwd-only / bwd-only contracts return no state: without one they refuse

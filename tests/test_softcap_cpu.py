@@ -217,7 +217,11 @@ def test_abi_rejects_bad_softcap_without_launch():
 # ---- Python surface: what is still refused, and a bad cap ------------------------------------------------------------------------------
 def test_python_refusals_unchanged_and_bad_softcap_raises():
     import yunchang_amd as Y
-    from yunchang_amd.kernels.attention import _check_plain, hip_attn_func, hip_attn_forward
+    from yunchang_amd.kernels.attention import hip_attn_func, hip_attn_forward
+    from yunchang_amd.kernels.features import Features
+
+    def _check_plain(dropout_p, softcap, alibi_slopes):      # (no operands: the combination is judged before the slopes' shape)
+        return Features.of(None, None, False, softcap=softcap, alibi_slopes=alibi_slopes, dropout_p=dropout_p).softcap
     from yunchang_amd.ring.zigzag_ring_flash_attn import _check_hot_path_args
     q = torch.zeros(1, 8, 2, 64, dtype=torch.bfloat16)
     with pytest.raises(NotImplementedError):
