@@ -286,38 +286,55 @@ def test_public_path_padded_head_dim(dev, nccl_single, path):
 
 # ---- 7. the basic ring on virtual ranks -----------------------------------------------------------------------------------------
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("rd", [2, 4])
+@pytest.mark.parametrize("rd", [2, 4, pytest.param((2, 2), id="ud2-rd2")])
 def test_basic_ring_on_virtual_ranks(dev, nccl_single, monkeypatch, rd):
     """S_total = 1024: documents crossing rank edges, one rank (the last of four) holding only whole small documents -- its
-    steps beyond the diagonal see nothing and are dropped."""
+    steps beyond the diagonal see nothing and are dropped.  (ud, rd) = (2, 2): the Ulysses exchange around the ring, built as
+    tests/test_gpu_sink.py::test_grid_invariance_on_virtual_ranks builds its grid, with B = 2 and one list per entry -- a single
+    document, and a list with a boundary on the ring's rank edge, so that this entry sees nothing in the second ring rank's
+    step below the diagonal while the other one does."""
+    import yunchang_amd.comm.all_to_all as A
     import yunchang_amd.ring.ring_flash_attn as R
     from yunchang_amd.ring import doc_blocks
     from virtual_grid import VirtualGridPairwise, patch_dist, run_grid
+    ud, rd = rd if isinstance(rd, tuple) else (1, rd)
     S, Hq, Hkv, D = 1024, 4, 2, 64
-    cu = [0, 100, 300, 515, 768, 800, 900, 1024]
-    docs = doc_blocks.parse(cu, 1, S)
-    grid = VirtualGridPairwise(1, rd, nccl_single)
+    B, cu = (1, [0, 100, 300, 515, 768, 800, 900, 1024]) if ud == 1 else (2, [[0, S], [0, 100, 300, 512, 768, 800, 1024]])
+    docs = doc_blocks.parse(cu, B, S)
+    ws = ud * rd
+    grid = VirtualGridPairwise(ud, rd, nccl_single)
     patch_dist(monkeypatch, grid)
-    g = torch.Generator().manual_seed(rd)
-    q, k, v, do = (torch.randn(1, S, h, D, generator=g).to(torch.bfloat16).to(dev) for h in (Hq, Hkv, Hkv, Hq))
-    rows, scale = S // rd, D ** -0.5
-    loc = [[t[:, r * rows:(r + 1) * rows].contiguous() for t in (q, k, v, do)] for r in range(rd)]
-    streams = [torch.cuda.Stream(device=dev) for _ in range(rd)]
+    g = torch.Generator().manual_seed(rd if ud == 1 else 22)
+    q, k, v, do = (torch.randn(B, S, h, D, generator=g).to(torch.bfloat16).to(dev) for h in (Hq, Hkv, Hkv, Hq))
+    rows, scale = S // ws, D ** -0.5
+    loc = [[t[:, r * rows:(r + 1) * rows].contiguous() for t in (q, k, v, do)] for r in range(ws)]
+    streams = [torch.cuda.Stream(device=dev) for _ in range(ws)]
     torch.cuda.synchronize()
 
     def rank_fn(r):
         torch.cuda.set_device(dev)
-        _, rpg = grid.groups_of(r)
+        upg, rpg = grid.groups_of(r)
         lq, lk, lv, ldo = loc[r]
         with torch.cuda.stream(streams[r]):
+            if ud > 1:                                       # rank = ring * ud + u: sequence shards in, head shards around the ring
+                lq, ldo = (A.heads_to_seq(t, upg, contiguous=True) for t in (lq, ldo))
+                lk, lv = (A.kv_heads_to_seq(t, upg, contiguous=True) for t in (lk, lv))
             out, lse = R.ring_flash_attn_forward(rpg, lq, lk, lv, scale, causal=True, cu_doclens=docs)
-            return [out] + list(R.ring_flash_attn_backward(rpg, ldo, lq, lk, lv, out, lse, scale, causal=True, cu_doclens=docs))
-    res = run_grid(grid, rd, rank_fn)
+            grads = list(R.ring_flash_attn_backward(rpg, ldo, lq, lk, lv, out, lse, scale, causal=True, cu_doclens=docs))
+            if ud > 1:
+                return [A.seq_to_heads(out, upg), A.seq_to_heads(grads[0], upg), A.kv_seq_to_heads(grads[1], upg, Hkv),
+                        A.kv_seq_to_heads(grads[2], upg, Hkv)]
+            return [out] + grads
+    res = run_grid(grid, ws, rank_fn)
     torch.cuda.synchronize()
-    ref = doc_ref.ref_bwd(do, q, k, v, scale, doc_ref.global_mask(cu, S), out_dtype=q.dtype)
-    if rd == 4:
+    ref = doc_ref.ref_bwd(do, q, k, v, scale, doc_ref.global_mask(cu, S, B), out_dtype=q.dtype)
+    if ud == 1 and rd == 4:
         assert not doc_blocks.ring_visible(docs, rows, 3, 1) and doc_blocks.ring_visible(docs, rows, 2, 1)
-    for r in range(rd):
+    if ud > 1:                                               # the ring's shard is S / rd rows: entry 1 sees nothing in (rank 1, step 1)
+        assert doc_blocks.ring_visible(docs, S // rd, 1, 1)
+        assert doc_blocks.block_arrays(docs[0], S // rd, S // rd, 0, S // rd) is not None
+        assert doc_blocks.block_arrays(docs[1], S // rd, S // rd, 0, S // rd) is None
+    for r in range(ws):
         sl = slice(r * rows, (r + 1) * rows)
         for got, want, tol, name in ((res[r][0], ref[0], TOL["bfloat16"]["out"], "out"), (res[r][1], ref[2], grad_tol("bfloat16", 2), "dq"),
                                      (res[r][2], ref[3], grad_tol("bfloat16", 2), "dk"), (res[r][3], ref[4], grad_tol("bfloat16", 2), "dv")):

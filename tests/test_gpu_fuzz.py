@@ -2,7 +2,8 @@
 Sq != Sk, every head dim, both dtypes) through the C ABI against the CPU oracle, every call launched twice and
 required to be bit-identical (the kernels are deterministic; a difference means a race).  Sizes keep the fp64
 oracle at a few milliseconds per case.  Seeds are fixed: failures reproduce.  `test_fuzz_features` puts softcap, ALiBi and dropout
-(one a case) through the shapes of the shifted sweep, the second launch with an independent strided layout per tensor."""
+(one a case) through the shapes of the shifted sweep, the second launch with an independent strided layout per tensor.
+Attention sinks and the document mask have sweeps of their own on these shapes: tests/test_gpu_fuzz_sink_doc.py."""
 import numpy as np
 import pytest
 import torch
