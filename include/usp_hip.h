@@ -121,6 +121,10 @@ enum {
 /* USP_ATTN_DOC: a FEATURE bit like USP_ATTN_ALIBI: the library exports usp_flash_fwd_doc / usp_flash_bwd_doc (below), which take a
  * per-row left key bound (the document mask of packed pre-training sequences) beside the unchanged argument blocks (ABI still v7). */
 #define USP_ATTN_DOC 2048
+/* USP_ATTN_SPAN: a FEATURE bit like USP_ATTN_DOC: the library exports usp_flash_fwd_span / usp_flash_bwd_span (below), which take a
+ * per-row right key bound beside the document's left one (bidirectional spans: prefix-LM blocks, packed bidirectional documents)
+ * beside the unchanged argument blocks (ABI still v7). */
+#define USP_ATTN_SPAN 4096
 
 typedef struct usp_tensor {
   void* ptr;
@@ -409,6 +413,45 @@ int usp_flash_fwd_doc(const usp_fwd_args* args, const int32_t* row_lo, int64_t r
 int usp_flash_bwd_doc(const usp_bwd_args* args, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* key_hi,
                       int64_t key_hi_stride_b, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Span bound: usp_flash_fwd_doc / usp_flash_bwd_doc with a right key bound read per row in place of the causal diagonal.  Inside a
+ * bidirectional span (an image or prefix block of a prefix-LM, a whole document of a packed encoder) every row sees the whole
+ * span; for one launch (a whole sequence, or one block of a ring) that is
+ *     row i sees key j   iff   row_lo[i] <= j < row_hi[i]      ( equally:  key_lo[j] <= i < key_hi[j] ),
+ * with four HOST-computed DEVICE int32 arrays in the LAUNCH'S OWN coordinates, laid out and strided like row_lo / key_hi above:
+ *     row_lo[i] in [0, Sk]   the first key row i sees                        key_lo[j] in [0, Sq]   the first row that sees key j
+ *     row_hi[i] in [0, Sk]   one past the last key row i sees                                         ( = #{ i : row_hi[i] <= j } )
+ *                                                                            key_hi[j] in [0, Sq]   one past the last row that sees it
+ *                                                                                                     ( = #{ i : row_lo[i] <= j } )
+ * ALL FOUR MUST BE NON-DECREASING and describe the same set; a row is empty when row_lo[i] >= row_hi[i].  The library cannot check
+ * it.  Arrays that break it give wrong results, never an out-of-range access: every value read is clamped to [0, Sk] / [0, Sq].
+ * THE DIAGONAL IS FOLDED INTO row_hi BY THE CALLER (a causal row outside every span has row_hi[i] = i + 1 + Sk - Sq in a diagonal
+ * block): these launches run with causal = 0.  Nothing else about the function changes: `lse` is the logsumexp over the visible
+ * keys; a row or a launch that sees nothing gives out = 0, lse = -inf and zero gradients, as ever.  A row tile touches no key tile
+ * in front of its first row's row_lo and none at or past ceil(row_hi[last valid row] / tile); a key block no row tile in front of
+ * key_lo[first key] / tile and none behind its last key's key_hi.
+ *   - row_hi == NULL (backward: and key_lo == NULL) is exactly usp_flash_fwd_doc / usp_flash_bwd_doc on the remaining arrays -- and
+ *     so, with everything NULL, the plain launch: the same kernels, bit-identical results, the strides of the absent arrays ignored;
+ *   - forward: with row_hi, row_lo == NULL means "all zero";
+ *   - backward: the dQ launch reads (row_lo, row_hi) and the dK/dV launch (key_lo, key_hi).  With row_hi or key_lo, a launch that
+ *     is not skipped and lacks one of its two arrays is USP_EINVAL; USP_BWD_SKIP_* drops the requirement for the skipped launch;
+ *   - a negative stride is USP_EINVAL;
+ *   - with row_hi / key_lo: causal != 0, USP_ATTN_SOFTCAP, USP_ATTN_WINDOW, USP_ATTN_SHIFT, a packed batch (seq_q / seq_k) and
+ *     USP_FORCE_ROW64 are USP_EUNSUPPORTED, nothing launched or written (these checks follow the argument checks every call gets);
+ *   - k_splits, dq_splits and dkdv_splits are IGNORED with the arrays, as under the document mask;
+ *   - every head dim runs on the two-waves-per-SIMD family (span instantiations of its kernels: a wave's tiles below its first
+ *     row's row_hi, and past its item's last row_lo, keep the pipelined loop); usp_last_launch_kinds() reports the wave8 / wave4 /
+ *     reduce bits that were launched.
+ * Everything else is as the argument block says (dkdv_heads, merge_in, final_begin / final_end with acc, USP_LAUNCH_INTERLEAVE,
+ * USP_BWD_SKIP_*, GQA, dq16 / dk16 / dv16, both 16-bit types, head dims 32 / 64 / 128, any aligned layout).  Spans together
+ * with ALiBi, dropout or sinks have no entry point.
+ * -------------------------------------------------------------------------------------------- */
+int usp_flash_fwd_span(const usp_fwd_args* args, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* row_hi,
+                       int64_t row_hi_stride_b, void* stream);
+int usp_flash_bwd_span(const usp_bwd_args* args, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* row_hi,
+                       int64_t row_hi_stride_b, const int32_t* key_lo, int64_t key_lo_stride_b, const int32_t* key_hi,
+                       int64_t key_hi_stride_b, void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -509,7 +552,7 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
- * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC, the last four feature bits: the *_alibi / *_dropout / *_sink / *_doc entry points exist).  Unknown flag bits are not rejected by
+ * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN, the last five feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

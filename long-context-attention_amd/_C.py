@@ -32,6 +32,7 @@ USP_ATTN_ALIBI = 256           # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_DROPOUT = 512         # feature bit of usp_attn_features(): usp_flash_fwd_dropout / usp_flash_bwd_dropout exist (not an args flag)
 USP_ATTN_SINK = 1024           # feature bit of usp_attn_features(): usp_flash_fwd_sink / usp_sink_bwd exist (not an args flag)
 USP_ATTN_DOC = 2048            # feature bit of usp_attn_features(): usp_flash_fwd_doc / usp_flash_bwd_doc exist (not an args flag)
+USP_ATTN_SPAN = 4096           # feature bit of usp_attn_features(): usp_flash_fwd_span / usp_flash_bwd_span exist (not an args flag)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -113,14 +114,15 @@ class UspBwdArgs(ctypes.Structure):
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
-           "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc")
-# The entry points of ALiBi, dropout, the sinks and the document mask are the only exports load() does not insist on: they are
+           "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span")
+# The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
 ALIBI_EXPORTS = ("usp_flash_fwd_alibi", "usp_flash_bwd_alibi")
 DROPOUT_EXPORTS = ("usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
 SINK_EXPORTS = ("usp_flash_fwd_sink", "usp_sink_bwd")
 DOC_EXPORTS = ("usp_flash_fwd_doc", "usp_flash_bwd_doc")
+SPAN_EXPORTS = ("usp_flash_fwd_span", "usp_flash_bwd_span")
 
 
 def lib_path() -> str:
@@ -139,7 +141,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -443,6 +445,33 @@ def doc_value(doc, B: int, Sq: int, Sk: int, device):
     return one(row_lo, Sq, "row_lo"), one(key_hi, Sk, "key_hi")
 
 
+def span_value(span, B: int, Sq: int, Sk: int, device):
+    """A block call's `span` keyword -> four (tensor, batch stride) pairs (row_lo, row_hi, key_lo, key_hi) as usp_flash_fwd_span /
+    usp_flash_bwd_span take them, or None when it is off.  `span` = (row_lo, row_hi, key_lo, key_hi): contiguous int32 DEVICE
+    tensors of shape (Sq,) or (B, Sq) for the row arrays and (Sk,) or (B, Sk) for the key arrays, in the launch's own
+    coordinates, the diagonal folded into row_hi (include/usp_hip.h; built on the host by ring/doc_blocks.py); any may be None
+    where the call does not read it (the forward reads the row arrays alone).  Anything else raises ValueError.  (Pure argument
+    check: the CPU orchestration tests call it without a library.)"""
+    if span is None:
+        return None
+    if len(span) != 4:
+        raise ValueError(f"span must be (row_lo, row_hi, key_lo, key_hi), got {len(span)} entries")
+    if all(t is None for t in span):
+        return None
+
+    def one(t, n, what):
+        if t is None:
+            return None, 0
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise ValueError(f"span {what} must be an int32 torch.Tensor")
+        if tuple(t.shape) not in ((n,), (B, n)) or not t.is_contiguous():
+            raise ValueError(f"span {what} must be contiguous with shape ({n},) or ({B}, {n}), got {tuple(t.shape)}")
+        if t.device != torch.device(device):
+            raise ValueError(f"span {what} is on {t.device}, the operands on {device}")
+        return t, (n if t.dim() == 2 else 0)
+    return tuple(one(t, n, what) for t, n, what in zip(span, (Sq, Sq, Sk, Sk), ("row_lo", "row_hi", "key_lo", "key_hi")))
+
+
 def _feature_entries():
     """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
     does not insist on."""
@@ -455,7 +484,9 @@ def _feature_entries():
             "usp_flash_fwd_sink": (USP_ATTN_SINK, "sinks (USP_ATTN_SINK)", [fwd, vp, vp]),
             "usp_sink_bwd": (USP_ATTN_SINK, "sinks (USP_ATTN_SINK)", [i32, i32, i32, vp, vp, i64, i64, vp, i64, i64, vp, i32, vp]),
             "usp_flash_fwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [fwd, vp, i64, vp]),
-            "usp_flash_bwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [bwd, vp, i64, vp, i64, vp])}
+            "usp_flash_bwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [bwd, vp, i64, vp, i64, vp]),
+            "usp_flash_fwd_span": (USP_ATTN_SPAN, "bidirectional (USP_ATTN_SPAN)", [fwd, vp, i64, vp, i64, vp]),
+            "usp_flash_bwd_span": (USP_ATTN_SPAN, "bidirectional (USP_ATTN_SPAN)", [bwd, vp, i64, vp, i64, vp, i64, vp, i64, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -475,7 +506,7 @@ def _feature_entry(name: str):
     return fn
 
 
-_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _feature_entry      # (the names the per-feature tests call it by)
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):
@@ -505,10 +536,21 @@ def _shift(shift) -> Optional[int]:
     return s
 
 
-def _flash_call(which: str, a, al, dr, sk, dc):
+def _flash_call(which: str, a, al, dr, sk, dc, sp=None):
     """Issues the flash launch `which` ("fwd" | "bwd") of the filled argument block `a` with the decoded extras (alibi_value,
-    dropout_args, sinks_value, doc_value; None = off): through the entry point of the one that is on -- two of them are
-    refused (kernels/features.py) -- or the plain one."""
+    dropout_args, sinks_value, doc_value, span_value; None = off): through the entry point of the one that is on -- two of them
+    are refused (kernels/features.py) -- or the plain one."""
+    if sp is not None:
+        from .kernels.features import Features
+        from .kernels.features import SPAN_ON
+        Features(alibi=al, dropout=dr, sinks=sk, doc=SPAN_ON).check()
+        if dc is not None:
+            raise ValueError("a launch takes doc= or span=, not both: the span arrays hold the document bound")
+        (rl, rl_sb), (rh, rh_sb), (kl, kl_sb), (kh, kh_sb) = sp
+        name = f"usp_flash_{which}_span"             # (the forward reads the row arrays alone)
+        extra = (_ptr(rl), rl_sb, _ptr(rh), rh_sb) + (() if which == "fwd" else (_ptr(kl), kl_sb, _ptr(kh), kh_sb))
+        _check(_feature_entry(name)(ctypes.byref(a), *extra, _stream()), name)
+        return
     if al is None and dr is None and sk is None and dc is None:
         name, extra = "usp_flash_" + which, ()
         fn = getattr(load(), name)
@@ -571,7 +613,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None, dropout=None, sinks=None, doc=None):
+              alibi=None, dropout=None, sinks=None, doc=None, span=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -589,15 +631,19 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     value; `lse` includes it (usp_flash_fwd_sink; a launch without merge_in only; not with softcap, alibi, dropout or
     family="row64").
     `doc`: (row_lo, key_hi) int32 device arrays (doc_value), None = off: row i sees key j only if j >= row_lo[i], the document
-    mask of one launch (usp_flash_fwd_doc; served uncut; not with window, softcap, shift, alibi, dropout, sinks or family="row64")."""
+    mask of one launch (usp_flash_fwd_doc; served uncut; not with window, softcap, shift, alibi, dropout, sinks or family="row64").
+    `span`: (row_lo, row_hi, key_lo, key_hi) int32 device arrays (span_value), None = off: row i sees key j only if
+    row_lo[i] <= j < row_hi[i], the mask of one launch under bidirectional spans with the diagonal folded into row_hi
+    (usp_flash_fwd_span; causal=False only; served uncut; not with doc or anything doc refuses)."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
     cap = softcap_value(softcap)
     ff = _family_flag(family)
     win, sh = _window(window), _shift(shift)
     dc = doc_value(doc, B, Sq, k.shape[1], q.device)     # None: off -- (None, None) included, which is the call without the keyword
+    sp = span_value(span, B, Sq, k.shape[1], q.device)   # None: off, likewise
     if k_splits is None:
-        n = 0 if (sh is not None or dc is not None) else fwd_k_splits(B, Sq, Hq, causal)   # (a document launch is served uncut)
+        n = 0 if (sh is not None or dc is not None or sp is not None) else fwd_k_splits(B, Sq, Hq, causal)   # (a document launch is served uncut)
     else:
         n = int(k_splits)
     a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
@@ -615,7 +661,7 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
-    _flash_call("fwd", a, al, dr, sk, dc)
+    _flash_call("fwd", a, al, dr, sk, dc, sp)
 
 
 def _t3(t: Optional[torch.Tensor]) -> UspTensor:
@@ -754,7 +800,7 @@ def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None, alibi=None, dropout=None, doc=None):
+              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
@@ -764,7 +810,8 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle).  `alibi`: as flash_fwd
     (usp_flash_bwd_alibi).  `dropout`: as flash_fwd (usp_flash_bwd_dropout): the same tuple regenerates the forward's mask;
     `delta` is that of the dropped `out`.  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
-    key_hi; with `only` the other one may be None."""
+    key_hi; with `only` the other one may be None.  `span`: as flash_fwd (usp_flash_bwd_span): the dQ launch reads (row_lo,
+    row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -787,8 +834,9 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     a.flags = (USP_LAUNCH_INTERLEAVE if interleave else 0) | ff | {None: 0, "dkdv": USP_BWD_SKIP_DQ, "dq": USP_BWD_SKIP_DKDV}[only]
     sh = _shift(shift)
     dc = doc_value(doc, B, Sq, Sk, q.device)             # None: off -- (None, None) included
+    sp = span_value(span, B, Sq, Sk, q.device)
     if splits is None:
-        a.dq_splits, a.dkdv_splits = (0, 0) if (sh is not None or dc is not None) else bwd_splits(B, Sq, Sk, Hq, bool(causal))
+        a.dq_splits, a.dkdv_splits = (0, 0) if (sh is not None or dc is not None or sp is not None) else bwd_splits(B, Sq, Sk, Hq, bool(causal))
     else:
         a.dq_splits, a.dkdv_splits = splits
     a.dkdv_heads = int(dkdv_heads)
@@ -806,7 +854,7 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
-    _flash_call("bwd", a, al, dr, None, dc)
+    _flash_call("bwd", a, al, dr, None, dc, sp)
 
 
 def lse_merge(acc, lse, blk_out, blk_lse, first: bool):

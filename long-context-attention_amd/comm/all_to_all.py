@@ -140,7 +140,8 @@ def local_sinks(sinks, H: int, P: int, rank: int):
                      f"got {tuple(sinks.shape)}")
 
 
-def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, rank: int, head_scatter: bool, how: str):
+def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, rank: int, head_scatter: bool, how: str,
+                  bidirectional=None):
     """What a layer of H heads hands its attention function for the options that depend on WHICH heads ulysses rank `rank` of P
     holds behind the exchange: (keyword dict, local slopes).
       alibi_slopes  cut to the rank's heads (local_alibi_slopes);
@@ -152,11 +153,15 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
                     no all-reduce;
       cu_doclens    as given: the list describes the WHOLE sequence and is the same on every rank; behind the exchange a rank
                     holds whole rows of some heads, so the attention function plans its arrays alone (ring/doc_blocks.py).
+      bidirectional as given, likewise (a layer that has parsed it already hands the plan over as `cu_doclens`: the spans ride
+                    inside, ring/doc_blocks.py: Spans).
     Each of them needs an exchange that scatters heads and gathers the sequence (`head_scatter`; `how`: that, in the layer's
     words): NotImplementedError otherwise."""
     p = dropout_value(dropout_p)
     if not head_scatter:
-        for name, value in (("alibi_slopes", alibi_slopes), ("dropout_p != 0", p), ("sinks", sinks), ("cu_doclens", cu_doclens)):
+        doc_name = "cu_doclens" if getattr(cu_doclens, "spans", None) is None else "bidirectional"
+        for name, value in (("alibi_slopes", alibi_slopes), ("dropout_p != 0", p), ("sinks", sinks), (doc_name, cu_doclens),
+                            ("bidirectional", bidirectional)):
             if value is not None:
                 raise NotImplementedError(f"{name} needs the head-scatter exchange ({how})")
     kw = {}
@@ -166,6 +171,8 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
         kw["sinks"] = local_sinks(sinks, H, P, rank)
     if cu_doclens is not None:
         kw["cu_doclens"] = cu_doclens
+    if bidirectional is not None:
+        kw["bidirectional"] = bidirectional
     return kw, local_alibi_slopes(alibi_slopes, H, P, rank)
 
 

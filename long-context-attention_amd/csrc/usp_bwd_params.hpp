@@ -75,6 +75,20 @@ struct BwdDoc {
   int64_t row_lo_sb, key_hi_sb;         // batch strides in elements (0: one array for the whole batch)
 };
 struct BwdArgsDOC : BwdParams, BwdDoc {};
+// Span bound (usp_flash_bwd_span): kernel arguments of the span instantiations only (usp_flash_bwd_span.hip:
+// flash_bwd_span_kernel, flash_bwd_dkdv_span_kernel); every other kernel keeps its argument block and machine code.
+struct BwdSpan {
+  const int* row_hi;                    // int32 (Sq,): one past the last key row i sees (the dQ launch reads it)
+  const int* key_lo;                    // int32 (Sk,): the first row that sees key j (the dK/dV launch reads it)
+  int64_t row_hi_sb, key_lo_sb;         // batch strides in elements (0: one array for the whole batch)
+};
+struct BwdArgsSPAN : BwdParams, BwdDoc, BwdSpan {};
+// What a kernel without the span switch defines for the shared bodies (usp_flash_bwd_dq_body.inc, usp_flash_bwd_dkdv_body.inc)
+#define USP_BWD_NO_SPAN                                          \
+  [[maybe_unused]] constexpr bool SPAN = false;                  \
+  [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
+  [[maybe_unused]] constexpr const int* span_key_lo = nullptr;   \
+  [[maybe_unused]] constexpr int64_t span_rh_sb = 0, span_kl_sb = 0;
 
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the
@@ -127,5 +141,8 @@ int launch_dq_dropout(const BwdArgsDR& p, int D, int dtype, bool causal, int gri
 // The document-mask backward launches (usp_flash_bwd_doc.hip), likewise.
 int launch_dkdv_doc(const BwdArgsDOC& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 int launch_dq_doc(const BwdArgsDOC& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+// The span backward launches (usp_flash_bwd_span.hip), likewise; never causal: the diagonal is folded into the arrays.
+int launch_dkdv_span(const BwdArgsSPAN& p, int D, int dtype, int grid, size_t lds, hipStream_t st);
+int launch_dq_span(const BwdArgsSPAN& p, int D, int dtype, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -36,7 +36,8 @@ namespace usp {
   constexpr bool DOC = false;                       \
   [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
   [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
+  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;   \
+  USP_BWD_NO_SPAN
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_kernel(
@@ -173,8 +174,9 @@ struct BwdExtras {
   BwdAlibi al{};
   DropoutCall dc{};
   BwdDoc doc{};
+  BwdSpan span{};
   Dropout dr{};
-  bool any() const { return al.al_slopes || dr.t || doc.row_lo || doc.key_hi; }
+  bool any() const { return al.al_slopes || dr.t || doc.row_lo || doc.key_hi || span.row_hi || span.key_lo; }
 };
 
 // dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
@@ -206,6 +208,12 @@ static int launch_dkdv(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_
       static_cast<BwdParams&>(pd) = pb;
       static_cast<Dropout&>(pd) = x.dr;
       if (int rc2 = launch_dkdv_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
+    } else if (x.span.key_lo) {                    // span bound: likewise (usp_flash_bwd_span.hip), never causal
+      BwdArgsSPAN pd;
+      static_cast<BwdParams&>(pd) = pb;
+      static_cast<BwdDoc&>(pd) = x.doc;
+      static_cast<BwdSpan&>(pd) = x.span;
+      if (int rc2 = launch_dkdv_span(pd, D, DT, grid, lds_q, st)) return rc2;
     } else if (x.doc.key_hi) {                     // document mask: likewise (usp_flash_bwd_doc.hip)
       BwdArgsDOC pd;
       static_cast<BwdParams&>(pd) = pb;
@@ -253,6 +261,12 @@ static int launch_dq(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_t 
     static_cast<BwdParams&>(pd) = pb;
     static_cast<Dropout&>(pd) = x.dr;
     if (int rc2 = launch_dq_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
+  } else if (x.span.row_hi) {                      // span bound: likewise (usp_flash_bwd_span.hip), never causal
+    BwdArgsSPAN pd;
+    static_cast<BwdParams&>(pd) = pb;
+    static_cast<BwdDoc&>(pd) = x.doc;
+    static_cast<BwdSpan&>(pd) = x.span;
+    if (int rc2 = launch_dq_span(pd, D, DT, grid, lds_q, st)) return rc2;
   } else if (x.doc.row_lo) {                       // document mask: likewise (usp_flash_bwd_doc.hip)
     BwdArgsDOC pd;
     static_cast<BwdParams&>(pd) = pb;
@@ -356,7 +370,8 @@ extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
   return pl.dkdv_bytes + pl.dq_bytes;
 }
 
-// usp_flash_bwd (alibi_slopes == NULL, p_drop == 0, no document array), usp_flash_bwd_alibi, usp_flash_bwd_dropout and usp_flash_bwd_doc
+// usp_flash_bwd (alibi_slopes == NULL, p_drop == 0, no document array), usp_flash_bwd_alibi, usp_flash_bwd_dropout, usp_flash_bwd_doc
+// and usp_flash_bwd_span
 static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stream) {
   const usp_bwd_args* a = a_in;
   using namespace usp;
@@ -372,7 +387,14 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   const bool has_doc = doc.row_lo || doc.key_hi;
   // the dQ launch reads row_lo, the dK/dV launch key_hi: the array of a launch that runs must be there
   if (has_doc && ((!(skip & USP_BWD_SKIP_DQ) && !doc.row_lo) || (!(skip & USP_BWD_SKIP_DKDV) && !doc.key_hi))) return USP_EINVAL;
-  if (int rc = check_doc(*a, has_doc, doc.row_lo_sb, doc.key_hi_sb)) return rc;
+  // span: the dQ launch reads (row_lo, row_hi), the dK/dV launch (key_lo, key_hi): a launch that runs must have both of its arrays
+  // (with them the span's check judges every stride before any decline; it declines all the document's check does)
+  const BwdSpan& span = x.span;
+  const bool has_span = span.row_hi || span.key_lo;
+  if (int rc = check_doc(*a, has_doc && !has_span, doc.row_lo_sb, doc.key_hi_sb)) return rc;
+  if (has_span && ((!(skip & USP_BWD_SKIP_DQ) && !(doc.row_lo && span.row_hi)) || (!(skip & USP_BWD_SKIP_DKDV) && !(doc.key_hi && span.key_lo))))
+    return USP_EINVAL;
+  if (int rc = check_span(*a, has_span, doc.row_lo_sb, doc.key_hi_sb, span.row_hi_sb, span.key_lo_sb)) return rc;
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
@@ -391,7 +413,7 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (packed && (mask.windowed || mask.shifted)) return USP_EUNSUPPORTED;        // dense launches only
   if (a->dq_splits < 0 || a->dq_splits > 8 || a->dkdv_splits < 0 || a->dkdv_splits > 8) return USP_EINVAL;
   usp_bwd_args uncut;                              // a document launch is served uncut (usp_hip.h): the plan of the same call without cuts
-  if (has_doc) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
+  if (has_doc || has_span) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
   const BwdPlan plan = plan_bwd(a);
   if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
   BwdArgsSC p;
@@ -473,5 +495,15 @@ extern "C" int usp_flash_bwd_doc(const usp_bwd_args* a, const int32_t* row_lo, i
   const bool any = row_lo || key_hi;
   usp::BwdExtras x;
   x.doc = usp::BwdDoc{row_lo, key_hi, any ? row_lo_stride_b : 0, any ? key_hi_stride_b : 0};
+  return flash_bwd_call(a, x, stream);
+}
+
+extern "C" int usp_flash_bwd_span(const usp_bwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* row_hi,
+                                  int64_t row_hi_stride_b, const int32_t* key_lo, int64_t key_lo_stride_b, const int32_t* key_hi,
+                                  int64_t key_hi_stride_b, void* stream) {
+  const bool any = row_lo || key_hi, any_span = row_hi || key_lo;    // row_hi == key_lo == NULL: exactly usp_flash_bwd_doc
+  usp::BwdExtras x;
+  x.doc = usp::BwdDoc{row_lo, key_hi, any ? row_lo_stride_b : 0, any ? key_hi_stride_b : 0};
+  x.span = usp::BwdSpan{row_hi, key_lo, any_span ? row_hi_stride_b : 0, any_span ? key_lo_stride_b : 0};
   return flash_bwd_call(a, x, stream);
 }

@@ -22,6 +22,7 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_alibi_kernel(const BwdArgsAL
   [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
   [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;
   [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
+  USP_BWD_NO_SPAN
 #include "usp_flash_bwd_dq_body.inc"
 }
 
@@ -38,6 +39,7 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_alibi_kernel(const BwdA
   [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
   [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;
   [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
+  USP_BWD_NO_SPAN
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

@@ -5,6 +5,8 @@
 // (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones, the document kernels (usp_flash_bwd_doc.hip) the `if constexpr (DOC)`
 // ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
 // (usp_dropout_rng.h: Dropout) and doc_key_hi / doc_kh_sb (int32 key bounds and their batch stride).
+// The span kernels (usp_flash_bwd_span.hip) add the `if constexpr (SPAN)` steps on top of DOC's (span_key_lo / span_kl_sb;
+// USP_BWD_NO_SPAN elsewhere).
 // Dropout: role A forms the un-dropped P, uses P o keep for its dV MFMAs and hands B the un-dropped P with the keep decision in
 // the sign bit (P >= 0: set = dropped; no extra LDS); role B starts its dP chain from -delta t/256 and forms
 // |P| (kept ? chain : -delta t/256); 256/t goes into the epilogue's factor of both outputs.
@@ -93,6 +95,17 @@
     doc_hi = usp_doc_key_hi(kh, orow, p.Sq, p.Sk);
     doc_hi_w0 = usp_doc_key_hi(kh, ow, p.Sq, p.Sk);
     doc_hi_w1 = usp_doc_key_hi(kh, ow + 31, p.Sq, p.Sk);
+  }
+  // SPAN (usp_flash_bwd_span.hip, DOC with the transpose of a right key bound, never CAUSAL): ... and only if i >= key_lo[j]
+  // (monotone): the row tiles in front of the first row that sees the block's first key are not streamed
+  [[maybe_unused]] int span_lo = 0, span_lo_w0 = 0, span_lo_w1 = 0;
+  if constexpr (SPAN) {
+    const int* const kl = span_key_lo + b * span_kl_sb;
+    const int tb = usp_span_first_row_tile(usp_span_key_lo(kl, own0, p.Sq, p.Sk), t_end, kTile);
+    t_begin = tb > t_begin ? tb : t_begin;
+    span_lo = usp_span_key_lo(kl, orow, p.Sq, p.Sk);
+    span_lo_w0 = usp_span_key_lo(kl, ow, p.Sq, p.Sk);
+    span_lo_w1 = usp_span_key_lo(kl, ow + 31, p.Sq, p.Sk);
   }
   const int n_iter = (t_end - t_begin) * p.gsub;
 
@@ -235,6 +248,10 @@
       if constexpr (DOC) {
         active = active && usp_doc_row_tile_live(s0, doc_hi_w1);
         need_mask = need_mask || usp_doc_row_tile_masked(s0, kTile, doc_hi_w0);
+      }
+      if constexpr (SPAN) {
+        active = active && usp_span_row_tile_live(s0, kTile, span_lo_w0);
+        need_mask = need_mask || usp_span_row_tile_masked(s0, span_lo_w1);
       }
 
       if (active) {
@@ -386,6 +403,12 @@
 #pragma unroll
             for (int r = 0; r < 16; ++r)
               if (dh <= 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
+          }
+          if constexpr (SPAN) {                                // ... and only if i >= key_lo[j]
+            const int dlo = span_lo - s0 - 4 * hi;
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (dlo > 32 * h + (r & 3) + 8 * (r >> 2)) sc[h][r] = USP_NEG_INF;
           }
         };
 

@@ -21,7 +21,8 @@ namespace usp {
   constexpr Dropout dr{};                           \
   [[maybe_unused]] const int* const doc_row_lo = p_in.row_lo;   \
   [[maybe_unused]] const int* const doc_key_hi = p_in.key_hi;   \
-  [[maybe_unused]] const int64_t doc_rl_sb = p_in.row_lo_sb, doc_kh_sb = p_in.key_hi_sb;
+  [[maybe_unused]] const int64_t doc_rl_sb = p_in.row_lo_sb, doc_kh_sb = p_in.key_hi_sb;   \
+  USP_BWD_NO_SPAN
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_doc_kernel(const BwdArgsDOC p_in) {

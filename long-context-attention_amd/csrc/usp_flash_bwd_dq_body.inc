@@ -5,6 +5,8 @@
 // (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones, the document kernels (usp_flash_bwd_doc.hip) the `if constexpr (DOC)`
 // ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
 // (usp_dropout_rng.h: Dropout) and doc_row_lo / doc_rl_sb (int32 row bounds and their batch stride).
+// The span kernels (usp_flash_bwd_span.hip) add the `if constexpr (SPAN)` steps on top of DOC's (span_row_hi / span_rh_sb;
+// USP_BWD_NO_SPAN elsewhere).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
@@ -87,6 +89,17 @@
     doc_lo = usp_doc_row_lo(rl, orow, p.Sq, p.Sk);
     doc_lo_w0 = usp_doc_row_lo(rl, ow, p.Sq, p.Sk);
     doc_lo_w1 = usp_doc_row_lo(rl, ow + 31, p.Sq, p.Sk);
+  }
+  // SPAN (usp_flash_bwd_span.hip, DOC with a right bound, never CAUSAL): ... and only if j < row_hi[i] (monotone): the key tiles
+  // behind the last key of the block's last valid row are not streamed; lane and wave keep their bounds like the left ones
+  [[maybe_unused]] int span_hi = 0, span_hi_w0 = 0, span_hi_w1 = 0;
+  if constexpr (SPAN) {
+    const int* const rh = span_row_hi + b * span_rh_sb;
+    t_end = usp_span_key_tiles_end(usp_span_row_hi(rh, own0 + OWN - 1, p.Sq, p.Sk), t_end, kTile);
+    if (t_begin > t_end) t_begin = t_end;
+    span_hi = usp_span_row_hi(rh, orow, p.Sq, p.Sk);
+    span_hi_w0 = usp_span_row_hi(rh, ow, p.Sq, p.Sk);
+    span_hi_w1 = usp_span_row_hi(rh, ow + 31, p.Sq, p.Sk);
   }
   const int n_iter = t_end - t_begin;
 
@@ -199,6 +212,10 @@
       active = active && s0 + kTile > doc_lo_w0;                 // (usp_doc_key_tile_live's left-bound term)
       need_mask = need_mask || usp_doc_key_tile_masked(s0, doc_lo_w1);
     }
+    if constexpr (SPAN) {
+      active = active && s0 < span_hi_w1;                        // (usp_span_key_tile_live's right-bound term)
+      need_mask = need_mask || usp_span_key_tile_masked(s0, kTile, span_hi_w0);
+    }
 
     if (active) {
       // Hand-pinned pipeline over the two 32-row halves h0, h1 of the tile (sched_barrier(0) fences;
@@ -223,6 +240,7 @@
         if (CAUSAL) klim = orow + off < klim ? orow + off : klim;
         int klo = p.win_on ? orow + p.win_lo : -0x40000000;
         if constexpr (DOC) klo = doc_lo;
+        if constexpr (SPAN) klim = span_hi - 1 < klim ? span_hi - 1 : klim;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = k0 + (r & 3) + 8 * (r >> 2);

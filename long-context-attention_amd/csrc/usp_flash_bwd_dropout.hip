@@ -22,7 +22,8 @@ namespace usp {
   constexpr bool DOC = false;                       \
   [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
   [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
+  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;   \
+  USP_BWD_NO_SPAN
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dropout_kernel(const BwdArgsDR p_in) {

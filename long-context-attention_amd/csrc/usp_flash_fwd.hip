@@ -47,7 +47,8 @@ namespace usp {
   constexpr const float* sink_s = nullptr;          \
   constexpr bool DOC = false;                       \
   constexpr const int* doc_row_lo = nullptr;        \
-  constexpr int64_t doc_sb = 0;
+  constexpr int64_t doc_sb = 0;                     \
+  USP_FWD_NO_SPAN
 
 template <int D, int DT, bool CAUSAL, int NWAVES, bool KSPLIT = false>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_kernel(const FwdArgsT<KSPLIT> p_in) {
@@ -149,8 +150,9 @@ struct FwdExtras {
   DropoutCall dc{};
   const float* sinks = nullptr;
   FwdDoc doc{};
+  FwdSpan span{};                // (usp_flash_fwd_span: with row_hi, a NULL doc.row_lo is all zero)
   Dropout dr{};
-  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo; }
+  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo || span.row_hi; }
 };
 
 template <int D, int DT, int NWAVES>
@@ -178,6 +180,12 @@ static int launch_fwd_w(FwdArgsSC p, const FwdExtras& x, bool causal, hipStream_
     static_cast<FwdArgsT<true>&>(pk) = ps;
     pk.sinks = x.sinks;
     if (int rc = launch_fwd_sink(pk, D, DT, causal, NWAVES, grid, lds, st)) return rc;
+  } else if (x.span.row_hi) {                                // span bound: likewise (usp_flash_fwd_span.hip), never causal
+    FwdArgsSPAN pd;
+    static_cast<FwdParams&>(pd) = p;
+    static_cast<FwdDoc&>(pd) = x.doc;
+    static_cast<FwdSpan&>(pd) = x.span;
+    if (int rc = launch_fwd_span(pd, D, DT, NWAVES, grid, lds, st)) return rc;
   } else if (x.doc.row_lo) {                                 // document mask: likewise (usp_flash_fwd_doc.hip)
     FwdArgsDOC pd;
     static_cast<FwdParams&>(pd) = p;
@@ -257,7 +265,7 @@ extern "C" int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* a, int32_t 
 }
 
 // usp_flash_fwd (alibi_slopes == NULL, p_drop == 0, sinks == NULL, row_lo == NULL), usp_flash_fwd_alibi, usp_flash_fwd_dropout,
-// usp_flash_fwd_sink and usp_flash_fwd_doc
+// usp_flash_fwd_sink, usp_flash_fwd_doc and usp_flash_fwd_span
 static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream) {
   using namespace usp;
   launch_kinds_reset();
@@ -267,7 +275,9 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   if (int rc = check_alibi(*a, x.al.al_slopes, x.al.al_sb)) return rc;
   if (int rc = check_dropout(*a, x.dc, &x.dr)) return rc;
   if (int rc = check_sink(*a, x.sinks)) return rc;
-  if (int rc = check_doc(*a, x.doc.row_lo != nullptr, x.doc.row_lo_sb, 0)) return rc;
+  // (with row_hi the span's check judges every stride before any decline; it declines all the document's check does)
+  if (int rc = check_doc(*a, x.doc.row_lo != nullptr && !x.span.row_hi, x.doc.row_lo_sb, 0)) return rc;
+  if (int rc = check_span(*a, x.span.row_hi != nullptr, x.doc.row_lo_sb, x.span.row_hi_sb, 0, 0)) return rc;
   if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
@@ -305,7 +315,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo) {   // (a document launch is served uncut: usp_hip.h)
+  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo && !x.span.row_hi) {   // (a document or span launch is served uncut: usp_hip.h)
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
     if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
@@ -345,5 +355,13 @@ extern "C" int usp_flash_fwd_sink(const usp_fwd_args* a, const float* sinks, voi
 extern "C" int usp_flash_fwd_doc(const usp_fwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, void* stream) {
   usp::FwdExtras x;
   x.doc = usp::FwdDoc{row_lo, row_lo ? row_lo_stride_b : 0};
+  return flash_fwd_call(a, x, stream);
+}
+
+extern "C" int usp_flash_fwd_span(const usp_fwd_args* a, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* row_hi,
+                                  int64_t row_hi_stride_b, void* stream) {
+  usp::FwdExtras x;
+  x.doc = usp::FwdDoc{row_lo, row_lo ? row_lo_stride_b : 0};         // row_hi == NULL: exactly usp_flash_fwd_doc
+  x.span = usp::FwdSpan{row_hi, row_hi ? row_hi_stride_b : 0};
   return flash_fwd_call(a, x, stream);
 }

@@ -4,7 +4,8 @@
 // the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones, the ALiBi kernel (usp_flash_fwd_alibi.hip) the
 // `if constexpr (AL)` ones, the dropout kernel (usp_flash_fwd_dropout.hip) the `if constexpr (DR)` ones, the sink kernel
 // (usp_flash_fwd_sink.hip) the `if constexpr (SINK)` one in the epilogue, the document kernel (usp_flash_fwd_doc.hip) the
-// `if constexpr (DOC)` ones.  The including kernel
+// `if constexpr (DOC)` ones, the span kernel (usp_flash_fwd_span.hip) the `if constexpr (SPAN)` ones on top of them (span_row_hi /
+// span_sb: int32 right row bounds and their batch stride; USP_FWD_NO_SPAN elsewhere).  The including kernel
 // defines `p_in`, KSPLIT / SC / WIN / AL / DR / SINK / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr` (usp_dropout_rng.h:
 // Dropout), sink_s (fp32 (Hq,) sink logits) and doc_row_lo / doc_sb (int32 row bounds and their batch stride).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
@@ -126,7 +127,35 @@
   // wave-uniform ones (first and last valid row of the wave, last row of the item) stay in scalar registers.
   [[maybe_unused]] int doc_lo_w0 = 0, doc_lo_w1 = 0, doc_rot = 0;
   [[maybe_unused]] USP_LDS const int* doc_lds = nullptr;
-  if constexpr (DOC) {
+  // SPAN (usp_flash_fwd_span.hip, DOC with a right bound, never CAUSAL): row i sees key j only if row_lo[i] <= j < row_hi[i], both
+  // monotone.  The same rebasing; row_hi takes the causal diagonal's place in the KV range below: the item ends behind the last key
+  // of its last valid row, a wave's unmasked tiles end at its first row's bound.  The rows' right bounds lie in LDS behind the left
+  // ones.  A NULL row_lo is all zero.
+  [[maybe_unused]] int span_hi_w0 = 0, span_hi_w1 = 0, span_hi_blk = 0;
+  if constexpr (SPAN) {
+    const int* const rl = doc_row_lo ? doc_row_lo + b * doc_sb : nullptr;
+    const int* const rh = span_row_hi + b * span_sb;
+    auto lo_of = [&](int i) { return rl ? usp_doc_row_lo(rl, i, p.Sq, p.Sk) : 0; };
+    const int q0d = qt * kBM, qwd = q0d + wave * 32;
+    const int e = usp_span_row_hi(rh, q0d + kBM - 1, p.Sq, p.Sk);
+    const int kb = usp_doc_first_key_tile(lo_of(q0d), usp_tiles_holding(e, kBN), kBN) * kBN;
+    doc_lo_w0 = lo_of(qwd) - kb;
+    doc_lo_w1 = lo_of(qwd + 31) - kb;
+    doc_rot = usp_doc_uncut_key_tile(lo_of(q0d + kBM - 1) - kb, kBN);
+    span_hi_w0 = usp_span_row_hi(rh, qwd, p.Sq, p.Sk) - kb;
+    span_hi_w1 = usp_span_row_hi(rh, qwd + 31, p.Sq, p.Sk) - kb;
+    span_hi_blk = e - kb;
+    USP_LDS int* const dl = (USP_LDS int*)(smem + 4 * KBYTES + 16);
+    if (tid < kBM) {                            // visible behind the prologue's barrier
+      dl[tid] = lo_of(q0d + tid) - kb;
+      dl[kBM + tid] = usp_span_row_hi(rh, q0d + tid, p.Sq, p.Sk) - kb;
+    }
+    doc_lds = dl + wave * 32 + l31;
+    p.k += 2 * (int64_t)kb * p.k_ss;
+    p.v += 2 * (int64_t)kb * p.v_ss;
+    p.Sk = p.Sk > kb ? p.Sk - kb : 0;
+    p.causal_off -= kb;
+  } else if constexpr (DOC) {
     const int* const rl = doc_row_lo + b * doc_sb;
     const int q0d = qt * kBM, qwd = q0d + wave * 32;
     int e = p.Sk;
@@ -158,6 +187,10 @@
     blk_kv_end = usp_rows_key_end(q0, kBM, p.Sq, p.Sk, 1, off);
     wave_kv_end = wav_last + off + 1 < p.Sk ? wav_last + off + 1 : p.Sk;
   }
+  if constexpr (SPAN) {                                   // the right bound in the diagonal's place (rebased numbering)
+    blk_kv_end = span_hi_blk < p.Sk ? span_hi_blk : p.Sk;
+    wave_kv_end = span_hi_w1 < p.Sk ? span_hi_w1 : p.Sk;
+  }
   if (qw >= p.Sq) wave_kv_end = 0;
   const int nt = blk_kv_end > 0 ? (blk_kv_end + kBN - 1) / kBN : 0;     // = usp_tiles_holding: called, the softcap streams change
   // leading tiles that need neither a causal nor a ragged mask for this wave (= usp_unmasked_tiles: called, the causal split
@@ -166,6 +199,10 @@
   if (CAUSAL) {
     const int lim = qw + off + 1;                         // keys < lim are visible to EVERY row of the wave
     const int nf = lim > 0 ? lim / kBN : 0;
+    n_full = nf < n_full ? nf : n_full;
+  }
+  if constexpr (SPAN) {                                   // keys < the first row's right bound are visible to EVERY row of the wave
+    const int nf = usp_span_unmasked_key_tiles(span_hi_w0, kBN);
     n_full = nf < n_full ? nf : n_full;
   }
   if (qw + 32 > p.Sq) n_full = 0;                         // ragged / inactive waves take the generic loop
@@ -365,6 +402,10 @@
   auto mask = [&](int kt0, f32x16& s0, f32x16& s1) {
     int klim = p.Sk - 1;
     if (CAUSAL) klim = row + off < klim ? row + off : klim;
+    if constexpr (SPAN) {                        // this lane's row_hi, rebased, read like its row_lo below
+      const int khi = doc_lds[kBM] - 1;
+      klim = khi < klim ? khi : klim;
+    }
     const int kb0 = kt0 + 4 * hi;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -586,6 +627,7 @@
       bool need_mask = (kt0 + kBN > p.Sk) || (CAUSAL && kt0 + kBN - 1 > qw + off);
       if constexpr (KSPLIT) need_mask = need_mask || (win && kt0 < qw + 31 + win_lo);
       if constexpr (DOC) need_mask = need_mask || usp_doc_key_tile_masked(kt0, doc_lo_w1);
+      if constexpr (SPAN) need_mask = need_mask || usp_span_key_tile_masked(kt0, kBN, span_hi_w0);
       if constexpr (SC) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {

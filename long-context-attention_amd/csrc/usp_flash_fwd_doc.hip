@@ -26,6 +26,7 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_doc_kernel(const PA 
   constexpr const float* sink_s = nullptr;
   const int* const doc_row_lo = p_in.row_lo;
   const int64_t doc_sb = p_in.row_lo_sb;
+  USP_FWD_NO_SPAN
 #include "usp_flash_fwd_body.inc"
 }
 

@@ -27,6 +27,7 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_sink_kernel(const st
   constexpr bool DOC = false;
   constexpr const int* doc_row_lo = nullptr;
   constexpr int64_t doc_sb = 0;
+  USP_FWD_NO_SPAN
 #include "usp_flash_fwd_body.inc"
 }
 

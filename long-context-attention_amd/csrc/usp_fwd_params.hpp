@@ -78,6 +78,19 @@ struct FwdDoc {
   int64_t row_lo_sb;                    // batch stride in elements (0: one array for the whole batch)
 };
 struct FwdArgsDOC : FwdArgsT<false>, FwdDoc {};
+// Span bound (usp_flash_fwd_span): kernel arguments of the span instantiations only (usp_flash_fwd_span.hip: flash_fwd_span_kernel,
+// the document kernel with a right key bound read per row in place of the causal diagonal); every other kernel keeps its
+// argument block and machine code.
+struct FwdSpan {
+  const int* row_hi;                    // int32 (Sq,): one past the last key row i sees, in the launch's key numbering; NULL = no span launch
+  int64_t row_hi_sb;                    // batch stride in elements (0: one array for the whole batch)
+};
+struct FwdArgsSPAN : FwdArgsT<false>, FwdDoc, FwdSpan {};      // (row_lo may be NULL here: all zero)
+// What a kernel without the span switch defines for the shared body (usp_flash_fwd_body.inc)
+#define USP_FWD_NO_SPAN                                          \
+  [[maybe_unused]] constexpr bool SPAN = false;                  \
+  [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
+  [[maybe_unused]] constexpr int64_t span_sb = 0;
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -102,5 +115,7 @@ int launch_fwd_dropout(const FwdArgsDR& p, int D, int dtype, bool causal, int wa
 int launch_fwd_sink(const FwdArgsSK& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 // The document-mask forward (usp_flash_fwd_doc.hip), likewise; `lds` is the plain kernel's, the launch adds the bounds' room.
 int launch_fwd_doc(const FwdArgsDOC& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
+// The span forward (usp_flash_fwd_span.hip), likewise; never causal: the diagonal is folded into row_hi.
+int launch_fwd_span(const FwdArgsSPAN& p, int D, int dtype, int waves, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -156,6 +156,16 @@ template <class Args> int check_doc(const Args& a, bool has_doc, int64_t row_lo_
   return check_extras(a);
 }
 
+// Span bound (usp_flash_fwd_span / usp_flash_bwd_span).  No row_hi / key_lo: the call is usp_flash_fwd_doc / usp_flash_bwd_doc on the
+// remaining arrays.  With them the diagonal lies in the arrays: a causal call is declined, and the rest is the document's list.
+template <class Args> int check_span(const Args& a, bool has_span, int64_t stride_a, int64_t stride_b, int64_t stride_c, int64_t stride_d) {
+  if (!has_span) return USP_OK;
+  if (stride_a < 0 || stride_b < 0 || stride_c < 0 || stride_d < 0) return USP_EINVAL;
+  if (a.causal) return USP_EUNSUPPORTED;                            // the planner folds the diagonal into row_hi
+  if (a.flags & (USP_ATTN_WINDOW | USP_ATTN_SHIFT)) return USP_EUNSUPPORTED;   // no third bound beside them
+  return check_extras(a);
+}
+
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound
 // at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
 // (forward: the split instantiation, FwdSplit).

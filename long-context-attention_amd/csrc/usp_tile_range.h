@@ -81,6 +81,30 @@
  *                        (the caller ANDs the causal term of usp_row_tile_live)
  *   usp_doc_row_tile_masked ... holds a (row, key of the wave) pair this bound hides, hi_first = usp_doc_key_hi of key ow.
  *                        EXACT for this bound alone; CONSERVATIVE in that rows past Sq count
+ * The span bound (usp_flash_fwd_span / usp_flash_bwd_span): a right key bound read per row in place of the causal diagonal, beside
+ * the document bound's left one.  Four int32 arrays in the launch's own coordinates, all non-decreasing and describing the same
+ * set: row i sees key j iff row_lo[i] <= j < row_hi[i], equally key_lo[j] <= i < key_hi[j], with row_hi[i] in [0, n_keys] one
+ * past the last key row i sees and key_lo[j] in [0, Sq] the first row that sees key j (= #{i : row_hi[i] <= j}).  The launch
+ * runs with causal = 0: the diagonal is folded into row_hi.  A row is empty when row_lo[i] >= row_hi[i].
+ *   usp_span_row_hi      row_hi of row min(i, Sq - 1), clamped to [0, n_keys]   (usp_span_key_lo: key_lo of key min(j, n_keys - 1),
+ *                        clamped to [0, Sq])
+ *   usp_span_key_tiles_end  query side: no key tile from it on holds a key that a valid row up to the last one sees, hi_last =
+ *                        usp_span_row_hi of the last valid row; EXACT for that row; never above t_end
+ *   usp_span_unmasked_key_tiles  query side: the right bound hides no key of the tiles below it from any row from the first
+ *                        one on, hi_first = usp_span_row_hi of the first row.  EXACT (the tile it names, if it lies wholly below n_keys, holds a
+ *                        key the first row does not see)
+ *   usp_span_key_tile_live  query side, wave of rows: hi_last / lo_first = the bounds of its last valid / first row.  CONSERVATIVE:
+ *                        live when each bound alone leaves the wave a pair in the tile; EXACT where the key intervals of
+ *                        consecutive valid rows are not empty and touch or overlap
+ *   usp_span_key_tile_masked ... the right-bound term: some valid row of the wave does not see some key of the tile, hi_first =
+ *                        usp_span_row_hi of the wave's first row.  EXACT for this bound alone; CONSERVATIVE in that keys past
+ *                        n_keys count (they are masked anyway)
+ *   usp_span_first_row_tile key side: no row tile below it holds a row that sees a key of the block from own0 on, lo_first =
+ *                        usp_span_key_lo of key own0; EXACT for that key; never above t_end
+ *   usp_span_row_tile_live  key side, wave of keys, lo_first = usp_span_key_lo of its first key: the tile of rows from s0 holds a
+ *                        row at or past it.  EXACT for this bound alone (the caller ANDs usp_doc_row_tile_live)
+ *   usp_span_row_tile_masked ... holds a (row, key of the wave) pair this bound hides, lo_last = usp_span_key_lo of the wave's last
+ *                        key below n_keys.  EXACT for this bound alone
  * Every sum stays in `int` for Sq + Sk < 2^29 (usp_mask_decode.h lists them). */
 #ifndef USP_TILE_RANGE_H
 #define USP_TILE_RANGE_H
@@ -275,5 +299,39 @@ USP_RANGE_FN int usp_doc_last_row_tile(int hi_last, int t_end, int tile) {
 USP_RANGE_FN int usp_doc_row_tile_live(int s0, int hi_last) { return s0 < hi_last; }
 
 USP_RANGE_FN int usp_doc_row_tile_masked(int s0, int tile, int hi_first) { return s0 + tile - 1 >= hi_first; }
+
+/* ---- the span bound: a right key bound per row (row_hi) and its transpose (key_lo), both monotone ---- */
+USP_RANGE_FN int usp_span_row_hi(const int* row_hi, int i, int Sq, int n_keys) {
+  return usp_doc_clamp(row_hi[i < Sq ? i : Sq - 1], n_keys);
+}
+
+USP_RANGE_FN int usp_span_key_lo(const int* key_lo, int j, int Sq, int n_keys) {
+  return usp_doc_clamp(key_lo[j < n_keys ? j : n_keys - 1], Sq);
+}
+
+/* hi_last = usp_span_row_hi of the last valid row of the item */
+USP_RANGE_FN int usp_span_key_tiles_end(int hi_last, int t_end, int tile) {
+  const int te = hi_last > 0 ? (hi_last + tile - 1) / tile : 0;
+  return te < t_end ? te : t_end;
+}
+
+/* hi_first = usp_span_row_hi of the first row of the item or wave */
+USP_RANGE_FN int usp_span_unmasked_key_tiles(int hi_first, int tile) { return hi_first > 0 ? hi_first / tile : 0; }
+
+USP_RANGE_FN int usp_span_key_tile_live(int kt0, int tile, int hi_last, int lo_first) {
+  return kt0 < hi_last && kt0 + tile > lo_first;
+}
+
+USP_RANGE_FN int usp_span_key_tile_masked(int kt0, int tile, int hi_first) { return kt0 + tile > hi_first; }
+
+/* lo_first = usp_span_key_lo of the block's first key */
+USP_RANGE_FN int usp_span_first_row_tile(int lo_first, int t_end, int tile) {
+  const int t0 = lo_first / tile;
+  return t0 < t_end ? t0 : t_end;
+}
+
+USP_RANGE_FN int usp_span_row_tile_live(int s0, int tile, int lo_first) { return s0 + tile > lo_first; }
+
+USP_RANGE_FN int usp_span_row_tile_masked(int s0, int lo_last) { return s0 < lo_last; }
 
 #endif

@@ -64,13 +64,15 @@ class _USPLayer(torch.nn.Module):
         return local_options(alibi_slopes, dropout_p, sinks, cu_doclens, heads, P, dist.get_rank(self.ulysses_pg) if P > 1 else 0,
                              P == 1 or (scatter_idx, self.gather_idx) == (2, 1), "heads scattered, sequence gathered")
 
-    def _docs(self, cu_doclens, batch: int, local_len: int):
+    def _docs(self, cu_doclens, batch: int, local_len: int, bidirectional=None):
         """`cu_doclens` checked against the WHOLE sequence (ring/doc_blocks.py: parse; a rank holds local_len of its
         ulysses_size x ring_size x local_len positions): the parsed lists, or None when it is off or names the single document
-        [0, S_total] -- which is exactly the call without it, the same exchange and the same launches."""
-        if cu_doclens is None:
+        [0, S_total] -- which is exactly the call without it, the same exchange and the same launches.  `bidirectional`: the spans
+        of the whole sequence (doc_blocks.parse_plan); where they are on, the plan that comes back carries them, and it travels on
+        as `cu_doclens`; where they are off (None, empty, length 1 only) the result is that of `cu_doclens` alone."""
+        if cu_doclens is None and bidirectional is None:
             return None
-        docs = doc_blocks.parse(cu_doclens, batch, self.ulysses_size * self.ring_size * local_len)
+        docs = doc_blocks.parse_plan(cu_doclens, bidirectional, batch, self.ulysses_size * self.ring_size * local_len)
         return None if docs is doc_blocks.SINGLE else docs
 
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
@@ -126,20 +128,24 @@ class LongContextAttention(_USPLayer):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None) -> Tensor:
+                deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None,
+                bidirectional=None) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
         layer, (head_cnt,) fp32 or the operands' type (comm/all_to_all.py: local_options: the gradient contract).  `cu_doclens` (keyword
         only): the cumulative document lengths of the WHOLE sequence, host data, the same on every rank (ring/doc_blocks.py):
         global row i sees global key j iff start(i) <= j <= i.  Needs causal=True; served with the basic ring at any ring
-        degree, with the zigzag and stripe rings at ring degree 1."""
+        degree, with the zigzag and stripe rings at ring degree 1.  `bidirectional` (keyword only): half-open spans [(s, e), ...]
+        of global positions of the WHOLE sequence, host data, the same on every rank, or "documents" (ring/doc_blocks.py:
+        parse_plan): inside a span every row sees the whole span; with or without cu_doclens, served where it is.  None, an empty
+        list or spans of length 1 only: exactly the call without it -- the same exchange and the same launches."""
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
                                causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens)
+                               cu_doclens=cu_doclens, bidirectional=bidirectional)
             return out[..., :D]
-        cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1])     # (the single document: None from here on)
+        cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1], bidirectional)     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
         if ng_cap is not None and (cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
                                    or dropout_value(dropout_p) is not None or sinks is not None):
@@ -182,15 +188,15 @@ class LongContextAttentionQKVPacked(_USPLayer):
 
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                *args: Any, sinks=None, cu_doclens=None) -> Tensor:
+                *args: Any, sinks=None, cu_doclens=None, bidirectional=None) -> Tensor:
         D = qkv.shape[-1]
         if kernel_head_dim(D) != D:
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                                window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens)
+                               cu_doclens=cu_doclens, bidirectional=bidirectional)
             return out[..., :D]
         exchange = self.ulysses_size > 1
-        cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1])
+        cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1], bidirectional)
         head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)

@@ -80,10 +80,10 @@ class HipBlockBackend:
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
             final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None,
-            sinks=None, doc=None):
+            sinks=None, doc=None, span=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
                      interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi,
-                     dropout=dropout, sinks=sinks, doc=doc)
+                     dropout=dropout, sinks=sinks, doc=doc, span=span)
 
     def sink_grad(self, sinks, lse, delta, out=None, accum=False):
         return _C.sink_grad(sinks, lse, delta, out=out, accum=accum)
@@ -93,10 +93,10 @@ class HipBlockBackend:
 
     def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq=False,
             accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None, softcap=None,
-            shift=None, alibi=None, dropout=None, doc=None):
+            shift=None, alibi=None, dropout=None, doc=None, span=None):
         _C.flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq,
                      accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only,
-                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout, doc=doc)
+                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout, doc=doc, span=span)
 
     def fwd_packed(self, q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out=None,
                    acc=None, merge_in=False, final_begin=0, final_end=2, softcap=None):
@@ -145,7 +145,9 @@ class _FeatureBackend:
                (usp_flash_fwd_sink).  (Hq,) over the heads of the block calls; sink_grad(lse, delta) binds them.
       doc      the bound of a launch depends on WHERE the launch lies, and only the schedule knows that: fwd and bwd take the
                per-launch arrays as `doc=(row_lo, key_hi)` from the schedule (ring/doc_blocks.py) and hand them on; a launch without
-               the keyword is refused, so that no block of such a call can run unmasked by oversight.
+               the keyword is refused, so that no block of such a call can run unmasked by oversight.  Under a plan with
+               bidirectional spans the schedule hands `span=(row_lo, row_hi, key_lo, key_hi)` instead -- the document bound and
+               the diagonal lie inside those arrays -- and launches with causal=False (DocCall.kw / DocCall.causal).
     The packed calls serve softcap alone and refuse the rest (Features.refuse_packed)."""
 
     def __init__(self, be, f: Features, seed: int = 0, head0: int = 0):
@@ -160,7 +162,7 @@ class _FeatureBackend:
         if f.dropout is not None:
             row0, key0 = kw.pop("at", (0, 0))
             kw["dropout"] = (f.dropout, self._seed, int(row0), int(key0), self._head0)
-        if f.doc is not None and kw.get("doc") is None:
+        if f.doc is not None and kw.get("doc") is None and kw.get("span") is None:
             raise RuntimeError("a launch under cu_doclens carries its doc=(row_lo, key_hi) arrays (ring/doc_blocks.py)")
         return kw
 
@@ -255,21 +257,22 @@ def _dropout_of(p, rng_state, what):
 
 
 def _block_call(f: Features, q, dr):
-    """(backend, per-call keywords) of the one launch of a single-block call with the features `f` and the dropout state `dr`."""
+    """(backend, per-call keywords) of the one launch of a single-block call with the features `f` and the dropout state `dr`.
+    Under a plan with spans the keywords hold `span`: the caller then launches with causal=False (the diagonal is in row_hi)."""
     be = get_block_backend(softcap=f.softcap, alibi=f.alibi, dropout=None if dr is None else (dr[0], dr[1], dr[4]),
                            sinks=f.sinks, doc=f.doc)
     kw = {"window": f.window}
     if dr is not None:
         kw["at"] = (dr[2], dr[3])
     if f.doc is not None:
-        kw["doc"] = _whole_doc(f.doc, q)
+        kw.update(_whole_doc(f.doc, q))
     return be, kw
 
 
 def _whole_doc(docs, q):
-    """The `doc=` keyword of the one launch of a single-block call."""
+    """The `doc=` (or, under spans, `span=`) keyword of the one launch of a single-block call."""
     from ..ring import doc_blocks
-    return doc_blocks.whole_call(docs, q.shape[1], q.device).doc(0)
+    return doc_blocks.whole_call(docs, q.shape[1], q.device).kw(0)
 
 
 def window_of(window_size):
@@ -278,7 +281,8 @@ def window_of(window_size):
 
 
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
-                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None):
+                     softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
+                     bidirectional=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -290,8 +294,12 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     together with softcap, alibi_slopes or dropout_p.
     `cu_doclens` (keyword only): the cumulative document lengths [0, e1, ..., Sq] of the sequence, host data (ring/doc_blocks.py):
     row i sees key j iff start(i) <= j <= i.  Needs causal=True and equally long q and k; not together with window_size, softcap,
-    alibi_slopes, dropout_p or sinks.  None or the single document [0, Sq]: exactly the call without it."""
-    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens)
+    alibi_slopes, dropout_p or sinks.  None or the single document [0, Sq]: exactly the call without it.
+    `bidirectional` (keyword only): half-open spans [(s, e), ...] of positions, host data, sorted and disjoint, each inside one
+    document, or "documents" (ring/doc_blocks.py: parse_plan): inside a span every row sees the whole span, so row i sees key j
+    iff start(i) <= j < hi(i).  With or without cu_doclens, under its preconditions and refusals.  None, an empty list or spans
+    of length 1 only: exactly the call without it."""
+    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional=bidirectional)
     dr = _dropout_of(f.dropout, rng_state, "hip_attn_forward")
     B, Sq, Hq, D = q.shape
     scale = _default_scale(q, softmax_scale)
@@ -303,21 +311,21 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
     be, kw = _block_call(f, q, dr)
-    be.fwd(q, k, v, scale, bool(causal), lse, out=out, **kw)
+    be.fwd(q, k, v, scale, bool(causal) and "span" not in kw, lse, out=out, **kw)
     return out, lse
 
 
 def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk_buffer,
                       block_dv_buffer, dropout_p=0.0, softmax_scale=None, bwd_causal=False,
                       window_size=(-1, -1), softcap=None, alibi_slopes=None, deterministic=False,
-                      rng_state=None, *args, sinks=None, dsinks=None, cu_doclens=None, **kwargs):
+                      rng_state=None, *args, sinks=None, dsinks=None, cu_doclens=None, bidirectional=None, **kwargs):
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
     (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one.
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
-    `cu_doclens` (keyword only): as hip_attn_forward took it."""
-    f = Features.of(q, k, bwd_causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens)
+    `cu_doclens`, `bidirectional` (keyword only): as hip_attn_forward took them."""
+    f = Features.of(q, k, bwd_causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional=bidirectional)
     if sinks is not None and dsinks is None:
         raise ValueError("hip_attn_backward with sinks needs the fp32 (Hq,) buffer dsinks")
     dr = _dropout_of(f.dropout, rng_state, "hip_attn_backward")
@@ -345,7 +353,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
         return t.dim() == 4 and t.stride(3) == 1 and all(st % 4 == 0 for st in t.stride()[:3])
     tgt = [t if direct(t) else torch.empty(t.shape, dtype=t.dtype, device=dev)
            for t in (block_dq_buffer, block_dk_buffer, block_dv_buffer)]
-    be.bwd(dout, q, k, v, lse, delta, None, None, None, _default_scale(q, softmax_scale), bool(bwd_causal),
+    be.bwd(dout, q, k, v, lse, delta, None, None, None, _default_scale(q, softmax_scale), bool(bwd_causal) and "span" not in kw,
            dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], **kw)
     for t, dst in zip(tgt, (block_dq_buffer, block_dk_buffer, block_dv_buffer)):
         if t is not dst:
@@ -393,7 +401,7 @@ class _HipAttnFunc(torch.autograd.Function):
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                  *args, dropout_head0=0, sinks=None, cu_doclens=None, **kwargs):
+                  *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -403,8 +411,10 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     only): the global index of q's head 0 in the mask's counter (a Ulysses rank passes the first head it holds).
     `sinks` (keyword only): one learned logit per query head, (Hq,) fp32 or q.dtype (hip_attn_forward); it may require grad, and
     its gradient comes back in its own dtype and shape.  Not together with softcap, alibi_slopes or dropout_p.
-    `cu_doclens` (keyword only): the document mask of a packed sequence (hip_attn_forward), padded head dims included."""
-    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens)
+    `cu_doclens` (keyword only): the document mask of a packed sequence (hip_attn_forward), padded head dims included.
+    `bidirectional` (keyword only): bidirectional spans beside or without it (hip_attn_forward), likewise; parsed here once, the
+    plan travels on as `cu_doclens`."""
+    f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional=bidirectional)
     cap, cu_doclens = f.softcap, f.doc
     D = q.shape[-1]
     if kernel_head_dim(D) != D:                 # on zero-padded copies (autograd differentiates the pad and the slice)

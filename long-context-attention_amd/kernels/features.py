@@ -1,5 +1,7 @@
 """The optional features of one attention call -- window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens -- as ONE
-record, and the ONE table of which of them the kernels serve together.  Pure argument logic: nothing here loads the library,
+record, and the ONE table of which of them the kernels serve together.  `bidirectional` (spans) is no seventh field: it goes
+together with cu_doclens and RIDES INSIDE the parsed document plan (ring/doc_blocks.py: Spans), so the record keeps its six
+fields and every positional construction its meaning; a `doc` that carries spans is named "bidirectional" in the refusals.  Pure argument logic: nothing here loads the library,
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
@@ -18,10 +20,27 @@ REFUSES = (("doc", ("window", "softcap", "alibi", "dropout", "sinks")),
 PACKED = ("softcap",)         # what the packed (variable-length) launches serve
 
 
+class _SpanMark:
+    """A `doc` value that stands for "a plan with spans is on" where only that matters (Features.check)."""
+    spans = ()
+
+
+SPAN_ON = _SpanMark()
+
+
+def _argument(f, idx: int) -> str:
+    """The argument the refusals name for field `idx` of the record `f`: a document plan with spans is `bidirectional`."""
+    field = f._fields[idx]
+    if field == "doc" and getattr(f[idx], "spans", None) is not None:
+        return "bidirectional"
+    return ARGUMENT[field]
+
+
 class Features(NamedTuple):
     """The decoded options of one call; None = off.  window: (left, right); softcap: the cap, a float > 0; alibi: the slopes as
     the block calls take them; dropout: the drop probability in (0, 1); sinks: the logits as given (they may require grad);
-    doc: the parsed document lists (ring/doc_blocks.py) -- or any marker where only "on" matters."""
+    doc: the parsed document lists (ring/doc_blocks.py), with the bidirectional spans inside where they are on (Spans) -- or any
+    marker where only "on" matters (SPAN_ON: on with spans)."""
     window: object = None
     softcap: object = None
     alibi: object = None
@@ -31,17 +50,29 @@ class Features(NamedTuple):
 
     @classmethod
     def of(cls, q, k, causal, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
-           ring_degree: int = 1):
+           ring_degree: int = 1, bidirectional=None):
         """The checked record of a call with flash-attn-style arguments on q (B, Sq, Hq, D) and k, each rank holding 1 /
         ring_degree of the sequence.  ValueError: a malformed value (_C.softcap_value, dropout_value, alibi_value, sinks_value,
         doc_blocks.parse); NotImplementedError: a refused combination -- judged first, on what is given --, a document mask that is
-        not causal self-attention.  A cu_doclens of one document is exactly the call without it: off -- after the checks."""
+        not causal self-attention.  A cu_doclens of one document is exactly the call without it: off -- after the checks.
+        `bidirectional`: the spans of the whole sequence (doc_blocks.parse_plan), read FIRST: one that is off (None, empty, spans
+        of length 1 only) is exactly the call without the keyword, whatever else is given; one that is on makes `doc` a plan with
+        spans, refused beside the other five as "bidirectional together with ..." and where the call is not causal self-attention."""
+        if bidirectional is not None:
+            from ..ring import doc_blocks
+            S_total = ring_degree * q.shape[1]
+            plan = doc_blocks.parse_plan(cu_doclens, bidirectional, q.shape[0], S_total)
+            if doc_blocks.spans_of(plan) is not None:
+                f = cls(_window(window_size), softcap_value(softcap), alibi_slopes, dropout_value(dropout_p), sinks, plan).check()
+                doc_blocks.refuse_not_causal_self(causal, S_total, ring_degree * k.shape[1], "bidirectional")
+                return f
         f = cls(_window(window_size), softcap_value(softcap), alibi_slopes, dropout_value(dropout_p), sinks, cu_doclens)
         f.check()                                  # (on what is on and off: a refused pair is refused before a tensor or list is read)
         if cu_doclens is not None:
             from ..ring import doc_blocks
             docs = doc_blocks.parse(cu_doclens, q.shape[0], ring_degree * q.shape[1])
-            doc_blocks.refuse_not_causal_self(causal, ring_degree * q.shape[1], ring_degree * k.shape[1])
+            doc_blocks.refuse_not_causal_self(causal, ring_degree * q.shape[1], ring_degree * k.shape[1],
+                                              "cu_doclens" if doc_blocks.spans_of(docs) is None else "bidirectional")
             return f._replace(doc=None if docs is doc_blocks.SINGLE else docs)
         if alibi_slopes is not None:
             f = f._replace(alibi=alibi_value(alibi_slopes, q.shape[0], q.shape[2], q.device)[0])
@@ -59,7 +90,7 @@ class Features(NamedTuple):
             if self[owner] is not None:
                 for other in refused:
                     if self[other] is not None:
-                        a, b = ARGUMENT[self._fields[owner]], ARGUMENT[self._fields[other]]
+                        a, b = _argument(self, owner), _argument(self, other)
                         raise NotImplementedError(f"{a} together with {b} is not supported by the HIP attention kernels")
                 break
         return self
@@ -68,6 +99,8 @@ class Features(NamedTuple):
         """Refuses what the packed (variable-length) launches do not serve."""
         for field, name in ARGUMENT.items():
             if field != "window" and field not in PACKED and getattr(self, field) is not None:
+                if field == "doc" and getattr(self.doc, "spans", None) is not None:
+                    name = "bidirectional"
                 raise NotImplementedError(f"{name} is not supported on packed (variable-length) batches")
 
 

@@ -44,16 +44,18 @@ class RingServes(NamedTuple):
     dropout: int = NOT_SERVED
     sinks: int = NOT_SERVED
     doc: int = NOT_SERVED
+    span: int = NOT_SERVED        # bidirectional spans: they ride inside the parsed `cu_doclens` plan (ring/doc_blocks.py: Spans)
 
 
 PACKED_RING = RingServes()
-DENSE_RING = RingServes(alibi=ONE_BLOCK, dropout=ONE_BLOCK, sinks=ANY_DEGREE, doc=ONE_BLOCK)       # zigzag, stripe
-BASIC_RING = RingServes(*(ANY_DEGREE,) * 5)
+DENSE_RING = RingServes(alibi=ONE_BLOCK, dropout=ONE_BLOCK, sinks=ANY_DEGREE, doc=ONE_BLOCK, span=ONE_BLOCK)       # zigzag, stripe
+BASIC_RING = RingServes(*(ANY_DEGREE,) * 6)
 
 # feature -> (its name in the refusals, what the packed rings advise, what a ONE_BLOCK ring advises beyond ring degree 1)
 _BASIC = "use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func)"
 _ADVICE = {
     "doc": ("cu_doclens", "use LongContextAttention (ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches", _BASIC),
+    "span": ("bidirectional", "use LongContextAttention (ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches", _BASIC),
     "sinks": ("sinks", "use a dense ring (ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)", None),
     "alibi": ("alibi_slopes", _BASIC + " on dense batches", _BASIC + ", which serves it over global positions with "
                                                                       "USP_RING_ALIBI=global"),
@@ -64,9 +66,43 @@ _ADVICE = {
 def _refuse_unserved(serves, doc=None, sinks=None, alibi=None, dropout=None):
     """NOT_SERVED is what the packed rings are: the first of the given ones that is on and not served is refused in their name."""
     for feature, value in (("doc", doc), ("sinks", sinks), ("alibi", alibi), ("dropout", dropout)):
+        if feature == "doc" and _has_spans(value):
+            feature = "span"
         if value is not None and not getattr(serves, feature):
             name, advice, _ = _ADVICE[feature]
             raise NotImplementedError(f"{name} is not supported by the variable-length (packed) rings: {advice}")
+
+
+def _has_spans(docs) -> bool:
+    return getattr(docs, "spans", None) is not None
+
+
+def span_plan(q, group, cu_doclens, bidirectional):
+    """`cu_doclens` for the rest of a ring call that was given `bidirectional`: the parsed plan with the spans inside
+    (ring/doc_blocks.py: parse_plan, over the WHOLE sequence: ring degree x the local length), or `cu_doclens` as given where the
+    spans are off -- None, an empty list, spans of length 1 only: exactly the call without the keyword."""
+    if bidirectional is None:
+        return cu_doclens
+    from . import doc_blocks
+    plan = doc_blocks.parse_plan(cu_doclens, bidirectional, q.shape[0], group_info(dist, group)[0] * q.shape[1])
+    return plan if _has_spans(plan) else cu_doclens
+
+
+def _span_given(bidirectional) -> bool:
+    """Is `bidirectional` anything but None or an empty list?  (What the packed rings, which hold no whole sequence to parse
+    it against, refuse.)"""
+    if bidirectional is None:
+        return False
+    try:
+        return isinstance(bidirectional, str) or len(bidirectional) > 0
+    except TypeError:
+        return True
+
+
+def _refuse_packed_spans(bidirectional):
+    if _span_given(bidirectional):
+        name, advice, _ = _ADVICE["span"]
+        raise NotImplementedError(f"{name} is not supported by the variable-length (packed) rings: {advice}")
 
 
 def _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, group):
@@ -91,8 +127,9 @@ def _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, 
     if f.doc is not None or f.alibi is not None or p is not None:
         P = group_info(dist, group)[0]
         for feature in ("doc", "alibi", "dropout"):
-            if P > 1 and getattr(f, feature) is not None and getattr(serves, feature) != ANY_DEGREE:
-                name, _, advice = _ADVICE[feature]
+            key = "span" if feature == "doc" and _has_spans(f.doc) else feature
+            if P > 1 and getattr(f, feature) is not None and getattr(serves, key) != ANY_DEGREE:
+                name, _, advice = _ADVICE[key]
                 raise NotImplementedError(f"{name} across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
                                           f"rings: {advice}")
         if P > 1 and p is not None and q.shape[1] % 4:
@@ -221,21 +258,24 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
-                 cu_doclens=None):
+                 cu_doclens=None, bidirectional=None):
+            _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group)
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None, *, sinks=None, cu_doclens=None):
+                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None):
+            _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
                               softcap, alibi_slopes, deterministic, return_attn_probs, group)
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None, *, sinks=None, cu_doclens=None):
+                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None):
+            _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
                               window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group)
@@ -250,7 +290,9 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None):
+                 attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
+                 bidirectional=None):
+            cu_doclens = span_plan(q, group, cu_doclens, bidirectional)       # (the spans travel inside the plan from here on)
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
                 res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
@@ -266,13 +308,15 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None):
+                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None):
+            cu_doclens = span_plan(q, group, cu_doclens, bidirectional)
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                               deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks, cu_doclens))
 
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None):
+                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None):
+            cu_doclens = span_plan(qkv[:, :, 0], group, cu_doclens, bidirectional)
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type),
                               *head0_arg(dropout_head0, sinks, cu_doclens))

@@ -24,6 +24,14 @@ A document mask (`cu_doclens`, ring/doc_blocks.py) is served at any ring degree,
 keys [kr S, (kr + 1) S)) -- the diagonal block causal, the blocks below it full with a left bound.  A block in which nothing is
 visible (start(r S) >= (kr + 1) S) is not launched: the rows' running state is untouched and its dK/dV block is zero.  The
 diagonal block always sees something and stays first, so it opens the rows' state; the transfers stay as they are.
+
+Bidirectional spans (`bidirectional`, riding inside the parsed `cu_doclens` plan: ring/doc_blocks.py) are served at any ring
+degree too: every launch takes the four arrays of (its rows, its keys) as `span=` and runs non-causal -- the diagonal lies in
+row_hi.  Where no span straddles a shard boundary the live blocks are the document ring's and its schedule is kept as it is.
+A span across a boundary makes a block ABOVE the diagonal live (kr > r; a span longer than a shard several): such a call takes
+the planned direct transport of the windowed ring -- one grouped send / recv of K/V with the peers of the plan
+(doc_blocks.SpanRingPlan: which (rank, step) blocks are live is host arithmetic any rank does for any other), every dK/dV block
+straight to its owner, added there in step order, so two identical calls give the same bits.
 """
 import os
 
@@ -153,14 +161,23 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     if cu_doclens is not None:       # the document mask: the steps with something visible, each with its own arrays
         assert k.shape[1] == S, "the basic ring holds equally long chunks of q and k"
         call = doc_blocks.ring_call(cu_doclens, S, P, r, dev)
+        if P > 1 and doc_blocks.spans_cross_shards(cu_doclens, S, P):   # a live block above the diagonal: the planned transport
+            plan = doc_blocks.SpanRingPlan(cu_doclens, S, P, r)
+            acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if len(plan.steps) > 1 else None
+            with KVRelay(process_group, k, v, recv_steps=plan.recv, send_steps=plan.send) as relay:
+                for i, step in enumerate(plan.steps):                  # (step 0, the diagonal block, is always the first)
+                    kk, vv = relay.get(step)
+                    be.fwd(q, kk, vv, softmax_scale, False, lse, out, acc, i > 0, 0, S if step == plan.steps[-1] else 0,
+                           **call.kw(step))
+            return out, lse
         steps = [s for s in range(r + 1) if call.visible(s)]          # (step 0, the diagonal block, is always among them)
         acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if len(steps) > 1 else None
         with KVRelay(process_group, k, v) as relay:
             for step in range(P):
                 kk, vv = relay.get(step)
                 if step in steps:
-                    be.fwd(q, kk, vv, softmax_scale, step == 0, lse, out, acc, step > 0, 0, S if step == steps[-1] else 0,
-                           doc=call.doc(step))
+                    be.fwd(q, kk, vv, softmax_scale, call.causal(step, step == 0), lse, out, acc, step > 0, 0,
+                           S if step == steps[-1] else 0, **call.kw(step))
         return out, lse
     win = _ring_window(window_size, P)
     if win is not None and P == 1:   # ring degree 1: one block, the kernels take flash-attn's window (left, right)
@@ -214,8 +231,9 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     call = None if cu_doclens is None else doc_blocks.ring_call(cu_doclens, S, P, r, dev)
     if P == 1:   # one block: the kernels round the gradients to q.dtype in their epilogues
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale, bool(causal),
-               dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)), **({} if call is None else {"doc": call.doc(0)}))
+        be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale,
+               bool(causal) if call is None else call.causal(0, causal),
+               dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)), **({} if call is None else call.kw(0)))
         return with_dsinks((dq, dk, dv))
     win = _ring_window(window_size, P)
     dq_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev)
@@ -233,10 +251,26 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
                                             relay_kw=dict(recv_steps=plan.recv, send_steps=plan.send))
         return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
+    if call is not None and doc_blocks.spans_cross_shards(cu_doclens, S, P):
+        # spans across a shard boundary: blocks above the diagonal are live -- every live block straight to its owner
+        plan = doc_blocks.SpanRingPlan(cu_doclens, S, P, r)
+
+        def span_block(step, kk, vv, dk_dst, dv_dst):
+            be.bwd(dout, q, kk, vv, softmax_lse, delta, dq_acc, dk_dst, dv_dst, softmax_scale, False,
+                   accum_dq=step > 0, **call.kw(step))                 # (step 0 is never empty: it is the first to write dq)
+
+        dk_acc, dv_acc = return_dkdv_direct(process_group, k, v, span_block, plan.key_extent, be,
+                                            relay_kw=dict(recv_steps=plan.recv, send_steps=plan.send))
+        return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
+
     def block(step, kk, vv, dk_dst, dv_dst):
         if call is not None:          # the document mask: a step in which nothing is visible computes nothing
             if step > r or not call.visible(step):
                 return False
+            if doc_blocks.spans_of(cu_doclens) is not None:           # (the diagonal lies in row_hi: never causal)
+                be.bwd(dout, q, kk, vv, softmax_lse, delta, dq_acc, dk_dst, dv_dst, softmax_scale, False,
+                       accum_dq=step > 0, **call.kw(step))
+                return True
             return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
                                    dq_acc, dk_dst, dv_dst, doc=call.doc(step))
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
@@ -249,7 +283,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     # under causal only steps <= rank compute (:93-122)
     dk_acc, dv_acc = travel_dkdv(process_group, k, v, block, fold, be=be, final_dtype=k.dtype, defer=defer,
                                  extent=lambda rank, step: None if (causal and step > rank) or
-                                 (cu_doclens is not None and not doc_blocks.ring_visible(cu_doclens, S, rank, step)) else FULL)
+                                 (cu_doclens is not None and not doc_blocks.ring_visible(cu_doclens, S, rank, step, P)) else FULL)
     return with_dsinks(final_grads(be, (q, k, v), (dq_acc, dk_acc, dv_acc)))
 
 

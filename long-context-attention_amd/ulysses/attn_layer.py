@@ -38,12 +38,17 @@ class UlyssesAttention(torch.nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None) -> Tensor:
+                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None) -> Tensor:
+        # `bidirectional`: spans of the whole sequence beside or without cu_doclens (kernels/attention.py: hip_attn_forward); an
+        # empty list is the call without it.
+        if bidirectional is not None and not isinstance(bidirectional, str) and len(bidirectional) == 0:
+            bidirectional = None
         # what depends on the heads this rank holds behind the exchange (comm/all_to_all.py: local_options; cu_doclens is checked
         # against the whole sequence q then holds: kernels/features.py)
         head_kw, alibi_slopes = local_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2],
                                               dist.get_world_size(self.spg), dist.get_rank(self.spg),
-                                              (self.scatter_idx, self.gather_idx) == (2, 1), "scatter_idx=2, gather_idx=1")
+                                              (self.scatter_idx, self.gather_idx) == (2, 1), "scatter_idx=2, gather_idx=1",
+                                              bidirectional=bidirectional)
         q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
