@@ -125,6 +125,9 @@ enum {
  * per-row right key bound beside the document's left one (bidirectional spans: prefix-LM blocks, packed bidirectional documents)
  * beside the unchanged argument blocks (ABI still v7). */
 #define USP_ATTN_SPAN 4096
+/* USP_ATTN_BLOCK_MASK: a FEATURE bit like USP_ATTN_DOC: the library exports usp_block_list_bytes / usp_flash_fwd_bsp /
+ * usp_flash_bwd_bsp (below), which take a 128 x 128 block mask beside the unchanged argument blocks. */
+#define USP_ATTN_BLOCK_MASK 8192
 
 typedef struct usp_tensor {
   void* ptr;
@@ -451,6 +454,50 @@ int usp_flash_fwd_span(const usp_fwd_args* args, const int32_t* row_lo, int64_t 
 int usp_flash_bwd_span(const usp_bwd_args* args, const int32_t* row_lo, int64_t row_lo_stride_b, const int32_t* row_hi,
                        int64_t row_hi_stride_b, const int32_t* key_lo, int64_t key_lo_stride_b, const int32_t* key_hi,
                        int64_t key_hi_stride_b, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
+ * Block-sparse mask: usp_flash_fwd / usp_flash_bwd with a set of visible 128 x 128 blocks per (batch, query head).  Selected-block
+ * attention (MoBA, NSA), block-sparse video attention: a row block sees a non-contiguous set of key blocks, often chosen on the
+ * device at every step.  For one launch (a whole sequence, or one block of a ring; Sq == Sk) that is
+ *     row i sees key j   iff   mask[b][h][i / 128][j / 128] != 0   and   the mask of the argument block (causal, ragged Sk) lets it,
+ * with `mask` a DEVICE array of bytes (0 = hidden), block (r, c) of head h of batch b at
+ *     mask[b * mask_stride_b + h * mask_stride_h + r * mask_stride_row + c],     r, c in [0, ceil(Sq / USP_BLOCK_MASK_SIZE)),
+ * strides in bytes, 0 allowed (one mask for every batch entry / every head).  h is the QUERY head.  Nothing on the call path reads
+ * the mask on the host: it may be written by a kernel earlier on the same stream.  With causal != 0 set bytes above the diagonal
+ * are ignored and the diagonal blocks are masked causally.  `lse` is the logsumexp over the visible keys; a row that sees nothing
+ * gives out = 0, lse = -inf and zero gradients, as ever.
+ * `lists` is DEVICE scratch of usp_block_list_bytes(B, Hq, nb, nb) bytes (nb = ceil(Sq / 128)), 4-byte aligned, owned by the call
+ * until its launches have finished: a builder launch (HBM-bound, one wave per list, no atomics) compacts the mask into int32 lists
+ * [count, ascending tile indices] at the kernels' 64-wide tile granularity -- per (b, h, row block) for the forward, per
+ * (b, h, pair of row blocks) with one "live" bit per half for dQ, and the transpose per (b, h, key block) for dK/dV; under causal
+ * without the blocks above the diagonal -- and the kernels stream the listed tiles only.  The forward builds and reads the first
+ * family, the backward the other two (of the launches USP_BWD_SKIP_* leaves).  Every count and entry is clamped as read: a
+ * corrupt workspace gives wrong results, never an out-of-range access.
+ *   - mask == NULL is exactly usp_flash_fwd / usp_flash_bwd: the same kernels, bit-identical results, strides and lists ignored.
+ *     An all-set mask runs the block-sparse kernels and gives the bits of the two-waves-per-SIMD family's launch of the same
+ *     workgroup shape (forward: the 4-wave, 128-row shape);
+ *   - a negative stride, and lists == NULL or not 4-byte aligned, are USP_EINVAL;
+ *   - USP_ATTN_SOFTCAP, USP_ATTN_WINDOW, USP_ATTN_SHIFT, a packed batch (seq_q / seq_k), USP_FORCE_ROW64 and Sq != Sk are
+ *     USP_EUNSUPPORTED, nothing launched or written (these checks follow the argument checks every call gets);
+ *   - k_splits, dq_splits and dkdv_splits are IGNORED with the mask, as under the document mask;
+ *   - every head dim runs on the two-waves-per-SIMD family (block-sparse instantiations of its kernels; the forward always in the
+ *     4-wave shape, whose work item is one mask row block: the listed tiles below a wave's diagonal keep the pipelined loop);
+ *     usp_last_launch_kinds() reports what was launched: fwd_wave4 for the forward, the wave8 / reduce bits for the backward.
+ * Everything else is as the argument block says (dkdv_heads -- each query head of a dK/dV item streams its own list --, merge_in,
+ * final_begin / final_end with acc, USP_LAUNCH_INTERLEAVE, USP_BWD_SKIP_*, GQA, dq16 / dk16 / dv16, both 16-bit types, head dims
+ * 32 / 64 / 128, any aligned layout).  The block mask together with ALiBi, dropout, sinks, documents or spans has no entry point.
+ * -------------------------------------------------------------------------------------------- */
+#define USP_BLOCK_MASK_SIZE 128
+int64_t usp_block_list_bytes(int32_t B, int32_t Hq, int32_t n_row_blocks, int32_t n_key_blocks);
+/* The builder launch alone, on `stream`: the lists of `which` (1: forward, 2: dQ, 4: dK/dV; any sum) of an S x S launch, exactly as
+ * the two entry points below build them into `lists` (tools and tests time it and read the lists back; a call of the entry
+ * points needs no call of this).  USP_EINVAL: a NULL or misaligned pointer, a non-positive size, a negative stride, which outside 1..7. */
+int usp_block_lists_build(const void* mask, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_row, int32_t B, int32_t Hq,
+                          int32_t S, int32_t causal, int32_t which, void* lists, void* stream);
+int usp_flash_fwd_bsp(const usp_fwd_args* args, const void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                      int64_t mask_stride_row, void* lists, void* stream);
+int usp_flash_bwd_bsp(const usp_bwd_args* args, const void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                      int64_t mask_stride_row, void* lists, void* stream);
 
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):

@@ -33,6 +33,8 @@ USP_ATTN_DROPOUT = 512         # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_SINK = 1024           # feature bit of usp_attn_features(): usp_flash_fwd_sink / usp_sink_bwd exist (not an args flag)
 USP_ATTN_DOC = 2048            # feature bit of usp_attn_features(): usp_flash_fwd_doc / usp_flash_bwd_doc exist (not an args flag)
 USP_ATTN_SPAN = 4096           # feature bit of usp_attn_features(): usp_flash_fwd_span / usp_flash_bwd_span exist (not an args flag)
+USP_ATTN_BLOCK_MASK = 8192     # feature bit of usp_attn_features(): usp_block_list_bytes / usp_flash_fwd_bsp / usp_flash_bwd_bsp exist (not an args flag)
+BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
@@ -114,7 +116,8 @@ class UspBwdArgs(ctypes.Structure):
 EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "usp_flash_bwd_workspace_bytes", "usp_bwd_delta", "usp_lse_merge", "usp_copy_rows",
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
-           "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span")
+           "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
+           "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -123,6 +126,7 @@ DROPOUT_EXPORTS = ("usp_flash_fwd_dropout", "usp_flash_bwd_dropout")
 SINK_EXPORTS = ("usp_flash_fwd_sink", "usp_sink_bwd")
 DOC_EXPORTS = ("usp_flash_fwd_doc", "usp_flash_bwd_doc")
 SPAN_EXPORTS = ("usp_flash_fwd_span", "usp_flash_bwd_span")
+BSP_EXPORTS = ("usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp")
 
 
 def lib_path() -> str:
@@ -141,7 +145,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -472,6 +476,70 @@ def span_value(span, B: int, Sq: int, Sk: int, device):
     return tuple(one(t, n, what) for t, n, what in zip(span, (Sq, Sq, Sk, Sk), ("row_lo", "row_hi", "key_lo", "key_hi")))
 
 
+def block_mask_value(mask, B: int, Hq: int, S: int, device):
+    """A `block_mask` / `bsp` argument -> (mask as a (B, Hq, nb, nb) uint8 view, byte strides of batch, head, row block) as
+    usp_flash_fwd_bsp / usp_flash_bwd_bsp take them, or None when it is off.  A torch.bool tensor on the operands' device of shape
+    (nb, nb), (Hq, nb, nb) or (B, Hq, nb, nb), nb = ceil(S / BLOCK_MASK_SIZE); missing dimensions become stride 0 (no copy).  Any
+    strides are taken as they are while the last dimension has stride 1; otherwise the value is made contiguous once.  Anything
+    else raises ValueError.  Nothing here reads the mask's values.  (Pure argument check: the CPU orchestration tests call it
+    without a library.)"""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+        raise ValueError(f"block_mask must be a torch.bool tensor, got {getattr(mask, 'dtype', type(mask).__name__)}")
+    nb = (S + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if tuple(mask.shape) not in ((nb, nb), (Hq, nb, nb), (B, Hq, nb, nb)):
+        raise ValueError(f"block_mask must have shape ({nb}, {nb}), ({Hq}, {nb}, {nb}) or ({B}, {Hq}, {nb}, {nb}) "
+                         f"({BLOCK_MASK_SIZE} x {BLOCK_MASK_SIZE} blocks of {S} rows), got {tuple(mask.shape)}")
+    if mask.device != torch.device(device):
+        raise ValueError(f"block_mask is on {mask.device}, the operands on {device}")
+    m = mask.detach()
+    if nb > 1 and m.stride(-1) != 1:
+        m = m.contiguous()
+    m = m.view(torch.uint8)
+    sr = m.stride(-2) if nb > 1 else nb
+    sh = m.stride(-3) if m.dim() >= 3 else 0
+    sb = m.stride(0) if m.dim() == 4 else 0
+    return m, sb, sh, sr
+
+
+def block_list_bytes(B: int, Hq: int, nb: int) -> int:
+    """usp_block_list_bytes: the scratch a block-sparse call of nb x nb blocks needs for its lists."""
+    return int(_feature_entry("usp_block_list_bytes")(B, Hq, nb, nb))
+
+
+def block_list_layout(B: int, Hq: int, nb: int) -> dict:
+    """Where the lists lie in that scratch, in int32 elements (csrc/usp_host.hpp: BlockLists): family -> (offset of the first
+    list, lists per (batch, head), ints per list); every list is [count, entries ...].  "fwd": per 128-row block, 64-key tiles;
+    "dq": per pair of row blocks, 4 * tile + the live halves' bits; "dkdv": per 128-key block, 64-row tiles."""
+    nqb, lf = (nb + 1) // 2, 2 * nb + 2
+    off_q = B * Hq * nb * lf
+    return dict(fwd=(0, nb, lf), dq=(off_q, nqb, lf), dkdv=(off_q + B * Hq * nqb * lf, nb, lf), ints=off_q + B * Hq * (nqb + nb) * lf)
+
+
+def block_lists_build(mask, B: int, Hq: int, S: int, causal: bool, lists, which: int = 7):
+    """usp_block_lists_build: the builder launch alone, into `lists` (a contiguous device tensor of block_list_bytes bytes);
+    which: 1 forward, 2 dQ, 4 dK/dV lists, any sum."""
+    m, sb, sh, sr = block_mask_value(mask, B, Hq, S, lists.device)
+    _check(_feature_entry("usp_block_lists_build")(_ptr(m), sb, sh, sr, B, Hq, S, 1 if causal else 0, int(which), _ptr(lists), _stream()),
+           "usp_block_lists_build")
+
+
+def _bsp_call(which: str, a, bsp, lists=None):
+    """Issues the flash launch `which` of `a` under the block mask `bsp` (block_mask_value).  `lists`: the scratch of the
+    lists (a uint8 / int32 device tensor of block_list_bytes; tests read it back); None: from the caching allocator
+    (stream-ordered, no host read)."""
+    m, sb, sh, sr = bsp
+    nb = (a.Sq + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    need = block_list_bytes(a.B, a.Hq, nb)
+    if lists is None:
+        lists = torch.empty(need, dtype=torch.uint8, device=m.device)
+    elif lists.numel() * lists.element_size() < need or not lists.is_contiguous() or lists.device != m.device:
+        raise ValueError(f"bsp_lists must be a contiguous device tensor of at least {need} bytes")
+    name = f"usp_flash_{which}_bsp"
+    _check(_feature_entry(name)(ctypes.byref(a), _ptr(m), sb, sh, sr, _ptr(lists), _stream()), name)
+
+
 def _feature_entries():
     """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
     does not insist on."""
@@ -486,7 +554,12 @@ def _feature_entries():
             "usp_flash_fwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [fwd, vp, i64, vp]),
             "usp_flash_bwd_doc": (USP_ATTN_DOC, "cu_doclens (USP_ATTN_DOC)", [bwd, vp, i64, vp, i64, vp]),
             "usp_flash_fwd_span": (USP_ATTN_SPAN, "bidirectional (USP_ATTN_SPAN)", [fwd, vp, i64, vp, i64, vp]),
-            "usp_flash_bwd_span": (USP_ATTN_SPAN, "bidirectional (USP_ATTN_SPAN)", [bwd, vp, i64, vp, i64, vp, i64, vp, i64, vp])}
+            "usp_flash_bwd_span": (USP_ATTN_SPAN, "bidirectional (USP_ATTN_SPAN)", [bwd, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
+            "usp_block_list_bytes": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [i32, i32, i32, i32]),
+            "usp_block_lists_build": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)",
+                                      [vp, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp]),
+            "usp_flash_fwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [fwd, vp, i64, i64, i64, vp, vp]),
+            "usp_flash_bwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [bwd, vp, i64, i64, i64, vp, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -502,11 +575,11 @@ def _feature_entry(name: str):
     fn = getattr(L, name)
     if fn.argtypes is None:
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
+        fn.restype = ctypes.c_int64 if name == "usp_block_list_bytes" else ctypes.c_int
     return fn
 
 
-_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _feature_entry      # (the names the per-feature tests call it by)
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):
@@ -613,7 +686,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None, dropout=None, sinks=None, doc=None, span=None):
+              alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -634,9 +707,20 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     mask of one launch (usp_flash_fwd_doc; served uncut; not with window, softcap, shift, alibi, dropout, sinks or family="row64").
     `span`: (row_lo, row_hi, key_lo, key_hi) int32 device arrays (span_value), None = off: row i sees key j only if
     row_lo[i] <= j < row_hi[i], the mask of one launch under bidirectional spans with the diagonal folded into row_hi
-    (usp_flash_fwd_span; causal=False only; served uncut; not with doc or anything doc refuses)."""
+    (usp_flash_fwd_span; causal=False only; served uncut; not with doc or anything doc refuses).
+    `bsp`: a torch.bool block mask (block_mask_value) of this launch's BLOCK_MASK_SIZE-square blocks, None = off: row i sees key j
+    only if bsp[b, h, i // 128, j // 128] (usp_flash_fwd_bsp; Sq == Sk; served uncut; not with any other option above but causal).  `bsp_lists`: the scratch of its lists
+    (block_list_bytes, block_list_layout; None: allocated here)."""
     _require_cuda(q, k, v, lse, out, acc)
     B, Sq, Hq, D = q.shape
+    bm = block_mask_value(bsp, B, Hq, Sq, q.device)
+    if bm is not None:
+        _bsp_alone(window=_window(window), softcap=softcap_value(softcap), shift=_shift(shift), alibi=alibi, dropout=dropout_args(dropout),
+                   sinks=sinks, doc=doc_value(doc, B, Sq, k.shape[1], q.device), span=span_value(span, B, Sq, k.shape[1], q.device))
+        a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
+                      bool(interleave), 0, None, _family_flag(family), None, None)
+        _bsp_call("fwd", a, bm, bsp_lists)
+        return
     cap = softcap_value(softcap)
     ff = _family_flag(family)
     win, sh = _window(window), _shift(shift)
@@ -662,6 +746,13 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
     _flash_call("fwd", a, al, dr, sk, dc, sp)
+
+
+def _bsp_alone(**others):
+    """A block-sparse launch takes no other option: the entry point has no second extra and declines the flag bits."""
+    for name, value in others.items():
+        if value is not None:
+            raise NotImplementedError(f"bsp together with {name} is not supported by the HIP attention kernels")
 
 
 def _t3(t: Optional[torch.Tensor]) -> UspTensor:
@@ -800,7 +891,7 @@ def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None):
+              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None, bsp_lists=None):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
@@ -811,7 +902,7 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     (usp_flash_bwd_alibi).  `dropout`: as flash_fwd (usp_flash_bwd_dropout): the same tuple regenerates the forward's mask;
     `delta` is that of the dropped `out`.  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
     key_hi; with `only` the other one may be None.  `span`: as flash_fwd (usp_flash_bwd_span): the dQ launch reads (row_lo,
-    row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None."""
+    row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None.  `bsp`: as flash_fwd (usp_flash_bwd_bsp)."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -835,8 +926,11 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     sh = _shift(shift)
     dc = doc_value(doc, B, Sq, Sk, q.device)             # None: off -- (None, None) included
     sp = span_value(span, B, Sq, Sk, q.device)
+    bm = block_mask_value(bsp, B, Hq, Sq, q.device)
+    if bm is not None:
+        _bsp_alone(window=_window(window), softcap=cap, shift=sh, alibi=alibi, dropout=dropout_args(dropout), doc=dc, span=sp)
     if splits is None:
-        a.dq_splits, a.dkdv_splits = (0, 0) if (sh is not None or dc is not None or sp is not None) else bwd_splits(B, Sq, Sk, Hq, bool(causal))
+        a.dq_splits, a.dkdv_splits = (0, 0) if (sh is not None or dc is not None or sp is not None or bm is not None) else bwd_splits(B, Sq, Sk, Hq, bool(causal))
     else:
         a.dq_splits, a.dkdv_splits = splits
     a.dkdv_heads = int(dkdv_heads)
@@ -852,6 +946,9 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     if need > 0:
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)   # caching allocator; stream-ordered
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    if bm is not None:
+        _bsp_call("bwd", a, bm, bsp_lists)
+        return
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
     _flash_call("bwd", a, al, dr, None, dc, sp)

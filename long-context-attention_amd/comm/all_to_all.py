@@ -140,8 +140,24 @@ def local_sinks(sinks, H: int, P: int, rank: int):
                      f"got {tuple(sinks.shape)}")
 
 
+def local_block_mask(block_mask, H: int, P: int, rank: int):
+    """The block mask of the heads ulysses rank `rank` holds behind the head-scatter exchange of an H-head layer.  One with a
+    head dimension over the layer's H heads, (H, nb, nb) or (B, H, nb, nb), is cut to them (local_heads: a view, no copy); one
+    over the local H / P heads, or without a head dimension, is taken as it is; any other head count raises ValueError.  None
+    stays None.  Never read on the host."""
+    if block_mask is None or P == 1 or block_mask.dim() < 3:
+        return block_mask
+    n = block_mask.shape[-3]
+    if n == H:
+        return block_mask[..., local_heads(H, P, rank), :, :]
+    if H % P == 0 and n == H // P:
+        return block_mask
+    raise ValueError(f"block_mask must cover the layer's {H} heads or the {H // max(P, 1)} heads of one ulysses rank, "
+                     f"got {tuple(block_mask.shape)}")
+
+
 def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, rank: int, head_scatter: bool, how: str,
-                  bidirectional=None):
+                  bidirectional=None, block_mask=None):
     """What a layer of H heads hands its attention function for the options that depend on WHICH heads ulysses rank `rank` of P
     holds behind the exchange: (keyword dict, local slopes).
       alibi_slopes  cut to the rank's heads (local_alibi_slopes);
@@ -161,7 +177,7 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
     if not head_scatter:
         doc_name = "cu_doclens" if getattr(cu_doclens, "spans", None) is None else "bidirectional"
         for name, value in (("alibi_slopes", alibi_slopes), ("dropout_p != 0", p), ("sinks", sinks), (doc_name, cu_doclens),
-                            ("bidirectional", bidirectional)):
+                            ("bidirectional", bidirectional), ("block_mask", block_mask)):
             if value is not None:
                 raise NotImplementedError(f"{name} needs the head-scatter exchange ({how})")
     kw = {}
@@ -173,6 +189,8 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
         kw["cu_doclens"] = cu_doclens
     if bidirectional is not None:
         kw["bidirectional"] = bidirectional
+    if block_mask is not None:                     # cut to the rank's heads (local_block_mask)
+        kw["block_mask"] = local_block_mask(block_mask, H, P, rank)
     return kw, local_alibi_slopes(alibi_slopes, H, P, rank)
 
 

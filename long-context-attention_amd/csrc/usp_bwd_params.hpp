@@ -88,7 +88,22 @@ struct BwdArgsSPAN : BwdParams, BwdDoc, BwdSpan {};
   [[maybe_unused]] constexpr bool SPAN = false;                  \
   [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
   [[maybe_unused]] constexpr const int* span_key_lo = nullptr;   \
-  [[maybe_unused]] constexpr int64_t span_rh_sb = 0, span_kl_sb = 0;
+  [[maybe_unused]] constexpr int64_t span_rh_sb = 0, span_kl_sb = 0; \
+  USP_BWD_NO_BSP
+// Block-sparse mask (usp_flash_bwd_bsp): kernel arguments of the block-sparse instantiations only (usp_flash_bwd_bsp.hip:
+// flash_bwd_bsp_kernel, flash_bwd_dkdv_bsp_kernel); every other kernel keeps its argument block and machine code.  The dQ launch
+// gets the lists of its 256-row blocks (two mask row blocks each: entry = 4 * key tile + the live halves' bits), the dK/dV launch
+// the transposed lists of its 128-key blocks (entry = 64-row tile), one per QUERY head (usp_host.hpp: BlockLists).
+struct BwdBsp {
+  const int* bsp_lists;                 // int32: the list of (b, query head h, block i) starts at ((b * Hq + h) * nblk + i) * bsp_stride
+  int bsp_stride;                       // ints per list: [0] = count, [1 ..] = ascending entries
+};
+struct BwdArgsBSP : BwdParams, BwdBsp {};
+// What a kernel without the block-sparse switch defines for the shared bodies
+#define USP_BWD_NO_BSP                                           \
+  [[maybe_unused]] constexpr bool BSP = false;                   \
+  [[maybe_unused]] constexpr const int* bsp_lists = nullptr;     \
+  [[maybe_unused]] constexpr int bsp_stride = 0;
 
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the
@@ -144,5 +159,8 @@ int launch_dq_doc(const BwdArgsDOC& p, int D, int dtype, bool causal, int grid, 
 // The span backward launches (usp_flash_bwd_span.hip), likewise; never causal: the diagonal is folded into the arrays.
 int launch_dkdv_span(const BwdArgsSPAN& p, int D, int dtype, int grid, size_t lds, hipStream_t st);
 int launch_dq_span(const BwdArgsSPAN& p, int D, int dtype, int grid, size_t lds, hipStream_t st);
+// The block-sparse backward launches (usp_flash_bwd_bsp.hip), likewise.
+int launch_dkdv_bsp(const BwdArgsBSP& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+int launch_dq_bsp(const BwdArgsBSP& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

@@ -175,8 +175,9 @@ struct BwdExtras {
   DropoutCall dc{};
   BwdDoc doc{};
   BwdSpan span{};
+  BspCall bsp{};                 // (usp_flash_bwd_bsp: the block mask and the workspace of its lists)
   Dropout dr{};
-  bool any() const { return al.al_slopes || dr.t || doc.row_lo || doc.key_hi || span.row_hi || span.key_lo; }
+  bool any() const { return al.al_slopes || dr.t || doc.row_lo || doc.key_hi || span.row_hi || span.key_lo || bsp.mask; }
 };
 
 // dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
@@ -208,6 +209,12 @@ static int launch_dkdv(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_
       static_cast<BwdParams&>(pd) = pb;
       static_cast<Dropout&>(pd) = x.dr;
       if (int rc2 = launch_dkdv_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
+    } else if (x.bsp.mask) {                       // block-sparse mask: likewise (usp_flash_bwd_bsp.hip); the lists are built by now
+      const BlockLists& bl = x.bsp.layout;
+      BwdArgsBSP pd;
+      static_cast<BwdParams&>(pd) = pb;
+      pd.bsp_lists = x.bsp.lists + bl.off_t; pd.bsp_stride = bl.lt;
+      if (int rc2 = launch_dkdv_bsp(pd, D, DT, causal, grid, lds_q, st)) return rc2;
     } else if (x.span.key_lo) {                    // span bound: likewise (usp_flash_bwd_span.hip), never causal
       BwdArgsSPAN pd;
       static_cast<BwdParams&>(pd) = pb;
@@ -261,6 +268,12 @@ static int launch_dq(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_t 
     static_cast<BwdParams&>(pd) = pb;
     static_cast<Dropout&>(pd) = x.dr;
     if (int rc2 = launch_dq_dropout(pd, D, DT, causal, grid, lds_q, st)) return rc2;
+  } else if (x.bsp.mask) {                         // block-sparse mask: likewise (usp_flash_bwd_bsp.hip); the lists are built by now
+    const BlockLists& bl = x.bsp.layout;
+    BwdArgsBSP pd;
+    static_cast<BwdParams&>(pd) = pb;
+    pd.bsp_lists = x.bsp.lists + bl.off_q; pd.bsp_stride = bl.lf;
+    if (int rc2 = launch_dq_bsp(pd, D, DT, causal, grid, lds_q, st)) return rc2;
   } else if (x.span.row_hi) {                      // span bound: likewise (usp_flash_bwd_span.hip), never causal
     BwdArgsSPAN pd;
     static_cast<BwdParams&>(pd) = pb;
@@ -301,6 +314,10 @@ static int launch_bwd(BwdArgsSC p, const BwdExtras& x, bool causal, hipStream_t 
   // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
   const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !x.any();   // (... and no ALiBi, dropout or document step)
   int rc = USP_OK;
+  if (x.bsp.mask) {                               // the lists of the launches that run, once, in front of them on the same stream
+    rc = launch_block_lists(x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists, x.bsp.layout, p.Sq, p.Sk, causal, (want_dq ? 2 : 0) | (want_dkdv ? 4 : 0), st);
+    if (rc != USP_OK) return rc;
+  }
   if (want_dkdv && (rc = launch_dkdv<D, DT>(p, x, causal, st, row64)) != USP_OK) return rc;
   if (want_dq && (rc = launch_dq<D, DT>(p, x, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
   return rc;
@@ -395,6 +412,9 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (has_span && ((!(skip & USP_BWD_SKIP_DQ) && !(doc.row_lo && span.row_hi)) || (!(skip & USP_BWD_SKIP_DKDV) && !(doc.key_hi && span.key_lo))))
     return USP_EINVAL;
   if (int rc = check_span(*a, has_span, doc.row_lo_sb, doc.key_hi_sb, span.row_hi_sb, span.key_lo_sb)) return rc;
+  if (int rc = check_bsp(*a, x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists)) return rc;
+  const bool has_bsp = x.bsp.mask != nullptr;
+  if (has_bsp) x.bsp.layout = block_lists(a->B, a->Hq, (a->Sq + 127) / 128, (a->Sk + 127) / 128);   // once per call
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
@@ -413,7 +433,7 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (packed && (mask.windowed || mask.shifted)) return USP_EUNSUPPORTED;        // dense launches only
   if (a->dq_splits < 0 || a->dq_splits > 8 || a->dkdv_splits < 0 || a->dkdv_splits > 8) return USP_EINVAL;
   usp_bwd_args uncut;                              // a document launch is served uncut (usp_hip.h): the plan of the same call without cuts
-  if (has_doc || has_span) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
+  if (has_doc || has_span || has_bsp) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
   const BwdPlan plan = plan_bwd(a);
   if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
   BwdArgsSC p;
@@ -505,5 +525,12 @@ extern "C" int usp_flash_bwd_span(const usp_bwd_args* a, const int32_t* row_lo, 
   usp::BwdExtras x;
   x.doc = usp::BwdDoc{row_lo, key_hi, any ? row_lo_stride_b : 0, any ? key_hi_stride_b : 0};
   x.span = usp::BwdSpan{row_hi, key_lo, any_span ? row_hi_stride_b : 0, any_span ? key_lo_stride_b : 0};
+  return flash_bwd_call(a, x, stream);
+}
+
+extern "C" int usp_flash_bwd_bsp(const usp_bwd_args* a, const void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                                 int64_t mask_stride_row, void* lists, void* stream) {
+  usp::BwdExtras x;                                                   // mask == NULL: exactly usp_flash_bwd
+  if (mask) x.bsp = usp::BspCall{mask, mask_stride_b, mask_stride_h, mask_stride_row, (int*)lists};
   return flash_bwd_call(a, x, stream);
 }

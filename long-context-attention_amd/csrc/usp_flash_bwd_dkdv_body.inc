@@ -6,7 +6,8 @@
 // ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
 // (usp_dropout_rng.h: Dropout) and doc_key_hi / doc_kh_sb (int32 key bounds and their batch stride).
 // The span kernels (usp_flash_bwd_span.hip) add the `if constexpr (SPAN)` steps on top of DOC's (span_key_lo / span_kl_sb;
-// USP_BWD_NO_SPAN elsewhere).
+// USP_BWD_NO_SPAN elsewhere).  The block-sparse kernels (usp_flash_bwd_bsp.hip) add the `if constexpr (BSP)` steps (bsp_lists /
+// bsp_stride; USP_BWD_NO_BSP elsewhere): the streamed row tiles of each query head are a list, not a range.
 // Dropout: role A forms the un-dropped P, uses P o keep for its dV MFMAs and hands B the un-dropped P with the keep decision in
 // the sign bit (P >= 0: set = dropped; no extra LDS); role B starts its dP chain from -delta t/256 and forms
 // |P| (kept ? chain : -delta t/256); 256/t goes into the epilogue's factor of both outputs.
@@ -107,7 +108,22 @@
     span_lo_w0 = usp_span_key_lo(kl, ow, p.Sq, p.Sk);
     span_lo_w1 = usp_span_key_lo(kl, ow + 31, p.Sq, p.Sk);
   }
-  const int n_iter = (t_end - t_begin) * p.gsub;
+  // BSP (usp_flash_bwd_bsp.hip): the 128-key block is ONE column of the 128 x 128 block mask; for each of its gsub query heads it
+  // streams the ascending list of 64-row tiles of that head's transposed list (usp_block_lists.hip) -- under CAUSAL without the
+  // blocks above the diagonal.  Only the staging cursor reads the lists (count and entries clamped as read); the two roles take the
+  // tile of their iteration from what was staged one and two iterations ago.
+  [[maybe_unused]] const int* bsp_l = nullptr;
+  [[maybe_unused]] int bsp_cnt = 0, bsp_i = 0, bsp_total = 0, bsp_tn = 0, bsp_ta = 0, bsp_tb = 0;
+  [[maybe_unused]] auto bsp_list_of = [&](int hh) { return bsp_lists + ((int64_t)(b * p.Hq + h0 + hh) * p.nblk + blk) * bsp_stride; };
+  [[maybe_unused]] auto bsp_count_of = [&](const int* l) {
+    const int c0 = l[0], cap = bsp_stride - 2;
+    return (c0 < 0 || t_end <= 0) ? 0 : (c0 > cap ? cap : c0);
+  };
+  if constexpr (BSP) {
+    t_begin = 0;
+    for (int hh = 0; hh < p.gsub; ++hh) bsp_total += bsp_count_of(bsp_list_of(hh));
+  }
+  const int n_iter = BSP ? bsp_total : (t_end - t_begin) * p.gsub;
 
   // ---- LDS-DMA staging of the Q / dO tiles -----------------------------------------------------------------
   // ONE buffer descriptor pair per (item, query head), based on row 0 of that head; a tile is addressed by a scalar byte
@@ -147,8 +163,26 @@
     do_soff = t_begin * do_step;
   };
   pf_head();
+  // BSP: base the cursor on the first head from pf_hh on whose list is not empty (stage_next is called n_iter times: there is one)
+  [[maybe_unused]] auto bsp_head = [&]() {
+    for (; pf_hh < p.gsub; ++pf_hh) {
+      bsp_l = bsp_list_of(pf_hh);
+      bsp_cnt = bsp_count_of(bsp_l);
+      if (bsp_cnt > 0) break;
+    }
+    bsp_i = 0;
+    if (pf_hh < p.gsub) pf_head();
+  };
+  if constexpr (BSP) bsp_head();
   // issue the cursor's tile into LDS buffer `buf`, fetch its row statistics, advance the cursor
   auto stage_next = [&](int buf) {
+    if constexpr (BSP) {                         // the cursor jumps to the next listed tile of its head
+      const int e = bsp_l[1 + bsp_i];
+      pf_tile = e < 0 ? 0 : (e >= t_end ? t_end - 1 : e);
+      bsp_tn = pf_tile;
+      q_soff = pf_tile * q_step;
+      do_soff = pf_tile * do_step;
+    }
     if (stat_wave) {                             // raw loads only: the values are consumed by stage_stats, a tile later
       const int r = pf_tile * kTile + lane;
       st_in = r < p.Sq;                          // rows past the end: P = 0 (their Q / dO rows read as zero)
@@ -165,10 +199,14 @@
         lds_dma16(do_rs, dst + TILEB, do_voff[i], do_soff);
       }
     }
+    if constexpr (BSP) {
+      if (++bsp_i == bsp_cnt) { ++pf_hh; bsp_head(); }
+    } else {
     ++pf_tile;
     q_soff += q_step;
     do_soff += do_step;
     if (p.gsub > 1 && pf_tile == t_end) { ++pf_hh; pf_head(); }
+    }
   };
   auto stage_stats = [&](int buf) {
     if (stat_wave) {
@@ -227,10 +265,11 @@
     for (int it = 0; it <= n_iter; ++it) {
       const bool prefetch = it + 1 < n_iter;
       const int buf_n = buf_a + 1 == NBUF ? 0 : buf_a + 1;      // (it + 1) % NBUF
+      if constexpr (BSP) { bsp_tb = bsp_ta; bsp_ta = bsp_tn; }  // (in front of the stage_next that replaces bsp_tn)
       if (prefetch) stage_next(buf_n);
 
       const int my_it = it - ROLE;
-      const int tile = ROLE == 0 ? tile_a : tile_b;
+      const int tile = BSP ? (ROLE == 0 ? bsp_ta : bsp_tb) : (ROLE == 0 ? tile_a : tile_b);
       tile_b = tile_a;
       tile_a = (tile_a + 1 == t_end) ? t_begin : tile_a + 1;
       const int s0 = tile * kTile;

@@ -6,7 +6,8 @@
 // ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
 // (usp_dropout_rng.h: Dropout) and doc_row_lo / doc_rl_sb (int32 row bounds and their batch stride).
 // The span kernels (usp_flash_bwd_span.hip) add the `if constexpr (SPAN)` steps on top of DOC's (span_row_hi / span_rh_sb;
-// USP_BWD_NO_SPAN elsewhere).
+// USP_BWD_NO_SPAN elsewhere).  The block-sparse kernels (usp_flash_bwd_bsp.hip) add the `if constexpr (BSP)` steps (bsp_lists /
+// bsp_stride; USP_BWD_NO_BSP elsewhere): the streamed key tiles are a list, not a range.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
@@ -101,7 +102,22 @@
     span_hi_w0 = usp_span_row_hi(rh, ow, p.Sq, p.Sk);
     span_hi_w1 = usp_span_row_hi(rh, ow + 31, p.Sq, p.Sk);
   }
-  const int n_iter = t_end - t_begin;
+  // BSP (usp_flash_bwd_bsp.hip): the 256-row block holds TWO row blocks of the 128 x 128 block mask; it streams the ascending union
+  // of their lists (usp_block_lists.hip), entry = 4 * key tile + (bit 0: live for rows [0, 128), bit 1: for [128, 256)) -- under
+  // CAUSAL without the blocks above the diagonal.  A wave skips the compute of an entry dead for its half, and still stages and
+  // meets the barrier.  Count and entries are clamped as read; the entry of an iteration was read when its tile was staged.
+  // The entries come 64 at a time, one per lane (one vector load every 64 tiles), and the cursor picks its own with
+  // v_readlane: no memory latency in front of a stage's descriptors.  (It measured like a scalar load per tile: the 1.8 x of
+  // this kernel on an all-set mask against the plain one lies elsewhere -- profiles/block_mask_rates.txt.)
+  [[maybe_unused]] const int* bsp_l = nullptr;
+  [[maybe_unused]] int bsp_cnt = 0, bsp_i = 0, bsp_ent = 0, bsp_vec = 0;
+  if constexpr (BSP) {
+    bsp_l = bsp_lists + ((int64_t)(b * p.Hq + h0) * p.nblk + blk) * bsp_stride;
+    const int c0 = bsp_l[0], cap = bsp_stride - 2;
+    bsp_cnt = (c0 < 0 || t_end <= 0) ? 0 : (c0 > cap ? cap : c0);
+    t_begin = 0;
+  }
+  const int n_iter = BSP ? bsp_cnt : t_end - t_begin;
 
   // ---- staging: LDS-DMA (buffer_load ... lds), no staging registers, no ds_write ---------------------
   // One wave-instruction fills 1 KiB of LDS linearly (wave-uniform base + lane*16), i.e. 1024/ROWB
@@ -134,6 +150,17 @@
   // build the descriptors for the cursor's tile, then advance the cursor
   auto stage_setup = [&](int buf) {
     auto clampu = [](int64_t r) { return (int)(uint32_t)(r < 0 ? 0 : (r > 0xffffffffLL ? 0xffffffffLL : r)); };
+    if constexpr (BSP) {                       // the cursor jumps to the next listed tile
+      if ((bsp_i & 63) == 0) bsp_vec = bsp_i + lane < bsp_cnt ? bsp_l[1 + bsp_i + lane] : 0;
+      const int e = __builtin_amdgcn_readlane(bsp_vec, bsp_i & 63);
+      ++bsp_i;
+      const int t = e < 0 ? 0 : ((e >> 2) >= t_end ? t_end - 1 : (e >> 2));
+      bsp_ent = 4 * t + (e & 3);
+      k_next = p.k + 2 * (b * p.k_sb + hkv * p.k_sh) + t * k_step;
+      v_next = p.v + 2 * (b * p.v_sb + hkv * p.v_sh) + t * v_step;
+      k_rem = ((int64_t)(p.Sk - 1 - t * kTile) * p.k_ss + D) * 2;
+      v_rem = ((int64_t)(p.Sk - 1 - t * kTile) * p.v_ss + D) * 2;
+    }
     k_rs = __builtin_amdgcn_make_buffer_rsrc((void*)k_next, 0, clampu(k_rem), 0x00020000);
     v_rs = __builtin_amdgcn_make_buffer_rsrc((void*)v_next, 0, clampu(v_rem), 0x00020000);
     dma_buf = buf;
@@ -196,7 +223,8 @@
   int cur_tile = t_begin;                              // streamed tile of the current iteration
   for (int it = 0; it < n_iter; ++it) {
     const int buf = it & 1;
-    const int tile = cur_tile;
+    const int tile = BSP ? (bsp_ent >> 2) : cur_tile;    // (BSP: read here, in front of the stage_setup that replaces it)
+    [[maybe_unused]] const int bsp_halves = bsp_ent & 3;
     cur_tile = (cur_tile + 1 == t_end) ? t_begin : cur_tile + 1;
     const int s0 = tile * kTile;                       // first key of this tile
     const bool prefetch = it + 1 < n_iter;
@@ -216,6 +244,7 @@
       active = active && s0 < span_hi_w1;                        // (usp_span_key_tile_live's right-bound term)
       need_mask = need_mask || usp_span_key_tile_masked(s0, kTile, span_hi_w0);
     }
+    if constexpr (BSP) active = active && ((bsp_halves >> (wave >> 2)) & 1) != 0;     // waves 0-3: the first mask row block
 
     if (active) {
       // Hand-pinned pipeline over the two 32-row halves h0, h1 of the tile (sched_barrier(0) fences;

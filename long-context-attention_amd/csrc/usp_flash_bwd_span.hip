@@ -23,7 +23,8 @@ namespace usp {
   [[maybe_unused]] const int64_t doc_rl_sb = p_in.row_lo_sb, doc_kh_sb = p_in.key_hi_sb;   \
   [[maybe_unused]] const int* const span_row_hi = p_in.row_hi;  \
   [[maybe_unused]] const int* const span_key_lo = p_in.key_lo;  \
-  [[maybe_unused]] const int64_t span_rh_sb = p_in.row_hi_sb, span_kl_sb = p_in.key_lo_sb;
+  [[maybe_unused]] const int64_t span_rh_sb = p_in.row_hi_sb, span_kl_sb = p_in.key_lo_sb; \
+  USP_BWD_NO_BSP
 
 template <int D, int DT>
 __global__ __launch_bounds__(512, 2) void flash_bwd_span_kernel(const BwdArgsSPAN p_in) {

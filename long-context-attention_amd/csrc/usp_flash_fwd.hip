@@ -151,8 +151,9 @@ struct FwdExtras {
   const float* sinks = nullptr;
   FwdDoc doc{};
   FwdSpan span{};                // (usp_flash_fwd_span: with row_hi, a NULL doc.row_lo is all zero)
+  BspCall bsp{};                 // (usp_flash_fwd_bsp: the block mask and the workspace of its lists)
   Dropout dr{};
-  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo || span.row_hi; }
+  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo || span.row_hi || bsp.mask; }
 };
 
 template <int D, int DT, int NWAVES>
@@ -180,6 +181,17 @@ static int launch_fwd_w(FwdArgsSC p, const FwdExtras& x, bool causal, hipStream_
     static_cast<FwdArgsT<true>&>(pk) = ps;
     pk.sinks = x.sinks;
     if (int rc = launch_fwd_sink(pk, D, DT, causal, NWAVES, grid, lds, st)) return rc;
+  } else if (x.bsp.mask) {                                   // block-sparse mask: likewise (usp_flash_fwd_bsp.hip), 4 waves only
+    if constexpr (NWAVES == 4) {                             // (launch_fwd picks 4 waves under the mask: p.nq counts mask row blocks)
+      const BlockLists& bl = x.bsp.layout;
+      if (int rc = launch_block_lists(x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists, bl, p.Sq, p.Sk, causal, 1, st)) return rc;
+      FwdArgsBSP pd;
+      static_cast<FwdParams&>(pd) = p;
+      pd.bsp_lists = x.bsp.lists; pd.bsp_stride = bl.lf;
+      if (int rc = launch_fwd_bsp(pd, D, DT, causal, grid, lds, st)) return rc;
+    } else {
+      return USP_ELAUNCH;                                    // unreachable: no 8-wave block-sparse instantiation exists
+    }
   } else if (x.span.row_hi) {                                // span bound: likewise (usp_flash_fwd_span.hip), never causal
     FwdArgsSPAN pd;
     static_cast<FwdParams&>(pd) = p;
@@ -241,6 +253,7 @@ static int launch_fwd(const FwdArgsSC& p, const FwdExtras& x, bool causal, hipSt
     // profiles/r05_fwd64_ksplit.txt)
     const bool long_cuts = p.ksplit <= 1 || (int64_t)p.Sk >= (int64_t)96 * kBN * p.ksplit;
     if (waves == 8 && fwd64_ok && long_cuts && !(force & USP_FORCE_WAVE32)) waves = 64;
+    if (x.bsp.mask) waves = 4;                               // a block-sparse item is one 128-row mask block
   }
   if (waves == 64) {
     int rc = USP_ELAUNCH;
@@ -278,6 +291,8 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   // (with row_hi the span's check judges every stride before any decline; it declines all the document's check does)
   if (int rc = check_doc(*a, x.doc.row_lo != nullptr && !x.span.row_hi, x.doc.row_lo_sb, 0)) return rc;
   if (int rc = check_span(*a, x.span.row_hi != nullptr, x.doc.row_lo_sb, x.span.row_hi_sb, 0, 0)) return rc;
+  if (int rc = check_bsp(*a, x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists)) return rc;
+  if (x.bsp.mask) x.bsp.layout = block_lists(a->B, a->Hq, (a->Sq + 127) / 128, (a->Sk + 127) / 128);   // once per call
   if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
@@ -315,7 +330,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo && !x.span.row_hi) {   // (a document or span launch is served uncut: usp_hip.h)
+  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo && !x.span.row_hi && !x.bsp.mask) {   // (a document, span or block-sparse launch is served uncut: usp_hip.h)
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
     if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
@@ -363,5 +378,12 @@ extern "C" int usp_flash_fwd_span(const usp_fwd_args* a, const int32_t* row_lo, 
   usp::FwdExtras x;
   x.doc = usp::FwdDoc{row_lo, row_lo ? row_lo_stride_b : 0};         // row_hi == NULL: exactly usp_flash_fwd_doc
   x.span = usp::FwdSpan{row_hi, row_hi ? row_hi_stride_b : 0};
+  return flash_fwd_call(a, x, stream);
+}
+
+extern "C" int usp_flash_fwd_bsp(const usp_fwd_args* a, const void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                                 int64_t mask_stride_row, void* lists, void* stream) {
+  usp::FwdExtras x;                                                   // mask == NULL: exactly usp_flash_fwd
+  if (mask) x.bsp = usp::BspCall{mask, mask_stride_b, mask_stride_h, mask_stride_row, (int*)lists};
   return flash_fwd_call(a, x, stream);
 }

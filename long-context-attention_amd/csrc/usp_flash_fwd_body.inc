@@ -5,7 +5,8 @@
 // `if constexpr (AL)` ones, the dropout kernel (usp_flash_fwd_dropout.hip) the `if constexpr (DR)` ones, the sink kernel
 // (usp_flash_fwd_sink.hip) the `if constexpr (SINK)` one in the epilogue, the document kernel (usp_flash_fwd_doc.hip) the
 // `if constexpr (DOC)` ones, the span kernel (usp_flash_fwd_span.hip) the `if constexpr (SPAN)` ones on top of them (span_row_hi /
-// span_sb: int32 right row bounds and their batch stride; USP_FWD_NO_SPAN elsewhere).  The including kernel
+// span_sb: int32 right row bounds and their batch stride; USP_FWD_NO_SPAN elsewhere), the block-sparse kernel
+// (usp_flash_fwd_bsp.hip) the `if constexpr (BSP)` ones (bsp_lists / bsp_stride; USP_FWD_NO_BSP elsewhere).  The including kernel
 // defines `p_in`, KSPLIT / SC / WIN / AL / DR / SINK / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr` (usp_dropout_rng.h:
 // Dropout), sink_s (fp32 (Hq,) sink logits) and doc_row_lo / doc_sb (int32 row bounds and their batch stride).
 // (Not a header: no include guard, no declarations of its own outside the function body.)
@@ -192,7 +193,19 @@
     wave_kv_end = span_hi_w1 < p.Sk ? span_hi_w1 : p.Sk;
   }
   if (qw >= p.Sq) wave_kv_end = 0;
-  const int nt = blk_kv_end > 0 ? (blk_kv_end + kBN - 1) / kBN : 0;     // = usp_tiles_holding: called, the softcap streams change
+  // BSP (usp_flash_fwd_bsp.hip, 4 waves: the item is ONE 128-row mask block): the item walks the ascending list of 64-key tiles
+  // the builder (usp_block_lists.hip) left for it -- under CAUSAL without the blocks above the diagonal -- instead of [0, nt).  The
+  // count and every entry are clamped as read: a corrupt list gives wrong results, never an access outside K / V.
+  [[maybe_unused]] const int* bsp_l = nullptr;
+  [[maybe_unused]] int bsp_cnt = 0, bsp_tmax = 0;
+  if constexpr (BSP) {
+    bsp_l = bsp_lists + ((int64_t)(b * p.Hq + h) * p.nq + qt) * bsp_stride;
+    const int c0 = bsp_l[0], cap = bsp_stride - 2;
+    bsp_cnt = c0 < 0 ? 0 : (c0 > cap ? cap : c0);
+    bsp_tmax = usp_tiles_holding(blk_kv_end, kBN) - 1;
+    if (bsp_tmax < 0) { bsp_tmax = 0; bsp_cnt = 0; }
+  }
+  const int nt = BSP ? bsp_cnt : (blk_kv_end > 0 ? (blk_kv_end + kBN - 1) / kBN : 0);     // = usp_tiles_holding: called, the softcap streams change
   // leading tiles that need neither a causal nor a ragged mask for this wave (= usp_unmasked_tiles: called, the causal split
   // streams change)
   int n_full = p.Sk / kBN;
@@ -210,6 +223,16 @@
   if constexpr (SC) n_full = 0;                           // softcap: every tile through the generic loop
   if constexpr (AL) n_full = 0;                           // ALiBi: likewise (the bias step lives there)
   if constexpr (DR) n_full = 0;                           // dropout: likewise (the keep step lives in the generic softmax)
+  if constexpr (BSP) {     // the listed tiles below the wave's diagonal / ragged limit are a prefix of the ascending list
+    const int nfd = n_full;
+    int nf = 0;
+    for (int i0 = 0; i0 < nt; i0 += 64) {
+      const int i = i0 + lane;
+      const int e = i < nt ? bsp_l[1 + i] : 0x7fffffff;
+      nf += __builtin_popcountll(__ballot(e >= 0 && e < nfd));
+    }
+    n_full = __builtin_amdgcn_readfirstlane(nf);
+  }
   if (n_full > nt) n_full = nt;
   // WIN (flash_fwd_window_kernel: every launch has a left bound): the tiles are walked in the ROTATED order [rot, nt) then
   // [0, rot) -- online softmax does not care -- where rot is the workgroup-uniform number of leading tiles the left bound
@@ -233,13 +256,15 @@
     else n_full = n_full > rot ? n_full - rot : 0;
   }
   auto tmap = [&](int j) {
-    if constexpr (WIN || DOC) { const int t = j + rot; return t < nt ? t : t - nt; }
+    if constexpr (BSP) { const int t = bsp_l[1 + j]; return t < 0 ? 0 : (t > bsp_tmax ? bsp_tmax : t); }
+    else if constexpr (WIN || DOC) { const int t = j + rot; return t < nt ? t : t - nt; }
     else return j;
   };
   // does this wave have a visible key in the tile that starts at key kt0?  (WIN only: also skips tiles wholly left of the wave's window)
   // = usp_key_tile_live (kt0 + kBN - 1 >= qw + win_lo), which changes the window streams when called
   auto tile_live = [&](int kt0) {
-    if constexpr (DOC) return usp_doc_key_tile_live(kt0, kBN, wave_kv_end, doc_lo_w0) != 0;
+    if constexpr (BSP) return kt0 < wave_kv_end;
+    else if constexpr (DOC) return usp_doc_key_tile_live(kt0, kBN, wave_kv_end, doc_lo_w0) != 0;
     else return kt0 < wave_kv_end && kt0 + kBN > qw + win_lo;
   };
 
@@ -445,7 +470,7 @@
   }
   dma_drain();
   __syncthreads();
-  if constexpr (WIN || DOC) { if (nt > 0 && tile_live(tmap(0) * kBN)) qk(0, sa, sb); }
+  if constexpr (WIN || DOC || BSP) { if (nt > 0 && tile_live(tmap(0) * kBN)) qk(0, sa, sb); }
   else { if (nt > 0 && wave_kv_end > 0) qk(0, sa, sb); }
   // K(0) must have been read by EVERY wave before the first loop iteration refills Kbuf[0] with K(2): a
   // wave that skips qk(0) (no valid rows) reaches that DMA at once, and a mostly out-of-range K(2) tile
@@ -490,10 +515,22 @@
       for (int r = 0; r < 16; ++r) o[dj][r] *= alpha;
   };
   // one pipelined iteration: softmax + PV of tile jj (scores in ca/cb), scores of tile jj+1 into na/nb
+  // BSP: the list entries of the two stages an iteration issues were read an iteration ahead (scalar loads)
+  [[maybe_unused]] int bsp_tk = 0, bsp_tv = 0;
+  if constexpr (BSP) {
+    if (nt > 1) { bsp_tk = tmap(2 < nt ? 2 : nt - 1); bsp_tv = tmap(1); }
+  }
   auto iter = [&](int jj, f32x16& ca, f32x16& cb, f32x16& na, f32x16& nb) {
     const int jk = jj + 2 < nt ? jj + 2 : nt - 1;           // clamped prefetch (redundant load at the end)
+    if constexpr (BSP) {
+      dma_k(bsp_tk, jj & 1);
+      dma_v(bsp_tv, (jj + 1) & 1);
+      bsp_tv = bsp_tk;
+      bsp_tk = tmap(jj + 3 < nt ? jj + 3 : nt - 1);
+    } else {
     dma_k(tmap(jk), jj & 1);            // Kbuf[jj&1] held K(jj): last read in the previous iteration
     dma_v(tmap(jj + 1), (jj + 1) & 1);  // Vbuf[(jj+1)&1] held V(jj-1): last read in the previous iteration
+    }
     // ---------------- phase A ----------------
     USP_LDS const char* kb = smem + ((jj + 1) & 1) * KBYTES + k_rd_row;
     u32x4 ka[NKT], kc[NKT];
@@ -615,7 +652,7 @@
 #pragma unroll
     for (int r = 0; r < 16; ++r) { na[r] = 0.f; nb[r] = 0.f; }
     bool live;
-    if constexpr (WIN || DOC) {
+    if constexpr (WIN || DOC || BSP) {
       if (j + 1 < nt && tile_live(tmap(j + 1) * kBN)) qk((j + 1) & 1, na, nb);
       live = tile_live(kt0);
     } else {

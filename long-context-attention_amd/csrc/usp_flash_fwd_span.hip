@@ -19,6 +19,7 @@ template <int D, int DT, int NWAVES, class PA = FwdArgsSPAN>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_span_kernel(const PA p_in) {
   constexpr bool KSPLIT = !std::is_same_v<PA, FwdArgsSPAN>, WIN = false, SC = false, AL = false, DR = false, SINK = false, DOC = true;
   constexpr bool SPAN = true, CAUSAL = false;
+  USP_FWD_NO_BSP
   constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
   constexpr const float* al_slopes = nullptr;
   constexpr int64_t al_sb = 0;

@@ -90,7 +90,21 @@ struct FwdArgsSPAN : FwdArgsT<false>, FwdDoc, FwdSpan {};      // (row_lo may be
 #define USP_FWD_NO_SPAN                                          \
   [[maybe_unused]] constexpr bool SPAN = false;                  \
   [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t span_sb = 0;
+  [[maybe_unused]] constexpr int64_t span_sb = 0;                \
+  USP_FWD_NO_BSP
+// Block-sparse mask (usp_flash_fwd_bsp): kernel arguments of the block-sparse instantiations only (usp_flash_fwd_bsp.hip:
+// flash_fwd_bsp_kernel, the plain kernel's loops walking a list of key tiles); every other kernel keeps its argument block and
+// machine code.  The lists are built by usp_block_lists.hip (layout: BlockLists below).
+struct FwdBsp {
+  const int* bsp_lists;                 // int32: the list of item (b, h, 128-row block r) starts at ((b * Hq + h) * nq + r) * bsp_stride
+  int bsp_stride;                       // ints per list: [0] = count, [1 ..] = ascending 64-key tile indices
+};
+struct FwdArgsBSP : FwdArgsT<false>, FwdBsp {};
+// What a kernel without the block-sparse switch defines for the shared body (usp_flash_fwd_body.inc)
+#define USP_FWD_NO_BSP                                           \
+  [[maybe_unused]] constexpr bool BSP = false;                   \
+  [[maybe_unused]] constexpr const int* bsp_lists = nullptr;     \
+  [[maybe_unused]] constexpr int bsp_stride = 0;
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -117,5 +131,7 @@ int launch_fwd_sink(const FwdArgsSK& p, int D, int dtype, bool causal, int waves
 int launch_fwd_doc(const FwdArgsDOC& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 // The span forward (usp_flash_fwd_span.hip), likewise; never causal: the diagonal is folded into row_hi.
 int launch_fwd_span(const FwdArgsSPAN& p, int D, int dtype, int waves, int grid, size_t lds, hipStream_t st);
+// The block-sparse forward (usp_flash_fwd_bsp.hip), likewise; always the 4-wave shape: one work item is one 128-row mask block.
+int launch_fwd_bsp(const FwdArgsBSP& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

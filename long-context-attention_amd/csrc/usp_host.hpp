@@ -166,6 +166,44 @@ template <class Args> int check_span(const Args& a, bool has_span, int64_t strid
   return check_extras(a);
 }
 
+// Block-sparse mask (usp_flash_fwd_bsp / usp_flash_bwd_bsp).  NULL mask: the call is usp_flash_fwd / usp_flash_bwd, whatever the rest.
+template <class Args> int check_bsp(const Args& a, const void* mask, int64_t stride_b, int64_t stride_h, int64_t stride_row, const void* lists) {
+  if (!mask) return USP_OK;
+  if (stride_b < 0 || stride_h < 0 || stride_row < 0) return USP_EINVAL;
+  if (!lists || !aligned(lists, 4)) return USP_EINVAL;
+  if (a.flags & (USP_ATTN_WINDOW | USP_ATTN_SHIFT)) return USP_EUNSUPPORTED;   // no bound beside the mask
+  if (a.Sq != a.Sk) return USP_EUNSUPPORTED;                        // whole blocks of one sequence against itself
+  return check_extras(a);
+}
+// The lists of a block-sparse call in the caller's workspace (usp_block_lists.hip builds them, the kernels of usp_flash_fwd_bsp.hip /
+// usp_flash_bwd_bsp.hip read them), in ints: bh * nrb forward lists of `lf` ints, then from off_q bh * nqb dQ lists of `lf` ints (nqb
+// pairs of row blocks), then from off_t bh * nkb transposed lists of `lt` ints; every list is [count, entries ...].
+struct BlockLists {
+  int64_t bh;                   // B * Hq
+  int hq, nrb, nqb, nkb;
+  int lf, lt;
+  int64_t off_q, off_t, ints;
+};
+inline BlockLists block_lists(int B, int Hq, int nrb, int nkb) {
+  BlockLists l;
+  l.bh = (int64_t)B * Hq; l.hq = Hq; l.nrb = nrb; l.nqb = (nrb + 1) / 2; l.nkb = nkb;
+  l.lf = 2 * nkb + 2; l.lt = 2 * nrb + 2;
+  l.off_q = l.bh * nrb * l.lf;
+  l.off_t = l.off_q + l.bh * l.nqb * l.lf;
+  l.ints = l.off_t + l.bh * nkb * l.lt;
+  return l;
+}
+// What usp_flash_fwd_bsp / usp_flash_bwd_bsp add to a plain call (mask == NULL: nothing)
+struct BspCall {
+  const void* mask = nullptr;
+  int64_t sb = 0, sh = 0, sr = 0;
+  int* lists = nullptr;
+  BlockLists layout{};          // of `lists`, computed once per call (flash_fwd_call / flash_bwd_call) and handed down
+};
+// The builder launch (usp_block_lists.hip); which: bit 0 = forward lists, bit 1 = dQ lists, bit 2 = transposed (dK/dV) lists
+int launch_block_lists(const void* mask, int64_t sb, int64_t sh, int64_t sr, int* ws, const BlockLists& l, int Sq, int Sk, bool causal,
+                       int which, hipStream_t st);
+
 // Sliding window (flash-attn's window_size) and softcap of a call, as the kernels take them: causal caps the right bound
 // at 0; a right bound is the causal limit with a shifted offset (causal instantiation); a left bound is a second mask term
 // (forward: the split instantiation, FwdSplit).

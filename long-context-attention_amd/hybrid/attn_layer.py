@@ -19,6 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
+from ..kernels.features import block_mask_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -57,12 +58,13 @@ class _USPLayer(torch.nn.Module):
             self._ring_size = dist.get_world_size(self.ring_pg) if self.ring_pg is not None else 1
         return self._ring_size
 
-    def _head_options(self, alibi_slopes, dropout_p, sinks, cu_doclens, heads: int, scatter_idx: int):
+    def _head_options(self, alibi_slopes, dropout_p, sinks, cu_doclens, heads: int, scatter_idx: int, block_mask=None):
         """(the ring function's keywords dropout_head0 / sinks / cu_doclens, the slopes) for the heads this Ulysses rank holds
         behind the exchange (comm/all_to_all.py: local_options); with nothing to exchange any layout serves."""
         P = self.ulysses_size
         return local_options(alibi_slopes, dropout_p, sinks, cu_doclens, heads, P, dist.get_rank(self.ulysses_pg) if P > 1 else 0,
-                             P == 1 or (scatter_idx, self.gather_idx) == (2, 1), "heads scattered, sequence gathered")
+                             P == 1 or (scatter_idx, self.gather_idx) == (2, 1), "heads scattered, sequence gathered",
+                             block_mask=block_mask)
 
     def _docs(self, cu_doclens, batch: int, local_len: int, bidirectional=None):
         """`cu_doclens` checked against the WHOLE sequence (ring/doc_blocks.py: parse; a rank holds local_len of its
@@ -129,7 +131,7 @@ class LongContextAttention(_USPLayer):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                 deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None,
-                bidirectional=None) -> Tensor:
+                bidirectional=None, block_mask=None) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
         layer, (head_cnt,) fp32 or the operands' type (comm/all_to_all.py: local_options: the gradient contract).  `cu_doclens` (keyword
@@ -138,16 +140,22 @@ class LongContextAttention(_USPLayer):
         degree, with the zigzag and stripe rings at ring degree 1.  `bidirectional` (keyword only): half-open spans [(s, e), ...]
         of global positions of the WHOLE sequence, host data, the same on every rank, or "documents" (ring/doc_blocks.py:
         parse_plan): inside a span every row sees the whole span; with or without cu_doclens, served where it is.  None, an empty
-        list or spans of length 1 only: exactly the call without it -- the same exchange and the same launches."""
+        list or spans of length 1 only: exactly the call without it -- the same exchange and the same launches.
+        `block_mask` (keyword only): a torch.bool DEVICE tensor of 128 x 128 blocks over the WHOLE sequence, the same on every
+        rank, (nb, nb), (head_cnt, nb, nb) or (bs, head_cnt, nb, nb) (or over the local heads): global row i sees global key j iff
+        block_mask[b, h, i // 128, j // 128] and (not causal or j <= i).  Never read on the host; not together with any other
+        option.  Served with the basic ring at any ring degree (a local length that is a multiple of 128), with the zigzag and
+        stripe rings at ring degree 1, through three exchanges.  None: exactly the call without it."""
+        block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
                                causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens, bidirectional=bidirectional)
+                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask)
             return out[..., :D]
         cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1], bidirectional)     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
-        if ng_cap is not None and (cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
+        if ng_cap is not None and (block_mask is not None or cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
                                    or dropout_value(dropout_p) is not None or sinks is not None):
             # Any of them: the reference's structure (three exchanges), and the ring function serves it (ring/front_end.py: _place).
             # The pipeline issues blocks in row pieces and head groups: under a document mask each piece would need its own
@@ -160,7 +168,8 @@ class LongContextAttention(_USPLayer):
             _check_hot_path_args(dropout_p, window_size, softcap)
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
                                        self.ring_impl_type, ng_cap, softcap_value(softcap))
-        head_kw, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2], self.scatter_idx)
+        head_kw, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2], self.scatter_idx,
+                                                   block_mask)
         options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                                      return_attn_probs)
         options.update(head_kw)
@@ -188,16 +197,18 @@ class LongContextAttentionQKVPacked(_USPLayer):
 
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                *args: Any, sinks=None, cu_doclens=None, bidirectional=None) -> Tensor:
+                *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None) -> Tensor:
+        block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = qkv.shape[-1]
         if kernel_head_dim(D) != D:
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                                window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens, bidirectional=bidirectional)
+                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask)
             return out[..., :D]
         exchange = self.ulysses_size > 1
         cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1], bidirectional)
-        head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1)
+        head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1,
+                                                 block_mask)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,

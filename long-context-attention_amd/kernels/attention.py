@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from .. import _C
-from .features import Features
+from .features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, expand_block_mask  # noqa: F401
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -80,10 +80,10 @@ class HipBlockBackend:
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
             final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None,
-            sinks=None, doc=None, span=None):
+            sinks=None, doc=None, span=None, bsp=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
                      interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi,
-                     dropout=dropout, sinks=sinks, doc=doc, span=span)
+                     dropout=dropout, sinks=sinks, doc=doc, span=span, bsp=bsp)
 
     def sink_grad(self, sinks, lse, delta, out=None, accum=False):
         return _C.sink_grad(sinks, lse, delta, out=out, accum=accum)
@@ -93,10 +93,10 @@ class HipBlockBackend:
 
     def bwd(self, dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq=False,
             accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None, window=None, only=None, softcap=None,
-            shift=None, alibi=None, dropout=None, doc=None, span=None):
+            shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None):
         _C.flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, causal, accum_dq,
                      accum_dk, accum_dv, dq16, dk16, dv16, interleave=self.interleave, window=window, only=only,
-                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout, doc=doc, span=span)
+                     softcap=softcap, shift=shift, alibi=alibi, dropout=dropout, doc=doc, span=span, bsp=bsp)
 
     def fwd_packed(self, q, k, v, seq_q, seq_k, max_q, max_k, softmax_scale, causal, lse, out=None,
                    acc=None, merge_in=False, final_begin=0, final_end=2, softcap=None):
@@ -280,9 +280,17 @@ def window_of(window_size):
     return _C._window(window_size)
 
 
+def block_mask_of(block_mask, q, k):
+    """`block_mask` of a whole single-device call on q (B, S, Hq, D) and k, checked (ValueError: shape, dtype, device;
+    NotImplementedError: q and k of different lengths) and returned as given; no value of it is read."""
+    block_mask_self_attention(q.shape[1], k.shape[1])
+    _C.block_mask_value(block_mask, q.shape[0], q.shape[2], q.shape[1], q.device)
+    return block_mask
+
+
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                      softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
-                     bidirectional=None):
+                     bidirectional=None, block_mask=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -298,7 +306,23 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     `bidirectional` (keyword only): half-open spans [(s, e), ...] of positions, host data, sorted and disjoint, each inside one
     document, or "documents" (ring/doc_blocks.py: parse_plan): inside a span every row sees the whole span, so row i sees key j
     iff start(i) <= j < hi(i).  With or without cu_doclens, under its preconditions and refusals.  None, an empty list or spans
-    of length 1 only: exactly the call without it."""
+    of length 1 only: exactly the call without it.
+    `block_mask` (keyword only): a torch.bool DEVICE tensor (nb, nb), (Hq, nb, nb) or (B, Hq, nb, nb), nb = ceil(Sq / BLOCK_MASK_SIZE):
+    row i sees key j iff block_mask[b, h, i // 128, j // 128] and (not causal or j <= i); under causal the bits above the diagonal
+    are ignored.  It is never read on the host (it may come from a kernel on the same stream) and gets no gradient.  Needs
+    equally long q and k; not together with any of window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
+    bidirectional.  None: exactly the call without it."""
+    if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        block_mask_of(block_mask, q, k)
+        B, Sq, Hq, D = q.shape
+        scale = _default_scale(q, softmax_scale)
+        if kernel_head_dim(D) != D:
+            out, lse = hip_attn_forward(*pad_head_dim(q, k, v), softmax_scale=scale, causal=causal, block_mask=block_mask)
+            return out[..., :D].contiguous(), lse
+        out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        get_block_backend().fwd(q, k, v, scale, bool(causal), lse, out=out, bsp=block_mask)
+        return out, lse
     f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional=bidirectional)
     dr = _dropout_of(f.dropout, rng_state, "hip_attn_forward")
     B, Sq, Hq, D = q.shape
@@ -318,13 +342,17 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
 def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk_buffer,
                       block_dv_buffer, dropout_p=0.0, softmax_scale=None, bwd_causal=False,
                       window_size=(-1, -1), softcap=None, alibi_slopes=None, deterministic=False,
-                      rng_state=None, *args, sinks=None, dsinks=None, cu_doclens=None, bidirectional=None, **kwargs):
+                      rng_state=None, *args, sinks=None, dsinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
+                      **kwargs):
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
     (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one.
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
-    `cu_doclens`, `bidirectional` (keyword only): as hip_attn_forward took them."""
+    `cu_doclens`, `bidirectional`, `block_mask` (keyword only): as hip_attn_forward took them."""
+    bsp_kw = {}
+    if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        bsp_kw = dict(bsp=block_mask_of(block_mask, q, k))
     f = Features.of(q, k, bwd_causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional=bidirectional)
     if sinks is not None and dsinks is None:
         raise ValueError("hip_attn_backward with sinks needs the fp32 (Hq,) buffer dsinks")
@@ -336,7 +364,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
         g = [torch.empty_like(t) for t in (pq, pk, pv)]
         hip_attn_backward(pdo, pq, pk, pv, po, softmax_lse, g[0], g[1], g[2], dropout_p, _default_scale(q, softmax_scale),
                           bwd_causal, window_size, f.softcap, alibi_slopes, deterministic, rng_state, sinks=sinks, dsinks=dsinks,
-                          cu_doclens=f.doc)
+                          cu_doclens=f.doc, block_mask=block_mask)
         for dst, src in zip((block_dq_buffer, block_dk_buffer, block_dv_buffer), g):
             dst.copy_(src[..., :D])
         return
@@ -354,7 +382,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     tgt = [t if direct(t) else torch.empty(t.shape, dtype=t.dtype, device=dev)
            for t in (block_dq_buffer, block_dk_buffer, block_dv_buffer)]
     be.bwd(dout, q, k, v, lse, delta, None, None, None, _default_scale(q, softmax_scale), bool(bwd_causal) and "span" not in kw,
-           dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], **kw)
+           dq16=tgt[0], dk16=tgt[1], dv16=tgt[2], **kw, **bsp_kw)
     for t, dst in zip(tgt, (block_dq_buffer, block_dk_buffer, block_dv_buffer)):
         if t is not dst:
             dst.copy_(t)
@@ -366,7 +394,7 @@ class _HipAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None,
-                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None):
+                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None, block_mask=None):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
         # dropout: one seed per call, drawn here, kept for the backward (draw_seed); the block is the whole sequence
@@ -374,8 +402,9 @@ class _HipAttnFunc(torch.autograd.Function):
         ctx.rng_state = (draw_seed(), 0, 0, int(dropout_head0)) if ctx.dropout_p else None
         out, lse = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
                                     softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks,
-                                    cu_doclens=cu_doclens)
+                                    cu_doclens=cu_doclens, block_mask=block_mask)
         ctx.cu_doclens = cu_doclens
+        ctx.block_mask = block_mask                # (no gradient; the backward rebuilds its lists from it, on the device)
         ctx.has_sinks = sinks is not None          # (never beside slopes: the one optional saved tensor is either)
         ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)),
                               *(() if sinks is None else (sinks,)))                                     # (slopes: no gradient,
@@ -393,15 +422,15 @@ class _HipAttnFunc(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, ctx.dropout_p, ctx.scale, ctx.causal,
                           ctx.window_size, ctx.softcap, slopes[0] if slopes else None, rng_state=ctx.rng_state, sinks=sinks,
-                          dsinks=dsinks, cu_doclens=ctx.cu_doclens)
+                          dsinks=dsinks, cu_doclens=ctx.cu_doclens, block_mask=ctx.block_mask)
         if dsinks is not None:
             dsinks = dsinks.to(sinks.dtype) if ctx.needs_input_grad[11] else None
-        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None
+        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                  *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, **kwargs):
+                  *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -413,7 +442,18 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     its gradient comes back in its own dtype and shape.  Not together with softcap, alibi_slopes or dropout_p.
     `cu_doclens` (keyword only): the document mask of a packed sequence (hip_attn_forward), padded head dims included.
     `bidirectional` (keyword only): bidirectional spans beside or without it (hip_attn_forward), likewise; parsed here once, the
-    plan travels on as `cu_doclens`."""
+    plan travels on as `cu_doclens`.
+    `block_mask` (keyword only): a 128 x 128 block mask (hip_attn_forward), padded head dims included; no gradient."""
+    if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        block_mask_of(block_mask, q, k)
+        D = q.shape[-1]
+        if kernel_head_dim(D) != D:
+            res = hip_attn_func(*pad_head_dim(q, k, v), softmax_scale=_default_scale(q, softmax_scale), causal=causal,
+                                return_attn_probs=return_attn_probs, block_mask=block_mask)
+            return (res[0][..., :D], res[1], None) if return_attn_probs else res[..., :D]
+        res = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, bool(return_attn_probs), (-1, -1), None, None, 0.0, 0, None, None,
+                                 block_mask)
+        return (res[0], res[1], None) if return_attn_probs else res
     f = Features.of(q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional=bidirectional)
     cap, cu_doclens = f.softcap, f.doc
     D = q.shape[-1]

@@ -1,7 +1,9 @@
 """The optional features of one attention call -- window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens -- as ONE
 record, and the ONE table of which of them the kernels serve together.  `bidirectional` (spans) is no seventh field: it goes
 together with cu_doclens and RIDES INSIDE the parsed document plan (ring/doc_blocks.py: Spans), so the record keeps its six
-fields and every positional construction its meaning; a `doc` that carries spans is named "bidirectional" in the refusals.  Pure argument logic: nothing here loads the library,
+fields and every positional construction its meaning; a `doc` that carries spans is named "bidirectional" in the refusals.
+`block_mask` (a 128 x 128 block mask) is no field either: it goes with none of the seven and is judged in one place, before the
+record is made (block_mask_alone).  Pure argument logic: nothing here loads the library,
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
@@ -18,6 +20,40 @@ REFUSES = (("doc", ("window", "softcap", "alibi", "dropout", "sinks")),
            ("alibi", ("softcap",)),
            ("softcap", ()))
 PACKED = ("softcap",)         # what the packed (variable-length) launches serve
+
+
+BLOCK_MASK_SIZE = 128        # rows and keys of one block of `block_mask` (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
+
+
+def expand_block_mask(mask, block_size: int):
+    """A block mask of `block_size`-square blocks (a multiple of BLOCK_MASK_SIZE) as the BLOCK_MASK_SIZE-square one the kernels
+    take: every entry repeated block_size / BLOCK_MASK_SIZE times along the last two dimensions, on the mask's device."""
+    if block_size <= 0 or block_size % BLOCK_MASK_SIZE:
+        raise ValueError(f"block_size must be a positive multiple of {BLOCK_MASK_SIZE}, got {block_size}")
+    n = block_size // BLOCK_MASK_SIZE
+    return mask if n == 1 else mask.repeat_interleave(n, dim=-2).repeat_interleave(n, dim=-1)
+
+
+def block_mask_alone(block_mask, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
+                     bidirectional=None) -> bool:
+    """Is `block_mask` on?  It is no field of the record: it is judged HERE, before Features.of and before any tensor is read,
+    and goes with none of the other options -- the block-sparse kernels hold no second mask or score-level step.  None is
+    exactly the call without the keyword."""
+    if block_mask is None:
+        return False
+    given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
+             ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"block_mask together with {name} is not supported by the HIP attention kernels")
+    return True
+
+
+def block_mask_self_attention(Sq: int, Sk: int):
+    """A block mask covers one sequence against itself."""
+    if Sq != Sk:
+        raise NotImplementedError(f"block_mask needs whole q and k of the same length (self-attention), got {Sq} and {Sk}: "
+                                  f"for cross-attention use a dense call without the keyword")
 
 
 class _SpanMark:

@@ -9,7 +9,7 @@ import torch.distributed as dist
 from .._C import dropout_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
-from ..kernels.features import Features
+from ..kernels.features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention
 from .utils import group_info
 from .varlen_utils import unflatten_lse
 
@@ -45,11 +45,14 @@ class RingServes(NamedTuple):
     sinks: int = NOT_SERVED
     doc: int = NOT_SERVED
     span: int = NOT_SERVED        # bidirectional spans: they ride inside the parsed `cu_doclens` plan (ring/doc_blocks.py: Spans)
+    block_mask: int = NOT_SERVED  # a 128 x 128 block mask: it rides in the `cu_doclens` slot as a BlockMask (below); ANY_DEGREE:
+                                  # the ring's forward / backward hand every (rank, step) launch its view of it (`bsp=`)
 
 
 PACKED_RING = RingServes()
-DENSE_RING = RingServes(alibi=ONE_BLOCK, dropout=ONE_BLOCK, sinks=ANY_DEGREE, doc=ONE_BLOCK, span=ONE_BLOCK)       # zigzag, stripe
-BASIC_RING = RingServes(*(ANY_DEGREE,) * 6)
+DENSE_RING = RingServes(alibi=ONE_BLOCK, dropout=ONE_BLOCK, sinks=ANY_DEGREE, doc=ONE_BLOCK, span=ONE_BLOCK,
+                        block_mask=ONE_BLOCK)                                                                      # zigzag, stripe
+BASIC_RING = RingServes(*(ANY_DEGREE,) * 7)
 
 # feature -> (its name in the refusals, what the packed rings advise, what a ONE_BLOCK ring advises beyond ring degree 1)
 _BASIC = "use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func)"
@@ -103,6 +106,51 @@ def _refuse_packed_spans(bidirectional):
     if _span_given(bidirectional):
         name, advice, _ = _ADVICE["span"]
         raise NotImplementedError(f"{name} is not supported by the variable-length (packed) rings: {advice}")
+
+
+class BlockMask:
+    """The `block_mask` of a dense ring call on its way to the ring's forward / backward: it travels in the `cu_doclens` slot
+    (with which it never goes together), so the Function keeps its arguments.  `mask` covers the WHOLE sequence -- ring degree x
+    the local length -- and is the same on every rank; it is a device tensor and is never read on the host."""
+    spans = None
+
+    def __init__(self, mask):
+        self.mask = mask
+
+    def view(self, r: int, kr: int, S: int, P: int):
+        """The sub-mask of the launch of rank r's rows [r S, (r + 1) S) against ring rank kr's keys: a strided view, no copy."""
+        if P == 1:
+            return self.mask
+        n = S // BLOCK_MASK_SIZE
+        return self.mask[..., r * n:(r + 1) * n, kr * n:(kr + 1) * n]
+
+
+def _refuse_packed_block_mask(block_mask):
+    if block_mask is not None:
+        raise NotImplementedError("block_mask is not supported by the variable-length (packed) rings: use LongContextAttention "
+                                  "(ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches")
+
+
+def block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+    """`cu_doclens` for the rest of a dense ring call: the BlockMask where `block_mask` is given -- judged first, alone
+    (kernels/features.py: block_mask_alone) --, else `cu_doclens` as it is."""
+    if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        return BlockMask(block_mask)
+    return cu_doclens
+
+
+def _place_block_mask(serves, q, k, bm, group):
+    """The checks of a ring call under a block mask: what this ring serves, whole blocks per rank, the value itself."""
+    from .._C import block_mask_value
+    P = group_info(dist, group)[0]
+    if P > 1 and serves.block_mask != ANY_DEGREE:
+        raise NotImplementedError(f"block_mask across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
+                                  f"rings: {_BASIC}")
+    block_mask_self_attention(q.shape[1], k.shape[1])
+    if P > 1 and q.shape[1] % BLOCK_MASK_SIZE:
+        raise NotImplementedError(f"block_mask at ring degree {P} needs a local sequence length that is a multiple of "
+                                  f"{BLOCK_MASK_SIZE} (whole mask blocks per rank), got {q.shape[1]}: pad the sequence")
+    block_mask_value(bm.mask, q.shape[0], q.shape[2], P * q.shape[1], q.device)
 
 
 def _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, group):
@@ -188,7 +236,10 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
     def ring_pair(docs):
         """The (forward, backward) that run a call: this ring's, or -- under a document mask on a ring that serves it as
-        ONE_BLOCK, which _place lets through at ring degree 1 only -- the basic ring's one-block call."""
+        ONE_BLOCK, which _place lets through at ring degree 1 only -- the basic ring's one-block call.  `docs` is whatever rides
+        in the `cu_doclens` slot: the parsed document plan, or a BlockMask (`block_mask=`; _place_block_mask lets it through
+        beyond ring degree 1 on a ring with block_mask == ANY_DEGREE only) -- so a zigzag or stripe call under a block mask at
+        ring degree 1 runs the basic ring's functions too."""
         return (forward, backward) if serves.doc == ANY_DEGREE or docs is None else _basic_ring()
 
     def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw,
@@ -197,7 +248,12 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         backward)."""
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
-        p, docs = _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sink_t, cu_doc, group)
+        if isinstance(cu_doc, BlockMask):           # (judged alone already: nothing else is on)
+            _place_block_mask(serves, q, k, cu_doc, group)
+            _check_hot_path_args(dropout_p, window_size, softcap)
+            p, docs = None, cu_doc
+        else:
+            p, docs = _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sink_t, cu_doc, group)
         if packed:
             k, v = k.contiguous(), v.contiguous()
         else:
@@ -258,7 +314,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
-                 cu_doclens=None, bidirectional=None):
+                 cu_doclens=None, bidirectional=None, block_mask=None):
+            _refuse_packed_block_mask(block_mask)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
@@ -266,7 +323,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None):
+                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None):
+            _refuse_packed_block_mask(block_mask)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
@@ -274,7 +332,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None):
+                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None):
+            _refuse_packed_block_mask(block_mask)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
@@ -291,7 +350,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                  attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
-                 bidirectional=None):
+                 bidirectional=None, block_mask=None):
+            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)       # (the spans travel inside the plan from here on)
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
@@ -308,14 +368,18 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None):
+                          attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
+                          block_mask=None):
+            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                               deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks, cu_doclens))
 
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
-                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None):
+                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
+                           block_mask=None):
+            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
             cu_doclens = span_plan(qkv[:, :, 0], group, cu_doclens, bidirectional)
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type),

@@ -41,7 +41,7 @@ import torch.distributed as dist
 from ..kernels import AttnType
 from ..kernels.attention import get_block_backend, window_of
 from . import block_pieces, doc_blocks
-from .front_end import BASIC_RING, ring_dropout, ring_front_end
+from .front_end import BASIC_RING, BlockMask, ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, return_dkdv_direct, travel_dkdv
 from .window_blocks import WindowPlan
 
@@ -107,6 +107,19 @@ def _step_launch_kw(al, dr, r, P, step, S, blk_kw=None):
     return blk_kw
 
 
+def _block_mask_of(cu_doclens):
+    """(the BlockMask that rides in the cu_doclens slot | None, the document plan | None)"""
+    return (cu_doclens, None) if isinstance(cu_doclens, BlockMask) else (None, cu_doclens)
+
+
+def _bsp_kw(bm, r, P, step, S):
+    """The `bsp=` keyword of the launch of ring step `step` under a block mask: the view of the global mask that holds this
+    rank's row blocks against the key blocks of ring rank kr = r - step (mod P) -- a strided view, no copy, never read here.
+    The schedule is untouched: the diagonal block is causal, the blocks below it full, and a block whose sub-mask is all false
+    is launched all the same (skipping it would need a host read of the mask); the kernels return quickly on empty lists."""
+    return {} if bm is None else {"bsp": bm.view(r, (r - step) % P, S, P)}
+
+
 def _window_plan(win, P, r, c, causal):
     return WindowPlan(P, c, bool(causal), win[0], win[1], r)
 
@@ -144,7 +157,9 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     the launch that opens the rows' state (step 0; the window planner's first block), at any ring degree.  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
+    bm, cu_doclens = _block_mask_of(cu_doclens)
     pieces = first is not None or tail is not None
+    assert bm is None or not pieces, "block_mask: ring/front_end.py"
     dr = ring_dropout(dropout_p, rng_state)
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
@@ -183,6 +198,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     if win is not None and P == 1:   # ring degree 1: one block, the kernels take flash-attn's window (left, right)
         be.fwd(q, k, v, softmax_scale, bool(causal), lse, out, window=win)
         return out, lse
+    assert bm is None or (win is None and k.shape[1] == S), "block_mask: ring/front_end.py"
     if win is not None:              # USP_RING_WINDOW=global: only the blocks the window touches, each with its own bounds
         assert k.shape[1] == S, "the basic ring holds equally long chunks of q and k"
         plan = _window_plan(win, P, r, S, causal)
@@ -200,7 +216,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
         for step in range(P):
             kk, vv = relay.get(step)
             basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc,
-                           **_step_launch_kw(al, dr, r, P, step, S))
+                           **_step_launch_kw(al, dr, r, P, step, S), **_bsp_kw(bm, r, P, step, S))
     return out, lse
 
 
@@ -213,7 +229,9 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
     block kernels are unchanged, and this rank's share of their gradient (its rows) is returned as a fourth, fp32 element.  `defer`: travel_dkdv's list for the pending last hop.  `first`, `dq_first`: see zigzag_ring_flash_attn_backward; served at
     ring degree 1 only (ring/block_pieces.py)."""
     P, r = group_info(dist, process_group)
+    bm, cu_doclens = _block_mask_of(cu_doclens)
     pieces = first is not None or dq_first is not None
+    assert bm is None or (not pieces and window_of(window_size) is None), "block_mask: ring/front_end.py"
     dr = ring_dropout(dropout_p, rng_state)
     assert not pieces or (P == 1 and causal and window_of(window_size) is None and alibi_slopes is None and dr is None)
     al = _ring_alibi(alibi_slopes, P)
@@ -233,7 +251,8 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         be.bwd(dout, q, k, v, softmax_lse, delta, None, None, None, softmax_scale,
                bool(causal) if call is None else call.causal(0, causal),
-               dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)), **({} if call is None else call.kw(0)))
+               dq16=dq, dk16=dk, dv16=dv, **_window_kw(_ring_window(window_size, P)), **({} if call is None else call.kw(0)),
+               **_bsp_kw(bm, 0, 1, 0, q.shape[1]))
         return with_dsinks((dq, dk, dv))
     win = _ring_window(window_size, P)
     dq_acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev)
@@ -274,7 +293,7 @@ def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, sof
             return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
                                    dq_acc, dk_dst, dv_dst, doc=call.doc(step))
         return basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, softmax_lse, delta, softmax_scale,
-                               dq_acc, dk_dst, dv_dst, **_step_launch_kw(al, dr, r, P, step, S))
+                               dq_acc, dk_dst, dv_dst, **_step_launch_kw(al, dr, r, P, step, S), **_bsp_kw(bm, r, P, step, S))
 
     def fold(step, dk_acc, dv_acc, dk_blk, dv_blk):
         be.add(dk_acc, dk_acc, dk_blk)

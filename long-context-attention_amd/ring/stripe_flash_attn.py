@@ -8,6 +8,10 @@ token i*P + r, the K/V of ring rank r_k = r - step are visible to query i iff
 Both shapes are what the HIP kernel already does (bottom-right aligned causal on a square block);
 the row offset is a pointer offset on q / out / acc / lse.  Differences from the reference are the
 ones listed in zigzag_ring_flash_attn.py (fused merge, fp32 in-place gradients, side-stream relay).
+
+A block mask (`block_mask`, ring/front_end.py: BlockMask, riding in the `cu_doclens` slot) is served at ring degree 1 only, and there
+by the BASIC ring's forward / backward (ring_front_end: ring_pair) -- one block over the natural order; beyond degree 1 the front
+end refuses and names the basic ring.
 """
 import torch
 import torch.distributed as dist

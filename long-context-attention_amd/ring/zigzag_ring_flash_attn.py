@@ -17,6 +17,10 @@ MI355X-first differences (results identical up to fp32 rounding order):
   * the backward kernels accumulate dQ in place in fp32 and emit fp32 dK/dV blocks, replacing the
     16-bit dq/dk/dv buffers + fp32 adds of :115-170;
   * K/V are relayed ahead of the kernels on a side HIP stream (ring/utils.py KVRelay).
+
+A block mask (`block_mask`, ring/front_end.py: BlockMask, riding in the `cu_doclens` slot) is served at ring degree 1 only, and there
+by the BASIC ring's forward / backward (ring_front_end: ring_pair) -- one block over the natural order; beyond degree 1 the front
+end refuses and names the basic ring.
 """
 import os
 

@@ -13,6 +13,7 @@ from torch import Tensor
 
 from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_options
 from ..kernels import AttnType, select_flash_attn_impl
+from ..kernels.features import block_mask_alone
 
 
 class UlyssesAttention(torch.nn.Module):
@@ -38,7 +39,10 @@ class UlyssesAttention(torch.nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None) -> Tensor:
+                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None) -> Tensor:
+        # `block_mask`: a 128 x 128 block mask of the whole sequence (kernels/attention.py: hip_attn_forward), over the layer's
+        # heads (cut to this rank's), the local heads or none; judged alone, before anything else
+        block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         # `bidirectional`: spans of the whole sequence beside or without cu_doclens (kernels/attention.py: hip_attn_forward); an
         # empty list is the call without it.
         if bidirectional is not None and not isinstance(bidirectional, str) and len(bidirectional) == 0:
@@ -48,7 +52,7 @@ class UlyssesAttention(torch.nn.Module):
         head_kw, alibi_slopes = local_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2],
                                               dist.get_world_size(self.spg), dist.get_rank(self.spg),
                                               (self.scatter_idx, self.gather_idx) == (2, 1), "scatter_idx=2, gather_idx=1",
-                                              bidirectional=bidirectional)
+                                              bidirectional=bidirectional, block_mask=block_mask)
         q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
