@@ -175,11 +175,14 @@ def test_no_host_sync(dev):
 # ---- 2. the built lists ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", MASKS)
 @pytest.mark.parametrize("causal", [True, False], ids=["causal", "full"])
-@pytest.mark.parametrize("shape", [(1, 640, 4, 2, 128), (2, 384, 2, 2, 64), (1, 333, 3, 1, 32), (1, 128, 1, 1, 128), (1, 8300, 1, 1, 32)],
+@pytest.mark.parametrize("shape", [(1, 640, 4, 2, 128), (2, 384, 2, 2, 64), (1, 333, 3, 1, 32), (1, 128, 1, 1, 128), (1, 8300, 1, 1, 32),
+                                   (1, 300, 3, 1, 32), (1, 4400, 1, 1, 32)],
                          ids=lambda s: "B%d-S%d-H%d" % s[:3])
 def test_built_lists(dev, shape, causal, kind):
     """Counts, order, the causal drop, the half bits and the transpose, read back and compared with a numpy enumeration.
-    S = 8300: 65 blocks, more than one 64-lane step of the builder, and a last block whose second tile does not exist."""
+    S = 8300: 65 blocks, more than one 64-lane step of the builder; its last block holds 108 keys, so both of its tiles exist
+    (tiles 128 and 129 of 130).  S = 300 and S = 4400 (44 and 48 keys in the last block): a last block whose second tile does not
+    exist."""
     from yunchang_amd import _C
     B, S, Hq, Hkv, D = shape
     q, k, v, do = inputs(dev, B, S, Hq, Hkv, D, "bfloat16")
