@@ -128,6 +128,9 @@ enum {
 /* USP_ATTN_BLOCK_MASK: a FEATURE bit like USP_ATTN_DOC: the library exports usp_block_list_bytes / usp_flash_fwd_bsp /
  * usp_flash_bwd_bsp (below), which take a 128 x 128 block mask beside the unchanged argument blocks. */
 #define USP_ATTN_BLOCK_MASK 8192
+/* USP_ATTN_MAX_LOGIT: a FEATURE bit like USP_ATTN_SINK: the library exports usp_flash_fwd_maxlogit / usp_row_max_reduce (below),
+ * which return the largest visible pre-softmax logit of every row / head beside the unchanged argument blocks (ABI still v7). */
+#define USP_ATTN_MAX_LOGIT 16384
 
 typedef struct usp_tensor {
   void* ptr;
@@ -379,6 +382,40 @@ int usp_sink_bwd(int32_t B, int32_t S, int32_t H, const float* sinks, const floa
                  int32_t accum, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Max logits: usp_flash_fwd that also returns, per query row, the largest pre-softmax logit the row sees (QK-clip / MuonClip
+ * need the per-head maximum at every step; TransformerEngine's `return_max_logit`).  With S_ij = softmax_scale * q_i . k_j:
+ *     row_max[b, h, i] = max over the keys j row i SEES of S_ij          ( -inf for a row that sees no key )
+ * in SCORE units, the unit `sinks` uses.  The mask is the call's own (causal, ragged Sk, USP_ATTN_WINDOW, USP_ATTN_SHIFT): a
+ * hidden key never counts.  `row_max` is DEVICE fp32, element (b, h, i) at b * stride_b + h * stride_h + i (seq stride 1, like
+ * lse); rows i < Sq are written, with ordinary stores, nothing else.  out, acc and lse are bit for bit those of usp_flash_fwd on
+ * the two-waves-per-SIMD kernels.  The value is the TRUE maximum, not the online softmax's reference (which the pipelined loop
+ * raises lazily): every score is one fp32 MFMA chain over D, so the result does not depend on the tiling, and
+ *     |row_max - exact| <= 2 * softmax_scale * D * 2^-24 * sum_d |q_d k_d| + 2^-23 |exact|.
+ * The maximum is row-local and position-free and travels with lse: the launch that opens the rows' running state
+ * (merge_in == 0) writes it, a merge_in launch over further keys takes the maximum with the value already there.
+ *   - row_max == NULL is exactly usp_flash_fwd: the same kernels, bit-identical results, whatever the strides;
+ *   - a negative stride (or a row_max off a 4-byte boundary) is USP_EINVAL;
+ *   - USP_ATTN_SOFTCAP, a packed batch (seq_q / seq_k) and USP_FORCE_ROW64 are USP_EUNSUPPORTED, nothing launched or written
+ *     (these checks follow the argument checks every call gets, as for the sinks);
+ *   - k_splits is IGNORED, as under the document mask: the launch is served uncut, never refused;
+ *   - every head dim runs on the two-waves-per-SIMD family (flash_fwd_maxl_kernel: the plain family's tile loops, pipelined
+ *     interior tiles included, at one v_max per tile; unforced D = 128 included); usp_last_launch_kinds() reports wave8 / wave4.
+ * Everything else is as the argument block says (final_begin / final_end with acc, USP_LAUNCH_INTERLEAVE, GQA, any aligned
+ * layout).  The backward is untouched.  Max logits together with ALiBi, dropout, sinks, documents, spans or a block mask have no
+ * entry point.
+ *
+ * usp_row_max_reduce: out[h] = max_{b < B, i < S} row_max[b,h,i] for h < H; with accum != 0 the maximum with out[h] as well.
+ * row_max is (B,H,S) fp32 with seq stride 1 and the given batch / head strides; out is (H,) fp32.  Exact and deterministic (one
+ * workgroup per head, no atomics).  Null pointers, non-positive sizes and negative strides are USP_EINVAL.
+ * Over a sequence-parallel group each rank holds its SHARE -- the maximum over its own rows (ring) or heads (Ulysses); the MAX
+ * over the group is the value.  Nothing in this library reduces it across ranks.
+ * -------------------------------------------------------------------------------------------- */
+int usp_flash_fwd_maxlogit(const usp_fwd_args* args, float* row_max, int64_t row_max_stride_b, int64_t row_max_stride_h,
+                           void* stream);
+int usp_row_max_reduce(int32_t B, int32_t S, int32_t H, const float* row_max, int64_t row_max_stride_b,
+                       int64_t row_max_stride_h, float* out, int32_t accum, void* stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Document mask: usp_flash_fwd / usp_flash_bwd with a left key bound read per row.  A sequence that packs several documents must
  * keep every row from attending across a document boundary; for one launch (a whole sequence, or one block of a ring) that is
  *     row i sees key j   iff   j >= row_lo[i]   and   the mask of the argument block (causal, ragged Sk) lets it,
@@ -599,7 +636,8 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
- * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN, the last five feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span entry points exist).  Unknown flag bits are not rejected by
+ * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT, the last seven feature
+ * bits: the *_alibi / *_dropout / *_sink / *_doc / *_span / *_bsp / *_maxlogit entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -34,6 +34,7 @@ USP_ATTN_SINK = 1024           # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_DOC = 2048            # feature bit of usp_attn_features(): usp_flash_fwd_doc / usp_flash_bwd_doc exist (not an args flag)
 USP_ATTN_SPAN = 4096           # feature bit of usp_attn_features(): usp_flash_fwd_span / usp_flash_bwd_span exist (not an args flag)
 USP_ATTN_BLOCK_MASK = 8192     # feature bit of usp_attn_features(): usp_block_list_bytes / usp_flash_fwd_bsp / usp_flash_bwd_bsp exist (not an args flag)
+USP_ATTN_MAX_LOGIT = 16384     # feature bit of usp_attn_features(): usp_flash_fwd_maxlogit / usp_row_max_reduce exist (not an args flag)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
@@ -117,7 +118,8 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_sum_rows", "usp_cast_from_f32", "usp_add_f32", "usp_abi_version", "usp_strerror", "usp_last_launch_kinds", "usp_mfma_probe",
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
-           "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp")
+           "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
+           "usp_flash_fwd_maxlogit", "usp_row_max_reduce")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -127,6 +129,7 @@ SINK_EXPORTS = ("usp_flash_fwd_sink", "usp_sink_bwd")
 DOC_EXPORTS = ("usp_flash_fwd_doc", "usp_flash_bwd_doc")
 SPAN_EXPORTS = ("usp_flash_fwd_span", "usp_flash_bwd_span")
 BSP_EXPORTS = ("usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp")
+MAXL_EXPORTS = ("usp_flash_fwd_maxlogit", "usp_row_max_reduce")
 
 
 def lib_path() -> str:
@@ -145,7 +148,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -559,7 +562,9 @@ def _feature_entries():
             "usp_block_lists_build": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)",
                                       [vp, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp]),
             "usp_flash_fwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [fwd, vp, i64, i64, i64, vp, vp]),
-            "usp_flash_bwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [bwd, vp, i64, i64, i64, vp, vp])}
+            "usp_flash_bwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [bwd, vp, i64, i64, i64, vp, vp]),
+            "usp_flash_fwd_maxlogit": (USP_ATTN_MAX_LOGIT, "return_max_logits (USP_ATTN_MAX_LOGIT)", [fwd, vp, i64, i64, vp]),
+            "usp_row_max_reduce": (USP_ATTN_MAX_LOGIT, "return_max_logits (USP_ATTN_MAX_LOGIT)", [i32, i32, i32, vp, i64, i64, vp, i32, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -579,7 +584,7 @@ def _feature_entry(name: str):
     return fn
 
 
-_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _feature_entry      # (the names the per-feature tests call it by)
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):
@@ -609,10 +614,16 @@ def _shift(shift) -> Optional[int]:
     return s
 
 
-def _flash_call(which: str, a, al, dr, sk, dc, sp=None):
+def _flash_call(which: str, a, al, dr, sk, dc, sp=None, mx=None):
     """Issues the flash launch `which` ("fwd" | "bwd") of the filled argument block `a` with the decoded extras (alibi_value,
     dropout_args, sinks_value, doc_value, span_value; None = off): through the entry point of the one that is on -- two of them
-    are refused (kernels/features.py) -- or the plain one."""
+    are refused (kernels/features.py) -- or the plain one.  `mx`: the forward's buffer of row maxima (row_max_value), which goes
+    with none of the others."""
+    if mx is not None:
+        _maxl_alone(alibi=al, dropout=dr, sinks=sk, doc=dc, span=sp)
+        name = "usp_flash_fwd_maxlogit"
+        _check(_feature_entry(name)(ctypes.byref(a), *mx, _stream()), name)
+        return
     if sp is not None:
         from .kernels.features import Features
         from .kernels.features import SPAN_ON
@@ -686,7 +697,7 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None):
+              alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None, row_max=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
@@ -710,10 +721,16 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     (usp_flash_fwd_span; causal=False only; served uncut; not with doc or anything doc refuses).
     `bsp`: a torch.bool block mask (block_mask_value) of this launch's BLOCK_MASK_SIZE-square blocks, None = off: row i sees key j
     only if bsp[b, h, i // 128, j // 128] (usp_flash_fwd_bsp; Sq == Sk; served uncut; not with any other option above but causal).  `bsp_lists`: the scratch of its lists
-    (block_list_bytes, block_list_layout; None: allocated here)."""
-    _require_cuda(q, k, v, lse, out, acc)
+    (block_list_bytes, block_list_layout; None: allocated here).
+    `row_max`: an fp32 (B, Hq, Sq) device tensor with unit seq stride (row_max_value), None = off: receives the largest visible
+    softmax_scale * q.k of every row, -inf where a row sees nothing; with merge_in the maximum with the value there
+    (usp_flash_fwd_maxlogit; served uncut, k_splits ignored; goes with window and shift alone; not with family="row64")."""
+    _require_cuda(q, k, v, lse, out, acc, row_max)
     B, Sq, Hq, D = q.shape
+    mx = row_max_value(row_max, B, Hq, Sq, q.device)
     bm = block_mask_value(bsp, B, Hq, Sq, q.device)
+    if mx is not None:
+        _maxl_alone(softcap=softcap_value(softcap), bsp=bm)
     if bm is not None:
         _bsp_alone(window=_window(window), softcap=softcap_value(softcap), shift=_shift(shift), alibi=alibi, dropout=dropout_args(dropout),
                    sinks=sinks, doc=doc_value(doc, B, Sq, k.shape[1], q.device), span=span_value(span, B, Sq, k.shape[1], q.device))
@@ -727,7 +744,7 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     dc = doc_value(doc, B, Sq, k.shape[1], q.device)     # None: off -- (None, None) included, which is the call without the keyword
     sp = span_value(span, B, Sq, k.shape[1], q.device)   # None: off, likewise
     if k_splits is None:
-        n = 0 if (sh is not None or dc is not None or sp is not None) else fwd_k_splits(B, Sq, Hq, causal)   # (a document launch is served uncut)
+        n = 0 if (sh is not None or dc is not None or sp is not None or mx is not None) else fwd_k_splits(B, Sq, Hq, causal)   # (a document or max-logit launch is served uncut)
     else:
         n = int(k_splits)
     a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
@@ -745,7 +762,44 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
-    _flash_call("fwd", a, al, dr, sk, dc, sp)
+    _flash_call("fwd", a, al, dr, sk, dc, sp, mx)
+
+
+def _maxl_alone(**others):
+    """A max-logit launch takes no other option but a window and a shift: the entry point has no second extra."""
+    for name, value in others.items():
+        if value is not None:
+            raise NotImplementedError(f"row_max together with {name} is not supported by the HIP attention kernels")
+
+
+def row_max_value(row_max, B: int, Hq: int, Sq: int, device):
+    """A `row_max` argument -> (pointer, batch stride, head stride) as usp_flash_fwd_maxlogit / usp_row_max_reduce take it, or None
+    when it is off."""
+    if row_max is None:
+        return None
+    if not isinstance(row_max, torch.Tensor) or row_max.dtype != torch.float32:
+        raise ValueError("row_max must be a float32 torch.Tensor")
+    if tuple(row_max.shape) != (B, Hq, Sq):
+        raise ValueError(f"row_max must have shape ({B}, {Hq}, {Sq}): one value per (batch, query head, row), got {tuple(row_max.shape)}")
+    if row_max.device != torch.device(device):
+        raise ValueError(f"row_max is on {row_max.device}, the operands on {device}")
+    return _lse3(row_max)
+
+
+def row_max_reduce(row_max, out=None, accum: bool = False):
+    """usp_row_max_reduce: out[h] = max_{b,i} row_max[b,h,i] (with `accum`: and of out[h]) of an fp32 (B,H,S) tensor with unit seq
+    stride.  `out`: an fp32 contiguous (H,) buffer (None: a new one).  Returns it.  Exact, deterministic, no host read."""
+    _require_cuda(row_max, out)
+    B, H, S = row_max.shape
+    mx = row_max_value(row_max, B, H, S, row_max.device)
+    if out is None:
+        if accum:
+            raise ValueError("row_max_reduce: accum needs the buffer to take the maximum with")
+        out = torch.empty(H, dtype=torch.float32, device=row_max.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (H,) or not out.is_contiguous():
+        raise ValueError("row_max_reduce: out must be a contiguous float32 (H,) tensor")
+    _check(_feature_entry("usp_row_max_reduce")(B, S, H, *mx, _ptr(out), 1 if accum else 0, _stream()), "usp_row_max_reduce")
+    return out
 
 
 def _bsp_alone(**others):

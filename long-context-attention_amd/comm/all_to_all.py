@@ -140,6 +140,18 @@ def local_sinks(sinks, H: int, P: int, rank: int):
                      f"got {tuple(sinks.shape)}")
 
 
+def layer_max_logits(max_logits: Tensor, H: int, P: int, rank: int) -> Tensor:
+    """The share of ulysses rank `rank` in the max logits of an H-head layer (return_max_logits): fp32 (H,) holding the maxima of
+    the heads the rank holds behind the head-scatter exchange (local_heads) and -inf for the heads other ranks hold, so that the
+    MAX over the sequence-parallel group is the value -- the replication contract of the sinks' gradient with max in the place of
+    sum.  The layers do no all-reduce.  No host read."""
+    if P == 1:
+        return max_logits
+    out = torch.full((H,), float("-inf"), dtype=torch.float32, device=max_logits.device)
+    out[local_heads(H, P, rank)] = max_logits
+    return out
+
+
 def local_block_mask(block_mask, H: int, P: int, rank: int):
     """The block mask of the heads ulysses rank `rank` holds behind the head-scatter exchange of an H-head layer.  One with a
     head dimension over the layer's H heads, (H, nb, nb) or (B, H, nb, nb), is cut to them (local_heads: a view, no copy); one

@@ -225,9 +225,37 @@ __global__ __launch_bounds__(kSinkThreads) void sink_bwd_kernel(const float* sin
   if (tid == 0) dsinks[h] = accum ? dsinks[h] - part[0] : -part[0];
 }
 
+// ---- out[h] = max_{b,i} row_max[b,h,i]  (accum: ... and of out[h]) -----------------------------------------------------------
+// One workgroup per head, as above (B * S * 4 bytes to read): thread t takes the maximum of the entries t, t + 1024, ... of every
+// batch, then a fixed LDS tree.  A maximum does not depend on the order, so the result is exact; no atomics.
+__global__ __launch_bounds__(kSinkThreads) void row_max_reduce_kernel(const float* row_max, int64_t r_sb, int64_t r_sh, float* out,
+                                                                      int B, int S, int accum) {
+  __shared__ float part[kSinkThreads];
+  const int h = blockIdx.x, tid = threadIdx.x;
+  float mx = USP_NEG_INF;
+  for (int b = 0; b < B; ++b) {
+    const float* rp = row_max + b * r_sb + h * r_sh;
+    for (int i = tid; i < S; i += kSinkThreads) mx = fmaxf(mx, rp[i]);
+  }
+  part[tid] = mx;
+  for (int st = kSinkThreads / 2; st > 0; st >>= 1) {
+    __syncthreads();
+    if (tid < st) part[tid] = fmaxf(part[tid], part[tid + st]);
+  }
+  if (tid == 0) out[h] = accum ? fmaxf(out[h], part[0]) : part[0];
+}
+
 }  // namespace usp
 
 using namespace usp;
+
+extern "C" int usp_row_max_reduce(int32_t B, int32_t S, int32_t H, const float* row_max, int64_t r_sb, int64_t r_sh, float* out,
+                                  int32_t accum, void* stream) {
+  if (!row_max || !out || B <= 0 || S <= 0 || H <= 0 || r_sb < 0 || r_sh < 0) return USP_EINVAL;
+  hipLaunchKernelGGL(row_max_reduce_kernel, dim3(H), dim3(kSinkThreads), 0, (hipStream_t)stream, row_max, r_sb, r_sh, out, (int)B,
+                     (int)S, accum ? 1 : 0);
+  return launched();
+}
 
 extern "C" int usp_sink_bwd(int32_t B, int32_t S, int32_t H, const float* sinks, const float* lse, int64_t l_sb, int64_t l_sh,
                             const float* delta, int64_t d_sb, int64_t d_sh, float* dsinks, int32_t accum, void* stream) {
@@ -382,7 +410,7 @@ extern "C" int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32
 }
 
 extern "C" int usp_abi_version(void) { return USP_ABI_VERSION; }
-extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK; }
+extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT; }
 
 // What the calling thread's last flash call launched (include/usp_hip.h: usp_last_launch_kinds).  Thread-local: the entry
 // points share no mutable state.

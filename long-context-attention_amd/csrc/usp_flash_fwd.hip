@@ -153,7 +153,8 @@ struct FwdExtras {
   FwdSpan span{};                // (usp_flash_fwd_span: with row_hi, a NULL doc.row_lo is all zero)
   BspCall bsp{};                 // (usp_flash_fwd_bsp: the block mask and the workspace of its lists)
   Dropout dr{};
-  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo || span.row_hi || bsp.mask; }
+  FwdMaxl mx{};                  // (usp_flash_fwd_maxlogit: the buffer of row maxima and its strides)
+  bool any() const { return al.al_slopes || dr.t || sinks || doc.row_lo || span.row_hi || bsp.mask || mx.row_max; }
 };
 
 template <int D, int DT, int NWAVES>
@@ -181,6 +182,11 @@ static int launch_fwd_w(FwdArgsSC p, const FwdExtras& x, bool causal, hipStream_
     static_cast<FwdArgsT<true>&>(pk) = ps;
     pk.sinks = x.sinks;
     if (int rc = launch_fwd_sink(pk, D, DT, causal, NWAVES, grid, lds, st)) return rc;
+  } else if (x.mx.row_max) {                                 // max logits: likewise (usp_flash_fwd_maxl.hip)
+    FwdArgsMX pm;
+    static_cast<FwdArgsT<true>&>(pm) = ps;
+    static_cast<FwdMaxl&>(pm) = x.mx;
+    if (int rc = launch_fwd_maxl(pm, D, DT, causal, NWAVES, grid, lds, st)) return rc;
   } else if (x.bsp.mask) {                                   // block-sparse mask: likewise (usp_flash_fwd_bsp.hip), 4 waves only
     if constexpr (NWAVES == 4) {                             // (launch_fwd picks 4 waves under the mask: p.nq counts mask row blocks)
       const BlockLists& bl = x.bsp.layout;
@@ -278,7 +284,7 @@ extern "C" int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* a, int32_t 
 }
 
 // usp_flash_fwd (alibi_slopes == NULL, p_drop == 0, sinks == NULL, row_lo == NULL), usp_flash_fwd_alibi, usp_flash_fwd_dropout,
-// usp_flash_fwd_sink, usp_flash_fwd_doc and usp_flash_fwd_span
+// usp_flash_fwd_sink, usp_flash_fwd_maxlogit, usp_flash_fwd_doc and usp_flash_fwd_span
 static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream) {
   using namespace usp;
   launch_kinds_reset();
@@ -288,6 +294,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   if (int rc = check_alibi(*a, x.al.al_slopes, x.al.al_sb)) return rc;
   if (int rc = check_dropout(*a, x.dc, &x.dr)) return rc;
   if (int rc = check_sink(*a, x.sinks)) return rc;
+  if (int rc = check_maxl(*a, x.mx.row_max, x.mx.row_max_sb, x.mx.row_max_sh)) return rc;
   // (with row_hi the span's check judges every stride before any decline; it declines all the document's check does)
   if (int rc = check_doc(*a, x.doc.row_lo != nullptr && !x.span.row_hi, x.doc.row_lo_sb, 0)) return rc;
   if (int rc = check_span(*a, x.span.row_hi != nullptr, x.doc.row_lo_sb, x.span.row_hi_sb, 0, 0)) return rc;
@@ -330,7 +337,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo && !x.span.row_hi && !x.bsp.mask) {   // (a document, span or block-sparse launch is served uncut: usp_hip.h)
+  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo && !x.span.row_hi && !x.bsp.mask && !x.mx.row_max) {   // (a document, span, block-sparse or max-logit launch is served uncut: usp_hip.h)
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
     if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
@@ -364,6 +371,13 @@ extern "C" int usp_flash_fwd_dropout(const usp_fwd_args* a, float p_drop, uint64
 extern "C" int usp_flash_fwd_sink(const usp_fwd_args* a, const float* sinks, void* stream) {
   usp::FwdExtras x;
   x.sinks = sinks;
+  return flash_fwd_call(a, x, stream);
+}
+
+extern "C" int usp_flash_fwd_maxlogit(const usp_fwd_args* a, float* row_max, int64_t row_max_stride_b, int64_t row_max_stride_h,
+                                       void* stream) {
+  usp::FwdExtras x;                                                   // row_max == NULL: exactly usp_flash_fwd
+  if (row_max) x.mx = usp::FwdMaxl{row_max, row_max_stride_b, row_max_stride_h};
   return flash_fwd_call(a, x, stream);
 }
 

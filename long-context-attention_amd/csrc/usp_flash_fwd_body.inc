@@ -9,7 +9,16 @@
 // (usp_flash_fwd_bsp.hip) the `if constexpr (BSP)` ones (bsp_lists / bsp_stride; USP_FWD_NO_BSP elsewhere).  The including kernel
 // defines `p_in`, KSPLIT / SC / WIN / AL / DR / SINK / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr` (usp_dropout_rng.h:
 // Dropout), sink_s (fp32 (Hq,) sink logits) and doc_row_lo / doc_sb (int32 row bounds and their batch stride).
+// The max-logit kernel (usp_flash_fwd_maxl.hip) defines USP_FWD_HAS_MAXL, MAXL = true and maxl_row / maxl_sb / maxl_sh (the fp32
+// (B, Hq, Sq) buffer of row maxima and its batch / head strides) and compiles the `if constexpr (MAXL)` steps: a TRUE running
+// row maximum beside the lazily raised reference m_run, written in score units by the epilogue.  Every other kernel gets the
+// switch off right here.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
+#ifndef USP_FWD_HAS_MAXL
+  [[maybe_unused]] constexpr bool MAXL = false;
+  [[maybe_unused]] constexpr float* maxl_row = nullptr;
+  [[maybe_unused]] constexpr int64_t maxl_sb = 0, maxl_sh = 0;
+#endif
   using E = Elem<DT>;
   constexpr int kThreads = 64 * NWAVES;
   constexpr int kBM = 32 * NWAVES;
@@ -341,6 +350,9 @@
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[dj][r] = 0.f;
   float m_run = USP_NEG_INF;   // running row max, raw score units
+  // MAXL: the TRUE maximum of the raw scores this lane has seen of its row (its 32 keys of a pipelined tile, the whole masked tile
+  // maximum of a generic one).  m_run is no substitute: the pipelined loop raises it lazily (up to kThr / c below the maximum).
+  [[maybe_unused]] float m_true = USP_NEG_INF;
   float l_run = 0.f;           // this lane's share of the row sum
   const float c = (SC || AL) ? 1.f : p.scale_log2;   // softcap, ALiBi: the scores arrive capped / biased and in exp2 units
   // ALiBi: -slope * log2(e) of this item's (batch, head), read per item: the persistent walk and the K cuts of a tile change it
@@ -370,6 +382,7 @@
 #pragma unroll
     for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s1[r]);
     mt = xhalf_max(mt);
+    if constexpr (MAXL) m_true = fmaxf(m_true, mt);         // behind the mask: a hidden key is -inf here
     const float m_new = fmaxf(m_run, mt);
     const float m_use = (m_new == USP_NEG_INF) ? 0.f : m_new;
     const float mc = m_use * c;
@@ -620,6 +633,9 @@
     // row max itself, behind the mask.  Raising the reference to the score of a key the row must not see costs no
     // correctness but, in fp16, the precision of every visible P (a masked score 20 above the visible ones leaves them
     // subnormal: `out` off by 5e-3 with lse exact; tests/test_gpu_needle.py, wave4-d64-fp16) -- so that tile decides nothing.
+    // MAXL: for the same reason that tile is not folded here -- a key the row must not see would be reported; the tail's softmax
+    // folds its masked maximum.  Every tile before it belongs to the main loop: one v_max each.
+    if constexpr (MAXL) { if (jj + 1 < n_main) m_true = fmaxf(m_true, mt); }
     if (!keep && jj + 1 < n_main) rescale(mt);
     dma_drain();                 // this wave's pieces of K(jj+2), V(jj+1) have landed ...
     __syncthreads();             // ... and so have everybody else's
@@ -631,6 +647,7 @@
     for (int r = 1; r < 16; ++r) mt = fmaxf(mt, sa[r]);
 #pragma unroll
     for (int r = 0; r < 16; ++r) mt = fmaxf(mt, sb[r]);
+    if constexpr (MAXL) m_true = mt;                        // tile 0 is a main-loop tile here (n_main > 0): unmasked, and the first
     if (!__all(mt <= m_thr)) rescale(mt);
     f32x16 ta, tb;
     for (; j + 1 < n_main; j += 2) {
@@ -706,6 +723,16 @@
   const bool fin = row >= p.final_begin && row < p.final_end;
   // single-pass call whose 32 rows are all final and 16-byte aligned: straight-line widened stores
   const bool wide = !p.merge_in && p.out_wide && __all(!valid || fin);
+  if constexpr (MAXL) {
+    // The two half-waves hold the maxima of complementary keys of the row; -inf (a row that saw nothing) stays -inf.  Row-local
+    // and position-free, the value travels with lse: the launch that opens the rows' state writes it, a merging launch takes the
+    // maximum with what is there.  One lane per row, a plain vector store.
+    const float row_maxl = xhalf_max(m_true) * p.scale;
+    if (valid && hi == 0) {
+      float* const rp = maxl_row + b * maxl_sb + h * maxl_sh + row;
+      *rp = p.merge_in ? fmaxf(*rp, row_maxl) : row_maxl;
+    }
+  }
   if (valid) {
     if (p.merge_in) {
       const float old = *lse_p;

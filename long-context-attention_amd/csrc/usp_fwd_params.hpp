@@ -105,6 +105,15 @@ struct FwdArgsBSP : FwdArgsT<false>, FwdBsp {};
   [[maybe_unused]] constexpr bool BSP = false;                   \
   [[maybe_unused]] constexpr const int* bsp_lists = nullptr;     \
   [[maybe_unused]] constexpr int bsp_stride = 0;
+// Max logits (usp_flash_fwd_maxlogit): kernel arguments of the max-logit instantiations only (usp_flash_fwd_maxl.hip:
+// flash_fwd_maxl_kernel, the plain and window kernels' tile loops with a true row maximum kept beside the lazy reference); every
+// other kernel keeps its argument block and machine code.
+struct FwdMaxl {
+  float* row_max;                       // fp32 (B, Hq, Sq), seq stride 1: max over the keys row i sees of softmax_scale * q_i . k_j
+  int64_t row_max_sb, row_max_sh;       // batch and head strides in elements
+};
+struct FwdArgsMX : FwdArgsT<true>, FwdMaxl {};
+struct FwdArgsMXP : FwdArgsT<false>, FwdMaxl {};      // ... of the max-logit kernels on the plain (unsplit) argument block
 
 constexpr int kBN = 64;    // keys per KV tile
 
@@ -133,5 +142,7 @@ int launch_fwd_doc(const FwdArgsDOC& p, int D, int dtype, bool causal, int waves
 int launch_fwd_span(const FwdArgsSPAN& p, int D, int dtype, int waves, int grid, size_t lds, hipStream_t st);
 // The block-sparse forward (usp_flash_fwd_bsp.hip), likewise; always the 4-wave shape: one work item is one 128-row mask block.
 int launch_fwd_bsp(const FwdArgsBSP& p, int D, int dtype, bool causal, int grid, size_t lds, hipStream_t st);
+// The max-logit forward (usp_flash_fwd_maxl.hip), likewise; p.win_on picks the window form, else the plain one (p.ksplit is 1).
+int launch_fwd_maxl(const FwdArgsMX& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st);
 
 }  // namespace usp

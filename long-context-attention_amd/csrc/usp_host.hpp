@@ -148,6 +148,13 @@ inline int check_sink(const usp_fwd_args& a, const float* sinks) {
   return check_extras(a);
 }
 
+// Max logits (usp_flash_fwd_maxlogit).  NULL row_max: the call is usp_flash_fwd, whatever the strides.
+inline int check_maxl(const usp_fwd_args& a, const float* row_max, int64_t stride_b, int64_t stride_h) {
+  if (!row_max) return USP_OK;
+  if (stride_b < 0 || stride_h < 0 || !aligned(row_max, 4)) return USP_EINVAL;
+  return check_extras(a);
+}
+
 // Document mask (usp_flash_fwd_doc / usp_flash_bwd_doc).  No array: the call is usp_flash_fwd / usp_flash_bwd, whatever the strides.
 template <class Args> int check_doc(const Args& a, bool has_doc, int64_t row_lo_stride_b, int64_t key_hi_stride_b) {
   if (!has_doc) return USP_OK;

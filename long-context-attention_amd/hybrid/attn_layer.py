@@ -15,11 +15,11 @@ import torch.distributed as dist
 from torch import Tensor
 
 from .._C import dropout_value, softcap_value
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, local_options
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_replicas, layer_max_logits, local_options
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..kernels.features import block_mask_alone
+from ..kernels.features import block_mask_alone, max_logits_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -77,6 +77,13 @@ class _USPLayer(torch.nn.Module):
         docs = doc_blocks.parse_plan(cu_doclens, bidirectional, batch, self.ulysses_size * self.ring_size * local_len)
         return None if docs is doc_blocks.SINGLE else docs
 
+    def _max_logits(self, result, heads: int):
+        """This rank's share of the layer's max logits from the ring function's result (its last element: the ring's share, the
+        rows of this ring rank, over the heads this Ulysses rank holds): fp32 (heads,), -inf for the heads other Ulysses ranks
+        hold (comm/all_to_all.py: layer_max_logits).  The MAX over the sequence-parallel group is the value; no all-reduce here."""
+        P = self.ulysses_size
+        return layer_max_logits(result[-1], heads, P, dist.get_rank(self.ulysses_pg) if P > 1 else 0)
+
     def _ring_options(self, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                       return_attn_probs):
         return dict(dropout_p=dropout_p, softmax_scale=softmax_scale, causal=causal, window_size=window_size,
@@ -131,7 +138,7 @@ class LongContextAttention(_USPLayer):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                 deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None,
-                bidirectional=None, block_mask=None) -> Tensor:
+                bidirectional=None, block_mask=None, return_max_logits=False) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
         layer, (head_cnt,) fp32 or the operands' type (comm/all_to_all.py: local_options: the gradient contract).  `cu_doclens` (keyword
@@ -145,18 +152,23 @@ class LongContextAttention(_USPLayer):
         rank, (nb, nb), (head_cnt, nb, nb) or (bs, head_cnt, nb, nb) (or over the local heads): global row i sees global key j iff
         block_mask[b, h, i // 128, j // 128] and (not causal or j <= i).  Never read on the host; not together with any other
         option.  Served with the basic ring at any ring degree (a local length that is a multiple of 128), with the zigzag and
-        stripe rings at ring degree 1, through three exchanges.  None: exactly the call without it."""
+        stripe rings at ring degree 1, through three exchanges.  None: exactly the call without it.
+        `return_max_logits` (keyword only; beside window_size alone): the result is (context, max_logits), max_logits fp32
+        (head_cnt,) without gradient: this rank's SHARE of the largest visible pre-softmax logit of every head -- its rows of the
+        ring, the heads it holds under Ulysses, -inf for the heads other ranks hold.  The MAX over the sequence-parallel group is
+        the value (QK-clip takes it); the layer does no all-reduce and reads nothing on the host.  Through three exchanges."""
+        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
                                causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask)
-            return out[..., :D]
+                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml)
+            return (out[0][..., :D], out[1]) if ml else out[..., :D]
         cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1], bidirectional)     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
         if ng_cap is not None and (block_mask is not None or cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
-                                   or dropout_value(dropout_p) is not None or sinks is not None):
+                                   or dropout_value(dropout_p) is not None or sinks is not None or ml):
             # Any of them: the reference's structure (three exchanges), and the ring function serves it (ring/front_end.py: _place).
             # The pipeline issues blocks in row pieces and head groups: under a document mask each piece would need its own
             # arrays; a sliding window is served by the basic ring function at ring degree 1 and, with USP_RING_WINDOW=global,
@@ -173,15 +185,19 @@ class LongContextAttention(_USPLayer):
         options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                                      return_attn_probs)
         options.update(head_kw)
+        if ml:
+            options["return_max_logits"] = True
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
-            return _first(self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options))
+            res = self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options)
+            return (_first(res), self._max_logits(res, query.shape[2])) if ml else _first(res)
         # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
         # form (a KV head shared by several ranks travels to each of them, and their gradients are summed)
         q, k, v = (fn.apply(self.ulysses_pg, t, self.scatter_idx, self.gather_idx, self.use_sync, False)
                    for fn, t in ((SeqAllToAll4D, query), (SeqAllToAll4DKV, key), (SeqAllToAll4DKV, value)))
-        context = _first(self.ring_attn_fn(q, k, v, attn_processor=self.attn_processor, **options))
+        res = self.ring_attn_fn(q, k, v, attn_processor=self.attn_processor, **options)
         # ... and back: (bs, seq_len, heads/N, d) -> (bs, seq_len/N, heads, d)
-        return SeqAllToAll4D.apply(self.ulysses_pg, context, self.gather_idx, self.scatter_idx, self.use_sync, False)
+        context = SeqAllToAll4D.apply(self.ulysses_pg, _first(res), self.gather_idx, self.scatter_idx, self.use_sync, False)
+        return (context, self._max_logits(res, query.shape[2])) if ml else context
 
 
 class LongContextAttentionQKVPacked(_USPLayer):
@@ -197,24 +213,28 @@ class LongContextAttentionQKVPacked(_USPLayer):
 
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None) -> Tensor:
+                *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False) -> Tensor:
+        """`return_max_logits` (keyword only): (out, max_logits) as LongContextAttention.forward returns it."""
+        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = qkv.shape[-1]
         if kernel_head_dim(D) != D:
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                                window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask)
-            return out[..., :D]
+                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml)
+            return (out[0][..., :D], out[1]) if ml else out[..., :D]
         exchange = self.ulysses_size > 1
         cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1], bidirectional)
         head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1,
                                                  block_mask)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
-        out = _first(self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size,
-                                                                  softcap, alibi_slopes, deterministic,
-                                                                  return_attn_probs), **head0))
+        heads = qkv.shape[3] * (self.ulysses_size if exchange else 1)          # (of the layer: qkv holds this rank's by now)
+        res = self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
+                                                          deterministic, return_attn_probs), **head0,
+                                **(dict(return_max_logits=True) if ml else {}))
+        out = _first(res)
         if exchange:         # (bs, seq_len, head_cnt/N, head_size) -> (bs, seq_len/N, head_cnt, head_size)
             out = SeqAllToAll4D.apply(self.ulysses_pg, out, self.gather_idx, self.scatter_idx - 1,
                                       self.use_sync, False)
-        return out
+        return (out, self._max_logits(res, heads)) if ml else out

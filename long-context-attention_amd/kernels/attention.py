@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from .. import _C
-from .features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, expand_block_mask  # noqa: F401
+from .features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, expand_block_mask, max_logits_alone  # noqa: F401
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -80,10 +80,14 @@ class HipBlockBackend:
 
     def fwd(self, q, k, v, softmax_scale, causal, lse, out=None, acc=None, merge_in=False,
             final_begin=0, final_end=None, window=None, k_splits=None, softcap=None, shift=None, alibi=None, dropout=None,
-            sinks=None, doc=None, span=None, bsp=None):
+            sinks=None, doc=None, span=None, bsp=None, row_max=None):
         _C.flash_fwd(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end,
                      interleave=self.interleave, window=window, k_splits=k_splits, softcap=softcap, shift=shift, alibi=alibi,
-                     dropout=dropout, sinks=sinks, doc=doc, span=span, bsp=bsp)
+                     dropout=dropout, sinks=sinks, doc=doc, span=span, bsp=bsp, row_max=row_max)
+
+    def row_max_reduce(self, row_max, out=None, accum=False):
+        """(Hq,) fp32: the maximum over batch and rows of the (B, Hq, S) row maxima a `row_max=` forward left (no host read)."""
+        return _C.row_max_reduce(row_max, out=out, accum=accum)
 
     def sink_grad(self, sinks, lse, delta, out=None, accum=False):
         return _C.sink_grad(sinks, lse, delta, out=out, accum=accum)
@@ -190,6 +194,43 @@ class _FeatureBackend:
         return getattr(self._be, name)
 
 
+class RowMaxBackend:
+    """A block backend whose forward launches also leave the rows' largest visible logit (`row_max=`, usp_flash_fwd_maxlogit), for
+    the schedules that run under return_max_logits.  The row maximum is row-local and position-free and travels wherever lse
+    travels -- so it is kept in a SHADOW of the lse's storage: whatever view of its lse a schedule hands a launch (all rows, the
+    zigzag ring's `rows c:`, a row piece), the launch gets the same view of the shadow.  The launch that opens a row range writes
+    it (merge_in off), a merging one takes the maximum, exactly as the kernels treat lse; a merge outside the kernels (`merge`)
+    combines the maxima of its two lse's likewise.  `max_logits(lse)` reduces the shadow of a whole (B, Hq, S) lse to fp32 (Hq,),
+    once, at the end; nothing is read on the host.  Everything else is the wrapped backend's."""
+
+    def __init__(self, be):
+        self._be, self._shadows = be, {}
+
+    def _shadow(self, lse):
+        st = lse.untyped_storage()
+        held = self._shadows.get(st.data_ptr())
+        if held is None:        # (the lse is kept too: its storage cannot be freed and its address reused while the shadow lives)
+            held = self._shadows[st.data_ptr()] = (torch.empty(st.nbytes() // 4, dtype=torch.float32, device=lse.device), lse)
+        return held[0].as_strided(lse.shape, lse.stride(), lse.storage_offset())
+
+    def fwd(self, q, k, v, softmax_scale, causal, lse, *args, **kw):
+        self._be.fwd(q, k, v, softmax_scale, causal, lse, *args, row_max=self._shadow(lse), **kw)
+
+    def merge(self, acc, lse, blk_out, blk_lse, first):
+        self._be.merge(acc, lse, blk_out, blk_lse, first)
+        mine, blk = self._shadow(lse), self._shadow(blk_lse)
+        if first:
+            mine.copy_(blk)
+        else:
+            torch.maximum(mine, blk, out=mine)
+
+    def max_logits(self, lse):
+        return self._be.row_max_reduce(self._shadow(lse))
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+
 def draw_seed() -> int:
     """The seed of one call with dropout: one 63-bit draw from torch's default CPU generator -- host side, no device sync,
     reproducible under torch.manual_seed, advancing with every call.  Drawn in the autograd forward, kept on ctx and reused by the
@@ -290,7 +331,7 @@ def block_mask_of(block_mask, q, k):
 
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                      softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
-                     bidirectional=None, block_mask=None):
+                     bidirectional=None, block_mask=None, return_max_logits=False):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -311,7 +352,24 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     row i sees key j iff block_mask[b, h, i // 128, j // 128] and (not causal or j <= i); under causal the bits above the diagonal
     are ignored.  It is never read on the host (it may come from a kernel on the same stream) and gets no gradient.  Needs
     equally long q and k; not together with any of window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
-    bidirectional.  None: exactly the call without it."""
+    bidirectional.  None: exactly the call without it.
+    `return_max_logits` (keyword only): the result is (out, lse, max_logits), max_logits an fp32 (Hq,) device tensor without
+    gradient: max over batch, rows i and the keys j row i sees of softmax_scale * q_i . k_j, in score units, -inf for a head whose
+    rows see nothing (include/usp_hip.h: usp_flash_fwd_maxlogit; nothing is read on the host).  out and lse are those of the call
+    without it on the two-waves-per-SIMD kernels.  Goes with window_size alone.  False: exactly the call without it."""
+    if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask):
+        B, Sq, Hq, D = q.shape
+        scale = _default_scale(q, softmax_scale)
+        if kernel_head_dim(D) != D:                 # zero padding changes no score
+            out, lse, ml = hip_attn_forward(*pad_head_dim(q, k, v), softmax_scale=scale, causal=causal, window_size=window_size,
+                                            return_max_logits=True)
+            return out[..., :D].contiguous(), lse, ml
+        out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        row_max = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        be = get_block_backend()
+        be.fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size), row_max=row_max)
+        return out, lse, be.row_max_reduce(row_max)
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         block_mask_of(block_mask, q, k)
         B, Sq, Hq, D = q.shape
@@ -394,24 +452,25 @@ class _HipAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None,
-                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None, block_mask=None):
+                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None, block_mask=None, return_max_logits=False):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
         # dropout: one seed per call, drawn here, kept for the backward (draw_seed); the block is the whole sequence
         ctx.dropout_p = _C.dropout_value(dropout_p) or 0.0
         ctx.rng_state = (draw_seed(), 0, 0, int(dropout_head0)) if ctx.dropout_p else None
-        out, lse = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
-                                    softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks,
-                                    cu_doclens=cu_doclens, block_mask=block_mask)
+        out, lse, *ml = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
+                                         softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks,
+                                         cu_doclens=cu_doclens, block_mask=block_mask, return_max_logits=return_max_logits)
         ctx.cu_doclens = cu_doclens
         ctx.block_mask = block_mask                # (no gradient; the backward rebuilds its lists from it, on the device)
         ctx.has_sinks = sinks is not None          # (never beside slopes: the one optional saved tensor is either)
         ctx.save_for_backward(q, k, v, out, lse, *(() if alibi_slopes is None else (alibi_slopes,)),
                               *(() if sinks is None else (sinks,)))                                     # (slopes: no gradient,
         ctx.scale, ctx.causal, ctx.window_size, ctx.softcap = scale, bool(causal), window_size, softcap   # as in flash-attn)
-        if return_lse:
-            ctx.mark_non_differentiable(lse)
-            return out, lse
+        extra = ((lse,) if return_lse else ()) + tuple(ml)     # (ml: the max logits, a statistic the backward never sees)
+        if extra:
+            ctx.mark_non_differentiable(*extra)
+            return (out,) + extra
         return out
 
     @staticmethod
@@ -425,12 +484,13 @@ class _HipAttnFunc(torch.autograd.Function):
                           dsinks=dsinks, cu_doclens=ctx.cu_doclens, block_mask=ctx.block_mask)
         if dsinks is not None:
             dsinks = dsinks.to(sinks.dtype) if ctx.needs_input_grad[11] else None
-        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None, None, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                  *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, **kwargs):
+                  *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False,
+                  **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -443,7 +503,18 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     `cu_doclens` (keyword only): the document mask of a packed sequence (hip_attn_forward), padded head dims included.
     `bidirectional` (keyword only): bidirectional spans beside or without it (hip_attn_forward), likewise; parsed here once, the
     plan travels on as `cu_doclens`.
-    `block_mask` (keyword only): a 128 x 128 block mask (hip_attn_forward), padded head dims included; no gradient."""
+    `block_mask` (keyword only): a 128 x 128 block mask (hip_attn_forward), padded head dims included; no gradient.
+    `return_max_logits` (keyword only): the result becomes `(out, max_logits)`, with return_attn_probs `(out, softmax_lse, None,
+    max_logits)`: the fp32 (Hq,) per-head maximum of the visible pre-softmax logits (hip_attn_forward), padded head dims
+    included; no gradient, never read on the host.  `out` and the gradients are those of the call without it.  Goes with
+    window_size alone."""
+    if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask):
+        D = q.shape[-1]
+        scale = _default_scale(q, softmax_scale)                 # (of the unpadded head dim)
+        res = _HipAttnFunc.apply(*pad_head_dim(q, k, v), scale, causal, bool(return_attn_probs), window_size, None, None, 0.0, 0,
+                                 None, None, None, True)
+        out = res[0] if kernel_head_dim(D) == D else res[0][..., :D]
+        return (out, res[1], None, res[2]) if return_attn_probs else (out, res[1])
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         block_mask_of(block_mask, q, k)
         D = q.shape[-1]

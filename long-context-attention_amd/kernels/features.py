@@ -3,7 +3,8 @@ record, and the ONE table of which of them the kernels serve together.  `bidirec
 together with cu_doclens and RIDES INSIDE the parsed document plan (ring/doc_blocks.py: Spans), so the record keeps its six
 fields and every positional construction its meaning; a `doc` that carries spans is named "bidirectional" in the refusals.
 `block_mask` (a 128 x 128 block mask) is no field either: it goes with none of the seven and is judged in one place, before the
-record is made (block_mask_alone).  Pure argument logic: nothing here loads the library,
+record is made (block_mask_alone).  `return_max_logits` (an extra RESULT, the largest visible logit of every head) likewise: it
+goes with window_size alone (max_logits_alone).  Pure argument logic: nothing here loads the library,
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
@@ -46,6 +47,21 @@ def block_mask_alone(block_mask, window_size=None, softcap=None, alibi_slopes=No
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"block_mask together with {name} is not supported by the HIP attention kernels")
+    return True
+
+
+def max_logits_alone(return_max_logits, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
+                     bidirectional=None, block_mask=None) -> bool:
+    """Is `return_max_logits` on?  Like block_mask it is no field of the record: it is judged HERE, before Features.of and before
+    any tensor is read.  It goes with window_size and nothing else -- the max-logit kernels hold no second mask or score-level
+    step.  False / None is exactly the call without the keyword."""
+    if not return_max_logits:
+        return False
+    given = (("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes), ("dropout_p", dropout_value(dropout_p)),
+             ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional), ("block_mask", block_mask))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"return_max_logits together with {name} is not supported by the HIP attention kernels")
     return True
 
 

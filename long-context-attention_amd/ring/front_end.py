@@ -9,7 +9,7 @@ import torch.distributed as dist
 from .._C import dropout_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
-from ..kernels.features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention
+from ..kernels.features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, max_logits_alone
 from .utils import group_info
 from .varlen_utils import unflatten_lse
 
@@ -47,12 +47,14 @@ class RingServes(NamedTuple):
     span: int = NOT_SERVED        # bidirectional spans: they ride inside the parsed `cu_doclens` plan (ring/doc_blocks.py: Spans)
     block_mask: int = NOT_SERVED  # a 128 x 128 block mask: it rides in the `cu_doclens` slot as a BlockMask (below); ANY_DEGREE:
                                   # the ring's forward / backward hand every (rank, step) launch its view of it (`bsp=`)
+    max_logits: int = NOT_SERVED  # return_max_logits: row-local and position-free like the sinks, so ANY_DEGREE or not at all; the
+                                  # ring's forward takes `max_logits=True` and returns (out, lse, this rank's share fp32 (Hq,))
 
 
 PACKED_RING = RingServes()
 DENSE_RING = RingServes(alibi=ONE_BLOCK, dropout=ONE_BLOCK, sinks=ANY_DEGREE, doc=ONE_BLOCK, span=ONE_BLOCK,
-                        block_mask=ONE_BLOCK)                                                                      # zigzag, stripe
-BASIC_RING = RingServes(*(ANY_DEGREE,) * 7)
+                        block_mask=ONE_BLOCK, max_logits=ANY_DEGREE)                                                                    # zigzag, stripe
+BASIC_RING = RingServes(*(ANY_DEGREE,) * 8)
 
 # feature -> (its name in the refusals, what the packed rings advise, what a ONE_BLOCK ring advises beyond ring degree 1)
 _BASIC = "use the basic ring (ring_impl_type=\"basic\", ring_flash_attn_func)"
@@ -129,6 +131,12 @@ def _refuse_packed_block_mask(block_mask):
     if block_mask is not None:
         raise NotImplementedError("block_mask is not supported by the variable-length (packed) rings: use LongContextAttention "
                                   "(ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches")
+
+
+def _refuse_packed_max_logits(return_max_logits):
+    if return_max_logits:
+        raise NotImplementedError("return_max_logits is not supported by the variable-length (packed) rings: use a dense ring "
+                                  "(ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)")
 
 
 def block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
@@ -229,7 +237,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         attn_processor     the Function carries `attn_processor` to the forward (the basic ring).
     The dense <stem>_func pads head dims the kernels do not instantiate and skips the autograd node when nothing requires
     grad; both exist here only."""
-    assert ONE_BLOCK not in (serves.window, serves.sinks), f"{class_name}: RingServes has no ONE_BLOCK for window and sinks"
+    assert ONE_BLOCK not in (serves.window, serves.sinks, serves.max_logits), \
+        f"{class_name}: RingServes has no ONE_BLOCK for window, sinks and max_logits"
     n_lead = 2 if packed else 0
     extra = () if packed else (("attn_type", "attn_processor") if attn_processor else ("attn_type",))
     n_args = n_lead + 9 + len(extra)
@@ -243,9 +252,10 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         return (forward, backward) if serves.doc == ANY_DEGREE or docs is None else _basic_ring()
 
     def run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group, extra_kw,
-                    head0=0, sink_t=None, cu_doc=None):
+                    head0=0, sink_t=None, cu_doc=None, max_logits=False):
         """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse, the dropout keywords of the
-        backward)."""
+        backward, this rank's share of the max logits | None).  `max_logits`: judged alone already (max_logits_alone): beside it
+        only a window can be on, which the ring's forward judges or _check_hot_path_args refuses."""
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
         if isinstance(cu_doc, BlockMask):           # (judged alone already: nothing else is on)
@@ -262,40 +272,47 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         if docs is not None:                      # (kept with the backward's keywords: drop_kw is what the backward adds)
             drop_kw = dict(drop_kw, cu_doclens=docs)
         ring_forward = ring_pair(docs)[0]
-        out, lse = ring_forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
-                                window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw,
-                                **drop_kw, **({} if sink_t is None else dict(sinks=sink_t)))
-        return q, k, v, softmax_scale, out, lse, drop_kw
+        out, lse, *ml = ring_forward(group, q, k, v, *lead, softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
+                                     window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes, deterministic=False, **extra_kw,
+                                     **drop_kw, **({} if sink_t is None else dict(sinks=sink_t)),
+                                     **(dict(max_logits=True) if max_logits else {}))
+        return q, k, v, softmax_scale, out, lse, drop_kw, (ml[0] if max_logits else None)
 
-    def result(out, lse, lead, return_softmax):
+    def result(out, lse, lead, return_softmax, ml=None):
+        """`out`, or `(out, lse, None)`; under return_max_logits `(out, max_logits)` or `(out, lse, None, max_logits)`."""
+        tail = () if ml is None else (ml,)
         if not return_softmax:
-            return out
-        return out, (unflatten_lse(lse, *lead) if packed else lse), None
+            return (out,) + tail if tail else out
+        return (out, (unflatten_lse(lse, *lead) if packed else lse), None) + tail
 
     class Func(torch.autograd.Function):
         """forward(ctx, q, k, v, [cu_seqlens, max_seqlen,] dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-        deterministic, return_softmax, group[, attn_type[, attn_processor]][, dropout_head0[, sinks]])"""
+        deterministic, return_softmax, group[, attn_type[, attn_processor]][, dropout_head0[, sinks[, cu_doclens[, max_logits]]]])"""
 
         @staticmethod
         def forward(ctx, q, k, v, *args):
-            assert len(args) in (n_args, n_args + 1, n_args + 2, n_args + 3), \
-                f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0 (+ sinks (+ cu_doclens)))"
+            assert len(args) in (n_args, n_args + 1, n_args + 2, n_args + 3, n_args + 4), \
+                f"{class_name}: {n_args + 3} arguments expected (+ dropout_head0 (+ sinks (+ cu_doclens (+ max_logits))))"
             ctx.n_none = len(args)
             head0 = args[n_args] if len(args) > n_args else 0
             sink_t = args[n_args + 1] if len(args) > n_args + 1 else None
             cu_doc = args[n_args + 2] if len(args) > n_args + 2 else None
+            max_logits = bool(args[n_args + 3]) if len(args) > n_args + 3 else False
             lead, extra_kw = args[:n_lead], dict(zip(extra, args[n_lead + 9:n_args]))
             dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, return_softmax, group = \
                 args[n_lead:n_lead + 9]
-            q, k, v, softmax_scale, out, lse, drop_kw = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size,
-                                                                    softcap, alibi_slopes, group, extra_kw, head0, sink_t, cu_doc)
+            q, k, v, softmax_scale, out, lse, drop_kw, ml = run_forward(q, k, v, lead, dropout_p, softmax_scale, causal, window_size,
+                                                                        softcap, alibi_slopes, group, extra_kw, head0, sink_t, cu_doc,
+                                                                        max_logits)
+            if ml is not None:
+                ctx.mark_non_differentiable(ml)                                   # (a statistic: the backward is untouched)
             ctx.has_sinks = sink_t is not None                                    # (dense rings only: `lead` is then empty)
             ctx.save_for_backward(q, k, v, out, lse, *lead[:1], *(() if sink_t is None else (sink_t,)))   # (cu_seqlens is a tensor)
             extra_kw.pop("attn_processor", None)                                  # (the backwards take none)
             ctx.call = (group, lead[1:], dict(softmax_scale=softmax_scale, dropout_p=dropout_p, causal=causal,
                                               window_size=window_size, softcap=softcap, alibi_slopes=alibi_slopes,
                                               deterministic=deterministic, **extra_kw, **drop_kw))
-            return result(out, lse, lead, return_softmax)
+            return result(out, lse, lead, return_softmax, ml)
 
         @staticmethod
         def backward(ctx, dout, *args):
@@ -314,7 +331,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
-                 cu_doclens=None, bidirectional=None, block_mask=None):
+                 cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False):
+            _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
@@ -323,7 +341,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None):
+                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False):
+            _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
@@ -332,7 +351,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None):
+                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False):
+            _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
@@ -342,7 +362,9 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def last(attn_type, processor=None):      # the Function's trailing arguments
             return (attn_type, processor)[:len(extra)]
 
-        def head0_arg(dropout_head0, sink_t=None, cu_doc=None):    # ... and the optional ones behind them
+        def head0_arg(dropout_head0, sink_t=None, cu_doc=None, max_logits=False):    # ... and the optional ones behind them
+            if max_logits:
+                return (dropout_head0, sink_t, cu_doc, True)
             if cu_doc is not None:
                 return (dropout_head0, sink_t, cu_doc)
             return (dropout_head0, sink_t) if sink_t is not None else ((dropout_head0,) if dropout_head0 else ())
@@ -350,40 +372,43 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                  attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
-                 bidirectional=None, block_mask=None):
+                 bidirectional=None, block_mask=None, return_max_logits=False):
+            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
             cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)       # (the spans travel inside the plan from here on)
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
                 res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                            window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor,
-                           dropout_head0=dropout_head0, sinks=sinks, cu_doclens=cu_doclens)
+                           dropout_head0=dropout_head0, sinks=sinks, cu_doclens=cu_doclens, return_max_logits=ml)
                 return (res[0][..., :D],) + tuple(res[1:]) if isinstance(res, tuple) else res[..., :D]
             if not needs_grad(q, k, v, *(() if sinks is None else (sinks,))):      # inference / forward-only benchmarks: no autograd node, no saved tensors (~25 us)
-                out, lse = run_forward(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group,
-                                       dict(zip(extra, last(attn_type, attn_processor))), dropout_head0, sinks, cu_doclens)[4:6]
-                return result(out, lse, (), return_attn_probs)
+                done = run_forward(q, k, v, (), dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, group,
+                                   dict(zip(extra, last(attn_type, attn_processor))), dropout_head0, sinks, cu_doclens, ml)
+                return result(done[4], done[5], (), return_attn_probs, done[7])
             return Func.apply(q, k, v, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
-                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0, sinks, cu_doclens))
+                              return_attn_probs, group, *last(attn_type, attn_processor), *head0_arg(dropout_head0, sinks, cu_doclens, ml))
 
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
-                          block_mask=None):
+                          block_mask=None, return_max_logits=False):
+            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
             cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks, cu_doclens))
+                              deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks, cu_doclens, ml))
 
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                            attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
-                           block_mask=None):
+                           block_mask=None, return_max_logits=False):
+            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
             cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
             cu_doclens = span_plan(qkv[:, :, 0], group, cu_doclens, bidirectional)
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type),
-                              *head0_arg(dropout_head0, sinks, cu_doclens))
+                              *head0_arg(dropout_head0, sinks, cu_doclens, ml))
 
     for fn, suffix in ((func, "_func"), (kvpacked_func, "_kvpacked_func"), (qkvpacked_func, "_qkvpacked_func")):
         fn.__name__ = fn.__qualname__ = stem + suffix

@@ -39,7 +39,7 @@ import torch
 import torch.distributed as dist
 
 from ..kernels import AttnType
-from ..kernels.attention import get_block_backend, window_of
+from ..kernels.attention import RowMaxBackend, get_block_backend, window_of
 from . import block_pieces, doc_blocks
 from .front_end import BASIC_RING, BlockMask, ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, return_dkdv_direct, travel_dkdv
@@ -151,8 +151,11 @@ def basic_bwd_block(be, r, P, step, causal, dout, q, kk, vv, lse, delta, softmax
 def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                             window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                             attn_type: AttnType = AttnType.HIP, attn_processor=None, overlap=False, first=None, tail=None,
-                            rng_state=None, sinks=None, cu_doclens=None):
+                            rng_state=None, sinks=None, cu_doclens=None, max_logits=False):
     """`cu_doclens`: the parsed document lists of the whole sequence (ring/front_end.py: _place), None = off.
+    `max_logits` (ring/front_end.py: return_max_logits; beside a window alone): the result is (out, lse, max_logits) -- every launch
+    leaves the row maxima where its lse goes (kernels/attention.py: RowMaxBackend) and ONE reduce at the end gives this rank's
+    share, fp32 (Hq,): the maximum over its rows.
     `rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it).  `sinks`: one logit per query head; it rides on
     the launch that opens the rows' state (step 0; the window planner's first block), at any ring degree.  `overlap`, `first`, `tail`: the caller has exchanges of its own in flight (the head-group pipeline), see
     zigzag_ring_flash_attn_forward.  This ring serves `first` and `tail` at ring degree 1 only (ring/block_pieces.py)."""
@@ -167,12 +170,17 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     assert cu_doclens is None or (causal and not pieces and window_of(window_size) is None), "cu_doclens: ring/front_end.py: _place"
     be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=al, dropout=dr, sinks=sinks,
                            doc=cu_doclens)
+    if max_logits:
+        assert not pieces and bm is None and cu_doclens is None and al is None and dr is None and sinks is None, \
+            "return_max_logits: kernels/features.py: max_logits_alone"
+        be = RowMaxBackend(be)
     if pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=dev)
+    done = (lambda: (out, lse, be.max_logits(lse))) if max_logits else (lambda: (out, lse))
     if cu_doclens is not None:       # the document mask: the steps with something visible, each with its own arrays
         assert k.shape[1] == S, "the basic ring holds equally long chunks of q and k"
         call = doc_blocks.ring_call(cu_doclens, S, P, r, dev)
@@ -197,7 +205,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
     win = _ring_window(window_size, P)
     if win is not None and P == 1:   # ring degree 1: one block, the kernels take flash-attn's window (left, right)
         be.fwd(q, k, v, softmax_scale, bool(causal), lse, out, window=win)
-        return out, lse
+        return done()
     assert bm is None or (win is None and k.shape[1] == S), "block_mask: ring/front_end.py"
     if win is not None:              # USP_RING_WINDOW=global: only the blocks the window touches, each with its own bounds
         assert k.shape[1] == S, "the basic ring holds equally long chunks of q and k"
@@ -209,7 +217,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
                 blk = plan.block(step)
                 be.fwd(q, kk, vv, softmax_scale, blk.causal, lse, out, acc, i > 0, 0, S if step == plan.steps[-1] else 0,
                        **_step_launch_kw(al, dr, r, P, step, S, blk.launch_kw()))
-        return out, lse
+        return done()
     last_compute = r if causal else P - 1
     acc = torch.empty((B, S, H, D), dtype=torch.float32, device=dev) if last_compute > 0 else None
     with KVRelay(process_group, k, v) as relay:
@@ -217,7 +225,7 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
             kk, vv = relay.get(step)
             basic_fwd_step(be, r, P, step, causal, q, kk, vv, softmax_scale, lse, out, acc,
                            **_step_launch_kw(al, dr, r, P, step, S), **_bsp_kw(bm, r, P, step, S))
-    return out, lse
+    return done()
 
 
 def ring_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,

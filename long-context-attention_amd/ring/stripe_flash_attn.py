@@ -17,7 +17,7 @@ import torch
 import torch.distributed as dist
 
 from ..kernels import AttnType
-from ..kernels.attention import get_block_backend
+from ..kernels.attention import RowMaxBackend, get_block_backend
 from .front_end import DENSE_RING, ring_dropout, ring_front_end
 from .utils import FULL, KVRelay, group_info, final_grads, travel_dkdv
 
@@ -55,7 +55,7 @@ def stripe_bwd_fold(be, r, step, dk_acc, dv_acc, dk_blk, dv_blk):
 
 def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                               window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                              attn_type: AttnType = AttnType.HIP, overlap=False, rng_state=None, sinks=None):
+                              attn_type: AttnType = AttnType.HIP, overlap=False, rng_state=None, sinks=None, max_logits=False):
     assert causal, "stripe flash attn only supports causal attention, if not causal, use ring flash attn instead"
     P, r = group_info(dist, process_group)
     assert alibi_slopes is None or P == 1, "ALiBi: this ring places one block only (ring/front_end.py: _place)"
@@ -63,6 +63,11 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
     assert dr is None or P == 1, "dropout: this ring places one block only (ring/front_end.py: _place)"
     # `sinks`: one logit per query head, on the launch that opens the rows' state (step 0, every row), at any ring degree
     be = get_block_backend(beside_transfers=P > 1 or overlap, softcap=softcap, alibi=alibi_slopes, dropout=dr, sinks=sinks)
+    # `max_logits` (ring/front_end.py: return_max_logits): (out, lse, max_logits) -- every launch, the `rows 1:` ones included, leaves
+    # the row maxima where its lse goes (kernels/attention.py: RowMaxBackend); one reduce at the end: this rank's rows, fp32 (Hq,)
+    if max_logits:
+        assert alibi_slopes is None and dr is None and sinks is None, "return_max_logits: kernels/features.py: max_logits_alone"
+        be = RowMaxBackend(be)
     B, S, H, D = q.shape
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
@@ -72,7 +77,7 @@ def stripe_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0
         for step in range(P):
             kk, vv = relay.get(step)
             stripe_fwd_step(be, r, P, step, q, kk, vv, softmax_scale, lse, out, acc)
-    return out, lse
+    return (out, lse, be.max_logits(lse)) if max_logits else (out, lse)
 
 
 def stripe_flash_attn_backward(process_group, dout, q, k, v, out, softmax_lse, softmax_scale,

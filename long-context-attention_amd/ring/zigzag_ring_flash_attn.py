@@ -28,7 +28,7 @@ import torch
 import torch.distributed as dist
 
 from ..kernels import AttnType
-from ..kernels.attention import get_block_backend
+from ..kernels.attention import RowMaxBackend, get_block_backend
 from . import block_pieces
 from .front_end import DENSE_RING, _check_hot_path_args, ring_dropout, ring_front_end      # (_check_hot_path_args: still importable from here)
 from .utils import FULL, KVRelay, group_info, ZigzagKVFetch, final_grads, kv_relay_mode, travel_dkdv, zigzag_fetch_pieces
@@ -205,7 +205,7 @@ def _final_rows(be, q, kp, vp, softmax_scale, lse, out, acc, lo, hi, tail):
 
 
 def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, first=None, tail=None, softcap=None, alibi=None,
-                          dropout=None, sinks=None):
+                          dropout=None, sinks=None, max_logits=False):
     """The zigzag ring forward as a generator of two phases.  With `first` beside a ring (degree > 1) it yields ONCE, behind the
     launch on the owned chunk and in front of the wait for the caller's exchange -- the caller may start other head groups' owned
     chunks there -- and returns (out, lse) through StopIteration; otherwise it never yields.  zigzag_ring_flash_attn_forward drives it
@@ -214,13 +214,20 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
     `alibi`: flash-attn's alibi_slopes, served where the ring is ONE block (ring degree 1, no pieces).
     `dropout`: (p, seed, head0), likewise (ring/front_end.py: _place).
     `sinks`: one logit per query head, on the launch that opens the rows' state (step 0, every row), at any ring degree; not with
-    `first` / `tail` (ring/block_pieces.py: refuse_sinks)."""
+    `first` / `tail` (ring/block_pieces.py: refuse_sinks).
+    `max_logits` (ring/front_end.py: return_max_logits): the result is (out, lse, max_logits) -- every launch, the `rows c:` ones
+    included, leaves the row maxima where its lse goes (kernels/attention.py: RowMaxBackend), and ONE reduce at the end gives this
+    rank's share, fp32 (Hq,): the maximum over its rows.  Not with `first` / `tail`."""
     P, r = group_info(dist, process_group)
     pieces = first is not None or tail is not None          # (the caller has exchanges in flight by definition)
     assert alibi is None or (P == 1 and not pieces), "ALiBi: this ring places one block only (ring/front_end.py: _place)"
     assert dropout is None or (P == 1 and not pieces), "dropout: this ring places one block only (ring/front_end.py: _place)"
     block_pieces.refuse_sinks(sinks, pieces)
     be = get_block_backend(beside_transfers=P > 1 or overlap or pieces, softcap=softcap, alibi=alibi, dropout=dropout, sinks=sinks)
+    if max_logits:
+        assert not pieces and alibi is None and dropout is None and sinks is None, "return_max_logits: kernels/features.py: max_logits_alone"
+        be = RowMaxBackend(be)
+    done = (lambda o, l: (o, l, be.max_logits(l))) if max_logits else (lambda o, l: (o, l))
     B, S2, H, D = q.shape
     assert S2 % 2 == 0, "zigzag layout needs an even local sequence length"
     if P == 1 and pieces:
@@ -230,7 +237,7 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
     lse = torch.empty((B, H, S2), dtype=torch.float32, device=dev)
     if P == 1:           # one block, no relay, no running accumulator
         be.fwd(q, k, v, softmax_scale, True, lse, out)
-        return out, lse
+        return done(out, lse)
     acc = torch.empty((B, S2, H, D), dtype=torch.float32, device=dev)
     c = S2 // 2
     if first is not None:
@@ -257,7 +264,7 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
                     be.fwd(q, kp, vp, softmax_scale, False, lse, out, acc, True, 0, fe)
                 else:
                     be.fwd(q[:, c:], kp, vp, softmax_scale, False, lse[:, :, c:], out[:, c:], acc[:, c:], True, 0, fe)
-        return out, lse
+        return done(out, lse)
     with KVRelay(process_group, k, v) as relay:
         for step in range(P):
             kk, vv = relay.get(step)
@@ -270,14 +277,14 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
                     _final_rows(be, q, kk, vv, softmax_scale, lse, out, acc, c, S2, tail)
             else:
                 zigzag_fwd_step(be, r, P, step, q, kk, vv, softmax_scale, lse, out, acc)
-    return out, lse
+    return done(out, lse)
 
 
 def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, causal=True,
                                    window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                                    deterministic=False, attn_type: AttnType = AttnType.HIP, overlap=False, first=None, tail=None,
-                                   rng_state=None, sinks=None):
-    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it; ring degree 1 only).  `sinks`: zigzag_forward_phases.
+                                   rng_state=None, sinks=None, max_logits=False):
+    """`rng_state` = (seed, head0) with dropout_p > 0 (ring/front_end.py draws it; ring degree 1 only).  `sinks`, `max_logits`: zigzag_forward_phases.
     `overlap`: the caller has transfers of its own in flight (pipelined Ulysses exchange), so the kernels are
     launched so that collectives can run beside them even at ring degree 1.
     `first` = (u, (q, k, v) of the owned chunk, wait): q / k / v are still in flight (the caller's Ulysses exchange at degree
@@ -289,7 +296,7 @@ def zigzag_ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropou
     Either one means transfers in flight: the kernels are launched as under `overlap`."""
     assert causal == True, "zigzag ring is meaningless for causal=False"
     gen = zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap, first, tail, softcap, alibi_slopes,
-                                ring_dropout(dropout_p, rng_state), sinks)
+                                ring_dropout(dropout_p, rng_state), sinks, max_logits)
     try:
         while True:
             next(gen)

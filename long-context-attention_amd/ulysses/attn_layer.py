@@ -11,9 +11,9 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
-from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, local_options
+from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, layer_max_logits, local_options
 from ..kernels import AttnType, select_flash_attn_impl
-from ..kernels.features import block_mask_alone
+from ..kernels.features import block_mask_alone, max_logits_alone
 
 
 class UlyssesAttention(torch.nn.Module):
@@ -21,7 +21,10 @@ class UlyssesAttention(torch.nn.Module):
     (1 = sequence), use_sync (synchronise the device after each exchange), attn_type (any dense AttnType).
     forward takes the keyword-only `sinks`: one learned logit per head of the layer, (H,) (or per local head, (H / N,)), fp32 or
     the operands' type, cut to this rank's heads by slicing.  It is a parameter replicated over the group: each rank's gradient
-    holds its own heads and zeros elsewhere, the SUM over the group is the gradient, and the layer does no all-reduce."""
+    holds its own heads and zeros elsewhere, the SUM over the group is the gradient, and the layer does no all-reduce.
+    `return_max_logits` (keyword only; beside window_size alone): the result is (out, max_logits), max_logits fp32 (H,) over the
+    layer's heads without gradient: this rank's SHARE -- the largest visible pre-softmax logit of the heads it holds behind the
+    exchange, -inf for the heads other ranks hold.  The MAX over the group is the value; the layer does no all-reduce."""
 
     def __init__(self, sequence_process_group: dist.ProcessGroup = None, scatter_idx: int = 2,
                  gather_idx: int = 1, use_sync: bool = False, attn_type: AttnType = AttnType.FA) -> None:
@@ -39,7 +42,10 @@ class UlyssesAttention(torch.nn.Module):
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
-                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None) -> Tensor:
+                return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
+                return_max_logits=False) -> Tensor:
+        # `return_max_logits`: judged alone and first (kernels/features.py: max_logits_alone)
+        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
         # `block_mask`: a 128 x 128 block mask of the whole sequence (kernels/attention.py: hip_attn_forward), over the layer's
         # heads (cut to this rank's), the local heads or none; judged alone, before anything else
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
@@ -57,5 +63,8 @@ class UlyssesAttention(torch.nn.Module):
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
                        softmax_scale=q.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale, **head_kw)
-        attended = self.attn_fn(q, k, v, **options)
-        return self._to_seq(attended[0] if isinstance(attended, tuple) else attended)
+        attended = self.attn_fn(q, k, v, **options, **(dict(return_max_logits=True) if ml else {}))
+        out = self._to_seq(attended[0] if isinstance(attended, tuple) else attended)
+        if not ml:
+            return out
+        return out, layer_max_logits(attended[-1], query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
