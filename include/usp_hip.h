@@ -131,6 +131,10 @@ enum {
 /* USP_ATTN_MAX_LOGIT: a FEATURE bit like USP_ATTN_SINK: the library exports usp_flash_fwd_maxlogit / usp_row_max_reduce (below),
  * which return the largest visible pre-softmax logit of every row / head beside the unchanged argument blocks (ABI still v7). */
 #define USP_ATTN_MAX_LOGIT 16384
+/* USP_ATTN_BLOCK_SELECT: a FEATURE bit like USP_ATTN_BLOCK_MASK: the library exports usp_block_means / usp_block_select (below),
+ * which produce a 128 x 128 block mask on the device -- top-k of mean-pooled blocks -- for usp_flash_fwd_bsp / usp_flash_bwd_bsp
+ * (ABI still v7). */
+#define USP_ATTN_BLOCK_SELECT 32768
 
 typedef struct usp_tensor {
   void* ptr;
@@ -536,6 +540,44 @@ int usp_flash_fwd_bsp(const usp_fwd_args* args, const void* mask, int64_t mask_s
 int usp_flash_bwd_bsp(const usp_bwd_args* args, const void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
                       int64_t mask_stride_row, void* lists, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Top-k block selection: the producer of a block mask for usp_flash_fwd_bsp / usp_flash_bwd_bsp, on the same stream.  The MoBA
+ * gate at the kernels' block size: with nb = ceil(S / USP_BLOCK_MASK_SIZE), G = Hq / Hkv,
+ *     qbar[b][I][h] = fp32 mean of the rows of block I of q (a ragged last block: over the rows it has), kbar likewise,
+ *     score[b][h][I][J] = scale * qbar[b][I][h] . kbar[b][J][h / G],
+ * row block I (global index Ig = row_block0 + I) sees the candidates J < nbk, under causal J <= Ig; the FORCED blocks
+ * J < keep_first and Ig - keep_local < J <= Ig (of the visible ones) are always selected, and beside them the best
+ * max(0, top_k - n_forced) of the other visible candidates, by score descending, ties to the lower J: exactly
+ * min(max(top_k, n_forced), n_visible) bytes of a row are set.  EVERY byte of the mask is written (0 or 1), the ones above the
+ * diagonal included.  Nothing is read on the host, there are no atomics, and results leave in ordinary vector stores.  With NaN
+ * or infinite inputs the selection is unspecified; every access stays in range.
+ *
+ * usp_block_means pools a 16-bit (B, S, H, D) tensor `x` (strides in elements, head dim contiguous) into `out`, fp32
+ * (B, nb, H, D) contiguous.  HBM-bound: every element is read once, in 16-byte loads.  A block's 128 rows are added in 8 runs of
+ * 16 rows, each in ascending row order, and the runs in ascending order: the order of every sum is a function of (row, d) alone,
+ * so the result does not depend on B, H, the grid or the workgroup that holds a block.  The last block is divided by its own row
+ * count.  D: any multiple of 8 up to 128.
+ *   - a NULL pointer, a non-positive size, a negative stride or a dtype other than USP_BF16 / USP_FP16 is USP_EINVAL;
+ *   - another D, `x` off a 16-byte boundary or a stride that is no multiple of 8 elements is USP_EUNSUPPORTED.
+ *
+ * usp_block_select takes the means -- qbar fp32 (B, nbq, Hq, D), kbar fp32 (B, nbk, Hkv, D), both contiguous and 16-byte aligned
+ * -- and writes mask[b * mask_stride_b + h * mask_stride_h + I * mask_stride_row + J] for I < nbq, J < nbk (strides in bytes, h the
+ * QUERY head).  On one device nbq = nbk = nb and row_block0 = 0; rank r of a ring of n-block slices pools its own slices,
+ * gathers kbar over the ring and selects its nbq = n rows against all nbk = nb key blocks with row_block0 = r * n.  One
+ * workgroup per (b, h, I): the scores in fp32 (one chain of fused multiply-adds over ascending d), the k-th largest found exactly
+ * on order-preserving integer keys in LDS, ties by a prefix over ascending J.
+ *   - a NULL pointer, a non-positive size, a negative row_block0 / top_k / keep_first / keep_local / stride, a NaN scale, and
+ *     causal != 0 with keep_local < 1 (a row must keep its own block) are USP_EINVAL;
+ *   - D not a multiple of 8 or above 128, Hq % Hkv != 0, qbar / kbar off a 16-byte boundary and nbk > USP_BLOCK_SELECT_MAX_BLOCKS
+ *     (8192 blocks = 1M tokens: the keys of one row live in LDS) are USP_EUNSUPPORTED; nothing is launched or written.
+ * -------------------------------------------------------------------------------------------- */
+#define USP_BLOCK_SELECT_MAX_BLOCKS 8192
+int usp_block_means(const void* x, int32_t dtype, int32_t B, int32_t S, int32_t H, int32_t D, int64_t stride_b, int64_t stride_s,
+                    int64_t stride_h, float* out, void* stream);
+int usp_block_select(const float* qbar, const float* kbar, int32_t B, int32_t Hq, int32_t Hkv, int32_t D, int32_t nbq, int32_t nbk,
+                     int32_t row_block0, float scale, int32_t causal, int32_t top_k, int32_t keep_first, int32_t keep_local,
+                     void* mask, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_row, void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -636,8 +678,9 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
- * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT, the last seven feature
- * bits: the *_alibi / *_dropout / *_sink / *_doc / *_span / *_bsp / *_maxlogit entry points exist).  Unknown flag bits are not rejected by
+ * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT,
+ * the last eight feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span / *_bsp / *_maxlogit / usp_block_means and
+ * usp_block_select entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -35,6 +35,8 @@ USP_ATTN_DOC = 2048            # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_SPAN = 4096           # feature bit of usp_attn_features(): usp_flash_fwd_span / usp_flash_bwd_span exist (not an args flag)
 USP_ATTN_BLOCK_MASK = 8192     # feature bit of usp_attn_features(): usp_block_list_bytes / usp_flash_fwd_bsp / usp_flash_bwd_bsp exist (not an args flag)
 USP_ATTN_MAX_LOGIT = 16384     # feature bit of usp_attn_features(): usp_flash_fwd_maxlogit / usp_row_max_reduce exist (not an args flag)
+USP_ATTN_BLOCK_SELECT = 32768  # feature bit of usp_attn_features(): usp_block_means / usp_block_select exist (not an args flag)
+BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
@@ -119,7 +121,7 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
-           "usp_flash_fwd_maxlogit", "usp_row_max_reduce")
+           "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -130,6 +132,7 @@ DOC_EXPORTS = ("usp_flash_fwd_doc", "usp_flash_bwd_doc")
 SPAN_EXPORTS = ("usp_flash_fwd_span", "usp_flash_bwd_span")
 BSP_EXPORTS = ("usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp")
 MAXL_EXPORTS = ("usp_flash_fwd_maxlogit", "usp_row_max_reduce")
+SELECT_EXPORTS = ("usp_block_means", "usp_block_select")
 
 
 def lib_path() -> str:
@@ -148,7 +151,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -543,6 +546,60 @@ def _bsp_call(which: str, a, bsp, lists=None):
     _check(_feature_entry(name)(ctypes.byref(a), _ptr(m), sb, sh, sr, _ptr(lists), _stream()), name)
 
 
+def block_select_value(top_k, keep_first=0, keep_local=1, causal=False):
+    """The checked host integers of a block selection (kernels/features.py: BlockSelect): (top_k, keep_first, keep_local).
+    ValueError: a top_k that is no int (a bool is none), a keep_first / keep_local that is none, a negative value, and
+    keep_local < 1 under `causal` (no row may be left without its own block).  (Pure argument check.)"""
+    for name, x in (("top_k", top_k), ("keep_first", keep_first), ("keep_local", keep_local)):
+        if isinstance(x, bool) or not isinstance(x, int):
+            raise ValueError(f"block_select: {name} must be an int, got {x!r}")
+        if x < 0:
+            raise ValueError(f"block_select: {name} must be >= 0, got {x}")
+    if causal and keep_local < 1:
+        raise ValueError(f"block_select: a causal selection needs keep_local >= 1 (every row keeps its own block), got {keep_local}")
+    i32max = (1 << 31) - 1
+    return min(top_k, i32max), min(keep_first, i32max), min(keep_local, i32max)
+
+
+def block_means(x, out=None):
+    """usp_block_means: the fp32 means (B, nb, H, D) of the BLOCK_MASK_SIZE-row blocks of a 16-bit (B, S, H, D) tensor with unit
+    head-dim stride (16-byte aligned, strides multiples of 8 elements: kernels/attention.py: kernel_operand), D a multiple of 8
+    up to 128.  The last block is divided by its own row count.  `out`: a contiguous fp32 (B, nb, H, D) device tensor."""
+    _require_cuda(x)
+    B, S, H, D = x.shape
+    nb = (S + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if out is None:
+        out = torch.empty((B, nb, H, D), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, nb, H, D) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"block_means: out must be a contiguous fp32 ({B}, {nb}, {H}, {D}) tensor on {x.device}")
+    t = _t4(x)
+    _check(_feature_entry("usp_block_means")(t.ptr, dtype_code(x.dtype), B, S, H, D, t.stride_b, t.stride_s, t.stride_h, _ptr(out),
+                                             _stream()), "usp_block_means")
+    return out
+
+
+def block_select(qbar, kbar, top_k, scale: float, causal: bool, keep_first: int = 0, keep_local: int = 1, row_block0: int = 0,
+                 out=None):
+    """usp_block_select: the torch.bool mask (B, Hq, nbq, nbk) of the means qbar fp32 (B, nbq, Hq, D) and kbar fp32
+    (B, nbk, Hkv, D), both contiguous; `row_block0`: the global index of row block 0 (a ring rank's r * n).  Every byte of `out`
+    (a torch.bool / uint8 (B, Hq, nbq, nbk) device tensor with unit last stride; None: a new one) is written."""
+    _require_cuda(qbar, kbar)
+    B, nbq, Hq, D = qbar.shape
+    nbk, Hkv = kbar.shape[1], kbar.shape[2]
+    for t, shape in ((qbar, (B, nbq, Hq, D)), (kbar, (B, nbk, Hkv, D))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"block_select: the means must be contiguous fp32 {shape} tensors, got {tuple(t.shape)} {t.dtype}")
+    if out is None:
+        out = torch.empty((B, Hq, nbq, nbk), dtype=torch.bool, device=qbar.device)
+    elif out.dtype not in (torch.bool, torch.uint8) or tuple(out.shape) != (B, Hq, nbq, nbk) or (nbk > 1 and out.stride(-1) != 1) \
+            or out.device != qbar.device:
+        raise ValueError(f"block_select: out must be a torch.bool ({B}, {Hq}, {nbq}, {nbk}) tensor with unit last stride on {qbar.device}")
+    _check(_feature_entry("usp_block_select")(_ptr(qbar), _ptr(kbar), B, Hq, Hkv, D, nbq, nbk, int(row_block0), float(scale),
+                                              1 if causal else 0, int(top_k), int(keep_first), int(keep_local), _ptr(out),
+                                              out.stride(0), out.stride(1), out.stride(2), _stream()), "usp_block_select")
+    return out
+
+
 def _feature_entries():
     """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
     does not insist on."""
@@ -564,7 +621,10 @@ def _feature_entries():
             "usp_flash_fwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [fwd, vp, i64, i64, i64, vp, vp]),
             "usp_flash_bwd_bsp": (USP_ATTN_BLOCK_MASK, "block_mask (USP_ATTN_BLOCK_MASK)", [bwd, vp, i64, i64, i64, vp, vp]),
             "usp_flash_fwd_maxlogit": (USP_ATTN_MAX_LOGIT, "return_max_logits (USP_ATTN_MAX_LOGIT)", [fwd, vp, i64, i64, vp]),
-            "usp_row_max_reduce": (USP_ATTN_MAX_LOGIT, "return_max_logits (USP_ATTN_MAX_LOGIT)", [i32, i32, i32, vp, i64, i64, vp, i32, vp])}
+            "usp_row_max_reduce": (USP_ATTN_MAX_LOGIT, "return_max_logits (USP_ATTN_MAX_LOGIT)", [i32, i32, i32, vp, i64, i64, vp, i32, vp]),
+            "usp_block_means": (USP_ATTN_BLOCK_SELECT, "block_select (USP_ATTN_BLOCK_SELECT)", [vp, i32, i32, i32, i32, i32, i64, i64, i64, vp, vp]),
+            "usp_block_select": (USP_ATTN_BLOCK_SELECT, "block_select (USP_ATTN_BLOCK_SELECT)",
+                                 [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp, i64, i64, i64, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -584,7 +644,7 @@ def _feature_entry(name: str):
     return fn
 
 
-_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _feature_entry      # (the names the per-feature tests call it by)
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _select_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):

@@ -169,7 +169,7 @@ def local_block_mask(block_mask, H: int, P: int, rank: int):
 
 
 def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, rank: int, head_scatter: bool, how: str,
-                  bidirectional=None, block_mask=None):
+                  bidirectional=None, block_mask=None, block_select=None):
     """What a layer of H heads hands its attention function for the options that depend on WHICH heads ulysses rank `rank` of P
     holds behind the exchange: (keyword dict, local slopes).
       alibi_slopes  cut to the rank's heads (local_alibi_slopes);
@@ -183,13 +183,15 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
                     holds whole rows of some heads, so the attention function plans its arrays alone (ring/doc_blocks.py).
       bidirectional as given, likewise (a layer that has parsed it already hands the plan over as `cu_doclens`: the spans ride
                     inside, ring/doc_blocks.py: Spans).
+      block_select  as given: the selection has no cross-head term, so behind the exchange the attention function selects for the
+                    heads the rank holds over the whole sequence it then holds (kernels/attention.py: select_blocks).
     Each of them needs an exchange that scatters heads and gathers the sequence (`head_scatter`; `how`: that, in the layer's
     words): NotImplementedError otherwise."""
     p = dropout_value(dropout_p)
     if not head_scatter:
         doc_name = "cu_doclens" if getattr(cu_doclens, "spans", None) is None else "bidirectional"
         for name, value in (("alibi_slopes", alibi_slopes), ("dropout_p != 0", p), ("sinks", sinks), (doc_name, cu_doclens),
-                            ("bidirectional", bidirectional), ("block_mask", block_mask)):
+                            ("bidirectional", bidirectional), ("block_mask", block_mask), ("block_select", block_select)):
             if value is not None:
                 raise NotImplementedError(f"{name} needs the head-scatter exchange ({how})")
     kw = {}
@@ -203,6 +205,8 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
         kw["bidirectional"] = bidirectional
     if block_mask is not None:                     # cut to the rank's heads (local_block_mask)
         kw["block_mask"] = local_block_mask(block_mask, H, P, rank)
+    if block_select is not None:
+        kw["block_select"] = block_select
     return kw, local_alibi_slopes(alibi_slopes, H, P, rank)
 
 

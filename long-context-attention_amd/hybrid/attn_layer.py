@@ -19,7 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..kernels.features import block_mask_alone, max_logits_alone
+from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -58,13 +58,14 @@ class _USPLayer(torch.nn.Module):
             self._ring_size = dist.get_world_size(self.ring_pg) if self.ring_pg is not None else 1
         return self._ring_size
 
-    def _head_options(self, alibi_slopes, dropout_p, sinks, cu_doclens, heads: int, scatter_idx: int, block_mask=None):
+    def _head_options(self, alibi_slopes, dropout_p, sinks, cu_doclens, heads: int, scatter_idx: int, block_mask=None,
+                      block_select=None):
         """(the ring function's keywords dropout_head0 / sinks / cu_doclens, the slopes) for the heads this Ulysses rank holds
         behind the exchange (comm/all_to_all.py: local_options); with nothing to exchange any layout serves."""
         P = self.ulysses_size
         return local_options(alibi_slopes, dropout_p, sinks, cu_doclens, heads, P, dist.get_rank(self.ulysses_pg) if P > 1 else 0,
                              P == 1 or (scatter_idx, self.gather_idx) == (2, 1), "heads scattered, sequence gathered",
-                             block_mask=block_mask)
+                             block_mask=block_mask, block_select=block_select)
 
     def _docs(self, cu_doclens, batch: int, local_len: int, bidirectional=None):
         """`cu_doclens` checked against the WHOLE sequence (ring/doc_blocks.py: parse; a rank holds local_len of its
@@ -138,7 +139,7 @@ class LongContextAttention(_USPLayer):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                 deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None,
-                bidirectional=None, block_mask=None, return_max_logits=False) -> Tensor:
+                bidirectional=None, block_mask=None, return_max_logits=False, block_select=None) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
         layer, (head_cnt,) fp32 or the operands' type (comm/all_to_all.py: local_options: the gradient contract).  `cu_doclens` (keyword
@@ -156,18 +157,26 @@ class LongContextAttention(_USPLayer):
         `return_max_logits` (keyword only; beside window_size alone): the result is (context, max_logits), max_logits fp32
         (head_cnt,) without gradient: this rank's SHARE of the largest visible pre-softmax logit of every head -- its rows of the
         ring, the heads it holds under Ulysses, -inf for the heads other ranks hold.  The MAX over the sequence-parallel group is
-        the value (QK-clip takes it); the layer does no all-reduce and reads nothing on the host.  Through three exchanges."""
-        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
+        the value (QK-clip takes it); the layer does no all-reduce and reads nothing on the host.  Through three exchanges.
+        `block_select` (keyword only): a BlockSelect(top_k, keep_first=0, keep_local=1): the block mask is SELECTED on the device,
+        behind the head exchange, from the q and k of the whole sequence (kernels/attention.py: select_blocks) -- the call with
+        block_mask=select_blocks(q, k, ...) of the gathered sequence and the layer's heads.  Served where block_mask is (on a ring
+        of degree > 1 each rank pools its slices and the pooled keys are all-gathered: ring/front_end.py: select_block_rows); not
+        together with block_mask or anything block_mask refuses.  None: exactly the call without it."""
+        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                              block_select=block_select)
+        block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = query.shape[-1]
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
                                causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml)
+                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml,
+                               block_select=block_select)
             return (out[0][..., :D], out[1]) if ml else out[..., :D]
         cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1], bidirectional)     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
-        if ng_cap is not None and (block_mask is not None or cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
+        if ng_cap is not None and (block_mask is not None or block_select is not None or cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
                                    or dropout_value(dropout_p) is not None or sinks is not None or ml):
             # Any of them: the reference's structure (three exchanges), and the ring function serves it (ring/front_end.py: _place).
             # The pipeline issues blocks in row pieces and head groups: under a document mask each piece would need its own
@@ -181,7 +190,7 @@ class LongContextAttention(_USPLayer):
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
                                        self.ring_impl_type, ng_cap, softcap_value(softcap))
         head_kw, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2], self.scatter_idx,
-                                                   block_mask)
+                                                   block_mask, block_select)
         options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                                      return_attn_probs)
         options.update(head_kw)
@@ -213,20 +222,25 @@ class LongContextAttentionQKVPacked(_USPLayer):
 
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False) -> Tensor:
-        """`return_max_logits` (keyword only): (out, max_logits) as LongContextAttention.forward returns it."""
-        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
+                *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False,
+                block_select=None) -> Tensor:
+        """`return_max_logits` (keyword only): (out, max_logits) as LongContextAttention.forward returns it.  `block_select`
+        (keyword only): as LongContextAttention.forward takes it."""
+        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                              block_select=block_select)
+        block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = qkv.shape[-1]
         if kernel_head_dim(D) != D:
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                                window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
-                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml)
+                               cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml,
+                               block_select=block_select)
             return (out[0][..., :D], out[1]) if ml else out[..., :D]
         exchange = self.ulysses_size > 1
         cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1], bidirectional)
         head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1,
-                                                 block_mask)
+                                                 block_mask, block_select)
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         heads = qkv.shape[3] * (self.ulysses_size if exchange else 1)          # (of the layer: qkv holds this rank's by now)

@@ -13,8 +13,10 @@ from .attention import (
     hip_attn_backward,
     hip_attn_forward,
     hip_attn_func,
+    select_blocks,
     set_block_backend,
 )
+from .features import BlockSelect
 
 
 class AttnType(Enum):
@@ -69,4 +71,4 @@ def select_flash_attn_impl(impl_type: AttnType, stage: str = "fwd-bwd", attn_pro
 
 
 __all__ = ["AttnType", "select_flash_attn_impl", "hip_attn_forward", "hip_attn_backward",
-           "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend"]
+           "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect"]

@@ -14,7 +14,8 @@ from __future__ import annotations
 import torch
 
 from .. import _C
-from .features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, expand_block_mask, max_logits_alone  # noqa: F401
+from .features import (BLOCK_MASK_SIZE, BlockSelect, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
+                       block_select_alone, expand_block_mask, max_logits_alone)
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -91,6 +92,15 @@ class HipBlockBackend:
 
     def sink_grad(self, sinks, lse, delta, out=None, accum=False):
         return _C.sink_grad(sinks, lse, delta, out=out, accum=accum)
+
+    def block_means(self, x):
+        """fp32 (B, nb, H, D): the means of the 128-row blocks of a 16-bit (B, S, H, D) operand (usp_block_means)."""
+        return _C.block_means(x)
+
+    def block_select(self, qbar, kbar, top_k, scale, causal, keep_first=0, keep_local=1, row_block0=0):
+        """torch.bool (B, Hq, nbq, nbk): the selected key blocks of the row blocks whose means are `qbar`, the first of them the
+        global row block `row_block0`, among the key blocks whose means are `kbar` (usp_block_select; no host read)."""
+        return _C.block_select(qbar, kbar, top_k, scale, causal, keep_first, keep_local, row_block0)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
@@ -329,9 +339,52 @@ def block_mask_of(block_mask, q, k):
     return block_mask
 
 
+def select_operands(q, k, softmax_scale=None):
+    """(q, k, scale) as the selection kernels take them: values without gradient, any view the kernels can address
+    (kernel_operand), head dims the kernels do not instantiate zero-padded -- the pad adds 0 to every score -- and the scale of
+    the UNPADDED head dim where none is given."""
+    if q.dim() != 4 or k.dim() != 4 or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3] or q.dtype != k.dtype:
+        raise ValueError(f"block selection takes q (B, S, Hq, D) and k (B, S, Hkv, D) of one 16-bit type, got {tuple(q.shape)} "
+                         f"{q.dtype} and {tuple(k.shape)} {k.dtype}")
+    _C.dtype_code(q.dtype)
+    if k.shape[2] <= 0 or q.shape[2] % k.shape[2]:
+        raise ValueError(f"block selection needs Hq a multiple of Hkv, got {q.shape[2]} and {k.shape[2]}")
+    scale = float(_default_scale(q, softmax_scale))
+    with torch.no_grad():
+        q, k = pad_head_dim(q.detach(), k.detach())
+        return kernel_operand(q), kernel_operand(k), scale
+
+
+def select_blocks(q, k, top_k, *, softmax_scale=None, causal=False, keep_first=0, keep_local=1):
+    """The block mask a `block_select=BlockSelect(top_k, keep_first, keep_local)` call runs under: torch.bool (B, Hq, nb, nb),
+    nb = ceil(S / 128), of q (B, S, Hq, D) and k (B, S, Hkv, D) (bf16 / fp16, any strides with a unit last one), selected on the
+    device and never read on the host -- the MoBA gate at the kernels' block size.  With qbar / kbar the fp32 means of the
+    128-row blocks (a ragged last block: over the rows it has) and score[b, h, I, J] = softmax_scale * qbar[b, h, I] .
+    kbar[b, h // (Hq / Hkv), J] (default scale: D ** -0.5), row block I sees every J, under `causal` J <= I; the blocks J <
+    keep_first and I - keep_local < J <= I of them are always selected, and beside them the best max(0, top_k - n_forced) of the
+    others, by score descending, ties to the lower J: every row block selects exactly min(max(top_k, n_forced), n_visible) blocks.
+    Every element of the result is written (False above the diagonal under causal).  No gradient: q and k are read as values.
+    ValueError: a negative or non-int top_k / keep_first / keep_local, keep_local < 1 under causal; NotImplementedError: q and k of
+    different lengths, more than 8192 blocks.  With NaN or Inf inputs the selection is unspecified."""
+    top_k, keep_first, keep_local = _C.block_select_value(top_k, keep_first, keep_local, causal)
+    block_mask_self_attention(q.shape[1], k.shape[1], "block_select")
+    q, k, scale = select_operands(q, k, softmax_scale)
+    nb = (q.shape[1] + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if nb > _C.BLOCK_SELECT_MAX_BLOCKS:
+        raise NotImplementedError(f"block_select serves up to {_C.BLOCK_SELECT_MAX_BLOCKS} blocks of {BLOCK_MASK_SIZE} keys, got {nb}")
+    be = get_block_backend()
+    return be.block_select(be.block_means(q), be.block_means(k), top_k, scale, bool(causal), keep_first, keep_local, 0)
+
+
+def _selected(block_select, q, k, softmax_scale, causal):
+    """The mask of a call under `block_select` (judged alone already)."""
+    return select_blocks(q, k, block_select.top_k, softmax_scale=softmax_scale, causal=causal, keep_first=block_select.keep_first,
+                         keep_local=block_select.keep_local)
+
+
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                      softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
-                     bidirectional=None, block_mask=None, return_max_logits=False):
+                     bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -356,8 +409,13 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     `return_max_logits` (keyword only): the result is (out, lse, max_logits), max_logits an fp32 (Hq,) device tensor without
     gradient: max over batch, rows i and the keys j row i sees of softmax_scale * q_i . k_j, in score units, -inf for a head whose
     rows see nothing (include/usp_hip.h: usp_flash_fwd_maxlogit; nothing is read on the host).  out and lse are those of the call
-    without it on the two-waves-per-SIMD kernels.  Goes with window_size alone.  False: exactly the call without it."""
-    if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask):
+    without it on the two-waves-per-SIMD kernels.  Goes with window_size alone.  False: exactly the call without it.
+    `block_select` (keyword only): a BlockSelect(top_k, keep_first=0, keep_local=1): exactly the call with
+    block_mask=select_blocks(q, k, top_k, softmax_scale=, causal=, keep_first=, keep_local=) -- the same launches behind the two
+    selection kernels, the same bits.  Not together with block_mask or anything block_mask refuses.  None: the call without it.
+    (hip_attn_backward takes the mask, not the selection.)"""
+    if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                        block_select=block_select):
         B, Sq, Hq, D = q.shape
         scale = _default_scale(q, softmax_scale)
         if kernel_head_dim(D) != D:                 # zero padding changes no score
@@ -370,6 +428,8 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
         be = get_block_backend()
         be.fwd(q, k, v, scale, bool(causal), lse, out=out, window=window_of(window_size), row_max=row_max)
         return out, lse, be.row_max_reduce(row_max)
+    if block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        block_mask = _selected(block_select, q, k, softmax_scale, causal)
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         block_mask_of(block_mask, q, k)
         B, Sq, Hq, D = q.shape
@@ -490,7 +550,7 @@ class _HipAttnFunc(torch.autograd.Function):
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                   *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False,
-                  **kwargs):
+                  block_select=None, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -507,14 +567,20 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     `return_max_logits` (keyword only): the result becomes `(out, max_logits)`, with return_attn_probs `(out, softmax_lse, None,
     max_logits)`: the fp32 (Hq,) per-head maximum of the visible pre-softmax logits (hip_attn_forward), padded head dims
     included; no gradient, never read on the host.  `out` and the gradients are those of the call without it.  Goes with
-    window_size alone."""
-    if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask):
+    window_size alone.
+    `block_select` (keyword only): a BlockSelect: the block mask is selected here, once, from the values of q and k
+    (select_blocks; no gradient through the gate), and the call is the one with that block_mask: the autograd node keeps the mask
+    for its backward, which never selects again."""
+    if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                        block_select=block_select):
         D = q.shape[-1]
         scale = _default_scale(q, softmax_scale)                 # (of the unpadded head dim)
         res = _HipAttnFunc.apply(*pad_head_dim(q, k, v), scale, causal, bool(return_attn_probs), window_size, None, None, 0.0, 0,
                                  None, None, None, True)
         out = res[0] if kernel_head_dim(D) == D else res[0][..., :D]
         return (out, res[1], None, res[2]) if return_attn_probs else (out, res[1])
+    if block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        block_mask = _selected(block_select, q, k, softmax_scale, causal)
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         block_mask_of(block_mask, q, k)
         D = q.shape[-1]

@@ -4,11 +4,13 @@ together with cu_doclens and RIDES INSIDE the parsed document plan (ring/doc_blo
 fields and every positional construction its meaning; a `doc` that carries spans is named "bidirectional" in the refusals.
 `block_mask` (a 128 x 128 block mask) is no field either: it goes with none of the seven and is judged in one place, before the
 record is made (block_mask_alone).  `return_max_logits` (an extra RESULT, the largest visible logit of every head) likewise: it
-goes with window_size alone (max_logits_alone).  Pure argument logic: nothing here loads the library,
+goes with window_size alone (max_logits_alone).  `block_select` (a BlockSelect: the block mask is PRODUCED on the device,
+kernels/attention.py: select_blocks) goes where block_mask goes, with nothing block_mask refuses and not with block_mask itself
+(block_select_alone).  Pure argument logic: nothing here loads the library,
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
-from .._C import _window, alibi_value, dropout_value, sinks_value, softcap_value
+from .._C import _window, alibi_value, block_select_value, dropout_value, sinks_value, softcap_value
 
 # field of the record -> the flash-attn-style argument the messages name
 ARGUMENT = dict(window="window_size", softcap="softcap", alibi="alibi_slopes", dropout="dropout_p", sinks="sinks", doc="cu_doclens")
@@ -50,25 +52,55 @@ def block_mask_alone(block_mask, window_size=None, softcap=None, alibi_slopes=No
     return True
 
 
+class BlockSelect(NamedTuple):
+    """`block_select=`: the block mask of the call is selected on the device from its own q and k -- top_k key blocks per
+    (batch, query head, row block) by the score of the mean-pooled 128-blocks, the first `keep_first` key blocks and the last
+    `keep_local` ones up to the row block's own always among them (kernels/attention.py: select_blocks).  Host integers."""
+    top_k: int
+    keep_first: int = 0
+    keep_local: int = 1
+
+
+def block_select_alone(block_select, block_mask=None, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
+                       cu_doclens=None, bidirectional=None) -> bool:
+    """Is `block_select` on?  Judged HERE like block_mask (block_mask_alone), before any tensor is read: it goes with nothing
+    block_mask goes without, and not with block_mask itself.  None is exactly the call without the keyword; anything but a
+    BlockSelect raises ValueError, and so does a malformed one (_C.block_select_value; keep_local under causal is judged where
+    causal is known: select_blocks)."""
+    if block_select is None:
+        return False
+    if not isinstance(block_select, BlockSelect):
+        raise ValueError(f"block_select must be a BlockSelect(top_k, keep_first=0, keep_local=1), got {type(block_select).__name__}")
+    given = (("block_mask", block_mask), ("window_size", _window(window_size)), ("softcap", softcap_value(softcap)),
+             ("alibi_slopes", alibi_slopes), ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens),
+             ("bidirectional", bidirectional))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"block_select together with {name} is not supported by the HIP attention kernels")
+    block_select_value(*block_select)
+    return True
+
+
 def max_logits_alone(return_max_logits, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
-                     bidirectional=None, block_mask=None) -> bool:
+                     bidirectional=None, block_mask=None, block_select=None) -> bool:
     """Is `return_max_logits` on?  Like block_mask it is no field of the record: it is judged HERE, before Features.of and before
     any tensor is read.  It goes with window_size and nothing else -- the max-logit kernels hold no second mask or score-level
     step.  False / None is exactly the call without the keyword."""
     if not return_max_logits:
         return False
     given = (("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes), ("dropout_p", dropout_value(dropout_p)),
-             ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional), ("block_mask", block_mask))
+             ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional), ("block_mask", block_mask),
+             ("block_select", block_select))
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"return_max_logits together with {name} is not supported by the HIP attention kernels")
     return True
 
 
-def block_mask_self_attention(Sq: int, Sk: int):
-    """A block mask covers one sequence against itself."""
+def block_mask_self_attention(Sq: int, Sk: int, name: str = "block_mask"):
+    """A block mask (given, or selected: `name`) covers one sequence against itself."""
     if Sq != Sk:
-        raise NotImplementedError(f"block_mask needs whole q and k of the same length (self-attention), got {Sq} and {Sk}: "
+        raise NotImplementedError(f"{name} needs whole q and k of the same length (self-attention), got {Sq} and {Sk}: "
                                   f"for cross-attention use a dense call without the keyword")
 
 

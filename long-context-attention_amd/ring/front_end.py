@@ -6,10 +6,12 @@ from typing import NamedTuple
 import torch
 import torch.distributed as dist
 
-from .._C import dropout_value, softcap_value
+from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_value, dropout_value, softcap_value
 from ..kernels import AttnType
-from ..kernels.attention import draw_seed, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim
-from ..kernels.features import BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, max_logits_alone
+from ..kernels.attention import (draw_seed, get_block_backend, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim,
+                                 select_blocks, select_operands)
+from ..kernels.features import (BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, block_select_alone,
+                                max_logits_alone)
 from .utils import group_info
 from .varlen_utils import unflatten_lse
 
@@ -113,18 +115,37 @@ def _refuse_packed_spans(bidirectional):
 class BlockMask:
     """The `block_mask` of a dense ring call on its way to the ring's forward / backward: it travels in the `cu_doclens` slot
     (with which it never goes together), so the Function keeps its arguments.  `mask` covers the WHOLE sequence -- ring degree x
-    the local length -- and is the same on every rank; it is a device tensor and is never read on the host."""
+    the local length -- and is the same on every rank; it is a device tensor and is never read on the host.
+    `rows_only` (what a ring rank SELECTS under `block_select=`: select_block_rows): `mask` (B, Hq, n, nb) holds this rank's n
+    row blocks against the key blocks of the whole sequence -- a whole (nb, nb) mask is never made."""
     spans = None
 
-    def __init__(self, mask):
-        self.mask = mask
+    def __init__(self, mask, rows_only: bool = False):
+        self.mask, self.rows_only = mask, bool(rows_only)
 
     def view(self, r: int, kr: int, S: int, P: int):
         """The sub-mask of the launch of rank r's rows [r S, (r + 1) S) against ring rank kr's keys: a strided view, no copy."""
         if P == 1:
             return self.mask
         n = S // BLOCK_MASK_SIZE
+        if self.rows_only:
+            return self.mask[..., kr * n:(kr + 1) * n]
         return self.mask[..., r * n:(r + 1) * n, kr * n:(kr + 1) * n]
+
+
+class BlockSelection:
+    """The `block_select` of a dense ring call on its way to the ring's forward: like a BlockMask it rides in the `cu_doclens`
+    slot, and run_forward turns it into the BlockMask it selects -- once: the backward gets that mask."""
+    spans = None
+
+    def __init__(self, select):
+        self.select = select
+
+
+def _refuse_packed_block_select(block_select):
+    if block_select is not None:
+        raise NotImplementedError("block_select is not supported by the variable-length (packed) rings: use LongContextAttention "
+                                  "(ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches")
 
 
 def _refuse_packed_block_mask(block_mask):
@@ -139,9 +160,12 @@ def _refuse_packed_max_logits(return_max_logits):
                                   "(ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)")
 
 
-def block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+def block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_select=None):
     """`cu_doclens` for the rest of a dense ring call: the BlockMask where `block_mask` is given -- judged first, alone
-    (kernels/features.py: block_mask_alone) --, else `cu_doclens` as it is."""
+    (kernels/features.py: block_mask_alone) --, the BlockSelection where `block_select` is (block_select_alone), else
+    `cu_doclens` as it is."""
+    if block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
+        return BlockSelection(block_select)
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         return BlockMask(block_mask)
     return cu_doclens
@@ -159,6 +183,42 @@ def _place_block_mask(serves, q, k, bm, group):
         raise NotImplementedError(f"block_mask at ring degree {P} needs a local sequence length that is a multiple of "
                                   f"{BLOCK_MASK_SIZE} (whole mask blocks per rank), got {q.shape[1]}: pad the sequence")
     block_mask_value(bm.mask, q.shape[0], q.shape[2], P * q.shape[1], q.device)
+
+
+def _place_block_select(serves, q, k, sel, causal, group):
+    """The checks of a ring call under a block selection: those of a block mask, in its name, and the selection's own."""
+    P = group_info(dist, group)[0]
+    if P > 1 and serves.block_mask != ANY_DEGREE:
+        raise NotImplementedError(f"block_select across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
+                                  f"rings: {_BASIC}")
+    block_mask_self_attention(q.shape[1], k.shape[1], "block_select")
+    if P > 1 and q.shape[1] % BLOCK_MASK_SIZE:
+        raise NotImplementedError(f"block_select at ring degree {P} needs a local sequence length that is a multiple of "
+                                  f"{BLOCK_MASK_SIZE} (whole mask blocks per rank), got {q.shape[1]}: pad the sequence")
+    block_select_value(*sel.select, causal)
+
+
+def select_block_rows(q, k, select, softmax_scale, causal, group):
+    """The BlockMask a ring rank runs under `block_select`: kernels/attention.py: select_blocks over the WHOLE sequence,
+    restricted to this rank's rows.  Ring degree 1: the whole mask.  Beyond: the rank pools its own q and k slices (n =
+    S_local / 128 blocks each), all-gathers the pooled keys -- fp32 (B, n, Hkv, D), ONE all_gather_into_tensor per call -- and
+    selects its n row blocks, the first of them the global block r * n, against all nb key blocks: a rows-only mask
+    (B, Hq, n, nb).  Nothing is read on the host."""
+    P, r = group_info(dist, group)
+    top_k, keep_first, keep_local = block_select_value(*select, causal)
+    if P == 1:
+        return BlockMask(select_blocks(q, k, top_k, softmax_scale=softmax_scale, causal=causal, keep_first=keep_first,
+                                       keep_local=keep_local))
+    qs, ks, scale = select_operands(q, k, softmax_scale)
+    be = get_block_backend()
+    qbar, kbar_local = be.block_means(qs), be.block_means(ks)
+    B, n, Hkv, D = kbar_local.shape
+    if P * n > BLOCK_SELECT_MAX_BLOCKS:
+        raise NotImplementedError(f"block_select serves up to {BLOCK_SELECT_MAX_BLOCKS} blocks of {BLOCK_MASK_SIZE} keys, got {P * n}")
+    gathered = torch.empty((P * B, n, Hkv, D), dtype=torch.float32, device=kbar_local.device)
+    dist.all_gather_into_tensor(gathered, kbar_local.contiguous(), group=group)
+    kbar = gathered.view(P, B, n, Hkv, D).permute(1, 0, 2, 3, 4).reshape(B, P * n, Hkv, D)   # (rank-major -> the global order)
+    return BlockMask(be.block_select(qbar, kbar.contiguous(), top_k, scale, bool(causal), keep_first, keep_local, r * n), rows_only=True)
 
 
 def _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, group):
@@ -262,12 +322,18 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
             _place_block_mask(serves, q, k, cu_doc, group)
             _check_hot_path_args(dropout_p, window_size, softcap)
             p, docs = None, cu_doc
+        elif isinstance(cu_doc, BlockSelection):    # (likewise; the mask is selected below, from the operands as launched)
+            _place_block_select(serves, q, k, cu_doc, causal, group)
+            _check_hot_path_args(dropout_p, window_size, softcap)
+            p, docs = None, cu_doc
         else:
             p, docs = _place(serves, q, k, causal, window_size, softcap, alibi_slopes, dropout_p, sink_t, cu_doc, group)
         if packed:
             k, v = k.contiguous(), v.contiguous()
         else:
             q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)     # any view a caller holds (maybe_contiguous)
+        if isinstance(docs, BlockSelection):      # selected ONCE: the backward's keywords hold the mask (drop_kw below)
+            docs = select_block_rows(q, k, docs.select, softmax_scale, causal, group)
         drop_kw = {} if p is None else dict(rng_state=(draw_seed(), int(head0)))  # one seed per call, host side
         if docs is not None:                      # (kept with the backward's keywords: drop_kw is what the backward adds)
             drop_kw = dict(drop_kw, cu_doclens=docs)
@@ -331,9 +397,10 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
-                 cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False):
+                 cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
+            _refuse_packed_block_select(block_select)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, k, v, cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size, softcap,
@@ -341,9 +408,10 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False):
+                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
+            _refuse_packed_block_select(block_select)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(q, kv[:, 0], kv[:, 1], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal, window_size,
@@ -351,9 +419,10 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False):
+                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
+            _refuse_packed_block_select(block_select)
             _refuse_packed_spans(bidirectional)
             _refuse_unserved(serves, doc=cu_doclens, sinks=sinks)
             return Func.apply(qkv[:, 0], qkv[:, 1], qkv[:, 2], cu_seqlens, max_seqlen, dropout_p, softmax_scale, causal,
@@ -372,9 +441,11 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                  attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
-                 bidirectional=None, block_mask=None, return_max_logits=False):
-            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
-            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
+                 bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
+            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                                  block_select=block_select)
+            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                         block_select)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)       # (the spans travel inside the plan from here on)
             D = q.shape[-1]
             if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
@@ -392,9 +463,11 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
-                          block_mask=None, return_max_logits=False):
-            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
-            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
+                          block_mask=None, return_max_logits=False, block_select=None):
+            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                                  block_select=block_select)
+            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                         block_select)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)
             return Func.apply(q, kv[:, :, 0], kv[:, :, 1], dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                               deterministic, return_attn_probs, group, *last(attn_type), *head0_arg(dropout_head0, sinks, cu_doclens, ml))
@@ -402,9 +475,11 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                            attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
-                           block_mask=None, return_max_logits=False):
-            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
-            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
+                           block_mask=None, return_max_logits=False, block_select=None):
+            ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                                  block_select=block_select)
+            cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                         block_select)
             cu_doclens = span_plan(qkv[:, :, 0], group, cu_doclens, bidirectional)
             return Func.apply(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dropout_p, softmax_scale, causal, window_size, softcap,
                               alibi_slopes, deterministic, return_attn_probs, group, *last(attn_type),

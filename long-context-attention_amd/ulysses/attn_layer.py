@@ -13,7 +13,7 @@ from torch import Tensor
 
 from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, layer_max_logits, local_options
 from ..kernels import AttnType, select_flash_attn_impl
-from ..kernels.features import block_mask_alone, max_logits_alone
+from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone
 
 
 class UlyssesAttention(torch.nn.Module):
@@ -43,9 +43,13 @@ class UlyssesAttention(torch.nn.Module):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
-                return_max_logits=False) -> Tensor:
+                return_max_logits=False, block_select=None) -> Tensor:
         # `return_max_logits`: judged alone and first (kernels/features.py: max_logits_alone)
-        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
+        ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                              block_select=block_select)
+        # `block_select`: a BlockSelect: the block mask is selected behind the exchange, on this rank's heads over the whole
+        # sequence (kernels/attention.py: select_blocks); judged alone, where block_mask is
+        block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         # `block_mask`: a 128 x 128 block mask of the whole sequence (kernels/attention.py: hip_attn_forward), over the layer's
         # heads (cut to this rank's), the local heads or none; judged alone, before anything else
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
@@ -58,7 +62,7 @@ class UlyssesAttention(torch.nn.Module):
         head_kw, alibi_slopes = local_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2],
                                               dist.get_world_size(self.spg), dist.get_rank(self.spg),
                                               (self.scatter_idx, self.gather_idx) == (2, 1), "scatter_idx=2, gather_idx=1",
-                                              bidirectional=bidirectional, block_mask=block_mask)
+                                              bidirectional=bidirectional, block_mask=block_mask, block_select=block_select)
         q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
