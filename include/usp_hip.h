@@ -135,6 +135,22 @@ enum {
  * which produce a 128 x 128 block mask on the device -- top-k of mean-pooled blocks -- for usp_flash_fwd_bsp / usp_flash_bwd_bsp
  * (ABI still v7). */
 #define USP_ATTN_BLOCK_SELECT 32768
+/* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
+ * exists in two forms, both noted as USP_KIND_DKDV_ROW64:
+ *   USP_DKDV_KEYS128  flash_bwd_dkdv64_kernel: a work item owns 128 keys, two waves share a 64-key slice (S, P, dV | dP, dS, dK);
+ *   USP_DKDV_KEYS256  flash_bwd_dkdv64u_kernel: a work item owns 256 keys, each wave does all four products for its 64 keys --
+ *                     Q / dO are streamed half as often and P never crosses LDS; a short causal range pays more masked
+ *                     tiles per item and has half the items.  At equal dkdv_heads, dK / dV are bit-identical between the two for
+ *                     uncut launches and for cut launches without a causal bound; a cut causal launch cuts the second 128
+ *                     keys of a 256-key block at other query tiles than the 128-key item that owns them, so their fp32
+ *                     partial sums group differently there (tests/test_gpu_dkdv256.py).
+ * With neither bit the library picks per launch (csrc/usp_flash_bwd.hip: dkdv_keys_of); dkdv_heads = 0 and the workspace size
+ * follow the width, so ask usp_flash_bwd_workspace_bytes with the same flags.  With a bit, a call whose dK/dV launch the
+ * 64-row family does not serve (head dim != 128, packed batch, window, softcap, one of the extra entry points' features, a layout
+ * above) returns USP_EUNSUPPORTED and launches nothing; a call that skips the dK/dV launch ignores the bits.  Both bits at once,
+ * or one of them with USP_FORCE_WAVE32: USP_EINVAL.  USP_KIND_DKDV_KEYS256 in usp_last_launch_kinds() says which form ran. */
+#define USP_DKDV_KEYS256 65536
+#define USP_DKDV_KEYS128 131072
 
 typedef struct usp_tensor {
   void* ptr;
@@ -661,7 +677,8 @@ enum {
   USP_KIND_DQ_ROW64 = 64,       /* flash_bwd_dq64_kernel */
   USP_KIND_DQ_WAVE8 = 128,      /* flash_bwd_kernel (dQ) */
   USP_KIND_REDUCE_HEADS = 256,  /* reduce_heads_kernel (GQA head split / dK,dV cuts) */
-  USP_KIND_REDUCE_CUTS = 512    /* reduce_cuts_kernel (dQ key cuts) */
+  USP_KIND_REDUCE_CUTS = 512,   /* reduce_cuts_kernel (dQ key cuts) */
+  USP_KIND_DKDV_KEYS256 = 1024  /* beside USP_KIND_DKDV_ROW64: it was flash_bwd_dkdv64u_kernel (256-key items) */
 };
 int usp_last_launch_kinds(void);
 

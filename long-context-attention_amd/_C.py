@@ -36,6 +36,8 @@ USP_ATTN_SPAN = 4096           # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_BLOCK_MASK = 8192     # feature bit of usp_attn_features(): usp_block_list_bytes / usp_flash_fwd_bsp / usp_flash_bwd_bsp exist (not an args flag)
 USP_ATTN_MAX_LOGIT = 16384     # feature bit of usp_attn_features(): usp_flash_fwd_maxlogit / usp_row_max_reduce exist (not an args flag)
 USP_ATTN_BLOCK_SELECT = 32768  # feature bit of usp_attn_features(): usp_block_means / usp_block_select exist (not an args flag)
+USP_DKDV_KEYS256 = 65536       # usp_flash_bwd: 256-key items for the 64-row family's dK/dV launch (one wave does all four products) ...
+USP_DKDV_KEYS128 = 131072      # ... or its 128-key items (two waves share a 64-key slice); neither: the library picks per launch
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
@@ -65,6 +67,16 @@ def _family_flag(family) -> int:
         return _FAMILY_FLAG[family]
     except KeyError:
         raise ValueError(f"kernel family must be one of {sorted(k for k in _FAMILY_FLAG if k)}, got {family!r}") from None
+
+
+_DKDV_KEYS_FLAG = {0: 0, None: 0, 128: USP_DKDV_KEYS128, 256: USP_DKDV_KEYS256}
+USP_KIND_DKDV_KEYS256 = 1024   # beside "dkdv_row64": the 256-key-item kernel ran (not a kernel of its own: not in KINDS)
+
+
+def last_dkdv_item_keys() -> int:
+    """Keys per work item of the 64-row dK/dV kernel the calling thread's last flash_bwd launched: 128 | 256; 0 if it launched none."""
+    m = load().usp_last_launch_kinds()
+    return 0 if not m & 16 else (256 if m & USP_KIND_DKDV_KEYS256 else 128)
 
 
 def last_launch_kinds() -> tuple:
@@ -1005,7 +1017,7 @@ def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None, bsp_lists=None):
+              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None, bsp_lists=None, dkdv_keys: int = 0):
     """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
@@ -1014,7 +1026,8 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     group one dK/dV work item streams (a divisor of Hq / Hkv; 0 = the library decides).  `softcap`, `shift`: as flash_fwd (a
     shifted launch gets no automatic cuts: bwd_splits sizes them for a causal triangle).  `alibi`: as flash_fwd
     (usp_flash_bwd_alibi).  `dropout`: as flash_fwd (usp_flash_bwd_dropout): the same tuple regenerates the forward's mask;
-    `delta` is that of the dropped `out`.  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
+    `delta` is that of the dropped `out`.  `dkdv_keys`: 128 | 256 pins the item width of the 64-row dK/dV kernel (USP_DKDV_KEYS128 /
+    USP_DKDV_KEYS256; 0: the library picks; last_dkdv_item_keys() tells which ran).  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
     key_hi; with `only` the other one may be None.  `span`: as flash_fwd (usp_flash_bwd_span): the dQ launch reads (row_lo,
     row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None.  `bsp`: as flash_fwd (usp_flash_bwd_bsp)."""
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
@@ -1037,6 +1050,9 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     a.accum_dq, a.accum_dk, a.accum_dv = int(bool(accum_dq)), int(bool(accum_dk)), int(bool(accum_dv))
     ff = _family_flag(family)
     a.flags = (USP_LAUNCH_INTERLEAVE if interleave else 0) | ff | {None: 0, "dkdv": USP_BWD_SKIP_DQ, "dq": USP_BWD_SKIP_DKDV}[only]
+    if dkdv_keys not in _DKDV_KEYS_FLAG:
+        raise ValueError(f"dkdv_keys must be 0, 128 or 256, got {dkdv_keys!r}")
+    a.flags |= _DKDV_KEYS_FLAG[dkdv_keys]
     sh = _shift(shift)
     dc = doc_value(doc, B, Sq, Sk, q.device)             # None: off -- (None, None) included
     sp = span_value(span, B, Sq, Sk, q.device)

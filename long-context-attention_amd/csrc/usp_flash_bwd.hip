@@ -183,11 +183,14 @@ struct BwdExtras {
 // dK/dV of a call: the one-wave-per-SIMD kernel (4 waves x 64 keys, usp_flash_bwd64.hip) where `row64` allows it and it serves
 // the launch, the 8-wave kernel otherwise; then the sum over the partial slabs of a head-split / cut launch.
 template <int D, int DT>
-static int launch_dkdv(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_t st, bool row64) {
+static int launch_dkdv(BwdArgsSC& p, const BwdExtras& x, bool causal, hipStream_t st, bool row64, int keys) {
   p.nblk = (p.Sk + 127) / 128;
   p.n_items = p.B * p.Hkv * p.nblk * p.ngrp * p.qsplit;
   int rc = USP_ELAUNCH;
-  if (row64 && launch_dkdv64(p, DT, causal, st, &rc)) {
+  if (row64 && keys == 256 && launch_dkdv64u(p, DT, causal, st, &rc)) {      // 256-key items (usp_flash_bwd64u.hip; dkdv_keys_of)
+    if (rc != USP_OK) return rc;
+    launch_kinds_note(USP_KIND_DKDV_ROW64 | USP_KIND_DKDV_KEYS256);
+  } else if (row64 && launch_dkdv64(p, DT, causal, st, &rc)) {
     if (rc != USP_OK) return rc;
     launch_kinds_note(USP_KIND_DKDV_ROW64);
   } else {
@@ -305,7 +308,7 @@ static int launch_reduce_cuts(const BwdParams& p, hipStream_t st) {
 }
 
 template <int D, int DT>
-static int launch_bwd(BwdArgsSC p, const BwdExtras& x, bool causal, hipStream_t st, int force, int skip) {
+static int launch_bwd(BwdArgsSC p, const BwdExtras& x, bool causal, hipStream_t st, int force, int skip, int keys) {
   const bool want_dkdv = !(skip & USP_BWD_SKIP_DKDV), want_dq = !(skip & USP_BWD_SKIP_DQ);
   // per call, `force` = USP_FORCE_ROW64 / USP_FORCE_WAVE32 (include/usp_hip.h) picks the family; forced onto the 64-row
   // family, only the launches that will run have to be served
@@ -313,12 +316,14 @@ static int launch_bwd(BwdArgsSC p, const BwdExtras& x, bool causal, hipStream_t 
     return USP_EUNSUPPORTED;
   // the 64-row kernels: head dim 128; their hand-pinned pipelines have no softcap step
   const bool row64 = D == 128 && !(force & USP_FORCE_WAVE32) && !p.cap_on && !x.any();   // (... and no ALiBi, dropout or document step)
+  // an item width forced on the dK/dV launch (USP_DKDV_KEYS256 / _KEYS128): that launch must be one the 64-row family serves
+  if (want_dkdv && (force & (USP_DKDV_KEYS256 | USP_DKDV_KEYS128)) && !(row64 && dkdv64u_serves(p))) return USP_EUNSUPPORTED;
   int rc = USP_OK;
   if (x.bsp.mask) {                               // the lists of the launches that run, once, in front of them on the same stream
     rc = launch_block_lists(x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists, x.bsp.layout, p.Sq, p.Sk, causal, (want_dq ? 2 : 0) | (want_dkdv ? 4 : 0), st);
     if (rc != USP_OK) return rc;
   }
-  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, x, causal, st, row64)) != USP_OK) return rc;
+  if (want_dkdv && (rc = launch_dkdv<D, DT>(p, x, causal, st, row64, keys)) != USP_OK) return rc;
   if (want_dq && (rc = launch_dq<D, DT>(p, x, causal, st, row64)) == USP_OK && p.ksplit > 1) rc = launch_reduce_cuts<D, DT>(p, st);
   return rc;
 }
@@ -326,6 +331,32 @@ static int launch_bwd(BwdArgsSC p, const BwdExtras& x, bool causal, hipStream_t 
 }  // namespace usp
 
 static int cuts_of(int32_t n, bool packed) { return (packed || n < 2) ? 1 : (n > 8 ? 8 : n); }
+
+// Keys per work item of the 64-row family's dK/dV launch: 128 (usp_flash_bwd64.hip) or 256 (usp_flash_bwd64u.hip).  A property of
+// the call's arguments alone, so that plan_bwd, usp_flash_bwd_workspace_bytes and the launch take the same decision; a launch
+// the 64-row family then does not serve runs on another kernel with the plan made here (any plan is valid for any kernel).
+// USP_DKDV_KEYS256 / USP_DKDV_KEYS128 force the width.  Otherwise, from what was measured on MI355X (profiles/dkdv_unified.txt;
+// the dK/dV launch alone, bf16 causal, medians of 8 alternating rounds, 128 | 256 keys, A/A spread of the 128 arm):
+//   B1 S65536 H32/4   8192 items at 256 keys and one head (32 per CU), <= 1024 tiles a head   56.29 | 54.94 ms  (-2.2 %, spread 0.10;
+//                                                                                             second box 56.5 | 53.9, -4.6 %)
+//   B2 S8192  H16/16  1024 items (4 per CU), <= 128 tiles                                      0.950 | 0.884 ms  (-6.8 %, spread 0.002)
+//   B1 S16384 H16/2   1024 items (4 per CU), <= 256 tiles a head                               1.778 | 1.737 ms  (-2.3 %, spread 0.001)
+// and, on another box, without the mask (bf16) and in fp16 (causal) -- the other instantiations the rule reaches:
+//   full:  B1 S16384 H16/2  3.381 | 3.240 (-4.2 %)   B2 S8192 H16  1.726 | 1.629 (-5.6 %)   B1 S32768 H32/4  27.40 | 25.42 (-7.2 %)
+//   fp16:  B1 S16384 H16/2  1.868 | 1.803 (-3.5 %)   B2 S8192 H16  0.982 | 0.916 (-6.7 %)   B1 S65536 H32/4  57.80 | 55.41 (-4.1 %)
+//   (A/A spreads 0.012 / 0.0005 / 0.036 and 0.003 / 0.0001 / 0.10 ms)
+// -> 256 keys where the launch is one the 64-row family can serve, its 256-key blocks x query heads are at least four per CU and
+// its rows at least 8192: the smallest launch measured on either count.  Below that a launch has fewer items than 128-key items
+// leave it (half as many, each with 4 - 5 masked tiles at the diagonal instead of 2 - 3) and nothing was measured: 128.  Where
+// this picks 256, dkdv_heads_of picks what it picks for 128 (B Hq blocks / 2 >= 2 CUs: its cap, either way).  dkdv_heads in
+// {1, 2, 4} at 256 keys, B1 S65536: 55.13 / 54.96 / 55.20 ms; B1 S16384 H16/2: 1.785 / 1.768 / 2.625 -- the causal cap of 2 stays.
+static int dkdv_keys_of(const usp_bwd_args* a) {
+  if (a->flags & USP_DKDV_KEYS256) return 256;
+  if (a->flags & USP_DKDV_KEYS128) return 128;
+  if (a->D != 128 || a->seq_q || a->seq_k || (a->flags & (USP_FORCE_WAVE32 | USP_ATTN_SOFTCAP)) || usp::decode_mask(*a).windowed) return 128;
+  const int64_t items = (int64_t)a->B * a->Hq * ((a->Sk + 255) / 256);
+  return (a->Sq >= 8192 && items >= 4LL * usp::device_cus()) ? 256 : 128;
+}
 
 // Query heads of a KV group that ONE dK/dV work item streams into its accumulators (ABI v7: usp_bwd_args.dkdv_heads; a divisor
 // of G = Hq / Hkv).  More heads per item: K / V fragments and the epilogue once per run of heads, fewer fp32
@@ -342,13 +373,13 @@ static int cuts_of(int32_t n, bool packed) { return (packed || n < 2) ? 1 : (n >
 // blocks, whose first visible tiles lie up to 62 tiles apart; head after head inside an item that lead adds up, and from three
 // heads on the window of Q / dO tiles they stream together (62 tiles x 32 KiB x heads) no longer fits the XCD's 4 MiB L2 -- the
 // fetch triples for a time gain inside the noise.  Packed batches keep 1.
-static int dkdv_heads_of(const usp_bwd_args* a) {
+static int dkdv_heads_of(const usp_bwd_args* a, int keys) {
   const int G = a->Hq / a->Hkv;
   // an explicit value must divide G whatever G is: MHA (G = 1) accepts 1 only, as usp_hip.h states
   if (a->dkdv_heads > 0) return (G % a->dkdv_heads == 0) ? a->dkdv_heads : -1;
   if (G <= 1) return 1;
   if (a->seq_q || a->seq_k) return 1;
-  const int64_t base = (int64_t)a->B * a->Hkv * ((a->Sk + 127) / 128) * cuts_of(a->dkdv_splits, false);
+  const int64_t base = (int64_t)a->B * a->Hkv * ((a->Sk + keys - 1) / keys) * cuts_of(a->dkdv_splits, false);
   const bool triangles = usp::decode_mask(*a).causal;
   const int64_t want = (triangles ? 2LL : 1LL) * usp::device_cus();
   int best = 1;
@@ -362,6 +393,7 @@ static int dkdv_heads_of(const usp_bwd_args* a) {
 // (ngrp * qsplit) slabs of ws_rows x Hkv x D each for dK and for dV (none when that is one slab: the whole group in one item
 // and no cut), ksplit slabs of B x Sq x Hq x D for dQ (none without a cut).  Needs Hkv > 0 and Hq % Hkv == 0.
 struct BwdPlan {
+  int keys;                        // keys per dK/dV item of the 64-row family: 128 | 256 (dkdv_keys_of)
   int gsub, ngrp;                  // query heads per dK/dV item (< 1: dkdv_heads does not divide the group), items per KV group
   int qsplit, ksplit;              // cuts of the dK/dV launch, of the dQ launch
   int64_t ws_rows;                 // key rows of a dK/dV slab
@@ -370,7 +402,8 @@ struct BwdPlan {
 static BwdPlan plan_bwd(const usp_bwd_args* a) {
   const bool packed = a->seq_q || a->seq_k;
   BwdPlan pl;
-  pl.gsub = dkdv_heads_of(a);
+  pl.keys = dkdv_keys_of(a);
+  pl.gsub = dkdv_heads_of(a, pl.keys);
   pl.ngrp = pl.gsub < 1 ? 0 : (a->Hq / a->Hkv) / pl.gsub;
   pl.qsplit = cuts_of(a->dkdv_splits, packed);
   pl.ksplit = cuts_of(a->dq_splits, packed);
@@ -395,6 +428,8 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   launch_kinds_reset();
   if (!a || !a->lse || !a->delta) return USP_EINVAL;
   if (int rc = check_force(a->flags)) return rc;
+  if ((a->flags & USP_DKDV_KEYS256) && (a->flags & (USP_DKDV_KEYS128 | USP_FORCE_WAVE32))) return USP_EINVAL;
+  if ((a->flags & USP_DKDV_KEYS128) && (a->flags & USP_FORCE_WAVE32)) return USP_EINVAL;
   const int skip = a->flags & (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV);
   if (skip == (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV)) return USP_EINVAL;
   if (int rc = check_problem(*a)) return rc;
@@ -489,9 +524,9 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
     if (p.ksplit > 1) p.ws_dq = (float*)((char*)a->workspace + plan.dkdv_bytes);
   }
   x.al.al_diag = alibi_diag(*a);
-  const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
+  const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32 | USP_DKDV_KEYS256 | USP_DKDV_KEYS128);
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
-    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, x, mask.causal, (hipStream_t)stream, force, skip);
+    return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, x, mask.causal, (hipStream_t)stream, force, skip, plan.keys);
   });
 }
 

@@ -167,7 +167,7 @@ def check_stream(ins, out=print, where=""):
             ppos, pop, pops, _ = ins[p]
             if pop.startswith("s_nop"):
                 continue                                     # enough states on this way in
-            if pops and _is_producer(pop) and regs(pops[0]) & (a | b | (c - d)):
+            if pops and _is_producer(pop) and regs(pops[0]) & (a | b | c):     # (SrcC too, also where it is D: a chain's start constants)
                 out(f"A: {where}{ppos}: {pop} {pops[0]} feeds MFMA at {pos} ({k} instruction(s) earlier)")
                 bad += 1
             if k < 2:
@@ -211,7 +211,7 @@ def check(path, pat, out=print):
     return check_stream(_parse_s(path, pat), out, "line ")
 
 
-def check_library(lib, out=print, only=("64_kernel",)):
+def check_library(lib, out=print, only=("64_kernel", "64u_kernel")):
     """(kernels checked, potential hazards) over the kernels of the shipped library whose name contains one of `only`
     (default: the three one-wave-per-SIMD families, whose MFMAs are inline asm; the builtin MFMAs of the 8-wave kernels
     are padded by hipcc itself)."""
