@@ -83,13 +83,6 @@ struct BwdSpan {
   int64_t row_hi_sb, key_lo_sb;         // batch strides in elements (0: one array for the whole batch)
 };
 struct BwdArgsSPAN : BwdParams, BwdDoc, BwdSpan {};
-// What a kernel without the span switch defines for the shared bodies (usp_flash_bwd_dq_body.inc, usp_flash_bwd_dkdv_body.inc)
-#define USP_BWD_NO_SPAN                                          \
-  [[maybe_unused]] constexpr bool SPAN = false;                  \
-  [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
-  [[maybe_unused]] constexpr const int* span_key_lo = nullptr;   \
-  [[maybe_unused]] constexpr int64_t span_rh_sb = 0, span_kl_sb = 0; \
-  USP_BWD_NO_BSP
 // Block-sparse mask (usp_flash_bwd_bsp): kernel arguments of the block-sparse instantiations only (usp_flash_bwd_bsp.hip:
 // flash_bwd_bsp_kernel, flash_bwd_dkdv_bsp_kernel); every other kernel keeps its argument block and machine code.  The dQ launch
 // gets the lists of its 256-row blocks (two mask row blocks each: entry = 4 * key tile + the live halves' bits), the dK/dV launch
@@ -99,11 +92,6 @@ struct BwdBsp {
   int bsp_stride;                       // ints per list: [0] = count, [1 ..] = ascending entries
 };
 struct BwdArgsBSP : BwdParams, BwdBsp {};
-// What a kernel without the block-sparse switch defines for the shared bodies
-#define USP_BWD_NO_BSP                                           \
-  [[maybe_unused]] constexpr bool BSP = false;                   \
-  [[maybe_unused]] constexpr const int* bsp_lists = nullptr;     \
-  [[maybe_unused]] constexpr int bsp_stride = 0;
 
 // Packed variable-length batch: rebase the local copy of the parameters on the rows of sequence b (the
 // host passes batch strides of 0 in this mode, so every `b * stride_b` vanishes).  Returns false if the

@@ -19,40 +19,19 @@
 
 namespace usp {
 
-// SC: logit soft-capping (USP_ATTN_SOFTCAP; PA = BwdArgsSC): with t = tanh(S/cap) of the raw (masked) score,
+// Every kernel of the two launches is a shared body under a __global__ template that gives it a name, an argument block `p_in`
+// and CAUSAL; the body derives its switches from the block's type ("How a kernel variant is declared").  The variants
+// live in usp_flash_bwd_{alibi,dropout,doc,span,bsp}.hip.
+// SC (BwdArgsSC), logit soft-capping (USP_ATTN_SOFTCAP): with t = tanh(S/cap) of the raw (masked) score,
 // P = exp2(cap*log2e*t - lse2) (0 where masked) and dS = P (dP - delta) (1 - t^2), in place; the epilogue's `scale` is
-// unchanged.  The body is shared by two __global__ templates so that the kernel without softcap keeps its symbol name
-// and machine code.
-// AL: ALiBi has instantiations of its own in usp_flash_bwd_alibi.hip (flash_bwd_alibi_kernel, flash_bwd_dkdv_alibi_kernel); the
-// kernels here compile the bodies with AL = false.  DR: dropout likewise (usp_flash_bwd_dropout.hip).  DOC: the document mask
-// likewise (usp_flash_bwd_doc.hip).
-#define USP_BWD_NO_ALIBI                            \
-  constexpr bool AL = false;                        \
-  constexpr const float* al_slopes = nullptr;       \
-  constexpr int64_t al_sb = 0;                      \
-  constexpr int al_diag = 0;                        \
-  constexpr bool DR = false;                        \
-  constexpr Dropout dr{};                           \
-  constexpr bool DOC = false;                       \
-  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
-  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;   \
-  USP_BWD_NO_SPAN
-
+// unchanged.
 template <int D, int DT, bool CAUSAL>
-__global__ __launch_bounds__(512, 2) void flash_bwd_kernel(
-    const BwdParams p_in) {
-  constexpr bool SC = false;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  USP_BWD_NO_ALIBI
+__global__ __launch_bounds__(512, 2) void flash_bwd_kernel(const BwdParams p_in) {
 #include "usp_flash_bwd_dq_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_softcap_kernel(const BwdArgsSC p_in) {
-  constexpr bool SC = true;
-  const float sc_cl2 = p_in.cap_log2, sc_k2 = p_in.tanh_k2;
-  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dq_body.inc"
 }
 
@@ -77,17 +56,11 @@ __global__ __launch_bounds__(512, 2) void flash_bwd_softcap_kernel(const BwdArgs
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_kernel(const BwdParams p_in) {
-  constexpr bool SC = false;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_softcap_kernel(const BwdArgsSC p_in) {
-  constexpr bool SC = true;
-  const float sc_cl2 = p_in.cap_log2, sc_k2 = p_in.tanh_k2;
-  USP_BWD_NO_ALIBI
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

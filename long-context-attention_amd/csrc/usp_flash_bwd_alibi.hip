@@ -11,35 +11,11 @@ namespace usp {
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_alibi_kernel(const BwdArgsAL p_in) {
-  constexpr bool SC = false, AL = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  const float* const al_slopes = p_in.al_slopes;
-  const int64_t al_sb = p_in.al_sb;
-  const int al_diag = p_in.al_diag;
-  constexpr bool DR = false;
-  constexpr Dropout dr{};
-  constexpr bool DOC = false;
-  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
-  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
-  USP_BWD_NO_SPAN
 #include "usp_flash_bwd_dq_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_alibi_kernel(const BwdArgsAL p_in) {
-  constexpr bool SC = false, AL = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  const float* const al_slopes = p_in.al_slopes;
-  const int64_t al_sb = p_in.al_sb;
-  const int al_diag = p_in.al_diag;
-  constexpr bool DR = false;
-  constexpr Dropout dr{};
-  constexpr bool DOC = false;
-  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
-  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;
-  USP_BWD_NO_SPAN
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

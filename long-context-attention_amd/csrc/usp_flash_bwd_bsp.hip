@@ -13,32 +13,13 @@
 
 namespace usp {
 
-#define USP_BWD_BSP_ONLY                            \
-  constexpr bool SC = false, AL = false, DR = false, DOC = false, BSP = true; \
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;        \
-  constexpr const float* al_slopes = nullptr;       \
-  constexpr int64_t al_sb = 0;                      \
-  constexpr int al_diag = 0;                        \
-  constexpr Dropout dr{};                           \
-  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
-  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;   \
-  [[maybe_unused]] constexpr bool SPAN = false;                  \
-  [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
-  [[maybe_unused]] constexpr const int* span_key_lo = nullptr;   \
-  [[maybe_unused]] constexpr int64_t span_rh_sb = 0, span_kl_sb = 0; \
-  const int* const bsp_lists = p_in.bsp_lists;      \
-  const int bsp_stride = p_in.bsp_stride;
-
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_bsp_kernel(const BwdArgsBSP p_in) {
-  USP_BWD_BSP_ONLY
 #include "usp_flash_bwd_dq_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_bsp_kernel(const BwdArgsBSP p_in) {
-  USP_BWD_BSP_ONLY
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

@@ -1,17 +1,12 @@
-// Body of flash_bwd_dkdv_kernel / flash_bwd_dkdv_softcap_kernel (usp_flash_bwd.hip): the dK/dV launch, role-specialised waves.
-// Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
-// the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones, the dropout kernels
-// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones, the document kernels (usp_flash_bwd_doc.hip) the `if constexpr (DOC)`
-// ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
-// (usp_dropout_rng.h: Dropout) and doc_key_hi / doc_kh_sb (int32 key bounds and their batch stride).
-// The span kernels (usp_flash_bwd_span.hip) add the `if constexpr (SPAN)` steps on top of DOC's (span_key_lo / span_kl_sb;
-// USP_BWD_NO_SPAN elsewhere).  The block-sparse kernels (usp_flash_bwd_bsp.hip) add the `if constexpr (BSP)` steps (bsp_lists /
-// bsp_stride; USP_BWD_NO_BSP elsewhere): the streamed row tiles of each query head are a list, not a range.
+// Body of the two-waves-per-SIMD backward kernels (usp_flash_bwd*.hip): the dK/dV launch, role-specialised waves.
+// Contract: the including __global__ template has D / DT in scope and defines `p_in` (its argument block, by value) and CAUSAL;
+// everything else -- SC AL DR DOC SPAN BSP and their values -- is derived from p_in's type by usp_flash_bwd_prelude.inc.  A switch
+// that is off compiles none of its `if constexpr` steps.  DESIGN.md, "How a kernel variant is declared".
 // Dropout: role A forms the un-dropped P, uses P o keep for its dV MFMAs and hands B the un-dropped P with the keep decision in
 // the sign bit (P >= 0: set = dropped; no extra LDS); role B starts its dP chain from -delta t/256 and forms
 // |P| (kept ? chain : -delta t/256); 256/t goes into the epilogue's factor of both outputs.
 // (Not a header: no include guard, no declarations of its own outside the function body.)
+#include "usp_flash_bwd_prelude.inc"
   using E = Elem<DT>;
   constexpr int NW = 8, OWN = 128;
   constexpr int ROWB = D * 2;

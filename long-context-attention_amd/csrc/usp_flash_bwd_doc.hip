@@ -12,27 +12,13 @@
 
 namespace usp {
 
-#define USP_BWD_DOC_ONLY                            \
-  constexpr bool SC = false, AL = false, DR = false, DOC = true; \
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;        \
-  constexpr const float* al_slopes = nullptr;       \
-  constexpr int64_t al_sb = 0;                      \
-  constexpr int al_diag = 0;                        \
-  constexpr Dropout dr{};                           \
-  [[maybe_unused]] const int* const doc_row_lo = p_in.row_lo;   \
-  [[maybe_unused]] const int* const doc_key_hi = p_in.key_hi;   \
-  [[maybe_unused]] const int64_t doc_rl_sb = p_in.row_lo_sb, doc_kh_sb = p_in.key_hi_sb;   \
-  USP_BWD_NO_SPAN
-
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_doc_kernel(const BwdArgsDOC p_in) {
-  USP_BWD_DOC_ONLY
 #include "usp_flash_bwd_dq_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_doc_kernel(const BwdArgsDOC p_in) {
-  USP_BWD_DOC_ONLY
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

@@ -1,14 +1,9 @@
-// Body of flash_bwd_kernel / flash_bwd_softcap_kernel (usp_flash_bwd.hip): the dQ launch, 8 waves x 32 query rows.
-// Included as the body of the kernel templates in usp_flash_bwd.hip: the kernels without softcap (SC = false) compile exactly
-// the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps, the ALiBi kernels (usp_flash_bwd_alibi.hip) the `if constexpr (AL)` ones, the dropout kernels
-// (usp_flash_bwd_dropout.hip) the `if constexpr (DR)` ones, the document kernels (usp_flash_bwd_doc.hip) the `if constexpr (DOC)`
-// ones.  The including kernel defines `p_in`, SC / AL / DR / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr`
-// (usp_dropout_rng.h: Dropout) and doc_row_lo / doc_rl_sb (int32 row bounds and their batch stride).
-// The span kernels (usp_flash_bwd_span.hip) add the `if constexpr (SPAN)` steps on top of DOC's (span_row_hi / span_rh_sb;
-// USP_BWD_NO_SPAN elsewhere).  The block-sparse kernels (usp_flash_bwd_bsp.hip) add the `if constexpr (BSP)` steps (bsp_lists /
-// bsp_stride; USP_BWD_NO_BSP elsewhere): the streamed key tiles are a list, not a range.
+// Body of the two-waves-per-SIMD backward kernels (usp_flash_bwd*.hip): the dQ launch, 8 waves x 32 query rows.
+// Contract: the including __global__ template has D / DT in scope and defines `p_in` (its argument block, by value) and CAUSAL;
+// everything else -- SC AL DR DOC SPAN BSP and their values -- is derived from p_in's type by usp_flash_bwd_prelude.inc.  A switch
+// that is off compiles none of its `if constexpr` steps.  DESIGN.md, "How a kernel variant is declared".
 // (Not a header: no include guard, no declarations of its own outside the function body.)
+#include "usp_flash_bwd_prelude.inc"
   using E = Elem<DT>;
   constexpr int NT = 512;     // threads
   constexpr int OWN = (NT / 64) * 32;           // query rows of the workgroup

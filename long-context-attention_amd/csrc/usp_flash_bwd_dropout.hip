@@ -12,28 +12,13 @@
 
 namespace usp {
 
-#define USP_BWD_DROPOUT_ONLY                        \
-  constexpr bool SC = false, AL = false, DR = true; \
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;        \
-  constexpr const float* al_slopes = nullptr;       \
-  constexpr int64_t al_sb = 0;                      \
-  constexpr int al_diag = 0;                        \
-  const Dropout& dr = p_in;                         \
-  constexpr bool DOC = false;                       \
-  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;   \
-  [[maybe_unused]] constexpr const int* doc_key_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t doc_rl_sb = 0, doc_kh_sb = 0;   \
-  USP_BWD_NO_SPAN
-
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dropout_kernel(const BwdArgsDR p_in) {
-  USP_BWD_DROPOUT_ONLY
 #include "usp_flash_bwd_dq_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_dropout_kernel(const BwdArgsDR p_in) {
-  USP_BWD_DROPOUT_ONLY
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

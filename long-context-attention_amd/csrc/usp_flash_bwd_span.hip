@@ -11,30 +11,15 @@
 
 namespace usp {
 
-#define USP_BWD_SPAN_ONLY                           \
-  constexpr bool SC = false, AL = false, DR = false, DOC = true, SPAN = true, CAUSAL = false; \
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;        \
-  constexpr const float* al_slopes = nullptr;       \
-  constexpr int64_t al_sb = 0;                      \
-  constexpr int al_diag = 0;                        \
-  constexpr Dropout dr{};                           \
-  [[maybe_unused]] const int* const doc_row_lo = p_in.row_lo;   \
-  [[maybe_unused]] const int* const doc_key_hi = p_in.key_hi;   \
-  [[maybe_unused]] const int64_t doc_rl_sb = p_in.row_lo_sb, doc_kh_sb = p_in.key_hi_sb;   \
-  [[maybe_unused]] const int* const span_row_hi = p_in.row_hi;  \
-  [[maybe_unused]] const int* const span_key_lo = p_in.key_lo;  \
-  [[maybe_unused]] const int64_t span_rh_sb = p_in.row_hi_sb, span_kl_sb = p_in.key_lo_sb; \
-  USP_BWD_NO_BSP
-
 template <int D, int DT>
 __global__ __launch_bounds__(512, 2) void flash_bwd_span_kernel(const BwdArgsSPAN p_in) {
-  USP_BWD_SPAN_ONLY
+  constexpr bool CAUSAL = false;
 #include "usp_flash_bwd_dq_body.inc"
 }
 
 template <int D, int DT>
 __global__ __launch_bounds__(512, 2) void flash_bwd_dkdv_span_kernel(const BwdArgsSPAN p_in) {
-  USP_BWD_SPAN_ONLY
+  constexpr bool CAUSAL = false;
 #include "usp_flash_bwd_dkdv_body.inc"
 }
 

@@ -23,54 +23,33 @@ namespace usp {
 
 // NWAVES waves per workgroup, 32 query rows each: 8 (one 256-row workgroup per CU) or 4 (two 128-row
 // workgroups per CU: half the causal diagonal waste, and the two workgroups desynchronise).
-// KSPLIT: the K-split variant is its own instantiation -- the plain kernels sit on the register cliff (256 VGPRs), and
-// with the split code compiled in unconditionally hipcc spilled 16 more bytes in them.
-// SC: logit soft-capping (USP_ATTN_SOFTCAP; KSPLIT instantiation, PA = FwdArgsSC): every tile takes the generic loop,
-// which replaces the raw score tile by cap*tanh(S/cap) (in exp2 units) BEFORE the mask -- tanh(-inf) = -1, a key masked
-// first would keep a weight -- and runs the online softmax with c = 1.  The body is shared by two __global__ templates
-// so that the kernels without softcap keep their symbol names and machine code.
-// WIN: a left window bound (USP_ATTN_WINDOW with window_left >= 0) has its own instantiation, flash_fwd_window_kernel (KSPLIT
-// form): there the tiles no bound cuts for a wave take the hand-pinned main loop (rotated tile walk, see the body); in the
-// other kernels a left bound -- softcap launches still carry one -- sends every tile through the generic loop.
-// AL: ALiBi has instantiations of its own in usp_flash_fwd_alibi.hip (flash_fwd_alibi_kernel); the kernels here compile the body
-// with AL = false.  DR: dropout likewise (usp_flash_fwd_dropout.hip: flash_fwd_dropout_kernel).  SINK: attention sinks likewise
-// (usp_flash_fwd_sink.hip: flash_fwd_sink_kernel, the loops of the split and window kernels here with one more epilogue step).
-// DOC: the document mask likewise (usp_flash_fwd_doc.hip: flash_fwd_doc_kernel, the plain kernel's loops under the window walk).
-#define USP_FWD_NO_ALIBI                            \
-  constexpr bool AL = false;                        \
-  constexpr const float* al_slopes = nullptr;       \
-  constexpr int64_t al_sb = 0;                      \
-  constexpr int al_diag = 0;                        \
-  constexpr bool DR = false;                        \
-  constexpr Dropout dr{};                           \
-  constexpr bool SINK = false;                      \
-  constexpr const float* sink_s = nullptr;          \
-  constexpr bool DOC = false;                       \
-  constexpr const int* doc_row_lo = nullptr;        \
-  constexpr int64_t doc_sb = 0;                     \
-  USP_FWD_NO_SPAN
-
-template <int D, int DT, bool CAUSAL, int NWAVES, bool KSPLIT = false>
-__global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_kernel(const FwdArgsT<KSPLIT> p_in) {
-  constexpr bool SC = false, WIN = false;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  USP_FWD_NO_ALIBI
+// Every kernel of the family is the shared body (usp_flash_fwd_body.inc) under a __global__ template that gives it a name, an
+// argument block `p_in`, WIN and CAUSAL; the body derives its other switches from the block's type ("How a kernel
+// variant is declared").  The kernels here and the variants in usp_flash_fwd_{alibi,dropout,sink,maxl,doc,span,bsp}.hip:
+//   flash_fwd_kernel<.., false>  the plain argument block.  The K-split form is an instantiation of its own, <.., true> on
+//     FwdArgsT<true>: the plain kernels sit on the register cliff (256 VGPRs), and with the split code compiled in
+//     unconditionally hipcc spilled 16 more bytes in them.
+//   flash_fwd_window_kernel  WIN: a left window bound (USP_ATTN_WINDOW with window_left >= 0) on the split block.  The tiles no
+//     bound cuts for a wave take the hand-pinned main loop (rotated tile walk, see the body); in the other kernels a left bound
+//     -- softcap launches still carry one -- sends every tile through the generic loop.
+//   flash_fwd_softcap_kernel  FwdArgsSC, logit soft-capping (USP_ATTN_SOFTCAP): every tile takes the generic loop, which replaces
+//     the raw score tile by cap*tanh(S/cap) (in exp2 units) BEFORE the mask -- tanh(-inf) = -1, a key masked first would keep a
+//     weight -- and runs the online softmax with c = 1.
+template <int D, int DT, bool CAUSAL, int NWAVES, bool KS = false>
+__global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_kernel(const FwdArgsT<KS> p_in) {
+  constexpr bool WIN = false;
 #include "usp_flash_fwd_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_window_kernel(const FwdArgsT<true> p_in) {
-  constexpr bool KSPLIT = true, SC = false, WIN = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  USP_FWD_NO_ALIBI
+  constexpr bool WIN = true;
 #include "usp_flash_fwd_body.inc"
 }
 
 template <int D, int DT, bool CAUSAL, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_softcap_kernel(const FwdArgsSC p_in) {
-  constexpr bool KSPLIT = true, SC = true, WIN = false;
-  const float sc_cl2 = p_in.cap_log2, sc_k2 = p_in.tanh_k2;
-  USP_FWD_NO_ALIBI
+  constexpr bool WIN = false;
 #include "usp_flash_fwd_body.inc"
 }
 

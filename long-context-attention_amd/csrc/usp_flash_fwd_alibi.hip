@@ -11,19 +11,7 @@ namespace usp {
 
 template <int D, int DT, bool CAUSAL, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_alibi_kernel(const FwdArgsAL p_in) {
-  constexpr bool KSPLIT = true, SC = false, WIN = false, AL = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  const float* const al_slopes = p_in.al_slopes;
-  const int64_t al_sb = p_in.al_sb;
-  const int al_diag = p_in.al_diag;
-  constexpr bool DR = false;
-  constexpr Dropout dr{};
-  constexpr bool SINK = false;
-  constexpr const float* sink_s = nullptr;
-  constexpr bool DOC = false;
-  constexpr const int* doc_row_lo = nullptr;
-  constexpr int64_t doc_sb = 0;
-  USP_FWD_NO_SPAN
+  constexpr bool WIN = false;
 #include "usp_flash_fwd_body.inc"
 }
 

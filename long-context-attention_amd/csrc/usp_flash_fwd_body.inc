@@ -1,24 +1,10 @@
-// Body of flash_fwd_kernel / flash_fwd_softcap_kernel (usp_flash_fwd.hip): one workgroup = NWAVES x 32 query rows.
-// Included as the body of the kernel templates in usp_flash_fwd.hip: the kernels without softcap (SC = false) compile exactly
-// the source they were profiled with, so they keep their symbol names and machine code; the softcap kernels add
-// the `if constexpr (SC)` steps, the window kernel the `if constexpr (WIN)` ones, the ALiBi kernel (usp_flash_fwd_alibi.hip) the
-// `if constexpr (AL)` ones, the dropout kernel (usp_flash_fwd_dropout.hip) the `if constexpr (DR)` ones, the sink kernel
-// (usp_flash_fwd_sink.hip) the `if constexpr (SINK)` one in the epilogue, the document kernel (usp_flash_fwd_doc.hip) the
-// `if constexpr (DOC)` ones, the span kernel (usp_flash_fwd_span.hip) the `if constexpr (SPAN)` ones on top of them (span_row_hi /
-// span_sb: int32 right row bounds and their batch stride; USP_FWD_NO_SPAN elsewhere), the block-sparse kernel
-// (usp_flash_fwd_bsp.hip) the `if constexpr (BSP)` ones (bsp_lists / bsp_stride; USP_FWD_NO_BSP elsewhere).  The including kernel
-// defines `p_in`, KSPLIT / SC / WIN / AL / DR / SINK / DOC, sc_cl2 / sc_k2, al_slopes / al_sb / al_diag, `dr` (usp_dropout_rng.h:
-// Dropout), sink_s (fp32 (Hq,) sink logits) and doc_row_lo / doc_sb (int32 row bounds and their batch stride).
-// The max-logit kernel (usp_flash_fwd_maxl.hip) defines USP_FWD_HAS_MAXL, MAXL = true and maxl_row / maxl_sb / maxl_sh (the fp32
-// (B, Hq, Sq) buffer of row maxima and its batch / head strides) and compiles the `if constexpr (MAXL)` steps: a TRUE running
-// row maximum beside the lazily raised reference m_run, written in score units by the epilogue.  Every other kernel gets the
-// switch off right here.
+// Body of the two-waves-per-SIMD forward kernels (usp_flash_fwd*.hip): one workgroup = NWAVES x 32 query rows.
+// Contract: the including __global__ template has D / DT / NWAVES in scope and defines `p_in` (its argument block, by value),
+// WIN (the window kernels' rotated walk) and CAUSAL; everything else -- KSPLIT SC AL DR SINK DOC SPAN BSP MAXL and their values --
+// is derived from p_in's type by usp_flash_fwd_prelude.inc.  A switch that is off compiles none of its `if constexpr` steps, so
+// a kernel's machine code depends on its own features alone.  DESIGN.md, "How a kernel variant is declared".
 // (Not a header: no include guard, no declarations of its own outside the function body.)
-#ifndef USP_FWD_HAS_MAXL
-  [[maybe_unused]] constexpr bool MAXL = false;
-  [[maybe_unused]] constexpr float* maxl_row = nullptr;
-  [[maybe_unused]] constexpr int64_t maxl_sb = 0, maxl_sh = 0;
-#endif
+#include "usp_flash_fwd_prelude.inc"
   using E = Elem<DT>;
   constexpr int kThreads = 64 * NWAVES;
   constexpr int kBM = 32 * NWAVES;

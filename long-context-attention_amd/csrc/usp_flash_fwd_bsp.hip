@@ -13,25 +13,11 @@
 namespace usp {
 
 // (PA: the argument block as a template parameter, so that the body's discarded K-split steps, which name fields this block does
-// not have, are not looked up)
+// not have, are not looked up; it is part of the kernels' symbol names)
 template <int D, int DT, bool CAUSAL, class PA = FwdArgsBSP>
 __global__ __launch_bounds__(256, 2) void flash_fwd_bsp_kernel(const PA p_in) {
   constexpr int NWAVES = 4;
-  constexpr bool KSPLIT = !std::is_same_v<PA, FwdArgsBSP>, WIN = false, SC = false, AL = false, DR = false, SINK = false, DOC = false;
-  constexpr bool BSP = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  constexpr const float* al_slopes = nullptr;
-  constexpr int64_t al_sb = 0;
-  constexpr int al_diag = 0;
-  constexpr Dropout dr{};
-  constexpr const float* sink_s = nullptr;
-  [[maybe_unused]] constexpr const int* doc_row_lo = nullptr;
-  [[maybe_unused]] constexpr int64_t doc_sb = 0;
-  [[maybe_unused]] constexpr bool SPAN = false;
-  [[maybe_unused]] constexpr const int* span_row_hi = nullptr;
-  [[maybe_unused]] constexpr int64_t span_sb = 0;
-  const int* const bsp_lists = p_in.bsp_lists;
-  const int bsp_stride = p_in.bsp_stride;
+  constexpr bool WIN = false;
 #include "usp_flash_fwd_body.inc"
 }
 

@@ -14,19 +14,10 @@
 namespace usp {
 
 // (PA: the argument block as a template parameter, so that the body's discarded K-split steps, which name fields this block does
-// not have, are not looked up)
+// not have, are not looked up; it is part of the kernels' symbol names)
 template <int D, int DT, bool CAUSAL, int NWAVES, class PA = FwdArgsDOC>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_doc_kernel(const PA p_in) {
-  constexpr bool KSPLIT = !std::is_same_v<PA, FwdArgsDOC>, WIN = false, SC = false, AL = false, DR = false, SINK = false, DOC = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  constexpr const float* al_slopes = nullptr;
-  constexpr int64_t al_sb = 0;
-  constexpr int al_diag = 0;
-  constexpr Dropout dr{};
-  constexpr const float* sink_s = nullptr;
-  const int* const doc_row_lo = p_in.row_lo;
-  const int64_t doc_sb = p_in.row_lo_sb;
-  USP_FWD_NO_SPAN
+  constexpr bool WIN = false;
 #include "usp_flash_fwd_body.inc"
 }
 

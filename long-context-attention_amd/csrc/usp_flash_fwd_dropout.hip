@@ -12,18 +12,7 @@ namespace usp {
 
 template <int D, int DT, bool CAUSAL, int NWAVES>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_dropout_kernel(const FwdArgsDR p_in) {
-  constexpr bool KSPLIT = true, SC = false, WIN = false, AL = false, DR = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  constexpr const float* al_slopes = nullptr;
-  constexpr int64_t al_sb = 0;
-  constexpr int al_diag = 0;
-  const Dropout& dr = p_in;
-  constexpr bool SINK = false;
-  constexpr const float* sink_s = nullptr;
-  constexpr bool DOC = false;
-  constexpr const int* doc_row_lo = nullptr;
-  constexpr int64_t doc_sb = 0;
-  USP_FWD_NO_SPAN
+  constexpr bool WIN = false;
 #include "usp_flash_fwd_body.inc"
 }
 

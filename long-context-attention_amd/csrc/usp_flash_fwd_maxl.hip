@@ -15,25 +15,11 @@
 
 namespace usp {
 
-#define USP_FWD_HAS_MAXL
 template <int D, int DT, bool CAUSAL, int NWAVES, int FORM>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_maxl_kernel(const std::conditional_t<FORM == 0, FwdArgsMXP, FwdArgsMX> p_in) {
-  constexpr bool KSPLIT = FORM != 0, WIN = FORM == 2, SC = false, AL = false, DR = false, SINK = false, MAXL = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  constexpr const float* al_slopes = nullptr;
-  constexpr int64_t al_sb = 0;
-  constexpr int al_diag = 0;
-  constexpr Dropout dr{};
-  constexpr const float* sink_s = nullptr;
-  constexpr bool DOC = false;
-  constexpr const int* doc_row_lo = nullptr;
-  constexpr int64_t doc_sb = 0;
-  float* const maxl_row = p_in.row_max;
-  const int64_t maxl_sb = p_in.row_max_sb, maxl_sh = p_in.row_max_sh;
-  USP_FWD_NO_SPAN
+  constexpr bool WIN = FORM == 2;
 #include "usp_flash_fwd_body.inc"
 }
-#undef USP_FWD_HAS_MAXL
 
 int launch_fwd_maxl(const FwdArgsMX& p, int D, int dtype, bool causal, int waves, int grid, size_t lds, hipStream_t st) {
   FwdArgsMXP plain;                                          // the argument block of form 0: FwdParams and the row maxima alone

@@ -17,17 +17,7 @@ namespace usp {
 
 template <int D, int DT, bool CAUSAL, int NWAVES, int FORM>
 __global__ __launch_bounds__(64 * NWAVES, 2) void flash_fwd_sink_kernel(const std::conditional_t<FORM == 0, FwdArgsSKP, FwdArgsSK> p_in) {
-  constexpr bool KSPLIT = FORM != 0, WIN = FORM == 2, SC = false, AL = false, DR = false, SINK = true;
-  constexpr float sc_cl2 = 0.f, sc_k2 = 0.f;
-  constexpr const float* al_slopes = nullptr;
-  constexpr int64_t al_sb = 0;
-  constexpr int al_diag = 0;
-  constexpr Dropout dr{};
-  const float* const sink_s = p_in.sinks;
-  constexpr bool DOC = false;
-  constexpr const int* doc_row_lo = nullptr;
-  constexpr int64_t doc_sb = 0;
-  USP_FWD_NO_SPAN
+  constexpr bool WIN = FORM == 2;
 #include "usp_flash_fwd_body.inc"
 }
 

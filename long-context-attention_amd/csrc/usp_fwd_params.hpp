@@ -86,12 +86,6 @@ struct FwdSpan {
   int64_t row_hi_sb;                    // batch stride in elements (0: one array for the whole batch)
 };
 struct FwdArgsSPAN : FwdArgsT<false>, FwdDoc, FwdSpan {};      // (row_lo may be NULL here: all zero)
-// What a kernel without the span switch defines for the shared body (usp_flash_fwd_body.inc)
-#define USP_FWD_NO_SPAN                                          \
-  [[maybe_unused]] constexpr bool SPAN = false;                  \
-  [[maybe_unused]] constexpr const int* span_row_hi = nullptr;   \
-  [[maybe_unused]] constexpr int64_t span_sb = 0;                \
-  USP_FWD_NO_BSP
 // Block-sparse mask (usp_flash_fwd_bsp): kernel arguments of the block-sparse instantiations only (usp_flash_fwd_bsp.hip:
 // flash_fwd_bsp_kernel, the plain kernel's loops walking a list of key tiles); every other kernel keeps its argument block and
 // machine code.  The lists are built by usp_block_lists.hip (layout: BlockLists below).
@@ -100,11 +94,6 @@ struct FwdBsp {
   int bsp_stride;                       // ints per list: [0] = count, [1 ..] = ascending 64-key tile indices
 };
 struct FwdArgsBSP : FwdArgsT<false>, FwdBsp {};
-// What a kernel without the block-sparse switch defines for the shared body (usp_flash_fwd_body.inc)
-#define USP_FWD_NO_BSP                                           \
-  [[maybe_unused]] constexpr bool BSP = false;                   \
-  [[maybe_unused]] constexpr const int* bsp_lists = nullptr;     \
-  [[maybe_unused]] constexpr int bsp_stride = 0;
 // Max logits (usp_flash_fwd_maxlogit): kernel arguments of the max-logit instantiations only (usp_flash_fwd_maxl.hip:
 // flash_fwd_maxl_kernel, the plain and window kernels' tile loops with a true row maximum kept beside the lazy reference); every
 // other kernel keeps its argument block and machine code.

@@ -78,8 +78,10 @@ def isa_identity(lib):
 
 
 if __name__ == "__main__":
-    lib = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                             "long-context-attention_amd", "libusp_hip.so")
+    paths = [a for a in sys.argv[1:] if not a.startswith("--")]     # before or behind the flags: `--every <lib>` once listed the default
+    assert len(paths) <= 1, f"one library at a time: {paths}"
+    lib = paths[0] if paths else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "long-context-attention_amd", "libusp_hip.so")
+    print(f"# {os.path.abspath(lib)}", file=sys.stderr)
     r, a, n = isa_identity(lib)
     print(f"roofline_kernel_isa_sha16: {r}")
     print(f"plain_forward_kernels_isa_sha16: {a}  ({n} kernels)")
