@@ -135,6 +135,9 @@ enum {
  * which produce a 128 x 128 block mask on the device -- top-k of mean-pooled blocks -- for usp_flash_fwd_bsp / usp_flash_bwd_bsp
  * (ABI still v7). */
 #define USP_ATTN_BLOCK_SELECT 32768
+/* USP_ATTN_BLOCK_SELECT_TOP_P: a FEATURE bit like USP_ATTN_BLOCK_SELECT: the library exports usp_block_select_top_p (below), which
+ * selects the block mask by cumulative softmax mass of the pooled scores in place of a fixed count (ABI still v7). */
+#define USP_ATTN_BLOCK_SELECT_TOP_P 65536
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
  * exists in two forms, both noted as USP_KIND_DKDV_ROW64:
  *   USP_DKDV_KEYS128  flash_bwd_dkdv64_kernel: a work item owns 128 keys, two waves share a 64-key slice (S, P, dV | dP, dS, dK);
@@ -594,6 +597,46 @@ int usp_block_select(const float* qbar, const float* kbar, int32_t B, int32_t Hq
                      int32_t row_block0, float scale, int32_t causal, int32_t top_k, int32_t keep_first, int32_t keep_local,
                      void* mask, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_row, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Top-p block selection: usp_block_select with a cumulative-mass rule in place of the count (FlexPrefill, XAttention, SpargeAttn,
+ * Twilight: the fewest key blocks whose softmax mass reaches top_p).  qbar, kbar, score, Ig, the visible and the FORCED blocks,
+ * the mask layout and the ring use (nbq rows from row_block0 against all nbk key blocks) are those of usp_block_select above.
+ * For one (b, h, I), in real numbers:
+ *     w[J] = exp(score[J] - m) / Z over the VISIBLE blocks (m their maximum, Z their sum; the forced ones included), 0 elsewhere;
+ *     the forced blocks are selected, and their mass counts;
+ *     the other visible blocks are ordered by w descending, ties to the lower J, and the SHORTEST prefix of that order with
+ *     mass(forced) + mass(prefix) >= top_p is selected beside them (none where the forced blocks alone reach top_p; with
+ *     top_p = 1 blocks whose weight has underflowed to zero may be left out).
+ * share_group != 0: w[J] is the mean over the G = Hq / Hkv query heads of KV head h / G of their per-head weights -- each head
+ * normalised by its own Z, not a softmax of averaged scores -- and all G heads get the same mask row (NSA's rule).  With G = 1
+ * the result is bit for bit the unshared one.  EVERY byte of the mask is written (0 or 1).  Nothing is read on the host, there
+ * are no atomics, results leave in ordinary vector stores.  With NaN or infinite inputs the selection is unspecified; every
+ * access stays in range.
+ *
+ * In fp32, one workgroup of 256 threads per (b, h, I) -- share_group: per (b, KV head, I), the group's heads in ascending order:
+ *   - score[J]: one chain of fused multiply-adds over ascending d from 0, times scale; m: the maximum (exact);
+ *     e[J] = expf(score[J] - m); Z = SUM(e); W[J] = e[J] / Z, with share_group W[J] = (..(e0[J] / Z0 + e1[J] / Z1) + ..), the SUM
+ *     over the heads (not divided by G: the rule compares against top_p * total);
+ *   - SUM(x), the one order of every sum over blocks: thread t adds x[t], x[t + 256], ... ascending from 0; the 64 lanes of a
+ *     wave are added by the butterfly x += x[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; the four waves ((w0 + w1) + w2) + w3.  A sum
+ *     over a subset is SUM with 0 for the blocks left out: the order is a function of J alone, so results do not depend on the
+ *     grid and repeat from call to call, and with non-negative terms the sum is monotone in the subset;
+ *   - total = SUM(W), target = top_p * total (one fp32 product); key[J] = the order-preserving integer of W[J];
+ *     mass(T) = SUM(W[J] where J is forced, or a non-forced visible block with key[J] >= T);
+ *     the cut T = the largest 32-bit T with mass(T) >= target, found bit by bit from the top bit down;
+ *   - selected: the forced blocks, the non-forced visible blocks with key > T, and of those with key == T (n_eq blocks of the
+ *     one weight wt) the first `need` in ascending J, where with m_gt = mass(T + 1)
+ *         need = the smallest c in [1, n_eq] with fmaf((float)c, wt, m_gt) >= target, n_eq where no c has
+ *     (one fused multiply-add and one comparison per count; fmaf is monotone in c).
+ *   - the argument rules of usp_block_select; besides, a top_p that is NaN, <= 0 or > 1 is USP_EINVAL;
+ *   - USP_EUNSUPPORTED as for usp_block_select (D, Hq % Hkv, alignment, nbk > USP_BLOCK_SELECT_MAX_BLOCKS: the weights and
+ *     a scratch row live in LDS, 64 KiB + 544 bytes at the limit); nothing is launched or written.
+ * -------------------------------------------------------------------------------------------- */
+int usp_block_select_top_p(const float* qbar, const float* kbar, int32_t B, int32_t Hq, int32_t Hkv, int32_t D, int32_t nbq,
+                           int32_t nbk, int32_t row_block0, float scale, int32_t causal, float top_p, int32_t keep_first,
+                           int32_t keep_local, int32_t share_group, void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
+                           int64_t mask_stride_row, void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -695,9 +738,9 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
- * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT,
- * the last eight feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span / *_bsp / *_maxlogit / usp_block_means and
- * usp_block_select entry points exist).  Unknown flag bits are not rejected by
+ * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT |
+ * USP_ATTN_BLOCK_SELECT_TOP_P, the last nine feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span / *_bsp / *_maxlogit /
+ * usp_block_means and usp_block_select / usp_block_select_top_p entry points exist).  Unknown flag bits are not rejected by
  * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

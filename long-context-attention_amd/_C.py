@@ -38,6 +38,7 @@ USP_ATTN_MAX_LOGIT = 16384     # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_BLOCK_SELECT = 32768  # feature bit of usp_attn_features(): usp_block_means / usp_block_select exist (not an args flag)
 USP_DKDV_KEYS256 = 65536       # usp_flash_bwd: 256-key items for the 64-row family's dK/dV launch (one wave does all four products) ...
 USP_DKDV_KEYS128 = 131072      # ... or its 128-key items (two waves share a 64-key slice); neither: the library picks per launch
+USP_ATTN_BLOCK_SELECT_TOP_P = 65536  # feature bit of usp_attn_features(): usp_block_select_top_p exists (not an args flag)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
@@ -133,7 +134,8 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_attn_features", "usp_flash_fwd_alibi", "usp_flash_bwd_alibi", "usp_flash_fwd_dropout", "usp_flash_bwd_dropout",
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
-           "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select")
+           "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
+           "usp_block_select_top_p")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -145,6 +147,7 @@ SPAN_EXPORTS = ("usp_flash_fwd_span", "usp_flash_bwd_span")
 BSP_EXPORTS = ("usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp")
 MAXL_EXPORTS = ("usp_flash_fwd_maxlogit", "usp_row_max_reduce")
 SELECT_EXPORTS = ("usp_block_means", "usp_block_select")
+SELECT_TOP_P_EXPORTS = ("usp_block_select_top_p",)
 
 
 def lib_path() -> str:
@@ -163,7 +166,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -612,6 +615,50 @@ def block_select(qbar, kbar, top_k, scale: float, causal: bool, keep_first: int 
     return out
 
 
+def block_select_top_p_value(top_p, keep_first=0, keep_local=1, share_group=False, causal=False):
+    """The checked host values of a top-p block selection (kernels/features.py: BlockSelectTopP): (top_p, keep_first, keep_local,
+    share_group).  ValueError: a top_p that is no real number in (0, 1] (a bool is none, NaN is none), a keep_first / keep_local
+    that is no int or negative, a share_group that is no bool, and keep_local < 1 under `causal` (no row may be left without
+    its own block).  (Pure argument check.)"""
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not (0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"block_select: top_p must be a real number in (0, 1], got {top_p!r}")
+    for name, x in (("keep_first", keep_first), ("keep_local", keep_local)):
+        if isinstance(x, bool) or not isinstance(x, int):
+            raise ValueError(f"block_select: {name} must be an int, got {x!r}")
+        if x < 0:
+            raise ValueError(f"block_select: {name} must be >= 0, got {x}")
+    if not isinstance(share_group, bool):
+        raise ValueError(f"block_select: share_group must be a bool, got {share_group!r}")
+    if causal and keep_local < 1:
+        raise ValueError(f"block_select: a causal selection needs keep_local >= 1 (every row keeps its own block), got {keep_local}")
+    i32max = (1 << 31) - 1
+    return float(top_p), min(keep_first, i32max), min(keep_local, i32max), share_group
+
+
+def block_select_top_p(qbar, kbar, top_p, scale: float, causal: bool, keep_first: int = 0, keep_local: int = 1,
+                       share_group: bool = False, row_block0: int = 0, out=None):
+    """usp_block_select_top_p: the torch.bool mask (B, Hq, nbq, nbk) of the means qbar fp32 (B, nbq, Hq, D) and kbar fp32
+    (B, nbk, Hkv, D), both contiguous, by cumulative softmax mass (include/usp_hip.h); `row_block0`: the global index of row
+    block 0 (a ring rank's r * n).  Every byte of `out` (a torch.bool / uint8 (B, Hq, nbq, nbk) device tensor with unit last
+    stride; None: a new one) is written."""
+    _require_cuda(qbar, kbar)
+    B, nbq, Hq, D = qbar.shape
+    nbk, Hkv = kbar.shape[1], kbar.shape[2]
+    for t, shape in ((qbar, (B, nbq, Hq, D)), (kbar, (B, nbk, Hkv, D))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"block_select_top_p: the means must be contiguous fp32 {shape} tensors, got {tuple(t.shape)} {t.dtype}")
+    if out is None:
+        out = torch.empty((B, Hq, nbq, nbk), dtype=torch.bool, device=qbar.device)
+    elif out.dtype not in (torch.bool, torch.uint8) or tuple(out.shape) != (B, Hq, nbq, nbk) or (nbk > 1 and out.stride(-1) != 1) \
+            or out.device != qbar.device:
+        raise ValueError(f"block_select_top_p: out must be a torch.bool ({B}, {Hq}, {nbq}, {nbk}) tensor with unit last stride on {qbar.device}")
+    _check(_feature_entry("usp_block_select_top_p")(_ptr(qbar), _ptr(kbar), B, Hq, Hkv, D, nbq, nbk, int(row_block0), float(scale),
+                                                    1 if causal else 0, float(top_p), int(keep_first), int(keep_local),
+                                                    1 if share_group else 0, _ptr(out), out.stride(0), out.stride(1), out.stride(2),
+                                                    _stream()), "usp_block_select_top_p")
+    return out
+
+
 def _feature_entries():
     """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
     does not insist on."""
@@ -636,7 +683,9 @@ def _feature_entries():
             "usp_row_max_reduce": (USP_ATTN_MAX_LOGIT, "return_max_logits (USP_ATTN_MAX_LOGIT)", [i32, i32, i32, vp, i64, i64, vp, i32, vp]),
             "usp_block_means": (USP_ATTN_BLOCK_SELECT, "block_select (USP_ATTN_BLOCK_SELECT)", [vp, i32, i32, i32, i32, i32, i64, i64, i64, vp, vp]),
             "usp_block_select": (USP_ATTN_BLOCK_SELECT, "block_select (USP_ATTN_BLOCK_SELECT)",
-                                 [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp, i64, i64, i64, vp])}
+                                 [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp, i64, i64, i64, vp]),
+            "usp_block_select_top_p": (USP_ATTN_BLOCK_SELECT_TOP_P, "block_select=BlockSelectTopP (USP_ATTN_BLOCK_SELECT_TOP_P)",
+                                       [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, i32, i32, vp, i64, i64, i64, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -656,7 +705,7 @@ def _feature_entry(name: str):
     return fn
 
 
-_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _select_entry = _feature_entry      # (the names the per-feature tests call it by)
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _select_entry = _select_top_p_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):

@@ -169,7 +169,7 @@ def local_block_mask(block_mask, H: int, P: int, rank: int):
 
 
 def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, rank: int, head_scatter: bool, how: str,
-                  bidirectional=None, block_mask=None, block_select=None):
+                  bidirectional=None, block_mask=None, block_select=None, kv_heads=None):
     """What a layer of H heads hands its attention function for the options that depend on WHICH heads ulysses rank `rank` of P
     holds behind the exchange: (keyword dict, local slopes).
       alibi_slopes  cut to the rank's heads (local_alibi_slopes);
@@ -184,7 +184,10 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
       bidirectional as given, likewise (a layer that has parsed it already hands the plan over as `cu_doclens`: the spans ride
                     inside, ring/doc_blocks.py: Spans).
       block_select  as given: the selection has no cross-head term, so behind the exchange the attention function selects for the
-                    heads the rank holds over the whole sequence it then holds (kernels/attention.py: select_blocks).
+                    heads the rank holds over the whole sequence it then holds (kernels/attention.py: select_blocks).  A
+                    BlockSelectTopP with share_group adds the weights of the query heads of one KV head: served where every
+                    rank holds whole groups (P <= `kv_heads`, the layer's KV heads), refused (NotImplementedError) where the
+                    KV heads are replicated over ranks (kv_heads < P) and a group's heads live on several of them.
     Each of them needs an exchange that scatters heads and gathers the sequence (`head_scatter`; `how`: that, in the layer's
     words): NotImplementedError otherwise."""
     p = dropout_value(dropout_p)
@@ -194,6 +197,10 @@ def local_options(alibi_slopes, dropout_p, sinks, cu_doclens, H: int, P: int, ra
                             ("bidirectional", bidirectional), ("block_mask", block_mask), ("block_select", block_select)):
             if value is not None:
                 raise NotImplementedError(f"{name} needs the head-scatter exchange ({how})")
+    if getattr(block_select, "share_group", False) and P > 1 and kv_heads is not None and kv_heads % P:
+        raise NotImplementedError(f"block_select with share_group=True needs every ulysses rank to hold whole KV groups, got "
+                                  f"{kv_heads} KV heads over ulysses degree {P} (a group's query heads live on several ranks): "
+                                  f"use share_group=False or a ulysses degree that divides the KV heads")
     kw = {}
     if p is not None and P > 1:
         kw["dropout_head0"] = local_heads(H, P, rank).start

@@ -59,13 +59,13 @@ class _USPLayer(torch.nn.Module):
         return self._ring_size
 
     def _head_options(self, alibi_slopes, dropout_p, sinks, cu_doclens, heads: int, scatter_idx: int, block_mask=None,
-                      block_select=None):
+                      block_select=None, kv_heads=None):
         """(the ring function's keywords dropout_head0 / sinks / cu_doclens, the slopes) for the heads this Ulysses rank holds
         behind the exchange (comm/all_to_all.py: local_options); with nothing to exchange any layout serves."""
         P = self.ulysses_size
         return local_options(alibi_slopes, dropout_p, sinks, cu_doclens, heads, P, dist.get_rank(self.ulysses_pg) if P > 1 else 0,
                              P == 1 or (scatter_idx, self.gather_idx) == (2, 1), "heads scattered, sequence gathered",
-                             block_mask=block_mask, block_select=block_select)
+                             block_mask=block_mask, block_select=block_select, kv_heads=kv_heads)
 
     def _docs(self, cu_doclens, batch: int, local_len: int, bidirectional=None):
         """`cu_doclens` checked against the WHOLE sequence (ring/doc_blocks.py: parse; a rank holds local_len of its
@@ -158,7 +158,8 @@ class LongContextAttention(_USPLayer):
         (head_cnt,) without gradient: this rank's SHARE of the largest visible pre-softmax logit of every head -- its rows of the
         ring, the heads it holds under Ulysses, -inf for the heads other ranks hold.  The MAX over the sequence-parallel group is
         the value (QK-clip takes it); the layer does no all-reduce and reads nothing on the host.  Through three exchanges.
-        `block_select` (keyword only): a BlockSelect(top_k, keep_first=0, keep_local=1): the block mask is SELECTED on the device,
+        `block_select` (keyword only): a BlockSelect(top_k, keep_first=0, keep_local=1) or a BlockSelectTopP(top_p, keep_first=0,
+        keep_local=1, share_group=False; kernels/attention.py: select_blocks_top_p): the block mask is SELECTED on the device,
         behind the head exchange, from the q and k of the whole sequence (kernels/attention.py: select_blocks) -- the call with
         block_mask=select_blocks(q, k, ...) of the gathered sequence and the layer's heads.  Served where block_mask is (on a ring
         of degree > 1 each rank pools its slices and the pooled keys are all-gathered: ring/front_end.py: select_block_rows); not
@@ -190,7 +191,7 @@ class LongContextAttention(_USPLayer):
             return _AsyncUSPFunc.apply(query, key, value, softmax_scale, causal, self.ulysses_pg, self.ring_pg,
                                        self.ring_impl_type, ng_cap, softcap_value(softcap))
         head_kw, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2], self.scatter_idx,
-                                                   block_mask, block_select)
+                                                   block_mask, block_select, key.shape[2])
         options = self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic,
                                      return_attn_probs)
         options.update(head_kw)
@@ -240,7 +241,7 @@ class LongContextAttentionQKVPacked(_USPLayer):
         exchange = self.ulysses_size > 1
         cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1], bidirectional)
         head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1,
-                                                 block_mask, block_select)
+                                                 block_mask, block_select, qkv.shape[3])
         if exchange:         # scatter 3 (heads), gather 1 (sequence)
             qkv = SeqAllToAll5D.apply(self.ulysses_pg, qkv, self.scatter_idx, self.gather_idx, self.use_sync, False)
         heads = qkv.shape[3] * (self.ulysses_size if exchange else 1)          # (of the layer: qkv holds this rank's by now)

@@ -14,9 +14,10 @@ from .attention import (
     hip_attn_forward,
     hip_attn_func,
     select_blocks,
+    select_blocks_top_p,
     set_block_backend,
 )
-from .features import BlockSelect
+from .features import BlockSelect, BlockSelectTopP
 
 
 class AttnType(Enum):
@@ -71,4 +72,5 @@ def select_flash_attn_impl(impl_type: AttnType, stage: str = "fwd-bwd", attn_pro
 
 
 __all__ = ["AttnType", "select_flash_attn_impl", "hip_attn_forward", "hip_attn_backward",
-           "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect"]
+           "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect",
+           "select_blocks_top_p", "BlockSelectTopP"]

@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 
 from .. import _C
-from .features import (BLOCK_MASK_SIZE, BlockSelect, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
+from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
                        block_select_alone, expand_block_mask, max_logits_alone)
 
 
@@ -101,6 +101,10 @@ class HipBlockBackend:
         """torch.bool (B, Hq, nbq, nbk): the selected key blocks of the row blocks whose means are `qbar`, the first of them the
         global row block `row_block0`, among the key blocks whose means are `kbar` (usp_block_select; no host read)."""
         return _C.block_select(qbar, kbar, top_k, scale, causal, keep_first, keep_local, row_block0)
+
+    def block_select_top_p(self, qbar, kbar, top_p, scale, causal, keep_first=0, keep_local=1, share_group=False, row_block0=0):
+        """torch.bool (B, Hq, nbq, nbk): block_select's mask by cumulative softmax mass (usp_block_select_top_p; no host read)."""
+        return _C.block_select_top_p(qbar, kbar, top_p, scale, causal, keep_first, keep_local, share_group, row_block0)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
@@ -376,8 +380,34 @@ def select_blocks(q, k, top_k, *, softmax_scale=None, causal=False, keep_first=0
     return be.block_select(be.block_means(q), be.block_means(k), top_k, scale, bool(causal), keep_first, keep_local, 0)
 
 
+def select_blocks_top_p(q, k, top_p, *, softmax_scale=None, causal=False, keep_first=0, keep_local=1, share_group=False):
+    """The block mask a `block_select=BlockSelectTopP(top_p, keep_first, keep_local, share_group)` call runs under: torch.bool
+    (B, Hq, nb, nb) like select_blocks, selected on the device and never read on the host.  With the scores of select_blocks,
+    w[b, h, I, J] = the softmax of row (b, h, I) over the blocks it sees (every J, under `causal` J <= I); the blocks J <
+    keep_first and I - keep_local < J <= I of them are always selected and their mass counts; the others are ordered by w
+    descending, ties to the lower J, and the shortest prefix with mass(forced) + mass(prefix) >= top_p is selected beside them
+    (nothing where the forced blocks reach top_p; with top_p = 1 blocks whose weight has underflowed to zero may be left out).
+    `share_group`: w is the mean over the query heads of one KV head of their weights (each its own softmax) and the group's
+    heads get the same mask (include/usp_hip.h: usp_block_select_top_p states every sum's order and the tie expression).  No
+    gradient.  ValueError: a top_p outside (0, 1], a negative or non-int keep_first / keep_local, a non-bool share_group,
+    keep_local < 1 under causal; NotImplementedError: q and k of different lengths, more than 8192 blocks."""
+    top_p, keep_first, keep_local, share_group = _C.block_select_top_p_value(top_p, keep_first, keep_local, share_group, causal)
+    block_mask_self_attention(q.shape[1], k.shape[1], "block_select")
+    q, k, scale = select_operands(q, k, softmax_scale)
+    nb = (q.shape[1] + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if nb > _C.BLOCK_SELECT_MAX_BLOCKS:
+        raise NotImplementedError(f"block_select serves up to {_C.BLOCK_SELECT_MAX_BLOCKS} blocks of {BLOCK_MASK_SIZE} keys, got {nb}")
+    be = get_block_backend()
+    return be.block_select_top_p(be.block_means(q), be.block_means(k), top_p, scale, bool(causal), keep_first, keep_local,
+                                 share_group, 0)
+
+
 def _selected(block_select, q, k, softmax_scale, causal):
-    """The mask of a call under `block_select` (judged alone already)."""
+    """The mask of a call under `block_select` (judged alone already): by the record's type."""
+    if isinstance(block_select, BlockSelectTopP):
+        return select_blocks_top_p(q, k, block_select.top_p, softmax_scale=softmax_scale, causal=causal,
+                                   keep_first=block_select.keep_first, keep_local=block_select.keep_local,
+                                   share_group=block_select.share_group)
     return select_blocks(q, k, block_select.top_k, softmax_scale=softmax_scale, causal=causal, keep_first=block_select.keep_first,
                          keep_local=block_select.keep_local)
 
@@ -412,7 +442,8 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     without it on the two-waves-per-SIMD kernels.  Goes with window_size alone.  False: exactly the call without it.
     `block_select` (keyword only): a BlockSelect(top_k, keep_first=0, keep_local=1): exactly the call with
     block_mask=select_blocks(q, k, top_k, softmax_scale=, causal=, keep_first=, keep_local=) -- the same launches behind the two
-    selection kernels, the same bits.  Not together with block_mask or anything block_mask refuses.  None: the call without it.
+    selection kernels, the same bits; or a BlockSelectTopP(top_p, keep_first=0, keep_local=1, share_group=False): likewise the
+    call with block_mask=select_blocks_top_p(q, k, top_p, ...).  Not together with block_mask or anything block_mask refuses.  None: the call without it.
     (hip_attn_backward takes the mask, not the selection.)"""
     if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                         block_select=block_select):
@@ -568,8 +599,8 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     max_logits)`: the fp32 (Hq,) per-head maximum of the visible pre-softmax logits (hip_attn_forward), padded head dims
     included; no gradient, never read on the host.  `out` and the gradients are those of the call without it.  Goes with
     window_size alone.
-    `block_select` (keyword only): a BlockSelect: the block mask is selected here, once, from the values of q and k
-    (select_blocks; no gradient through the gate), and the call is the one with that block_mask: the autograd node keeps the mask
+    `block_select` (keyword only): a BlockSelect or a BlockSelectTopP: the block mask is selected here, once, from the values
+    of q and k (select_blocks / select_blocks_top_p; no gradient through the gate), and the call is the one with that block_mask: the autograd node keeps the mask
     for its backward, which never selects again."""
     if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                         block_select=block_select):

@@ -6,11 +6,12 @@ fields and every positional construction its meaning; a `doc` that carries spans
 record is made (block_mask_alone).  `return_max_logits` (an extra RESULT, the largest visible logit of every head) likewise: it
 goes with window_size alone (max_logits_alone).  `block_select` (a BlockSelect: the block mask is PRODUCED on the device,
 kernels/attention.py: select_blocks) goes where block_mask goes, with nothing block_mask refuses and not with block_mask itself
-(block_select_alone).  Pure argument logic: nothing here loads the library,
+(block_select_alone); it is a BlockSelect (a count) or a BlockSelectTopP (a cumulative softmax mass,
+kernels/attention.py: select_blocks_top_p).  Pure argument logic: nothing here loads the library,
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
-from .._C import _window, alibi_value, block_select_value, dropout_value, sinks_value, softcap_value
+from .._C import _window, alibi_value, block_select_top_p_value, block_select_value, dropout_value, sinks_value, softcap_value
 
 # field of the record -> the flash-attn-style argument the messages name
 ARGUMENT = dict(window="window_size", softcap="softcap", alibi="alibi_slopes", dropout="dropout_p", sinks="sinks", doc="cu_doclens")
@@ -61,23 +62,39 @@ class BlockSelect(NamedTuple):
     keep_local: int = 1
 
 
+class BlockSelectTopP(NamedTuple):
+    """`block_select=` by cumulative mass: per (batch, query head, row block) the fewest key blocks whose softmax weight -- the
+    softmax, over the visible blocks, of the scores of the mean-pooled 128-blocks -- reaches `top_p`; the first `keep_first` key
+    blocks and the last `keep_local` ones up to the row block's own are always selected, and their mass counts.  `share_group`:
+    the query heads of one KV head select together, on the mean of their weights, and get one mask row (NSA's rule)
+    (kernels/attention.py: select_blocks_top_p).  Host values."""
+    top_p: float
+    keep_first: int = 0
+    keep_local: int = 1
+    share_group: bool = False
+
+
 def block_select_alone(block_select, block_mask=None, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
                        cu_doclens=None, bidirectional=None) -> bool:
     """Is `block_select` on?  Judged HERE like block_mask (block_mask_alone), before any tensor is read: it goes with nothing
     block_mask goes without, and not with block_mask itself.  None is exactly the call without the keyword; anything but a
-    BlockSelect raises ValueError, and so does a malformed one (_C.block_select_value; keep_local under causal is judged where
-    causal is known: select_blocks)."""
+    BlockSelect or a BlockSelectTopP raises ValueError, and so does a malformed one (_C.block_select_value,
+    _C.block_select_top_p_value; keep_local under causal is judged where causal is known: select_blocks, select_blocks_top_p)."""
     if block_select is None:
         return False
-    if not isinstance(block_select, BlockSelect):
-        raise ValueError(f"block_select must be a BlockSelect(top_k, keep_first=0, keep_local=1), got {type(block_select).__name__}")
+    if not isinstance(block_select, (BlockSelect, BlockSelectTopP)):
+        raise ValueError(f"block_select must be a BlockSelect(top_k, keep_first=0, keep_local=1) or a BlockSelectTopP(top_p, "
+                         f"keep_first=0, keep_local=1, share_group=False), got {type(block_select).__name__}")
     given = (("block_mask", block_mask), ("window_size", _window(window_size)), ("softcap", softcap_value(softcap)),
              ("alibi_slopes", alibi_slopes), ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens),
              ("bidirectional", bidirectional))
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"block_select together with {name} is not supported by the HIP attention kernels")
-    block_select_value(*block_select)
+    if isinstance(block_select, BlockSelectTopP):
+        block_select_top_p_value(*block_select)
+    else:
+        block_select_value(*block_select)
     return True
 
 

@@ -6,11 +6,11 @@ from typing import NamedTuple
 import torch
 import torch.distributed as dist
 
-from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_value, dropout_value, softcap_value
+from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_top_p_value, block_select_value, dropout_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import (draw_seed, get_block_backend, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim,
-                                 select_blocks, select_operands)
-from ..kernels.features import (BLOCK_MASK_SIZE, Features, block_mask_alone, block_mask_self_attention, block_select_alone,
+                                 select_blocks, select_blocks_top_p, select_operands)
+from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone,
                                 max_logits_alone)
 from .utils import group_info
 from .varlen_utils import unflatten_lse
@@ -195,7 +195,10 @@ def _place_block_select(serves, q, k, sel, causal, group):
     if P > 1 and q.shape[1] % BLOCK_MASK_SIZE:
         raise NotImplementedError(f"block_select at ring degree {P} needs a local sequence length that is a multiple of "
                                   f"{BLOCK_MASK_SIZE} (whole mask blocks per rank), got {q.shape[1]}: pad the sequence")
-    block_select_value(*sel.select, causal)
+    if isinstance(sel.select, BlockSelectTopP):
+        block_select_top_p_value(*sel.select, causal)
+    else:
+        block_select_value(*sel.select, causal)
 
 
 def select_block_rows(q, k, select, softmax_scale, causal, group):
@@ -203,9 +206,17 @@ def select_block_rows(q, k, select, softmax_scale, causal, group):
     restricted to this rank's rows.  Ring degree 1: the whole mask.  Beyond: the rank pools its own q and k slices (n =
     S_local / 128 blocks each), all-gathers the pooled keys -- fp32 (B, n, Hkv, D), ONE all_gather_into_tensor per call -- and
     selects its n row blocks, the first of them the global block r * n, against all nb key blocks: a rows-only mask
-    (B, Hq, n, nb).  Nothing is read on the host."""
+    (B, Hq, n, nb).  Nothing is read on the host.  A BlockSelectTopP runs the same scheme through select_blocks_top_p /
+    block_select_top_p (a rank of the ring holds every head, so share_group needs nothing more)."""
     P, r = group_info(dist, group)
-    top_k, keep_first, keep_local = block_select_value(*select, causal)
+    top_p = isinstance(select, BlockSelectTopP)
+    if top_p:
+        p, keep_first, keep_local, share = block_select_top_p_value(*select, causal)
+        if P == 1:
+            return BlockMask(select_blocks_top_p(q, k, p, softmax_scale=softmax_scale, causal=causal, keep_first=keep_first,
+                                                 keep_local=keep_local, share_group=share))
+    else:
+        top_k, keep_first, keep_local = block_select_value(*select, causal)
     if P == 1:
         return BlockMask(select_blocks(q, k, top_k, softmax_scale=softmax_scale, causal=causal, keep_first=keep_first,
                                        keep_local=keep_local))
@@ -218,6 +229,9 @@ def select_block_rows(q, k, select, softmax_scale, causal, group):
     gathered = torch.empty((P * B, n, Hkv, D), dtype=torch.float32, device=kbar_local.device)
     dist.all_gather_into_tensor(gathered, kbar_local.contiguous(), group=group)
     kbar = gathered.view(P, B, n, Hkv, D).permute(1, 0, 2, 3, 4).reshape(B, P * n, Hkv, D)   # (rank-major -> the global order)
+    if top_p:
+        return BlockMask(be.block_select_top_p(qbar, kbar.contiguous(), p, scale, bool(causal), keep_first, keep_local, share, r * n),
+                         rows_only=True)
     return BlockMask(be.block_select(qbar, kbar.contiguous(), top_k, scale, bool(causal), keep_first, keep_local, r * n), rows_only=True)
 
 

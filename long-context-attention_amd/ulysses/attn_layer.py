@@ -47,7 +47,7 @@ class UlyssesAttention(torch.nn.Module):
         # `return_max_logits`: judged alone and first (kernels/features.py: max_logits_alone)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                               block_select=block_select)
-        # `block_select`: a BlockSelect: the block mask is selected behind the exchange, on this rank's heads over the whole
+        # `block_select`: a BlockSelect or BlockSelectTopP: the block mask is selected behind the exchange, on this rank's heads over the whole
         # sequence (kernels/attention.py: select_blocks); judged alone, where block_mask is
         block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         # `block_mask`: a 128 x 128 block mask of the whole sequence (kernels/attention.py: hip_attn_forward), over the layer's
@@ -62,7 +62,8 @@ class UlyssesAttention(torch.nn.Module):
         head_kw, alibi_slopes = local_options(alibi_slopes, dropout_p, sinks, cu_doclens, query.shape[2],
                                               dist.get_world_size(self.spg), dist.get_rank(self.spg),
                                               (self.scatter_idx, self.gather_idx) == (2, 1), "scatter_idx=2, gather_idx=1",
-                                              bidirectional=bidirectional, block_mask=block_mask, block_select=block_select)
+                                              bidirectional=bidirectional, block_mask=block_mask, block_select=block_select,
+                                              kv_heads=key.shape[2])
         q, k, v = (self._to_heads(t, kv) for t, kv in ((query, False), (key, True), (value, True)))
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
