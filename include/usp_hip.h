@@ -138,6 +138,10 @@ enum {
 /* USP_ATTN_BLOCK_SELECT_TOP_P: a FEATURE bit like USP_ATTN_BLOCK_SELECT: the library exports usp_block_select_top_p (below), which
  * selects the block mask by cumulative softmax mass of the pooled scores in place of a fixed count (ABI still v7). */
 #define USP_ATTN_BLOCK_SELECT_TOP_P 65536
+/* USP_ATTN_BLOCK_MASS: a FEATURE bit like USP_ATTN_BLOCK_SELECT: the library exports usp_block_attn_mass (below), which returns the
+ * block-pooled attention map of a call -- the share of the softmax mass every 128 x 128 block holds (ABI still v7; the value is
+ * no flag of an argument block, where it means USP_DKDV_KEYS128). */
+#define USP_ATTN_BLOCK_MASS 131072
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
  * exists in two forms, both noted as USP_KIND_DKDV_ROW64:
  *   USP_DKDV_KEYS128  flash_bwd_dkdv64_kernel: a work item owns 128 keys, two waves share a 64-key slice (S, P, dV | dP, dS, dK);
@@ -637,6 +641,43 @@ int usp_block_select_top_p(const float* qbar, const float* kbar, int32_t B, int3
                            int32_t keep_local, int32_t share_group, void* mask, int64_t mask_stride_b, int64_t mask_stride_h,
                            int64_t mask_stride_row, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Block attention mass: the block-pooled attention map, the quantity the block gates above approximate (the recall of a block
+ * mask is the mass on its selected blocks; SeerAttention distils its gate from this map).  q is 16-bit (B, Sq, Hq, D), k 16-bit
+ * (B, Sk, Hkv, D), both with strides in elements and the head dim contiguous; lse is fp32 with lse[b * lse_stride_b +
+ * h * lse_stride_h + i] the log-sum-exp of row i (natural log, of the scaled scores: what usp_flash_fwd writes).  With
+ * G = Hq / Hkv, nbq = ceil(Sq / USP_BLOCK_MASK_SIZE), nbk = ceil(Sk / USP_BLOCK_MASK_SIZE), in real numbers:
+ *     mass[b][h][I][J] = (1 / rows(I)) * sum over the rows i of block I (i < Sq) and the keys j of block J VISIBLE to i of
+ *                        exp(scale * q[b][i][h] . k[b][j][h / G] - lse[b][h][i]),
+ * where every key j < Sk is visible, under causal != 0 only j <= i + diag, and rows(I) is the number of rows block I has (a
+ * ragged last block counts the rows it has: the rule of usp_block_means).  A row with lse = -inf contributes 0.  With the lse of
+ * the same attention call every row of mass sums to 1 over J (under sinks: to 1 minus the sink's share).  out[b * out_stride_b +
+ * h * out_stride_h + I * out_stride_row + J] is written for EVERY I < nbq, J < nbk (strides in elements: a caller may point it at
+ * a column slice of a larger result), blocks above the diagonal as 0.  fp32, no atomics, ordinary vector stores, nothing read on
+ * the host.  With NaN inputs or a +inf lse the result is unspecified; every access stays in range.
+ *
+ * One work item per (b, h, I) walks the 64-key tiles up to the item's last visible key: S^T = K Q^T on v_mfma_f32_32x32x16, one
+ * chain over ascending d per score, then p = exp2(fma(s, c, -(lse_i * log2e))) with c = scale * log2e (one fp32 product each; exp2 is
+ * v_exp_f32), a hidden key's p set to 0.  ORDER of the sum of one (I, J), a function of the position inside the block alone:
+ *   1. the lane of (row i = 32 w + l, half hf) adds ascending from 0.f its 64 keys: the tile of keys 128 J .. + 63, then the tile
+ *      128 J + 64 .. + 127; inside a tile at kt0 the keys kt0 + 4 hf + (r & 3) + 8 (r >> 2), r = 0 .. 15, then those + 32, r = 0 .. 15;
+ *   2. the two halves of a row: x(hf = 0) + x(hf = 1);
+ *   3. the 32 rows l of wave w by the butterfly x += x[l ^ 16], ^ 8, ^ 4, ^ 2, ^ 1;
+ *   4. the four waves ((w0 + w1) + w2) + w3;   5. one division by rows(I).
+ * Terms left out (hidden keys, rows past Sq, tiles the item does not reach) enter as +0.  So the result repeats from call to
+ * call and does not depend on the grid, B or H; a launch on the rows [r n, (r + 1) n) against the keys [c n, (c + 1) n), n a
+ * multiple of 128, with diag = (r - c) * n gives bit for bit the corresponding sub-matrix of the whole call (a ring's step).
+ *   - a NULL pointer, a non-positive size, a negative stride, a dtype other than USP_BF16 / USP_FP16 or a NaN scale is USP_EINVAL;
+ *   - D other than 32 / 64 / 128, Hq % Hkv != 0, q / k off a 16-byte boundary or with a stride that is no multiple of 8 elements,
+ *     lse / out off a 4-byte boundary, Sq, Sk or |diag| >= 2^29 and a k row stride of 2^24 elements or more are
+ *     USP_EUNSUPPORTED; nothing is launched or written.
+ * -------------------------------------------------------------------------------------------- */
+int usp_block_attn_mass(const void* q, const void* k, const float* lse, int32_t dtype, int32_t B, int32_t Sq, int32_t Sk, int32_t Hq,
+                        int32_t Hkv, int32_t D, int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, int64_t k_stride_b,
+                        int64_t k_stride_s, int64_t k_stride_h, int64_t lse_stride_b, int64_t lse_stride_h, float scale,
+                        int32_t causal, int32_t diag, float* out, int64_t out_stride_b, int64_t out_stride_h, int64_t out_stride_row,
+                        void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -739,9 +780,9 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
  * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT |
- * USP_ATTN_BLOCK_SELECT_TOP_P, the last nine feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span / *_bsp / *_maxlogit /
- * usp_block_means and usp_block_select / usp_block_select_top_p entry points exist).  Unknown flag bits are not rejected by
- * usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
+ * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS, the last ten feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
+ * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist).
+ * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);
 

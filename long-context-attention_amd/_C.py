@@ -39,6 +39,7 @@ USP_ATTN_BLOCK_SELECT = 32768  # feature bit of usp_attn_features(): usp_block_m
 USP_DKDV_KEYS256 = 65536       # usp_flash_bwd: 256-key items for the 64-row family's dK/dV launch (one wave does all four products) ...
 USP_DKDV_KEYS128 = 131072      # ... or its 128-key items (two waves share a 64-key slice); neither: the library picks per launch
 USP_ATTN_BLOCK_SELECT_TOP_P = 65536  # feature bit of usp_attn_features(): usp_block_select_top_p exists (not an args flag)
+USP_ATTN_BLOCK_MASS = 131072   # feature bit of usp_attn_features(): usp_block_attn_mass exists (not an args flag)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
@@ -135,7 +136,7 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
-           "usp_block_select_top_p")
+           "usp_block_select_top_p", "usp_block_attn_mass")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -148,6 +149,7 @@ BSP_EXPORTS = ("usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_b
 MAXL_EXPORTS = ("usp_flash_fwd_maxlogit", "usp_row_max_reduce")
 SELECT_EXPORTS = ("usp_block_means", "usp_block_select")
 SELECT_TOP_P_EXPORTS = ("usp_block_select_top_p",)
+MASS_EXPORTS = ("usp_block_attn_mass",)
 
 
 def lib_path() -> str:
@@ -166,7 +168,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -659,6 +661,33 @@ def block_select_top_p(qbar, kbar, top_p, scale: float, causal: bool, keep_first
     return out
 
 
+def block_attn_mass(q, k, lse, scale: float, causal: bool, diag: int = 0, out=None):
+    """usp_block_attn_mass: the block-pooled attention map (include/usp_hip.h) of 16-bit q (B, Sq, Hq, D) and k (B, Sk, Hkv, D) with
+    unit head-dim stride (kernels/attention.py: kernel_operand) and the fp32 lse (B, Hq, Sq) with unit last stride; under `causal`
+    row i sees key j iff j <= i + diag.  `out`: an fp32 (B, Hq, nbq, nbk) device tensor with unit last stride -- a column slice
+    of a larger result serves; None: a new one.  Every element of `out` is written."""
+    _require_cuda(q, k, lse)
+    B, Sq, Hq, D = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    if k.shape[0] != B or k.shape[3] != D or k.dtype != q.dtype:
+        raise ValueError(f"block_attn_mass: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} do not belong together")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (B, Hq, Sq):
+        raise ValueError(f"block_attn_mass: lse must be an fp32 ({B}, {Hq}, {Sq}) tensor, got {tuple(lse.shape)} {lse.dtype}")
+    nbq, nbk = (Sq + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE, (Sk + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if out is None:
+        out = torch.empty((B, Hq, nbq, nbk), dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Hq, nbq, nbk) or (nbk > 1 and out.stride(-1) != 1) \
+            or out.device != q.device:
+        raise ValueError(f"block_attn_mass: out must be an fp32 ({B}, {Hq}, {nbq}, {nbk}) tensor with unit last stride on {q.device}")
+    tq, tk = _t4(q), _t4(k)
+    lp, lsb, lsh = _lse3(lse)
+    _check(_feature_entry("usp_block_attn_mass")(tq.ptr, tk.ptr, lp, dtype_code(q.dtype), B, Sq, Sk, Hq, Hkv, D, tq.stride_b,
+                                                 tq.stride_s, tq.stride_h, tk.stride_b, tk.stride_s, tk.stride_h, lsb, lsh,
+                                                 float(scale), 1 if causal else 0, int(diag), _ptr(out), out.stride(0),
+                                                 out.stride(1), out.stride(2), _stream()), "usp_block_attn_mass")
+    return out
+
+
 def _feature_entries():
     """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
     does not insist on."""
@@ -685,7 +714,10 @@ def _feature_entries():
             "usp_block_select": (USP_ATTN_BLOCK_SELECT, "block_select (USP_ATTN_BLOCK_SELECT)",
                                  [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, i32, i32, i32, vp, i64, i64, i64, vp]),
             "usp_block_select_top_p": (USP_ATTN_BLOCK_SELECT_TOP_P, "block_select=BlockSelectTopP (USP_ATTN_BLOCK_SELECT_TOP_P)",
-                                       [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, i32, i32, vp, i64, i64, i64, vp])}
+                                       [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, i32, i32, vp, i64, i64, i64, vp]),
+            "usp_block_attn_mass": (USP_ATTN_BLOCK_MASS, "return_block_mass (USP_ATTN_BLOCK_MASS)",
+                                    [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, f32,
+                                     i32, i32, vp, i64, i64, i64, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -705,7 +737,7 @@ def _feature_entry(name: str):
     return fn
 
 
-_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _select_entry = _select_top_p_entry = _feature_entry      # (the names the per-feature tests call it by)
+_alibi_entry = _dropout_entry = _sink_entry = _doc_entry = _span_entry = _bsp_entry = _maxl_entry = _select_entry = _select_top_p_entry = _mass_entry = _feature_entry      # (the names the per-feature tests call it by)
 
 
 def _ptr(t):

@@ -15,6 +15,7 @@ from .comm.extract_local import (
     zigzag_extract_local,
     EXTRACT_FUNC_DICT,
 )
-from .kernels import AttnType, BlockSelect, BlockSelectTopP, select_blocks, select_blocks_top_p, select_flash_attn_impl
+from .kernels import (AttnType, BlockSelect, BlockSelectTopP, block_attention_mass, block_mask_recall, select_blocks,
+                      select_blocks_top_p, select_flash_attn_impl)
 
 __version__ = "0.6.0"

@@ -410,7 +410,7 @@ extern "C" int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32
 }
 
 extern "C" int usp_abi_version(void) { return USP_ABI_VERSION; }
-extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT | USP_ATTN_BLOCK_SELECT_TOP_P; }
+extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT | USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS; }
 
 // What the calling thread's last flash call launched (include/usp_hip.h: usp_last_launch_kinds).  Thread-local: the entry
 // points share no mutable state.

@@ -518,8 +518,11 @@ class AsyncLongContextAttention(torch.nn.Module):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
-                return_max_logits=False, block_select=None) -> Tensor:
+                return_max_logits=False, block_select=None, return_block_mass=False) -> Tensor:
         """query (bs, seqlen/P, hc, hs); key/value (bs, seqlen/P, hc_kv, hs) -> (bs, seqlen/P, hc, hs)."""
+        if return_block_mass:
+            raise NotImplementedError("return_block_mass is not supported by AsyncLongContextAttention (its head-group pipeline "
+                                      "keeps neither the exchanged k nor one lse per call): use LongContextAttention")
         if block_select is not None:
             raise NotImplementedError("block_select is not supported by AsyncLongContextAttention (its head-group pipeline issues "
                                       "blocks in pieces): use LongContextAttention with the basic ring (ring_impl_type=\"basic\")")

@@ -19,7 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone
+from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone, return_block_mass_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -139,7 +139,8 @@ class LongContextAttention(_USPLayer):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
                 deterministic=False, return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None,
-                bidirectional=None, block_mask=None, return_max_logits=False, block_select=None) -> Tensor:
+                bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
+                return_block_mass=False) -> Tensor:
         """query (bs, seq_len/N, head_cnt, head_size); key/value (bs, seq_len/N, kv_head_cnt,
         head_size) -> context (bs, seq_len/N, head_cnt, head_size).  `sinks` (keyword only): one learned logit per head of the
         layer, (head_cnt,) fp32 or the operands' type (comm/all_to_all.py: local_options: the gradient contract).  `cu_doclens` (keyword
@@ -163,7 +164,16 @@ class LongContextAttention(_USPLayer):
         behind the head exchange, from the q and k of the whole sequence (kernels/attention.py: select_blocks) -- the call with
         block_mask=select_blocks(q, k, ...) of the gathered sequence and the layer's heads.  Served where block_mask is (on a ring
         of degree > 1 each rank pools its slices and the pooled keys are all-gathered: ring/front_end.py: select_block_rows); not
-        together with block_mask or anything block_mask refuses.  None: exactly the call without it."""
+        together with block_mask or anything block_mask refuses.  None: exactly the call without it.
+        `return_block_mass` (keyword only; beside no other option): the result is (context, mass), mass fp32 without gradient: this
+        rank's SHARE of the block-pooled attention map of the whole sequence (kernels/attention.py: block_attention_mass) -- the
+        heads it holds behind the exchange (comm/all_to_all.py: local_heads) and its ring shard's n row blocks against all nb key
+        blocks, (bs, head_cnt / ulysses degree, n, nb) (ring/front_end.py: ring_block_attention_mass: K alone makes a second
+        rotation behind the forward, from the exchanged k and the ring's lse).  The layer gathers nothing and reads nothing on
+        the host.  Served with the basic ring at any ring degree (a local length behind the exchange that is a multiple of
+        128), with the zigzag and stripe rings at ring degree 1, through three exchanges."""
+        bmass = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
+                                        bidirectional, block_mask, block_select, return_max_logits)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                               block_select=block_select)
         block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
@@ -173,12 +183,12 @@ class LongContextAttention(_USPLayer):
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
                                causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
                                cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml,
-                               block_select=block_select)
-            return (out[0][..., :D], out[1]) if ml else out[..., :D]
+                               block_select=block_select, return_block_mass=bmass)
+            return (out[0][..., :D], out[1]) if ml or bmass else out[..., :D]
         cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1], bidirectional)     # (the single document: None from here on)
         ng_cap = self._packed_exchange(query, key)
         if ng_cap is not None and (block_mask is not None or block_select is not None or cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
-                                   or dropout_value(dropout_p) is not None or sinks is not None or ml):
+                                   or dropout_value(dropout_p) is not None or sinks is not None or ml or bmass):
             # Any of them: the reference's structure (three exchanges), and the ring function serves it (ring/front_end.py: _place).
             # The pipeline issues blocks in row pieces and head groups: under a document mask each piece would need its own
             # arrays; a sliding window is served by the basic ring function at ring degree 1 and, with USP_RING_WINDOW=global,
@@ -197,8 +207,12 @@ class LongContextAttention(_USPLayer):
         options.update(head_kw)
         if ml:
             options["return_max_logits"] = True
+        if bmass:
+            options["return_block_mass"] = True
         if self.ulysses_size == 1:      # nothing to exchange (the reference still makes 8 layout copies here)
             res = self.ring_attn_fn(query, key, value, attn_processor=self.attn_processor, **options)
+            if bmass:
+                return _first(res), res[-1]
             return (_first(res), self._max_logits(res, query.shape[2])) if ml else _first(res)
         # sequence shards -> head shards: (bs, seq_len/N, heads, d) -> (bs, seq_len, heads/N, d); k and v through the KV
         # form (a KV head shared by several ranks travels to each of them, and their gradients are summed)
@@ -207,6 +221,8 @@ class LongContextAttention(_USPLayer):
         res = self.ring_attn_fn(q, k, v, attn_processor=self.attn_processor, **options)
         # ... and back: (bs, seq_len, heads/N, d) -> (bs, seq_len/N, heads, d)
         context = SeqAllToAll4D.apply(self.ulysses_pg, _first(res), self.gather_idx, self.scatter_idx, self.use_sync, False)
+        if bmass:                       # (the ring function's share: this rank's heads, its ring shard's row blocks)
+            return context, res[-1]
         return (context, self._max_logits(res, query.shape[2])) if ml else context
 
 
@@ -224,9 +240,12 @@ class LongContextAttentionQKVPacked(_USPLayer):
     def forward(self, qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                 softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                 *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False,
-                block_select=None) -> Tensor:
+                block_select=None, return_block_mass=False) -> Tensor:
         """`return_max_logits` (keyword only): (out, max_logits) as LongContextAttention.forward returns it.  `block_select`
-        (keyword only): as LongContextAttention.forward takes it."""
+        (keyword only): as LongContextAttention.forward takes it.  `return_block_mass` (keyword only): (out, mass) as
+        LongContextAttention.forward returns it."""
+        bmass = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
+                                        bidirectional, block_mask, block_select, return_max_logits)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                               block_select=block_select)
         block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
@@ -236,8 +255,8 @@ class LongContextAttentionQKVPacked(_USPLayer):
             out = self.forward(pad_head_dim(qkv)[0], dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                                window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
                                cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml,
-                               block_select=block_select)
-            return (out[0][..., :D], out[1]) if ml else out[..., :D]
+                               block_select=block_select, return_block_mass=bmass)
+            return (out[0][..., :D], out[1]) if ml or bmass else out[..., :D]
         exchange = self.ulysses_size > 1
         cu_doclens = self._docs(cu_doclens, qkv.shape[0], qkv.shape[1], bidirectional)
         head0, alibi_slopes = self._head_options(alibi_slopes, dropout_p, sinks, cu_doclens, qkv.shape[3], self.scatter_idx - 1,
@@ -247,9 +266,11 @@ class LongContextAttentionQKVPacked(_USPLayer):
         heads = qkv.shape[3] * (self.ulysses_size if exchange else 1)          # (of the layer: qkv holds this rank's by now)
         res = self.ring_attn_fn(qkv, **self._ring_options(dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
                                                           deterministic, return_attn_probs), **head0,
-                                **(dict(return_max_logits=True) if ml else {}))
+                                **(dict(return_max_logits=True) if ml else {}), **(dict(return_block_mass=True) if bmass else {}))
         out = _first(res)
         if exchange:         # (bs, seq_len, head_cnt/N, head_size) -> (bs, seq_len/N, head_cnt, head_size)
             out = SeqAllToAll4D.apply(self.ulysses_pg, out, self.gather_idx, self.scatter_idx - 1,
                                       self.use_sync, False)
+        if bmass:
+            return out, res[-1]
         return (out, self._max_logits(res, heads)) if ml else out

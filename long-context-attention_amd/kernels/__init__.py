@@ -8,6 +8,8 @@ the vendor-specific types that are out of scope (SageAttention, FlashInfer, Asce
 from enum import Enum
 
 from .attention import (
+    block_attention_mass,
+    block_mask_recall,
     HipBlockBackend,
     get_block_backend,
     hip_attn_backward,
@@ -73,4 +75,4 @@ def select_flash_attn_impl(impl_type: AttnType, stage: str = "fwd-bwd", attn_pro
 
 __all__ = ["AttnType", "select_flash_attn_impl", "hip_attn_forward", "hip_attn_backward",
            "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect",
-           "select_blocks_top_p", "BlockSelectTopP"]
+           "select_blocks_top_p", "BlockSelectTopP", "block_attention_mass", "block_mask_recall"]

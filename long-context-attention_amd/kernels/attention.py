@@ -15,7 +15,7 @@ import torch
 
 from .. import _C
 from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
-                       block_select_alone, expand_block_mask, max_logits_alone)
+                       block_select_alone, expand_block_mask, max_logits_alone, return_block_mass_alone)
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -105,6 +105,12 @@ class HipBlockBackend:
     def block_select_top_p(self, qbar, kbar, top_p, scale, causal, keep_first=0, keep_local=1, share_group=False, row_block0=0):
         """torch.bool (B, Hq, nbq, nbk): block_select's mask by cumulative softmax mass (usp_block_select_top_p; no host read)."""
         return _C.block_select_top_p(qbar, kbar, top_p, scale, causal, keep_first, keep_local, share_group, row_block0)
+
+    def block_mass(self, q, k, lse, scale, causal, diag=0, out=None):
+        """fp32 (B, Hq, nbq, nbk): the share of the softmax mass the rows of every 128-row block of q give to every 128-key block
+        of k, from the rows' `lse`; under `causal` row i sees key j iff j <= i + diag; `out` may be a column slice of a larger
+        result (usp_block_attn_mass; no host read)."""
+        return _C.block_attn_mass(q, k, lse, scale, causal, diag, out)
 
     def delta(self, dout, out, delta):
         _C.bwd_delta(dout, out, delta)
@@ -412,9 +418,51 @@ def _selected(block_select, q, k, softmax_scale, causal):
                          keep_local=block_select.keep_local)
 
 
+def mass_operands(q, k, lse, softmax_scale=None):
+    """(q, k, lse, scale) as usp_block_attn_mass takes them: select_operands' q and k, and the fp32 lse (B, Hq, S_q) with a unit
+    last stride, read as a value."""
+    if lse.dim() != 3 or tuple(lse.shape) != (q.shape[0], q.shape[2], q.shape[1]):
+        raise ValueError(f"block attention mass takes the lse (B, Hq, S) of q (B, S, Hq, D), got {tuple(lse.shape)} beside "
+                         f"{tuple(q.shape)}")
+    q, k, scale = select_operands(q, k, softmax_scale)
+    with torch.no_grad():
+        lse = lse.detach()
+        if lse.dtype != torch.float32:
+            lse = lse.float()
+        if lse.stride(-1) != 1:
+            lse = lse.contiguous()
+    return q, k, lse, scale
+
+
+def block_attention_mass(q, k, lse, *, softmax_scale=None, causal=False):
+    """The block-pooled attention map of a self-attention call: fp32 (B, Hq, nb, nb), nb = ceil(S / 128), of q (B, S, Hq, D), k
+    (B, S, Hkv, D) (bf16 / fp16, any strides with a unit last one) and the call's `lse` (B, Hq, S) -- what
+    hip_attn_func(..., return_attn_probs=True) returns.  mass[b, h, I, J] is the mean over the rows i of block I of the attention
+    probability row i gives to the keys of block J: sum_j exp(softmax_scale * q_i . k_j - lse_i) over the keys j of J that i
+    sees (every key, under `causal` j <= i); a ragged last block is averaged over the rows it has, a row with lse = -inf adds 0,
+    blocks above the diagonal are 0 and every element is written.  With the lse of the same call every row of the map sums to 1;
+    with the lse of a call with sinks, to 1 minus the sink's share -- the function takes whatever lse it is given.  It is the
+    ground truth the block gates (select_blocks, select_blocks_top_p) approximate: block_mask_recall(mass, mask) is the recall of
+    a mask.  Computed on the device by one kernel that forms no S x S scores in memory (include/usp_hip.h: usp_block_attn_mass
+    states the order of every sum; results repeat bit for bit); never read on the host, no gradient.  Padded head dims are
+    included.  NotImplementedError: q and k of different lengths."""
+    block_mask_self_attention(q.shape[1], k.shape[1], "block_attention_mass")
+    q, k, lse, scale = mass_operands(q, k, lse, softmax_scale)
+    return get_block_backend().block_mass(q, k, lse, scale, bool(causal), 0)
+
+
+def block_mask_recall(mass, mask):
+    """The recall of a block mask under a block attention map: (B, Hq, nbq), the sum over J of mass * mask -- the share of the
+    softmax mass of every row block that lies on the blocks the mask selects (the figure the FlexPrefill / XAttention /
+    MInference papers report).  `mass`: (B, Hq, nbq, nbk) from block_attention_mass or a rank's rows-only share from
+    ring_block_attention_mass; `mask`: a torch.bool mask that broadcasts against it (select_blocks' result, a ring rank's
+    select_block_rows).  Plain torch, on the device of its arguments."""
+    return (mass * mask.to(mass.dtype)).sum(dim=-1)
+
+
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                      softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
-                     bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
+                     bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -444,7 +492,15 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     block_mask=select_blocks(q, k, top_k, softmax_scale=, causal=, keep_first=, keep_local=) -- the same launches behind the two
     selection kernels, the same bits; or a BlockSelectTopP(top_p, keep_first=0, keep_local=1, share_group=False): likewise the
     call with block_mask=select_blocks_top_p(q, k, top_p, ...).  Not together with block_mask or anything block_mask refuses.  None: the call without it.
-    (hip_attn_backward takes the mask, not the selection.)"""
+    (hip_attn_backward takes the mask, not the selection.)
+    `return_block_mass` (keyword only): the result is (out, lse, mass), mass = block_attention_mass(q, k, lse, ...) of the call's
+    own lse, computed behind the forward: fp32 (B, Hq, nb, nb) without gradient.  out and lse are bit for bit those of the call
+    without it.  Goes with none of the other options and needs equally long q and k.  False: exactly the call without it."""
+    if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                               block_mask, block_select, return_max_logits):
+        block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")
+        out, lse = hip_attn_forward(q, k, v, softmax_scale=softmax_scale, causal=causal)
+        return out, lse, block_attention_mass(q, k, lse, softmax_scale=softmax_scale, causal=causal)
     if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                         block_select=block_select):
         B, Sq, Hq, D = q.shape
@@ -581,7 +637,7 @@ class _HipAttnFunc(torch.autograd.Function):
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                   *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False,
-                  block_select=None, **kwargs):
+                  block_select=None, return_block_mass=False, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -601,7 +657,18 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     window_size alone.
     `block_select` (keyword only): a BlockSelect or a BlockSelectTopP: the block mask is selected here, once, from the values
     of q and k (select_blocks / select_blocks_top_p; no gradient through the gate), and the call is the one with that block_mask: the autograd node keeps the mask
-    for its backward, which never selects again."""
+    for its backward, which never selects again.
+    `return_block_mass` (keyword only): the result becomes `(out, mass)`, with return_attn_probs `(out, softmax_lse, None, mass)`:
+    the fp32 (B, Hq, nb, nb) block-pooled attention map of the call (block_attention_mass on the call's own lse, computed under
+    no_grad behind the forward), padded head dims included; no gradient, never read on the host.  `out`, the lse and the
+    gradients are bit for bit those of the call without it.  Goes with none of the other options."""
+    if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                               block_mask, block_select, return_max_logits):
+        block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")
+        out, lse, _ = hip_attn_func(q, k, v, softmax_scale=softmax_scale, causal=causal, deterministic=deterministic,
+                                    return_attn_probs=True)
+        mass = block_attention_mass(q, k, lse, softmax_scale=softmax_scale, causal=causal)
+        return (out, lse, None, mass) if return_attn_probs else (out, mass)
     if max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                         block_select=block_select):
         D = q.shape[-1]

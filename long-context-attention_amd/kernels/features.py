@@ -114,6 +114,25 @@ def max_logits_alone(return_max_logits, softcap=None, alibi_slopes=None, dropout
     return True
 
 
+def return_block_mass_alone(return_block_mass, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
+                            cu_doclens=None, bidirectional=None, block_mask=None, block_select=None, return_max_logits=False) -> bool:
+    """Is `return_block_mass` on?  Like return_max_logits it is no field of the record: it is judged HERE, before Features.of and
+    before any tensor is read.  The map is that of the plain softmax under the causal mask alone -- the kernel behind it
+    (usp_block_attn_mass) holds no second mask and no score-level step -- so the keyword goes with none of the other options.
+    (The stand-alone block_attention_mass takes whatever lse it is given: that is how a caller gets the map of a call with
+    sinks.)  False / None is exactly the call without the keyword."""
+    if not return_block_mass:
+        return False
+    given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
+             ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens),
+             ("bidirectional", bidirectional), ("block_mask", block_mask), ("block_select", block_select),
+             ("return_max_logits", return_max_logits or None))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"return_block_mass together with {name} is not supported by the HIP attention kernels")
+    return True
+
+
 def block_mask_self_attention(Sq: int, Sk: int, name: str = "block_mask"):
     """A block mask (given, or selected: `name`) covers one sequence against itself."""
     if Sq != Sk:

@@ -17,6 +17,8 @@ for _module, _stem in ((ring_flash_attn, "ring_flash_attn"), (zigzag_ring_flash_
                        (zigzag_ring_flash_attn_varlen, "zigzag_ring_flash_attn_varlen")):
     _export(_module, [f"{_stem}{suffix}" for suffix in ("_func", "_kvpacked_func", "_qkvpacked_func")])
 _export(utils, ["RingComm", "KVRelay", "update_out_and_lse"])
+from . import front_end  # noqa: E402
+_export(front_end, ["ring_block_attention_mass"])
 _export(varlen_utils, ["extract_local_varlen", "flatten_lse", "unflatten_lse"])
 
 

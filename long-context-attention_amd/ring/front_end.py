@@ -8,11 +8,11 @@ import torch.distributed as dist
 
 from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_top_p_value, block_select_value, dropout_value, softcap_value
 from ..kernels import AttnType
-from ..kernels.attention import (draw_seed, get_block_backend, kernel_head_dim, kernel_operand, needs_grad, pad_head_dim,
-                                 select_blocks, select_blocks_top_p, select_operands)
+from ..kernels.attention import (block_attention_mass, draw_seed, get_block_backend, kernel_head_dim, kernel_operand,
+                                 mass_operands, needs_grad, pad_head_dim, select_blocks, select_blocks_top_p, select_operands)
 from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone,
-                                max_logits_alone)
-from .utils import group_info
+                                max_logits_alone, return_block_mass_alone)
+from .utils import RingComm, group_info
 from .varlen_utils import unflatten_lse
 
 
@@ -158,6 +158,70 @@ def _refuse_packed_max_logits(return_max_logits):
     if return_max_logits:
         raise NotImplementedError("return_max_logits is not supported by the variable-length (packed) rings: use a dense ring "
                                   "(ring_flash_attn_func, zigzag_ring_flash_attn_func, stripe_flash_attn_func)")
+
+
+def _refuse_packed_block_mass(return_block_mass):
+    if return_block_mass:
+        raise NotImplementedError("return_block_mass is not supported by the variable-length (packed) rings: use "
+                                  "LongContextAttention (ring_impl_type=\"basic\") or ring_flash_attn_func on dense batches")
+
+
+def ring_block_attention_mass(q, k, lse, *, softmax_scale=None, causal=False, group=None):
+    """The block-pooled attention map (kernels/attention.py: block_attention_mass) of the BASIC ring, this rank's share: rank r of
+    ring degree P holds the rows [r S, (r + 1) S) of the whole sequence (q (B, S, Hq, D), k (B, S, Hkv, D), and the ring's lse
+    (B, Hq, S) of those rows -- what ring_flash_attn_func(..., return_attn_probs=True) returns) and gets the rows-only share
+    fp32 (B, Hq, n, nb), n = S / 128 row blocks against all nb = P n key blocks: the coordinates of a ring rank's selected mask
+    (select_block_rows), so block_mask_recall takes both.  The shares of the ranks, stacked along the row-block dim in rank
+    order, are the single-device map bit for bit.  K alone makes the ring's rotation -- P - 1 hops, no V: step s holds the keys
+    of ring rank kr = r - s (mod P) and writes the column slice [kr n, (kr + 1) n) with the diagonal s * S
+    (include/usp_hip.h: usp_block_attn_mass).  Under `causal` the steps s > r launch nothing and their slices stay zero.  No
+    gradient, nothing read on the host.  Ring degree 1: block_attention_mass.  NotImplementedError: q and k of different
+    lengths, a local length that is no multiple of 128 at ring degree > 1."""
+    P, r = group_info(dist, group)
+    if P == 1:
+        return block_attention_mass(q, k, lse, softmax_scale=softmax_scale, causal=causal)
+    block_mask_self_attention(q.shape[1], k.shape[1], "ring_block_attention_mass")
+    S = q.shape[1]
+    if S % BLOCK_MASK_SIZE:
+        raise NotImplementedError(f"ring_block_attention_mass at ring degree {P} needs a local sequence length that is a multiple "
+                                  f"of {BLOCK_MASK_SIZE} (whole blocks per rank), got {S}: pad the sequence")
+    q, k, lse, scale = mass_operands(q, k, lse, softmax_scale)
+    n = S // BLOCK_MASK_SIZE
+    make = torch.zeros if causal else torch.empty        # (causal: the slices of the steps that launch nothing stay zero)
+    mass = make((q.shape[0], q.shape[2], n, P * n), dtype=torch.float32, device=q.device)
+    be = get_block_backend()
+    kk = k.contiguous()
+    for step in range(P):
+        comm = nxt = None
+        if step + 1 < P:                                 # K alone travels: P - 1 hops
+            comm = RingComm(group)
+            nxt = comm.send_recv(kk)
+            comm.commit()
+        if not causal or step <= r:
+            kr = (r - step) % P
+            be.block_mass(q, kk, lse, scale, bool(causal), step * S, mass[..., kr * n:(kr + 1) * n])
+        if comm is not None:
+            comm.wait()
+            kk = nxt
+    return mass
+
+
+def block_mass_call(serves, call, q, k, softmax_scale, causal, group, return_attn_probs):
+    """A dense ring call under `return_block_mass` (judged alone already: nothing else is on): `call(return_attn_probs=True)` --
+    the call without the keyword, bit for bit -- and behind it the rank's share of the map from the call's own lse
+    (ring_block_attention_mass).  The zigzag and stripe rings hold other rows than the basic ring's slices: they serve ring
+    degree 1."""
+    P = group_info(dist, group)[0]
+    if P > 1 and serves.block_mask != ANY_DEGREE:
+        raise NotImplementedError(f"return_block_mass across ring steps (ring degree > 1) is not supported by the zigzag and "
+                                  f"stripe rings: {_BASIC}")
+    block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")
+    if P > 1 and q.shape[1] % BLOCK_MASK_SIZE:
+        raise NotImplementedError(f"return_block_mass at ring degree {P} needs a local sequence length that is a multiple of "
+                                  f"{BLOCK_MASK_SIZE} (whole blocks per rank), got {q.shape[1]}: pad the sequence")
+    out, lse, _ = call(True)
+    mass = ring_block_attention_mass(q, k, lse, softmax_scale=softmax_scale, causal=causal, group=group)
+    return (out, lse, None, mass) if return_attn_probs else (out, mass)
 
 
 def block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_select=None):
@@ -411,7 +475,9 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
     if packed:
         def func(q, k, v, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
-                 cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
+                 cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
+                 return_block_mass=False):
+            _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
             _refuse_packed_block_select(block_select)
@@ -422,7 +488,9 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def kvpacked_func(q, kv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
+                          group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
+                 return_block_mass=False):
+            _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
             _refuse_packed_block_select(block_select)
@@ -433,7 +501,9 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
 
         def qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0, softmax_scale=None, causal=False,
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
-                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
+                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
+                 return_block_mass=False):
+            _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
             _refuse_packed_block_select(block_select)
@@ -455,7 +525,13 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                  attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
-                 bidirectional=None, block_mask=None, return_max_logits=False, block_select=None):
+                 bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                       block_mask, block_select, return_max_logits):
+                return block_mass_call(serves, lambda probs: func(q, k, v, 0.0, softmax_scale, causal, deterministic=deterministic,
+                                                                  return_attn_probs=probs, group=group, attn_type=attn_type,
+                                                                  attn_processor=attn_processor),
+                                       q, k, softmax_scale, causal, group, return_attn_probs)
             ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                                   block_select=block_select)
             cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
@@ -477,7 +553,13 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
-                          block_mask=None, return_max_logits=False, block_select=None):
+                          block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                       block_mask, block_select, return_max_logits):
+                return block_mass_call(serves, lambda probs: kvpacked_func(q, kv, 0.0, softmax_scale, causal,
+                                                                           deterministic=deterministic, return_attn_probs=probs,
+                                                                           group=group, attn_type=attn_type),
+                                       q, kv[:, :, 0], softmax_scale, causal, group, return_attn_probs)
             ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                                   block_select=block_select)
             cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
@@ -489,7 +571,13 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         def qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                            attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
-                           block_mask=None, return_max_logits=False, block_select=None):
+                           block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                       block_mask, block_select, return_max_logits):
+                return block_mass_call(serves, lambda probs: qkvpacked_func(qkv, 0.0, softmax_scale, causal,
+                                                                            deterministic=deterministic, return_attn_probs=probs,
+                                                                            group=group, attn_type=attn_type),
+                                       qkv[:, :, 0], qkv[:, :, 1], softmax_scale, causal, group, return_attn_probs)
             ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                                   block_select=block_select)
             cu_doclens = block_mask_plan(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,

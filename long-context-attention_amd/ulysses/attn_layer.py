@@ -13,7 +13,7 @@ from torch import Tensor
 
 from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, layer_max_logits, local_options
 from ..kernels import AttnType, select_flash_attn_impl
-from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone
+from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone, return_block_mass_alone
 
 
 class UlyssesAttention(torch.nn.Module):
@@ -24,7 +24,10 @@ class UlyssesAttention(torch.nn.Module):
     holds its own heads and zeros elsewhere, the SUM over the group is the gradient, and the layer does no all-reduce.
     `return_max_logits` (keyword only; beside window_size alone): the result is (out, max_logits), max_logits fp32 (H,) over the
     layer's heads without gradient: this rank's SHARE -- the largest visible pre-softmax logit of the heads it holds behind the
-    exchange, -inf for the heads other ranks hold.  The MAX over the group is the value; the layer does no all-reduce."""
+    exchange, -inf for the heads other ranks hold.  The MAX over the group is the value; the layer does no all-reduce.
+    `return_block_mass` (keyword only; beside no other option): the result is (out, mass), mass fp32 (bs, H / N, nb, nb) without
+    gradient: the block-pooled attention map (kernels/attention.py: block_attention_mass) of the heads this rank holds behind the
+    exchange (comm/all_to_all.py: local_heads) over the whole sequence, from the call's own lse.  The layer gathers nothing."""
 
     def __init__(self, sequence_process_group: dist.ProcessGroup = None, scatter_idx: int = 2,
                  gather_idx: int = 1, use_sync: bool = False, attn_type: AttnType = AttnType.FA) -> None:
@@ -43,8 +46,11 @@ class UlyssesAttention(torch.nn.Module):
     def forward(self, query: Tensor, key: Tensor, value: Tensor, dropout_p=0.0, softmax_scale=None,
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
-                return_max_logits=False, block_select=None) -> Tensor:
-        # `return_max_logits`: judged alone and first (kernels/features.py: max_logits_alone)
+                return_max_logits=False, block_select=None, return_block_mass=False) -> Tensor:
+        # `return_block_mass`: judged alone and first (kernels/features.py: return_block_mass_alone)
+        bm = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                                     block_mask, block_select, return_max_logits)
+        # `return_max_logits`: judged alone (kernels/features.py: max_logits_alone)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                               block_select=block_select)
         # `block_select`: a BlockSelect or BlockSelectTopP: the block mask is selected behind the exchange, on this rank's heads over the whole
@@ -68,8 +74,11 @@ class UlyssesAttention(torch.nn.Module):
         options = dict(dropout_p=dropout_p, causal=causal, window_size=window_size, softcap=softcap,
                        alibi_slopes=alibi_slopes, deterministic=deterministic, return_attn_probs=return_attn_probs,
                        softmax_scale=q.shape[-1] ** -0.5 if softmax_scale is None else softmax_scale, **head_kw)
-        attended = self.attn_fn(q, k, v, **options, **(dict(return_max_logits=True) if ml else {}))
+        attended = self.attn_fn(q, k, v, **options, **(dict(return_max_logits=True) if ml else {}),
+                                **(dict(return_block_mass=True) if bm else {}))
         out = self._to_seq(attended[0] if isinstance(attended, tuple) else attended)
+        if bm:
+            return out, attended[-1]
         if not ml:
             return out
         return out, layer_max_logits(attended[-1], query.shape[2], dist.get_world_size(self.spg), dist.get_rank(self.spg))
