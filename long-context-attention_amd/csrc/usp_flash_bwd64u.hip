@@ -15,6 +15,16 @@
 // the dP chain's slots, dS's through the dV slots and the head of the dK slots; LDS fragments are read a few slots ahead of the
 // MFMA that takes them.  Every wave stages one 16-row group of Q and one of dO per tile (8 LDS-DMA pieces per 128 MFMAs), the
 // statistics wave works as in usp_flash_bwd64.hip, one barrier per tile.
+// What is NOT arithmetic is kept off the issue port, which is what bounds this kernel (profiles/dkdv64u_diet.txt):
+//   addresses   a swizzled LDS address is formed once per slice and serves every fragment that differs from it by an immediate:
+//               the seven kr ^ (32 j) of the Q rows serve the dO rows (+ TILEB), the seven tr ^ (64 dj [+ 32]) of dO^T serve its second
+//               k-step and both of Q^T's -- 28 v_xor per tile, not 56.  They live where other tile state is dead (see rd()).
+//   constants   the rows' constants of a chain are the same for both key blocks: ONE read, into key block 1's accumulator; key block
+//               0's first MFMA takes them from there as SrcC with its own accumulator as D.  No second read, no copy, and so no
+//               VALU write in front of an MFMA's SrcC: the plain loop's chains start without wait states.
+//   staging     the two LDS-DMA descriptors ARE the tile cursors (stepped in place, 3 scalar instructions each), a piece's row step
+//               rides its lanes' offsets instead of a scalar offset, the ring position is a byte offset, and the statistics rows'
+//               validity is recomputed where it is used instead of being carried as a lane mask.
 // Arithmetic is that kernel's, step for step (dS = the 16-bit P that feeds dV, unpacked, times (dP - delta); same tile, half and
 // k-step order): at equal dkdv_heads, dK and dV are bit-identical to it for uncut launches and for cut launches without a causal
 // bound (a cut causal launch cuts a block's second 128 keys at other query tiles than the 128-key item: tests/test_gpu_dkdv256.py).
@@ -81,6 +91,11 @@ template <int DT> struct MU;
     if (SAFE) asm volatile("s_nop 1\n\t" USP_MU_MN " %0, %1, %2, %0" : "+v"(s) : "v"(a), "v"(b));                     \
     else asm volatile(USP_MU_MN " %0, %1, %2, %0" : "+v"(s) : "v"(a), "v"(b));                                          \
   }                                                                                                                     \
+  /* a chain's FIRST step of key block 0: D = s, C = the rows' constants, which were read into key block 1's accumulator c */  \
+  template <bool SAFE = false> static USP_DEV void chain_from(f32x16& s, const u32x4& a, const u32x4& b, const f32x16& c) { \
+    if (SAFE) asm volatile("s_nop 1\n\t" USP_MU_MN " %0, %1, %2, %3" : "=&v"(s) : "v"(a), "v"(b), "v"(c));             \
+    else asm volatile(USP_MU_MN " %0, %1, %2, %3" : "=&v"(s) : "v"(a), "v"(b), "v"(c));                                 \
+  }                                                                                                                     \
   /* gradient accumulate: C/D = accumulator ac, A = transposed fragment, B = packed P / dS */                           \
   template <bool SAFE = false> static USP_DEV void grad(int ac, const u32x4& a, const u32x4& b) {                       \
     if (SAFE) asm volatile("s_nop 1");                                                                                  \
@@ -94,6 +109,7 @@ template <int DT> struct MU;
 #else
 #define USP_MU_BODY                                                                                                    \
   template <bool SAFE = false> static USP_DEV void chain(f32x16&, const u32x4&, const u32x4&) {}                        \
+  template <bool SAFE = false> static USP_DEV void chain_from(f32x16&, const u32x4&, const u32x4&, const f32x16&) {}    \
   template <bool SAFE = false> static USP_DEV void grad(int, const u32x4&, const u32x4&) {}                             \
   static USP_DEV void zero(int, const u32x4&) {}
 #endif
@@ -228,40 +244,54 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64u_kernel(const BwdPara
 
   // ---- LDS-DMA staging of the Q / dO tiles: wave w stages group w (16 rows) of Q and group w of dO ----------------------
   const int64_t tb1 = (int64_t)kTile * p->q_ss * 2, tb2 = (int64_t)kTile * p->do_ss * 2;     // bytes per tile step
-  int q_step = 4 * (int)p->q_ss * 2 - 1024, do_step = 4 * (int)p->do_ss * 2 - 1024;
   const int q_rowb = (int)p->q_ss * 2, do_rowb = (int)p->do_ss * 2;
   int lds_q = wave * 4096, lds_d = TILEB + wave * 4096;                        // LDS offsets of the groups inside a buffer
-  const char *q_cur = nullptr, *do_cur = nullptr;
+  // piece i of a group: rows 4 i .. 4 i + 3.  Its lanes' byte offsets carry the swizzle (^ 16 i) AND the row step (the instruction
+  // offset 1024 i, which places the piece in LDS, counts on the global side too): lane constants, nothing scalar per piece
+  int q_vo[4], do_vo[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    q_vo[i] = (q_voff ^ (16 * i)) + i * (4 * q_rowb - 1024);
+    do_vo[i] = (do_voff ^ (16 * i)) + i * (4 * do_rowb - 1024);
+  }
+  // the tile cursors ARE the descriptors (words 0-1: the 48-bit address, advanced in place; 2: the bytes the tile may read; 3: flags)
+  u32x4 q_rs = u32x4{0u, 0u, 0u, 0x00020000u}, do_rs = q_rs;
   int rows_g = 0;                                // valid rows from the cursors on (<= 0: nothing left, lanes read 0)
+  auto rs_move = [](u32x4& rs, int64_t by) {     // base += by, mod 2^48
+    const uint64_t a = (((uint64_t)rs[1] << 32) | rs[0]) + (uint64_t)by;
+    rs[0] = (uint32_t)a;
+    rs[1] = (uint32_t)(a >> 32) & 0xffffu;
+  };
 
   const float *lse_h = nullptr, *dl_h = nullptr;
   int st_row = 0;
   float st_lse = 0.f, st_delta = 0.f;
-  bool st_in = false;
   const bool stat_wave = wave == 0;
-  auto pf_head = [&](int h) {                    // base the cursors on query head h, tile t_begin (scalar work only)
-    q_cur = p->q + 2 * (b * p->q_sb + h * p->q_sh) + t_begin * tb1 + (int64_t)wave * 16 * q_rowb;
-    do_cur = p->dout + 2 * (b * p->do_sb + h * p->do_sh) + t_begin * tb2 + (int64_t)wave * 16 * do_rowb;
-    rows_g = p->Sq - t_begin * kTile - 16 * wave;
+  auto pf_head = [&](int h) {                    // base the cursors one tile IN FRONT of query head h's tile t_begin: dma_open steps first
+    const uint64_t qa = (uint64_t)(p->q + 2 * (b * p->q_sb + h * p->q_sh) + (t_begin - 1) * tb1 + (int64_t)wave * 16 * q_rowb);
+    const uint64_t da = (uint64_t)(p->dout + 2 * (b * p->do_sb + h * p->do_sh) + (t_begin - 1) * tb2 + (int64_t)wave * 16 * do_rowb);
+    q_rs[0] = (uint32_t)qa; q_rs[1] = (uint32_t)(qa >> 32) & 0xffffu;
+    do_rs[0] = (uint32_t)da; do_rs[1] = (uint32_t)(da >> 32) & 0xffffu;
+    rows_g = p->Sq - (t_begin - 1) * kTile - 16 * wave;
     lse_h = p->lse + b * p->lse_sb + h * p->lse_sh;
     dl_h = p->delta + b * p->dl_sb + h * p->dl_sh;
     st_row = t_begin * kTile;
   };
-  u32x4 q_rs, do_rs;
-  int dma_buf = 0;
-  auto dma_open = [&](int buf) {                 // descriptors of the cursor's tile for LDS buffer `buf`; advance the cursor
-    q_rs = make_rsrc_rows(q_cur, rows_g, 16, q_rowb, 2 * D);
-    do_rs = make_rsrc_rows(do_cur, rows_g, 16, do_rowb, 2 * D);
-    dma_buf = buf;
-    q_cur += tb1;
-    do_cur += tb2;
+  int dma_boff = 0;
+  auto dma_open = [&](int boff) {                // step the cursors to the next tile, for the LDS buffer at byte offset `boff`
+    rs_move(q_rs, tb1);
+    rs_move(do_rs, tb2);
     rows_g -= kTile;
+    const int r = (rows_g < 16 ? rows_g : 16) - 1;           // make_rsrc_rows (usp_mfma64.hpp): the group's last valid row ends the range
+    const int nq = r * q_rowb + 2 * D, nd = r * do_rowb + 2 * D;
+    q_rs[2] = (uint32_t)(nq > 0 ? nq : 0);
+    do_rs[2] = (uint32_t)(nd > 0 ? nd : 0);
+    dma_boff = boff;
   };
   auto stats_fetch = [&]() {
     if (stat_wave) {
       const int r = st_row + lane;
-      st_in = r < p->Sq;                         // rows past the end: P = 0 (their Q / dO rows read as zero)
-      const int rc = st_in ? r : p->Sq - 1;
+      const int rc = r < p->Sq ? r : p->Sq - 1;
       const float* pl = lse_h + rc;
       const float* pd = dl_h + rc;
       asm volatile("global_load_dword %0, %2, off\n\tglobal_load_dword %1, %3, off" : "=&v"(st_lse), "=&v"(st_delta) : "v"(pl), "v"(pd) : "memory");
@@ -269,17 +299,19 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64u_kernel(const BwdPara
     st_row += kTile;
   };
   auto dma_piece = [&](int n) {                  // n < 4: Q piece n, else dO piece n - 4
-    asm volatile("" : "+s"(lds_q), "+s"(lds_d), "+s"(q_step), "+s"(do_step));
+    asm volatile("" : "+s"(lds_q), "+s"(lds_d));
     const int i = n & 3;
-    if (n < 4) lds_dma16_asm(q_rs, lds_q + dma_buf * BUFB, q_voff ^ (16 * i), i * q_step, i);
-    else lds_dma16_asm(do_rs, lds_d + dma_buf * BUFB, do_voff ^ (16 * i), i * do_step, i);
+    if (n < 4) lds_dma16_asm(q_rs, lds_q + dma_boff, q_vo[i], 0, i);
+    else lds_dma16_asm(do_rs, lds_d + dma_boff, do_vo[i], 0, i);
   };
-  auto stats_store = [&](int buf) {              // behind the wave's vmcnt(0): the constants the chains START from
+  auto stats_store = [&](int boff) {             // behind the wave's vmcnt(0): the constants the chains START from
     if (stat_wave) {
       asm volatile("" : "+v"(st_lse), "+v"(st_delta));
+      const bool st_in = st_row - kTile + lane < p->Sq;      // the row stats_fetch asked for (not carried: a lane mask across the tile is
+                                                             // scalar work per tile).  Rows past the end: P = 0 (their Q / dO rows read as zero)
       const float l2 = (st_in && st_lse != USP_NEG_INF) ? st_lse * neg_inv_scale : -__builtin_inff();
-      *(USP_LDS float*)(smem + buf * BUFB + 2 * TILEB + 4 * lane) = l2;
-      *(USP_LDS float*)(smem + buf * BUFB + 2 * TILEB + 4 * kTile + 4 * lane) = st_in ? -st_delta : 0.f;
+      *(USP_LDS float*)(smem + boff + 2 * TILEB + 4 * lane) = l2;
+      *(USP_LDS float*)(smem + boff + 2 * TILEB + 4 * kTile + 4 * lane) = st_in ? -st_delta : 0.f;
     }
   };
 
@@ -295,7 +327,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_dkdv64u_kernel(const BwdPara
   // item, counted per wave: a tile none of whose rows sees the wave's keys runs fully masked, P = 0 -- run in a loop instance
   // of their own (MASK).  Every instance ends in the tile's one barrier, so the waves' barrier counts agree whatever n_mask is.
   const int n_mask = usp_masked_row_tiles(ow, CAUSAL, off, t_begin, n_iter, kTile);
-  int tile_cur = t_begin, buf_a = 0;
+  int tile_cur = t_begin, boff_a = 0;             // boff_a: byte offset of the LDS buffer that holds the current tile
 USP_TM(
   uint64_t tm_body = 0, tm_drain = 0, tm_bar = 0, tm_last = __builtin_amdgcn_s_memtime();
 )
@@ -305,40 +337,51 @@ USP_TM(
     static_assert(PE0 >= 17 && PE1 <= 40 && PE1 > PE0 && (PE0 + (PE1 - PE0 + 1) / 2) <= 31, "P of k-step 0 in front of dV");
     static_assert(SE0 >= 33 && SE1 <= 55 && SE1 > SE0 && (SE0 + (SE1 - SE0 + 1) / 2) <= 47, "dS of k-step 0 in front of dK");
     static_assert(LA >= 1 && LA <= 7, "");
-    const int buf_n = buf_a + 1 == NBUF ? 0 : buf_a + 1;
+    const int boff_n = boff_a + BUFB == NBUF * BUFB ? 0 : boff_a + BUFB;
     stats_fetch();
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int t = 0; t < NKT; ++t) { pin_vgpr4(kf[kb][t]); pin_vgpr4(vf[kb][t]); }
     const int s0 = tile_cur * kTile;
-    USP_LDS const char* stat = smem + buf_a * BUFB + 2 * TILEB + 16 * hi;
+    USP_LDS const char* stat = smem + boff_a + 2 * TILEB + 16 * hi;
     // the buffer base goes INTO the swizzled offsets before the XOR (bases are multiples of 256, the XORs touch bits 5-7)
-    int kr = rd_base + buf_a * BUFB, tr = tr_base + buf_a * BUFB;
+    int kr = rd_base + boff_a, tr = tr_base + boff_a;
+    int krx[8], trx[8];                          // kr ^ (32 j); tr ^ (64 dj) at dj, tr ^ (64 dj + 32) at 4 + dj: formed ONCE per slice
     f32x16 sc[2], dp[2];                         // S / dP - delta of the slice: [key block]
     u32x4 pkp[2][2], pks[2][2];                  // packed P / dS: [key block][k-step]
     u32x4 fr[2][32];                             // the slices' LDS fragments, in MFMA order: 8 Q rows | 8 dO rows | 8 dO^T | 8 Q^T
     auto rd = [&](int h, int gf) {               // request fragment gf of slice h
       const int j = gf & 7;
+      // A swizzled address is formed where its first fragment is requested and serves every fragment that differs from it by
+      // an immediate: the Q rows' kr ^ (32 j) serve the dO rows (+ TILEB), dO^T's tr ^ .. serve its second k-step and Q^T.  They are
+      // opaque (hipcc neither re-forms them nor hoists them out of the slice, where they would be live across the whole tile):
+      // krx lives from the S chain into the dP chain, where pks is dead; trx from the end of the dP chain on, where sc dies.
       if (gf < 16) {
-        if (j == 0) asm volatile("" : "+v"(kr)); // opaque per phase: hipcc otherwise hoists the kr ^ 32 t and keeps them live
-        fr[h][gf] = *(USP_LDS const u32x4*)(smem + (kr ^ (32 * j)) + (gf < 8 ? 0 : TILEB) + h * 32 * ROWB);
+        if (gf == 0) asm volatile("" : "+v"(kr));
+        if (gf < 8 && j) { krx[j] = kr ^ (32 * j); asm volatile("" : "+v"(krx[j])); }
+        fr[h][gf] = *(USP_LDS const u32x4*)(smem + (j ? krx[j] : kr) + (gf < 8 ? 0 : TILEB) + h * 32 * ROWB);
       } else {
-        if (j == 0) asm volatile("" : "+v"(tr));
+        if (gf == 16) asm volatile("" : "+v"(tr));
         const int k2 = j / NDJ, dj = j % NDJ;
+        if (gf < 16 + NDJ) {
+          if (dj) { trx[dj] = tr ^ (64 * dj); asm volatile("" : "+v"(trx[dj])); }
+          trx[4 + dj] = tr ^ (64 * dj + 32); asm volatile("" : "+v"(trx[4 + dj]));
+        }
         USP_LDS const char* xb = smem + (gf < 24 ? TILEB : 0) + (2 * h + k2) * 16 * ROWB;
-        const u32x2 a0 = lds_read_tr16(xb + (tr ^ (64 * dj)));
-        const u32x2 a1 = lds_read_tr16(xb + (tr ^ (64 * dj + 32)) + 2048);
+        const u32x2 a0 = lds_read_tr16(xb + (dj ? trx[dj] : tr));
+        const u32x2 a1 = lds_read_tr16(xb + trx[4 + dj] + 2048);
         fr[h][gf] = u32x4{a0[0], a0[1], a1[0], a1[1]};
       }
     };
-    // a chain STARTS from its rows' constants, read straight into its accumulator (once per key block: no 16 registers of their
-    // own).  which 0: -lse / scale -> S, 1: -delta -> dP; n = 4 kb + j; register r of a C tile is row (r & 3) + 8 (r >> 2) + 4 hi
-    auto rd_stats = [&](int h, int which, int n) {
-      const int kb = n >> 2, j = n & 3;
+    // a chain STARTS from its rows' constants, the same for both key blocks: they are read ONCE, straight into key block 1's
+    // accumulator, and key block 0's first MFMA takes them from there as SrcC (D = its own accumulator, chain_from) one slot in front
+    // of key block 1's own first MFMA -- no registers of their own, no second read, no copy (a VALU write in front of an MFMA's SrcC
+    // costs wait states).  which 0: -lse / scale -> S, 1: -delta -> dP; register r of a C tile is row (r & 3) + 8 (r >> 2) + 4 hi
+    auto rd_stats = [&](int h, int which, int j) {
       const f32x4 t = *(USP_LDS const f32x4*)(stat + 4 * kTile * which + 128 * h + 32 * j);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) (which ? dp : sc)[kb][4 * j + e] = t[e];
+      for (int e = 0; e < 4; ++e) (which ? dp : sc)[1][4 * j + e] = t[e];
     };
     // element n of a slice, in the order the gradient k-steps need them: n = 16 k2 + 8 kb + r8 -> [kb][8 k2 + r8]
     auto p_elem = [&](int n) {
@@ -386,7 +429,7 @@ USP_TM(
 #pragma unroll
     for (int gf = 0; gf < LA; ++gf) rd(0, gf);
 #pragma unroll
-    for (int n = 0; n < 8; ++n) rd_stats(0, 0, n);
+    for (int n = 0; n < 4; ++n) rd_stats(0, 0, n);
     __builtin_amdgcn_sched_barrier(0);
     static_for<2>([&](auto h_c) __attribute__((always_inline)) {
       constexpr int h = decltype(h_c)::value;
@@ -394,9 +437,11 @@ USP_TM(
         constexpr int sl = decltype(sl_c)::value;
         constexpr int gf = sl >> 1, kb = sl & 1, j = gf & 7;
         if (gf < 8) {
-          U::template chain<MASK || j == 0>(sc[kb], fr[h][gf], kf[kb][j]);     // (j == 0: hipcc reads the constants once and COPIES them
+          if (sl == 0) U::template chain_from<MASK>(sc[0], fr[h][gf], kf[0][0], sc[1]);
+          else U::template chain<MASK>(sc[kb], fr[h][gf], kf[kb][j]);
         } else if (gf < 16) {
-          U::template chain<MASK || j == 0>(dp[kb], fr[h][gf], vf[kb][j]);     // for the other key block: VALU write -> MFMA SrcC, 2 wait states)
+          if (sl == 16) U::template chain_from<MASK>(dp[0], fr[h][gf], vf[0][0], dp[1]);
+          else U::template chain<MASK>(dp[kb], fr[h][gf], vf[kb][j]);
         } else if (gf < 24) {
           U::template grad<MASK>(4 * kb + j % NDJ, fr[h][gf], pkp[kb][j / NDJ]);
         } else {
@@ -404,15 +449,15 @@ USP_TM(
         }
         if (h == 0 && sl == 0) {                 // behind the first MFMA: its scalar work must not idle the matrix pipe
           __builtin_amdgcn_sched_barrier(0);
-          dma_open(buf_n);
+          dma_open(boff_n);
         }
         if (kb == 0) {                           // the fragment LA ahead
           if (gf + LA < 32) rd(h, gf + LA);
           else if (h == 0) rd(1, gf + LA - 32);
         }
         // the next chain's constants: -delta behind the S chain's first MFMAs, the next slice's -lse / scale late in dK
-        if (sl >= 6 && sl < 14) rd_stats(h, 1, sl - 6);
-        if (h == 0 && sl >= 54 && sl < 62) rd_stats(1, 0, sl - 54);
+        if (sl >= 6 && sl < 10) rd_stats(h, 1, sl - 6);
+        if (h == 0 && sl >= 54 && sl < 58) rd_stats(1, 0, sl - 54);
         if (h == 0 && sl >= 1 && sl <= 8) dma_piece(sl - 1);      // the next tile's pieces
         elem_slot(sl);
         __builtin_amdgcn_sched_barrier(0);
@@ -423,12 +468,12 @@ USP_TM(
         }
       });
     });
-    buf_a = buf_n;
+    boff_a = boff_n;
     ++tile_cur;
     USP_TM(const uint64_t tm0 = __builtin_amdgcn_s_memtime();)
     dma_drain();            // this wave's DMA pieces of the staged tile have landed
     USP_TM(const uint64_t tm1 = __builtin_amdgcn_s_memtime();)
-    stats_store(buf_n);
+    stats_store(boff_n);
     __syncthreads();
     USP_TM(const uint64_t tm2 = __builtin_amdgcn_s_memtime();
            tm_body += tm0 - tm_last; tm_drain += tm1 - tm0; tm_bar += tm2 - tm1; tm_last = tm2;)
@@ -446,7 +491,7 @@ USP_TM(
     dma_drain();
     stats_store(0);
     __syncthreads();
-    tile_cur = t_begin; buf_a = 0;
+    tile_cur = t_begin; boff_a = 0;
   };
   for (int hh = 0; hh < gsub; ++hh) {              // head by head: the diagonal tiles first, then the plain ones
     open_head(h0 + hh);
