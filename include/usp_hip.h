@@ -33,7 +33,7 @@ enum { USP_BF16 = 0, USP_FP16 = 1 };
 enum {
   USP_OK = 0,
   USP_EINVAL = -1,      /* bad argument (null pointer, non-positive size, bad dtype) */
-  USP_EUNSUPPORTED = -2,/* head_dim not in {32, 64, 128}, Hq % Hkv != 0, misaligned pointer/stride */
+  USP_EUNSUPPORTED = -2,/* head_dim not in {32, 64, 128, 256}, Hq % Hkv != 0, misaligned pointer/stride */
   USP_ELAUNCH = -3      /* hipLaunchKernel reported an error */
 };
 
@@ -142,6 +142,22 @@ enum {
  * block-pooled attention map of a call -- the share of the softmax mass every 128 x 128 block holds (ABI still v7; the value is
  * no flag of an argument block, where it means USP_DKDV_KEYS128). */
 #define USP_ATTN_BLOCK_MASS 131072
+/* USP_ATTN_HEAD_DIM_256: a FEATURE bit (ABI still v7; the value is free as a flag and means nothing in an argument block):
+ * usp_flash_fwd / usp_flash_bwd serve head_dim == 256, bf16 and fp16, causal and full, on a kernel family of its own
+ * (csrc/usp_flash_fwd_d256.hip, csrc/usp_flash_bwd_d256.hip: 4 waves, one per SIMD, 32 query rows or keys each; noted as
+ * USP_KIND_FWD_D256 / USP_KIND_DKDV_D256 / USP_KIND_DQ_D256), and usp_bwd_delta / usp_lse_merge take D == 256.
+ *   forward   everything the plain dense launch honours: causal with the bottom-right alignment, ragged Sq / Sk, Sq != Sk (a row
+ *             that sees no key: out = 0, lse = -inf), USP_ATTN_SHIFT on a causal launch, GQA, any aligned strides, merge_in, acc,
+ *             final_begin / final_end, the fp32 lse, USP_LAUNCH_INTERLEAVE;
+ *   backward  accum_dq / accum_dk / accum_dv, dq16 / dk16 / dv16, USP_BWD_SKIP_DQ / USP_BWD_SKIP_DKDV.  A dK/dV item loops over
+ *             the whole KV group: deterministic, no partials, no reduce launch, no atomics;
+ *   cuts      k_splits, dq_splits, dkdv_splits and the workspace are ignored: the launch is served uncut (as a document or max-logit
+ *             launch is).  dkdv_heads must be 0 or Hq / Hkv; anything else is USP_EINVAL;
+ *   declined  USP_EUNSUPPORTED, nothing launched or written: USP_ATTN_SOFTCAP, a window bound that cuts something, a packed batch
+ *             (seq_q / seq_k), USP_FORCE_ROW64, USP_FORCE_WAVE32, USP_DKDV_KEYS128, USP_DKDV_KEYS256, a row stride of K, V, Q or dO of
+ *             2^24 elements or more, and every extra entry point with its feature on: usp_flash_*_alibi, _dropout, _sink, _doc, _span,
+ *             _bsp, usp_flash_fwd_maxlogit.  usp_block_means, usp_block_select* and usp_block_attn_mass keep declining D == 256. */
+#define USP_ATTN_HEAD_DIM_256 262144
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
  * exists in two forms, both noted as USP_KIND_DKDV_ROW64:
  *   USP_DKDV_KEYS128  flash_bwd_dkdv64_kernel: a work item owns 128 keys, two waves share a 64-key slice (S, P, dV | dP, dS, dK);
@@ -762,7 +778,10 @@ enum {
   USP_KIND_DQ_WAVE8 = 128,      /* flash_bwd_kernel (dQ) */
   USP_KIND_REDUCE_HEADS = 256,  /* reduce_heads_kernel (GQA head split / dK,dV cuts) */
   USP_KIND_REDUCE_CUTS = 512,   /* reduce_cuts_kernel (dQ key cuts) */
-  USP_KIND_DKDV_KEYS256 = 1024  /* beside USP_KIND_DKDV_ROW64: it was flash_bwd_dkdv64u_kernel (256-key items) */
+  USP_KIND_DKDV_KEYS256 = 1024, /* beside USP_KIND_DKDV_ROW64: it was flash_bwd_dkdv64u_kernel (256-key items) */
+  USP_KIND_FWD_D256 = 2048,     /* flash_fwd_d256_kernel     (head dim 256: 4 waves x 32 rows) */
+  USP_KIND_DKDV_D256 = 4096,    /* flash_bwd_dkdv_d256_kernel (head dim 256: 4 waves x 32 keys) */
+  USP_KIND_DQ_D256 = 8192       /* flash_bwd_dq_d256_kernel  (head dim 256: 4 waves x 32 rows) */
 };
 int usp_last_launch_kinds(void);
 
@@ -780,8 +799,8 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
  * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT |
- * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS, the last ten feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
- * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist).
+ * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS | USP_ATTN_HEAD_DIM_256, the last eleven feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
+ * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist, head dim 256 is served).
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -40,12 +40,16 @@ USP_DKDV_KEYS256 = 65536       # usp_flash_bwd: 256-key items for the 64-row fam
 USP_DKDV_KEYS128 = 131072      # ... or its 128-key items (two waves share a 64-key slice); neither: the library picks per launch
 USP_ATTN_BLOCK_SELECT_TOP_P = 65536  # feature bit of usp_attn_features(): usp_block_select_top_p exists (not an args flag)
 USP_ATTN_BLOCK_MASS = 131072   # feature bit of usp_attn_features(): usp_block_attn_mass exists (not an args flag)
+USP_ATTN_HEAD_DIM_256 = 262144 # feature bit of usp_attn_features(): usp_flash_fwd / usp_flash_bwd serve head_dim 256 (not an args flag)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
 # usp_last_launch_kinds(): bit -> kernel (include/usp_hip.h, USP_KIND_*)
 KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 16: "dkdv_row64", 32: "dkdv_wave8",
          64: "dq_row64", 128: "dq_wave8", 256: "reduce_heads", 512: "reduce_cuts"}
+# ... and the head-dim-256 family's (csrc/usp_flash_fwd_d256.hip, csrc/usp_flash_bwd_d256.hip), a table of its own: KINDS is the
+# list of the D <= 128 kernels the large-launch table covers one by one
+KINDS_D256 = {2048: "fwd_d256", 4096: "dkdv_d256", 8192: "dq_d256"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -84,7 +88,7 @@ def last_dkdv_item_keys() -> int:
 def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
-    return tuple(name for bit, name in KINDS.items() if m & bit)
+    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items()) if m & bit)
 
 
 class UspTensor(ctypes.Structure):
@@ -1009,6 +1013,8 @@ def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scal
     fp32; seq_q/seq_k (num_seq,2) int32 device tables of (first_row, rows); final_begin/final_end
     count half sequences (0,1,2); `softcap` as flash_fwd.  `sched=False` passes no control block: the workgroups walk their
     static item lists instead of the dynamic queue (include/usp_hip.h `sched`; tests and A/B runs)."""
+    from .kernels.features import head_dim_256_alone
+    head_dim_256_alone(q.shape[-1], packed=True)       # judged before any tensor is read
     _require_cuda(q, k, v, lse, out, acc)
     cap = softcap_value(softcap)
     n = seq_q.shape[0]
@@ -1034,6 +1040,8 @@ def flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q: int, max_k:
                      sched: bool = True):
     """usp_flash_bwd in packed variable-length mode (layouts as flash_fwd_packed; lse/delta (Hq,T); `softcap` and `sched`
     as flash_fwd_packed)."""
+    from .kernels.features import head_dim_256_alone
+    head_dim_256_alone(q.shape[-1], packed=True)       # judged before any tensor is read
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     n = seq_q.shape[0]

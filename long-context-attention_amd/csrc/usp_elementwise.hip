@@ -270,12 +270,12 @@ extern "C" int usp_bwd_delta(int32_t dtype, int32_t B, int32_t S, int32_t H, int
                              int64_t d_sb, int64_t d_sh, void* stream) {
   if (!dout || !out || !delta || B <= 0 || S <= 0 || H <= 0) return USP_EINVAL;
   if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
-  if (D != 32 && D != 64 && D != 128) return USP_EUNSUPPORTED;
+  if (D != 32 && D != 64 && D != 128 && D != 256) return USP_EUNSUPPORTED;
   if (!tensor_aligned(*dout, 16, 8) || !tensor_aligned(*out, 16, 8)) return USP_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)B * S * H;
   const int grid = ew_grid(rows * (D / 8));
-  return with_head_dim_dtype(D, dtype, [&](auto d, auto dt) {
+  return with_head_dim_dtype<true>(D, dtype, [&](auto d, auto dt) {
     hipLaunchKernelGGL((delta_kernel<decltype(d)::value, decltype(dt)::value>), dim3(grid), dim3(kEwThreads), 0, st,
                        (const char*)dout->ptr, dout->stride_b, dout->stride_s, dout->stride_h,
                        (const char*)out->ptr, out->stride_b, out->stride_s, out->stride_h, delta, d_sb, d_sh, B, S, H);
@@ -289,12 +289,12 @@ extern "C" int usp_lse_merge(int32_t dtype, int32_t B, int32_t S, int32_t H, int
                              int32_t first, void* stream) {
   if (!acc || !lse || !bo || !bl || B <= 0 || S <= 0 || H <= 0) return USP_EINVAL;
   if (dtype != USP_BF16 && dtype != USP_FP16) return USP_EINVAL;
-  if (D != 32 && D != 64 && D != 128) return USP_EUNSUPPORTED;
+  if (D != 32 && D != 64 && D != 128 && D != 256) return USP_EUNSUPPORTED;
   if (!tensor_aligned(*acc, 16, 4) || !tensor_aligned(*bo, 16, 8)) return USP_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)B * S * H;
   const int grid = ew_grid(rows * (D / 8));
-  return with_head_dim_dtype(D, dtype, [&](auto d, auto dt) {
+  return with_head_dim_dtype<true>(D, dtype, [&](auto d, auto dt) {
     hipLaunchKernelGGL((merge_kernel<decltype(d)::value, decltype(dt)::value>), dim3(grid), dim3(kEwThreads), 0, st,
                        (float*)acc->ptr, acc->stride_b, acc->stride_s, acc->stride_h, lse, l_sb, l_sh,
                        (const char*)bo->ptr, bo->stride_b, bo->stride_s, bo->stride_h, bl, bl_sb, bl_sh, B, S, H, first ? 1 : 0);
@@ -410,7 +410,7 @@ extern "C" int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32
 }
 
 extern "C" int usp_abi_version(void) { return USP_ABI_VERSION; }
-extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT | USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS; }
+extern "C" int usp_attn_features(void) { return USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI | USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT | USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS | USP_ATTN_HEAD_DIM_256; }
 
 // What the calling thread's last flash call launched (include/usp_hip.h: usp_last_launch_kinds).  Thread-local: the entry
 // points share no mutable state.
@@ -426,7 +426,7 @@ extern "C" const char* usp_strerror(int code) {
     case USP_OK: return "ok";
     case USP_EINVAL: return "invalid argument (null pointer, non-positive size or bad dtype)";
     case USP_EUNSUPPORTED:
-      return "unsupported shape/layout (head_dim must be 32/64/128, Hq % Hkv == 0, 16-byte aligned "
+      return "unsupported shape/layout (head_dim must be 32/64/128/256, Hq % Hkv == 0, 16-byte aligned "
              "pointers and strides; or a forced kernel family that does not serve the call)";
     case USP_ELAUNCH: return "HIP kernel launch failed";
   }

@@ -16,6 +16,7 @@
 // holds rows.  Which tiles an item streams and which of them are live or masked: usp_tile_range.h.
 #include "usp_bwd_params.hpp"
 #include "usp_host.hpp"
+#include "usp_d256.hpp"
 
 namespace usp {
 
@@ -388,7 +389,7 @@ static BwdPlan plan_bwd(const usp_bwd_args* a) {
 }
 
 extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
-  if (!a || a->Hkv <= 0 || a->Hq < a->Hkv || a->Hq % a->Hkv != 0) return 0;
+  if (!a || a->Hkv <= 0 || a->Hq < a->Hkv || a->Hq % a->Hkv != 0 || a->D == 256) return 0;   // (D = 256 is served uncut)
   const BwdPlan pl = plan_bwd(a);
   return pl.dkdv_bytes + pl.dq_bytes;
 }
@@ -423,6 +424,7 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (int rc = check_bsp(*a, x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists)) return rc;
   const bool has_bsp = x.bsp.mask != nullptr;
   if (has_bsp) x.bsp.layout = block_lists(a->B, a->Hq, (a->Sq + 127) / 128, (a->Sk + 127) / 128);   // once per call
+  if (int rc = check_d256(*a, x.any())) return rc;
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
@@ -444,6 +446,7 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (has_doc || has_span || has_bsp) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
   const BwdPlan plan = plan_bwd(a);
   if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
+  if (a->D == 256 && a->dkdv_heads > 0 && a->dkdv_heads != a->Hq / a->Hkv) return USP_EINVAL;   // its dK/dV item takes the whole group
   BwdArgsSC p;
   p.dout = (const char*)a->dout.ptr; p.q = (const char*)a->q.ptr;
   p.k = (const char*)a->k.ptr; p.v = (const char*)a->v.ptr;
@@ -498,6 +501,15 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   }
   x.al.al_diag = alibi_diag(*a);
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32 | USP_DKDV_KEYS256 | USP_DKDV_KEYS128);
+  if (a->D == 256) {                              // a family of its own (usp_flash_bwd_d256.hip), served uncut: cuts and workspace are ignored
+    p.split = 0; p.qsplit = 1; p.ksplit = 1; p.nslab = 1; p.ws_dk = nullptr; p.ws_dv = nullptr; p.ws_dq = nullptr;
+    p.gsub = p.G; p.ngrp = 1;
+    int rc = USP_OK;
+    if (want_dkdv && (rc = launch_dkdv_d256(p, a->dtype, mask.causal, (hipStream_t)stream)) != USP_OK) return rc;
+    if (want_dkdv) launch_kinds_note(USP_KIND_DKDV_D256);
+    if (want_dq && (rc = launch_dq_d256(p, a->dtype, mask.causal, (hipStream_t)stream)) == USP_OK) launch_kinds_note(USP_KIND_DQ_D256);
+    return rc;
+  }
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
     return launch_bwd<decltype(d)::value, decltype(dt)::value>(p, x, mask.causal, (hipStream_t)stream, force, skip, plan.keys);
   });

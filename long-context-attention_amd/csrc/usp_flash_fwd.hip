@@ -18,6 +18,7 @@
 //   * exp2 with softmax_scale*log2(e) folded into one FMA per score.
 #include "usp_fwd_params.hpp"
 #include "usp_host.hpp"
+#include "usp_d256.hpp"
 
 namespace usp {
 
@@ -257,7 +258,7 @@ static int launch_fwd(const FwdArgsSC& p, const FwdExtras& x, bool causal, hipSt
 }  // namespace usp
 
 extern "C" int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* a, int32_t k_splits) {
-  if (!a || k_splits <= 1 || k_splits > 8 || a->seq_q || a->seq_k) return 0;
+  if (!a || k_splits <= 1 || k_splits > 8 || a->seq_q || a->seq_k || a->D == 256) return 0;   // (D = 256 is served uncut)
   const int64_t rows = (int64_t)a->B * a->Sq * a->Hq;
   return (int64_t)k_splits * (rows * a->D + rows) * 4;         // partial outputs + partial LSEs, fp32 (a->D % 4 == 0)
 }
@@ -279,6 +280,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   if (int rc = check_span(*a, x.span.row_hi != nullptr, x.doc.row_lo_sb, x.span.row_hi_sb, 0, 0)) return rc;
   if (int rc = check_bsp(*a, x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists)) return rc;
   if (x.bsp.mask) x.bsp.layout = block_lists(a->B, a->Hq, (a->Sq + 127) / 128, (a->Sk + 127) / 128);   // once per call
+  if (int rc = check_d256(*a, x.any())) return rc;
   if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
@@ -327,6 +329,11 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   if (packed) p.q_sb = p.k_sb = p.v_sb = p.o_sb = p.a_sb = p.lse_sb = 0;
   x.al.al_diag = alibi_diag(*a);
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
+  if (a->D == 256) {                               // a family of its own (usp_flash_fwd_d256.hip), served uncut: k_splits is ignored
+    const int rc = launch_fwd_d256(p, a->dtype, mask.causal, (hipStream_t)stream);
+    if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_D256);
+    return rc;
+  }
   return with_head_dim_dtype(a->D, a->dtype, [&](auto d, auto dt) {
     return launch_fwd<decltype(d)::value, decltype(dt)::value>(p, x, mask.causal, (hipStream_t)stream, force);
   });

@@ -62,13 +62,16 @@ template <class F> auto with_causal(bool causal, F&& f) { return causal ? f(std:
 template <class F> auto with_dtype_causal(int dtype, bool causal, F&& f) {
   return with_dtype(dtype, [&](auto dt) { return with_causal(causal, [&](auto c) { return f(dt, c); }); });
 }
-// f(Int<D>, Int<DT>) -> int; USP_EUNSUPPORTED for a head dim without kernels
-template <class F> int with_head_dim_dtype(int D, int dtype, F&& f) {
+// f(Int<D>, Int<DT>) -> int; USP_EUNSUPPORTED for a head dim without kernels.  WITH256: the caller's f also has a D = 256 form (the
+// streaming helpers of usp_elementwise.hip; the flash entry points hand D = 256 to usp_flash_{fwd,bwd}_d256.hip before they get here,
+// so that no D <= 128 kernel is instantiated a fourth time)
+template <bool WITH256 = false, class F> int with_head_dim_dtype(int D, int dtype, F&& f) {
   return with_dtype(dtype, [&](auto dt) -> int {
     switch (D) {
       case 32: return f(Int<32>{}, dt);
       case 64: return f(Int<64>{}, dt);
       case 128: return f(Int<128>{}, dt);
+      case 256: if constexpr (WITH256) return f(Int<256>{}, dt); else break;
     }
     return USP_EUNSUPPORTED;
   });
@@ -86,8 +89,23 @@ template <class Args> int check_problem(const Args& a) {
   if (has_cap && !(__builtin_isfinite(a.softcap) && a.softcap > 0.f)) return USP_EINVAL;
   if (has_cap && (a.flags & USP_FORCE_ROW64)) return USP_EUNSUPPORTED;   // the 64-row family declines softcap
   if ((a.flags & USP_ATTN_SHIFT) && (a.mask_shift >= (1 << 30) || a.mask_shift <= -(1 << 30))) return USP_EINVAL;
-  if (a.D != 32 && a.D != 64 && a.D != 128) return USP_EUNSUPPORTED;
+  if (a.D != 32 && a.D != 64 && a.D != 128 && a.D != 256) return USP_EUNSUPPORTED;
   if (a.Hq % a.Hkv != 0) return USP_EUNSUPPORTED;
+  return USP_OK;
+}
+
+// Head dim 256 (usp_flash_fwd_d256.hip / usp_flash_bwd_d256.hip) is the plain dense launch and nothing else: declined are softcap, a
+// window bound that cuts something, a packed batch, a forced family or dK/dV item width, and every extra entry point (`extras`).
+// Judged behind check_problem and the extras' own checks, before anything is launched or written.
+template <class Args> int check_d256(const Args& a, bool extras) {
+  if (a.D != 256) return USP_OK;
+  if (extras || (a.flags & USP_ATTN_SOFTCAP) || a.seq_q || a.seq_k) return USP_EUNSUPPORTED;
+  if (a.flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32 | USP_DKDV_KEYS128 | USP_DKDV_KEYS256)) return USP_EUNSUPPORTED;
+  const bool has_win = (a.flags & USP_ATTN_WINDOW) != 0, has_shift = (a.flags & USP_ATTN_SHIFT) != 0;
+  const usp_mask_bounds mb = usp_decode_mask_bounds(a.Sq, a.Sk, a.causal ? 1 : 0, has_win ? 1 : 0, has_win ? a.window_left : -1,
+                                                    has_win ? a.window_right : -1, has_shift ? 1 : 0, has_shift ? a.mask_shift : 0);
+  if (mb.win_on || (mb.causal && !a.causal))       // a window bound, left or right, that cuts a (row, key) pair
+    return USP_EUNSUPPORTED;
   return USP_OK;
 }
 

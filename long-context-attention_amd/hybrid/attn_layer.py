@@ -19,7 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..kernels.features import block_mask_alone, block_select_alone, max_logits_alone, return_block_mass_alone
+from ..kernels.features import block_mask_alone, block_select_alone, head_dim_256_alone, max_logits_alone, return_block_mass_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -172,6 +172,8 @@ class LongContextAttention(_USPLayer):
         rotation behind the forward, from the exchanged k and the ring's lse).  The layer gathers nothing and reads nothing on
         the host.  Served with the basic ring at any ring degree (a local length behind the exchange that is a multiple of
         128), with the zigzag and stripe rings at ring degree 1, through three exchanges."""
+        head_dim_256_alone(query.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                           block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
         bmass = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
                                         bidirectional, block_mask, block_select, return_max_logits)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
@@ -244,6 +246,8 @@ class LongContextAttentionQKVPacked(_USPLayer):
         """`return_max_logits` (keyword only): (out, max_logits) as LongContextAttention.forward returns it.  `block_select`
         (keyword only): as LongContextAttention.forward takes it.  `return_block_mass` (keyword only): (out, mass) as
         LongContextAttention.forward returns it."""
+        head_dim_256_alone(qkv.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                           block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
         bmass = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
                                         bidirectional, block_mask, block_select, return_max_logits)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,

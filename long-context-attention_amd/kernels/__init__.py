@@ -14,6 +14,7 @@ from .attention import (
     get_block_backend,
     hip_attn_backward,
     hip_attn_forward,
+    set_head_dim_256,
     hip_attn_func,
     select_blocks,
     select_blocks_top_p,
@@ -75,4 +76,4 @@ def select_flash_attn_impl(impl_type: AttnType, stage: str = "fwd-bwd", attn_pro
 
 __all__ = ["AttnType", "select_flash_attn_impl", "hip_attn_forward", "hip_attn_backward",
            "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect",
-           "select_blocks_top_p", "BlockSelectTopP", "block_attention_mass", "block_mask_recall"]
+           "select_blocks_top_p", "BlockSelectTopP", "block_attention_mass", "block_mask_recall", "set_head_dim_256"]

@@ -11,11 +11,13 @@ which the LSE merge (ring/utils.py:10-51) and the fp32 gradient accumulation
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 from .. import _C
 from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
-                       block_select_alone, expand_block_mask, max_logits_alone, return_block_mass_alone)
+                       block_select_alone, expand_block_mask, head_dim_256_alone, max_logits_alone, return_block_mass_alone)
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -30,7 +32,19 @@ def kernel_operand(t: torch.Tensor) -> torch.Tensor:
     return t if ok else t.contiguous()
 
 
-KERNEL_HEAD_DIMS = (32, 64, 128)      # what libusp_hip.so instantiates (include/usp_hip.h: anything else is USP_EUNSUPPORTED)
+KERNEL_HEAD_DIMS = (32, 64, 128, 256) # what libusp_hip.so instantiates (include/usp_hip.h: anything else is USP_EUNSUPPORTED)
+# Head dim 256 through the entry points of this package is OPT-IN: USP_HEAD_DIM_256=1 at import, or set_head_dim_256(True).  Off
+# (the default), head dims above 128 raise NotImplementedError as they always have -- callers and tests rely on that refusal --
+# while the C ABI (usp_flash_fwd / usp_flash_bwd, _C.flash_fwd / _C.flash_bwd) serves D = 256 either way.
+_HEAD_DIM_256 = os.environ.get("USP_HEAD_DIM_256", "").strip() == "1"
+
+
+def set_head_dim_256(on: bool) -> bool:
+    """Serve head dims 129 ... 256 (at kernel head dim 256) through hip_attn_forward / hip_attn_backward / hip_attn_func, the rings
+    and the layers of this process; returns the previous setting."""
+    global _HEAD_DIM_256
+    prev, _HEAD_DIM_256 = _HEAD_DIM_256, bool(on)
+    return prev
 
 
 def kernel_head_dim(D: int) -> int:
@@ -38,11 +52,16 @@ def kernel_head_dim(D: int) -> int:
     dim changes neither the scores (the pad contributes 0 to every dot product; the softmax scale stays D ** -0.5) nor the first D
     output dims, so head dims such as 40, 72, 80, 96, 112 -- which flash-attn serves (kernels/attention.py:177-202: any
     multiple of 8 up to 256) -- run through the entry points of this package on padded copies, at the padded dim's cost.
-    Above 128 there is no kernel (a 256-dim tile does not fit the 256-register budget of the 8-wave shape)."""
-    for d in KERNEL_HEAD_DIMS:
+    With set_head_dim_256(True) (or USP_HEAD_DIM_256=1) head dims 129 ... 256 run at 256, on a kernel family of its own (one wave
+    per SIMD, 32 rows or keys per wave: 512 registers hold the 256-dim accumulators the two-waves-per-SIMD shape has no room for)
+    that serves the plain dense call only (kernels/features.py: head_dim_256_alone); without it they raise as they always have.
+    Above 256 there is no kernel."""
+    dims = KERNEL_HEAD_DIMS if _HEAD_DIM_256 else KERNEL_HEAD_DIMS[:-1]
+    for d in dims:
         if D <= d:
             return d
-    raise NotImplementedError(f"head_dim {D} > {KERNEL_HEAD_DIMS[-1]} is not supported by the HIP attention kernels")
+    hint = " (head dims up to 256 are served after set_head_dim_256(True) / USP_HEAD_DIM_256=1)" if D <= KERNEL_HEAD_DIMS[-1] else ""
+    raise NotImplementedError(f"head_dim {D} > {dims[-1]} is not supported by the HIP attention kernels{hint}")
 
 
 def pad_head_dim(*tensors):
@@ -377,6 +396,7 @@ def select_blocks(q, k, top_k, *, softmax_scale=None, causal=False, keep_first=0
     ValueError: a negative or non-int top_k / keep_first / keep_local, keep_local < 1 under causal; NotImplementedError: q and k of
     different lengths, more than 8192 blocks.  With NaN or Inf inputs the selection is unspecified."""
     top_k, keep_first, keep_local = _C.block_select_value(top_k, keep_first, keep_local, causal)
+    head_dim_256_alone(q.shape[-1], block_select=True)          # (the selection kernels stop at head dim 128)
     block_mask_self_attention(q.shape[1], k.shape[1], "block_select")
     q, k, scale = select_operands(q, k, softmax_scale)
     nb = (q.shape[1] + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
@@ -398,6 +418,7 @@ def select_blocks_top_p(q, k, top_p, *, softmax_scale=None, causal=False, keep_f
     gradient.  ValueError: a top_p outside (0, 1], a negative or non-int keep_first / keep_local, a non-bool share_group,
     keep_local < 1 under causal; NotImplementedError: q and k of different lengths, more than 8192 blocks."""
     top_p, keep_first, keep_local, share_group = _C.block_select_top_p_value(top_p, keep_first, keep_local, share_group, causal)
+    head_dim_256_alone(q.shape[-1], block_select=True)
     block_mask_self_attention(q.shape[1], k.shape[1], "block_select")
     q, k, scale = select_operands(q, k, softmax_scale)
     nb = (q.shape[1] + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
@@ -446,6 +467,7 @@ def block_attention_mass(q, k, lse, *, softmax_scale=None, causal=False):
     a mask.  Computed on the device by one kernel that forms no S x S scores in memory (include/usp_hip.h: usp_block_attn_mass
     states the order of every sum; results repeat bit for bit); never read on the host, no gradient.  Padded head dims are
     included.  NotImplementedError: q and k of different lengths."""
+    head_dim_256_alone(q.shape[-1], return_block_mass=True)     # (usp_block_attn_mass stops at head dim 128)
     block_mask_self_attention(q.shape[1], k.shape[1], "block_attention_mass")
     q, k, lse, scale = mass_operands(q, k, lse, softmax_scale)
     return get_block_backend().block_mass(q, k, lse, scale, bool(causal), 0)
@@ -495,7 +517,10 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     (hip_attn_backward takes the mask, not the selection.)
     `return_block_mass` (keyword only): the result is (out, lse, mass), mass = block_attention_mass(q, k, lse, ...) of the call's
     own lse, computed behind the forward: fp32 (B, Hq, nb, nb) without gradient.  out and lse are bit for bit those of the call
-    without it.  Goes with none of the other options and needs equally long q and k.  False: exactly the call without it."""
+    without it.  Goes with none of the other options and needs equally long q and k.  False: exactly the call without it.
+    Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone)."""
+    head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                       block_select, return_max_logits, return_block_mass)
     if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                block_mask, block_select, return_max_logits):
         block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")
@@ -555,6 +580,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
     `cu_doclens`, `bidirectional`, `block_mask` (keyword only): as hip_attn_forward took them."""
+    head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
     bsp_kw = {}
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         bsp_kw = dict(bsp=block_mask_of(block_mask, q, k))
@@ -661,7 +687,10 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     `return_block_mass` (keyword only): the result becomes `(out, mass)`, with return_attn_probs `(out, softmax_lse, None, mass)`:
     the fp32 (B, Hq, nb, nb) block-pooled attention map of the call (block_attention_mass on the call's own lse, computed under
     no_grad behind the forward), padded head dims included; no gradient, never read on the host.  `out`, the lse and the
-    gradients are bit for bit those of the call without it.  Goes with none of the other options."""
+    gradients are bit for bit those of the call without it.  Goes with none of the other options.
+    Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone)."""
+    head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                       block_select, return_max_logits, return_block_mass)
     if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                block_mask, block_select, return_max_logits):
         block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")

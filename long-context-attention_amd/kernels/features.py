@@ -133,6 +133,26 @@ def return_block_mass_alone(return_block_mass, window_size=None, softcap=None, a
     return True
 
 
+def head_dim_256_alone(D: int, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
+                        bidirectional=None, block_mask=None, block_select=None, return_max_logits=False, return_block_mass=False,
+                        packed=False) -> bool:
+    """Does a call of head dim `D` run at kernel head dim 256 (128 < D <= 256)?  That family (csrc/usp_flash_fwd_d256.hip,
+    csrc/usp_flash_bwd_d256.hip) is the plain dense call -- causal or full, GQA, the rings' fused merge -- and nothing else: judged
+    HERE like block_mask, before any tensor is read, it goes with none of the options, nor with a packed (variable-length) batch
+    (`packed`).  A head dim above 256 is refused where it always was (kernels/attention.py: kernel_head_dim)."""
+    if not 128 < D <= 256:
+        return False
+    given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
+             ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional),
+             ("block_mask", block_mask), ("block_select", block_select), ("return_max_logits", return_max_logits or None),
+             ("return_block_mass", return_block_mass or None), ("a packed (variable-length) batch", packed or None))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"head_dim {D} (kernel head dim 256) together with {name} is not supported by the HIP "
+                                      f"attention kernels")
+    return True
+
+
 def block_mask_self_attention(Sq: int, Sk: int, name: str = "block_mask"):
     """A block mask (given, or selected: `name`) covers one sequence against itself."""
     if Sq != Sk:

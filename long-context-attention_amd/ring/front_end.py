@@ -10,7 +10,7 @@ from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_top_p_value, block_select
 from ..kernels import AttnType
 from ..kernels.attention import (block_attention_mass, draw_seed, get_block_backend, kernel_head_dim, kernel_operand,
                                  mass_operands, needs_grad, pad_head_dim, select_blocks, select_blocks_top_p, select_operands)
-from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone,
+from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone, head_dim_256_alone,
                                 max_logits_alone, return_block_mass_alone)
 from .utils import RingComm, group_info
 from .varlen_utils import unflatten_lse
@@ -477,6 +477,7 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
                  cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
                  return_block_mass=False):
+            head_dim_256_alone(q.shape[-1], packed=True)     # judged first (kernels/features.py)
             _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
@@ -490,6 +491,7 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
                  return_block_mass=False):
+            head_dim_256_alone(q.shape[-1], packed=True)     # judged first (kernels/features.py)
             _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
@@ -503,6 +505,7 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                            window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                            group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
                  return_block_mass=False):
+            head_dim_256_alone(qkv.shape[-1], packed=True)     # judged first (kernels/features.py)
             _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
@@ -526,6 +529,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                  attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
                  bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                               block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
             if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                        block_mask, block_select, return_max_logits):
                 return block_mass_call(serves, lambda probs: func(q, k, v, 0.0, softmax_scale, causal, deterministic=deterministic,
@@ -554,6 +559,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
                           block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                               block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
             if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                        block_mask, block_select, return_max_logits):
                 return block_mass_call(serves, lambda probs: kvpacked_func(q, kv, 0.0, softmax_scale, causal,
@@ -572,6 +579,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                            alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                            attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
                            block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            head_dim_256_alone(qkv.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                               block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
             if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                        block_mask, block_select, return_max_logits):
                 return block_mass_call(serves, lambda probs: qkvpacked_func(qkv, 0.0, softmax_scale, causal,
