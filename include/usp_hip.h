@@ -158,6 +158,25 @@ enum {
  *             2^24 elements or more, and every extra entry point with its feature on: usp_flash_*_alibi, _dropout, _sink, _doc, _span,
  *             _bsp, usp_flash_fwd_maxlogit.  usp_block_means, usp_block_select* and usp_block_attn_mass keep declining D == 256. */
 #define USP_ATTN_HEAD_DIM_256 262144
+/* USP_ATTN_HEAD_DIMS_192_128: a FEATURE bit (ABI still v7; the value is free as a flag and means nothing in an argument block):
+ * usp_flash_fwd_vdim / usp_flash_bwd_vdim exist and serve q and k of head dim 192 with v of head dim 128 (multi-head latent
+ * attention: 128 "nope" + 64 rope dims against 128 value dims), bf16 and fp16, causal and full, on a kernel family of its own
+ * (csrc/usp_flash_fwd_qk192.hip, csrc/usp_flash_bwd_qk192.hip: 4 waves, one per SIMD; 64 query rows per wave in the forward, 32 rows
+ * or keys in the backward; noted as USP_KIND_FWD_QK192 / USP_KIND_DKDV_QK192 / USP_KIND_DQ_QK192).
+ *   int usp_flash_fwd_vdim(const usp_fwd_args*, int32_t head_dim_v, void* stream);
+ *   int usp_flash_bwd_vdim(const usp_bwd_args*, int32_t head_dim_v, void* stream);
+ * The argument blocks are unchanged.  args->D is the head dim of q, k, dq, dk (and dq16, dk16); head_dim_v that of v, out, acc,
+ * dout, dv (and dv16).  usp_bwd_delta and usp_lse_merge are called at D = head_dim_v.  The softmax scale is the caller's as ever
+ * (192 ** -0.5 is the usual one).
+ *   head_dim_v == args->D   exactly usp_flash_fwd / usp_flash_bwd; head_dim_v <= 0 is USP_EINVAL;
+ *   any other pair than (192, 128)   USP_EUNSUPPORTED, nothing launched;
+ *   served and declined   exactly as USP_ATTN_HEAD_DIM_256 lists it: ragged Sq / Sk, Sq != Sk, rows that see no key, USP_ATTN_SHIFT
+ *             on a causal launch, GQA, any aligned strides, merge_in / acc / final_begin / final_end, USP_LAUNCH_INTERLEAVE, accum_*,
+ *             dq16 / dk16 / dv16, USP_BWD_SKIP_* are served; softcap, a cutting window, packed batches, the forced-family and
+ *             item-width flags decline with USP_EUNSUPPORTED and nothing written.  The feature entry points take no head_dim_v:
+ *             D == 192 is USP_EUNSUPPORTED there.  Cuts and workspaces are ignored, the workspace queries are unchanged; dkdv_heads
+ *             other than 0 or Hq / Hkv is USP_EINVAL.  The dK/dV item loops over its whole KV group: deterministic. */
+#define USP_ATTN_HEAD_DIMS_192_128 524288
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
  * exists in two forms, both noted as USP_KIND_DKDV_ROW64:
  *   USP_DKDV_KEYS128  flash_bwd_dkdv64_kernel: a work item owns 128 keys, two waves share a 64-key slice (S, P, dV | dP, dS, dK);
@@ -252,6 +271,7 @@ typedef struct usp_fwd_args {
 } usp_fwd_args;
 
 int usp_flash_fwd(const usp_fwd_args* args, void* stream);
+int usp_flash_fwd_vdim(const usp_fwd_args* args, int32_t head_dim_v, void* stream);   /* USP_ATTN_HEAD_DIMS_192_128 */
 
 /* K split (dense launches): a launch with few (batch, head, 256-row tile) work items cannot fill 256 CUs, and a causal
  * one lasts as long as its heaviest item (measured on MI355X, B1 S16384 D128 causal: 2 heads 548 TFLOP/s, 4 heads 891,
@@ -324,6 +344,7 @@ typedef struct usp_bwd_args {
 } usp_bwd_args;
 
 int usp_flash_bwd(const usp_bwd_args* args, void* stream);
+int usp_flash_bwd_vdim(const usp_bwd_args* args, int32_t head_dim_v, void* stream);   /* USP_ATTN_HEAD_DIMS_192_128 */
 
 /* ----------------------------------------------------------------------------------------------
  * ALiBi: usp_flash_fwd / usp_flash_bwd with flash-attn's `alibi_slopes` (forwarded by the reference to every block call,
@@ -781,7 +802,10 @@ enum {
   USP_KIND_DKDV_KEYS256 = 1024, /* beside USP_KIND_DKDV_ROW64: it was flash_bwd_dkdv64u_kernel (256-key items) */
   USP_KIND_FWD_D256 = 2048,     /* flash_fwd_d256_kernel     (head dim 256: 4 waves x 32 rows) */
   USP_KIND_DKDV_D256 = 4096,    /* flash_bwd_dkdv_d256_kernel (head dim 256: 4 waves x 32 keys) */
-  USP_KIND_DQ_D256 = 8192       /* flash_bwd_dq_d256_kernel  (head dim 256: 4 waves x 32 rows) */
+  USP_KIND_DQ_D256 = 8192,      /* flash_bwd_dq_d256_kernel  (head dim 256: 4 waves x 32 rows) */
+  USP_KIND_FWD_QK192 = 16384,   /* flash_fwd_qk192_kernel      (head dims 192 / 128: 4 waves x 64 rows) */
+  USP_KIND_DKDV_QK192 = 32768,  /* flash_bwd_dkdv_qk192_kernel (head dims 192 / 128: 4 waves x 32 keys) */
+  USP_KIND_DQ_QK192 = 65536     /* flash_bwd_dq_qk192_kernel   (head dims 192 / 128: 4 waves x 32 rows) */
 };
 int usp_last_launch_kinds(void);
 
@@ -799,8 +823,8 @@ int usp_mfma_probe(const void* operands, int64_t operand_bytes, int32_t iters, i
 int usp_abi_version(void);
 /* The USP_ATTN_* bits this library serves (USP_ATTN_WINDOW | USP_ATTN_SOFTCAP | USP_ATTN_SHIFT | USP_ATTN_ALIBI |
  * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT |
- * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS | USP_ATTN_HEAD_DIM_256, the last eleven feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
- * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist, head dim 256 is served).
+ * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS | USP_ATTN_HEAD_DIM_256 | USP_ATTN_HEAD_DIMS_192_128, the last twelve feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
+ * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist, head dim 256 is served, usp_flash_*_vdim exist).
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -41,6 +41,8 @@ USP_DKDV_KEYS128 = 131072      # ... or its 128-key items (two waves share a 64-
 USP_ATTN_BLOCK_SELECT_TOP_P = 65536  # feature bit of usp_attn_features(): usp_block_select_top_p exists (not an args flag)
 USP_ATTN_BLOCK_MASS = 131072   # feature bit of usp_attn_features(): usp_block_attn_mass exists (not an args flag)
 USP_ATTN_HEAD_DIM_256 = 262144 # feature bit of usp_attn_features(): usp_flash_fwd / usp_flash_bwd serve head_dim 256 (not an args flag)
+USP_ATTN_HEAD_DIMS_192_128 = 524288  # feature bit of usp_attn_features(): usp_flash_fwd_vdim / usp_flash_bwd_vdim exist (not an args flag)
+HEAD_DIMS_QK_V = (192, 128)    # the one pair of unequal head dims (q and k, v) they serve (the rule: kernels/features.py)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
 ABI_VERSION = 7
@@ -50,6 +52,8 @@ KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 1
 # ... and the head-dim-256 family's (csrc/usp_flash_fwd_d256.hip, csrc/usp_flash_bwd_d256.hip), a table of its own: KINDS is the
 # list of the D <= 128 kernels the large-launch table covers one by one
 KINDS_D256 = {2048: "fwd_d256", 4096: "dkdv_d256", 8192: "dq_d256"}
+# ... and the (192, 128) family's (csrc/usp_flash_fwd_qk192.hip, csrc/usp_flash_bwd_qk192.hip)
+KINDS_QK192 = {16384: "fwd_qk192", 32768: "dkdv_qk192", 65536: "dq_qk192"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -88,7 +92,7 @@ def last_dkdv_item_keys() -> int:
 def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
-    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items()) if m & bit)
+    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items()) if m & bit)
 
 
 class UspTensor(ctypes.Structure):
@@ -140,7 +144,7 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
-           "usp_block_select_top_p", "usp_block_attn_mass")
+           "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -154,6 +158,7 @@ MAXL_EXPORTS = ("usp_flash_fwd_maxlogit", "usp_row_max_reduce")
 SELECT_EXPORTS = ("usp_block_means", "usp_block_select")
 SELECT_TOP_P_EXPORTS = ("usp_block_select_top_p",)
 MASS_EXPORTS = ("usp_block_attn_mass",)
+VDIM_EXPORTS = ("usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
 
 
 def lib_path() -> str:
@@ -172,7 +177,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -721,7 +726,9 @@ def _feature_entries():
                                        [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, i32, i32, vp, i64, i64, i64, vp]),
             "usp_block_attn_mass": (USP_ATTN_BLOCK_MASS, "return_block_mass (USP_ATTN_BLOCK_MASS)",
                                     [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, f32,
-                                     i32, i32, vp, i64, i64, i64, vp])}
+                                     i32, i32, vp, i64, i64, i64, vp]),
+            "usp_flash_fwd_vdim": (USP_ATTN_HEAD_DIMS_192_128, "v of another head dim (USP_ATTN_HEAD_DIMS_192_128)", [fwd, i32, vp]),
+            "usp_flash_bwd_vdim": (USP_ATTN_HEAD_DIMS_192_128, "v of another head dim (USP_ATTN_HEAD_DIMS_192_128)", [bwd, i32, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -769,6 +776,31 @@ def _shift(shift) -> Optional[int]:
     if abs(s) >= 1 << 30:
         raise ValueError(f"shift must lie inside (-2^30, 2^30), got {shift!r}")
     return s
+
+
+def head_dim_v_of(q, v) -> int:
+    """0 for a v of q's head dim; the head dim of a v of another one, which is served for HEAD_DIMS_QK_V alone: any other pair
+    raises NotImplementedError naming both dims (kernels/features.py: head_dims_192_128_alone; the library would answer
+    USP_EUNSUPPORTED)."""
+    from .kernels.features import head_dims_192_128_alone
+    return v.shape[-1] if head_dims_192_128_alone(q.shape[-1], v.shape[-1]) else 0
+
+
+def _vdim_alone(Dv: int, **options):
+    """Every option of a launch with a v of head dim `Dv` (0: q's, nothing to judge) is refused by name, before any tensor is read."""
+    for name, value in options.items():
+        if Dv and value is not None:
+            raise NotImplementedError(f"head dims {HEAD_DIMS_QK_V} together with {name} are not supported by the HIP attention kernels")
+
+
+def _vdim_call(which: str, a, Dv: int, widths):
+    """usp_flash_fwd_vdim / usp_flash_bwd_vdim: the plain dense launch with a v of head dim `Dv`.  `widths`: (name, tensor or None)
+    of the tensors that must have v's head dim: one sized by q's is refused before the launch would write 128 of its 192 dims."""
+    for name, t in widths:
+        if t is not None and t.shape[-1] != Dv:
+            raise NotImplementedError(f"head dims {HEAD_DIMS_QK_V}: {name} has head dim {t.shape[-1]}, it takes v's ({Dv})")
+    name = f"usp_flash_{which}_vdim"
+    _check(_feature_entry(name)(ctypes.byref(a), Dv, _stream()), name)
 
 
 def _flash_call(which: str, a, al, dr, sk, dc, sp=None, mx=None):
@@ -856,7 +888,8 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
               alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None, row_max=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
-    out 16-bit / acc fp32 (B,Sq,Hq,D).  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
+    out 16-bit / acc fp32 (B,Sq,Hq,D).  A v of head dim 128 beside q and k of head dim 192 (HEAD_DIMS_QK_V) goes to usp_flash_fwd_vdim,
+    with out / acc of v's head dim: the plain dense launch, every option below refused here or declined by the library.  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
     every query tile into that many work items (None: fwd_k_splits decides; 0 / 1: off).  `window` = flash-attn's
     window_size (left, right), None / (-1, -1) = none.  `family`: "row64" | "wave32" pins the kernel family of this call
     (ABI v6; None: set_kernel_family's default, normally "auto"); both families serve a K split.  `softcap`: flash-attn's
@@ -882,8 +915,16 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     `row_max`: an fp32 (B, Hq, Sq) device tensor with unit seq stride (row_max_value), None = off: receives the largest visible
     softmax_scale * q.k of every row, -inf where a row sees nothing; with merge_in the maximum with the value there
     (usp_flash_fwd_maxlogit; served uncut, k_splits ignored; goes with window and shift alone; not with family="row64")."""
+    Dv = head_dim_v_of(q, v)                            # judged before any tensor is read
+    _vdim_alone(Dv, window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), sinks=sinks,
+                doc=doc, span=span, bsp=bsp, row_max=row_max)
     _require_cuda(q, k, v, lse, out, acc, row_max)
     B, Sq, Hq, D = q.shape
+    if Dv:
+        a = _fwd_args(q, k, v, softmax_scale, bool(causal), lse, out, acc, bool(merge_in), final_begin, final_end,
+                      bool(interleave), 0, _window(window), _family_flag(family), softcap_value(softcap), _shift(shift))
+        _vdim_call("fwd", a, Dv, (("out", out), ("acc", acc)))
+        return
     mx = row_max_value(row_max, B, Hq, Sq, q.device)
     bm = block_mask_value(bsp, B, Hq, Sq, q.device)
     if mx is not None:
@@ -1013,8 +1054,9 @@ def flash_fwd_packed(q, k, v, seq_q, seq_k, max_q: int, max_k: int, softmax_scal
     fp32; seq_q/seq_k (num_seq,2) int32 device tables of (first_row, rows); final_begin/final_end
     count half sequences (0,1,2); `softcap` as flash_fwd.  `sched=False` passes no control block: the workgroups walk their
     static item lists instead of the dynamic queue (include/usp_hip.h `sched`; tests and A/B runs)."""
-    from .kernels.features import head_dim_256_alone
-    head_dim_256_alone(q.shape[-1], packed=True)       # judged before any tensor is read
+    from .kernels.features import head_dim_256_alone, head_dims_192_128_alone
+    if not head_dims_192_128_alone(q.shape[-1], v.shape[-1], packed=True):
+        head_dim_256_alone(q.shape[-1], packed=True)   # judged before any tensor is read
     _require_cuda(q, k, v, lse, out, acc)
     cap = softcap_value(softcap)
     n = seq_q.shape[0]
@@ -1040,8 +1082,9 @@ def flash_bwd_packed(dout, q, k, v, lse, delta, seq_q, seq_k, max_q: int, max_k:
                      sched: bool = True):
     """usp_flash_bwd in packed variable-length mode (layouts as flash_fwd_packed; lse/delta (Hq,T); `softcap` and `sched`
     as flash_fwd_packed)."""
-    from .kernels.features import head_dim_256_alone
-    head_dim_256_alone(q.shape[-1], packed=True)       # judged before any tensor is read
+    from .kernels.features import head_dim_256_alone, head_dims_192_128_alone
+    if not head_dims_192_128_alone(q.shape[-1], v.shape[-1], packed=True):
+        head_dim_256_alone(q.shape[-1], packed=True)   # judged before any tensor is read
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     n = seq_q.shape[0]
@@ -1107,7 +1150,8 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
               softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None, bsp_lists=None, dkdv_keys: int = 0):
-    """usp_flash_bwd.  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
+    """usp_flash_bwd (usp_flash_bwd_vdim for a v, dout and dv of head dim 128 beside q and k of 192: the plain dense launch, every
+    option below refused or declined by the library).  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
     unless it is accumulated from).  `splits` = (dq_splits, dkdv_splits), None: bwd_splits decides.  `window` =
     flash-attn's window_size (left, right), None / (-1, -1) = none.  `family`: as flash_fwd.  `only`: "dkdv" | "dq" issues
@@ -1119,6 +1163,9 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     USP_DKDV_KEYS256; 0: the library picks; last_dkdv_item_keys() tells which ran).  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
     key_hi; with `only` the other one may be None.  `span`: as flash_fwd (usp_flash_bwd_span): the dQ launch reads (row_lo,
     row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None.  `bsp`: as flash_fwd (usp_flash_bwd_bsp)."""
+    Dv = head_dim_v_of(q, v)                             # judged before any tensor is read
+    _vdim_alone(Dv, window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), doc=doc, span=span,
+                bsp=bsp)
     _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16)
     cap = softcap_value(softcap)
     B, Sq, Hq, D = q.shape
@@ -1159,6 +1206,9 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
         a.window_left, a.window_right = win
     _set_softcap(a, cap)
     _set_shift(a, sh)
+    if Dv:                                               # (served uncut: no workspace)
+        _vdim_call("bwd", a, Dv, (("dout", dout), ("dv", dv), ("dv16", dv16)))
+        return
     L = load()
     need = L.usp_flash_bwd_workspace_bytes(ctypes.byref(a))     # GQA head split and / or cuts of few-item launches
     ws = None

@@ -17,6 +17,7 @@
 #include "usp_bwd_params.hpp"
 #include "usp_host.hpp"
 #include "usp_d256.hpp"
+#include "usp_qk192.hpp"
 
 namespace usp {
 
@@ -395,18 +396,20 @@ extern "C" int64_t usp_flash_bwd_workspace_bytes(const usp_bwd_args* a) {
 }
 
 // usp_flash_bwd (alibi_slopes == NULL, p_drop == 0, no document array), usp_flash_bwd_alibi, usp_flash_bwd_dropout, usp_flash_bwd_doc
-// and usp_flash_bwd_span
-static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stream) {
+// and usp_flash_bwd_span; usp_flash_bwd_vdim with `head_dim_v` (0: that of q and k)
+static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stream, int head_dim_v = 0) {
   const usp_bwd_args* a = a_in;
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse || !a->delta) return USP_EINVAL;
+  const bool qk192 = head_dim_v != 0 && head_dim_v != a->D;       // v, dout and dv of another head dim: (192, 128) or nothing
+  if (qk192 && !(a->D == 192 && head_dim_v == 128)) return USP_EUNSUPPORTED;
   if (int rc = check_force(a->flags)) return rc;
   if ((a->flags & USP_DKDV_KEYS256) && (a->flags & (USP_DKDV_KEYS128 | USP_FORCE_WAVE32))) return USP_EINVAL;
   if ((a->flags & USP_DKDV_KEYS128) && (a->flags & USP_FORCE_WAVE32)) return USP_EINVAL;
   const int skip = a->flags & (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV);
   if (skip == (USP_BWD_SKIP_DQ | USP_BWD_SKIP_DKDV)) return USP_EINVAL;
-  if (int rc = check_problem(*a)) return rc;
+  if (int rc = check_problem(*a, qk192)) return rc;
   if (int rc = check_alibi(*a, x.al.al_slopes, x.al.al_sb)) return rc;
   if (int rc = check_dropout(*a, x.dc, &x.dr)) return rc;
   const BwdDoc& doc = x.doc;
@@ -424,7 +427,7 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (int rc = check_bsp(*a, x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists)) return rc;
   const bool has_bsp = x.bsp.mask != nullptr;
   if (has_bsp) x.bsp.layout = block_lists(a->B, a->Hq, (a->Sq + 127) / 128, (a->Sk + 127) / 128);   // once per call
-  if (int rc = check_d256(*a, x.any())) return rc;
+  if (int rc = check_plain_dense_family(*a, x.any(), qk192)) return rc;
   if (!a->dout.ptr || !a->q.ptr || !a->k.ptr || !a->v.ptr) return USP_EINVAL;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
   if (packed && !(a->seq_q && a->seq_k && a->total_k > 0)) return USP_EINVAL;
@@ -446,7 +449,7 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   if (has_doc || has_span || has_bsp) { uncut = *a; uncut.dq_splits = 0; uncut.dkdv_splits = 0; a = &uncut; }
   const BwdPlan plan = plan_bwd(a);
   if (a->dkdv_heads < 0 || plan.gsub < 1) return USP_EINVAL;       // (not a divisor of Hq / Hkv)
-  if (a->D == 256 && a->dkdv_heads > 0 && a->dkdv_heads != a->Hq / a->Hkv) return USP_EINVAL;   // its dK/dV item takes the whole group
+  if ((a->D == 256 || qk192) && a->dkdv_heads > 0 && a->dkdv_heads != a->Hq / a->Hkv) return USP_EINVAL;   // its dK/dV item takes the whole group
   BwdArgsSC p;
   p.dout = (const char*)a->dout.ptr; p.q = (const char*)a->q.ptr;
   p.k = (const char*)a->k.ptr; p.v = (const char*)a->v.ptr;
@@ -501,10 +504,16 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
   }
   x.al.al_diag = alibi_diag(*a);
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32 | USP_DKDV_KEYS256 | USP_DKDV_KEYS128);
-  if (a->D == 256) {                              // a family of its own (usp_flash_bwd_d256.hip), served uncut: cuts and workspace are ignored
+  if (a->D == 256 || qk192) {                     // families of their own (usp_flash_bwd_d256.hip, usp_flash_bwd_qk192.hip), served uncut: cuts and workspace are ignored
     p.split = 0; p.qsplit = 1; p.ksplit = 1; p.nslab = 1; p.ws_dk = nullptr; p.ws_dv = nullptr; p.ws_dq = nullptr;
     p.gsub = p.G; p.ngrp = 1;
     int rc = USP_OK;
+    if (qk192) {
+      if (want_dkdv && (rc = launch_dkdv_qk192(p, a->dtype, mask.causal, (hipStream_t)stream)) != USP_OK) return rc;
+      if (want_dkdv) launch_kinds_note(USP_KIND_DKDV_QK192);
+      if (want_dq && (rc = launch_dq_qk192(p, a->dtype, mask.causal, (hipStream_t)stream)) == USP_OK) launch_kinds_note(USP_KIND_DQ_QK192);
+      return rc;
+    }
     if (want_dkdv && (rc = launch_dkdv_d256(p, a->dtype, mask.causal, (hipStream_t)stream)) != USP_OK) return rc;
     if (want_dkdv) launch_kinds_note(USP_KIND_DKDV_D256);
     if (want_dq && (rc = launch_dq_d256(p, a->dtype, mask.causal, (hipStream_t)stream)) == USP_OK) launch_kinds_note(USP_KIND_DQ_D256);
@@ -516,6 +525,11 @@ static int flash_bwd_call(const usp_bwd_args* a_in, usp::BwdExtras x, void* stre
 }
 
 extern "C" int usp_flash_bwd(const usp_bwd_args* a, void* stream) { return flash_bwd_call(a, usp::BwdExtras{}, stream); }
+
+extern "C" int usp_flash_bwd_vdim(const usp_bwd_args* a, int32_t head_dim_v, void* stream) {
+  if (head_dim_v <= 0) return USP_EINVAL;
+  return flash_bwd_call(a, usp::BwdExtras{}, stream, head_dim_v);
+}
 
 extern "C" int usp_flash_bwd_alibi(const usp_bwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
   usp::BwdExtras x;

@@ -19,6 +19,7 @@
 #include "usp_fwd_params.hpp"
 #include "usp_host.hpp"
 #include "usp_d256.hpp"
+#include "usp_qk192.hpp"
 
 namespace usp {
 
@@ -264,13 +265,16 @@ extern "C" int64_t usp_flash_fwd_workspace_bytes(const usp_fwd_args* a, int32_t 
 }
 
 // usp_flash_fwd (alibi_slopes == NULL, p_drop == 0, sinks == NULL, row_lo == NULL), usp_flash_fwd_alibi, usp_flash_fwd_dropout,
-// usp_flash_fwd_sink, usp_flash_fwd_maxlogit, usp_flash_fwd_doc and usp_flash_fwd_span
-static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream) {
+// usp_flash_fwd_sink, usp_flash_fwd_maxlogit, usp_flash_fwd_doc and usp_flash_fwd_span; usp_flash_fwd_vdim with `head_dim_v` (0: that of
+// q and k)
+static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream, int head_dim_v = 0) {
   using namespace usp;
   launch_kinds_reset();
   if (!a || !a->lse) return USP_EINVAL;
+  const bool qk192 = head_dim_v != 0 && head_dim_v != a->D;       // v, out and acc of another head dim: (192, 128) or nothing
+  if (qk192 && !(a->D == 192 && head_dim_v == 128)) return USP_EUNSUPPORTED;
   if (int rc = check_force(a->flags)) return rc;
-  if (int rc = check_problem(*a)) return rc;
+  if (int rc = check_problem(*a, qk192)) return rc;
   if (int rc = check_alibi(*a, x.al.al_slopes, x.al.al_sb)) return rc;
   if (int rc = check_dropout(*a, x.dc, &x.dr)) return rc;
   if (int rc = check_sink(*a, x.sinks)) return rc;
@@ -280,7 +284,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   if (int rc = check_span(*a, x.span.row_hi != nullptr, x.doc.row_lo_sb, x.span.row_hi_sb, 0, 0)) return rc;
   if (int rc = check_bsp(*a, x.bsp.mask, x.bsp.sb, x.bsp.sh, x.bsp.sr, x.bsp.lists)) return rc;
   if (x.bsp.mask) x.bsp.layout = block_lists(a->B, a->Hq, (a->Sq + 127) / 128, (a->Sk + 127) / 128);   // once per call
-  if (int rc = check_d256(*a, x.any())) return rc;
+  if (int rc = check_plain_dense_family(*a, x.any(), qk192)) return rc;
   if (!tensor_aligned(a->q, 16, 8) || !tensor_aligned(a->k, 16, 8) || !tensor_aligned(a->v, 16, 8))
     return USP_EUNSUPPORTED;
   const bool packed = a->seq_q != nullptr || a->seq_k != nullptr;
@@ -318,7 +322,7 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   p.interleave = (a->flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
   p.ksplit = 1; p.ws_o = nullptr; p.ws_lse = nullptr;
-  if (a->k_splits > 1 && a->workspace != nullptr && !x.doc.row_lo && !x.span.row_hi && !x.bsp.mask && !x.mx.row_max) {   // (a document, span, block-sparse or max-logit launch is served uncut: usp_hip.h)
+  if (a->k_splits > 1 && a->workspace != nullptr && !qk192 && !x.doc.row_lo && !x.span.row_hi && !x.bsp.mask && !x.mx.row_max) {   // (a document, span, block-sparse or max-logit launch is served uncut: usp_hip.h)
     if (packed) return USP_EUNSUPPORTED;                       // dense launches only
     if (a->k_splits > 8 || !aligned(a->workspace, 16)) return USP_EINVAL;
     if ((any_acc || a->merge_in) && (a->acc.stride_h % 4 != 0)) return USP_EUNSUPPORTED;
@@ -329,6 +333,11 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
   if (packed) p.q_sb = p.k_sb = p.v_sb = p.o_sb = p.a_sb = p.lse_sb = 0;
   x.al.al_diag = alibi_diag(*a);
   const int force = a->flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32);
+  if (qk192) {                                     // a family of its own (usp_flash_fwd_qk192.hip), served uncut: k_splits is ignored
+    const int rc = launch_fwd_qk192(p, a->dtype, mask.causal, (hipStream_t)stream);
+    if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_QK192);
+    return rc;
+  }
   if (a->D == 256) {                               // a family of its own (usp_flash_fwd_d256.hip), served uncut: k_splits is ignored
     const int rc = launch_fwd_d256(p, a->dtype, mask.causal, (hipStream_t)stream);
     if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_D256);
@@ -340,6 +349,11 @@ static int flash_fwd_call(const usp_fwd_args* a, usp::FwdExtras x, void* stream)
 }
 
 extern "C" int usp_flash_fwd(const usp_fwd_args* a, void* stream) { return flash_fwd_call(a, usp::FwdExtras{}, stream); }
+
+extern "C" int usp_flash_fwd_vdim(const usp_fwd_args* a, int32_t head_dim_v, void* stream) {
+  if (head_dim_v <= 0) return USP_EINVAL;
+  return flash_fwd_call(a, usp::FwdExtras{}, stream, head_dim_v);
+}
 
 extern "C" int usp_flash_fwd_alibi(const usp_fwd_args* a, const float* alibi_slopes, int64_t alibi_stride_b, void* stream) {
   usp::FwdExtras x;

@@ -81,7 +81,8 @@ template <bool WITH256 = false, class F> int with_head_dim_dtype(int D, int dtyp
 inline int check_force(int flags) {
   return (flags & USP_FORCE_ROW64) && (flags & USP_FORCE_WAVE32) ? USP_EINVAL : USP_OK;
 }
-template <class Args> int check_problem(const Args& a) {
+// `qk192`: a usp_flash_*_vdim call of head dims (192, 128) -- the one place where D = 192 is a head dim with kernels
+template <class Args> int check_problem(const Args& a, bool qk192 = false) {
   if (a.dtype != USP_BF16 && a.dtype != USP_FP16) return USP_EINVAL;
   if (a.B <= 0 || a.Sq <= 0 || a.Sk <= 0 || a.Hq <= 0 || a.Hkv <= 0) return USP_EINVAL;
   if (!(a.softmax_scale > 0.f)) return USP_EINVAL;
@@ -89,16 +90,17 @@ template <class Args> int check_problem(const Args& a) {
   if (has_cap && !(__builtin_isfinite(a.softcap) && a.softcap > 0.f)) return USP_EINVAL;
   if (has_cap && (a.flags & USP_FORCE_ROW64)) return USP_EUNSUPPORTED;   // the 64-row family declines softcap
   if ((a.flags & USP_ATTN_SHIFT) && (a.mask_shift >= (1 << 30) || a.mask_shift <= -(1 << 30))) return USP_EINVAL;
-  if (a.D != 32 && a.D != 64 && a.D != 128 && a.D != 256) return USP_EUNSUPPORTED;
+  if (a.D != 32 && a.D != 64 && a.D != 128 && a.D != 256 && !(qk192 && a.D == 192)) return USP_EUNSUPPORTED;
   if (a.Hq % a.Hkv != 0) return USP_EUNSUPPORTED;
   return USP_OK;
 }
 
 // Head dim 256 (usp_flash_fwd_d256.hip / usp_flash_bwd_d256.hip) is the plain dense launch and nothing else: declined are softcap, a
 // window bound that cuts something, a packed batch, a forced family or dK/dV item width, and every extra entry point (`extras`).
-// Judged behind check_problem and the extras' own checks, before anything is launched or written.
-template <class Args> int check_d256(const Args& a, bool extras) {
-  if (a.D != 256) return USP_OK;
+// Judged behind check_problem and the extras' own checks, before anything is launched or written.  The (192, 128) family
+// (usp_flash_fwd_qk192.hip / usp_flash_bwd_qk192.hip: `qk192`) serves and declines exactly the same.
+template <class Args> int check_plain_dense_family(const Args& a, bool extras, bool qk192 = false) {
+  if (a.D != 256 && !qk192) return USP_OK;
   if (extras || (a.flags & USP_ATTN_SOFTCAP) || a.seq_q || a.seq_k) return USP_EUNSUPPORTED;
   if (a.flags & (USP_FORCE_ROW64 | USP_FORCE_WAVE32 | USP_DKDV_KEYS128 | USP_DKDV_KEYS256)) return USP_EUNSUPPORTED;
   const bool has_win = (a.flags & USP_ATTN_WINDOW) != 0, has_shift = (a.flags & USP_ATTN_SHIFT) != 0;

@@ -23,7 +23,7 @@ from .._C import softcap_value
 from ..comm import all_to_all as A
 from ..comm.link import device_cus, kernel_flops_per_s, link_bytes_per_s
 from ..kernels.attention import kernel_head_dim, pad_head_dim
-from ..kernels.features import head_dim_256_alone
+from ..kernels.features import head_dim_256_alone, head_dims_192_128_alone
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..ring.ring_flash_attn import ring_flash_attn_backward, ring_flash_attn_forward
@@ -554,6 +554,9 @@ class AsyncLongContextAttention(torch.nn.Module):
                                       "with the basic ring (ring_impl_type=\"basic\")")
         _check_hot_path_args(dropout_p, window_size, softcap)
         D = query.shape[-1]
+        if head_dims_192_128_alone(D, value.shape[-1], window_size, softcap, dropout_p=dropout_p):
+            raise NotImplementedError("AsyncLongContextAttention: the packed exchange and the head-group pipeline carry one head dim; "
+                                      "head dims (192, 128) of q / k and v are served by LongContextAttention")
         head_dim_256_alone(D, window_size, softcap, dropout_p=dropout_p)
         if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate: zero-padded copies
             query, key, value = pad_head_dim(query, key, value)

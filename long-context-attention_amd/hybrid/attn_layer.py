@@ -19,7 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..kernels.features import block_mask_alone, block_select_alone, head_dim_256_alone, max_logits_alone, return_block_mass_alone
+from ..kernels.features import block_mask_alone, block_select_alone, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone, return_block_mass_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -171,9 +171,15 @@ class LongContextAttention(_USPLayer):
         blocks, (bs, head_cnt / ulysses degree, n, nb) (ring/front_end.py: ring_block_attention_mass: K alone makes a second
         rotation behind the forward, from the exchanged k and the ring's lse).  The layer gathers nothing and reads nothing on
         the host.  Served with the basic ring at any ring degree (a local length behind the exchange that is a multiple of
-        128), with the zigzag and stripe rings at ring degree 1, through three exchanges."""
-        head_dim_256_alone(query.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
-                           block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
+        128), with the zigzag and stripe rings at ring degree 1, through three exchanges.
+        Head dims (192, 128) -- query and key of 192, value of 128 -- go with none of the options, through three exchanges (the packed
+        exchange and the head-group pipeline carry one width), with the basic and the zigzag ring: context is (bs, seq_len/N,
+        head_cnt, 128)."""
+        qk192 = head_dims_192_128_alone(query.shape[-1], value.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
+                                        bidirectional, block_mask, block_select, return_max_logits, return_block_mass)
+        if not qk192:
+            head_dim_256_alone(query.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                               block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
         bmass = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
                                         bidirectional, block_mask, block_select, return_max_logits)
         ml = max_logits_alone(return_max_logits, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
@@ -181,14 +187,14 @@ class LongContextAttention(_USPLayer):
         block_select_alone(block_select, block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional)
         D = query.shape[-1]
-        if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
+        if not qk192 and kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
             out = self.forward(*pad_head_dim(query, key, value), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale,
                                causal, window_size, softcap, alibi_slopes, deterministic, return_attn_probs, *args, sinks=sinks,
                                cu_doclens=cu_doclens, bidirectional=bidirectional, block_mask=block_mask, return_max_logits=ml,
                                block_select=block_select, return_block_mass=bmass)
             return (out[0][..., :D], out[1]) if ml or bmass else out[..., :D]
         cu_doclens = self._docs(cu_doclens, query.shape[0], query.shape[1], bidirectional)     # (the single document: None from here on)
-        ng_cap = self._packed_exchange(query, key)
+        ng_cap = None if qk192 else self._packed_exchange(query, key)
         if ng_cap is not None and (block_mask is not None or block_select is not None or cu_doclens is not None or window_of(window_size) is not None or alibi_slopes is not None
                                    or dropout_value(dropout_p) is not None or sinks is not None or ml or bmass):
             # Any of them: the reference's structure (three exchanges), and the ring function serves it (ring/front_end.py: _place).

@@ -17,7 +17,8 @@ import torch
 
 from .. import _C
 from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
-                       block_select_alone, expand_block_mask, head_dim_256_alone, max_logits_alone, return_block_mass_alone)
+                       block_select_alone, expand_block_mask, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone,
+                       return_block_mass_alone)
 
 
 def kernel_operand(t: torch.Tensor) -> torch.Tensor:
@@ -518,7 +519,17 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     `return_block_mass` (keyword only): the result is (out, lse, mass), mass = block_attention_mass(q, k, lse, ...) of the call's
     own lse, computed behind the forward: fp32 (B, Hq, nb, nb) without gradient.  out and lse are bit for bit those of the call
     without it.  Goes with none of the other options and needs equally long q and k.  False: exactly the call without it.
-    Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone)."""
+    Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone).
+    A v of head dim 128 beside q and k of head dim 192 runs on a kernel family of its own, with none of the options either
+    (kernels/features.py: head_dims_192_128_alone): block_out is (B,Sq,Hq,128), the default scale 192 ** -0.5; any other unequal
+    pair raises NotImplementedError."""
+    if head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                               block_mask, block_select, return_max_logits, return_block_mass):
+        B, Sq, Hq, _ = q.shape
+        out = torch.empty((B, Sq, Hq, v.shape[-1]), dtype=q.dtype, device=q.device)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        get_block_backend().fwd(q, k, v, _default_scale(q, softmax_scale), bool(causal), lse, out=out)
+        return out, lse
     head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                        block_select, return_max_logits, return_block_mass)
     if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
@@ -579,8 +590,12 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one.
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
-    `cu_doclens`, `bidirectional`, `block_mask` (keyword only): as hip_attn_forward took them."""
-    head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
+    `cu_doclens`, `bidirectional`, `block_mask` (keyword only): as hip_attn_forward took them.
+    Head dims (192, 128): dout, out and block_dv_buffer have v's head dim (kernels/features.py: head_dims_192_128_alone)."""
+    qk192 = head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
+                                    bidirectional, block_mask)
+    if not qk192:
+        head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
     bsp_kw = {}
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         bsp_kw = dict(bsp=block_mask_of(block_mask, q, k))
@@ -590,7 +605,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     dr = _dropout_of(f.dropout, rng_state, "hip_attn_backward")
     B, Sq, Hq, D = q.shape
     dev = q.device
-    if kernel_head_dim(D) != D:                 # on zero-padded copies; the first D dims of the gradients are the answer
+    if not qk192 and kernel_head_dim(D) != D:   # on zero-padded copies; the first D dims of the gradients are the answer
         pdo, pq, pk, pv, po = pad_head_dim(dout, q, k, v, out)
         g = [torch.empty_like(t) for t in (pq, pk, pv)]
         hip_attn_backward(pdo, pq, pk, pv, po, softmax_lse, g[0], g[1], g[2], dropout_p, _default_scale(q, softmax_scale),
@@ -688,7 +703,13 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     the fp32 (B, Hq, nb, nb) block-pooled attention map of the call (block_attention_mass on the call's own lse, computed under
     no_grad behind the forward), padded head dims included; no gradient, never read on the host.  `out`, the lse and the
     gradients are bit for bit those of the call without it.  Goes with none of the other options.
-    Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone)."""
+    Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone).
+    Head dims (192, 128) -- q and k of 192, v of 128 -- neither (kernels/features.py: head_dims_192_128_alone): out is
+    (B,Sq,Hq,128), the default scale 192 ** -0.5, dv has v's shape."""
+    if head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                               block_mask, block_select, return_max_logits, return_block_mass):
+        res = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, bool(return_attn_probs))
+        return (res[0], res[1], None) if return_attn_probs else res
     head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                        block_select, return_max_logits, return_block_mass)
     if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,

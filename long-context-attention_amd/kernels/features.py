@@ -11,7 +11,7 @@ kernels/attention.py: select_blocks_top_p).  Pure argument logic: nothing here l
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
-from .._C import _window, alibi_value, block_select_top_p_value, block_select_value, dropout_value, sinks_value, softcap_value
+from .._C import HEAD_DIMS_QK_V, _window, alibi_value, block_select_top_p_value, block_select_value, dropout_value, sinks_value, softcap_value
 
 # field of the record -> the flash-attn-style argument the messages name
 ARGUMENT = dict(window="window_size", softcap="softcap", alibi="alibi_slopes", dropout="dropout_p", sinks="sinks", doc="cu_doclens")
@@ -149,6 +149,30 @@ def head_dim_256_alone(D: int, window_size=None, softcap=None, alibi_slopes=None
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"head_dim {D} (kernel head dim 256) together with {name} is not supported by the HIP "
+                                      f"attention kernels")
+    return True
+
+
+def head_dims_192_128_alone(D: int, Dv: int, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
+                            cu_doclens=None, bidirectional=None, block_mask=None, block_select=None, return_max_logits=False,
+                            return_block_mass=False, packed=False) -> bool:
+    """Does a call with q and k of head dim `D` and v of head dim `Dv` run on the (192, 128) family (csrc/usp_flash_fwd_qk192.hip,
+    csrc/usp_flash_bwd_qk192.hip)?  False for equal head dims.  That family is the plain dense call -- causal or full, GQA, the
+    rings' fused merge -- and nothing else: judged HERE like head_dim_256_alone, before any tensor is read, it goes with none of
+    the options, nor with a packed (variable-length) batch (`packed`).  Any other unequal pair is refused, naming both dims: nothing
+    is padded to (192, 128)."""
+    if D == Dv:
+        return False
+    if (D, Dv) != HEAD_DIMS_QK_V:
+        raise NotImplementedError(f"head_dim {D} of q and k with head_dim {Dv} of v is not supported by the HIP attention kernels: "
+                                  f"unequal head dims are served for {HEAD_DIMS_QK_V} alone")
+    given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
+             ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional),
+             ("block_mask", block_mask), ("block_select", block_select), ("return_max_logits", return_max_logits or None),
+             ("return_block_mass", return_block_mass or None), ("a packed (variable-length) batch", packed or None))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"head dims {HEAD_DIMS_QK_V} of q / k and v together with {name} are not supported by the HIP "
                                       f"attention kernels")
     return True
 

@@ -10,7 +10,7 @@ from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_top_p_value, block_select
 from ..kernels import AttnType
 from ..kernels.attention import (block_attention_mass, draw_seed, get_block_backend, kernel_head_dim, kernel_operand,
                                  mass_operands, needs_grad, pad_head_dim, select_blocks, select_blocks_top_p, select_operands)
-from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone, head_dim_256_alone,
+from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone, head_dim_256_alone, head_dims_192_128_alone,
                                 max_logits_alone, return_block_mass_alone)
 from .utils import RingComm, group_info
 from .varlen_utils import unflatten_lse
@@ -353,6 +353,22 @@ def ring_dropout(dropout_p, rng_state):
     return p, int(rng_state[0]), int(rng_state[1])
 
 
+_QK192_RINGS = ("ring_flash_attn", "zigzag_ring_flash_attn")
+
+
+def head_dims_192_128_ring(name, D, Dv, *options):
+    """Does the ring call `name` (<stem>_func, ...) run at head dims (192, 128) (kernels/features.py: head_dims_192_128_alone, which
+    refuses every option and every other unequal pair)?  Judged first, before any tensor is read.  The dense basic and zigzag rings
+    serve it at any ring degree -- K and V travel in separate slots, and out, acc, dV and the travelling dV take v's width --; the
+    packed forms (one tensor cannot hold both widths), the stripe ring and the varlen rings refuse and name those two."""
+    if not head_dims_192_128_alone(D, Dv, *options):
+        return False
+    if name not in tuple(r + "_func" for r in _QK192_RINGS):
+        raise NotImplementedError(f"{name}: head dims (192, 128) of q / k and v are served by ring_flash_attn_func and "
+                                  f"zigzag_ring_flash_attn_func with separate q, k and v")
+    return True
+
+
 def ring_front_end(stem, class_name, forward, backward, serves: RingServes, packed=False, attn_processor=False):
     """(Function, <stem>_func, <stem>_kvpacked_func, <stem>_qkvpacked_func) of the ring `forward` / `backward`.
 
@@ -477,7 +493,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                  softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None, *, sinks=None,
                  cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
                  return_block_mass=False):
-            head_dim_256_alone(q.shape[-1], packed=True)     # judged first (kernels/features.py)
+            if not head_dims_192_128_ring(stem + "_func", q.shape[-1], v.shape[-1]):
+                head_dim_256_alone(q.shape[-1], packed=True)     # judged first (kernels/features.py)
             _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
@@ -491,7 +508,8 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                           window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                           group=None, *, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False, block_select=None,
                  return_block_mass=False):
-            head_dim_256_alone(q.shape[-1], packed=True)     # judged first (kernels/features.py)
+            if not head_dims_192_128_ring(stem + "_kvpacked_func", q.shape[-1], kv.shape[-1]):
+                head_dim_256_alone(q.shape[-1], packed=True)     # judged first (kernels/features.py)
             _refuse_packed_block_mass(return_block_mass)
             _refuse_packed_max_logits(return_max_logits)
             _refuse_packed_block_mask(block_mask)
@@ -529,8 +547,11 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                  alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                  attn_type: AttnType = AttnType.HIP, attn_processor=None, *, dropout_head0=0, sinks=None, cu_doclens=None,
                  bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
-            head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
-                               block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
+            qk192 = head_dims_192_128_ring(stem + "_func", q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks,
+                                           cu_doclens, bidirectional, block_mask, block_select, return_max_logits, return_block_mass)
+            if not qk192:
+                head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                                   block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
             if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                        block_mask, block_select, return_max_logits):
                 return block_mass_call(serves, lambda probs: func(q, k, v, 0.0, softmax_scale, causal, deterministic=deterministic,
@@ -543,7 +564,7 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                                          block_select)
             cu_doclens = span_plan(q, group, cu_doclens, bidirectional)       # (the spans travel inside the plan from here on)
             D = q.shape[-1]
-            if kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
+            if not qk192 and kernel_head_dim(D) != D:      # a head dim the kernels do not instantiate (e.g. 96): zero-padded copies
                 res = func(*pad_head_dim(q, k, v), dropout_p, D ** -0.5 if softmax_scale is None else softmax_scale, causal,
                            window_size, softcap, alibi_slopes, deterministic, return_attn_probs, group, attn_type, attn_processor,
                            dropout_head0=dropout_head0, sinks=sinks, cu_doclens=cu_doclens, return_max_logits=ml)
@@ -559,6 +580,7 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
                           alibi_slopes=None, deterministic=False, return_attn_probs=False, group=None,
                           attn_type: AttnType = AttnType.HIP, *, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None,
                           block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+            head_dims_192_128_ring(stem + "_kvpacked_func", q.shape[-1], kv.shape[-1])     # (one tensor cannot hold both widths)
             head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                                block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
             if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,

@@ -176,7 +176,8 @@ def ring_flash_attn_forward(process_group, q, k, v, softmax_scale, dropout_p=0, 
         be = RowMaxBackend(be)
     if pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
-    B, S, H, D = q.shape
+    B, S, H, _ = q.shape
+    D = v.shape[-1]                  # out and acc take v's head dim (head dims 192 / 128: not q's)
     dev = q.device
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, S), dtype=torch.float32, device=dev)

@@ -233,6 +233,7 @@ def zigzag_forward_phases(process_group, q, k, v, softmax_scale, overlap=False, 
     if P == 1 and pieces:
         return block_pieces.forward_in_pieces(be, q, k, v, softmax_scale, first, tail)
     dev = q.device
+    D = v.shape[-1]                  # out and acc take v's head dim (head dims 192 / 128: not q's)
     out = torch.empty((B, S2, H, D), dtype=q.dtype, device=dev)
     lse = torch.empty((B, H, S2), dtype=torch.float32, device=dev)
     if P == 1:           # one block, no relay, no running accumulator
