@@ -177,6 +177,41 @@ enum {
  *             D == 192 is USP_EUNSUPPORTED there.  Cuts and workspaces are ignored, the workspace queries are unchanged; dkdv_heads
  *             other than 0 or Hq / Hkv is USP_EINVAL.  The dK/dV item loops over its whole KV group: deterministic. */
 #define USP_ATTN_HEAD_DIMS_192_128 524288
+/* USP_ATTN_FP8: a FEATURE bit (ABI still v7; the value is free as a flag and means nothing in an argument block): usp_flash_fwd_fp8
+ * and usp_quantize_fp8 (both declared below) exist.  The forward serves q, k, v in OCP E4M3 (e4m3fn: one byte per element, largest
+ * finite value 448, no infinity), head dim 128, causal and full, on a kernel family of its own (csrc/usp_flash_fwd_fp8.hip: 4 waves,
+ * one per SIMD, 64 query rows each, both products on v_mfma_f32_32x32x64_f8f6f4; noted as USP_KIND_FWD_FP8).  Forward only: every
+ * backward stays 16-bit.  The argument block is unchanged: args->dtype is NOT read for q, k, v; `out_dtype` (USP_BF16 | USP_FP16) is
+ * the type of `out`; acc and lse are fp32 as ever; the strides of q, k, v count one-byte elements.  The descales are fp32 device
+ * arrays, contiguous, (B, Hq) for q and (B, Hkv) for k and v, NULL = all 1: the operands mean q8 * dq[b, h], k8 * dk[b, hkv],
+ * v8 * dv[b, hkv].
+ *   the numbers   s_ij = softmax_scale * dq[b, h] * dk[b, hkv] * sum_d q8_id k8_jd, one fp32 MFMA chain over d (products of two
+ *             e4m3 values are exact in fp32); the two descales are folded into the per-(b, head) exponent scale.
+ *             p_ij = exp2((s_ij - m_i) * log2(e)) in fp32 against the running row maximum m_i.  The ROW SUM and `lse` are taken from
+ *             these fp32 values: lse is the logsumexp of the dequantized scores to fp32 accuracy, and merges like any other.
+ *             For the value product p_ij is rounded to e4m3 (round to nearest even) after a multiplication by 2^8, which is folded
+ *             into the exponent offset: the maximum is the true one of every key seen so far (taken before the exponentials, never
+ *             raised lazily), so 2^8 p_ij <= 2^8 (1 + 2^-20) < 448 by construction and no conversion saturates or overflows;
+ *             probabilities down to 2^-14 stay normal (relative rounding error <= 2^-4), below that the step is 2^-9 / 2^8.  Row
+ *             sum and product carry the same 2^8, so it cancels in the quotient; dv[b, hkv] rides the epilogue factor.
+ *             out_i = dv * (sum_j e4m3(2^8 p_ij) v8_j) / (sum_j 2^8 p_ij), the numerator one fp32 MFMA chain per 64 keys.
+ *   served    everything the plain dense launch honours, as USP_ATTN_HEAD_DIM_256 lists it: causal with the bottom-right alignment,
+ *             ragged Sq / Sk, Sq != Sk (a row that sees no key: out = 0, lse = -inf), USP_ATTN_SHIFT on a causal launch, GQA,
+ *             merge_in, acc, final_begin / final_end, USP_LAUNCH_INTERLEAVE, any strides of q, k, v with a unit last one whose rows
+ *             are 16-byte aligned (pointer and every stride a multiple of 16 ELEMENTS); out and acc aligned as for usp_flash_fwd.
+ *             Served uncut: k_splits and the workspace are ignored, no workspace is needed.
+ *   declined  USP_EUNSUPPORTED, nothing launched or written: a head dim other than 128, USP_ATTN_SOFTCAP, a window bound that cuts
+ *             something, a packed batch (seq_q / seq_k), USP_FORCE_ROW64, USP_FORCE_WAVE32, misaligned tensors, a row stride of k
+ *             or v of 2^25 bytes or more.  out_dtype outside the two types, or a descale pointer off a 4-byte boundary: USP_EINVAL.
+ * usp_quantize_fp8 makes such operands from a 16-bit (B, S, H, D) tensor `x` (dtype = USP_BF16 | USP_FP16; usp_tensor strides in
+ * elements plus the last dim's stride, any values): descale[b * H + h] = max |x[b, :, h, :]| / 448 (one fp32 division; 1 for an
+ * all-zero head), x8 = e4m3(x / descale[b, h]) rounded to nearest even -- the largest element of a head becomes +-448.  Two launches
+ * on `stream`, no atomics, the same bits every run.  `partial`: fp32 device scratch of USP_QUANT_FP8_PARTIAL_FLOATS(B, S, H) floats,
+ * the maxima of every USP_QUANT_FP8_ROWS rows of a head.  NaN inputs are not looked for.  USP_EINVAL: a NULL pointer, a size <= 0, a
+ * bad dtype; USP_EUNSUPPORTED: B or H above 65535, D of 2^18 or more. */
+#define USP_ATTN_FP8 1048576
+#define USP_QUANT_FP8_ROWS 64
+#define USP_QUANT_FP8_PARTIAL_FLOATS(B, S, H) ((int64_t)(B) * (H) * (((S) + USP_QUANT_FP8_ROWS - 1) / USP_QUANT_FP8_ROWS))
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
  * exists in two forms, both noted as USP_KIND_DKDV_ROW64:
  *   USP_DKDV_KEYS128  flash_bwd_dkdv64_kernel: a work item owns 128 keys, two waves share a 64-key slice (S, P, dV | dP, dS, dK);
@@ -272,6 +307,11 @@ typedef struct usp_fwd_args {
 
 int usp_flash_fwd(const usp_fwd_args* args, void* stream);
 int usp_flash_fwd_vdim(const usp_fwd_args* args, int32_t head_dim_v, void* stream);   /* USP_ATTN_HEAD_DIMS_192_128 */
+/* USP_ATTN_FP8 (see the bit) */
+int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descale, const float* k_descale, const float* v_descale,
+                      int32_t out_dtype, void* stream);
+int usp_quantize_fp8(int32_t dtype, const usp_tensor* x, int64_t x_stride_d, const usp_tensor* x8, int64_t x8_stride_d,
+                     float* descale, float* partial, int32_t B, int32_t S, int32_t H, int32_t D, void* stream);
 
 /* K split (dense launches): a launch with few (batch, head, 256-row tile) work items cannot fill 256 CUs, and a causal
  * one lasts as long as its heaviest item (measured on MI355X, B1 S16384 D128 causal: 2 heads 548 TFLOP/s, 4 heads 891,
@@ -805,7 +845,8 @@ enum {
   USP_KIND_DQ_D256 = 8192,      /* flash_bwd_dq_d256_kernel  (head dim 256: 4 waves x 32 rows) */
   USP_KIND_FWD_QK192 = 16384,   /* flash_fwd_qk192_kernel      (head dims 192 / 128: 4 waves x 64 rows) */
   USP_KIND_DKDV_QK192 = 32768,  /* flash_bwd_dkdv_qk192_kernel (head dims 192 / 128: 4 waves x 32 keys) */
-  USP_KIND_DQ_QK192 = 65536     /* flash_bwd_dq_qk192_kernel   (head dims 192 / 128: 4 waves x 32 rows) */
+  USP_KIND_DQ_QK192 = 65536,    /* flash_bwd_dq_qk192_kernel   (head dims 192 / 128: 4 waves x 32 rows) */
+  USP_KIND_FWD_FP8 = 131072     /* flash_fwd_fp8_kernel        (e4m3 q, k, v at head dim 128: 4 waves x 64 rows) */
 };
 int usp_last_launch_kinds(void);
 
@@ -825,6 +866,7 @@ int usp_abi_version(void);
  * USP_ATTN_DROPOUT | USP_ATTN_SINK | USP_ATTN_DOC | USP_ATTN_SPAN | USP_ATTN_BLOCK_MASK | USP_ATTN_MAX_LOGIT | USP_ATTN_BLOCK_SELECT |
  * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS | USP_ATTN_HEAD_DIM_256 | USP_ATTN_HEAD_DIMS_192_128, the last twelve feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
  * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist, head dim 256 is served, usp_flash_*_vdim exist).
+ * USP_ATTN_FP8 is the thirteenth: usp_flash_fwd_fp8 and usp_quantize_fp8 exist.
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -42,6 +42,8 @@ USP_ATTN_BLOCK_SELECT_TOP_P = 65536  # feature bit of usp_attn_features(): usp_b
 USP_ATTN_BLOCK_MASS = 131072   # feature bit of usp_attn_features(): usp_block_attn_mass exists (not an args flag)
 USP_ATTN_HEAD_DIM_256 = 262144 # feature bit of usp_attn_features(): usp_flash_fwd / usp_flash_bwd serve head_dim 256 (not an args flag)
 USP_ATTN_HEAD_DIMS_192_128 = 524288  # feature bit of usp_attn_features(): usp_flash_fwd_vdim / usp_flash_bwd_vdim exist (not an args flag)
+USP_ATTN_FP8 = 1048576         # feature bit of usp_attn_features(): usp_flash_fwd_fp8 / usp_quantize_fp8 exist (not an args flag)
+QUANT_FP8_ROWS = 64            # rows of one partial maximum of usp_quantize_fp8 (include/usp_hip.h: USP_QUANT_FP8_ROWS)
 HEAD_DIMS_QK_V = (192, 128)    # the one pair of unequal head dims (q and k, v) they serve (the rule: kernels/features.py)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
 BLOCK_MASK_SIZE = 128          # rows and keys of one block of a block mask (include/usp_hip.h: USP_BLOCK_MASK_SIZE)
@@ -54,6 +56,8 @@ KINDS = {1: "fwd_row64", 2: "fwd_wave8", 4: "fwd_wave4", 8: "fwd_split_merge", 1
 KINDS_D256 = {2048: "fwd_d256", 4096: "dkdv_d256", 8192: "dq_d256"}
 # ... and the (192, 128) family's (csrc/usp_flash_fwd_qk192.hip, csrc/usp_flash_bwd_qk192.hip)
 KINDS_QK192 = {16384: "fwd_qk192", 32768: "dkdv_qk192", 65536: "dq_qk192"}
+# ... and the e4m3 forward's (csrc/usp_flash_fwd_fp8.hip)
+KINDS_FP8 = {131072: "fwd_fp8"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -92,7 +96,7 @@ def last_dkdv_item_keys() -> int:
 def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
-    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items()) if m & bit)
+    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items()) if m & bit)
 
 
 class UspTensor(ctypes.Structure):
@@ -144,7 +148,8 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_flash_fwd_sink", "usp_sink_bwd", "usp_flash_fwd_doc", "usp_flash_bwd_doc", "usp_flash_fwd_span", "usp_flash_bwd_span",
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
-           "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
+           "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim",
+           "usp_flash_fwd_fp8", "usp_quantize_fp8")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -159,6 +164,7 @@ SELECT_EXPORTS = ("usp_block_means", "usp_block_select")
 SELECT_TOP_P_EXPORTS = ("usp_block_select_top_p",)
 MASS_EXPORTS = ("usp_block_attn_mass",)
 VDIM_EXPORTS = ("usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
+FP8_EXPORTS = ("usp_flash_fwd_fp8", "usp_quantize_fp8")
 
 
 def lib_path() -> str:
@@ -177,7 +183,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -728,7 +734,10 @@ def _feature_entries():
                                     [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64, f32,
                                      i32, i32, vp, i64, i64, i64, vp]),
             "usp_flash_fwd_vdim": (USP_ATTN_HEAD_DIMS_192_128, "v of another head dim (USP_ATTN_HEAD_DIMS_192_128)", [fwd, i32, vp]),
-            "usp_flash_bwd_vdim": (USP_ATTN_HEAD_DIMS_192_128, "v of another head dim (USP_ATTN_HEAD_DIMS_192_128)", [bwd, i32, vp])}
+            "usp_flash_bwd_vdim": (USP_ATTN_HEAD_DIMS_192_128, "v of another head dim (USP_ATTN_HEAD_DIMS_192_128)", [bwd, i32, vp]),
+            "usp_flash_fwd_fp8": (USP_ATTN_FP8, "float8_e4m3fn q, k, v (USP_ATTN_FP8)", [fwd, vp, vp, vp, i32, vp]),
+            "usp_quantize_fp8": (USP_ATTN_FP8, "quantize_fp8 (USP_ATTN_FP8)",
+                                 [i32, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor), i64, vp, vp, i32, i32, i32, i32, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -886,7 +895,8 @@ def _fwd_args(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_beg
 def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=None,
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
-              alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None, row_max=None):
+              alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None, row_max=None,
+              q_descale=None, k_descale=None, v_descale=None, out_dtype=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  A v of head dim 128 beside q and k of head dim 192 (HEAD_DIMS_QK_V) goes to usp_flash_fwd_vdim,
     with out / acc of v's head dim: the plain dense launch, every option below refused here or declined by the library.  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
@@ -914,7 +924,18 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     (block_list_bytes, block_list_layout; None: allocated here).
     `row_max`: an fp32 (B, Hq, Sq) device tensor with unit seq stride (row_max_value), None = off: receives the largest visible
     softmax_scale * q.k of every row, -inf where a row sees nothing; with merge_in the maximum with the value there
-    (usp_flash_fwd_maxlogit; served uncut, k_splits ignored; goes with window and shift alone; not with family="row64")."""
+    (usp_flash_fwd_maxlogit; served uncut, k_splits ignored; goes with window and shift alone; not with family="row64").
+    q, k, v in torch.float8_e4m3fn at head dim 128 go to usp_flash_fwd_fp8 (kernels/features.py: fp8_alone): the plain dense launch
+    with `shift` alone of the options; `q_descale` (B, Hq), `k_descale` / `v_descale` (B, Hkv): fp32 device tensors, None = 1;
+    `out_dtype`: the type of `out` (None: out's own, bfloat16 without one); k_splits is ignored."""
+    from .kernels.features import fp8_alone
+    if fp8_alone(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale):   # judged before any tensor is read
+        _fp8_alone(window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), sinks=sinks,
+                   doc=doc, span=span, bsp=bsp, row_max=row_max, family=family)
+        _require_cuda(q, k, v, lse, out, acc, q_descale, k_descale, v_descale)
+        _flash_fwd_fp8(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end, interleave, shift,
+                       q_descale, k_descale, v_descale, out_dtype)
+        return
     Dv = head_dim_v_of(q, v)                            # judged before any tensor is read
     _vdim_alone(Dv, window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), sinks=sinks,
                 doc=doc, span=span, bsp=bsp, row_max=row_max)
@@ -961,6 +982,72 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
     _flash_call("fwd", a, al, dr, sk, dc, sp, mx)
+
+
+def _fp8_alone(**options):
+    """Every option of an e4m3 launch is refused by name: the entry point is the plain dense launch."""
+    for name, value in options.items():
+        if value is not None:
+            raise NotImplementedError(f"float8_e4m3fn q, k, v together with {name} are not supported by the HIP attention kernels")
+
+
+def _descale(t, name: str, B: int, H: int, device):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (B, H) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 ({B}, {H}) tensor: one factor per (batch, head)")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the operands on {device}")
+    return t
+
+
+def _flash_fwd_fp8(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, final_begin, final_end, interleave, shift,
+                   q_descale, k_descale, v_descale, out_dtype):
+    """usp_flash_fwd_fp8: the argument block of a dense launch on one-byte q, k, v (strides in elements = bytes)."""
+    B, Sq, Hq, D = q.shape
+    if out_dtype is None:
+        out_dtype = out.dtype if out is not None else torch.bfloat16
+    if out is not None and out.dtype != out_dtype:
+        raise TypeError(f"out is {out.dtype}, out_dtype {out_dtype}")
+    dq = _descale(q_descale, "q_descale", B, Hq, q.device)
+    dk = _descale(k_descale, "k_descale", B, k.shape[2], q.device)
+    dv = _descale(v_descale, "v_descale", B, k.shape[2], q.device)
+    a = UspFwdArgs()
+    a.dtype = dtype_code(out_dtype)                 # (not read for q, k, v)
+    a.B, a.Sq, a.Sk, a.Hq, a.Hkv, a.D = B, Sq, k.shape[1], Hq, k.shape[2], D
+    a.causal = 1 if causal else 0
+    a.softmax_scale = float(softmax_scale)
+    a.q, a.k, a.v, a.out, a.acc = _t4(q), _t4(k), _t4(v), _t4(out), _t4(acc)
+    a.lse, a.lse_stride_b, a.lse_stride_h = _lse3(lse)
+    a.merge_in = 1 if merge_in else 0
+    a.final_begin = final_begin
+    a.final_end = Sq if final_end is None else final_end
+    a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
+    _set_shift(a, _shift(shift))
+    _check(_feature_entry("usp_flash_fwd_fp8")(ctypes.byref(a), _ptr(dq), _ptr(dk), _ptr(dv), a.dtype, _stream()),
+           "usp_flash_fwd_fp8")
+
+
+def quantize_fp8(x, out=None):
+    """usp_quantize_fp8: a 16-bit (B, S, H, D) device tensor (any strides) -> (x8, descale): x8 torch.float8_e4m3fn of x's shape
+    (`out`, or a new contiguous one), descale fp32 (B, H) = max |x[b, :, h, :]| / 448 (1 for an all-zero head), x8 = x / descale
+    rounded to nearest even.  Two launches, deterministic, nothing read on the host."""
+    _require_cuda(x, out)
+    if x.dim() != 4:
+        raise ValueError(f"quantize_fp8 takes a (B, S, H, D) tensor, got {tuple(x.shape)}")
+    B, S, H, D = x.shape
+    code = dtype_code(x.dtype)
+    if out is None:
+        out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
+    if out.dtype != torch.float8_e4m3fn or out.shape != x.shape or out.device != x.device:
+        raise ValueError("quantize_fp8: out must be a torch.float8_e4m3fn tensor of x's shape on x's device")
+    descale = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    partial = torch.empty(B * H * ((S + QUANT_FP8_ROWS - 1) // QUANT_FP8_ROWS), dtype=torch.float32, device=x.device)
+    tx = UspTensor(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2))
+    ty = UspTensor(out.data_ptr(), out.stride(0), out.stride(1), out.stride(2))
+    _check(_feature_entry("usp_quantize_fp8")(code, ctypes.byref(tx), x.stride(3), ctypes.byref(ty), out.stride(3), _ptr(descale),
+                                              _ptr(partial), B, S, H, D, _stream()), "usp_quantize_fp8")
+    return out, descale
 
 
 def _maxl_alone(**others):

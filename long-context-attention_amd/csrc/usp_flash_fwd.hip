@@ -20,6 +20,7 @@
 #include "usp_host.hpp"
 #include "usp_d256.hpp"
 #include "usp_qk192.hpp"
+#include "usp_fp8.hpp"
 
 namespace usp {
 
@@ -400,4 +401,54 @@ extern "C" int usp_flash_fwd_bsp(const usp_fwd_args* a, const void* mask, int64_
   usp::FwdExtras x;                                                   // mask == NULL: exactly usp_flash_fwd
   if (mask) x.bsp = usp::BspCall{mask, mask_stride_b, mask_stride_h, mask_stride_row, (int*)lists};
   return flash_fwd_call(a, x, stream);
+}
+
+// usp_flash_fwd_fp8: e4m3 q, k, v at head dim 128 (usp_flash_fwd_fp8.hip) -- the plain dense launch and nothing else, checked as
+// flash_fwd_call checks the head-dim-256 family, with byte-sized inputs: rows of q, k, v are 16-byte = 16-element aligned.
+extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descale, const float* k_descale, const float* v_descale,
+                                 int32_t out_dtype, void* stream) {
+  using namespace usp;
+  launch_kinds_reset();
+  if (!args || !args->lse) return USP_EINVAL;
+  if (out_dtype != USP_BF16 && out_dtype != USP_FP16) return USP_EINVAL;
+  usp_fwd_args a = *args;
+  a.dtype = out_dtype;                             // (args->dtype is not read: q, k, v are e4m3, out is out_dtype)
+  if (int rc = check_force(a.flags)) return rc;
+  if (int rc = check_problem(a)) return rc;
+  if (a.D != 128) return USP_EUNSUPPORTED;
+  if (!aligned(q_descale, 4) || !aligned(k_descale, 4) || !aligned(v_descale, 4)) return USP_EINVAL;
+  if (int rc = check_plain_dense_family(a, false, true)) return rc;     // softcap, a cutting window, packed, forced families
+  if (!tensor_aligned(a.q, 16, 16) || !tensor_aligned(a.k, 16, 16) || !tensor_aligned(a.v, 16, 16)) return USP_EUNSUPPORTED;
+  const Mask mask = decode_mask(a);
+  int fb = a.final_begin < 0 ? 0 : a.final_begin;
+  int fe = a.final_end > a.Sq ? a.Sq : a.final_end;
+  if (fe < fb) fe = fb;
+  const bool any_final = fe > fb, any_acc = (fb > 0 || fe < a.Sq);
+  if (any_final && !tensor_aligned(a.out, 8, 4)) return a.out.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
+  if ((any_acc || a.merge_in) && !tensor_aligned(a.acc, 16, 4)) return a.acc.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
+
+  FwdParams p;
+  p.q = (const char*)a.q.ptr; p.k = (const char*)a.k.ptr; p.v = (const char*)a.v.ptr;
+  p.out = (char*)a.out.ptr; p.acc = (float*)a.acc.ptr; p.lse = a.lse;
+  p.q_sb = a.q.stride_b; p.q_ss = a.q.stride_s; p.q_sh = a.q.stride_h;
+  p.k_sb = a.k.stride_b; p.k_ss = a.k.stride_s; p.k_sh = a.k.stride_h;
+  p.v_sb = a.v.stride_b; p.v_ss = a.v.stride_s; p.v_sh = a.v.stride_h;
+  p.o_sb = a.out.stride_b; p.o_ss = a.out.stride_s; p.o_sh = a.out.stride_h;
+  p.a_sb = a.acc.stride_b; p.a_ss = a.acc.stride_s; p.a_sh = a.acc.stride_h;
+  p.lse_sb = a.lse_stride_b; p.lse_sh = a.lse_stride_h;
+  p.B = a.B; p.Sq = a.Sq; p.Sk = a.Sk; p.Hq = a.Hq; p.Hkv = a.Hkv;
+  p.G = a.Hq / a.Hkv;
+  p.nq = 0; p.n_items = 0;                         // set in launch_fwd_fp8
+  p.causal_off = mask.causal_off;
+  p.scale = a.softmax_scale;
+  p.scale_log2 = a.softmax_scale * kLog2e;
+  p.merge_in = a.merge_in ? 1 : 0;
+  p.final_begin = fb; p.final_end = fe;
+  p.out_wide = tensor_aligned(a.out, 16, 8) ? 1 : 0;
+  p.seq_q = nullptr; p.seq_k = nullptr; p.sched = nullptr;
+  p.interleave = (a.flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
+  p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
+  const int rc = launch_fwd_fp8(p, q_descale, k_descale, v_descale, out_dtype, mask.causal, (hipStream_t)stream);
+  if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_FP8);
+  return rc;
 }

@@ -23,7 +23,7 @@ from .._C import softcap_value
 from ..comm import all_to_all as A
 from ..comm.link import device_cus, kernel_flops_per_s, link_bytes_per_s
 from ..kernels.attention import kernel_head_dim, pad_head_dim
-from ..kernels.features import head_dim_256_alone, head_dims_192_128_alone
+from ..kernels.features import fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..ring.ring_flash_attn import ring_flash_attn_backward, ring_flash_attn_forward
@@ -521,6 +521,7 @@ class AsyncLongContextAttention(torch.nn.Module):
                 return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
                 return_max_logits=False, block_select=None, return_block_mass=False) -> Tensor:
         """query (bs, seqlen/P, hc, hs); key/value (bs, seqlen/P, hc_kv, hs) -> (bs, seqlen/P, hc, hs)."""
+        fp8_forward_only("AsyncLongContextAttention", query, key, value)
         if return_block_mass:
             raise NotImplementedError("return_block_mass is not supported by AsyncLongContextAttention (its head-group pipeline "
                                       "keeps neither the exchanged k nor one lse per call): use LongContextAttention")

@@ -19,7 +19,7 @@ from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, SeqAllToAll5D, kv_
 from ..globals import PROCESS_GROUP
 from ..kernels import AttnType
 from ..kernels.attention import kernel_head_dim, pad_head_dim, window_of
-from ..kernels.features import block_mask_alone, block_select_alone, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone, return_block_mass_alone
+from ..kernels.features import block_mask_alone, block_select_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone, return_block_mass_alone
 from ..ring import doc_blocks
 from ..ring.front_end import _check_hot_path_args
 from .async_attn_layer import _AsyncUSPFunc, _MAX_GROUPS, _RING_FWD_BWD, pipeline_mode
@@ -175,6 +175,7 @@ class LongContextAttention(_USPLayer):
         Head dims (192, 128) -- query and key of 192, value of 128 -- go with none of the options, through three exchanges (the packed
         exchange and the head-group pipeline carry one width), with the basic and the zigzag ring: context is (bs, seq_len/N,
         head_cnt, 128)."""
+        fp8_forward_only("LongContextAttention", query, key, value)
         qk192 = head_dims_192_128_alone(query.shape[-1], value.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
                                         bidirectional, block_mask, block_select, return_max_logits, return_block_mass)
         if not qk192:
@@ -252,6 +253,7 @@ class LongContextAttentionQKVPacked(_USPLayer):
         """`return_max_logits` (keyword only): (out, max_logits) as LongContextAttention.forward returns it.  `block_select`
         (keyword only): as LongContextAttention.forward takes it.  `return_block_mass` (keyword only): (out, mass) as
         LongContextAttention.forward returns it."""
+        fp8_forward_only("LongContextAttentionQKVPacked", qkv)
         head_dim_256_alone(qkv.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
                            block_select, return_max_logits, return_block_mass)   # judged first (kernels/features.py)
         bmass = return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,

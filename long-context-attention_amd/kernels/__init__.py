@@ -16,6 +16,7 @@ from .attention import (
     hip_attn_forward,
     set_head_dim_256,
     hip_attn_func,
+    quantize_fp8,
     select_blocks,
     select_blocks_top_p,
     set_block_backend,
@@ -76,4 +77,5 @@ def select_flash_attn_impl(impl_type: AttnType, stage: str = "fwd-bwd", attn_pro
 
 __all__ = ["AttnType", "select_flash_attn_impl", "hip_attn_forward", "hip_attn_backward",
            "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect",
-           "select_blocks_top_p", "BlockSelectTopP", "block_attention_mass", "block_mask_recall", "set_head_dim_256"]
+           "select_blocks_top_p", "BlockSelectTopP", "block_attention_mass", "block_mask_recall", "set_head_dim_256",
+           "quantize_fp8"]

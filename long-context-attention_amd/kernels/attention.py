@@ -17,7 +17,7 @@ import torch
 
 from .. import _C
 from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
-                       block_select_alone, expand_block_mask, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone,
+                       block_select_alone, expand_block_mask, fp8_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone,
                        return_block_mass_alone)
 
 
@@ -483,9 +483,18 @@ def block_mask_recall(mass, mask):
     return (mass * mask.to(mass.dtype)).sum(dim=-1)
 
 
+def quantize_fp8(x):
+    """Per-head e4m3 operands for hip_attn_forward: a bf16 / fp16 (B, S, H, D) device tensor (any strides) -> (x8, descale), x8
+    torch.float8_e4m3fn of x's shape, descale fp32 (B, H) = max |x[b, :, h, :]| / 448 (1 for an all-zero head); x8 * descale is x to
+    e4m3 rounding (round to nearest even; the largest element of a head becomes +-448).  Two launches (csrc/usp_quantize_fp8.hip),
+    deterministic, nothing read on the host; no gradient."""
+    return _C.quantize_fp8(x.detach())
+
+
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                      softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
-                     bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False):
+                     bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False,
+                     q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -522,7 +531,19 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone).
     A v of head dim 128 beside q and k of head dim 192 runs on a kernel family of its own, with none of the options either
     (kernels/features.py: head_dims_192_128_alone): block_out is (B,Sq,Hq,128), the default scale 192 ** -0.5; any other unequal
-    pair raises NotImplementedError."""
+    pair raises NotImplementedError.
+    q, k, v all in torch.float8_e4m3fn at head dim 128 run on the e4m3 forward (csrc/usp_flash_fwd_fp8.hip; kernels/features.py:
+    fp8_alone), with none of the options; forward only.  `q_descale` (B, Hq), `k_descale` / `v_descale` (B, Hkv) (keyword only): fp32
+    device tensors, the operands mean q8 * q_descale[b, h] etc. (quantize_fp8 makes both), None = 1; `out_dtype` (keyword only):
+    torch.bfloat16 | torch.float16, the type of block_out.  The numbers: include/usp_hip.h, USP_ATTN_FP8."""
+    if fp8_alone(q, k, v, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask, block_select,
+                 return_max_logits, return_block_mass, q_descale, k_descale, v_descale):
+        B, Sq, Hq, D = q.shape
+        out = torch.empty((B, Sq, Hq, D), dtype=out_dtype, device=q.device)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        _C.flash_fwd(q, k, v, _default_scale(q, softmax_scale), bool(causal), lse, out=out, q_descale=q_descale, k_descale=k_descale,
+                     v_descale=v_descale, out_dtype=out_dtype)
+        return out, lse
     if head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                block_mask, block_select, return_max_logits, return_block_mass):
         B, Sq, Hq, _ = q.shape
@@ -592,6 +613,7 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
     `cu_doclens`, `bidirectional`, `block_mask` (keyword only): as hip_attn_forward took them.
     Head dims (192, 128): dout, out and block_dv_buffer have v's head dim (kernels/features.py: head_dims_192_128_alone)."""
+    fp8_forward_only("hip_attn_backward", dout, q, k, v)
     qk192 = head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
                                     bidirectional, block_mask)
     if not qk192:
@@ -706,6 +728,7 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone).
     Head dims (192, 128) -- q and k of 192, v of 128 -- neither (kernels/features.py: head_dims_192_128_alone): out is
     (B,Sq,Hq,128), the default scale 192 ** -0.5, dv has v's shape."""
+    fp8_forward_only("hip_attn_func", q, k, v)
     if head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                block_mask, block_select, return_max_logits, return_block_mass):
         res = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, bool(return_attn_probs))

@@ -11,6 +11,8 @@ kernels/attention.py: select_blocks_top_p).  Pure argument logic: nothing here l
 so the CPU orchestration tests import it as it is."""
 from typing import NamedTuple
 
+import torch
+
 from .._C import HEAD_DIMS_QK_V, _window, alibi_value, block_select_top_p_value, block_select_value, dropout_value, sinks_value, softcap_value
 
 # field of the record -> the flash-attn-style argument the messages name
@@ -174,6 +176,56 @@ def head_dims_192_128_alone(D: int, Dv: int, window_size=None, softcap=None, ali
         if value is not None:
             raise NotImplementedError(f"head dims {HEAD_DIMS_QK_V} of q / k and v together with {name} are not supported by the HIP "
                                       f"attention kernels")
+    return True
+
+
+FP8_DTYPE = torch.float8_e4m3fn                  # OCP E4M3: the one 8-bit type the kernels take
+_FP8_OTHERS = tuple(getattr(torch, n) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+FP8_HEAD_DIM = 128
+
+
+def is_fp8(*tensors) -> bool:
+    """Is any of the tensors (None allowed) of an 8-bit float type?"""
+    return any(t is not None and t.dtype in (FP8_DTYPE,) + _FP8_OTHERS for t in tensors)
+
+
+def fp8_forward_only(name: str, *tensors):
+    """What every entry but hip_attn_forward answers to 8-bit operands."""
+    if is_fp8(*tensors):
+        raise NotImplementedError(f"{name} does not take float8 tensors: the fp8 path is forward-only and is reached through "
+                                  f"hip_attn_forward (q, k, v in torch.float8_e4m3fn with q_descale / k_descale / v_descale)")
+
+
+def fp8_alone(q, k, v, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
+              bidirectional=None, block_mask=None, block_select=None, return_max_logits=False, return_block_mass=False,
+              q_descale=None, k_descale=None, v_descale=None) -> bool:
+    """Does a forward call run on the e4m3 family (csrc/usp_flash_fwd_fp8.hip)?  True when q, k and v are all torch.float8_e4m3fn.
+    That family is the plain dense forward at head dim 128 -- causal or full, GQA, the fused merge -- and nothing else: judged HERE
+    like head_dim_256_alone, before any tensor is read, it goes with none of the options and no other head dim (nothing is
+    padded).  Mixed dtypes, the other 8-bit types, and descales beside 16-bit tensors are refused by name."""
+    dts = {"q": q.dtype, "k": k.dtype, "v": v.dtype}
+    for name, dt in dts.items():
+        if dt in _FP8_OTHERS:
+            raise NotImplementedError(f"{name} is {dt}: the HIP attention kernels take torch.float8_e4m3fn (OCP E4M3) alone")
+    n8 = sum(dt == FP8_DTYPE for dt in dts.values())
+    if n8 == 0:
+        for name, value in (("q_descale", q_descale), ("k_descale", k_descale), ("v_descale", v_descale)):
+            if value is not None:
+                raise NotImplementedError(f"{name} goes with torch.float8_e4m3fn q, k and v alone, got {dts['q']}")
+        return False
+    if n8 != 3:
+        raise NotImplementedError(f"mixed dtypes {dts}: the fp8 forward takes q, k and v all in torch.float8_e4m3fn")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.shape[-1] != FP8_HEAD_DIM:
+            raise NotImplementedError(f"head_dim {t.shape[-1]} of {name} in float8_e4m3fn is not supported by the HIP attention "
+                                      f"kernels: the fp8 forward serves head dim {FP8_HEAD_DIM} alone")
+    given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
+             ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional),
+             ("block_mask", block_mask), ("block_select", block_select), ("return_max_logits", return_max_logits or None),
+             ("return_block_mass", return_block_mass or None))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"float8_e4m3fn q, k, v together with {name} are not supported by the HIP attention kernels")
     return True
 
 

@@ -10,7 +10,7 @@ from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_top_p_value, block_select
 from ..kernels import AttnType
 from ..kernels.attention import (block_attention_mass, draw_seed, get_block_backend, kernel_head_dim, kernel_operand,
                                  mass_operands, needs_grad, pad_head_dim, select_blocks, select_blocks_top_p, select_operands)
-from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone, head_dim_256_alone, head_dims_192_128_alone,
+from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone,
                                 max_logits_alone, return_block_mass_alone)
 from .utils import RingComm, group_info
 from .varlen_utils import unflatten_lse
@@ -410,6 +410,7 @@ def ring_front_end(stem, class_name, forward, backward, serves: RingServes, pack
         """Checks, operands, the ring forward: (the operands as launched, the scale used, out, lse, the dropout keywords of the
         backward, this rank's share of the max logits | None).  `max_logits`: judged alone already (max_logits_alone): beside it
         only a window can be on, which the ring's forward judges or _check_hot_path_args refuses."""
+        fp8_forward_only(f"{stem}_func", q, k, v)
         if softmax_scale is None:
             softmax_scale = q.shape[-1] ** (-0.5)
         if isinstance(cu_doc, BlockMask):           # (judged alone already: nothing else is on)

@@ -13,7 +13,7 @@ from torch import Tensor
 
 from ..comm.all_to_all import SeqAllToAll4D, SeqAllToAll4DKV, layer_max_logits, local_options
 from ..kernels import AttnType, select_flash_attn_impl
-from ..kernels.features import block_mask_alone, block_select_alone, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone, return_block_mass_alone
+from ..kernels.features import block_mask_alone, block_select_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone, return_block_mass_alone
 
 
 class UlyssesAttention(torch.nn.Module):
@@ -47,6 +47,7 @@ class UlyssesAttention(torch.nn.Module):
                 causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None, deterministic=False,
                 return_attn_probs=False, *args: Any, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
                 return_max_logits=False, block_select=None, return_block_mass=False) -> Tensor:
+        fp8_forward_only("UlyssesAttention", query, key, value)
         # `return_block_mass`: judged alone and first (kernels/features.py: return_block_mass_alone)
         # head dims (192, 128): three separate exchanges carry q / k and v at their own widths; with none of the options
         if not head_dims_192_128_alone(query.shape[-1], value.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
