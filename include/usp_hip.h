@@ -210,6 +210,10 @@ enum {
  * the maxima of every USP_QUANT_FP8_ROWS rows of a head.  NaN inputs are not looked for.  USP_EINVAL: a NULL pointer, a size <= 0, a
  * bad dtype; USP_EUNSUPPORTED: B or H above 65535, D of 2^18 or more. */
 #define USP_ATTN_FP8 1048576
+/* USP_ATTN_BLOCK_SELECT_ANTIDIAG: a FEATURE bit like USP_ATTN_BLOCK_SELECT_TOP_P (ABI still v7; the value is free as a flag and means
+ * nothing in an argument block): the library exports usp_block_antidiag_weights and usp_block_select_weights (both declared below) --
+ * block weights from the antidiagonals of the true score matrix (XAttention's rule) and the top-p cut over weights that are given. */
+#define USP_ATTN_BLOCK_SELECT_ANTIDIAG 2097152
 #define USP_QUANT_FP8_ROWS 64
 #define USP_QUANT_FP8_PARTIAL_FLOATS(B, S, H) ((int64_t)(B) * (H) * (((S) + USP_QUANT_FP8_ROWS - 1) / USP_QUANT_FP8_ROWS))
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
@@ -755,6 +759,64 @@ int usp_block_attn_mass(const void* q, const void* k, const float* lse, int32_t 
                         int32_t causal, int32_t diag, float* out, int64_t out_stride_b, int64_t out_stride_h, int64_t out_stride_row,
                         void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Antidiagonal block weights (XAttention's gate at the kernels' block size): a block is scored from every `stride`-th antidiagonal
+ * of its TRUE score matrix, so a few strong keys inside a block -- a vertical or a slash line -- cannot hide as they do from a
+ * pooled mean: every (row, key) pair of a block lies on some antidiagonal.  q is 16-bit (B, S, Hq, D), k 16-bit (B, S, Hkv, D)
+ * (one length: the weights feed a block mask), strides in elements, head dim contiguous.  With s = stride (4 | 8 | 16),
+ * n = 128 / s, G = Hq / Hkv, sub-row r and sub-column c the s x s patch of the rows r s .. r s + s - 1 and the keys c s .. c s + s - 1,
+ * in real numbers:
+ *     a[b][h][r][c] = (scale / s) * sum_{t = 0 .. s-1} q[b][r s + s-1-t][h] . k[b][c s + t][h / G]     (a position >= S adds 0),
+ *     sub-column c is VISIBLE to sub-row r iff c s < S and (causal == 0 or c <= r) -- causality is judged at PATCH granularity,
+ *     XAttention's rule: the patch on the diagonal counts whole, keys behind the row included;
+ *     p[r][.] = the softmax of a[r][.] over the visible c;
+ *     w[b][h][I][J] = (1 / rows'(I)) * sum over the sub-rows r of block I with r s < S and the visible c of block J of p[r][c],
+ * rows'(I) the number of such sub-rows (a ragged last block counts what it has: the rule of usp_block_means).  w has the shape
+ * and the meaning of usp_block_attn_mass's map: every row sums to 1, blocks above the diagonal are 0 under causal, and
+ * out[b * out_stride_b + h * out_stride_h + I * out_stride_row + J] (strides in elements) is written for EVERY I, J < nb =
+ * ceil(S / USP_BLOCK_MASK_SIZE).  fp32, no atomics, ordinary vector stores, nothing read on the host, no scratch.  With NaN or
+ * infinite inputs the result is unspecified; every access stays in range.
+ *
+ * For a fixed t the sum is an ordinary Q K^T between every s-th row of q and every s-th row of k, fetched by strided row
+ * addressing (nothing is copied or reshaped): one v_mfma_f32_32x32x16 chain of depth s D per 32 x 32 tile of sub-scores, t ascending
+ * and d ascending inside.  A wave owns 32 sub-rows of one query head; the four waves of an item share one KV head's stages of k in
+ * LDS.  TWO sweeps over the keys, 2 / s of the matrix work of Q K^T: the first ends in the log-sum-exp of every sub-row, the second
+ * forms p against it and the block sums.  With y = fma(chain, c, .) in log2 units, c = (scale / (float)s) * log2e (fp32 operations in
+ * this order), exp2 = v_exp_f32; the lane of (sub-row l = lane & 31 of the wave, half hf = lane >> 5) holds in register r of tile
+ * ct the sub-column 32 ct + 4 hf + (r & 3) + 8 (r >> 2).  ORDER of every sum, a function of the position alone:
+ *   lse  per lane over the tiles ascending from m = -3e38, l = 0: m' = max(m, chain_r * c over the visible r); l = l * exp2(m - m');
+ *        l += exp2(fma(chain_r, c, -m')) for the visible r = 0 .. 15 ascending; then the halves: M = max(m(0), m(1)),
+ *        L = l(0) exp2(m(0) - M) + l(1) exp2(m(1) - M), lse2 = M + log2(L);
+ *   w    1. the lane adds ascending from 0.f the p = exp2(fma(chain_r, c, -lse2)) of the 16 / (s / 4) registers r of block J;
+ *        2. the halves x(hf = 0) + x(hf = 1);  3. the n sub-rows of block I by the butterfly x += x[l ^ n/2], .. , x[l ^ 1];
+ *        4. one division by rows'(I).  Hidden sub-columns and sub-rows past S enter as +0.
+ * So the result repeats from call to call and does not depend on the grid, B or H.
+ *   - a NULL pointer, a non-positive size, a negative stride of a tensor, a dtype other than USP_BF16 / USP_FP16, a `stride` other
+ *     than 4 / 8 / 16 or a NaN scale is USP_EINVAL;
+ *   - D other than 32 / 64 / 128, Hq % Hkv != 0, q / k off a 16-byte boundary or with a stride that is no multiple of 8 elements,
+ *     out off a 4-byte boundary, S >= 2^29 and a k row stride of 2^21 elements or more or below D (rows that overlap, an expanded
+ *     view: the range check that zeroes the rows past S needs distinct rows) are USP_EUNSUPPORTED; nothing is launched or written.
+ *
+ * usp_block_select_weights: the top-p cut of usp_block_select_top_p over weights that are GIVEN.  The row W[J] = w[b * w_stride_b +
+ * h * w_stride_h + I * w_stride_row + J], J < nbk (fp32, strides in elements), is read as it stands; Ig = row_block0 + I, the visible
+ * and the FORCED blocks (J < keep_first, Ig - keep_local < J <= Ig), the mask layout and EVERY step from "total = SUM(W)" on --
+ * SUM's order, the order-preserving keys, the bit-by-bit cut, the fmaf tie count with ties to the lower J -- are those of
+ * usp_block_select_top_p above, run by the same code: the mask is a function of the bits of w alone.  A weight of a block that is
+ * not visible counts in the total and is never selected.  w may be usp_block_antidiag_weights' result or the usp_block_attn_mass
+ * of an earlier call (an exact selector).  One workgroup per (b, h, I); every byte of the mask is written.
+ *   - a NULL pointer, a non-positive size, a negative row_block0 / keep_first / keep_local / stride, causal != 0 with
+ *     keep_local < 1, a top_p that is NaN, <= 0 or > 1 are USP_EINVAL;
+ *   - nbk > USP_BLOCK_SELECT_MAX_BLOCKS and w off a 4-byte boundary are USP_EUNSUPPORTED; nothing is launched or written.
+ * -------------------------------------------------------------------------------------------- */
+int usp_block_antidiag_weights(const void* q, const void* k, int32_t dtype, int32_t B, int32_t S, int32_t Hq, int32_t Hkv, int32_t D,
+                               int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, int64_t k_stride_b, int64_t k_stride_s,
+                               int64_t k_stride_h, float scale, int32_t causal, int32_t stride, float* out, int64_t out_stride_b,
+                               int64_t out_stride_h, int64_t out_stride_row, void* stream);
+int usp_block_select_weights(const float* w, int64_t w_stride_b, int64_t w_stride_h, int64_t w_stride_row, int32_t B, int32_t Hq,
+                             int32_t nbq, int32_t nbk, int32_t row_block0, int32_t causal, float top_p, int32_t keep_first,
+                             int32_t keep_local, void* mask, int64_t mask_stride_b, int64_t mask_stride_h, int64_t mask_stride_row,
+                             void* stream);
+
 /* Bytes of scratch with which the backward launches get more, smaller work items (fp32 partials + one deterministic,
  * HBM-bound reduce launch each; results identical up to fp32 summation order):
  *   - GQA (Hq > Hkv): a dK/dV work item streams dkdv_heads query heads of its KV group (ABI v7; rounds 1-5: one or all).
@@ -846,7 +908,10 @@ enum {
   USP_KIND_FWD_QK192 = 16384,   /* flash_fwd_qk192_kernel      (head dims 192 / 128: 4 waves x 64 rows) */
   USP_KIND_DKDV_QK192 = 32768,  /* flash_bwd_dkdv_qk192_kernel (head dims 192 / 128: 4 waves x 32 keys) */
   USP_KIND_DQ_QK192 = 65536,    /* flash_bwd_dq_qk192_kernel   (head dims 192 / 128: 4 waves x 32 rows) */
-  USP_KIND_FWD_FP8 = 131072     /* flash_fwd_fp8_kernel        (e4m3 q, k, v at head dim 128: 4 waves x 64 rows) */
+  USP_KIND_FWD_FP8 = 131072,    /* flash_fwd_fp8_kernel        (e4m3 q, k, v at head dim 128: 4 waves x 64 rows) */
+  /* ... and the two launches of the antidiagonal gate, which note themselves as a flash call does (their entry points reset the mask) */
+  USP_KIND_BLOCK_ANTIDIAG = 262144,       /* block_antidiag_kernel       (usp_block_antidiag_weights: 4 waves x 32 sub-rows) */
+  USP_KIND_BLOCK_SELECT_WEIGHTS = 524288  /* block_select_weights_kernel (usp_block_select_weights) */
 };
 int usp_last_launch_kinds(void);
 
@@ -867,6 +932,7 @@ int usp_abi_version(void);
  * USP_ATTN_BLOCK_SELECT_TOP_P | USP_ATTN_BLOCK_MASS | USP_ATTN_HEAD_DIM_256 | USP_ATTN_HEAD_DIMS_192_128, the last twelve feature bits: the *_alibi / *_dropout / *_sink / *_doc / *_span /
  * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist, head dim 256 is served, usp_flash_*_vdim exist).
  * USP_ATTN_FP8 is the thirteenth: usp_flash_fwd_fp8 and usp_quantize_fp8 exist.
+ * USP_ATTN_BLOCK_SELECT_ANTIDIAG is the fourteenth: usp_block_antidiag_weights and usp_block_select_weights exist.
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

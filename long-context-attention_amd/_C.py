@@ -43,6 +43,8 @@ USP_ATTN_BLOCK_MASS = 131072   # feature bit of usp_attn_features(): usp_block_a
 USP_ATTN_HEAD_DIM_256 = 262144 # feature bit of usp_attn_features(): usp_flash_fwd / usp_flash_bwd serve head_dim 256 (not an args flag)
 USP_ATTN_HEAD_DIMS_192_128 = 524288  # feature bit of usp_attn_features(): usp_flash_fwd_vdim / usp_flash_bwd_vdim exist (not an args flag)
 USP_ATTN_FP8 = 1048576         # feature bit of usp_attn_features(): usp_flash_fwd_fp8 / usp_quantize_fp8 exist (not an args flag)
+USP_ATTN_BLOCK_SELECT_ANTIDIAG = 2097152  # feature bit of usp_attn_features(): usp_block_antidiag_weights / usp_block_select_weights exist (not an args flag)
+ANTIDIAG_STRIDES = (4, 8, 16)  # the `stride` values of usp_block_antidiag_weights
 QUANT_FP8_ROWS = 64            # rows of one partial maximum of usp_quantize_fp8 (include/usp_hip.h: USP_QUANT_FP8_ROWS)
 HEAD_DIMS_QK_V = (192, 128)    # the one pair of unequal head dims (q and k, v) they serve (the rule: kernels/features.py)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
@@ -58,6 +60,8 @@ KINDS_D256 = {2048: "fwd_d256", 4096: "dkdv_d256", 8192: "dq_d256"}
 KINDS_QK192 = {16384: "fwd_qk192", 32768: "dkdv_qk192", 65536: "dq_qk192"}
 # ... and the e4m3 forward's (csrc/usp_flash_fwd_fp8.hip)
 KINDS_FP8 = {131072: "fwd_fp8"}
+# ... and the two launches of the antidiagonal gate (csrc/usp_block_antidiag.hip, csrc/usp_block_select_weights.hip), which note themselves
+KINDS_ANTIDIAG = {262144: "block_antidiag", 524288: "block_select_weights"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -96,7 +100,8 @@ def last_dkdv_item_keys() -> int:
 def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
-    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items()) if m & bit)
+    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items(), *KINDS_ANTIDIAG.items())
+                 if m & bit)
 
 
 class UspTensor(ctypes.Structure):
@@ -149,7 +154,7 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
            "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim",
-           "usp_flash_fwd_fp8", "usp_quantize_fp8")
+           "usp_flash_fwd_fp8", "usp_quantize_fp8", "usp_block_antidiag_weights", "usp_block_select_weights")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -165,6 +170,7 @@ SELECT_TOP_P_EXPORTS = ("usp_block_select_top_p",)
 MASS_EXPORTS = ("usp_block_attn_mass",)
 VDIM_EXPORTS = ("usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
 FP8_EXPORTS = ("usp_flash_fwd_fp8", "usp_quantize_fp8")
+ANTIDIAG_EXPORTS = ("usp_block_antidiag_weights", "usp_block_select_weights")
 
 
 def lib_path() -> str:
@@ -703,6 +709,56 @@ def block_attn_mass(q, k, lse, scale: float, causal: bool, diag: int = 0, out=No
     return out
 
 
+def antidiag_stride_value(stride):
+    """The checked `stride` of an antidiagonal block selection: an int of ANTIDIAG_STRIDES, else ValueError.  (Pure argument check.)"""
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride not in ANTIDIAG_STRIDES:
+        raise ValueError(f"block_select: stride must be one of {ANTIDIAG_STRIDES}, got {stride!r}")
+    return stride
+
+
+def block_antidiag_weights(q, k, scale: float, causal: bool, stride: int = 8, out=None):
+    """usp_block_antidiag_weights: the antidiagonal block weights (include/usp_hip.h) of 16-bit q (B, S, Hq, D) and k (B, S, Hkv, D)
+    with unit head-dim stride (kernels/attention.py: kernel_operand).  `out`: an fp32 (B, Hq, nb, nb) device tensor with unit last
+    stride; None: a new one.  Every element of `out` is written."""
+    _require_cuda(q, k)
+    B, S, Hq, D = q.shape
+    Hkv = k.shape[2]
+    if k.shape[0] != B or k.shape[1] != S or k.shape[3] != D or k.dtype != q.dtype:
+        raise ValueError(f"block_antidiag_weights: q {tuple(q.shape)} {q.dtype} and k {tuple(k.shape)} {k.dtype} do not belong together")
+    nb = (S + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if out is None:
+        out = torch.empty((B, Hq, nb, nb), dtype=torch.float32, device=q.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Hq, nb, nb) or (nb > 1 and out.stride(-1) != 1) or out.device != q.device:
+        raise ValueError(f"block_antidiag_weights: out must be an fp32 ({B}, {Hq}, {nb}, {nb}) tensor with unit last stride on {q.device}")
+    tq, tk = _t4(q), _t4(k)
+    _check(_feature_entry("usp_block_antidiag_weights")(tq.ptr, tk.ptr, dtype_code(q.dtype), B, S, Hq, Hkv, D, tq.stride_b, tq.stride_s,
+                                                        tq.stride_h, tk.stride_b, tk.stride_s, tk.stride_h, float(scale),
+                                                        1 if causal else 0, int(stride), _ptr(out), out.stride(0), out.stride(1),
+                                                        out.stride(2), _stream()), "usp_block_antidiag_weights")
+    return out
+
+
+def block_select_weights(w, top_p, causal: bool, keep_first: int = 0, keep_local: int = 1, row_block0: int = 0, out=None):
+    """usp_block_select_weights: the torch.bool mask (B, Hq, nbq, nbk) of the fp32 weights w (B, Hq, nbq, nbk) -- any strides with a
+    unit last one -- by the top-p cut of usp_block_select_top_p.  Every byte of `out` (a torch.bool / uint8 (B, Hq, nbq, nbk) device
+    tensor with unit last stride; None: a new one) is written."""
+    _require_cuda(w)
+    if w.dim() != 4 or w.dtype != torch.float32 or (w.shape[3] > 1 and w.stride(3) != 1):
+        raise ValueError(f"block_select_weights: w must be an fp32 (B, Hq, nbq, nbk) tensor with unit last stride, got "
+                         f"{tuple(w.shape)} {w.dtype}")
+    B, Hq, nbq, nbk = w.shape
+    if out is None:
+        out = torch.empty((B, Hq, nbq, nbk), dtype=torch.bool, device=w.device)
+    elif out.dtype not in (torch.bool, torch.uint8) or tuple(out.shape) != (B, Hq, nbq, nbk) or (nbk > 1 and out.stride(-1) != 1) \
+            or out.device != w.device:
+        raise ValueError(f"block_select_weights: out must be a torch.bool ({B}, {Hq}, {nbq}, {nbk}) tensor with unit last stride on {w.device}")
+    _check(_feature_entry("usp_block_select_weights")(_ptr(w), w.stride(0), w.stride(1), w.stride(2), B, Hq, nbq, nbk, int(row_block0),
+                                                      1 if causal else 0, float(top_p), int(keep_first), int(keep_local), _ptr(out),
+                                                      out.stride(0), out.stride(1), out.stride(2), _stream()),
+           "usp_block_select_weights")
+    return out
+
+
 def _feature_entries():
     """export -> (feature bit, the option as the "does not serve" message names it, argtypes) of the entry points that load()
     does not insist on."""
@@ -737,7 +793,12 @@ def _feature_entries():
             "usp_flash_bwd_vdim": (USP_ATTN_HEAD_DIMS_192_128, "v of another head dim (USP_ATTN_HEAD_DIMS_192_128)", [bwd, i32, vp]),
             "usp_flash_fwd_fp8": (USP_ATTN_FP8, "float8_e4m3fn q, k, v (USP_ATTN_FP8)", [fwd, vp, vp, vp, i32, vp]),
             "usp_quantize_fp8": (USP_ATTN_FP8, "quantize_fp8 (USP_ATTN_FP8)",
-                                 [i32, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor), i64, vp, vp, i32, i32, i32, i32, vp])}
+                                 [i32, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor), i64, vp, vp, i32, i32, i32, i32, vp]),
+            "usp_block_antidiag_weights": (USP_ATTN_BLOCK_SELECT_ANTIDIAG, "block_select=BlockSelectAntidiag (USP_ATTN_BLOCK_SELECT_ANTIDIAG)",
+                                           [vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32, i32, i32, vp, i64,
+                                            i64, i64, vp]),
+            "usp_block_select_weights": (USP_ATTN_BLOCK_SELECT_ANTIDIAG, "block_select=BlockSelectAntidiag (USP_ATTN_BLOCK_SELECT_ANTIDIAG)",
+                                         [vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, i64, i64, i64, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()

@@ -15,7 +15,8 @@ from .comm.extract_local import (
     zigzag_extract_local,
     EXTRACT_FUNC_DICT,
 )
-from .kernels import (AttnType, BlockSelect, BlockSelectTopP, block_attention_mass, block_mask_recall, quantize_fp8,
-                      select_blocks, select_blocks_top_p, select_flash_attn_impl)
+from .kernels import (AttnType, BlockSelect, BlockSelectAntidiag, BlockSelectTopP, antidiag_block_weights, block_attention_mass,
+                      block_mask_recall, quantize_fp8, select_blocks, select_blocks_antidiag, select_blocks_from_weights,
+                      select_blocks_top_p, select_flash_attn_impl)
 
 __version__ = "0.6.0"

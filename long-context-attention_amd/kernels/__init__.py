@@ -8,6 +8,9 @@ the vendor-specific types that are out of scope (SageAttention, FlashInfer, Asce
 from enum import Enum
 
 from .attention import (
+    antidiag_block_weights,
+    select_blocks_antidiag,
+    select_blocks_from_weights,
     block_attention_mass,
     block_mask_recall,
     HipBlockBackend,
@@ -21,7 +24,7 @@ from .attention import (
     select_blocks_top_p,
     set_block_backend,
 )
-from .features import BlockSelect, BlockSelectTopP
+from .features import BlockSelect, BlockSelectAntidiag, BlockSelectTopP
 
 
 class AttnType(Enum):
@@ -78,4 +81,4 @@ def select_flash_attn_impl(impl_type: AttnType, stage: str = "fwd-bwd", attn_pro
 __all__ = ["AttnType", "select_flash_attn_impl", "hip_attn_forward", "hip_attn_backward",
            "hip_attn_func", "HipBlockBackend", "get_block_backend", "set_block_backend", "select_blocks", "BlockSelect",
            "select_blocks_top_p", "BlockSelectTopP", "block_attention_mass", "block_mask_recall", "set_head_dim_256",
-           "quantize_fp8"]
+           "quantize_fp8", "antidiag_block_weights", "select_blocks_from_weights", "select_blocks_antidiag", "BlockSelectAntidiag"]

@@ -16,7 +16,7 @@ import os
 import torch
 
 from .. import _C
-from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention,  # noqa: F401
+from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectAntidiag, BlockSelectTopP, Features, block_select_antidiag_value, block_mask_alone, block_mask_self_attention,  # noqa: F401
                        block_select_alone, expand_block_mask, fp8_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone,
                        return_block_mass_alone)
 
@@ -125,6 +125,14 @@ class HipBlockBackend:
     def block_select_top_p(self, qbar, kbar, top_p, scale, causal, keep_first=0, keep_local=1, share_group=False, row_block0=0):
         """torch.bool (B, Hq, nbq, nbk): block_select's mask by cumulative softmax mass (usp_block_select_top_p; no host read)."""
         return _C.block_select_top_p(qbar, kbar, top_p, scale, causal, keep_first, keep_local, share_group, row_block0)
+
+    def block_antidiag_weights(self, q, k, scale, causal, stride=8):
+        """fp32 (B, Hq, nb, nb): the antidiagonal block weights of q and k (usp_block_antidiag_weights; no host read)."""
+        return _C.block_antidiag_weights(q, k, scale, causal, stride)
+
+    def block_select_weights(self, w, top_p, causal, keep_first=0, keep_local=1, row_block0=0):
+        """torch.bool (B, Hq, nbq, nbk): the top-p cut over given fp32 weights (usp_block_select_weights; no host read)."""
+        return _C.block_select_weights(w, top_p, causal, keep_first, keep_local, row_block0)
 
     def block_mass(self, q, k, lse, scale, causal, diag=0, out=None):
         """fp32 (B, Hq, nbq, nbk): the share of the softmax mass the rows of every 128-row block of q give to every 128-key block
@@ -430,8 +438,61 @@ def select_blocks_top_p(q, k, top_p, *, softmax_scale=None, causal=False, keep_f
                                  share_group, 0)
 
 
+def antidiag_block_weights(q, k, *, softmax_scale=None, causal=False, stride=8):
+    """The antidiagonal block weights of a self-attention call (XAttention's gate at the kernels' block size): fp32 (B, Hq, nb, nb),
+    nb = ceil(S / 128), of q (B, S, Hq, D) and k (B, S, Hkv, D) (bf16 / fp16, any strides with a unit last one).  With s = `stride`
+    (4, 8 or 16), sub-row r / sub-column c the s x s patch of rows r s .. and keys c s .., a[r, c] = (softmax_scale / s) * sum_t
+    q[r s + s-1-t] . k[c s + t] -- one antidiagonal of the patch; every (row, key) pair lies on some antidiagonal, so a vertical
+    or slash line cannot hide as it does from a pooled mean --, p = the softmax of a over the sub-columns a sub-row sees (every c
+    with c s < S, under `causal` c <= r: causality at patch granularity), and w[b, h, I, J] the mean over the sub-rows of block I
+    of the p on the sub-columns of block J.  The shape and meaning of block_attention_mass: every row sums to 1, blocks above the
+    diagonal are 0 under causal, every element is written.  One kernel, 2 / s of the matrix work of Q K^T, no S x S scores in
+    memory (include/usp_hip.h: usp_block_antidiag_weights states the order of every sum; results repeat bit for bit); never read
+    on the host, no gradient.  Padded head dims are zero-padded at the scale of the unpadded dim.  ValueError: a stride outside
+    (4, 8, 16); NotImplementedError: q and k of different lengths, head dim 256."""
+    stride = _C.antidiag_stride_value(stride)
+    head_dim_256_alone(q.shape[-1], block_select=True)
+    block_mask_self_attention(q.shape[1], k.shape[1], "block_select")
+    q, k, scale = select_operands(q, k, softmax_scale)
+    return get_block_backend().block_antidiag_weights(q, k, scale, bool(causal), stride)
+
+
+def select_blocks_from_weights(w, top_p, *, causal=False, keep_first=0, keep_local=1):
+    """The block mask of GIVEN block weights: torch.bool of w's shape, for any fp32 (B, Hq, nbq, nbk) device tensor `w` with a unit
+    last stride, by select_blocks_top_p's rule read off `w` as it stands: the blocks J < keep_first and I - keep_local < J <= I
+    are always selected and their weight counts; the others (under `causal` those with J <= I) are ordered by w descending, ties
+    to the lower J, and the shortest prefix with weight(forced) + weight(prefix) >= top_p * sum(w[b, h, I]) is selected beside
+    them.  A function of the bits of `w` alone (include/usp_hip.h: usp_block_select_weights).  `w` may be antidiag_block_weights'
+    result, or the block_attention_mass(...) of an earlier call: the map itself as an EXACT selector.  No gradient, nothing read
+    on the host.  ValueError: as select_blocks_top_p; NotImplementedError: more than 8192 key blocks."""
+    top_p, keep_first, keep_local, _ = _C.block_select_top_p_value(top_p, keep_first, keep_local, False, causal)
+    if w.dim() != 4 or w.dtype != torch.float32:
+        raise ValueError(f"select_blocks_from_weights takes fp32 (B, Hq, nbq, nbk) weights, got {tuple(w.shape)} {w.dtype}")
+    if w.shape[3] > _C.BLOCK_SELECT_MAX_BLOCKS:
+        raise NotImplementedError(f"block_select serves up to {_C.BLOCK_SELECT_MAX_BLOCKS} blocks of {BLOCK_MASK_SIZE} keys, got {w.shape[3]}")
+    with torch.no_grad():
+        w = w.detach()
+        if w.shape[3] > 1 and w.stride(3) != 1:
+            w = w.contiguous()
+        return get_block_backend().block_select_weights(w, top_p, bool(causal), keep_first, keep_local, 0)
+
+
+def select_blocks_antidiag(q, k, top_p, *, softmax_scale=None, causal=False, stride=8, keep_first=0, keep_local=1):
+    """The block mask a `block_select=BlockSelectAntidiag(top_p, stride, keep_first, keep_local)` call runs under: exactly
+    select_blocks_from_weights(antidiag_block_weights(q, k, ...), top_p, ...).  ValueError and NotImplementedError: as both, more than 8192 blocks included; judged before anything is launched."""
+    top_p, stride, keep_first, keep_local = block_select_antidiag_value(top_p, stride, keep_first, keep_local, causal)
+    nb = (q.shape[1] + BLOCK_MASK_SIZE - 1) // BLOCK_MASK_SIZE
+    if nb > _C.BLOCK_SELECT_MAX_BLOCKS:
+        raise NotImplementedError(f"block_select serves up to {_C.BLOCK_SELECT_MAX_BLOCKS} blocks of {BLOCK_MASK_SIZE} keys, got {nb}")
+    w = antidiag_block_weights(q, k, softmax_scale=softmax_scale, causal=causal, stride=stride)
+    return select_blocks_from_weights(w, top_p, causal=causal, keep_first=keep_first, keep_local=keep_local)
+
+
 def _selected(block_select, q, k, softmax_scale, causal):
     """The mask of a call under `block_select` (judged alone already): by the record's type."""
+    if isinstance(block_select, BlockSelectAntidiag):
+        return select_blocks_antidiag(q, k, block_select.top_p, softmax_scale=softmax_scale, causal=causal, stride=block_select.stride,
+                                      keep_first=block_select.keep_first, keep_local=block_select.keep_local)
     if isinstance(block_select, BlockSelectTopP):
         return select_blocks_top_p(q, k, block_select.top_p, softmax_scale=softmax_scale, causal=causal,
                                    keep_first=block_select.keep_first, keep_local=block_select.keep_local,

@@ -13,7 +13,7 @@ from typing import NamedTuple
 
 import torch
 
-from .._C import HEAD_DIMS_QK_V, _window, alibi_value, block_select_top_p_value, block_select_value, dropout_value, sinks_value, softcap_value
+from .._C import HEAD_DIMS_QK_V, _window, alibi_value, antidiag_stride_value, block_select_top_p_value, block_select_value, dropout_value, sinks_value, softcap_value
 
 # field of the record -> the flash-attn-style argument the messages name
 ARGUMENT = dict(window="window_size", softcap="softcap", alibi="alibi_slopes", dropout="dropout_p", sinks="sinks", doc="cu_doclens")
@@ -76,24 +76,46 @@ class BlockSelectTopP(NamedTuple):
     share_group: bool = False
 
 
+class BlockSelectAntidiag(NamedTuple):
+    """`block_select=` by cumulative mass of ANTIDIAGONAL weights (XAttention's rule): the block weights come from every `stride`-th
+    antidiagonal of the true score matrix (kernels/attention.py: antidiag_block_weights) where BlockSelectTopP pools means, so a
+    few strong keys inside a block cannot hide; the cut is BlockSelectTopP's -- the fewest key blocks whose weight reaches
+    `top_p`, the first `keep_first` and the last `keep_local` ones always among them (select_blocks_antidiag).  Host values;
+    `stride` is 4, 8 or 16.  Ring degree 1 only."""
+    top_p: float
+    stride: int = 8
+    keep_first: int = 0
+    keep_local: int = 1
+
+
+def block_select_antidiag_value(top_p, stride=8, keep_first=0, keep_local=1, causal=False):
+    """The checked host values of a BlockSelectAntidiag: (top_p, stride, keep_first, keep_local); ValueError as
+    _C.block_select_top_p_value, and for a stride that is no int of (4, 8, 16)."""
+    top_p, keep_first, keep_local, _ = block_select_top_p_value(top_p, keep_first, keep_local, False, causal)
+    return top_p, antidiag_stride_value(stride), keep_first, keep_local
+
+
 def block_select_alone(block_select, block_mask=None, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
                        cu_doclens=None, bidirectional=None) -> bool:
     """Is `block_select` on?  Judged HERE like block_mask (block_mask_alone), before any tensor is read: it goes with nothing
     block_mask goes without, and not with block_mask itself.  None is exactly the call without the keyword; anything but a
-    BlockSelect or a BlockSelectTopP raises ValueError, and so does a malformed one (_C.block_select_value,
+    BlockSelect, a BlockSelectTopP or a BlockSelectAntidiag raises ValueError, and so does a malformed one (_C.block_select_value,
     _C.block_select_top_p_value; keep_local under causal is judged where causal is known: select_blocks, select_blocks_top_p)."""
     if block_select is None:
         return False
-    if not isinstance(block_select, (BlockSelect, BlockSelectTopP)):
+    if not isinstance(block_select, (BlockSelect, BlockSelectTopP, BlockSelectAntidiag)):
         raise ValueError(f"block_select must be a BlockSelect(top_k, keep_first=0, keep_local=1) or a BlockSelectTopP(top_p, "
-                         f"keep_first=0, keep_local=1, share_group=False), got {type(block_select).__name__}")
+                         f"keep_first=0, keep_local=1, share_group=False) or a BlockSelectAntidiag(top_p, stride=8, keep_first=0, "
+                         f"keep_local=1), got {type(block_select).__name__}")
     given = (("block_mask", block_mask), ("window_size", _window(window_size)), ("softcap", softcap_value(softcap)),
              ("alibi_slopes", alibi_slopes), ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens),
              ("bidirectional", bidirectional))
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"block_select together with {name} is not supported by the HIP attention kernels")
-    if isinstance(block_select, BlockSelectTopP):
+    if isinstance(block_select, BlockSelectAntidiag):
+        block_select_antidiag_value(*block_select)
+    elif isinstance(block_select, BlockSelectTopP):
         block_select_top_p_value(*block_select)
     else:
         block_select_value(*block_select)

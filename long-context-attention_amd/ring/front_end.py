@@ -9,8 +9,8 @@ import torch.distributed as dist
 from .._C import BLOCK_SELECT_MAX_BLOCKS, block_select_top_p_value, block_select_value, dropout_value, softcap_value
 from ..kernels import AttnType
 from ..kernels.attention import (block_attention_mass, draw_seed, get_block_backend, kernel_head_dim, kernel_operand,
-                                 mass_operands, needs_grad, pad_head_dim, select_blocks, select_blocks_top_p, select_operands)
-from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectTopP, Features, block_mask_alone, block_mask_self_attention, block_select_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone,
+                                 mass_operands, needs_grad, pad_head_dim, select_blocks, select_blocks_antidiag, select_blocks_top_p, select_operands)
+from ..kernels.features import (BLOCK_MASK_SIZE, BlockSelectAntidiag, BlockSelectTopP, Features, block_select_antidiag_value, block_mask_alone, block_mask_self_attention, block_select_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone,
                                 max_logits_alone, return_block_mass_alone)
 from .utils import RingComm, group_info
 from .varlen_utils import unflatten_lse
@@ -252,6 +252,10 @@ def _place_block_mask(serves, q, k, bm, group):
 def _place_block_select(serves, q, k, sel, causal, group):
     """The checks of a ring call under a block selection: those of a block mask, in its name, and the selection's own."""
     P = group_info(dist, group)[0]
+    if P > 1 and isinstance(sel.select, BlockSelectAntidiag):
+        raise NotImplementedError(f"block_select=BlockSelectAntidiag at ring degree {P} is not supported: the antidiagonal weights need the "
+                                  f"whole K at every rank and a row statistic across the ring's steps; use BlockSelectTopP, which the "
+                                  f"basic ring serves at any degree, or a Ulysses-only grid")
     if P > 1 and serves.block_mask != ANY_DEGREE:
         raise NotImplementedError(f"block_select across ring steps (ring degree > 1) is not supported by the zigzag and stripe "
                                   f"rings: {_BASIC}")
@@ -259,7 +263,9 @@ def _place_block_select(serves, q, k, sel, causal, group):
     if P > 1 and q.shape[1] % BLOCK_MASK_SIZE:
         raise NotImplementedError(f"block_select at ring degree {P} needs a local sequence length that is a multiple of "
                                   f"{BLOCK_MASK_SIZE} (whole mask blocks per rank), got {q.shape[1]}: pad the sequence")
-    if isinstance(sel.select, BlockSelectTopP):
+    if isinstance(sel.select, BlockSelectAntidiag):
+        block_select_antidiag_value(*sel.select, causal)
+    elif isinstance(sel.select, BlockSelectTopP):
         block_select_top_p_value(*sel.select, causal)
     else:
         block_select_value(*sel.select, causal)
@@ -273,6 +279,10 @@ def select_block_rows(q, k, select, softmax_scale, causal, group):
     (B, Hq, n, nb).  Nothing is read on the host.  A BlockSelectTopP runs the same scheme through select_blocks_top_p /
     block_select_top_p (a rank of the ring holds every head, so share_group needs nothing more)."""
     P, r = group_info(dist, group)
+    if isinstance(select, BlockSelectAntidiag):                  # (ring degree 1: _place_block_select has refused the others)
+        p, stride, keep_first, keep_local = block_select_antidiag_value(*select, causal)
+        return BlockMask(select_blocks_antidiag(q, k, p, softmax_scale=softmax_scale, causal=causal, stride=stride,
+                                                keep_first=keep_first, keep_local=keep_local))
     top_p = isinstance(select, BlockSelectTopP)
     if top_p:
         p, keep_first, keep_local, share = block_select_top_p_value(*select, causal)
