@@ -214,6 +214,36 @@ enum {
  * nothing in an argument block): the library exports usp_block_antidiag_weights and usp_block_select_weights (both declared below) --
  * block weights from the antidiagonals of the true score matrix (XAttention's rule) and the top-p cut over weights that are given. */
 #define USP_ATTN_BLOCK_SELECT_ANTIDIAG 2097152
+/* USP_ATTN_MXFP8: a FEATURE bit (ABI still v7; the value is free as a flag and means nothing in an argument block): usp_flash_fwd_mxfp8
+ * and usp_quantize_mxfp8 (both declared below) exist.  The forward is USP_ATTN_FP8's -- e4m3 q, k, v, head dim 128, causal and full,
+ * forward only, the same argument block, `out_dtype`, numbers, served and declined cases -- with OCP Microscaling v1.0 (MXFP8) block
+ * scales in place of the per-head descales: one E8M0 byte per block of 32 elements, value 2^(byte - 127).  A kernel family of its own
+ * (csrc/usp_flash_fwd_mxfp8.hip: both products on v_mfma_scale_f32_32x32x64_f8f6f4, which applies the scales in the matrix pipe; noted
+ * as USP_KIND_FWD_MXFP8).  The scale tensors are DEVICE bytes, usp_tensor strides in BYTES, the last dim of unit stride:
+ *   q_scale (B, Sq, Hq, 4), k_scale (B, Sk, Hkv, 4)      blocks along the head dim:  q[b,i,h,d] = q8[b,i,h,d] * 2^(q_scale[b,i,h,d/32] - 127)
+ *   v_scale (B, ceil(Sk / 32), Hkv, 128)                 blocks along the sequence (the reduction axis of P V, the "columnwise" MX form):
+ *                                                        v[b,j,h,d] = v8[b,j,h,d] * 2^(v_scale[b,j/32,h,d] - 127); key blocks are counted in
+ *                                                        the launch's own key coordinates whatever USP_ATTN_SHIFT says, a ragged last block
+ *                                                        has the keys it has
+ *   the numbers   s_ij = softmax_scale * sum_d q_id k_jd, one fp32 MFMA chain over d with the scales applied to exact products; p, the
+ *             row sum, lse and the 2^8 shift before P's rounding to e4m3 as under USP_ATTN_FP8 (P's own scale byte is 127);
+ *             out_i = sum_j e4m3(2^8 p_ij) v_j / sum_j 2^8 p_ij.  No fp32 descale remains: the exponent scale is softmax_scale * log2(e).
+ *             A scale byte of 255 (NaN) is not looked for.
+ *   declined  as usp_flash_fwd_fp8, and a scale tensor whose pointer or strides are no multiples of 4: USP_EUNSUPPORTED, nothing
+ *             launched.  A NULL scale (all three are required) or a bad out_dtype: USP_EINVAL.
+ * usp_quantize_mxfp8 makes such operands from a 16-bit (B, S, H, D) tensor `x` (dtype = USP_BF16 | USP_FP16; usp_tensor strides in
+ * elements plus the last dim's stride, any values; x8's likewise; `scale`'s in bytes with a unit last stride).  `axis`:
+ *   USP_MX_AXIS_D  blocks of 32 dims of one token: scale is (B, S, H, D / 32)                          -- q and k
+ *   USP_MX_AXIS_S  blocks of 32 consecutive rows of one (b, h, d), over the rows that exist: scale is (B, ceil(S / 32), H, D), pointer
+ *                  and strides multiples of 4                                                          -- v
+ * The rule is OCP MX v1.0's: with amax the block's largest magnitude, e = floor(log2(amax)) - 8 clamped to [-127, 127], the byte is
+ * e + 127 (127 for an all-zero block), x8 = e4m3(x * 2^-e) rounded to nearest even and SATURATED at +-448 -- the scaled amax lies in
+ * [256, 512), so values above 448 clamp: that is the format's conversion rule.  floor(log2) is the fp32 exponent field and the scaling an
+ * exact power of two: the result is defined bit for bit.  One launch on `stream`, no atomics, no scratch.  NaN inputs are not looked
+ * for.  USP_EINVAL: a NULL pointer, a size <= 0, a bad dtype, an axis other than the two; USP_EUNSUPPORTED: D no multiple of 32. */
+#define USP_ATTN_MXFP8 4194304
+#define USP_MX_AXIS_D 0
+#define USP_MX_AXIS_S 1
 #define USP_QUANT_FP8_ROWS 64
 #define USP_QUANT_FP8_PARTIAL_FLOATS(B, S, H) ((int64_t)(B) * (H) * (((S) + USP_QUANT_FP8_ROWS - 1) / USP_QUANT_FP8_ROWS))
 /* Item width of the 64-row family's dK/dV launch (usp_flash_bwd only; selectors like USP_FORCE_*, per call).  That launch
@@ -316,6 +346,11 @@ int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descale, const fl
                       int32_t out_dtype, void* stream);
 int usp_quantize_fp8(int32_t dtype, const usp_tensor* x, int64_t x_stride_d, const usp_tensor* x8, int64_t x8_stride_d,
                      float* descale, float* partial, int32_t B, int32_t S, int32_t H, int32_t D, void* stream);
+/* USP_ATTN_MXFP8 (see the bit) */
+int usp_flash_fwd_mxfp8(const usp_fwd_args* args, const usp_tensor* q_scale, const usp_tensor* k_scale, const usp_tensor* v_scale,
+                        int32_t out_dtype, void* stream);
+int usp_quantize_mxfp8(int32_t dtype, int32_t axis, const usp_tensor* x, int64_t x_stride_d, const usp_tensor* x8, int64_t x8_stride_d,
+                       const usp_tensor* scale, int32_t B, int32_t S, int32_t H, int32_t D, void* stream);
 
 /* K split (dense launches): a launch with few (batch, head, 256-row tile) work items cannot fill 256 CUs, and a causal
  * one lasts as long as its heaviest item (measured on MI355X, B1 S16384 D128 causal: 2 heads 548 TFLOP/s, 4 heads 891,
@@ -911,7 +946,8 @@ enum {
   USP_KIND_FWD_FP8 = 131072,    /* flash_fwd_fp8_kernel        (e4m3 q, k, v at head dim 128: 4 waves x 64 rows) */
   /* ... and the two launches of the antidiagonal gate, which note themselves as a flash call does (their entry points reset the mask) */
   USP_KIND_BLOCK_ANTIDIAG = 262144,       /* block_antidiag_kernel       (usp_block_antidiag_weights: 4 waves x 32 sub-rows) */
-  USP_KIND_BLOCK_SELECT_WEIGHTS = 524288  /* block_select_weights_kernel (usp_block_select_weights) */
+  USP_KIND_BLOCK_SELECT_WEIGHTS = 524288, /* block_select_weights_kernel (usp_block_select_weights) */
+  USP_KIND_FWD_MXFP8 = 1048576  /* flash_fwd_mxfp8_kernel      (MXFP8 q, k, v at head dim 128: 4 waves x 64 rows) */
 };
 int usp_last_launch_kinds(void);
 
@@ -933,6 +969,7 @@ int usp_abi_version(void);
  * *_bsp / *_maxlogit / usp_block_means and usp_block_select / usp_block_select_top_p / usp_block_attn_mass entry points exist, head dim 256 is served, usp_flash_*_vdim exist).
  * USP_ATTN_FP8 is the thirteenth: usp_flash_fwd_fp8 and usp_quantize_fp8 exist.
  * USP_ATTN_BLOCK_SELECT_ANTIDIAG is the fourteenth: usp_block_antidiag_weights and usp_block_select_weights exist.
+ * USP_ATTN_MXFP8 is the fifteenth: usp_flash_fwd_mxfp8 and usp_quantize_mxfp8 exist.
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

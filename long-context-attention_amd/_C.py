@@ -45,6 +45,8 @@ USP_ATTN_HEAD_DIMS_192_128 = 524288  # feature bit of usp_attn_features(): usp_f
 USP_ATTN_FP8 = 1048576         # feature bit of usp_attn_features(): usp_flash_fwd_fp8 / usp_quantize_fp8 exist (not an args flag)
 USP_ATTN_BLOCK_SELECT_ANTIDIAG = 2097152  # feature bit of usp_attn_features(): usp_block_antidiag_weights / usp_block_select_weights exist (not an args flag)
 ANTIDIAG_STRIDES = (4, 8, 16)  # the `stride` values of usp_block_antidiag_weights
+USP_ATTN_MXFP8 = 4194304       # feature bit of usp_attn_features(): usp_flash_fwd_mxfp8 / usp_quantize_mxfp8 exist (not an args flag)
+MX_AXIS = {"d": 0, "s": 1}     # usp_quantize_mxfp8's block axis (include/usp_hip.h: USP_MX_AXIS_D / USP_MX_AXIS_S)
 QUANT_FP8_ROWS = 64            # rows of one partial maximum of usp_quantize_fp8 (include/usp_hip.h: USP_QUANT_FP8_ROWS)
 HEAD_DIMS_QK_V = (192, 128)    # the one pair of unequal head dims (q and k, v) they serve (the rule: kernels/features.py)
 BLOCK_SELECT_MAX_BLOCKS = 8192 # key blocks of one usp_block_select call (include/usp_hip.h: USP_BLOCK_SELECT_MAX_BLOCKS)
@@ -62,6 +64,8 @@ KINDS_QK192 = {16384: "fwd_qk192", 32768: "dkdv_qk192", 65536: "dq_qk192"}
 KINDS_FP8 = {131072: "fwd_fp8"}
 # ... and the two launches of the antidiagonal gate (csrc/usp_block_antidiag.hip, csrc/usp_block_select_weights.hip), which note themselves
 KINDS_ANTIDIAG = {262144: "block_antidiag", 524288: "block_select_weights"}
+# ... and the MXFP8 forward's (csrc/usp_flash_fwd_mxfp8.hip)
+KINDS_MXFP8 = {1048576: "fwd_mxfp8"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -100,7 +104,7 @@ def last_dkdv_item_keys() -> int:
 def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
-    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items(), *KINDS_ANTIDIAG.items())
+    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items(), *KINDS_ANTIDIAG.items(), *KINDS_MXFP8.items())
                  if m & bit)
 
 
@@ -154,7 +158,8 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_block_list_bytes", "usp_block_lists_build", "usp_flash_fwd_bsp", "usp_flash_bwd_bsp",
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
            "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim",
-           "usp_flash_fwd_fp8", "usp_quantize_fp8", "usp_block_antidiag_weights", "usp_block_select_weights")
+           "usp_flash_fwd_fp8", "usp_quantize_fp8", "usp_block_antidiag_weights", "usp_block_select_weights",
+           "usp_flash_fwd_mxfp8", "usp_quantize_mxfp8")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -171,6 +176,7 @@ MASS_EXPORTS = ("usp_block_attn_mass",)
 VDIM_EXPORTS = ("usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
 FP8_EXPORTS = ("usp_flash_fwd_fp8", "usp_quantize_fp8")
 ANTIDIAG_EXPORTS = ("usp_block_antidiag_weights", "usp_block_select_weights")
+MXFP8_EXPORTS = ("usp_flash_fwd_mxfp8", "usp_quantize_mxfp8")
 
 
 def lib_path() -> str:
@@ -189,7 +195,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS + MXFP8_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -798,7 +804,12 @@ def _feature_entries():
                                            [vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32, i32, i32, vp, i64,
                                             i64, i64, vp]),
             "usp_block_select_weights": (USP_ATTN_BLOCK_SELECT_ANTIDIAG, "block_select=BlockSelectAntidiag (USP_ATTN_BLOCK_SELECT_ANTIDIAG)",
-                                         [vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, i64, i64, i64, vp])}
+                                         [vp, i64, i64, i64, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, i64, i64, i64, vp]),
+            "usp_flash_fwd_mxfp8": (USP_ATTN_MXFP8, "float8_e8m0fnu block scales (USP_ATTN_MXFP8)",
+                                    [fwd, ctypes.POINTER(UspTensor), ctypes.POINTER(UspTensor), ctypes.POINTER(UspTensor), i32, vp]),
+            "usp_quantize_mxfp8": (USP_ATTN_MXFP8, "quantize_fp8(mx=) (USP_ATTN_MXFP8)",
+                                   [i32, i32, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor),
+                                    i32, i32, i32, i32, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -988,7 +999,9 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     (usp_flash_fwd_maxlogit; served uncut, k_splits ignored; goes with window and shift alone; not with family="row64").
     q, k, v in torch.float8_e4m3fn at head dim 128 go to usp_flash_fwd_fp8 (kernels/features.py: fp8_alone): the plain dense launch
     with `shift` alone of the options; `q_descale` (B, Hq), `k_descale` / `v_descale` (B, Hkv): fp32 device tensors, None = 1;
-    `out_dtype`: the type of `out` (None: out's own, bfloat16 without one); k_splits is ignored."""
+    `out_dtype`: the type of `out` (None: out's own, bfloat16 without one); k_splits is ignored.  Descales in torch.float8_e8m0fnu are
+    MX block scales -- (B, Sq, Hq, 4), (B, Sk, Hkv, 4), (B, ceil(Sk / 32), Hkv, 128), unit last stride, all three -- and the call
+    goes to usp_flash_fwd_mxfp8 (kernels/features.py: mx_scales)."""
     from .kernels.features import fp8_alone
     if fp8_alone(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale):   # judged before any tensor is read
         _fp8_alone(window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), sinks=sinks,
@@ -1070,9 +1083,12 @@ def _flash_fwd_fp8(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, fina
         out_dtype = out.dtype if out is not None else torch.bfloat16
     if out is not None and out.dtype != out_dtype:
         raise TypeError(f"out is {out.dtype}, out_dtype {out_dtype}")
-    dq = _descale(q_descale, "q_descale", B, Hq, q.device)
-    dk = _descale(k_descale, "k_descale", B, k.shape[2], q.device)
-    dv = _descale(v_descale, "v_descale", B, k.shape[2], q.device)
+    from .kernels.features import mx_scales
+    mx = mx_scales(q_descale, k_descale, v_descale)
+    if not mx:
+        dq = _descale(q_descale, "q_descale", B, Hq, q.device)
+        dk = _descale(k_descale, "k_descale", B, k.shape[2], q.device)
+        dv = _descale(v_descale, "v_descale", B, k.shape[2], q.device)
     a = UspFwdArgs()
     a.dtype = dtype_code(out_dtype)                 # (not read for q, k, v)
     a.B, a.Sq, a.Sk, a.Hq, a.Hkv, a.D = B, Sq, k.shape[1], Hq, k.shape[2], D
@@ -1085,14 +1101,23 @@ def _flash_fwd_fp8(q, k, v, softmax_scale, causal, lse, out, acc, merge_in, fina
     a.final_end = Sq if final_end is None else final_end
     a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
     _set_shift(a, _shift(shift))
+    if mx:                                          # (shapes, devices and last strides: fp8_alone; one-byte elements: strides in bytes)
+        sq, sk, sv = (ctypes.byref(_t4(t)) for t in (q_descale, k_descale, v_descale))
+        _check(_feature_entry("usp_flash_fwd_mxfp8")(ctypes.byref(a), sq, sk, sv, a.dtype, _stream()), "usp_flash_fwd_mxfp8")
+        return
     _check(_feature_entry("usp_flash_fwd_fp8")(ctypes.byref(a), _ptr(dq), _ptr(dk), _ptr(dv), a.dtype, _stream()),
            "usp_flash_fwd_fp8")
 
 
-def quantize_fp8(x, out=None):
+def quantize_fp8(x, out=None, mx=None):
     """usp_quantize_fp8: a 16-bit (B, S, H, D) device tensor (any strides) -> (x8, descale): x8 torch.float8_e4m3fn of x's shape
     (`out`, or a new contiguous one), descale fp32 (B, H) = max |x[b, :, h, :]| / 448 (1 for an all-zero head), x8 = x / descale
-    rounded to nearest even.  Two launches, deterministic, nothing read on the host."""
+    rounded to nearest even.  Two launches, deterministic, nothing read on the host.
+    `mx` = "d" | "s": usp_quantize_mxfp8 -- OCP MX blocks of 32 dims of a token ("d": scale (B, S, H, D / 32), for q and k) or of 32
+    rows of a (b, h, d) ("s": scale (B, ceil(S / 32), H, D), for v); the scale is torch.float8_e8m0fnu, x8 = e4m3(x / scale)
+    saturating at +-448.  One launch."""
+    if mx is not None and mx not in MX_AXIS:
+        raise ValueError(f"quantize_fp8: mx is {mx!r}, not None, 'd' or 's'")
     _require_cuda(x, out)
     if x.dim() != 4:
         raise ValueError(f"quantize_fp8 takes a (B, S, H, D) tensor, got {tuple(x.shape)}")
@@ -1102,6 +1127,12 @@ def quantize_fp8(x, out=None):
         out = torch.empty((B, S, H, D), dtype=torch.float8_e4m3fn, device=x.device)
     if out.dtype != torch.float8_e4m3fn or out.shape != x.shape or out.device != x.device:
         raise ValueError("quantize_fp8: out must be a torch.float8_e4m3fn tensor of x's shape on x's device")
+    if mx is not None:
+        scale = torch.empty((B, S, H, D // 32) if mx == "d" else (B, (S + 31) // 32, H, D), dtype=torch.uint8, device=x.device)
+        tx, ty, ts = (UspTensor(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)) for t in (x, out, scale))
+        _check(_feature_entry("usp_quantize_mxfp8")(code, MX_AXIS[mx], ctypes.byref(tx), x.stride(3), ctypes.byref(ty), out.stride(3),
+                                                    ctypes.byref(ts), B, S, H, D, _stream()), "usp_quantize_mxfp8")
+        return out, scale.view(torch.float8_e8m0fnu)
     descale = torch.empty((B, H), dtype=torch.float32, device=x.device)
     partial = torch.empty(B * H * ((S + QUANT_FP8_ROWS - 1) // QUANT_FP8_ROWS), dtype=torch.float32, device=x.device)
     tx = UspTensor(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2))

@@ -21,6 +21,7 @@
 #include "usp_d256.hpp"
 #include "usp_qk192.hpp"
 #include "usp_fp8.hpp"
+#include "usp_mxfp8.hpp"
 
 namespace usp {
 
@@ -403,12 +404,12 @@ extern "C" int usp_flash_fwd_bsp(const usp_fwd_args* a, const void* mask, int64_
   return flash_fwd_call(a, x, stream);
 }
 
-// usp_flash_fwd_fp8: e4m3 q, k, v at head dim 128 (usp_flash_fwd_fp8.hip) -- the plain dense launch and nothing else, checked as
-// flash_fwd_call checks the head-dim-256 family, with byte-sized inputs: rows of q, k, v are 16-byte = 16-element aligned.
-extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descale, const float* k_descale, const float* v_descale,
-                                 int32_t out_dtype, void* stream) {
+// The e4m3 entry points -- usp_flash_fwd_fp8 (usp_flash_fwd_fp8.hip: per-head descales) and usp_flash_fwd_mxfp8
+// (usp_flash_fwd_mxfp8.hip: MX block scales) -- are the plain dense launch at head dim 128 and nothing else, checked as flash_fwd_call
+// checks the head-dim-256 family, with byte-sized inputs: rows of q, k, v are 16-byte = 16-element aligned.  `scales_valid`: the
+// entry point's own USP_EINVAL case.  USP_OK: *p is complete but for nq / n_items, *causal names the instantiation.
+static int e4m3_params(const usp_fwd_args* args, int32_t out_dtype, bool scales_valid, usp::FwdParams* p_out, bool* causal) {
   using namespace usp;
-  launch_kinds_reset();
   if (!args || !args->lse) return USP_EINVAL;
   if (out_dtype != USP_BF16 && out_dtype != USP_FP16) return USP_EINVAL;
   usp_fwd_args a = *args;
@@ -416,7 +417,7 @@ extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descal
   if (int rc = check_force(a.flags)) return rc;
   if (int rc = check_problem(a)) return rc;
   if (a.D != 128) return USP_EUNSUPPORTED;
-  if (!aligned(q_descale, 4) || !aligned(k_descale, 4) || !aligned(v_descale, 4)) return USP_EINVAL;
+  if (!scales_valid) return USP_EINVAL;
   if (int rc = check_plain_dense_family(a, false, true)) return rc;     // softcap, a cutting window, packed, forced families
   if (!tensor_aligned(a.q, 16, 16) || !tensor_aligned(a.k, 16, 16) || !tensor_aligned(a.v, 16, 16)) return USP_EUNSUPPORTED;
   const Mask mask = decode_mask(a);
@@ -427,7 +428,7 @@ extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descal
   if (any_final && !tensor_aligned(a.out, 8, 4)) return a.out.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
   if ((any_acc || a.merge_in) && !tensor_aligned(a.acc, 16, 4)) return a.acc.ptr ? USP_EUNSUPPORTED : USP_EINVAL;
 
-  FwdParams p;
+  FwdParams& p = *p_out;
   p.q = (const char*)a.q.ptr; p.k = (const char*)a.k.ptr; p.v = (const char*)a.v.ptr;
   p.out = (char*)a.out.ptr; p.acc = (float*)a.acc.ptr; p.lse = a.lse;
   p.q_sb = a.q.stride_b; p.q_ss = a.q.stride_s; p.q_sh = a.q.stride_h;
@@ -438,7 +439,7 @@ extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descal
   p.lse_sb = a.lse_stride_b; p.lse_sh = a.lse_stride_h;
   p.B = a.B; p.Sq = a.Sq; p.Sk = a.Sk; p.Hq = a.Hq; p.Hkv = a.Hkv;
   p.G = a.Hq / a.Hkv;
-  p.nq = 0; p.n_items = 0;                         // set in launch_fwd_fp8
+  p.nq = 0; p.n_items = 0;                         // set in launch_fwd_fp8 / launch_fwd_mxfp8
   p.causal_off = mask.causal_off;
   p.scale = a.softmax_scale;
   p.scale_log2 = a.softmax_scale * kLog2e;
@@ -448,7 +449,34 @@ extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descal
   p.seq_q = nullptr; p.seq_k = nullptr; p.sched = nullptr;
   p.interleave = (a.flags & USP_LAUNCH_INTERLEAVE) ? 1 : 0;
   p.walk_g = p.G;                                  // a KV group's heads side by side in the item walk
-  const int rc = launch_fwd_fp8(p, q_descale, k_descale, v_descale, out_dtype, mask.causal, (hipStream_t)stream);
+  *causal = mask.causal;
+  return USP_OK;
+}
+
+extern "C" int usp_flash_fwd_fp8(const usp_fwd_args* args, const float* q_descale, const float* k_descale, const float* v_descale,
+                                 int32_t out_dtype, void* stream) {
+  using namespace usp;
+  launch_kinds_reset();
+  FwdParams p;
+  bool causal = false;
+  if (int rc = e4m3_params(args, out_dtype, aligned(q_descale, 4) && aligned(k_descale, 4) && aligned(v_descale, 4), &p, &causal)) return rc;
+  const int rc = launch_fwd_fp8(p, q_descale, k_descale, v_descale, out_dtype, causal, (hipStream_t)stream);
   if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_FP8);
+  return rc;
+}
+
+// The scale tensors hold one byte per element, strides in bytes: a q / k row's four bytes and a lane's v bytes are read where they
+// lie, so pointer and strides are multiples of 4 (else USP_EUNSUPPORTED); all three are required (USP_EINVAL).
+extern "C" int usp_flash_fwd_mxfp8(const usp_fwd_args* args, const usp_tensor* q_scale, const usp_tensor* k_scale, const usp_tensor* v_scale,
+                                   int32_t out_dtype, void* stream) {
+  using namespace usp;
+  launch_kinds_reset();
+  FwdParams p;
+  bool causal = false;
+  const bool given = q_scale && k_scale && v_scale && q_scale->ptr && k_scale->ptr && v_scale->ptr;
+  if (int rc = e4m3_params(args, out_dtype, given, &p, &causal)) return rc;
+  if (!tensor_aligned(*q_scale, 4, 4) || !tensor_aligned(*k_scale, 4, 4) || !tensor_aligned(*v_scale, 4, 4)) return USP_EUNSUPPORTED;
+  const int rc = launch_fwd_mxfp8(p, *q_scale, *k_scale, *v_scale, out_dtype, causal, (hipStream_t)stream);
+  if (rc == USP_OK) launch_kinds_note(USP_KIND_FWD_MXFP8);
   return rc;
 }

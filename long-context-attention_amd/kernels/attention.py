@@ -544,12 +544,16 @@ def block_mask_recall(mass, mask):
     return (mass * mask.to(mass.dtype)).sum(dim=-1)
 
 
-def quantize_fp8(x):
+def quantize_fp8(x, mx=None):
     """Per-head e4m3 operands for hip_attn_forward: a bf16 / fp16 (B, S, H, D) device tensor (any strides) -> (x8, descale), x8
     torch.float8_e4m3fn of x's shape, descale fp32 (B, H) = max |x[b, :, h, :]| / 448 (1 for an all-zero head); x8 * descale is x to
     e4m3 rounding (round to nearest even; the largest element of a head becomes +-448).  Two launches (csrc/usp_quantize_fp8.hip),
-    deterministic, nothing read on the host; no gradient."""
-    return _C.quantize_fp8(x.detach())
+    deterministic, nothing read on the host; no gradient.
+    `mx`: MXFP8 operands instead (OCP Microscaling v1.0; csrc/usp_quantize_mxfp8.hip, one launch) -> (x8, scale), scale in
+    torch.float8_e8m0fnu, one power of two per block of 32 elements: mx="d" for q and k (blocks along the head dim: scale (B, S, H,
+    D / 32)), mx="s" for v (blocks along the sequence: scale (B, ceil(S / 32), H, D)).  The scale is 2^(floor(log2(amax)) - 8), x8 =
+    e4m3(x / scale) saturating at +-448 (the format's rule); an all-zero block gets 1."""
+    return _C.quantize_fp8(x.detach(), mx=mx)
 
 
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
@@ -596,7 +600,10 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     q, k, v all in torch.float8_e4m3fn at head dim 128 run on the e4m3 forward (csrc/usp_flash_fwd_fp8.hip; kernels/features.py:
     fp8_alone), with none of the options; forward only.  `q_descale` (B, Hq), `k_descale` / `v_descale` (B, Hkv) (keyword only): fp32
     device tensors, the operands mean q8 * q_descale[b, h] etc. (quantize_fp8 makes both), None = 1; `out_dtype` (keyword only):
-    torch.bfloat16 | torch.float16, the type of block_out.  The numbers: include/usp_hip.h, USP_ATTN_FP8."""
+    torch.bfloat16 | torch.float16, the type of block_out.  The numbers: include/usp_hip.h, USP_ATTN_FP8.
+    Descales in torch.float8_e8m0fnu are MXFP8 block scales (quantize_fp8(x, mx=) makes them): q_descale (B, Sq, Hq, 4) and k_descale
+    (B, Sk, Hkv, 4) along the head dim, v_descale (B, ceil(Sk / 32), Hkv, 128) along the sequence, all three, unit last stride; the
+    call runs on the MX forward (csrc/usp_flash_fwd_mxfp8.hip; include/usp_hip.h, USP_ATTN_MXFP8), the scales applied in the MFMAs."""
     if fp8_alone(q, k, v, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask, block_select,
                  return_max_logits, return_block_mass, q_descale, k_descale, v_descale):
         B, Sq, Hq, D = q.shape

@@ -202,13 +202,43 @@ def head_dims_192_128_alone(D: int, Dv: int, window_size=None, softcap=None, ali
 
 
 FP8_DTYPE = torch.float8_e4m3fn                  # OCP E4M3: the one 8-bit type the kernels take
-_FP8_OTHERS = tuple(getattr(torch, n) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz") if hasattr(torch, n))
+_FP8_OTHERS = tuple(getattr(torch, n) for n in ("float8_e4m3fnuz", "float8_e5m2", "float8_e5m2fnuz", "float8_e8m0fnu") if hasattr(torch, n))
 FP8_HEAD_DIM = 128
+MX_SCALE_DTYPE = torch.float8_e8m0fnu             # OCP MX block scales: one power-of-two byte per 32 elements
+MX_BLOCK = 32
 
 
 def is_fp8(*tensors) -> bool:
     """Is any of the tensors (None allowed) of an 8-bit float type?"""
     return any(t is not None and t.dtype in (FP8_DTYPE,) + _FP8_OTHERS for t in tensors)
+
+
+def mx_scales(q_descale, k_descale, v_descale) -> bool:
+    """Are the descales of an e4m3 call MX block scales (csrc/usp_flash_fwd_mxfp8.hip)?  All three or none: fp8_alone has judged that."""
+    return q_descale is not None and q_descale.dtype == MX_SCALE_DTYPE
+
+
+def _mx_scales_alone(q, k, v, descales):
+    """The MX form of the descales, from shapes, dtypes, devices and strides alone: all three in float8_e8m0fnu, q's and k's one byte per
+    (token, head, 32-dim block), v's one per (32-key block, head, dim); last stride 1.  Mixed forms are refused by name."""
+    mx = [name for name, t in descales if t is not None and t.dtype == MX_SCALE_DTYPE]
+    if not mx:
+        return
+    for name, t in descales:
+        if t is None or t.dtype != MX_SCALE_DTYPE:
+            raise NotImplementedError(f"{name} is {'None' if t is None else t.dtype} beside {mx[0]} in torch.float8_e8m0fnu: MX block scales "
+                                      f"go with all three of q_descale, k_descale and v_descale in torch.float8_e8m0fnu")
+    B, Sq, Hq, D = q.shape
+    Sk, Hkv = k.shape[1], k.shape[2]
+    want = {"q_descale": (B, Sq, Hq, D // MX_BLOCK), "k_descale": (B, Sk, Hkv, D // MX_BLOCK),
+            "v_descale": (B, (Sk + MX_BLOCK - 1) // MX_BLOCK, Hkv, D)}
+    for name, t in descales:
+        if tuple(t.shape) != want[name]:
+            raise ValueError(f"{name} is {tuple(t.shape)}: the MX block scales of these operands are {want[name]}")
+        if t.stride(-1) != 1:
+            raise ValueError(f"{name} has a last stride of {t.stride(-1)}: MX block scales take a unit last stride")
+        if t.device != q.device:
+            raise ValueError(f"{name} is on {t.device}, the operands on {q.device}")
 
 
 def fp8_forward_only(name: str, *tensors):
@@ -224,7 +254,8 @@ def fp8_alone(q, k, v, window_size=None, softcap=None, alibi_slopes=None, dropou
     """Does a forward call run on the e4m3 family (csrc/usp_flash_fwd_fp8.hip)?  True when q, k and v are all torch.float8_e4m3fn.
     That family is the plain dense forward at head dim 128 -- causal or full, GQA, the fused merge -- and nothing else: judged HERE
     like head_dim_256_alone, before any tensor is read, it goes with none of the options and no other head dim (nothing is
-    padded).  Mixed dtypes, the other 8-bit types, and descales beside 16-bit tensors are refused by name."""
+    padded).  Mixed dtypes, the other 8-bit types, and descales beside 16-bit tensors are refused by name.  Descales in
+    torch.float8_e8m0fnu are MX block scales (mx_scales: csrc/usp_flash_fwd_mxfp8.hip, the same rules): all three, of the block shapes."""
     dts = {"q": q.dtype, "k": k.dtype, "v": v.dtype}
     for name, dt in dts.items():
         if dt in _FP8_OTHERS:
@@ -248,6 +279,7 @@ def fp8_alone(q, k, v, window_size=None, softcap=None, alibi_slopes=None, dropou
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"float8_e4m3fn q, k, v together with {name} are not supported by the HIP attention kernels")
+    _mx_scales_alone(q, k, v, (("q_descale", q_descale), ("k_descale", k_descale), ("v_descale", v_descale)))
     return True
 
 

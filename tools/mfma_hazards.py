@@ -156,6 +156,9 @@ def check_stream(ins, out=print, where=""):
             continue
         d, a, b = regs(ops[0]), regs(ops[1]), regs(ops[2])
         c = regs(ops[3]) if len(ops) > 3 else set()
+        if op.startswith("v_mfma_scale"):                    # ... d, a, b, c, scale_a, scale_b op_sel:[..]: the scale registers are sources too
+            for t in ops[4:6]:
+                c = c | regs(t.split(" ")[0])
         # A / C: producers one or two instructions in front, along every way into this MFMA
         front = [(p, 1) for p in preds[i]]
         seen = set()
