@@ -242,6 +242,34 @@ enum {
  * exact power of two: the result is defined bit for bit.  One launch on `stream`, no atomics, no scratch.  NaN inputs are not looked
  * for.  USP_EINVAL: a NULL pointer, a size <= 0, a bad dtype, an axis other than the two; USP_EUNSUPPORTED: D no multiple of 32. */
 #define USP_ATTN_MXFP8 4194304
+/* ---- Gathered keys ----
+ * USP_ATTN_KEY_INDEX: a FEATURE bit (ABI still v7; the value is free as a flag and means nothing in an argument block):
+ * usp_flash_fwd_gather (declared below) exists.  A sparse pattern at TOKEN granularity -- vertical-and-slash heads, sink + local
+ * heads, token-level top-k: every row sees a local band below its diagonal plus a short per-(batch, query head) list of individual keys.
+ *   semantics key_index holds n_index >= 1 int32 entries per (batch, query head): the list of (b, h) starts at key_index +
+ *             b * index_stride_b + h * index_stride_h (strides in entries, >= 0; 0 shares a list), entries contiguous.  Row i has the
+ *             diagonal position d_i = i + Sk - Sq.  It sees key j iff j <= d_i and at least one of
+ *               - USP_ATTN_WINDOW is set and d_i - j <= window_left (the band; window_left < 0: no left bound);
+ *               - j is an entry of the list of (b, h).
+ *             A key that is both listed and in the band counts ONCE.  A row that sees nothing gives out = 0, lse = -inf.  Without
+ *             USP_ATTN_WINDOW there is no band: the row sees its listed keys up to the diagonal and nothing else.
+ *   the list  entries of one (b, h) are non-decreasing; an entry outside [0, Sk) is ABSENT (lists of different lengths share one
+ *             n_index: pad with Sk or more); entries are distinct, the result for a repeated one is unspecified.  Whatever the
+ *             memory holds, no access leaves the tensors: every entry is range-checked as it is read, an absent one fetches zeros
+ *             through the buffer descriptor's byte count, which is the (batch, kv head) plane's true extent.  An unsorted list is
+ *             safe and its result unspecified.  The list is never read on the host.
+ *   kernel    csrc/usp_flash_fwd_gather.hip (noted as USP_KIND_FWD_GATHER): a work item is a (batch, head, 128-row tile), 4 waves x 32
+ *             rows, late row tiles first; it walks the list in tiles of 64 entries whose K / V rows LDS-DMA gathers with a per-lane
+ *             offset, up to the first tile that starts beyond the item's last diagonal position, then the contiguous 64-key tiles of
+ *             the band; one online softmax across both.
+ *   served    causal calls of head dim 64 or 128, bf16 and fp16, GQA, Sq != Sk (bottom-right aligned), ragged sizes,
+ *             USP_LAUNCH_INTERLEAVE, any strides of q, k, v, out under the alignment rules of usp_flash_fwd.  Served uncut: k_splits
+ *             and the workspace are ignored.  out is 16-bit, lse fp32; acc is not written.
+ *   declined  nothing launched or written.  USP_EINVAL: a NULL list, n_index < 1, a list pointer off a 4-byte boundary, a negative
+ *             list stride.  USP_EUNSUPPORTED: causal == 0, a head dim other than 64 / 128, window_right != 0 under USP_ATTN_WINDOW,
+ *             USP_ATTN_SOFTCAP, USP_ATTN_SHIFT, USP_FORCE_ROW64 / USP_FORCE_WAVE32, a packed batch (seq_q / seq_k), merge_in, an acc
+ *             tensor or a final range that leaves rows to one, a (batch, kv head) plane of k or v of 2^31 bytes or more. */
+#define USP_ATTN_KEY_INDEX 8388608
 #define USP_MX_AXIS_D 0
 #define USP_MX_AXIS_S 1
 #define USP_QUANT_FP8_ROWS 64
@@ -351,6 +379,9 @@ int usp_flash_fwd_mxfp8(const usp_fwd_args* args, const usp_tensor* q_scale, con
                         int32_t out_dtype, void* stream);
 int usp_quantize_mxfp8(int32_t dtype, int32_t axis, const usp_tensor* x, int64_t x_stride_d, const usp_tensor* x8, int64_t x8_stride_d,
                        const usp_tensor* scale, int32_t B, int32_t S, int32_t H, int32_t D, void* stream);
+/* USP_ATTN_KEY_INDEX (see the bit) */
+int usp_flash_fwd_gather(const usp_fwd_args* args, const int32_t* key_index, int64_t index_stride_b,
+                         int64_t index_stride_h, int32_t n_index, void* stream);
 
 /* K split (dense launches): a launch with few (batch, head, 256-row tile) work items cannot fill 256 CUs, and a causal
  * one lasts as long as its heaviest item (measured on MI355X, B1 S16384 D128 causal: 2 heads 548 TFLOP/s, 4 heads 891,
@@ -947,7 +978,8 @@ enum {
   /* ... and the two launches of the antidiagonal gate, which note themselves as a flash call does (their entry points reset the mask) */
   USP_KIND_BLOCK_ANTIDIAG = 262144,       /* block_antidiag_kernel       (usp_block_antidiag_weights: 4 waves x 32 sub-rows) */
   USP_KIND_BLOCK_SELECT_WEIGHTS = 524288, /* block_select_weights_kernel (usp_block_select_weights) */
-  USP_KIND_FWD_MXFP8 = 1048576  /* flash_fwd_mxfp8_kernel      (MXFP8 q, k, v at head dim 128: 4 waves x 64 rows) */
+  USP_KIND_FWD_MXFP8 = 1048576, /* flash_fwd_mxfp8_kernel      (MXFP8 q, k, v at head dim 128: 4 waves x 64 rows) */
+  USP_KIND_FWD_GATHER = 2097152 /* flash_fwd_gather_kernel     (key_index: 4 waves x 32 rows, gathered 64-key tiles) */
 };
 int usp_last_launch_kinds(void);
 
@@ -970,6 +1002,7 @@ int usp_abi_version(void);
  * USP_ATTN_FP8 is the thirteenth: usp_flash_fwd_fp8 and usp_quantize_fp8 exist.
  * USP_ATTN_BLOCK_SELECT_ANTIDIAG is the fourteenth: usp_block_antidiag_weights and usp_block_select_weights exist.
  * USP_ATTN_MXFP8 is the fifteenth: usp_flash_fwd_mxfp8 and usp_quantize_mxfp8 exist.
+ * USP_ATTN_KEY_INDEX is the sixteenth: usp_flash_fwd_gather exists.
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -46,6 +46,8 @@ USP_ATTN_FP8 = 1048576         # feature bit of usp_attn_features(): usp_flash_f
 USP_ATTN_BLOCK_SELECT_ANTIDIAG = 2097152  # feature bit of usp_attn_features(): usp_block_antidiag_weights / usp_block_select_weights exist (not an args flag)
 ANTIDIAG_STRIDES = (4, 8, 16)  # the `stride` values of usp_block_antidiag_weights
 USP_ATTN_MXFP8 = 4194304       # feature bit of usp_attn_features(): usp_flash_fwd_mxfp8 / usp_quantize_mxfp8 exist (not an args flag)
+USP_ATTN_KEY_INDEX = 8388608   # feature bit of usp_attn_features(): usp_flash_fwd_gather exists (not an args flag)
+KEY_INDEX_HEAD_DIMS = (64, 128)  # the head dims it serves (the rule: kernels/features.py: key_index_alone)
 MX_AXIS = {"d": 0, "s": 1}     # usp_quantize_mxfp8's block axis (include/usp_hip.h: USP_MX_AXIS_D / USP_MX_AXIS_S)
 QUANT_FP8_ROWS = 64            # rows of one partial maximum of usp_quantize_fp8 (include/usp_hip.h: USP_QUANT_FP8_ROWS)
 HEAD_DIMS_QK_V = (192, 128)    # the one pair of unequal head dims (q and k, v) they serve (the rule: kernels/features.py)
@@ -66,6 +68,8 @@ KINDS_FP8 = {131072: "fwd_fp8"}
 KINDS_ANTIDIAG = {262144: "block_antidiag", 524288: "block_select_weights"}
 # ... and the MXFP8 forward's (csrc/usp_flash_fwd_mxfp8.hip)
 KINDS_MXFP8 = {1048576: "fwd_mxfp8"}
+# ... and the gathered-key forward's (csrc/usp_flash_fwd_gather.hip)
+KINDS_GATHER = {2097152: "fwd_gather"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -104,7 +108,8 @@ def last_dkdv_item_keys() -> int:
 def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
-    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items(), *KINDS_ANTIDIAG.items(), *KINDS_MXFP8.items())
+    return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items(), *KINDS_ANTIDIAG.items(), *KINDS_MXFP8.items(),
+                                   *KINDS_GATHER.items())
                  if m & bit)
 
 
@@ -159,7 +164,7 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
            "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim",
            "usp_flash_fwd_fp8", "usp_quantize_fp8", "usp_block_antidiag_weights", "usp_block_select_weights",
-           "usp_flash_fwd_mxfp8", "usp_quantize_mxfp8")
+           "usp_flash_fwd_mxfp8", "usp_quantize_mxfp8", "usp_flash_fwd_gather")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -177,6 +182,7 @@ VDIM_EXPORTS = ("usp_flash_fwd_vdim", "usp_flash_bwd_vdim")
 FP8_EXPORTS = ("usp_flash_fwd_fp8", "usp_quantize_fp8")
 ANTIDIAG_EXPORTS = ("usp_block_antidiag_weights", "usp_block_select_weights")
 MXFP8_EXPORTS = ("usp_flash_fwd_mxfp8", "usp_quantize_mxfp8")
+GATHER_EXPORTS = ("usp_flash_fwd_gather",)
 
 
 def lib_path() -> str:
@@ -195,7 +201,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS + MXFP8_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS + MXFP8_EXPORTS + GATHER_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -809,7 +815,8 @@ def _feature_entries():
                                     [fwd, ctypes.POINTER(UspTensor), ctypes.POINTER(UspTensor), ctypes.POINTER(UspTensor), i32, vp]),
             "usp_quantize_mxfp8": (USP_ATTN_MXFP8, "quantize_fp8(mx=) (USP_ATTN_MXFP8)",
                                    [i32, i32, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor),
-                                    i32, i32, i32, i32, vp])}
+                                    i32, i32, i32, i32, vp]),
+            "usp_flash_fwd_gather": (USP_ATTN_KEY_INDEX, "key_index (USP_ATTN_KEY_INDEX)", [fwd, vp, i64, i64, i32, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -968,7 +975,7 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
               merge_in: bool = False, final_begin: int = 0, final_end: Optional[int] = None,
               interleave: bool = False, k_splits: Optional[int] = None, window=None, family=None, softcap=None, shift=None,
               alibi=None, dropout=None, sinks=None, doc=None, span=None, bsp=None, bsp_lists=None, row_max=None,
-              q_descale=None, k_descale=None, v_descale=None, out_dtype=None):
+              q_descale=None, k_descale=None, v_descale=None, out_dtype=None, *, key_index=None):
     """usp_flash_fwd (include/usp_hip.h).  q (B,Sq,Hq,D); k,v (B,Sk,Hkv,D); lse (B,Hq,Sq) fp32;
     out 16-bit / acc fp32 (B,Sq,Hq,D).  A v of head dim 128 beside q and k of head dim 192 (HEAD_DIMS_QK_V) goes to usp_flash_fwd_vdim,
     with out / acc of v's head dim: the plain dense launch, every option below refused here or declined by the library.  All may be strided views (unit dim stride).  `k_splits`: cut the keys of
@@ -1001,8 +1008,23 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     with `shift` alone of the options; `q_descale` (B, Hq), `k_descale` / `v_descale` (B, Hkv): fp32 device tensors, None = 1;
     `out_dtype`: the type of `out` (None: out's own, bfloat16 without one); k_splits is ignored.  Descales in torch.float8_e8m0fnu are
     MX block scales -- (B, Sq, Hq, 4), (B, Sk, Hkv, 4), (B, ceil(Sk / 32), Hkv, 128), unit last stride, all three -- and the call
-    goes to usp_flash_fwd_mxfp8 (kernels/features.py: mx_scales)."""
-    from .kernels.features import fp8_alone
+    goes to usp_flash_fwd_mxfp8 (kernels/features.py: mx_scales).
+    `key_index` (keyword only): an int32 device tensor (n,), (Hq, n) or (B, Hq, n) with unit last stride (key_index_value), None =
+    off: a causal launch in which row i sees the keys of `window` = (left, 0) below its diagonal plus the listed keys of its
+    (batch, head) up to the diagonal, each once (usp_flash_fwd_gather; include/usp_hip.h: USP_ATTN_KEY_INDEX).  Head dims 64 / 128;
+    goes with `window` and `interleave` alone; served uncut, k_splits ignored; out only (no acc, no merge_in)."""
+    from .kernels.features import fp8_alone, key_index_alone
+    if key_index is not None:                       # judged before any tensor is read; the other families refuse it in their own words
+        fp8_alone(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale, key_index=key_index)
+        _vdim_alone(head_dim_v_of(q, v), key_index=key_index)
+    if key_index_alone(key_index, q.shape[-1], causal, window, softcap, alibi, (dropout_args(dropout) or (None,))[0], sinks, doc, span,
+                       bsp, None, row_max is not None, False):
+        for name, value in (("shift", shift), ("family", family), ("acc", acc), ("merge_in", merge_in or None)):
+            if value is not None:
+                raise NotImplementedError(f"key_index together with {name} is not supported by the HIP attention kernels")
+        _require_cuda(q, k, v, lse, out, key_index)
+        _flash_fwd_gather(q, k, v, softmax_scale, lse, out, interleave, _window(window), key_index)
+        return
     if fp8_alone(q, k, v, q_descale=q_descale, k_descale=k_descale, v_descale=v_descale):   # judged before any tensor is read
         _fp8_alone(window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), sinks=sinks,
                    doc=doc, span=span, bsp=bsp, row_max=row_max, family=family)
@@ -1056,6 +1078,45 @@ def flash_fwd(q, k, v, softmax_scale: float, causal: bool, lse, out=None, acc=No
     dr = dropout_args(dropout)
     sk = sinks_value(sinks, Hq, q.device, q.dtype)
     _flash_call("fwd", a, al, dr, sk, dc, sp, mx)
+
+
+def key_index_value(key_index, B: int, Hq: int, device):
+    """A `key_index` argument -> (tensor, batch stride, head stride, n) as usp_flash_fwd_gather takes it, from shape, dtype, device and
+    strides alone: int32, (n,), (Hq, n) or (B, Hq, n) with n >= 1 and a unit last stride; a missing dimension is shared (stride 0)."""
+    if not isinstance(key_index, torch.Tensor) or key_index.dtype != torch.int32:
+        raise ValueError("key_index must be an int32 torch.Tensor")
+    shape = tuple(key_index.shape)
+    if key_index.dim() not in (1, 2, 3) or shape[:-1] != (B, Hq)[3 - key_index.dim():] or shape[-1] < 1:
+        raise ValueError(f"key_index must have shape (n,), ({Hq}, n) or ({B}, {Hq}, n) with n >= 1: one sorted list of keys per "
+                         f"(batch, query head), got {shape}")
+    if key_index.stride(-1) != 1:
+        raise ValueError(f"key_index has a last stride of {key_index.stride(-1)}: the entries of a list are contiguous")
+    if any(s < 0 for s in key_index.stride()):
+        raise ValueError("key_index must have non-negative strides")
+    if key_index.device != torch.device(device):
+        raise ValueError(f"key_index is on {key_index.device}, the operands on {device}")
+    sb = key_index.stride(0) if key_index.dim() == 3 else 0
+    sh = key_index.stride(-2) if key_index.dim() >= 2 else 0
+    return key_index, sb, sh, shape[-1]
+
+
+def _flash_fwd_gather(q, k, v, softmax_scale, lse, out, interleave, window, key_index):
+    """usp_flash_fwd_gather: the argument block of a causal dense launch plus the list (rules: kernels/features.py: key_index_alone)."""
+    B, Sq, Hq, D = q.shape
+    idx, sb, sh, n = key_index_value(key_index, B, Hq, q.device)
+    a = UspFwdArgs()
+    a.dtype = dtype_code(q.dtype)
+    a.B, a.Sq, a.Sk, a.Hq, a.Hkv, a.D = B, Sq, k.shape[1], Hq, k.shape[2], D
+    a.causal = 1
+    a.softmax_scale = float(softmax_scale)
+    a.q, a.k, a.v, a.out = _t4(q), _t4(k), _t4(v), _t4(out)
+    a.lse, a.lse_stride_b, a.lse_stride_h = _lse3(lse)
+    a.final_begin, a.final_end = 0, Sq
+    a.flags = USP_LAUNCH_INTERLEAVE if interleave else 0
+    if window is not None:
+        a.flags |= USP_ATTN_WINDOW
+        a.window_left, a.window_right = window
+    _check(_feature_entry("usp_flash_fwd_gather")(ctypes.byref(a), _ptr(idx), sb, sh, n, _stream()), "usp_flash_fwd_gather")
 
 
 def _fp8_alone(**options):

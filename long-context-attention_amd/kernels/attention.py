@@ -17,7 +17,8 @@ import torch
 
 from .. import _C
 from .features import (BLOCK_MASK_SIZE, BlockSelect, BlockSelectAntidiag, BlockSelectTopP, Features, block_select_antidiag_value, block_mask_alone, block_mask_self_attention,  # noqa: F401
-                       block_select_alone, expand_block_mask, fp8_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone, max_logits_alone,
+                       block_select_alone, expand_block_mask, fp8_alone, fp8_forward_only, head_dim_256_alone, head_dims_192_128_alone, key_index_alone,
+                       max_logits_alone,
                        return_block_mass_alone)
 
 
@@ -559,7 +560,7 @@ def quantize_fp8(x, mx=None):
 def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                      softcap=None, alibi_slopes=None, return_softmax=False, *, rng_state=None, sinks=None, cu_doclens=None,
                      bidirectional=None, block_mask=None, return_max_logits=False, block_select=None, return_block_mass=False,
-                     q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16):
+                     q_descale=None, k_descale=None, v_descale=None, out_dtype=torch.bfloat16, key_index=None):
     """`fwd-only` contract of the reference selector (kernels/__init__.py:63-65; call sites
     zigzag_ring_flash_attn.py:29-43, ring_flash_attn.py:36-48):
         (block_out (B,Sq,Hq,D) q.dtype, block_lse (B,Hq,Sq) fp32)
@@ -603,9 +604,17 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     torch.bfloat16 | torch.float16, the type of block_out.  The numbers: include/usp_hip.h, USP_ATTN_FP8.
     Descales in torch.float8_e8m0fnu are MXFP8 block scales (quantize_fp8(x, mx=) makes them): q_descale (B, Sq, Hq, 4) and k_descale
     (B, Sk, Hkv, 4) along the head dim, v_descale (B, ceil(Sk / 32), Hkv, 128) along the sequence, all three, unit last stride; the
-    call runs on the MX forward (csrc/usp_flash_fwd_mxfp8.hip; include/usp_hip.h, USP_ATTN_MXFP8), the scales applied in the MFMAs."""
+    call runs on the MX forward (csrc/usp_flash_fwd_mxfp8.hip; include/usp_hip.h, USP_ATTN_MXFP8), the scales applied in the MFMAs.
+    `key_index` (keyword only): an int32 DEVICE tensor (n,), (Hq, n) or (B, Hq, n), unit last stride: per (batch, query head) a
+    sorted list of individual keys.  Row i (diagonal position d_i = i + Sk - Sq) sees key j iff j <= d_i and j is in the band of
+    window_size = (left, 0) (d_i - j <= left) or in the list; a key that is both counts once; without a window the row sees its
+    listed keys alone, and a row that sees nothing gives out = 0, lse = -inf.  Entries are non-decreasing and distinct; an entry
+    outside [0, Sk) is absent (pad shorter lists with Sk).  The list is never read on the host (it may come from a kernel on the same
+    stream) and gets no gradient.  Runs on the gathered-key forward (csrc/usp_flash_fwd_gather.hip; include/usp_hip.h,
+    USP_ATTN_KEY_INDEX): causal=True, head dims 64 / 128, with window_size = (left, 0) and none of the other options
+    (kernels/features.py: key_index_alone); forward only.  None: exactly the call without it."""
     if fp8_alone(q, k, v, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask, block_select,
-                 return_max_logits, return_block_mass, q_descale, k_descale, v_descale):
+                 return_max_logits, return_block_mass, q_descale, k_descale, v_descale, key_index=key_index):
         B, Sq, Hq, D = q.shape
         out = torch.empty((B, Sq, Hq, D), dtype=out_dtype, device=q.device)
         lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
@@ -613,14 +622,23 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
                      v_descale=v_descale, out_dtype=out_dtype)
         return out, lse
     if head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
-                               block_mask, block_select, return_max_logits, return_block_mass):
+                               block_mask, block_select, return_max_logits, return_block_mass, key_index=key_index):
         B, Sq, Hq, _ = q.shape
         out = torch.empty((B, Sq, Hq, v.shape[-1]), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
         get_block_backend().fwd(q, k, v, _default_scale(q, softmax_scale), bool(causal), lse, out=out)
         return out, lse
     head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
-                       block_select, return_max_logits, return_block_mass)
+                       block_select, return_max_logits, return_block_mass, key_index=key_index)
+    if key_index_alone(key_index, q.shape[-1], causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                       block_mask, block_select, return_max_logits, return_block_mass):
+        B, Sq, Hq, D = q.shape
+        _C.key_index_value(key_index, B, Hq, q.device)           # shape, dtype, device, strides: before any tensor is read
+        _C._require_cuda(q, k, v, key_index)
+        out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        _C.flash_fwd(q, k, v, _default_scale(q, softmax_scale), True, lse, out=out, window=window_of(window_size), key_index=key_index)
+        return out, lse
     if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                block_mask, block_select, return_max_logits):
         block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")

@@ -159,7 +159,7 @@ def return_block_mass_alone(return_block_mass, window_size=None, softcap=None, a
 
 def head_dim_256_alone(D: int, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
                         bidirectional=None, block_mask=None, block_select=None, return_max_logits=False, return_block_mass=False,
-                        packed=False) -> bool:
+                        packed=False, key_index=None) -> bool:
     """Does a call of head dim `D` run at kernel head dim 256 (128 < D <= 256)?  That family (csrc/usp_flash_fwd_d256.hip,
     csrc/usp_flash_bwd_d256.hip) is the plain dense call -- causal or full, GQA, the rings' fused merge -- and nothing else: judged
     HERE like block_mask, before any tensor is read, it goes with none of the options, nor with a packed (variable-length) batch
@@ -169,7 +169,8 @@ def head_dim_256_alone(D: int, window_size=None, softcap=None, alibi_slopes=None
     given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
              ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional),
              ("block_mask", block_mask), ("block_select", block_select), ("return_max_logits", return_max_logits or None),
-             ("return_block_mass", return_block_mass or None), ("a packed (variable-length) batch", packed or None))
+             ("return_block_mass", return_block_mass or None), ("a packed (variable-length) batch", packed or None),
+             ("key_index", key_index))
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"head_dim {D} (kernel head dim 256) together with {name} is not supported by the HIP "
@@ -179,7 +180,7 @@ def head_dim_256_alone(D: int, window_size=None, softcap=None, alibi_slopes=None
 
 def head_dims_192_128_alone(D: int, Dv: int, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
                             cu_doclens=None, bidirectional=None, block_mask=None, block_select=None, return_max_logits=False,
-                            return_block_mass=False, packed=False) -> bool:
+                            return_block_mass=False, packed=False, key_index=None) -> bool:
     """Does a call with q and k of head dim `D` and v of head dim `Dv` run on the (192, 128) family (csrc/usp_flash_fwd_qk192.hip,
     csrc/usp_flash_bwd_qk192.hip)?  False for equal head dims.  That family is the plain dense call -- causal or full, GQA, the
     rings' fused merge -- and nothing else: judged HERE like head_dim_256_alone, before any tensor is read, it goes with none of
@@ -193,7 +194,8 @@ def head_dims_192_128_alone(D: int, Dv: int, window_size=None, softcap=None, ali
     given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
              ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional),
              ("block_mask", block_mask), ("block_select", block_select), ("return_max_logits", return_max_logits or None),
-             ("return_block_mass", return_block_mass or None), ("a packed (variable-length) batch", packed or None))
+             ("return_block_mass", return_block_mass or None), ("a packed (variable-length) batch", packed or None),
+             ("key_index", key_index))
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"head dims {HEAD_DIMS_QK_V} of q / k and v together with {name} are not supported by the HIP "
@@ -250,7 +252,7 @@ def fp8_forward_only(name: str, *tensors):
 
 def fp8_alone(q, k, v, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None, cu_doclens=None,
               bidirectional=None, block_mask=None, block_select=None, return_max_logits=False, return_block_mass=False,
-              q_descale=None, k_descale=None, v_descale=None) -> bool:
+              q_descale=None, k_descale=None, v_descale=None, key_index=None) -> bool:
     """Does a forward call run on the e4m3 family (csrc/usp_flash_fwd_fp8.hip)?  True when q, k and v are all torch.float8_e4m3fn.
     That family is the plain dense forward at head dim 128 -- causal or full, GQA, the fused merge -- and nothing else: judged HERE
     like head_dim_256_alone, before any tensor is read, it goes with none of the options and no other head dim (nothing is
@@ -275,11 +277,41 @@ def fp8_alone(q, k, v, window_size=None, softcap=None, alibi_slopes=None, dropou
     given = (("window_size", _window(window_size)), ("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes),
              ("dropout_p", dropout_value(dropout_p)), ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional),
              ("block_mask", block_mask), ("block_select", block_select), ("return_max_logits", return_max_logits or None),
-             ("return_block_mass", return_block_mass or None))
+             ("return_block_mass", return_block_mass or None), ("key_index", key_index))
     for name, value in given:
         if value is not None:
             raise NotImplementedError(f"float8_e4m3fn q, k, v together with {name} are not supported by the HIP attention kernels")
     _mx_scales_alone(q, k, v, (("q_descale", q_descale), ("k_descale", k_descale), ("v_descale", v_descale)))
+    return True
+
+
+KEY_INDEX_HEAD_DIMS = (64, 128)
+
+
+def key_index_alone(key_index, D: int, causal=True, window_size=None, softcap=None, alibi_slopes=None, dropout_p=None, sinks=None,
+                    cu_doclens=None, bidirectional=None, block_mask=None, block_select=None, return_max_logits=False,
+                    return_block_mass=False) -> bool:
+    """Is `key_index` on (csrc/usp_flash_fwd_gather.hip; the semantics: include/usp_hip.h, USP_ATTN_KEY_INDEX)?  Like block_mask it is
+    no field of the record: it is judged HERE, before Features.of and before any tensor is read.  It goes with window_size =
+    (left, 0) -- the band below the diagonal -- and nothing else: the gathered-key kernel holds no other mask and no score-level
+    step.  Causal calls of head dim 64 or 128 only (nothing is padded).  None is exactly the call without the keyword."""
+    if key_index is None:
+        return False
+    win = _window(window_size)
+    given = (("softcap", softcap_value(softcap)), ("alibi_slopes", alibi_slopes), ("dropout_p", dropout_value(dropout_p)),
+             ("sinks", sinks), ("cu_doclens", cu_doclens), ("bidirectional", bidirectional), ("block_mask", block_mask),
+             ("block_select", block_select), ("return_max_logits", return_max_logits or None),
+             ("return_block_mass", return_block_mass or None),
+             ("a window_size whose right bound is not 0", None if win is None or win[1] == 0 else win))
+    for name, value in given:
+        if value is not None:
+            raise NotImplementedError(f"key_index together with {name} is not supported by the HIP attention kernels")
+    if not causal:
+        raise NotImplementedError("key_index together with causal=False is not supported by the HIP attention kernels: a row sees "
+                                  "its listed keys up to the diagonal")
+    if D not in KEY_INDEX_HEAD_DIMS:
+        raise NotImplementedError(f"head_dim {D} together with key_index is not supported by the HIP attention kernels: the "
+                                  f"gathered-key forward serves head dims {KEY_INDEX_HEAD_DIMS} alone")
     return True
 
 
