@@ -270,6 +270,36 @@ enum {
  *             USP_ATTN_SOFTCAP, USP_ATTN_SHIFT, USP_FORCE_ROW64 / USP_FORCE_WAVE32, a packed batch (seq_q / seq_k), merge_in, an acc
  *             tensor or a final range that leaves rows to one, a (batch, kv head) plane of k or v of 2^31 bytes or more. */
 #define USP_ATTN_KEY_INDEX 8388608
+/* USP_ATTN_KEY_INDEX_BWD: a FEATURE bit (ABI still v7, argument blocks unchanged): usp_flash_bwd_gather and
+ * usp_flash_bwd_gather_workspace_bytes (declared below) exist -- dQ, dK and dV of usp_flash_fwd_gather under the same mask, word for word.
+ *   semantics lse is the lse the forward returned, delta = rowsum(dout * out) from usp_bwd_delta.  p_ij = exp(scale s_ij - lse_i) on
+ *             visible pairs, 0 elsewhere; dV_j = sum_i p_ij dO_i; dS_ij = p_ij (dO_i . v_j - delta_i); dQ_i = scale sum_j dS_ij k_j;
+ *             dK_j = scale sum_i dS_ij q_i.  A row with lse = -inf contributes nothing and gets a zero dq row (no NaN); a key no row
+ *             sees gets exactly zero dk / dv rows: EVERY row of dq, dk and dv is written.  The list gets no gradient, is never read on
+ *             the host, and no list content causes an access outside the operands or the workspace: entries are range-checked as
+ *             they are read, search positions lie in [0, n_index); an unsorted or repeating list gives wrong numbers only.
+ *   the work  the BAND (USP_ATTN_WINDOW: max(0, d_i - window_left) <= j <= d_i) is usp_flash_bwd itself on this lse and delta --
+ *             uncut, fp32 results, its launches noted under their own kinds -- and runs FIRST.  The LISTED part (entry e < d_i -
+ *             window_left; without a window e <= d_i) is csrc/usp_flash_bwd_gather.hip: a row-stationary dQ launch
+ *             (USP_KIND_DQ_GATHER), a key-stationary dK/dV launch per QUERY head that writes fp32 partials per list entry
+ *             (USP_KIND_DKDV_GATHER), and a scatter launch (notes nothing) that finishes every row of dk / dv.
+ *   sum order deterministic, no atomics, independent of the grid and of USP_LAUNCH_INTERLEAVE.  dq row = (accum ? dq : 0) + band, then
+ *             + the listed share (its list tiles in ascending order).  A list entry's partial = rows 0-31 of every streamed 64-row
+ *             tile in ascending order, plus rows 32-63 likewise.  dk / dv row j = (accum ? dk : 0) + band, then + the partials of the
+ *             KV group's query heads that list j, in ascending head order.  A 16-bit output is rounded once, at the end.
+ *   workspace args->workspace of usp_flash_bwd_gather_workspace_bytes(args, n_index) bytes, 16-byte aligned: the partials (2 x B x
+ *             Hq x ceil(n_index / 64) x 64 x D fp32) and, under USP_ATTN_WINDOW, the band's fp32 result of every gradient the caller
+ *             takes in 16 bits.  Ask with the flags and outputs of the call.
+ *   served    what usp_flash_fwd_gather serves (causal, head dim 64 / 128, bf16 / fp16, GQA, Sq != Sk, ragged sizes, any aligned
+ *             strides, USP_LAUNCH_INTERLEAVE), fp32 outputs with accum_*, 16-bit outputs, USP_BWD_SKIP_DQ / USP_BWD_SKIP_DKDV.  Uncut:
+ *             dq_splits, dkdv_splits and dkdv_heads are ignored.
+ *   declined  nothing launched or written.  USP_EINVAL: NULL args, lse or delta; a NULL list, n_index < 1, a list pointer off a
+ *             4-byte boundary, a negative list stride; both skip bits; a NULL dout, q, k or v; a gradient of a launch that runs
+ *             with neither an fp32 nor a 16-bit tensor; a workspace that is NULL, off a 16-byte boundary or too small.
+ *             USP_EUNSUPPORTED: causal == 0, a head dim other than 64 / 128, window_right != 0 under USP_ATTN_WINDOW,
+ *             USP_ATTN_SOFTCAP, USP_ATTN_SHIFT, USP_FORCE_ROW64 / USP_FORCE_WAVE32 / USP_DKDV_KEYS*, a packed batch, a 16-bit output
+ *             together with its accum flag, misaligned tensors, a (batch, head) plane of q, dout, k or v of 2^31 bytes or more. */
+#define USP_ATTN_KEY_INDEX_BWD 16777216
 #define USP_MX_AXIS_D 0
 #define USP_MX_AXIS_S 1
 #define USP_QUANT_FP8_ROWS 64
@@ -455,6 +485,10 @@ typedef struct usp_bwd_args {
 
 int usp_flash_bwd(const usp_bwd_args* args, void* stream);
 int usp_flash_bwd_vdim(const usp_bwd_args* args, int32_t head_dim_v, void* stream);   /* USP_ATTN_HEAD_DIMS_192_128 */
+/* USP_ATTN_KEY_INDEX_BWD (see the bit) */
+int64_t usp_flash_bwd_gather_workspace_bytes(const usp_bwd_args* args, int32_t n_index);
+int usp_flash_bwd_gather(const usp_bwd_args* args, const int32_t* key_index, int64_t index_stride_b,
+                         int64_t index_stride_h, int32_t n_index, void* stream);
 
 /* ----------------------------------------------------------------------------------------------
  * ALiBi: usp_flash_fwd / usp_flash_bwd with flash-attn's `alibi_slopes` (forwarded by the reference to every block call,
@@ -979,7 +1013,9 @@ enum {
   USP_KIND_BLOCK_ANTIDIAG = 262144,       /* block_antidiag_kernel       (usp_block_antidiag_weights: 4 waves x 32 sub-rows) */
   USP_KIND_BLOCK_SELECT_WEIGHTS = 524288, /* block_select_weights_kernel (usp_block_select_weights) */
   USP_KIND_FWD_MXFP8 = 1048576, /* flash_fwd_mxfp8_kernel      (MXFP8 q, k, v at head dim 128: 4 waves x 64 rows) */
-  USP_KIND_FWD_GATHER = 2097152 /* flash_fwd_gather_kernel     (key_index: 4 waves x 32 rows, gathered 64-key tiles) */
+  USP_KIND_FWD_GATHER = 2097152,/* flash_fwd_gather_kernel     (key_index: 4 waves x 32 rows, gathered 64-key tiles) */
+  USP_KIND_DQ_GATHER = 4194304, /* flash_bwd_gather_dq_kernel  (key_index backward: 4 waves x 32 rows, gathered 64-key tiles) */
+  USP_KIND_DKDV_GATHER = 8388608 /* flash_bwd_gather_dkdv_kernel (key_index backward: one 64-entry list tile per item; the scatter behind it notes nothing) */
 };
 int usp_last_launch_kinds(void);
 
@@ -1003,6 +1039,7 @@ int usp_abi_version(void);
  * USP_ATTN_BLOCK_SELECT_ANTIDIAG is the fourteenth: usp_block_antidiag_weights and usp_block_select_weights exist.
  * USP_ATTN_MXFP8 is the fifteenth: usp_flash_fwd_mxfp8 and usp_quantize_mxfp8 exist.
  * USP_ATTN_KEY_INDEX is the sixteenth: usp_flash_fwd_gather exists.
+ * USP_ATTN_KEY_INDEX_BWD is the seventeenth: usp_flash_bwd_gather and usp_flash_bwd_gather_workspace_bytes exist.
  * Unknown flag bits are not rejected by usp_flash_fwd / usp_flash_bwd, so a binding checks here before it relies on a bit added after ABI v7's first release. */
 int usp_attn_features(void);
 const char* usp_strerror(int code);

@@ -47,6 +47,7 @@ USP_ATTN_BLOCK_SELECT_ANTIDIAG = 2097152  # feature bit of usp_attn_features(): 
 ANTIDIAG_STRIDES = (4, 8, 16)  # the `stride` values of usp_block_antidiag_weights
 USP_ATTN_MXFP8 = 4194304       # feature bit of usp_attn_features(): usp_flash_fwd_mxfp8 / usp_quantize_mxfp8 exist (not an args flag)
 USP_ATTN_KEY_INDEX = 8388608   # feature bit of usp_attn_features(): usp_flash_fwd_gather exists (not an args flag)
+USP_ATTN_KEY_INDEX_BWD = 16777216  # feature bit of usp_attn_features(): usp_flash_bwd_gather exists (not an args flag)
 KEY_INDEX_HEAD_DIMS = (64, 128)  # the head dims it serves (the rule: kernels/features.py: key_index_alone)
 MX_AXIS = {"d": 0, "s": 1}     # usp_quantize_mxfp8's block axis (include/usp_hip.h: USP_MX_AXIS_D / USP_MX_AXIS_S)
 QUANT_FP8_ROWS = 64            # rows of one partial maximum of usp_quantize_fp8 (include/usp_hip.h: USP_QUANT_FP8_ROWS)
@@ -70,6 +71,8 @@ KINDS_ANTIDIAG = {262144: "block_antidiag", 524288: "block_select_weights"}
 KINDS_MXFP8 = {1048576: "fwd_mxfp8"}
 # ... and the gathered-key forward's (csrc/usp_flash_fwd_gather.hip)
 KINDS_GATHER = {2097152: "fwd_gather"}
+# ... and the gathered-key backward's (csrc/usp_flash_bwd_gather.hip; its scatter launch notes nothing)
+KINDS_GATHER_BWD = {4194304: "dq_gather", 8388608: "dkdv_gather"}
 _FAMILY_FLAG = {None: 0, "auto": 0, "row64": USP_FORCE_ROW64, "wave32": USP_FORCE_WAVE32}
 # In-process default of the `family` argument of flash_fwd / flash_bwd (tests, A/B runs: bench.py times both families
 # on the same box).  "auto": the library decides per launch.
@@ -109,7 +112,7 @@ def last_launch_kinds() -> tuple:
     """Names of the kernels the calling thread's last flash_fwd / flash_bwd launched (usp_last_launch_kinds)."""
     m = load().usp_last_launch_kinds()
     return tuple(name for bit, name in (*KINDS.items(), *KINDS_D256.items(), *KINDS_QK192.items(), *KINDS_FP8.items(), *KINDS_ANTIDIAG.items(), *KINDS_MXFP8.items(),
-                                   *KINDS_GATHER.items())
+                                   *KINDS_GATHER.items(), *KINDS_GATHER_BWD.items())
                  if m & bit)
 
 
@@ -164,7 +167,8 @@ EXPORTS = ("usp_flash_fwd", "usp_flash_fwd_workspace_bytes", "usp_flash_bwd", "u
            "usp_flash_fwd_maxlogit", "usp_row_max_reduce", "usp_block_means", "usp_block_select",
            "usp_block_select_top_p", "usp_block_attn_mass", "usp_flash_fwd_vdim", "usp_flash_bwd_vdim",
            "usp_flash_fwd_fp8", "usp_quantize_fp8", "usp_block_antidiag_weights", "usp_block_select_weights",
-           "usp_flash_fwd_mxfp8", "usp_quantize_mxfp8", "usp_flash_fwd_gather")
+           "usp_flash_fwd_mxfp8", "usp_quantize_mxfp8", "usp_flash_fwd_gather",
+           "usp_flash_bwd_gather_workspace_bytes", "usp_flash_bwd_gather")
 # The entry points of ALiBi, dropout, the sinks, the document mask and the spans are the only exports load() does not insist on: they are
 # looked up and prototyped on first use (_feature_entry), behind their feature bit, so a library built before them still loads
 # and serves everything else.
@@ -183,6 +187,7 @@ FP8_EXPORTS = ("usp_flash_fwd_fp8", "usp_quantize_fp8")
 ANTIDIAG_EXPORTS = ("usp_block_antidiag_weights", "usp_block_select_weights")
 MXFP8_EXPORTS = ("usp_flash_fwd_mxfp8", "usp_quantize_mxfp8")
 GATHER_EXPORTS = ("usp_flash_fwd_gather",)
+GATHER_BWD_EXPORTS = ("usp_flash_bwd_gather_workspace_bytes", "usp_flash_bwd_gather")
 
 
 def lib_path() -> str:
@@ -201,7 +206,7 @@ def load():
             f"`make -C long-context-attention_amd/csrc`. There is no CPU fallback.")
     L = ctypes.CDLL(_LIB_PATH)
     for name in EXPORTS:
-        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS + MXFP8_EXPORTS + GATHER_EXPORTS and not hasattr(L, name):
+        if name not in ALIBI_EXPORTS + DROPOUT_EXPORTS + SINK_EXPORTS + DOC_EXPORTS + SPAN_EXPORTS + BSP_EXPORTS + MAXL_EXPORTS + SELECT_EXPORTS + SELECT_TOP_P_EXPORTS + MASS_EXPORTS + VDIM_EXPORTS + FP8_EXPORTS + MXFP8_EXPORTS + GATHER_EXPORTS + GATHER_BWD_EXPORTS and not hasattr(L, name):
             raise RuntimeError(f"{_LIB_PATH} does not export {name} (stale build?)")
     L.usp_strerror.restype = ctypes.c_char_p
     L.usp_abi_version.restype = ctypes.c_int
@@ -816,7 +821,9 @@ def _feature_entries():
             "usp_quantize_mxfp8": (USP_ATTN_MXFP8, "quantize_fp8(mx=) (USP_ATTN_MXFP8)",
                                    [i32, i32, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor), i64, ctypes.POINTER(UspTensor),
                                     i32, i32, i32, i32, vp]),
-            "usp_flash_fwd_gather": (USP_ATTN_KEY_INDEX, "key_index (USP_ATTN_KEY_INDEX)", [fwd, vp, i64, i64, i32, vp])}
+            "usp_flash_fwd_gather": (USP_ATTN_KEY_INDEX, "key_index (USP_ATTN_KEY_INDEX)", [fwd, vp, i64, i64, i32, vp]),
+            "usp_flash_bwd_gather_workspace_bytes": (USP_ATTN_KEY_INDEX_BWD, "key_index in the backward (USP_ATTN_KEY_INDEX_BWD)", [bwd, i32]),
+            "usp_flash_bwd_gather": (USP_ATTN_KEY_INDEX_BWD, "key_index in the backward (USP_ATTN_KEY_INDEX_BWD)", [bwd, vp, i64, i64, i32, vp])}
 
 
 _FEATURE_ENTRIES = _feature_entries()
@@ -832,7 +839,7 @@ def _feature_entry(name: str):
     fn = getattr(L, name)
     if fn.argtypes is None:
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int64 if name == "usp_block_list_bytes" else ctypes.c_int
+        fn.restype = ctypes.c_int64 if name in ("usp_block_list_bytes", "usp_flash_bwd_gather_workspace_bytes") else ctypes.c_int
     return fn
 
 
@@ -1389,7 +1396,7 @@ def sink_grad(sinks, lse, delta, out=None, accum: bool = False):
 def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causal: bool,
               accum_dq=False, accum_dk=False, accum_dv=False, dq16=None, dk16=None, dv16=None,
               interleave: bool = False, splits=None, window=None, family=None, only=None, dkdv_heads: int = 0,
-              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None, bsp_lists=None, dkdv_keys: int = 0):
+              softcap=None, shift=None, alibi=None, dropout=None, doc=None, span=None, bsp=None, bsp_lists=None, dkdv_keys: int = 0, *, key_index=None, key_index_ws=None):
     """usp_flash_bwd (usp_flash_bwd_vdim for a v, dout and dv of head dim 128 beside q and k of 192: the plain dense launch, every
     option below refused or declined by the library).  dq/dk/dv are fp32 (B,S,H,D) views, written or accumulated; a 16-bit
     dq16/dk16/dv16 receives the FINAL rounded result instead (the fp32 tensor may then be None
@@ -1402,7 +1409,23 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     `delta` is that of the dropped `out`.  `dkdv_keys`: 128 | 256 pins the item width of the 64-row dK/dV kernel (USP_DKDV_KEYS128 /
     USP_DKDV_KEYS256; 0: the library picks; last_dkdv_item_keys() tells which ran).  `doc`: as flash_fwd (usp_flash_bwd_doc): the dQ launch reads row_lo, the dK/dV launch
     key_hi; with `only` the other one may be None.  `span`: as flash_fwd (usp_flash_bwd_span): the dQ launch reads (row_lo,
-    row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None.  `bsp`: as flash_fwd (usp_flash_bwd_bsp)."""
+    row_hi), the dK/dV launch (key_lo, key_hi); with `only` the other pair may be None.  `bsp`: as flash_fwd (usp_flash_bwd_bsp).
+    `key_index` (keyword only): as flash_fwd took it, None = off: dq, dk, dv of that forward under the same mask, `lse` the lse it
+    returned (usp_flash_bwd_gather; include/usp_hip.h: USP_ATTN_KEY_INDEX_BWD).  Goes with `window` = (left, 0), `interleave`, `only`,
+    the accum flags of fp32 outputs and 16-bit outputs alone; served uncut, `splits` ignored.  `key_index_ws`: its workspace, a 16-byte
+    aligned torch.uint8 device tensor of usp_flash_bwd_gather_workspace_bytes bytes or more (None: allocated here)."""
+    if key_index is not None:                            # judged before any tensor is read, in the forward's words
+        from .kernels.features import fp8_alone, key_index_alone
+        fp8_alone(q, k, v, key_index=key_index)
+        _vdim_alone(head_dim_v_of(q, v), key_index=key_index)
+        key_index_alone(key_index, q.shape[-1], causal, window, softcap, alibi, (dropout_args(dropout) or (None,))[0], None, doc, span, bsp)
+        for name, value in (("shift", shift), ("family", family), ("dkdv_keys", dkdv_keys or None), ("dkdv_heads", dkdv_heads or None)):
+            if value is not None:
+                raise NotImplementedError(f"key_index together with {name} is not supported by the HIP attention kernels")
+        _require_cuda(dout, q, k, v, lse, delta, dq, dk, dv, dq16, dk16, dv16, key_index)
+        _flash_bwd_gather(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, accum_dq, accum_dk, accum_dv, dq16, dk16, dv16,
+                          interleave, _window(window), only, key_index, key_index_ws)
+        return
     Dv = head_dim_v_of(q, v)                             # judged before any tensor is read
     _vdim_alone(Dv, window=_window(window), softcap=softcap_value(softcap), alibi=alibi, dropout=dropout_args(dropout), doc=doc, span=span,
                 bsp=bsp)
@@ -1461,6 +1484,38 @@ def flash_bwd(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale: float, causa
     al = alibi_value(alibi, B, Hq, q.device)
     dr = dropout_args(dropout)
     _flash_call("bwd", a, al, dr, None, dc, sp)
+
+
+def _flash_bwd_gather(dout, q, k, v, lse, delta, dq, dk, dv, softmax_scale, accum_dq, accum_dk, accum_dv, dq16, dk16, dv16, interleave,
+                      window, only, key_index, ws=None):
+    """usp_flash_bwd_gather: the argument block of a causal dense backward plus the list and the workspace it asks for."""
+    B, Sq, Hq, D = q.shape
+    idx, sb, sh, n = key_index_value(key_index, B, Hq, q.device)
+    a = UspBwdArgs()
+    a.dtype = dtype_code(q.dtype)
+    a.B, a.Sq, a.Sk, a.Hq, a.Hkv, a.D = B, Sq, k.shape[1], Hq, k.shape[2], D
+    a.causal = 1
+    a.softmax_scale = float(softmax_scale)
+    a.dout, a.q, a.k, a.v = _t4(dout), _t4(q), _t4(k), _t4(v)
+    a.lse, a.lse_stride_b, a.lse_stride_h = _lse3(lse)
+    a.delta, a.delta_stride_b, a.delta_stride_h = _lse3(delta)
+    for t in (dq, dk, dv):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("dq/dk/dv buffers of usp_flash_bwd_gather are fp32")
+    a.dq, a.dk, a.dv = _t4(dq), _t4(dk), _t4(dv)
+    a.dq16, a.dk16, a.dv16 = _t4(dq16), _t4(dk16), _t4(dv16)
+    a.accum_dq, a.accum_dk, a.accum_dv = int(bool(accum_dq)), int(bool(accum_dk)), int(bool(accum_dv))
+    a.flags = (USP_LAUNCH_INTERLEAVE if interleave else 0) | {None: 0, "dkdv": USP_BWD_SKIP_DQ, "dq": USP_BWD_SKIP_DKDV}[only]
+    if window is not None:
+        a.flags |= USP_ATTN_WINDOW
+        a.window_left, a.window_right = window
+    need = _feature_entry("usp_flash_bwd_gather_workspace_bytes")(ctypes.byref(a), n)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)    # caching allocator; stream-ordered
+    elif ws.dtype != torch.uint8 or ws.device != q.device or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() % 16:
+        raise ValueError(f"key_index_ws must be a contiguous 16-byte aligned torch.uint8 tensor of at least {need} bytes on {q.device}")
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    _check(_feature_entry("usp_flash_bwd_gather")(ctypes.byref(a), _ptr(idx), sb, sh, n, _stream()), "usp_flash_bwd_gather")
 
 
 def lse_merge(acc, lse, blk_out, blk_lse, first: bool):

@@ -612,7 +612,7 @@ def hip_attn_forward(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, w
     outside [0, Sk) is absent (pad shorter lists with Sk).  The list is never read on the host (it may come from a kernel on the same
     stream) and gets no gradient.  Runs on the gathered-key forward (csrc/usp_flash_fwd_gather.hip; include/usp_hip.h,
     USP_ATTN_KEY_INDEX): causal=True, head dims 64 / 128, with window_size = (left, 0) and none of the other options
-    (kernels/features.py: key_index_alone); forward only.  None: exactly the call without it."""
+    (kernels/features.py: key_index_alone); hip_attn_backward and hip_attn_func take the same keyword.  None: exactly the call without it."""
     if fp8_alone(q, k, v, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask, block_select,
                  return_max_logits, return_block_mass, q_descale, k_descale, v_descale, key_index=key_index):
         B, Sq, Hq, D = q.shape
@@ -691,19 +691,45 @@ def hip_attn_backward(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk
                       block_dv_buffer, dropout_p=0.0, softmax_scale=None, bwd_causal=False,
                       window_size=(-1, -1), softcap=None, alibi_slopes=None, deterministic=False,
                       rng_state=None, *args, sinks=None, dsinks=None, cu_doclens=None, bidirectional=None, block_mask=None,
-                      **kwargs):
+                      key_index=None, **kwargs):
     """`bwd-only` contract (argument order of kernels/attention.py:205-206): writes dq/dk/dv into
     the caller's (possibly sliced, 16-bit) buffers; `out`/`softmax_lse` are the GLOBAL rows' values
     (zigzag_ring_flash_attn.py:115-137).  `dropout_p` > 0: `rng_state` as hip_attn_forward took it; `out` is the dropped one.
     `sinks` (keyword only) with `dsinks`, a contiguous fp32 (Hq,) buffer: `softmax_lse` is the sink-including one, dq / dk / dv
     come from the unchanged kernels, and dsinks[h] = -sum exp(sinks[h] - lse) * delta is written (usp_sink_bwd).
     `cu_doclens`, `bidirectional`, `block_mask` (keyword only): as hip_attn_forward took them.
+    `key_index` (keyword only): as hip_attn_forward took it, under the same rules (kernels/features.py: key_index_alone): the
+    gathered-key backward (csrc/usp_flash_bwd_gather.hip; include/usp_hip.h, USP_ATTN_KEY_INDEX_BWD) -- the band of window_size through
+    the windowed causal backward on this lse, the listed keys through the gathered dQ, dK/dV and scatter launches; every row of the
+    three buffers is written, deterministically.  The list gets no gradient.  None: exactly the call without it.
     Head dims (192, 128): dout, out and block_dv_buffer have v's head dim (kernels/features.py: head_dims_192_128_alone)."""
     fp8_forward_only("hip_attn_backward", dout, q, k, v)
     qk192 = head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens,
-                                    bidirectional, block_mask)
+                                    bidirectional, block_mask, key_index=key_index)
     if not qk192:
-        head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask)
+        head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
+                           key_index=key_index)
+    if key_index_alone(key_index, q.shape[-1], bwd_causal, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                       block_mask):
+        B, Sq, Hq, D = q.shape
+        _C.key_index_value(key_index, B, Hq, q.device)           # shape, dtype, device, strides: before any tensor is read
+        _C._require_cuda(dout, q, k, v, out, softmax_lse, block_dq_buffer, block_dk_buffer, block_dv_buffer, key_index)
+        delta = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        _C.bwd_delta(dout, out, delta)
+        lse = softmax_lse if softmax_lse.dtype == torch.float32 else softmax_lse.float()
+        if lse.stride(-1) != 1:
+            lse = lse.contiguous()
+        bufs = (block_dq_buffer, block_dk_buffer, block_dv_buffer)
+        tgt = [t if t.stride(3) == 1 and all(st % 4 == 0 for st in t.stride()[:3]) else torch.empty(t.shape, dtype=t.dtype, device=q.device)
+               for t in bufs]
+        wide = [t.dtype == torch.float32 for t in tgt]            # an fp32 buffer is written as it stands, a 16-bit one rounded once
+        _C.flash_bwd(dout, q, k, v, lse, delta, *(t if w else None for t, w in zip(tgt, wide)), _default_scale(q, softmax_scale), True,
+                     dq16=None if wide[0] else tgt[0], dk16=None if wide[1] else tgt[1], dv16=None if wide[2] else tgt[2],
+                     window=window_of(window_size), key_index=key_index)
+        for t, dst in zip(tgt, bufs):
+            if t is not dst:
+                dst.copy_(t)
+        return
     bsp_kw = {}
     if block_mask_alone(block_mask, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional):
         bsp_kw = dict(bsp=block_mask_of(block_mask, q, k))
@@ -748,7 +774,7 @@ class _HipAttnFunc(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, k, v, softmax_scale, causal, return_lse, window_size=(-1, -1), softcap=None, alibi_slopes=None,
-                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None, block_mask=None, return_max_logits=False):
+                dropout_p=0.0, dropout_head0=0, sinks=None, cu_doclens=None, block_mask=None, return_max_logits=False, key_index=None):
         scale = _default_scale(q, softmax_scale)
         q, k, v = kernel_operand(q), kernel_operand(k), kernel_operand(v)
         # dropout: one seed per call, drawn here, kept for the backward (draw_seed); the block is the whole sequence
@@ -756,7 +782,9 @@ class _HipAttnFunc(torch.autograd.Function):
         ctx.rng_state = (draw_seed(), 0, 0, int(dropout_head0)) if ctx.dropout_p else None
         out, lse, *ml = hip_attn_forward(q, k, v, dropout_p=ctx.dropout_p, softmax_scale=scale, causal=causal, window_size=window_size,
                                          softcap=softcap, alibi_slopes=alibi_slopes, rng_state=ctx.rng_state, sinks=sinks,
-                                         cu_doclens=cu_doclens, block_mask=block_mask, return_max_logits=return_max_logits)
+                                         cu_doclens=cu_doclens, block_mask=block_mask, return_max_logits=return_max_logits,
+                                         key_index=key_index)
+        ctx.key_index = key_index                  # (no gradient; a device tensor the backward hands on unread)
         ctx.cu_doclens = cu_doclens
         ctx.block_mask = block_mask                # (no gradient; the backward rebuilds its lists from it, on the device)
         ctx.has_sinks = sinks is not None          # (never beside slopes: the one optional saved tensor is either)
@@ -777,16 +805,16 @@ class _HipAttnFunc(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         hip_attn_backward(kernel_operand(dout), q, k, v, out, lse, dq, dk, dv, ctx.dropout_p, ctx.scale, ctx.causal,
                           ctx.window_size, ctx.softcap, slopes[0] if slopes else None, rng_state=ctx.rng_state, sinks=sinks,
-                          dsinks=dsinks, cu_doclens=ctx.cu_doclens, block_mask=ctx.block_mask)
+                          dsinks=dsinks, cu_doclens=ctx.cu_doclens, block_mask=ctx.block_mask, key_index=ctx.key_index)
         if dsinks is not None:
             dsinks = dsinks.to(sinks.dtype) if ctx.needs_input_grad[11] else None
-        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None, None, dsinks, None, None, None, None
 
 
 def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                   softcap=0.0, alibi_slopes=None, deterministic=False, return_attn_probs=False,
                   *args, dropout_head0=0, sinks=None, cu_doclens=None, bidirectional=None, block_mask=None, return_max_logits=False,
-                  block_select=None, return_block_mass=False, **kwargs):
+                  block_select=None, return_block_mass=False, key_index=None, **kwargs):
     """`fwd-bwd` contract (flash_attn_func's signature): `out`, or `(out, softmax_lse, None)` with
     return_attn_probs (the probabilities themselves are never materialised, with dropout either: the third element stays
     None).  `softcap` > 0: flash-attn's tanh logit cap; None / 0 = off, a negative, NaN or infinite value raises ValueError.
@@ -813,14 +841,24 @@ def hip_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wind
     gradients are bit for bit those of the call without it.  Goes with none of the other options.
     Head dims 129 ... 256 (kernel head dim 256) go with none of the options (kernels/features.py: head_dim_256_alone).
     Head dims (192, 128) -- q and k of 192, v of 128 -- neither (kernels/features.py: head_dims_192_128_alone): out is
-    (B,Sq,Hq,128), the default scale 192 ** -0.5, dv has v's shape."""
+    (B,Sq,Hq,128), the default scale 192 ** -0.5, dv has v's shape.
+    `key_index` (keyword only): the gathered-key pattern of hip_attn_forward under its rules (causal=True, head dims 64 / 128,
+    window_size = (left, 0) and nothing else): forward and backward run on the gathered-key kernels; the list is kept on the autograd
+    node, is never read on the host and gets no gradient."""
     fp8_forward_only("hip_attn_func", q, k, v)
     if head_dims_192_128_alone(q.shape[-1], v.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
-                               block_mask, block_select, return_max_logits, return_block_mass):
+                               block_mask, block_select, return_max_logits, return_block_mass, key_index=key_index):
         res = _HipAttnFunc.apply(q, k, v, softmax_scale, causal, bool(return_attn_probs))
         return (res[0], res[1], None) if return_attn_probs else res
     head_dim_256_alone(q.shape[-1], window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional, block_mask,
-                       block_select, return_max_logits, return_block_mass)
+                       block_select, return_max_logits, return_block_mass, key_index=key_index)
+    if key_index_alone(key_index, q.shape[-1], causal, window_size, softcap or None, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
+                       block_mask, block_select, return_max_logits, return_block_mass):
+        _C.key_index_value(key_index, q.shape[0], q.shape[2], q.device)
+        _C._require_cuda(q, k, v, key_index)
+        res = _HipAttnFunc.apply(q, k, v, softmax_scale, True, bool(return_attn_probs), window_size, None, None, 0.0, 0, None, None, None,
+                                 False, key_index)
+        return (res[0], res[1], None) if return_attn_probs else res
     if return_block_mass_alone(return_block_mass, window_size, softcap, alibi_slopes, dropout_p, sinks, cu_doclens, bidirectional,
                                block_mask, block_select, return_max_logits):
         block_mask_self_attention(q.shape[1], k.shape[1], "return_block_mass")
